@@ -2,14 +2,17 @@
 """bench.py — BASELINE.json's metric on MI355X: frames/s embedded (OpenCLIP ViT-B/32, bs=256 per GPU)
 and, in the `search` object of the same JSON line, queries/s over a 10M x 512 flat IP index.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One process per GPU.  A "step" of the headline metric is one wise_vit_forward over a 256-frame batch
 already resident in HBM (weak scaling: every rank embeds its own batch, no collective on the data
-path).  A search step is one nq=1, k=10 scan of the index, whose 10M rows are sharded over the ranks
-(strong scaling; RCCL all-gather of the per-shard top-k, then the merge kernel).
+path).  A plain run does only that: set-up, W warm-up steps, K timed steps, the outputs of the last timed step
+under --dump-outputs, the result line.  --full adds everything else the line can carry: the same steps one batch
+at a time, the roofline pass, the `search` object (a search step is one nq=1, k=10 scan of the index, whose 10M
+rows are sharded over the ranks: strong scaling; RCCL all-gather of the per-shard top-k, then the merge kernel),
+the other models (`extra`) and the CPU baselines.
 Rank 0 prints ONE JSON line.
 """
 from __future__ import annotations
@@ -43,18 +46,43 @@ def parse():
     ap.add_argument("--index-rows", type=int, default=10_000_000)
     ap.add_argument("--dim", type=int, default=512)
     ap.add_argument("--topk", type=int, default=10)
-    ap.add_argument("--no-search", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the CLAP-HTSAT and ViT-L/14 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the one-batch-at-a-time and roofline passes, the search legs, the other "
+                         "models and the CPU baselines (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the [batch,512] fp32 embeddings) as DIR/<name>.npy")
+    ap.add_argument("--no-search", action="store_true", help="with --full: skip the search legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the CLAP-HTSAT and ViT-L/14 legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget per CPU baseline leg")
     ap.add_argument("--pmc-legs", action="store_true",
-                    help="profiling aid for the PMC passes: only the headline shapes run (ViT-B/32 bs=256; 10M x 512 search at "
-                         "nq=1, k=10 and nq=256, k=10; the fp32 scan), so that a per-kernel average of FETCH_SIZE / WRITE_SIZE is "
-                         "the traffic of THOSE launches and not a mean over shard-sized and split launches too")
+                    help="profiling aid for the PMC passes, with --full: only the headline shapes run (ViT-B/32 bs=256; 10M x "
+                         "512 search at nq=1, k=10 and nq=256, k=10; the fp32 scan), so that a per-kernel average of FETCH_SIZE "
+                         "/ WRITE_SIZE is the traffic of THOSE launches and not a mean over shard-sized and split launches too")
     ap.add_argument("--roofline-only", action="store_true",
                     help="profiling aid: run only the single-stream, event-bracketed ViT pass (the one `roofline` is "
                          "computed from) so that a rocprofv3 --stats of this command lists exactly those launches")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of all ranks together
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: each array as float32 DIR/<name>.npy (DIR/<name>_rank<r>.npy with several ranks).  Rows beyond a
+    rank's share of DUMP_LIMIT_BYTES are left out by a fixed, seeded sample (sorted row indices, the same every run)."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // (world * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > budget:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), budget // (a.nbytes // len(a)), replace=False))
+            a = a[keep]
+        np.save(d / (f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"), np.ascontiguousarray(a))
 
 
 def timed_region(fn, steps, world):
@@ -106,6 +134,34 @@ def traffic_fields(kernel_key):
     return {"traffic": load_pmc_traffic(kernel_key),
             "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of the profile "
                               "sequence committed with this round, corrected per MI355X_MICROARCH.md; not measured in this run)"}
+
+
+def vit_roofline(lib, spec, eng, one_stream_step, steps, frames_per_s, world):
+    """--full / --roofline-only: the `roofline` object of the ViT-B/32 leg from a pass of `steps` single-stream forwards
+    with HIP-event brackets around every GEMM launch."""
+    n_gemm_per_fwd = 4 * (4 * spec.layers + 2)  # capacity (split launches, patch embed, projection)
+    for i in range(2):
+        one_stream_step(i)
+    prof = prof_pass(lib, one_stream_step, steps, steps * n_gemm_per_fwd + 8)
+    g_ms, g_n, g_flop = prof[0]
+    gemm_tflops = (g_flop / g_n) / (g_ms / g_n * 1e-3) / 1e12 if g_n else 0.0
+    return {
+        "kernel": "bf16 MFMA GEMM family (gemm_w4p_kernel persistent 160x256 for QKV / fc1 with the row scale of the folded "
+                  "LayerNorm in the epilogue, gemm_w4_kernel 160x256 for the two residual GEMMs — which also emit bf16(x) and "
+                  "the rows' statistics — and 224x192 for the patch embedding: one wave per SIMD, MFMA 16x16x32; "
+                  "gemm_ring_kernel for the projection): every GEMM launch of the forward, HIP events on the launch "
+                  "stream, single-stream pass",
+        "bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+        "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
+        "avg_launch_us": round(g_ms / max(g_n, 1) * 1e3, 2), "launches": int(g_n),
+        "flop_per_launch_avg": g_flop / max(g_n, 1),
+        **traffic_fields("gemm_bf16_kernel"),
+        "end_to_end_tflops": round(frames_per_s / world * spec.flops_per_frame() / 1e12, 2),
+        "end_to_end_frac": round(frames_per_s / world * spec.flops_per_frame() / 1e12 / PEAK_BF16_TFLOPS, 4),
+        "note": ("with layernorm_fold the family's launches also carry the blocks' LayerNorm work (row statistics, the hi + lo "
+                 "split of the residual stream) and the 24 LayerNorm launches per forward are gone: `frac` is not comparable with "
+                 "the unfolded tower's (0.34-0.365 in round 3) — `end_to_end_frac` is (0.336 -> 0.353)") if eng.spec.ln_fold else "",
+    }
 
 
 def cpu_baseline_vit(spec, sd, seconds):
@@ -275,8 +331,11 @@ def main():
     frames_per_s = world * args.batch * args.steps / dt
     if "h" in out_holder:
         out_holder["o"] = out_holder["h"].result()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out_holder["o"]}, rank, world)
     serial_dt = None
-    if not args.roofline_only:   # the same K steps one batch at a time (wise_vit_forward: two half batches on two streams)
+    # --full: the same K steps one batch at a time (wise_vit_forward: two half batches on two streams)
+    if args.full and not args.roofline_only:
         for i in range(2):
             vit_step_serial(i)
         serial_dt = timed_region(vit_step_serial, args.steps, world)
@@ -286,29 +345,9 @@ def main():
     # Roofline pass: the same K steps again with HIP-event brackets around every GEMM launch.  The timed
     # region above overlaps two half-batches on two streams, which stretches every launch's wall time, so this
     # pass runs the forward on ONE stream: launch durations are then per-kernel and comparable with rocprofv3.
-    n_gemm_per_fwd = 4 * (4 * spec.layers + 2)  # capacity (split launches, patch embed, projection)
-    for i in range(2):
-        vit_step_one_stream(i)
-    prof = prof_pass(lib, vit_step_one_stream, args.steps, args.steps * n_gemm_per_fwd + 8)
-    g_ms, g_n, g_flop = prof[0]
-    gemm_tflops = (g_flop / g_n) / (g_ms / g_n * 1e-3) / 1e12 if g_n else 0.0
-    roofline = {
-        "kernel": "bf16 MFMA GEMM family (gemm_w4p_kernel persistent 160x256 for QKV / fc1 with the row scale of the folded "
-                  "LayerNorm in the epilogue, gemm_w4_kernel 160x256 for the two residual GEMMs — which also emit bf16(x) and "
-                  "the rows' statistics — and 224x192 for the patch embedding: one wave per SIMD, MFMA 16x16x32; "
-                  "gemm_ring_kernel for the projection): every GEMM launch of the forward, HIP events on the launch "
-                  "stream, single-stream pass",
-        "bound": "mfma", "achieved": round(gemm_tflops, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-        "frac": round(gemm_tflops / PEAK_BF16_TFLOPS, 4),
-        "avg_launch_us": round(g_ms / max(g_n, 1) * 1e3, 2), "launches": int(g_n),
-        "flop_per_launch_avg": g_flop / max(g_n, 1),
-        **traffic_fields("gemm_bf16_kernel"),
-        "end_to_end_tflops": round(frames_per_s / world * spec.flops_per_frame() / 1e12, 2),
-        "end_to_end_frac": round(frames_per_s / world * spec.flops_per_frame() / 1e12 / PEAK_BF16_TFLOPS, 4),
-        "note": ("with layernorm_fold the family's launches also carry the blocks' LayerNorm work (row statistics, the hi + lo "
-                 "split of the residual stream) and the 24 LayerNorm launches per forward are gone: `frac` is not comparable with "
-                 "the unfolded tower's (0.34-0.365 in round 3) — `end_to_end_frac` is (0.336 -> 0.353)") if eng.spec.ln_fold else "",
-    }
+    roofline = None
+    if args.full or args.roofline_only:
+        roofline = vit_roofline(lib, spec, eng, vit_step_one_stream, args.steps, frames_per_s, world)
 
     if args.roofline_only:
         if rank == 0:
@@ -320,7 +359,7 @@ def main():
         return
     result = {
         "metric": METRIC, "value": round(frames_per_s, 1), "unit": "frames/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+        "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(dt / args.steps * 1e3, 4),
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
         "config": {"workload": "OpenCLIP ViT-B/32 image tower (encode_image + L2 normalise), bs=256 frames per GPU, "
                                "fp32 normalised frames resident in HBM -> [256,512] fp32 unit vectors; "
@@ -331,11 +370,12 @@ def main():
                                                         if serial_dt else None),
                    "global_batch": world * args.batch, "frames_per_gpu": args.batch, "parallelism": f"dp{world}",
                    "gflop_per_frame": round(spec.flops_per_frame() / 1e9, 4), "device": dev_name},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        result["roofline"] = roofline
 
     # ------------------------------------------------------------------ HP-2: 10M x 512 flat IP, top-10
-    if not args.no_search:
+    if args.full and not args.no_search:
         N, d, k = args.index_rows, args.dim, args.topk
         lo, hi = shard_range(N, rank, world)
         n_loc = hi - lo
@@ -577,7 +617,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ other BASELINE configs (short legs)
-    if not args.no_extra and not args.pmc_legs:
+    if args.full and not args.no_extra and not args.pmc_legs:
         extra = {}
         # cfg-5: MS-CLAP HTSAT, 10-s clips @48 kHz, bs=128 per GPU (weak scaling, no collective)
         from wise_amd.feature.htsat import HtsatEngine, random_htsat_state_dict
@@ -1000,7 +1040,7 @@ def main():
         result["extra"] = extra
 
     # ------------------------------------------------------------------ CPU baselines (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_vit(spec, sd, args.cpu_seconds)
         if "search" in result:
             result["search"]["cpu_baseline"] = cpu_baseline_search(args.dim, args.topk, args.cpu_seconds)

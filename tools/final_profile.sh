@@ -9,9 +9,9 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out
 mkdir -p $OUT
 if [ "$PART" != "b" ]; then
-python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
+python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || exit 1
 echo "bench done"
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o stats -- python3 bench.py --steps 20 --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1 || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o stats -- python3 bench.py --full --steps 20 --no-cpu-baseline > $OUT/${TAG}_stats.log 2>&1 || exit 1
 python3 tools/prof_top.py $OUT/${TAG}_stats/stats_results.db 40 --csv $OUT/${TAG}_kernel_stats.csv > $OUT/${TAG}_kernel_stats.txt
 echo "stats done"
 # the single-stream bracketed pass alone: its per-kernel averages are the ones bench.py's roofline object reports
@@ -24,7 +24,7 @@ if [ "$PART" = "a" ]; then ls -la $OUT | tail -8; exit 0; fi
 # averages are those of the ViT-B/32 GEMMs and the 10M x 512 scans; the image-transform kernel from its own tool
 for C in FETCH_SIZE WRITE_SIZE; do
   L=$(echo $C | tr 'A-Z' 'a-z' | cut -d_ -f1)
-  timeout -k 10 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_$L -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --pmc-legs > $OUT/${TAG}_pmc_$L.log 2>&1 || exit 1
+  timeout -k 10 500 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_$L -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --pmc-legs > $OUT/${TAG}_pmc_$L.log 2>&1 || exit 1
   timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/${TAG}_pmc_${L}_pre -- python3 tools/preproc_bench.py 64 > $OUT/${TAG}_pmc_${L}_pre.log 2>&1 || exit 1
   cp "$(find $OUT/${TAG}_pmc_$L -name '*counter_collection.csv' | head -1)" $OUT/${TAG}_pmc_${L}_counter_collection.csv
   cp "$(find $OUT/${TAG}_pmc_${L}_pre -name '*counter_collection.csv' | head -1)" $OUT/${TAG}_pmc_${L}_pre_counter_collection.csv
