@@ -24,25 +24,265 @@
 
 namespace wise {
 
-// Tuning / ablation switches.  They exist only in the debug build (libwise_hip_debug.so, -DWISE_DEBUG_KNOBS: tools/ and
-// wise_debug_set_gemm_variant); in the product library they are compile-time constants and the branches fold away.
-#ifdef WISE_DEBUG_KNOBS
-__device__ int g_group_m = 0;        // 0 = default; tuning knob (bits 16..23 of wise_debug_set_gemm_variant)
-__device__ int g_epi_lds = 1;        // bf16 epilogue through LDS (bit 30 of the debug knob turns it off)
-__device__ int g_dephase = 0;        // tuning knob (bits 24..27): initial s_sleep units for the second block per CU
-__device__ int g_store_nt = 1;       // non-temporal stores in the bf16 epilogue of the 256-row tiles: the C tile is read by a
-                                     // later kernel, not by this one (ViT-L/14 +1.5 % end to end, ViT-B/32 unchanged)
-__device__ int g_skip_epilogue = 0;  // timing-only ablation (tools/gemm_bench.py), set via wise_debug_set_gemm_variant
-__device__ unsigned long long* g_stamp_buf = nullptr;   // in-kernel s_memtime stamps of one block (tools/gemm_stamps.py)
-__device__ int g_stamp_block = 0;
-#define WISE_STAMP(slot)                                                                              \
-    do {                                                                                              \
-        if (stamp_on) sbuf[(size_t)(kt) * 8 + (slot)] = __builtin_amdgcn_s_memtime();                 \
-    } while (0)
-#else
-constexpr int g_group_m = 0, g_epi_lds = 1, g_dephase = 0, g_store_nt = 1, g_skip_epilogue = 0;
-#define WISE_STAMP(slot) do {} while (0)
-#endif
+// ---------------------------------------------------------------------------------------------------------------------
+// The tile plan: every tile decision of the family, in host functions that launch nothing.  The entry points further
+// down (gemm_bf16, gemm_bf16_rows, gemm_resid_ln_rows, gemm_fold_*, conv3x3_bf16) ask the plan, then launch what it says;
+// tests/test_gemm_plan_cpu.py pins it shape by shape through wise_debug_gemm_plan (debug library).
+// Variant ids:  0 128x128, two blocks per CU             1 128x128 ring of 32-deep K-tiles (K % 64 != 0)
+//               2 128x128 ring of 64-deep K-tiles, one block per CU (skinny problems)      5 256x192
+//              40 / 42 / 44 ping-pong 256x256 / 320x256 / 320x128 (one block per CU)
+//              60 .. 70 the one-wave-per-SIMD kernel of gemm_w4.h: 60 256x256, 61 160x256, 62 320x256, 63 320x192,
+//                       64 160x256 persistent, 65 224x192, 66 256x192, 67 128x192, 68 128x256, 69 128x192 and
+//                       70 128x128 at two workgroups per CU
+// ---------------------------------------------------------------------------------------------------------------------
+struct GemmPlan {
+    int splitk = 0;         // K slices of the split-K pair (rows 0..127 through scratch); 0 = not a split-K case
+    int n = 1;              // launches of the tiled path: 1, or 2 when M is split between two tiles
+    int v[2] = {0, 0};      // variant of each launch, after every shape fallback
+    int rows[2] = {0, 0};   // rows of each launch, the second starting where the first ends
+};
+
+enum ConvTile { CONV_128x64 = 0, CONV_128x128 = 1, CONV_256x64 = 2, CONV_PP256 = 3 };
+
+// What variant v launches on this shape: a shape it cannot tile falls back to 0 (K % 64 != 0: to 1, the 32-deep ring;
+// the ping-pong kernels take 32-deep K-tiles themselves; an N that is no multiple of 128 only to the 128x128 kernels).
+static int resolve_variant(int v, int M, int N, int K, int mode) {
+    if (v >= 60 && v <= 70) {
+        bool ok = false;
+        switch (v) {
+            case 60: ok = w4_shape_ok(M, N, K, 8); break;
+            case 61: ok = w4_shape_ok(M, N, K, 5); break;
+            case 62: ok = bf16_out(mode) && w4_shape_ok(M, N, K, 10); break;   // (the fp32 epilogues of a 320-row tile spill)
+            case 63: ok = bf16_out(mode) && w4_shape_ok(M, N, K, 10, 6); break;
+            case 64: ok = bf16_out(mode) && w4p_shape_ok(M, N, K); break;
+            case 65: ok = w4_shape_ok(M, N, K, 7, 6); break;
+            case 66: ok = w4_shape_ok(M, N, K, 8, 6); break;
+            case 67: case 69: ok = w4_shape_ok(M, N, K, 4, 6); break;
+            case 68: ok = w4_shape_ok(M, N, K, 4, 8); break;
+            case 70: ok = w4_shape_ok(M, N, K, 4, 4); break;
+        }
+        return ok ? v : 0;
+    }
+    if (K % 64 != 0 && v != 40 && v != 42) v = 1;
+    else if (N % 128 != 0 && v != 1) v = 0;   // N edge is handled by the 128x128 kernels only
+    switch (v) {
+        case 1: case 2: return v;
+        case 5: return M % 256 == 0 && N % 192 == 0 ? 5 : 0;
+        case 40: return M % 256 == 0 && N % 256 == 0 ? 40 : 0;
+        case 42: return M % 320 == 0 && N % 256 == 0 ? 42 : 0;
+        case 44: return M % 320 == 0 && N % 128 == 0 ? 44 : 0;
+        default: return 0;
+    }
+}
+
+// shape heuristic among the two-blocks-per-CU kernels (measured with tools/gemm_bench.py on MI355X)
+static int auto_variant(int M, int N, int K) {
+    if (K % 64 != 0) return 1;  // K multiple of 32 only (HTSAT C=96): the BK=32 ring kernel
+    // Skinny problems (a text query: 77 rows against [N, K] weights; the heads of the towers): fewer blocks than CUs, each
+    // streaming its own slab of the weights from HBM over a long K — latency-bound with one K-tile in flight (12800x...
+    // shapes never come here).  The ring kernel keeps four 64-deep K-tiles in flight per block: 256x1024x4096 57 -> 19 us.
+    if ((long long)(M / 128) * ((N + 127) / 128) <= 128 && K >= 512) return 2;
+    // when a 256x192 tiling fits the chip in ONE well-filled round it beats 128x128 (fewer staged bytes, no
+    // second-round tail); otherwise the 128x128 tile at two blocks per CU wins because its epilogue overlaps
+    // the other block's main loop
+    const long long t5 = (long long)(M / 256) * (N / 192);
+    if (M % 256 == 0 && N % 192 == 0 && t5 <= 256 && t5 >= 160) return 5;
+    return 0;
+}
+
+// The one-wave-per-SIMD kernel (gemm_w4.h) takes every problem it can tile into at least ~3/4 of a round of the 256 CUs.
+// Among its tiles the model is rounds x (prologue + K-steps x cycles per step + epilogue) with the cycles its in-kernel
+// stamps show on MI355X (tools/gemm_lab.hip; the loops run at 76-79 % of the MFMA rate: 160 x 256 ~1700 cycles per
+// 64-deep step, 256 x 256 ~2560, 320 x 192 ~2430, 320 x 256 ~3250; prologue ~3200); the epilogue is bound by the HBM
+// traffic of the C tile, i.e. proportional to the tile's area whatever its shape, so it only enters through the
+// rounds.  Returns the variant id (60 .. 70) or 0.  cus: the compute units of the device (the persistent form's grid).
+static int w4_variant(int M, int N, int K, int mode, int cus) {
+    // (K >= 192: three 64-deep K-steps.  Short K used to stay with the two-blocks-per-CU kernels; on the HTSAT shapes —
+    // K = 192 / 384 at 131072 / 32768 rows — these tiles measured 5-25 % faster than those: tools/gemm_lab.hip htsat)
+    if (K < 192) return 0;
+    // Short K (HTSAT's stages: K = 192 / 384, and K = 768 on its 8192-row stage): a tile is a handful of K-steps between a
+    // prologue and an epilogue that one workgroup per CU cannot overlap with anything.  Two workgroups of 128 x 192 (or
+    // 128 x 128) per CU can: measured 7-22 % faster than the best single tile on the bf16-output shapes and 3-7 % on the
+    // residual ones at K <= 384 (profiles/r03_gemm_lab_htsat_two_per_cu.txt); at K >= 768 with many rows the small tiles
+    // are LDS-bound and lose to the large ones (ViT-B/32: same file, vit section), so the rule stops there.
+    // (K = 512, the CLIP text tower at 256 queries x 77 tokens: QKV 37.3 -> 35.0 us, out-projection 26.4 -> 21.9, fc1
+    // 62.9 -> 49.5 — `tools/gemm_lab text`.)
+    if ((K <= 512 || (K <= 768 && M <= 8192 && bf16_out(mode))) && !(bf16_out(mode) && w4p_shape_ok(M, N, K))) {
+        if (w4_shape_ok(M, N, K, 4, 6) && (long long)(M / 128) * (N / 192) >= 512) return 69;
+        if (w4_shape_ok(M, N, K, 4, 4) && (long long)(M / 128) * (N / 128) >= 512) return 70;
+    }
+    // (Measured and not taken: the same two-per-CU tiles on the output projections of the wide towers — N = K = 1024, fp32
+    // residual: 219 -> 194 us alone on ViT-L/14's shape, but no gain in the tower's step with two batches in flight.)
+    struct Cand { int id, mi, nj; double step; bool bf16_only; };
+    static const Cand cands[] = {{60, 8, 8, 2560.0, false}, {61, 5, 8, 1700.0, false}, {62, 10, 8, 3250.0, true},
+                                 {63, 10, 6, 2430.0, true}, {65, 7, 6, 1720.0, false}, {66, 8, 6, 1950.0, false},
+                                 {67, 4, 6, 1100.0, false}, {68, 4, 8, 1360.0, false}};
+    double best = 0.0;
+    int v = 0;
+    // The model ranks w4 tiles against each other; it knows nothing of the two-blocks-per-CU kernels.  So the tiles added
+    // for HTSAT (66 .. 68) compete only where the choice is inside the family already — one of the older tiles divides the
+    // shape — or K < 512, where they were measured against those kernels.  (ViT-L/14 and H/14, M = 129 x 128 and 65 x 128
+    // rows with K >= 1024, fit only the new tiles and lose 5 % on them: they stay where they were.)
+    // (... or the row count is a multiple of 4096 — HTSAT's token counts — where the new tiles were measured against those
+    // kernels on every shape: its stage-3 fc2, 32768 x 384 x 1536, has no older tile that divides N = 384: 58 -> 47 us)
+    bool family = K < 512 || M % 4096 == 0;
+    for (const Cand& c : cands)
+        if (c.id <= 65 && !(c.bf16_only && !bf16_out(mode)) && w4_shape_ok(M, N, K, c.mi, c.nj)) family = true;
+    for (const Cand& c : cands) {
+        if (c.id > 65 && !family) continue;
+        if (c.bf16_only && !bf16_out(mode)) continue;
+        if (!w4_shape_ok(M, N, K, c.mi, c.nj)) continue;
+        const long long tiles = (long long)(M / (32 * c.mi)) * (N / (32 * c.nj));
+        if (tiles < 192) continue;
+        const long long rounds = (tiles + 255) / 256;
+        const double epilogue = 10500.0 * (c.mi * c.nj / 64.0) * (bf16_out(mode) ? 1.0 : 2.0);
+        const double act = (mode == EPI_QUICKGELU || mode == EPI_GELU || mode == EPI_GELU_TANH) ? 5000.0 * (c.mi * c.nj / 40.0) : 0.0;
+        // operands beyond what the caches hold (> 64 MB): every CU streams its K-steps from the memory side, and a step
+        // cannot be shorter than its bytes at ~28 B per clock and CU (measured: 128 x 256 tiles 1360 -> 1640 cycles per
+        // step on ViT-L/14's fc2, 160 x 256 1700 -> 1950 on ViT-B/32's; 256 x 256, fewer bytes per flop, unchanged)
+        const bool streams = ((double)M + (double)N) * (double)K * 2.0 > 64.0e6;
+        const double step_bytes = (32.0 * c.mi + 32.0 * c.nj) * 128.0;
+        const double step = streams && step_bytes / 28.0 > c.step ? step_bytes / 28.0 : c.step;
+        const double cost = (double)rounds * (3200.0 + (K / 64) * step + epilogue + act);
+        if (v == 0 || cost < best) { best = cost; v = c.id; }
+    }
+    // the persistent form: no prologue between tiles, the C tile leaves under the next tile's loop; what stays exposed per
+    // tile is the packing of the accumulators (~1.9k cycles, ~6.2k with a sigmoid-shaped activation) and ~1.7k of drain
+    if (bf16_out(mode) && w4p_shape_ok(M, N, K)) {
+        const long long tiles = (long long)(M / 160) * (N / 256);
+        if (tiles >= cus) {
+            const long long rounds = (tiles + cus - 1) / cus;
+            const double pack = (mode == EPI_QUICKGELU || mode == EPI_GELU || mode == EPI_GELU_TANH) ? 6200.0 : 1900.0;
+            const bool streams = ((double)M + (double)N) * (double)K * 2.0 > 64.0e6;
+            const double cost = 3200.0 + (double)rounds * ((K / 64) * (streams ? 1902.0 : 1660.0) + 1700.0 + pack) + 5000.0;
+            if (v == 0 || cost < best) { best = cost; v = 64; }
+        }
+    }
+    return v;
+}
+
+// a GEMM whose split-K partials would not fit the scratch is not split
+constexpr size_t SPLITK_SCRATCH_CAP = (size_t)24 << 20;
+
+// slices of K for a skinny problem (rows 0..m_valid-1 <= 128 of A carry data); 0: not a split-K case
+static int splitk_slices(int M, int m_valid, int N, int K) {
+    if (m_valid < 1 || m_valid > 128 || M < 128 || K < 512 || K % 128 != 0 || N % 128 != 0 || N < 128) return 0;
+    const int slabs = N / 128;
+    int S = 1;
+    for (int c : {2, 4, 8, 16, 32}) {     // slices: enough blocks for the chip, at least two K-tiles per slice
+        if (K % (c * 64) != 0 || K / c < 128) break;
+        S = c;
+        if (slabs * c >= 160) break;
+    }
+    if (S < 2 || (size_t)S * 128 * N * sizeof(float) > SPLITK_SCRATCH_CAP) return 0;
+    return S;
+}
+
+// The plan of gemm_bf16 (m_valid = 0) and gemm_bf16_rows.  m_valid: the rows of A that carry data (the rest of the M rows
+// are padding nobody reads); overlapped: the calling thread runs another stream's kernels beside this one
+// (gemm_set_overlapped); cus: compute units of the device; force (debug library): a variant id for A/B runs, which goes
+// through the same shape fallbacks and never splits K.
+static GemmPlan gemm_plan(int M, int N, int K, int mode, int m_valid, bool overlapped, int cus, int force = 0) {
+    GemmPlan p;
+    p.rows[0] = M;
+    if (force) {
+        p.v[0] = resolve_variant(force, M, N, K, mode);
+        return p;
+    }
+    p.splitk = splitk_slices(M, m_valid, N, K);
+    auto one = [&](int v) {
+        p.v[0] = resolve_variant(v, M, N, K, mode);
+        return p;
+    };
+    if (const int vw = w4_variant(M, N, K, mode, cus)) return one(vw);
+    // Two whole batches in flight on two streams (VitEngine.forward_pipelined brackets its calls with wise_overlap_hint):
+    // measured in one process (ViT-B/32 bs=256): hint ignored 3.28 ms per step; the lone-stream heuristic minus the
+    // 320-row tilings (what follows below) 3.16; 128x128 everywhere 3.20.
+    // Tile quantisation decides between the ping-pong tilings: 6400 x 3072 is 300 tiles of 256x256 (two rounds
+    // at 59 %) but 240 tiles of 320x256 (one round at 94 %); measured 694 -> 799 TFLOP/s on that shape.
+    // (not when the caller overlaps two streams: a 144-KiB one-block-per-CU kernel leaves the other stream's
+    // kernels nowhere to run, measured 3.54 -> 3.74 ms per ViT-B/32 step)
+    if (!overlapped && M % 320 == 0 && N % 256 == 0) {
+        const long long t320 = (long long)(M / 320) * (N / 256), t256 = (long long)(M / 256) * (N / 256);
+        const double eff320 = (double)t320 / (double)(((t320 + 255) / 256) * 256);
+        const double eff256 = (M % 256 == 0) ? (double)t256 / (double)(((t256 + 255) / 256) * 256) : 0.0;
+        if (t320 >= 200 && eff320 >= 0.90 && eff320 > eff256 + 0.04) return one(42);
+    }
+    // fp32-output GEMMs with a narrow N (the two residual GEMMs of a ViT-B block, N = 768): 320 x 128 tiles of the
+    // ping-pong kernel when they fill the chip's 256 CUs almost exactly (12800 x 768: 240 tiles, against 200 tiles of
+    // 256 x 192 with a quarter more work each): 12800 x 768 x 3072 77 -> 70 us, x 768 32.6 -> 30.7 us
+    if ((mode == EPI_RESID || mode == EPI_F32) && !overlapped && M % 320 == 0 && N % 128 == 0 && K >= 128) {
+        const long long t = (long long)(M / 320) * (N / 128);
+        const double eff = (double)t / (double)(((t + 255) / 256) * 256);
+        if (t >= 200 && t <= 256 && eff >= 0.90) return one(44);
+    }
+    // The 256x256 ping-pong kernel (one block per CU) has the fastest main loop but no co-resident block to
+    // hide its epilogue or its tail.  Give it the rows whose tiles fill whole rounds of the 256 CUs and hand the
+    // remaining rows to the two-blocks-per-CU kernels (same stream, so the two launches are ordered).
+    if (M % 256 == 0 && N % 256 == 0) {
+        const int tiles_m = M / 256, tiles_n = N / 256;
+        const long long t256 = (long long)tiles_m * tiles_n;
+        const double eff256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
+        // (K < 512: a tile is 6-12 K-steps and its epilogue — the activation above all — is most of its life; the
+        // 128x128 kernel's second block per CU covers it: 131072x768x192 with GELU 120 -> 106 us, 32768x1536x384 79 -> 75)
+        if (t256 >= 200 && K >= 512 && (eff256 >= 0.85 || (K >= 2048 && eff256 >= 0.80))) return one(40);
+        // (measured: worth it only when the ping-pong part spans several rounds; at 1-2 rounds the second
+        // launch's own tail and the lost overlap cost more than the 128x128 kernel's slower main loop)
+        // ... or from two rounds when what is left over is small (ViT-L/14 half batch: 129 x 4 tiles = 2 rounds + 4)
+        if (t256 >= 2 * 256 && K >= 512) {
+            const int rounds = (int)(t256 / 256);
+            const int m_pp = (rounds * 256) / tiles_n;  // m-tiles whose tiles fill `rounds` rounds (within one row)
+            const bool small_rest = (tiles_m - m_pp) * 8 <= tiles_m;
+            if (m_pp >= 1 && m_pp < tiles_m && (long long)m_pp * tiles_n >= 200 && (t256 >= 3 * 256 || small_rest)) {
+                const int M1 = m_pp * 256, M2 = M - M1;
+                p.n = 2;
+                p.v[0] = resolve_variant(40, M1, N, K, mode);
+                p.rows[0] = M1;
+                p.v[1] = resolve_variant(auto_variant(M2, N, K), M2, N, K, mode);
+                p.rows[1] = M2;
+                return p;
+            }
+        }
+    }
+    return one(auto_variant(M, N, K));
+}
+
+// The LayerNorm fold (vit.hip's fold mode, HTSAT): every form is a one-wave-per-SIMD tile.  producer: the residual form
+// with statistics (mode EPI_RESID: x += ...; EPI_F32: x = ..., the rows that start a stream); wide96: the statistics are
+// kept per 32 columns (FoldArgs.group32).  Returns the variant id, 0 if no tile fits.
+static int fold_plan(int M, int N, int K, int mode, bool producer, bool wide96, int cus) {
+    // (the 160 x 256 producer has a residual form only: the rows that start a stream take 128 x 256 or 128 x 128)
+    auto tile = [&](int v) { return producer && mode == EPI_F32 && v == 61 ? (w4_shape_ok(M, N, K, 4, 8) ? 68 : 70) : v; };
+    const int v = w4_variant(M, N, K, mode, cus);
+    if (v == 61 || v == 68 || v == 70 || ((v == 60 || v == 64) && !producer)) return tile(v);   // (the 256 x 256 residual form with statistics spills)
+    // tiles with 96-column wave parts (256 x 192, 128 x 192, 128 x 192 at two workgroups per CU): any consumer; a producer
+    // only where the model's statistics are kept per 32 columns (FoldArgs.group32: MS-CLAP's HTSAT, widths 192 / 384 / 768)
+    if ((v == 66 || v == 67 || v == 69) && (!producer || wide96)) return v;
+    if (N % 128 != 0) return w4_shape_ok(M, N, K, 4, 6) ? ((long long)(M / 128) * (N / 192) >= 512 ? 69 : 67) : 0;
+    if (!producer && w4p_shape_ok(M, N, K) && (long long)(M / 160) * (N / 256) >= cus) return 64;
+    if (w4_shape_ok(M, N, K, 5, 8) && (long long)(M / 160) * (N / 256) >= 192) return tile(61);
+    if (w4_shape_ok(M, N, K, 4, 8) && (long long)(M / 128) * (N / 256) >= 256) return 68;
+    return 70;
+}
+
+// rows the tiles of conv3x3_bf16 walk: every cell, or the four members of every pooling window (floor: odd leftovers are
+// not computed)
+static long long conv_rows(int B, int T, int F, bool pool) { return pool ? 4ll * B * (T / 2) * (F / 2) : (long long)B * T * F; }
+
+// The tile of conv3x3_bf16 (M = conv_rows(...)).
+static ConvTile conv_plan(long long M, int Cout) {
+    // The ping-pong tile (one block per CU) where its tiles fill the chip in well-used rounds — measured per layer with
+    // tools/conv_bench.py (64 clips x 10 s): 1006-1162 against 904-1037 TFLOP/s on blocks 3 and 4 (6 and 3 rounds), 1031-1057
+    // against 978-996 on block 6 (184 tiles, one round), but 947-971 against 1049-1088 on block 5 (372 tiles = 1.45 rounds);
+    // its 256 x 128 form lost everywhere it was tried (block 2: 539-679 against 681-857) and is not used.
+    const long long tpp = ((M + 255) / 256) * (Cout / 256);
+    const double eff = tpp > 0 ? (double)tpp / (double)(((tpp + 255) / 256) * 256) : 0.0;
+    if (Cout % 256 == 0 && tpp >= 160 && eff >= 0.70 && (tpp <= 256 || eff >= 0.85)) return CONV_PP256;
+    if (Cout % 128 == 0) return CONV_128x128;
+    // 64-channel steps (block 1 of Cnn14): 256 x 64 tiles, every wave a 64 x 64 sub-tile (tools/conv_bench.py)
+    if (M >= 256 * 512) return CONV_256x64;
+    return CONV_128x64;
+}
 
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand per buffer
@@ -73,7 +313,6 @@ __device__ __forceinline__ bf16x8 lds_frag(const unsigned char* lds_tile, int ro
 template <int MODE>
 __device__ __forceinline__ void epilogue(f32x4 (&acc)[4][4], const float* __restrict__ bias, void* __restrict__ out,
                                          int N, int m0, int n0, int wm, int wn, int lane) {
-    const bool skip = g_skip_epilogue != 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int n = n0 + wn * 64 + j * 16 + (lane >> 4) * 4;
@@ -85,7 +324,6 @@ __device__ __forceinline__ void epilogue(f32x4 (&acc)[4][4], const float* __rest
             float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z,
                   v3 = acc[i][j][3] + bv.w;
             const size_t off = (size_t)m * N + n;
-            if (skip && v0 != 123456.75f) continue;
             if (MODE == EPI_RESID) {
                 float4* p = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + off);
                 float4 x = *p;
@@ -136,14 +374,12 @@ __device__ __forceinline__ void epilogue_lds(f32x4 (&acc)[4][4], const float* __
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool skip = g_skip_epilogue != 0;
     const int chunk = lane & 7;
     const int n = n0 + wn * 64 + chunk * 8;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
         const int row = t * 8 + (lane >> 3);
         const uint4 v = *reinterpret_cast<const uint4*>(my + row * RS + chunk * 16);
-        if (skip && v.x != 0x12345678u) continue;
         bf16_t* dst = out + (size_t)(m0 + wm * 64 + row) * N + n;
         if (n + 8 <= N)
             *reinterpret_cast<uint4*>(dst) = v;
@@ -189,12 +425,10 @@ __device__ __forceinline__ void epilogue_f32_lds_64x64(const f32x4 (*acc)[4] /*[
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool skip = g_skip_epilogue != 0;
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         const int r = t * 4 + g;
         float4 v = *reinterpret_cast<const float4*>(my + r * 256 + ((l15 ^ (r & 15)) << 4));
-        if (skip && v.x != 123456.75f) continue;
         if (MODE == EPI_RESID) { v.x += res[t].x; v.y += res[t].y; v.z += res[t].z; v.w += res[t].w; }
         if (in) *reinterpret_cast<float4*>(out + (size_t)(row0 + t * 4 + g) * N + n) = v;
     }
@@ -203,11 +437,10 @@ __device__ __forceinline__ void epilogue_f32_lds_64x64(const f32x4 (*acc)[4] /*[
 // The same for a (RI*16) x (NJ*16) piece of a wave's accumulators (the 8-wave kernels: NJ = 2, 3 or 4 column
 // tiles, RI <= 4 row tiles per pass so that the image stays within the wave's share of the dead staging LDS).
 // Rows are NJ*64 bytes; chunks are XOR-swizzled when a row has 16 or 8 of them and rotated when it has 12.
-// `pre` (optional): the residual values of this piece loaded earlier by prefetch_resid_piece with the same arguments.
 template <int MODE, int RI, int NJ>
 __device__ __forceinline__ void epilogue_f32_lds_piece(const f32x4 (*acc)[NJ], const float* __restrict__ bias,
                                                        float* __restrict__ out, int N, int row0, int col0, int lane,
-                                                       unsigned char* my, const float4* pre = nullptr) {
+                                                       unsigned char* my) {
     constexpr int CH = NJ * 4, RB = NJ * 64, ROWS = RI * 16;
     constexpr int RP = 64 / CH;                       // rows per wave instruction on the row-major walk (4, 5, 8)
     constexpr int IT = (ROWS + RP - 1) / RP;
@@ -222,10 +455,8 @@ __device__ __forceinline__ void epilogue_f32_lds_piece(const f32x4 (*acc)[NJ], c
 #pragma unroll
         for (int t = 0; t < IT; ++t) {
             const int r = t * RP + wr;
-            if (pre) res[t] = pre[t];
-            else
-                res[t] = (in && r < ROWS) ? *reinterpret_cast<const float4*>(out + (size_t)(row0 + r) * N + n)
-                                          : make_float4(0.f, 0.f, 0.f, 0.f);
+            res[t] = (in && r < ROWS) ? *reinterpret_cast<const float4*>(out + (size_t)(row0 + r) * N + n)
+                                      : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 #pragma unroll
@@ -243,36 +474,17 @@ __device__ __forceinline__ void epilogue_f32_lds_piece(const f32x4 (*acc)[NJ], c
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool skip = g_skip_epilogue != 0;
 #pragma unroll
     for (int t = 0; t < IT; ++t) {
         const int r = t * RP + wr;
         if (!in || r >= ROWS) continue;
         float4 v = *reinterpret_cast<const float4*>(my + r * RB + (phys(wc, r) << 4));
-        if (skip && v.x != 123456.75f) continue;
         if (MODE == EPI_RESID) { v.x += res[t].x; v.y += res[t].y; v.z += res[t].z; v.w += res[t].w; }
         *reinterpret_cast<float4*>(out + (size_t)(row0 + r) * N + n) = v;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// residual values of a (RI*16) x (NJ*16) piece in the lane order epilogue_f32_lds_piece adds them: issued at the top of
-// a kernel, the 200 KB a 256x192 tile reads back arrive under the main loop instead of in front of the store burst
-template <int RI, int NJ>
-__device__ __forceinline__ void prefetch_resid_piece(const float* __restrict__ out, int N, int row0, int col0, int lane,
-                                                     float4* res) {
-    constexpr int CH = NJ * 4, ROWS = RI * 16, RP = 64 / CH, IT = (ROWS + RP - 1) / RP;
-    const int wr = lane / CH, wc = lane - wr * CH;
-    const int n = col0 + wc * 4;
-    const bool in = wr < RP && n + 4 <= N;
-#pragma unroll
-    for (int t = 0; t < IT; ++t) {
-        const int r = t * RP + wr;
-        res[t] = (in && r < ROWS) ? *reinterpret_cast<const float4*>(out + (size_t)(row0 + r) * N + n)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
 }
 
 // a wave's whole MI x NJ accumulator block through epilogue_f32_lds_piece, four row tiles at a time
@@ -286,7 +498,7 @@ __device__ __forceinline__ void epilogue_f32_lds_wave(const f32x4 (*acc)[NJ], co
     if (MI == 10) epilogue_f32_lds_piece<MODE, 2, NJ>(acc + 8, bias, out, N, row0 + 128, col0, lane, my);
 }
 
-template <int MODE, int ABL = 0>  // ABL (timing-only builds): 1 = no staging in the loop, 2 = no LDS reads / MFMA
+template <int MODE>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restrict__ A,
                                                            const bf16_t* __restrict__ Wt,
                                                            const float* __restrict__ bias, int M, int N, int K,
@@ -300,7 +512,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
     // XCD-aware bijective remap: blocks b, b+8, ... share an XCD; give each XCD a contiguous run of tiles
     const int tiles_n = (N + BN - 1) / BN;
     int tm, tn;
-    tile_coords(M / BM, tiles_n, g_group_m ? g_group_m : 8, &tm, &tn);
+    tile_coords(M / BM, tiles_n, 8, &tm, &tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
     f32x4 acc[4][4];
@@ -309,14 +521,6 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // De-phase the two blocks that share a CU: all tiles cost the same, so co-resident blocks otherwise
-    // reach their (HBM-write-bound) epilogues together and the chip alternates between an MFMA phase and a
-    // store phase.  The second block per CU of the first dispatch round starts late by ~half a tile.
-    if (blockIdx.x >= 256 && blockIdx.x < 512) {
-        const int d = g_dephase;
-        for (int i = 0; i < d; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-
     const int nk = K / BK;
     stage_tile(A, K, m0, 0, smem, wave, lane, M - 1);
     stage_tile(Wt, K, n0, 0, smem + TILE_BYTES, wave, lane, N - 1);
@@ -324,14 +528,13 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         __syncthreads();  // waits vmcnt(0): tile kt landed; everyone done reading buffer cur^1
-        if (ABL != 1 && kt + 1 < nk) {
+        if (kt + 1 < nk) {
             unsigned char* nb = smem + (cur ^ 1) * 2 * TILE_BYTES;
             stage_tile(A, K, m0, (kt + 1) * BK, nb, wave, lane, M - 1);
             stage_tile(Wt, K, n0, (kt + 1) * BK, nb + TILE_BYTES, wave, lane, N - 1);
         }
         const unsigned char* At = smem + cur * 2 * TILE_BYTES;
         const unsigned char* Bt = At + TILE_BYTES;
-        if (ABL == 2) continue;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int chunk = s * 4 + (lane >> 4);
@@ -348,10 +551,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(const bf16_t* __restr
         }
     }
 
-    if (bf16_out(MODE) && (N & 7) == 0 && g_epi_lds) {
+    if (bf16_out(MODE) && (N & 7) == 0) {
         __syncthreads();  // staging buffers are dead from here on
         epilogue_lds<MODE>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-    } else if ((MODE == EPI_RESID || MODE == EPI_F32) && g_epi_lds) {
+    } else if (MODE == EPI_RESID || MODE == EPI_F32) {
         __syncthreads();
         epilogue_f32_lds_64x64<MODE>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * 64, n0 + wn * 64, lane,
                                      smem + wave * 16384);
@@ -585,7 +788,7 @@ __device__ __forceinline__ bf16x8 lds_frag_ring(const unsigned char* lds_tile, i
     return *reinterpret_cast<const bf16x8*>(lds_tile + row * (BKT * 2) + (swz_chunk<BKT>(row, chunk) << 4));
 }
 
-template <int MODE, int BKT, int STAGES, int MINB, int ABL = 0>
+template <int MODE, int BKT, int STAGES, int MINB>
 __global__ __launch_bounds__(256, MINB) void gemm_ring_kernel(const bf16_t* __restrict__ A,
                                                               const bf16_t* __restrict__ Wt,
                                                               const float* __restrict__ bias, int M, int N, int K,
@@ -600,7 +803,7 @@ __global__ __launch_bounds__(256, MINB) void gemm_ring_kernel(const bf16_t* __re
 
     const int tiles_n = (N + BN - 1) / BN;
     int tm, tn;
-    tile_coords(M / BM, tiles_n, g_group_m ? g_group_m : 8, &tm, &tn);
+    tile_coords(M / BM, tiles_n, 8, &tm, &tn);
     const int m0 = tm * BM, n0 = tn * BN;
 
     f32x4 acc[4][4];
@@ -637,7 +840,6 @@ __global__ __launch_bounds__(256, MINB) void gemm_ring_kernel(const bf16_t* __re
         }
         const unsigned char* At = smem + cur * SB;
         const unsigned char* Bt = At + TB;
-        if (ABL == 2) { cur = (cur + 1 == STAGES) ? 0 : cur + 1; continue; }
 #pragma unroll
         for (int s = 0; s < BKT / 32; ++s) {
             const int chunk = s * 4 + (lane >> 4);
@@ -657,10 +859,10 @@ __global__ __launch_bounds__(256, MINB) void gemm_ring_kernel(const bf16_t* __re
     // the ring (>= 64 KiB for the instantiations in use) is dead after the last fragment read: reuse it for the
     // row-major epilogues (these shapes, K = 96..384 with M in the 10^5s, are bound by their C traffic)
     constexpr bool RING_FITS = STAGES * SB >= 65536;
-    if (RING_FITS && bf16_out(MODE) && (N & 7) == 0 && g_epi_lds) {
+    if (RING_FITS && bf16_out(MODE) && (N & 7) == 0) {
         __syncthreads();
         epilogue_lds<MODE>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-    } else if (RING_FITS && (MODE == EPI_RESID || MODE == EPI_F32) && g_epi_lds) {
+    } else if (RING_FITS && (MODE == EPI_RESID || MODE == EPI_F32)) {
         __syncthreads();
         epilogue_f32_lds_64x64<MODE>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * 64, n0 + wn * 64, lane,
                                      smem + wave * 16384);
@@ -951,137 +1153,8 @@ __global__ __launch_bounds__(256, 2) void gemm_ln_kernel(const float* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
-// The whole MLP of a C = 96 Swin block in one kernel (HTSAT stage 1, 0.5M tokens):
-//     x += fc2( gelu( fc1( LayerNorm(x) ) ) )        fc1: 96 -> 384, fc2: 384 -> 96
-// As two GEMMs the 384-wide hidden activations (403 MB at batch 128) are written and read back once per block;
-// here a workgroup keeps its 128 rows on chip: the normalised rows sit in LDS as the A operand (as in
-// gemm_ln_kernel), the hidden layer is produced 96 columns at a time, activated, rounded to bf16 and parked in LDS in
-// the A-operand layout of the second GEMM, whose 128 x 96 accumulators collect the four chunks.  HBM sees x once
-// in each direction; W1 and W2 (147 KB together) come from L2.
-// LDS: A image 24 KiB + weight tile 24 KiB (W1 chunk, then W2 chunk) + hidden chunk 24 KiB = 72 KiB: two blocks per CU.
-// Wave layout 2 x 2, wave tile 64 x 48 for both GEMMs.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void mlp96_kernel(float* __restrict__ x, const float* __restrict__ lnw,
-                                                       const float* __restrict__ lnb, const bf16_t* __restrict__ W1,
-                                                       const float* __restrict__ b1, const bf16_t* __restrict__ W2,
-                                                       const float* __restrict__ b2, float eps) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int C = 96, HID = 384, NF = 3, TB = 128 * 64;
-    unsigned char* a_img = smem;              // LN(x) rows: [3][128][64 B]
-    unsigned char* w_img = smem + NF * TB;    // W1 chunk [96 hidden rows][96 k], then W2 chunk [96 out rows][96 k]
-    unsigned char* h_img = w_img + NF * TB;   // gelu(hidden chunk) [128][96] as an A operand
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int l15 = lane & 15, g = lane >> 4;
-    const int m0 = blockIdx.x * 128;
-
-    // ---- LayerNorm of the block's rows into the A image (8 lanes per row)
-    {
-        const int l8 = threadIdx.x & 7;
-#pragma unroll
-        for (int pass = 0; pass < 4; ++pass) {
-            const int r = pass * 32 + (threadIdx.x >> 3);
-            const float4* xr = reinterpret_cast<const float4*>(x + (size_t)(m0 + r) * C);
-            float4 v[NF];
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < NF; ++j) {
-                v[j] = xr[j * 8 + l8];
-                s += (v[j].x + v[j].y) + (v[j].z + v[j].w);
-            }
-            s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
-            const float mean = s / (float)C;
-            float q = 0.f;
-#pragma unroll
-            for (int j = 0; j < NF; ++j) {
-                const float a0 = v[j].x - mean, a1 = v[j].y - mean, a2 = v[j].z - mean, a3 = v[j].w - mean;
-                q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-            }
-            q += __shfl_xor(q, 1, 64); q += __shfl_xor(q, 2, 64); q += __shfl_xor(q, 4, 64);
-            const float rstd = rsqrtf(q / (float)C + eps);
-#pragma unroll
-            for (int j = 0; j < NF; ++j) {
-                const float4 gw = reinterpret_cast<const float4*>(lnw)[j * 8 + l8];
-                const float4 gb = reinterpret_cast<const float4*>(lnb)[j * 8 + l8];
-                uint2 pk;
-                pk.x = pack_bf16x2((v[j].x - mean) * rstd * gw.x + gb.x, (v[j].y - mean) * rstd * gw.y + gb.y);
-                pk.y = pack_bf16x2((v[j].z - mean) * rstd * gw.z + gb.z, (v[j].w - mean) * rstd * gw.w + gb.w);
-                *reinterpret_cast<uint2*>(a_img + j * TB + r * 64 + (swz_chunk<32>(r, l8 >> 1) << 4) + (l8 & 1) * 8) = pk;
-            }
-        }
-    }
-    f32x4 acc2[4][3];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    for (int c = 0; c < HID / 96; ++c) {
-        __syncthreads();   // A image complete (first trip) / GEMM2 of the previous chunk done with w_img and h_img
-        // ---- W1 rows c*96 .. c*96+95 (the tile helper stages 128 rows; the extra ones are never read)
-#pragma unroll
-        for (int t = 0; t < NF; ++t) stage_tile_ring<32>(W1, C, c * 96, t * 32, w_img + t * TB, wave, lane, HID - 1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        f32x4 acc1[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < NF; ++t) {
-            bf16x8 af[4], wf[3];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = lds_frag_ring<32>(a_img + t * TB, wm * 64 + i * 16 + l15, g);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) wf[j] = lds_frag_ring<32>(w_img + t * TB, wn * 48 + j * 16 + l15, g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc1[i][j], 0, 0, 0);
-        }
-        __syncthreads();   // W1 chunk consumed: the weight tile can take W2
-        // ---- W2 rows 0..95 (output columns), k = c*96 .. c*96+95
-#pragma unroll
-        for (int t = 0; t < NF; ++t) stage_tile_ring<32>(W2, HID, 0, c * 96 + t * 32, w_img + t * TB, wave, lane, C - 1);
-        // ---- hidden chunk: bias, GELU, bf16, into the A-operand image of the second GEMM
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int col = wn * 48 + j * 16 + g * 4;                    // column within the chunk
-            const float4 bv = *reinterpret_cast<const float4*>(b1 + c * 96 + col);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int r = wm * 64 + i * 16 + l15;
-                uint2 pk;
-                pk.x = pack_bf16x2(act_gelu(acc1[i][j][0] + bv.x), act_gelu(acc1[i][j][1] + bv.y));
-                pk.y = pack_bf16x2(act_gelu(acc1[i][j][2] + bv.z), act_gelu(acc1[i][j][3] + bv.w));
-                *reinterpret_cast<uint2*>(h_img + (col >> 5) * TB + r * 64 + (swz_chunk<32>(r, (col & 31) >> 3) << 4) +
-                                          ((col >> 2) & 1) * 8) = pk;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < NF; ++t) {
-            bf16x8 hf[4], wf[3];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) hf[i] = lds_frag_ring<32>(h_img + t * TB, wm * 64 + i * 16 + l15, g);
-#pragma unroll
-            for (int j = 0; j < 3; ++j) wf[j] = lds_frag_ring<32>(w_img + t * TB, wn * 48 + j * 16 + l15, g);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    acc2[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], hf[i], acc2[i][j], 0, 0, 0);
-        }
-    }
-    __syncthreads();       // all reads of w_img / h_img done: they become the residual epilogue's scratch (4 x 12 KiB)
-    epilogue_f32_lds_piece<EPI_RESID, 4, 3>(acc2, b2, x, C, m0 + wm * 64, wn * 48, lane, w_img + wave * 12288);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same MLP with BOTH weight matrices resident in LDS and nothing else going through it: a persistent workgroup (one per CU,
+// The whole MLP of a C = 96 Swin block in one kernel (HTSAT stage 1, 0.5M tokens): x += fc2(gelu(fc1(LayerNorm(x)))),
+// fc1: 96 -> 384, fc2: 384 -> 96, with BOTH weight matrices resident in LDS and nothing else going through it: a persistent workgroup (one per CU,
 // 8 waves) stages W1 [384][96] and W2 [96][384] once as MFMA operand images (147 KiB), and every wave takes 32 tokens at a
 // time through the whole MLP in registers:
 //   x rows -> LayerNorm (4 lanes per token, two-pass) -> bf16 B-operand fragments;
@@ -1090,8 +1163,8 @@ __global__ __launch_bounds__(256, 2) void mlp96_kernel(float* __restrict__ x, co
 //   image is stored with its k index permuted the way the first product's accumulators come out;
 //   + b2 + x, stored as 16-byte pieces.
 // No barrier after the prologue, no LDS write, no staging latency in the loop; what remains is the GELU's VALU work
-// (192 values per lane and 32 tokens).  mlp96_kernel above re-stages the weight tiles for every 128 rows (600 MB of
-// L2 -> LDS traffic per launch) and waits for them four times per block.
+// (192 values per lane and 32 tokens).  The staged form it replaced re-staged the weight tiles for every 128 rows (600 MB of
+// L2 -> LDS traffic per launch) and waited for them four times per block.
 // ------------------------------------------------------------------------------------------------
 constexpr int MLPR_W1_BYTES = 3 * 384 * 64, MLPR_W2_BYTES = 12 * 96 * 64;
 
@@ -1254,10 +1327,10 @@ static void launch_gemm_ln(const float* x, const float* lnw, const float* lnb, c
     hipLaunchKernelGGL(kern, dim3(M / 128), dim3(256), lds, st, x, lnw, lnb, Wt, bias, M, N, eps, out);
 }
 
-template <int MODE, int BKT, int STAGES, int MINB, int ABL = 0>
+template <int MODE, int BKT, int STAGES, int MINB>
 static void launch_ring(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
                         hipStream_t st) {
-    auto kern = gemm_ring_kernel<MODE, BKT, STAGES, MINB, ABL>;
+    auto kern = gemm_ring_kernel<MODE, BKT, STAGES, MINB>;
     const size_t lds = (size_t)STAGES * 2 * 128 * BKT * 2;
     static PerDeviceOnce attr_set;
     attr_set([&] {
@@ -1267,10 +1340,10 @@ static void launch_ring(const bf16_t* A, const bf16_t* Wt, const float* bias, in
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, A, Wt, bias, M, N, K, out);
 }
 
-template <int MODE, int ABL = 0>
+template <int MODE>
 static void launch_gemm(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
                         hipStream_t st) {
-    auto kern = gemm_bf16_kernel<MODE, ABL>;
+    auto kern = gemm_bf16_kernel<MODE>;
     const size_t lds = 4 * TILE_BYTES;  // 64 KiB
     static PerDeviceOnce attr_set;
     attr_set([&] {
@@ -1288,7 +1361,6 @@ static void launch_gemm(const bf16_t* A, const bf16_t* Wt, const float* bias, in
 template <int MODE, int NT, int MI = 8>
 __device__ __forceinline__ void epilogue_big(f32x4 (&acc)[MI][NT], const float* __restrict__ bias,
                                              void* __restrict__ out, int N, int m0, int n0, int wm, int wn, int lane) {
-    const bool skip = g_skip_epilogue != 0;
     // epilogue: acc[i][j][r] = C[m0 + wm*128 + i*16 + (lane&15)][n0 + wn*16*NT + j*16 + (lane>>4)*4 + r]
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
@@ -1300,7 +1372,6 @@ __device__ __forceinline__ void epilogue_big(f32x4 (&acc)[MI][NT], const float* 
             float v0 = acc[i][j][0] + bv.x, v1 = acc[i][j][1] + bv.y, v2 = acc[i][j][2] + bv.z,
                   v3 = acc[i][j][3] + bv.w;
             const size_t off = (size_t)m * N + n;
-            if (skip && v0 != 123456.75f) continue;
             if (MODE == EPI_RESID) {
                 float4* p = reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + off);
                 float4 x = *p;
@@ -1332,10 +1403,8 @@ __device__ __forceinline__ void stage_rows8(const bf16_t* __restrict__ G, int ld
     }
 }
 
-// PRE (residual mode): the tile's residual values are loaded into registers before the main loop (one block per CU:
-// 96 accumulator + 104 residual registers per lane)
-template <int MODE, int NT, int ABL = 0, bool PRE = false>
-__global__ __launch_bounds__(512, PRE ? 1 : 2) void gemm_big_kernel(const bf16_t* __restrict__ A,
+template <int MODE, int NT>
+__global__ __launch_bounds__(512, 2) void gemm_big_kernel(const bf16_t* __restrict__ A,
                                                                     const bf16_t* __restrict__ Wt,
                                                                     const float* __restrict__ bias, int M, int N, int K,
                                                                     void* __restrict__ out) {
@@ -1348,7 +1417,7 @@ __global__ __launch_bounds__(512, PRE ? 1 : 2) void gemm_big_kernel(const bf16_t
 
     const int tiles_n = N / BNB;
     int tm, tn;
-    tile_coords(M / BMB, tiles_n, g_group_m ? g_group_m : 4, &tm, &tn);
+    tile_coords(M / BMB, tiles_n, 4, &tm, &tn);
     const int m0 = tm * BMB, n0 = tn * BNB;
 
     f32x4 acc[8][NT];
@@ -1360,17 +1429,10 @@ __global__ __launch_bounds__(512, PRE ? 1 : 2) void gemm_big_kernel(const bf16_t
     const int nk = K / 64;
     stage_rows8<BMB>(A, K, m0, 0, smem, wave, lane);
     stage_rows8<BNB>(Wt, K, n0, 0, smem + TA, wave, lane);
-    constexpr int PIT = (64 + 64 / (NT * 4) - 1) / (64 / (NT * 4));   // residual float4 per lane and 64-row piece
-    float4 pre0[PRE ? PIT : 1], pre1[PRE ? PIT : 1];
-    if (PRE) {
-        prefetch_resid_piece<4, NT>(reinterpret_cast<const float*>(out), N, m0 + wm * 128, n0 + wn * (16 * NT), lane, pre0);
-        prefetch_resid_piece<4, NT>(reinterpret_cast<const float*>(out), N, m0 + wm * 128 + 64, n0 + wn * (16 * NT), lane,
-                                    pre1);
-    }
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         __syncthreads();
-        if (ABL != 1 && kt + 1 < nk) {
+        if (kt + 1 < nk) {
             unsigned char* nb = smem + (cur ^ 1) * SB;
             stage_rows8<BMB>(A, K, m0, (kt + 1) * 64, nb, wave, lane);
             stage_rows8<BNB>(Wt, K, n0, (kt + 1) * 64, nb + TA, wave, lane);
@@ -1392,14 +1454,7 @@ __global__ __launch_bounds__(512, PRE ? 1 : 2) void gemm_big_kernel(const bf16_t
             }
         }
     }
-    if (PRE) {
-        __syncthreads();
-        unsigned char* my = smem + wave * (2 * SB / 8);
-        epilogue_f32_lds_piece<MODE, 4, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * 128, n0 + wn * (16 * NT),
-                                            lane, my, pre0);
-        epilogue_f32_lds_piece<MODE, 4, NT>(acc + 4, bias, reinterpret_cast<float*>(out), N, m0 + wm * 128 + 64,
-                                            n0 + wn * (16 * NT), lane, my, pre1);
-    } else if ((MODE == EPI_RESID || MODE == EPI_F32) && g_epi_lds) {
+    if (MODE == EPI_RESID || MODE == EPI_F32) {
         __syncthreads();  // staging buffers are dead; each wave takes SB*2/8 >= 12 KiB of them
         epilogue_f32_lds_wave<MODE, 8, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * 128,
                                            n0 + wn * (16 * NT), lane, smem + wave * (2 * SB / 8));
@@ -1409,24 +1464,9 @@ __global__ __launch_bounds__(512, PRE ? 1 : 2) void gemm_big_kernel(const bf16_t
 }
 
 template <int MODE, int NT>
-static void launch_big_pre(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
-                           hipStream_t st) {
-    if constexpr (MODE == EPI_RESID) {
-        auto kern = gemm_big_kernel<MODE, NT, 0, true>;
-        const size_t lds = (size_t)2 * (256 + 64 * NT) * 128;
-        static PerDeviceOnce attr_set;
-        attr_set([&] {
-            raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
-        });
-        const int grid = (M / 256) * (N / (64 * NT));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, Wt, bias, M, N, K, out);
-    }
-}
-
-template <int MODE, int NT, int ABL = 0>
 static void launch_big(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
                        hipStream_t st) {
-    auto kern = gemm_big_kernel<MODE, NT, ABL>;
+    auto kern = gemm_big_kernel<MODE, NT>;
     const size_t lds = (size_t)2 * (256 + 64 * NT) * 128;
     static PerDeviceOnce attr_set;
     attr_set([&] {
@@ -1464,7 +1504,6 @@ __device__ __forceinline__ void epilogue_big_lds(f32x4 (&acc)[MI][4], const floa
     constexpr int RS = 144, HI = MI / 2, HROWS = HI * 16;  // i-tiles / rows per half (MI = 8: 64, MI = 10: 80)
     unsigned char* my = smem + wave * (HROWS * RS);
     const int l15 = lane & 15, g = lane >> 4;
-    const bool skip = g_skip_epilogue != 0;
     const int chunk = lane & 7;
     const int ncol = n0 + wn * 64 + chunk * 8;
 #pragma unroll
@@ -1493,14 +1532,11 @@ __device__ __forceinline__ void epilogue_big_lds(f32x4 (&acc)[MI][4], const floa
         for (int t = 0; t < HROWS / 8; ++t) {
             const int row = t * 8 + (lane >> 3);
             const uint4 v = *reinterpret_cast<const uint4*>(my + row * RS + chunk * 16);
-            if (skip && v.x != 0x12345678u) continue;
             uint4* gdst = reinterpret_cast<uint4*>(out + (size_t)(m0 + wm * (MI * 16) + half * HROWS + row) * N + ncol);
-            if (g_store_nt) {
-                typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(u32x4_t{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_t*>(gdst));
-            } else {
-                *gdst = v;
-            }
+            // non-temporal: the C tile is read by a later kernel, not by this one (ViT-L/14 +1.5 % end to end, ViT-B/32
+            // unchanged)
+            typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+            __builtin_nontemporal_store(u32x4_t{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_t*>(gdst));
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1519,23 +1555,20 @@ __device__ __forceinline__ void epilogue_big_lds(f32x4 (&acc)[MI][4], const floa
 //   WAR: tile kt+3 overwrites the slot of tile kt-1, whose fragment reads both groups retired
 //        (lgkmcnt(0)) before the barrier that precedes the overwrite.
 // ------------------------------------------------------------------------------------------------
-// WROWS = rows per wave: 128 -> 256x256 tile (waves 2x4, 4 stages of 32 KiB); 64 -> 256x128 tile
-// (waves 4x2, 5 stages of 24 KiB) for shapes whose 256x256 tiling leaves a long tail; 160 -> 320x256 tile
+// WROWS = rows per wave: 128 -> 256x256 tile (waves 2x4, 4 stages of 32 KiB); 80 -> 320x128 tile (waves 4x2, 4 stages
+// of 28 KiB) for the narrow fp32-output GEMMs; 160 -> 320x256 tile
 // (waves 2x4, 4 stages of 36 KiB) for shapes that fill the chip in whole rounds only with 320-row tiles
 // (M = 6400, N = 3072: 240 tiles).  A 320-row A tile is 20 KiB per stage = 2.5 rounds of the 8 waves, so waves
 // 0-3 (the early group) issue one LDS-DMA more per K-tile than waves 4-7: the counted vmcnt differs per group.
-// MF32 (debug library, TIMING ONLY — the result is not a GEMM): the cluster as 16 v_mfma_f32_32x32x16_bf16 on the same operand
-// registers instead of 32 v_mfma_f32_16x16x32_bf16: same LDS / LDS-DMA traffic and barriers, half the matrix instructions per
-// FLOP — what the loop would gain from the larger instruction before its fragment layouts and epilogues are rewritten for it.
-template <int MODE, int WROWS, int STG = 0, bool MF32 = false>
+template <int MODE, int WROWS>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Wt,
                                                          const float* __restrict__ bias, int M, int N, int K,
                                                          void* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int BKT = 32, NT = 4, MI = WROWS / 16;
-    constexpr int BMB = (WROWS == 64) ? 256 : (WROWS == 80) ? 320 : 2 * WROWS;   // 80: 320 x 128, four wave rows
+    constexpr int BMB = (WROWS == 80) ? 320 : 2 * WROWS;   // 80: 320 x 128, four wave rows
     constexpr int WM_WAVES = BMB / WROWS, WN_WAVES = 8 / WM_WAVES, BNB = WN_WAVES * 64;
-    constexpr int STAGES = STG ? STG : ((WROWS == 64) ? 5 : 4);
+    constexpr int STAGES = 4;
     constexpr int TA = BMB * BKT * 2, TBt = BNB * BKT * 2, SB = TA + TBt;
     // LDS-DMA instructions per thread per K-tile: waves 0-3 take the partial last round of a 320-row A tile
     constexpr int GPS_E = (TA / 1024 + 7) / 8 + TBt / 8192, GPS_L = TA / 8192 + TBt / 8192;
@@ -1548,7 +1581,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restric
 
     const int tiles_n = N / BNB;
     int tm, tn;
-    tile_coords(M / BMB, tiles_n, g_group_m ? g_group_m : 4, &tm, &tn);
+    tile_coords(M / BMB, tiles_n, 4, &tm, &tn);
     const int m0 = tm * BMB, n0 = tn * BNB;
 
     f32x4 acc[MI][NT];
@@ -1556,15 +1589,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restric
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    using f32x16 = __attribute__((ext_vector_type(16))) float;
-    f32x16 acc32[MF32 ? 8 : 1];
-    if constexpr (MF32) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc32[i][r] = 0.f;
-    }
     const int nk = K / BKT;
 #pragma unroll
     for (int s = 0; s < STAGES - 1; ++s) {
@@ -1579,19 +1603,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restric
         __builtin_amdgcn_s_barrier();
     }
     int cur = 0;
-#ifdef WISE_DEBUG_KNOBS
-    // stamps: lane 0 of waves 0 (early group) and 4 (late group) of block g_stamp_block; 8 slots per K-tile
-    const bool stamp_on = g_stamp_buf != nullptr && (int)blockIdx.x == g_stamp_block && lane == 0 && (wave & 3) == 0;
-    unsigned long long* sbuf = g_stamp_buf + (size_t)(wave >> 2) * 4096;
-#endif
     for (int kt = 0; kt < nk; ++kt) {
         // ---- L part
-        WISE_STAMP(0);
         if (kt + STAGES - 2 < nk) wait_inflight(); else wait_vmcnt<0>();   // my share of tile kt has landed
-        WISE_STAMP(1);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
-        WISE_STAMP(2);
         if (kt + STAGES - 1 < nk) {
             int ns = cur + STAGES - 1;
             if (ns >= STAGES) ns -= STAGES;
@@ -1607,48 +1623,26 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restric
 #pragma unroll
         for (int i = 0; i < MI; ++i) af[i] = lds_frag_ring<BKT>(At, wm * WROWS + i * 16 + (lane & 15), chunk);
         // my share of tile kt+1 has landed before the barrier after which the other group may read it
-        WISE_STAMP(3);
         if (kt + STAGES - 1 < nk) wait_inflight(); else wait_vmcnt<0>();
-        WISE_STAMP(4);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        WISE_STAMP(5);
         __builtin_amdgcn_s_barrier();
         // ---- M part: registers only
         __builtin_amdgcn_sched_barrier(0);
-        WISE_STAMP(6);
         __builtin_amdgcn_s_setprio(1);
-        if constexpr (MF32) {
-            static_assert(!MF32 || (MI == 8 && NT == 4), "timing variant: 128 x 64 per wave");
 #pragma unroll
-            for (int kh = 0; kh < 2; ++kh)         // k-half outermost: eight independent accumulators between two uses of one
+        for (int i = 0; i < MI; ++i)
 #pragma unroll
-                for (int i2 = 0; i2 < 4; ++i2)
-#pragma unroll
-                    for (int j2 = 0; j2 < 2; ++j2)
-                        acc32[i2 * 2 + j2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[j2 * 2 + kh], af[i2 * 2 + kh], acc32[i2 * 2 + j2], 0, 0, 0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-        }
+            for (int j = 0; j < NT; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_sched_barrier(0);
-        WISE_STAMP(7);
         cur = (cur + 1 == STAGES) ? 0 : cur + 1;
-    }
-    if constexpr (MF32) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r >> 2][r & 3] = acc32[i][r];
     }
     if (!late) __builtin_amdgcn_s_barrier();
     constexpr bool BF16OUT = bf16_out(MODE);
     if constexpr (WROWS == 80) {
-        if (!BF16OUT && g_epi_lds) {
+        if (!BF16OUT) {
             __syncthreads();  // the ring (112 KiB) is dead: 14 KiB of it per wave, pieces of 32 rows x 256 B
             unsigned char* my = smem + wave * 14336;
             float* o = reinterpret_cast<float*>(out);
@@ -1658,47 +1652,36 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(const bf16_t* __restric
         } else {
             epilogue_big<MODE, NT, MI>(acc, bias, out, N, m0, n0, wm, wn, lane);
         }
-    } else if constexpr (WROWS != 64) {
-        if (BF16OUT && g_epi_lds) {
-            __syncthreads();  // both groups are past their last fragment read: the ring is dead
-            epilogue_big_lds<MODE, MI>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-        } else if (!BF16OUT && g_epi_lds) {
-            __syncthreads();  // the ring is dead: 16 KiB (18 KiB) of it per wave
-            epilogue_f32_lds_wave<MODE, MI, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * WROWS,
-                                                n0 + wn * 64, lane, smem + wave * 16384);
-        } else {
-            epilogue_big<MODE, NT, MI>(acc, bias, out, N, m0, n0, wm, wn, lane);
-        }
+    } else if constexpr (BF16OUT) {
+        __syncthreads();  // both groups are past their last fragment read: the ring is dead
+        epilogue_big_lds<MODE, MI>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
     } else {
-        if (BF16OUT && g_epi_lds) {
-            __syncthreads();
-            epilogue_lds<MODE>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-        } else {
-            epilogue<MODE>(acc, bias, out, N, m0, n0, wm, wn, lane);
-        }
+        __syncthreads();  // the ring is dead: 16 KiB (18 KiB) of it per wave
+        epilogue_f32_lds_wave<MODE, MI, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * WROWS,
+                                            n0 + wn * 64, lane, smem + wave * 16384);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // The 3x3 convolution (conv3x3_kernel above) on the ping-pong kernel's tile, ring and schedule: 256 x 256 output
-// tile (WROWS 128) or 256 x 128 (WROWS 64), K-tiles of 32 input channels of one tap (Cin % 32 == 0).  Only the A
+// tile, K-tiles of 32 input channels of one tap (Cin % 32 == 0).  Only the A
 // staging differs from gemm_pp_kernel: the two (or, never here, three) rows a lane stages keep their (t, f) coordinates
 // in registers, the tap of the K-tile being staged shifts the source address, and a row whose neighbour lies outside
 // the image reads the page of zeros.  Same vmcnt counts (same number of LDS-DMA instructions per K-tile), same RAW / WAR
 // argument.  out has ceil256(M) rows.
 // ------------------------------------------------------------------------------------------------
-// POOL (WROWS 128): as in conv3x3_kernel — row wm*128 + i*16 + l is member i & 3 of the window of output cell
+// POOL: as in conv3x3_kernel — row wm*128 + i*16 + l is member i & 3 of the window of output cell
 // 64*tile + 32*wm + 16*(i >> 2) + l, so a window is acc[4h .. 4h+3][j] of one lane.
-template <int WROWS, bool POOL>
+template <bool POOL>
 __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt,
                                                             const float* __restrict__ bias,
                                                             const bf16_t* __restrict__ zeros, int T, int F, int Cin,
                                                             int M, int Cout, bf16_t* __restrict__ out) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int BKT = 32, NT = 4, MI = WROWS / 16;
+    constexpr int BKT = 32, NT = 4, WROWS = 128, MI = WROWS / 16;
     constexpr int BMB = 256;
     constexpr int WM_WAVES = BMB / WROWS, WN_WAVES = 8 / WM_WAVES, BNB = WN_WAVES * 64;
-    constexpr int STAGES = (WROWS == 64) ? 5 : 4;
+    constexpr int STAGES = 4;
     constexpr int TA = BMB * BKT * 2, TBt = BNB * BKT * 2, SB = TA + TBt;
     constexpr int GPS = TA / 8192 + TBt / 8192;
     constexpr int INFL = (STAGES - 2) * GPS;
@@ -1714,7 +1697,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const bf16_t* __rest
     const int m0 = tm * BMB, n0 = tn * BNB;
     const int K = 9 * Cin, ck = Cin / BKT, nk = 9 * ck;
 
-    static_assert(!POOL || WROWS == 128, "fused pooling: 256 x 256 tile only");
     int pt[RA], pf[RA];
     long long poff[RA];
     const int T2 = T >> 1, F2 = F >> 1;
@@ -1824,274 +1806,17 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const bf16_t* __rest
         return;
     }
     __syncthreads();  // both groups are past their last fragment read: the ring is dead
-    if constexpr (WROWS == 64)
-        epilogue_lds<EPI_RELU>(acc, bias, out, Cout, m0, n0, wm, wn, lane, wave, smem);
-    else if constexpr (!POOL)
-        epilogue_big_lds<EPI_RELU, MI>(acc, bias, out, Cout, m0, n0, wm, wn, lane, wave, smem);
+    epilogue_big_lds<EPI_RELU, MI>(acc, bias, out, Cout, m0, n0, wm, wn, lane, wave, smem);
 }
 
-#ifdef WISE_DEBUG_KNOBS
-// ------------------------------------------------------------------------------------------------
-// Ping-pong kernel, third form (debug variant 47; MEASURED SLOWER, 20-25 % on every shape — 980 against 1229 TFLOP/s at 8192^3:
-// a W fragment load is sixteen 64-byte row segments per instruction): only the A tile goes through the LDS-DMA ring; the W
-// fragments travel from L2 straight into registers, two K-tiles ahead.  Per K-tile and CU that is 16 KiB of LDS-DMA
-// writes instead of 32 and 64 KiB of fragment reads instead of 96, and the ring holds six A tiles in 96 KiB.
-// 256 x 256 tile, 8 waves as 2 x 4, each 128 rows x 64 columns.  Same two-group schedule and barriers as gemm_pp_kernel.
-//   vmcnt: a wave issues, per K-tile and in this order, 2 LDS-DMA (A tile kt + 5) and 4 loads (W fragments of kt + 2); loads
-//   complete in order, so vmcnt(12) in front of the cluster of tile kt says: W(kt) is here, and so is every A tile <= kt + 3.
-// ------------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(512, 2) void gemm_ppb_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Wt,
-                                                          const float* __restrict__ bias, int M, int N, int K,
-                                                          void* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int BKT = 32, NT = 4, MI = 8, WROWS = 128, BMB = 256, BNB = 256, STAGES = 6;
-    constexpr int TA = BMB * BKT * 2;              // 16 KiB
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const bool late = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
-    const int tiles_n = N / BNB;
-    int tm, tn;
-    tile_coords(M / BMB, tiles_n, g_group_m ? g_group_m : 4, &tm, &tn);
-    const int m0 = tm * BMB, n0 = tn * BNB;
-    f32x4 acc[MI][NT];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int nk = K / BKT;
-    // this lane's W rows: fragment j of K-tile kt = 16 bytes at wrow[j] + kt * 32
-    const bf16_t* wrow = Wt + (size_t)(n0 + wn * 64 + (lane & 15)) * K + (lane >> 4) * 8;
-    const size_t wj = (size_t)16 * K;
-    bf16x8 wq[3][NT];                              // W fragments of tiles kt, kt + 1, kt + 2 (slot = tile % 3)
-    auto load_w = [&](int kt, bf16x8 (&dst)[NT]) {
-#pragma unroll
-        for (int j = 0; j < NT; ++j) dst[j] = *reinterpret_cast<const bf16x8*>(wrow + j * wj + (size_t)kt * BKT);
-    };
-    // prologue: A tiles 0..4 and W of tiles 0, 1 — issued tile by tile in the loop's order (A first, then W)
-#pragma unroll
-    for (int s = 0; s < STAGES - 1; ++s)
-        if (s < nk) stage_rows8_ring<BMB, BKT>(A, K, m0, s * BKT, smem + s * TA, wave, lane);
-    load_w(0, wq[0]);
-    if (nk > 1) load_w(1, wq[1]);
-    if (late) {
-        wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-    }
-    auto step = [&](int kt, int cur, bf16x8 (&wf)[NT], bf16x8 (&wnext)[NT]) {
-        // ---- L part
-        // W(kt) was requested two steps ago; newer than it are only the previous step's requests (2 LDS-DMA + 4 loads,
-        // fewer at the ends).  Everything older — every A tile up to kt + 3 — has landed with it.
-        if (kt == 0) { if (nk > 1) wait_vmcnt<4>(); else wait_vmcnt<0>(); }
-        else if (kt + 4 < nk) wait_vmcnt<6>();
-        else if (kt + 1 < nk) wait_vmcnt<4>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (kt + STAGES - 1 < nk) {
-            int ns = cur + STAGES - 1;
-            if (ns >= STAGES) ns -= STAGES;
-            stage_rows8_ring<BMB, BKT>(A, K, m0, (kt + STAGES - 1) * BKT, smem + ns * TA, wave, lane);
-        }
-        if (kt + 2 < nk) load_w(kt + 2, wnext);
-        const unsigned char* At = smem + cur * TA;
-        const int chunk = lane >> 4;
-        bf16x8 af[MI];
-#pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = lds_frag_ring<BKT>(At, wm * WROWS + i * 16 + (lane & 15), chunk);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        // ---- M part: registers only
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < MI; ++i)
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    int cur = 0;
-    for (int kt = 0; kt < nk; kt += 3) {
-        step(kt, cur, wq[0], wq[2]);
-        cur = (cur + 1 == STAGES) ? 0 : cur + 1;
-        if (kt + 1 < nk) { step(kt + 1, cur, wq[1], wq[0]); cur = (cur + 1 == STAGES) ? 0 : cur + 1; }
-        if (kt + 2 < nk) { step(kt + 2, cur, wq[2], wq[1]); cur = (cur + 1 == STAGES) ? 0 : cur + 1; }
-    }
-    if (!late) __builtin_amdgcn_s_barrier();
-    constexpr bool BF16OUT = bf16_out(MODE);
-    __syncthreads();
-    if (BF16OUT)
-        epilogue_big_lds<MODE, MI>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-    else
-        epilogue_f32_lds_wave<MODE, MI, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * WROWS, n0 + wn * 64, lane,
-                                            smem + wave * 16384);
-}
 
-template <int MODE>
-static void launch_ppb(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out, hipStream_t st) {
-    auto kern = gemm_ppb_kernel<MODE>;
-    const size_t lds = 131072;   // six 16-KiB A tiles; the epilogues use up to 128 KiB of the same space
-    static PerDeviceOnce attr_set;
-    attr_set([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
-    });
-    hipLaunchKernelGGL(kern, dim3((M / 256) * (N / 256)), dim3(512), lds, st, A, Wt, bias, M, N, K, out);
-}
-#endif
-
-#ifdef WISE_DEBUG_KNOBS
-// ------------------------------------------------------------------------------------------------
-// Ping-pong kernel, second form: the fragment reads ride inside the MFMA cluster.  (MEASURED SLOWER — round 2, kept in
-// the debug library only as variant 50: 881 -> 795 TFLOP/s on 12800x2304x768, 1254 -> 1122 on 8192^3.  The reads
-// lengthen the cluster by more than they take off the part between clusters: on this chip work moved between the two
-// waves of a SIMD does not net, as MI355X_MICROARCH.md says for balanced pairings — and it does not for this one.)
-// In-kernel stamps of gemm_pp_kernel (tools/gemm_stamps.py) showed why its main loop stops at ~1100 TFLOP/s: per K-tile
-// a wave spends ~650 cycles in its 32-MFMA cluster but ~1100 in the part around it (two counted vmcnt waits, LDS-DMA
-// issue, 12 ds_read_b128 and the wait for them), so the partner wave's cluster cannot cover it and the matrix pipe
-// idles ~45 % of the time.  Here the reads of tile kt+1 are issued BETWEEN the MFMAs of tile kt: a row fragment is
-// reloaded right after its last use (same registers), the four column fragments go to a second register set first, so
-// nothing waits for LDS outside the cluster any more — an MFMA gap takes two ds_read_b128 for ~3 cycles
-// (MI355X_MICROARCH.md, LDS) — and the part between the clusters shrinks to: counted vmcnt, barrier, LDS-DMA issue.
-// Synchronisation (late group one barrier behind, as before; two barriers Ba, Bb per K-tile and wave):
-//   RAW  tile kt+1 is read during M(kt), i.e. after Bb(kt) by the early group and one barrier later by the late one:
-//        every wave waits for its own share of tile kt+1 before Ba(kt) and before Bb(kt);
-//   WAR  L(kt) refills the slot of tile kt-1 with tile kt+3; tile kt-1 was read during M(kt-2), and every wave retires
-//        its LDS reads (lgkmcnt(0), cheap: they were issued a whole part earlier) before Bb, so all reads of tile kt-1
-//        are complete before the barrier that precedes any refill of its slot.
-// 256x256 tile (WROWS = 128), 4-stage ring of 32-deep K-tiles, 8 waves as 2 x 4.
-// ------------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ Wt,
-                                                          const float* __restrict__ bias, int M, int N, int K,
-                                                          void* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int BKT = 32, NT = 4, MI = 8, WROWS = 128, BMB = 256, BNB = 256, STAGES = 4;
-    constexpr int TA = BMB * BKT * 2, TBt = BNB * BKT * 2, SB = TA + TBt;
-    constexpr int GPS = TA / 8192 + TBt / 8192;        // LDS-DMA instructions per thread per K-tile (4)
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int wm = wave >> 2, wn = wave & 3;
-    const bool late = __builtin_amdgcn_readfirstlane(threadIdx.x) >= 256;
-
-    int tm, tn;
-    tile_coords(M / BMB, N / BNB, g_group_m ? g_group_m : 4, &tm, &tn);
-    const int m0 = tm * BMB, n0 = tn * BNB;
-
-    f32x4 acc[MI][NT];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    const int nk = K / BKT;
-    // wait until my share of tile t has landed, given that my LDS-DMAs were issued in tile order up to tile `issued`
-    auto wait_tile = [&](int t, int issued) {
-        const int younger = issued - t;              // tiles issued after t that may stay in flight
-        if (younger >= 2) wait_vmcnt<2 * GPS>();
-        else if (younger == 1) wait_vmcnt<GPS>();
-        else wait_vmcnt<0>();
-    };
-    auto stage = [&](int t) {
-        const int slot = t % STAGES;
-        stage_rows8_ring<BMB, BKT>(A, K, m0, t * BKT, smem + slot * SB, wave, lane);
-        stage_rows8_ring<BNB, BKT>(Wt, K, n0, t * BKT, smem + slot * SB + TA, wave, lane);
-    };
-#pragma unroll
-    for (int t = 0; t < STAGES - 1; ++t)
-        if (t < nk) stage(t);
-    int issued = (nk < STAGES - 1 ? nk : STAGES - 1) - 1;    // newest tile whose DMAs this wave has issued
-    // tile 0 -> registers (both groups at the same barrier; the late group then falls one barrier behind)
-    wait_tile(0, issued);
-    __builtin_amdgcn_s_barrier();
-    const int chunk = lane >> 4;
-    bf16x8 wf[NT], wfn[NT], af[MI];
-    {
-        const unsigned char* At = smem;
-        const unsigned char* Bt = At + TA;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) wf[j] = lds_frag_ring<BKT>(Bt, wn * 64 + j * 16 + (lane & 15), chunk);
-#pragma unroll
-        for (int i = 0; i < MI; ++i) af[i] = lds_frag_ring<BKT>(At, wm * WROWS + i * 16 + (lane & 15), chunk);
-    }
-    if (late) {
-        wait_tile(1 < nk ? 1 : 0, issued);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-        const bool more = kt + 1 < nk;
-        // ---- L part: barrier, then refill the slot of tile kt-1
-        if (more) wait_tile(kt + 1, issued);
-        __builtin_amdgcn_s_barrier();                                   // Ba(kt)
-        __builtin_amdgcn_sched_barrier(0);
-        if (kt + STAGES - 1 < nk) { stage(kt + STAGES - 1); issued = kt + STAGES - 1; }   // slot of tile kt-1 (kt = 0: unused so far)
-        if (more) wait_tile(kt + 1, issued);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // my reads of tile kt (and older) are complete
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();                                   // Bb(kt)
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- M part: 32 MFMAs on tile kt, the 12 fragment reads of tile kt+1 between them
-        const unsigned char* At = smem + ((kt + 1) % STAGES) * SB;
-        const unsigned char* Bt = At + TA;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-            if (more) {
-                af[i] = lds_frag_ring<BKT>(At, wm * WROWS + i * 16 + (lane & 15), chunk);
-                // the column fragments of the next tile behind the first MFMAs (the compiler guards the first MFMA of
-                // the cluster with lgkmcnt(0): nothing new may be outstanding there)
-                if (i < NT) wfn[i] = lds_frag_ring<BKT>(Bt, wn * 64 + i * 16 + (lane & 15), chunk);
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
-        if (more) {
-#pragma unroll
-            for (int j = 0; j < NT; ++j) wf[j] = wfn[j];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if (!late) __builtin_amdgcn_s_barrier();
-    constexpr bool BF16OUT = bf16_out(MODE);
-    if (BF16OUT) {
-        __syncthreads();  // both groups are past their last fragment read: the ring is dead
-        epilogue_big_lds<MODE, MI>(acc, bias, reinterpret_cast<bf16_t*>(out), N, m0, n0, wm, wn, lane, wave, smem);
-    } else {
-        __syncthreads();
-        epilogue_f32_lds_wave<MODE, MI, NT>(acc, bias, reinterpret_cast<float*>(out), N, m0 + wm * WROWS, n0 + wn * 64,
-                                            lane, smem + wave * 16384);
-    }
-}
-
-template <int MODE>
-static void launch_pp2(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
-                       hipStream_t st) {
-    auto kern = gemm_pp2_kernel<MODE>;
-    const size_t lds = (size_t)4 * (256 + 256) * 32 * 2;  // 128 KiB
-    static PerDeviceOnce attr_set;
-    attr_set([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
-    });
-    const int grid = (M / 256) * (N / 256);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, Wt, bias, M, N, K, out);
-}
-
-#endif  // WISE_DEBUG_KNOBS
-
-template <int MODE, int WROWS, int STG = 0, bool MF32 = false>
+template <int MODE, int WROWS>
 static void launch_pp(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, void* out,
                       hipStream_t st) {
-    auto kern = gemm_pp_kernel<MODE, WROWS, STG, MF32>;
-    constexpr int BNB = (WROWS == 64 || WROWS == 80) ? 128 : 256;
-    constexpr int BMB = (WROWS == 64) ? 256 : (WROWS == 80) ? 320 : 2 * WROWS;
-    constexpr int STAGES = STG ? STG : ((WROWS == 64) ? 5 : 4);
-    const size_t lds = (size_t)STAGES * (BMB + BNB) * 32 * 2;  // 128 KiB / 120 KiB / 144 KiB
+    auto kern = gemm_pp_kernel<MODE, WROWS>;
+    constexpr int BNB = (WROWS == 80) ? 128 : 256;
+    constexpr int BMB = (WROWS == 80) ? 320 : 2 * WROWS;
+    const size_t lds = (size_t)4 * (BMB + BNB) * 32 * 2;  // 128 KiB / 112 KiB / 144 KiB
     static PerDeviceOnce attr_set;
     attr_set([&] {
         raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
@@ -2100,15 +1825,12 @@ static void launch_pp(const bf16_t* A, const bf16_t* Wt, const float* bias, int 
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, st, A, Wt, bias, M, N, K, out);
 }
 
-static int g_gemm_variant = 0;
-static int g_tile320 = 1;  // allow the 320x256 ping-pong tiling (wise_debug_set_gemm_flags bit 0 turns it off)
-static int g_mlp96_resident = 1;  // (debug knob) 0: the staged mlp96_kernel
+#ifdef WISE_DEBUG_KNOBS
+static int g_gemm_variant = 0;   // wise_debug_set_gemm_variant: a variant id forced for A/B runs (tools/gemm_bench.py)
+#else
+constexpr int g_gemm_variant = 0;
+#endif
 static thread_local int g_overlapped = 0;  // the calling thread is running another stream's kernels beside this one (gemm_set_overlapped)
-static int g_overlap_policy = 0;  // (debug knob) tiles under overlap: 0 = as for a lone stream minus the 320-row tilings (the product), 1 = 128x128 only, 2 = 128x128 except the QKV-shaped launches, 3 = hint ignored
-static int g_splitk_policy = 0;  // (debug knob) skinny GEMMs: 0 = the product rule, 1 = split-K for the residual GEMMs only, 2 = never
-static int g_w4_enabled = 1;  // (debug knob, bit 28 of wise_debug_set_gemm_variant: off) the one-wave-per-SIMD kernel of gemm_w4.h
-static int g_split_m = 1;  // split M between the ping-pong kernel and the 128x128 kernel (bit 29 of the knob: off)
-  // 0: 2-stage BK=64 ; 1: ring BK=32 x4 (2 blocks/CU) ; 2: ring BK=64 x4 (1 block/CU) ; 3: ring BK=64 x3
 
 // compute units of the current device (the persistent kernel's grid), asked once per device
 static int device_cus() {
@@ -2124,88 +1846,35 @@ static int device_cus() {
     return cus[dev];
 }
 
+// launches variant v as resolve_variant() returned it (the shape fits)
 template <int MODE>
-static void launch_variant(int variant, const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K,
+static void launch_variant(int v, const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K,
                            void* out, hipStream_t st) {
-    // 0: 128x128, two blocks per CU.  1: 128x128 ring with 32-deep K-tiles (K % 64 != 0).  5: 256x192.
-    // 40 / 42: 256x256 / 320x256 ping-pong.  41: 256x128 ping-pong.  8 / 9: timing-only ablations of variant 0.
-    // Shapes a variant cannot tile fall back to variant 0.
-    switch (variant) {
+    switch (v) {
         case 1: launch_ring<MODE, 32, 4, 2>(A, Wt, bias, M, N, K, out, st); break;
         case 2: launch_ring<MODE, 64, 4, 1>(A, Wt, bias, M, N, K, out, st); break;   // skinny problems: 4 K-tiles of 64 in flight per block
-        case 5: if (M % 256 == 0 && N % 192 == 0) { launch_big<MODE, 3>(A, Wt, bias, M, N, K, out, st); break; }
-                launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 6: if (MODE == EPI_RESID && M % 256 == 0 && N % 192 == 0) { launch_big_pre<MODE, 3>(A, Wt, bias, M, N, K, out, st); break; }
-                launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 40: if (M % 256 == 0 && N % 256 == 0) { launch_pp<MODE, 128>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-#ifdef WISE_DEBUG_KNOBS
-        case 45: if (M % 256 == 0 && N % 256 == 0) { launch_pp<MODE, 128, 5>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 46: if (M % 256 == 0 && N % 128 == 0) { launch_pp<MODE, 64, 3>(A, Wt, bias, M, N, K, out, st); break; }   // 72 KiB: two blocks per CU
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 47: if (M % 256 == 0 && N % 256 == 0 && K >= 192) { launch_ppb<MODE>(A, Wt, bias, M, N, K, out, st); break; }   // W fragments straight to registers
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 48: if (M % 256 == 0 && N % 256 == 0) { launch_pp<MODE, 128, 0, true>(A, Wt, bias, M, N, K, out, st); break; }   // TIMING ONLY: 32x32x16 MFMAs
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-#endif
-#ifdef WISE_DEBUG_KNOBS
-        case 50: if (M % 256 == 0 && N % 256 == 0 && K >= 96) { launch_pp2<MODE>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-#endif
-        case 44: if (M % 320 == 0 && N % 128 == 0) { launch_pp<MODE, 80>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 41: if (M % 256 == 0 && N % 128 == 0) { launch_pp<MODE, 64>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 42: if (M % 320 == 0 && N % 256 == 0) { launch_pp<MODE, 160>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        // 60 .. 63: the one-wave-per-SIMD kernel (gemm_w4.h), 256 x 256 / 160 x 256 / 320 x 256 / 320 x 192 tiles
-        case 60: if (w4_shape_ok(M, N, K, 8)) { launch_w4<MODE, 8, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 61: if (w4_shape_ok(M, N, K, 5)) { launch_w4<MODE, 5, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 62: if constexpr (bf16_out(MODE)) {   // (the fp32 epilogues of a 320-row tile spill: bf16 outputs only)
-                     if (w4_shape_ok(M, N, K, 10)) { launch_w4<MODE, 10, 8, 2, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 63: if constexpr (bf16_out(MODE)) {
-                     if (w4_shape_ok(M, N, K, 10, 6)) { launch_w4<MODE, 10, 6, 2, 3>(A, Wt, bias, M, N, K, out, st); break; }
-                 }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        // 65: 224 x 192 tiles (M = 12544 = 49 x 256 rows of a ViT-B/32 patch matrix: 56 x 4 = 224 tiles, one round)
-        case 65: if (w4_shape_ok(M, N, K, 7, 6)) { launch_w4<MODE, 7, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        // 66 .. 68: 256 x 192, 128 x 192, 128 x 256 tiles — row counts that are powers of two (MS-CLAP HTSAT: 131072 / 32768 /
-        // 8192 tokens at 128 clips) and widths of 192 k (its C = 192, 384, 768 and their multiples)
-        case 66: if (w4_shape_ok(M, N, K, 8, 6)) { launch_w4<MODE, 8, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 67: if (w4_shape_ok(M, N, K, 4, 6)) { launch_w4<MODE, 4, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 68: if (w4_shape_ok(M, N, K, 4, 8)) { launch_w4<MODE, 4, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        // 69, 70: 128 x 192 (2 + 2 slots) and 128 x 128 tiles with TWO workgroups per CU (80 KiB of LDS, <= 256 registers per
-        // wave): one workgroup's prologue and epilogue run under the other's K-loop — short-K shapes, where a tile is
-        // mostly prologue and epilogue
-        case 69: if (w4_shape_ok(M, N, K, 4, 6)) { launch_w4<MODE, 4, 6, 2, 2, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 70: if (w4_shape_ok(M, N, K, 4, 4)) { launch_w4<MODE, 4, 4, 3, 2, 2>(A, Wt, bias, M, N, K, out, st); break; }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        // 64: its persistent form (160 x 256 tiles, the C tile leaves during the next tile's loop), bf16 outputs
-        case 64: if constexpr (bf16_out(MODE)) {
-                     if (w4p_shape_ok(M, N, K)) { launch_w4p<MODE>(A, Wt, bias, M, N, K, out, device_cus(), st); break; }
-                 }
-                 launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
-        case 8: launch_gemm<MODE, 1>(A, Wt, bias, M, N, K, out, st); break;
-        case 9: launch_gemm<MODE, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 5: launch_big<MODE, 3>(A, Wt, bias, M, N, K, out, st); break;
+        case 40: launch_pp<MODE, 128>(A, Wt, bias, M, N, K, out, st); break;
+        case 42: launch_pp<MODE, 160>(A, Wt, bias, M, N, K, out, st); break;
+        case 44: launch_pp<MODE, 80>(A, Wt, bias, M, N, K, out, st); break;
+        case 60: launch_w4<MODE, 8, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 61: launch_w4<MODE, 5, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 62: if constexpr (bf16_out(MODE)) launch_w4<MODE, 10, 8, 2, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 63: if constexpr (bf16_out(MODE)) launch_w4<MODE, 10, 6, 2, 3>(A, Wt, bias, M, N, K, out, st); break;
+        case 64: if constexpr (bf16_out(MODE)) launch_w4p<MODE>(A, Wt, bias, M, N, K, out, device_cus(), st); break;
+        case 65: launch_w4<MODE, 7, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 66: launch_w4<MODE, 8, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 67: launch_w4<MODE, 4, 6, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 68: launch_w4<MODE, 4, 8, 3, 2>(A, Wt, bias, M, N, K, out, st); break;
+        // (69, 70: two workgroups per CU, 80 KiB of LDS: one workgroup's prologue and epilogue run under the other's K-loop)
+        case 69: launch_w4<MODE, 4, 6, 2, 2, 2>(A, Wt, bias, M, N, K, out, st); break;
+        case 70: launch_w4<MODE, 4, 4, 3, 2, 2>(A, Wt, bias, M, N, K, out, st); break;
         default: launch_gemm<MODE>(A, Wt, bias, M, N, K, out, st); break;
     }
 }
 
 static int launch_mode(int v, const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, int mode,
                        void* out, hipStream_t st) {
-    if (v >= 60 && v <= 70) { /* gemm_w4.h checks its own shape */ }
-    else if (K % 64 != 0 && v != 40 && v != 42 && v != 45 && v != 46 && v != 48 && v != 50) v = 1;
-    else if (N % BN != 0 && v != 1) v = 0;  // N edge is handled by the 128x128 kernels only
     switch (mode) {
         case EPI_BF16: launch_variant<EPI_BF16>(v, A, Wt, bias, M, N, K, out, st); break;
         case EPI_QUICKGELU: launch_variant<EPI_QUICKGELU>(v, A, Wt, bias, M, N, K, out, st); break;
@@ -2220,119 +1889,36 @@ static int launch_mode(int v, const bf16_t* A, const bf16_t* Wt, const float* bi
     return WISE_OK;
 }
 
-// shape heuristic (measured with tools/gemm_bench.py on MI355X)
-static int auto_variant(int M, int N, int K) {
-    if (K % 64 != 0) return 1;  // K multiple of 32 only (HTSAT C=96): the BK=32 ring kernel
-    // Skinny problems (a text query: 77 rows against [N, K] weights; the heads of the towers): fewer blocks than CUs, each
-    // streaming its own slab of the weights from HBM over a long K — latency-bound with one K-tile in flight (12800x...
-    // shapes never come here).  The ring kernel keeps four 64-deep K-tiles in flight per block: 256x1024x4096 57 -> 19 us.
-    if ((long long)(M / 128) * ((N + 127) / 128) <= 128 && K >= 512) return 2;
-    // when a 256x192 tiling fits the chip in ONE well-filled round it beats 128x128 (fewer staged bytes, no
-    // second-round tail); otherwise the 128x128 tile at two blocks per CU wins because its epilogue overlaps
-    // the other block's main loop
-    const long long t5 = (long long)(M / 256) * (N / 192);
-    if (M % 256 == 0 && N % 192 == 0 && t5 <= 256 && t5 >= 160) return 5;
-    return 0;
+// the tiled launches of a plan, one after the other on the stream
+static int launch_tiles(const GemmPlan& p, const bf16_t* A, const bf16_t* Wt, const float* bias, int N, int K, int mode,
+                        void* out, hipStream_t st) {
+    int M = 0;
+    for (int i = 0; i < p.n; ++i) M += p.rows[i];
+    ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K, st);
+    const size_t esz = (mode == EPI_RESID || mode == EPI_F32) ? 4 : 2;
+    for (int i = 0, m0 = 0; i < p.n; m0 += p.rows[i], ++i)
+        if (const int rc = launch_mode(p.v[i], A + (size_t)m0 * K, Wt, bias, p.rows[i], N, K, mode,
+                                       reinterpret_cast<unsigned char*>(out) + (size_t)m0 * N * esz, st))
+            return rc;
+    return WISE_OK;
 }
 
 void gemm_set_overlapped(bool on) { g_overlapped = on ? 1 : 0; }
-
-// The one-wave-per-SIMD kernel (gemm_w4.h) takes every problem it can tile into at least ~3/4 of a round of the 256 CUs.
-// Among its tiles the model is rounds x (prologue + K-steps x cycles per step + epilogue) with the cycles its in-kernel
-// stamps show on MI355X (tools/gemm_lab.hip; the loops run at 76-79 % of the MFMA rate: 160 x 256 ~1700 cycles per
-// 64-deep step, 256 x 256 ~2560, 320 x 192 ~2430, 320 x 256 ~3250; prologue ~3200); the epilogue is bound by the HBM
-// traffic of the C tile, i.e. proportional to the tile's area whatever its shape, so it only enters through the
-// rounds.  Returns the variant id (60 .. 63) or 0.
-static int w4_variant(int M, int N, int K, int mode) {
-    // (K >= 192: three 64-deep K-steps.  Short K used to stay with the two-blocks-per-CU kernels; on the HTSAT shapes —
-    // K = 192 / 384 at 131072 / 32768 rows — these tiles measured 5-25 % faster than those: tools/gemm_lab.hip htsat)
-    if (!g_w4_enabled || K < 192) return 0;
-    // Short K (HTSAT's stages: K = 192 / 384, and K = 768 on its 8192-row stage): a tile is a handful of K-steps between a
-    // prologue and an epilogue that one workgroup per CU cannot overlap with anything.  Two workgroups of 128 x 192 (or
-    // 128 x 128) per CU can: measured 7-22 % faster than the best single tile on the bf16-output shapes and 3-7 % on the
-    // residual ones at K <= 384 (profiles/r03_gemm_lab_htsat_two_per_cu.txt); at K >= 768 with many rows the small tiles
-    // are LDS-bound and lose to the large ones (ViT-B/32: same file, vit section), so the rule stops there.
-    // (K = 512, the CLIP text tower at 256 queries x 77 tokens: QKV 37.3 -> 35.0 us, out-projection 26.4 -> 21.9, fc1
-    // 62.9 -> 49.5 — `tools/gemm_lab text`.)
-    if ((K <= 512 || (K <= 768 && M <= 8192 && bf16_out(mode))) && !(bf16_out(mode) && w4p_shape_ok(M, N, K))) {
-        if (w4_shape_ok(M, N, K, 4, 6) && (long long)(M / 128) * (N / 192) >= 512) return 69;
-        if (w4_shape_ok(M, N, K, 4, 4) && (long long)(M / 128) * (N / 128) >= 512) return 70;
-    }
-    // (Measured and not taken: the same two-per-CU tiles on the output projections of the wide towers — N = K = 1024, fp32
-    // residual: 219 -> 194 us alone on ViT-L/14's shape, but no gain in the tower's step with two batches in flight.)
-    struct Cand { int id, mi, nj; double step; bool bf16_only; };
-    static const Cand cands[] = {{60, 8, 8, 2560.0, false}, {61, 5, 8, 1700.0, false}, {62, 10, 8, 3250.0, true},
-                                 {63, 10, 6, 2430.0, true}, {65, 7, 6, 1720.0, false}, {66, 8, 6, 1950.0, false},
-                                 {67, 4, 6, 1100.0, false}, {68, 4, 8, 1360.0, false}};
-    double best = 0.0;
-    int v = 0;
-    // The model ranks w4 tiles against each other; it knows nothing of the two-blocks-per-CU kernels.  So the tiles added
-    // for HTSAT (66 .. 68) compete only where the choice is inside the family already — one of the older tiles divides the
-    // shape — or K < 512, where they were measured against those kernels.  (ViT-L/14 and H/14, M = 129 x 128 and 65 x 128
-    // rows with K >= 1024, fit only the new tiles and lose 5 % on them: they stay where they were.)
-    // (... or the row count is a multiple of 4096 — HTSAT's token counts — where the new tiles were measured against those
-    // kernels on every shape: its stage-3 fc2, 32768 x 384 x 1536, has no older tile that divides N = 384: 58 -> 47 us)
-    bool family = K < 512 || M % 4096 == 0;
-    for (const Cand& c : cands)
-        if (c.id <= 65 && !(c.bf16_only && !bf16_out(mode)) && w4_shape_ok(M, N, K, c.mi, c.nj)) family = true;
-    for (const Cand& c : cands) {
-        if (c.id > 65 && !family) continue;
-        if (c.bf16_only && !bf16_out(mode)) continue;
-        if (!w4_shape_ok(M, N, K, c.mi, c.nj)) continue;
-        const long long tiles = (long long)(M / (32 * c.mi)) * (N / (32 * c.nj));
-        if (tiles < 192) continue;
-        const long long rounds = (tiles + 255) / 256;
-        const double epilogue = 10500.0 * (c.mi * c.nj / 64.0) * (bf16_out(mode) ? 1.0 : 2.0);
-        const double act = (mode == EPI_QUICKGELU || mode == EPI_GELU || mode == EPI_GELU_TANH) ? 5000.0 * (c.mi * c.nj / 40.0) : 0.0;
-        // operands beyond what the caches hold (> 64 MB): every CU streams its K-steps from the memory side, and a step
-        // cannot be shorter than its bytes at ~28 B per clock and CU (measured: 128 x 256 tiles 1360 -> 1640 cycles per
-        // step on ViT-L/14's fc2, 160 x 256 1700 -> 1950 on ViT-B/32's; 256 x 256, fewer bytes per flop, unchanged)
-        const bool streams = ((double)M + (double)N) * (double)K * 2.0 > 64.0e6;
-        const double step_bytes = (32.0 * c.mi + 32.0 * c.nj) * 128.0;
-        const double step = streams && step_bytes / 28.0 > c.step ? step_bytes / 28.0 : c.step;
-        const double cost = (double)rounds * (3200.0 + (K / 64) * step + epilogue + act);
-        if (v == 0 || cost < best) { best = cost; v = c.id; }
-    }
-    // the persistent form: no prologue between tiles, the C tile leaves under the next tile's loop; what stays exposed per
-    // tile is the packing of the accumulators (~1.9k cycles, ~6.2k with a sigmoid-shaped activation) and ~1.7k of drain
-    if (bf16_out(mode) && w4p_shape_ok(M, N, K)) {
-        const long long tiles = (long long)(M / 160) * (N / 256);
-        const int cus = device_cus();
-        if (tiles >= cus) {
-            const long long rounds = (tiles + cus - 1) / cus;
-            const double pack = (mode == EPI_QUICKGELU || mode == EPI_GELU || mode == EPI_GELU_TANH) ? 6200.0 : 1900.0;
-            const bool streams = ((double)M + (double)N) * (double)K * 2.0 > 64.0e6;
-            const double cost = 3200.0 + (double)rounds * ((K / 64) * (streams ? 1902.0 : 1660.0) + 1700.0 + pack) + 5000.0;
-            if (v == 0 || cost < best) { best = cost; v = 64; }
-        }
-    }
-    return v;
-}
 
 // x[M,96] += fc2(gelu(fc1(LN(x)))) in one kernel; M % 128 == 0 (rows readable and writable)
 int mlp96_fused(float* x, const float* lnw, const float* lnb, const bf16_t* W1, const float* b1, const bf16_t* W2,
                 const float* b2, int M, float eps, hipStream_t st) {
     WISE_CHECK_ARG(x && lnw && lnb && W1 && b1 && W2 && b2 && M > 0 && M % 128 == 0, "mlp96: bad argument (M=%d)", M);
     ProfScope prof(PROF_GEMM, 4.0 * (double)M * 96.0 * 384.0, st);
-    if (g_mlp96_resident) {
-        const size_t ldsr = (size_t)MLPR_W1_BYTES + MLPR_W2_BYTES + (384 + 3 * 96) * sizeof(float);   // 150 KiB
-        static PerDeviceOnce attr_r;
-        attr_r([&] {
-            raise_lds_limit(reinterpret_cast<const void*>(mlp96r_kernel), (int)ldsr);
-        });
-        const long long units = M / 32;
-        const int grid = units < 8 * 256 ? (int)((units + 7) / 8) : 256;
-        hipLaunchKernelGGL(mlp96r_kernel, dim3(grid), dim3(512), ldsr, st, x, lnw, lnb, W1, b1, W2, b2, units, eps);
-        WISE_LAUNCH_CHECK("mlp96r_kernel");
-        return WISE_OK;
-    }
-    const size_t lds = (size_t)9 * 128 * 64;  // 72 KiB
-    static PerDeviceOnce attr_set;
-    attr_set([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(mlp96_kernel), (int)lds);
+    const size_t ldsr = (size_t)MLPR_W1_BYTES + MLPR_W2_BYTES + (384 + 3 * 96) * sizeof(float);   // 150 KiB
+    static PerDeviceOnce attr_r;
+    attr_r([&] {
+        raise_lds_limit(reinterpret_cast<const void*>(mlp96r_kernel), (int)ldsr);
     });
-    hipLaunchKernelGGL(mlp96_kernel, dim3(M / 128), dim3(256), lds, st, x, lnw, lnb, W1, b1, W2, b2, eps);
-    WISE_LAUNCH_CHECK("mlp96_kernel");
+    const long long units = M / 32;
+    const int grid = units < 8 * 256 ? (int)((units + 7) / 8) : 256;
+    hipLaunchKernelGGL(mlp96r_kernel, dim3(grid), dim3(512), ldsr, st, x, lnw, lnb, W1, b1, W2, b2, units, eps);
+    WISE_LAUNCH_CHECK("mlp96r_kernel");
     return WISE_OK;
 }
 
@@ -2359,31 +1945,12 @@ int gemm_ln_bf16(const float* x, const float* lnw, const float* lnb, const bf16_
     return WISE_OK;
 }
 
-// fp32 scratch of the split-K path: a pool of eight buffers allocated together on the first skinny launch of the process
-// (outside any graph capture: the engines warm up before they capture); a stream is bound to one of them the first time it
-// takes the path — no allocation then, so a capture stream may be new — and a ninth stream gets the ordinary kernels.
-constexpr size_t SPLITK_SCRATCH_CAP = (size_t)24 << 20;   // a GEMM whose partials would not fit is not split
-
 template <int MODE>
 static void launch_reduce(const float* part, int S, int rows, int N, const float* bias, void* out, hipStream_t st) {
     const int total = rows * (N / 4);
     hipLaunchKernelGGL(splitk_reduce_kernel<MODE>, dim3((total + 255) / 256), dim3(256), 0, st, part, S, rows, N, bias, out);
 }
 
-// rows 0..m_valid-1 (<= 128) of A @ Wt^T through the split-K pair of kernels; false = not applicable here
-// slices of K for a skinny problem (0: not a split-K case) and the launch of the partial-tile kernel
-static int splitk_slices(int M, int m_valid, int N, int K) {
-    if (m_valid < 1 || m_valid > 128 || M < 128 || K < 512 || K % 128 != 0 || N % 128 != 0 || N < 128) return 0;
-    const int slabs = N / 128;
-    int S = 1;
-    for (int c : {2, 4, 8, 16, 32}) {     // slices: enough blocks for the chip, at least two K-tiles per slice
-        if (K % (c * 64) != 0 || K / c < 128) break;
-        S = c;
-        if (slabs * c >= 160) break;
-    }
-    if (S < 2 || (size_t)S * 128 * N * sizeof(float) > SPLITK_SCRATCH_CAP) return 0;
-    return S;
-}
 size_t gemm_splitk_bytes(int M, int m_valid, int N, int K) {
     return (size_t)splitk_slices(M, m_valid, N, K) * 128 * (size_t)N * sizeof(float);
 }
@@ -2397,10 +1964,11 @@ static void splitk_partials(const bf16_t* A, const bf16_t* Wt, int N, int K, int
     hipLaunchKernelGGL(gemm_splitk_kernel<STAGES>, dim3(N / 128, S), dim3(256), lds, st, A, Wt, N, K, K / S, part);
 }
 
-static bool gemm_splitk(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int m_valid, int N, int K, int mode,
+// rows 0..m_valid-1 (<= 128) of A @ Wt^T through the split-K pair of kernels, S slices of K, the partials in the caller's
+// fp32 scratch `part`; false = the scratch is missing or too small for this call.
+static bool gemm_splitk(const bf16_t* A, const bf16_t* Wt, const float* bias, int S, int m_valid, int N, int K, int mode,
                         void* out, hipStream_t st, float* part, size_t part_bytes) {
-    const int S = splitk_slices(M, m_valid, N, K);
-    if (S == 0 || !part || part_bytes < (size_t)S * 128 * N * sizeof(float)) return false;
+    if (!part || part_bytes < (size_t)S * 128 * N * sizeof(float)) return false;
     ProfScope prof(PROF_GEMM, 2.0 * (double)m_valid * (double)N * (double)K, st);
     splitk_partials(A, Wt, N, K, S, part, st);
     switch (mode) {
@@ -2414,20 +1982,18 @@ static bool gemm_splitk(const bf16_t* A, const bf16_t* Wt, const float* bias, in
     return true;
 }
 
-int gemm_bf16(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, int mode, void* out, hipStream_t st);
-
 // m_valid: the rows of A that carry data (the rest of the M rows are padding whose results nobody reads)
 int gemm_bf16_rows(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int m_valid, int N, int K, int mode,
                    void* out, hipStream_t st, float* sk, size_t sk_bytes) {
     WISE_CHECK_ARG(A && Wt && out, "gemm_bf16: null pointer");
     WISE_CHECK_ARG(M > 0 && M % BM == 0 && N > 0 && N % 4 == 0 && K > 0 && K % 32 == 0 && mode >= 0 && mode <= 6,
                    "gemm_bf16: M=%d must be a multiple of %d, N=%d of 4, K=%d of 32", M, BM, N, K);
-    if (g_gemm_variant == 0 && m_valid <= 128 && g_splitk_policy != 2 && !(g_splitk_policy == 1 && mode != EPI_RESID) &&
-        gemm_splitk(A, Wt, bias, M, m_valid, N, K, mode, out, st, sk, sk_bytes)) {
+    const GemmPlan p = gemm_plan(M, N, K, mode, m_valid, g_overlapped != 0, device_cus(), g_gemm_variant);
+    if (p.splitk && gemm_splitk(A, Wt, bias, p.splitk, m_valid, N, K, mode, out, st, sk, sk_bytes)) {
         WISE_LAUNCH_CHECK("gemm_splitk_kernel");
         return WISE_OK;
     }
-    return gemm_bf16(A, Wt, bias, M, N, K, mode, out, st);
+    return launch_tiles(p, A, Wt, bias, N, K, mode, out, st);
 }
 
 // x[M,N] += A @ Wt^T + bias (the residual GEMM of a block), then the LayerNorm that follows it: h = LN(x) as bf16, and for
@@ -2438,8 +2004,10 @@ int gemm_resid_ln_rows(const bf16_t* A, const bf16_t* Wt, const float* bias, int
                        float* x, const float* ln_w, const float* ln_b, float eps, bool post_ln, bf16_t* h, hipStream_t st,
                        float* sk, size_t sk_bytes) {
     WISE_CHECK_ARG(A && Wt && x && ln_w && ln_b && h, "gemm_resid_ln: null pointer");
-    // (ln_rows: the rows the LayerNorm covers — the caller's real rows; m_valid may include tile padding)
-    const int S = (g_gemm_variant == 0 && g_splitk_policy != 2 && N > 128 && N <= 4096 && ln_rows == m_valid) ? splitk_slices(M, m_valid, N, K) : 0;
+    // (ln_rows: the rows the LayerNorm covers — the caller's real rows; m_valid may include tile padding.  The fused
+    // reduction holds a row of up to 4096 columns.)
+    const GemmPlan p = gemm_plan(M, N, K, EPI_RESID, m_valid, g_overlapped != 0, device_cus(), g_gemm_variant);
+    const int S = (N > 128 && N <= 4096 && ln_rows == m_valid) ? p.splitk : 0;
     float* part = (S && sk && sk_bytes >= (size_t)S * 128 * N * sizeof(float)) ? sk : nullptr;
     if (part) {
         {
@@ -2468,78 +2036,8 @@ int gemm_bf16(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N
     WISE_CHECK_ARG(A && Wt && out, "gemm_bf16: null pointer");
     WISE_CHECK_ARG(M > 0 && M % BM == 0 && N > 0 && N % 4 == 0 && K > 0 && K % 32 == 0,
                    "gemm_bf16: M=%d must be a multiple of %d, N=%d of 4, K=%d of 32", M, BM, N, K);
-    ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K, st);
-    int v = g_gemm_variant;
-    if (v == 100) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);  // force 128x128 (A/B runs)
-    if (v != 0) return launch_mode(v, A, Wt, bias, M, N, K, mode, out, st);
-    // Two whole batches in flight on two streams (VitEngine.forward_pipelined brackets its calls with wise_overlap_hint):
-    // measured in one process (tools/vit_variant_pipe.py, ViT-B/32 bs=256): hint ignored 3.28 ms per step; the lone-stream
-    // heuristic minus the 320-row tilings (policy 0, what follows below) 3.16; 128x128 everywhere (policy 1) 3.20.
-    if (g_overlap_policy == 3) {   // (debug) ignore the hint altogether
-        const int keep = g_overlapped;
-        g_overlapped = 0;
-        g_overlap_policy = 0;
-        const int rc3 = gemm_bf16(A, Wt, bias, M, N, K, mode, out, st);
-        g_overlap_policy = 3;
-        g_overlapped = keep;
-        return rc3;
-    }
-    if (const int vw = w4_variant(M, N, K, mode)) return launch_mode(vw, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 1) return launch_mode(auto_variant(M, N, K) == 2 ? 2 : 0, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 2 && !(bf16_out(mode) && N >= 3 * K)) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 4 && (mode == EPI_RESID || mode == EPI_F32)) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 5 && bf16_out(mode) && N == 4 * K) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 6 && bf16_out(mode) && N == 3 * K) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);
-    if (g_overlapped && g_overlap_policy == 7 && bf16_out(mode) && N >= 3 * K) return launch_mode(0, A, Wt, bias, M, N, K, mode, out, st);
-
-    // Tile quantisation decides between the ping-pong tilings: 6400 x 3072 is 300 tiles of 256x256 (two rounds
-    // at 59 %) but 240 tiles of 320x256 (one round at 94 %); measured 694 -> 799 TFLOP/s on that shape.
-    // (not when the caller overlaps two streams: a 144-KiB one-block-per-CU kernel leaves the other stream's
-    // kernels nowhere to run, measured 3.54 -> 3.74 ms per ViT-B/32 step)
-    if (g_tile320 && !g_overlapped && M % 320 == 0 && N % 256 == 0) {
-        const long long t320 = (long long)(M / 320) * (N / 256), t256 = (long long)(M / 256) * (N / 256);
-        const double eff320 = (double)t320 / (double)(((t320 + 255) / 256) * 256);
-        const double eff256 = (M % 256 == 0) ? (double)t256 / (double)(((t256 + 255) / 256) * 256) : 0.0;
-        if (t320 >= 200 && eff320 >= 0.90 && eff320 > eff256 + 0.04)
-            return launch_mode(42, A, Wt, bias, M, N, K, mode, out, st);
-    }
-    // fp32-output GEMMs with a narrow N (the two residual GEMMs of a ViT-B block, N = 768): 320 x 128 tiles of the
-    // ping-pong kernel when they fill the chip's 256 CUs almost exactly (12800 x 768: 240 tiles, against 200 tiles of
-    // 256 x 192 with a quarter more work each): 12800 x 768 x 3072 77 -> 70 us, x 768 32.6 -> 30.7 us
-    if ((mode == EPI_RESID || mode == EPI_F32) && g_tile320 && !g_overlapped && M % 320 == 0 && N % 128 == 0 && K >= 128) {
-        const long long t = (long long)(M / 320) * (N / 128);
-        const double eff = (double)t / (double)(((t + 255) / 256) * 256);
-        if (t >= 200 && t <= 256 && eff >= 0.90) return launch_mode(44, A, Wt, bias, M, N, K, mode, out, st);
-    }
-    // The 256x256 ping-pong kernel (one block per CU) has the fastest main loop but no co-resident block to
-    // hide its epilogue or its tail.  Give it the rows whose tiles fill whole rounds of the 256 CUs and hand the
-    // remaining rows to the two-blocks-per-CU kernels (same stream, so the two launches are ordered).
-    if (M % 256 == 0 && N % 256 == 0) {
-        const int tiles_m = M / 256, tiles_n = N / 256;
-        const long long t256 = (long long)tiles_m * tiles_n;
-        const double eff256 = (double)t256 / (double)(((t256 + 255) / 256) * 256);
-        // (K < 512: a tile is 6-12 K-steps and its epilogue — the activation above all — is most of its life; the
-        // 128x128 kernel's second block per CU covers it: 131072x768x192 with GELU 120 -> 106 us, 32768x1536x384 79 -> 75)
-        if (t256 >= 200 && K >= 512 && (eff256 >= 0.85 || (K >= 2048 && eff256 >= 0.80)))
-            return launch_mode(40, A, Wt, bias, M, N, K, mode, out, st);
-        // (measured: worth it only when the ping-pong part spans several rounds; at 1-2 rounds the second
-        // launch's own tail and the lost overlap cost more than the 128x128 kernel's slower main loop)
-        // ... or from two rounds when what is left over is small (ViT-L/14 half batch: 129 x 4 tiles = 2 rounds + 4)
-        if (t256 >= 2 * 256 && K >= 512 && g_split_m) {
-            const int rounds = (int)(t256 / 256);
-            const int m_pp = (rounds * 256) / tiles_n;  // m-tiles whose tiles fill `rounds` rounds (within one row)
-            const bool small_rest = (tiles_m - m_pp) * 8 <= tiles_m;
-            if (m_pp >= 1 && m_pp < tiles_m && (long long)m_pp * tiles_n >= 200 && (t256 >= 3 * 256 || small_rest)) {
-                const int M1 = m_pp * 256, M2 = M - M1;
-                int rc = launch_mode(40, A, Wt, bias, M1, N, K, mode, out, st);
-                if (rc) return rc;
-                const size_t esz = (mode == EPI_RESID || mode == EPI_F32) ? 4 : 2;
-                return launch_mode(auto_variant(M2, N, K), A + (size_t)M1 * K, Wt, bias, M2, N, K, mode,
-                                   reinterpret_cast<unsigned char*>(out) + (size_t)M1 * N * esz, st);
-            }
-        }
-    }
-    return launch_mode(auto_variant(M, N, K), A, Wt, bias, M, N, K, mode, out, st);
+    return launch_tiles(gemm_plan(M, N, K, mode, 0, g_overlapped != 0, device_cus(), g_gemm_variant), A, Wt, bias, N, K,
+                        mode, out, st);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2550,19 +2048,6 @@ int gemm_bf16(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N
 // M % 128 == 0, N % 128 == 0, K % 64 == 0, K >= 192.  Tiles with 64- or 128-column wave parts only (the statistics' tree).
 // ---------------------------------------------------------------------------------------------------------------------
 bool gemm_fold_shape_ok(int M, int N, int K) { return M > 0 && M % 128 == 0 && N > 0 && (N % 128 == 0 || N % 192 == 0) && K % 64 == 0 && K >= 192; }
-
-static int fold_variant(int M, int N, int K, int mode, bool producer, bool wide96 = false) {
-    const int v = w4_variant(M, N, K, mode);
-    if (v == 61 || v == 68 || v == 70 || ((v == 60 || v == 64) && !producer)) return v;   // (the 256 x 256 residual form with statistics spills)
-    // tiles with 96-column wave parts (256 x 192, 128 x 192, 128 x 192 at two workgroups per CU): any consumer; a producer
-    // only where the model's statistics are kept per 32 columns (FoldArgs.group32: MS-CLAP's HTSAT, widths 192 / 384 / 768)
-    if ((v == 66 || v == 67 || v == 69) && (!producer || wide96)) return v;
-    if (N % 128 != 0) return w4_shape_ok(M, N, K, 4, 6) ? ((long long)(M / 128) * (N / 192) >= 512 ? 69 : 67) : 0;
-    if (!producer && w4p_shape_ok(M, N, K) && (long long)(M / 160) * (N / 256) >= device_cus()) return 64;
-    if (w4_shape_ok(M, N, K, 5, 8) && (long long)(M / 160) * (N / 256) >= 192) return 61;
-    if (w4_shape_ok(M, N, K, 4, 8) && (long long)(M / 128) * (N / 256) >= 256) return 68;
-    return 70;
-}
 
 template <int MODE>
 static void launch_fold_consumer(int v, const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int N, int K, bf16_t* out,
@@ -2586,7 +2071,7 @@ int gemm_fold_bf16(const bf16_t* A, const bf16_t* Wt, const float* bias, const f
     ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K, st);
     FoldArgs fa;
     fa.stats = const_cast<float*>(rstd);
-    const int v = fold_variant(M, N, K, mode, false);
+    const int v = fold_plan(M, N, K, mode, false, false, device_cus());
     WISE_CHECK_ARG(v != 0, "gemm_fold_bf16: no tile for M=%d N=%d K=%d", M, N, K);
     switch (mode) {
         case EPI_BF16: launch_fold_consumer<EPI_BF16>(v, A, Wt, bias, M, N, K, out, fa, st); break;
@@ -2627,16 +2112,13 @@ int gemm_fold_resid(const bf16_t* A, const bf16_t* Wt, const float* bias, int M,
     ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)N * (double)K, st);
     FoldArgs fa;
     fa.hcopy = hi; fa.lo_off = (int)lo_off; fa.stats = stats; fa.eps = eps; fa.group32 = group32 ? 1 : 0;
-    int v = fold_variant(M, N, K, accumulate ? EPI_RESID : EPI_F32, true, group32 != 0);
+    const int v = fold_plan(M, N, K, accumulate ? EPI_RESID : EPI_F32, true, group32 != 0, device_cus());
     WISE_CHECK_ARG(v != 0, "gemm_fold_resid: no tile for M=%d N=%d K=%d", M, N, K);
-    if (!accumulate && v == 61) v = w4_shape_ok(M, N, K, 4, 8) ? 68 : 70;
     if (accumulate) launch_fold_producer<EPI_RESID>(v, A, Wt, bias, M, N, K, fa, st);
     else launch_fold_producer<EPI_F32>(v, A, Wt, bias, M, N, K, fa, st);
     WISE_LAUNCH_CHECK("gemm_w4_kernel (fold, residual)");
     return WISE_OK;
 }
-
-static int g_conv_variant = 0;   // (debug knob) 0 = by shape, 1 = the 128-row tile everywhere, 2 = ping-pong wherever it tiles
 
 template <typename K>
 static void conv_launch(K kern, size_t lds, int grid, int threads, const bf16_t* X, const bf16_t* Wt, const float* bias,
@@ -2667,48 +2149,38 @@ int conv3x3_bf16(const bf16_t* X, const bf16_t* Wt, const float* bias, const bf1
     WISE_CHECK_ARG(X && Wt && bias && zeros && out, "conv3x3: null pointer");
     WISE_CHECK_ARG(B > 0 && T > 0 && F > 0 && Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && (!pool || (T >= 2 && F >= 2)),
                    "conv3x3: B=%d T=%d F=%d Cin=%d Cout=%d unsupported", B, T, F, Cin, Cout);
-    // rows the tiles walk: every cell, or the four members of every pooling window (floor: odd leftovers are not computed)
-    const long long M = pool ? 4ll * B * (T / 2) * (F / 2) : (long long)B * T * F;
+    const long long M = conv_rows(B, T, F, pool);
     WISE_CHECK_ARG((long long)B * T * F * (long long)(Cin > Cout ? Cin : Cout) < (1ll << 40) && (long long)B * T * F < (1ll << 31) - 256,
                    "conv3x3: B=%d T=%d F=%d too large", B, T, F);
     ProfScope prof(PROF_GEMM, 2.0 * (double)M * (double)Cout * 9.0 * (double)Cin, st);
-    const int tiles256 = (int)((M + 255) / 256);
-    // The ping-pong tile (one block per CU) where its tiles fill the chip in well-used rounds — measured per layer with
-    // tools/conv_bench.py (64 clips x 10 s): 1006-1162 against 904-1037 TFLOP/s on blocks 3 and 4 (6 and 3 rounds), 1031-1057
-    // against 978-996 on block 6 (184 tiles, one round), but 947-971 against 1049-1088 on block 5 (372 tiles = 1.45 rounds);
-    // its 256 x 128 form lost everywhere it was tried (block 2: 539-679 against 681-857) and is not used.
-    const long long tpp = (long long)tiles256 * (Cout / 256);
-    const double eff = tpp > 0 ? (double)tpp / (double)(((tpp + 255) / 256) * 256) : 0.0;
-    const bool pp256 = Cout % 256 == 0 && (g_conv_variant == 2 || (g_conv_variant == 0 && tpp >= 160 && eff >= 0.70 && (tpp <= 256 || eff >= 0.85)));
-    if (pp256) {
-        const size_t lds = (size_t)4 * (256 + 256) * 64;   // 128 KiB
-        if (pool) conv_launch(conv3x3_pp_kernel<128, true>, lds, (int)tpp, 512, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-        else conv_launch(conv3x3_pp_kernel<128, false>, lds, (int)tpp, 512, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-        WISE_LAUNCH_CHECK("conv3x3_pp_kernel");
-        return WISE_OK;
-    }
-#ifdef WISE_DEBUG_KNOBS
-    if (g_conv_variant == 2 && Cout % 128 == 0 && !pool) {   // the 256 x 128 form (measured slower; debug library only)
-        conv_launch(conv3x3_pp_kernel<64, false>, (size_t)5 * (256 + 128) * 64, tiles256 * (Cout / 128), 512, X, Wt, bias, zeros, T, F,
-                    Cin, (int)M, Cout, out, st);
-        WISE_LAUNCH_CHECK("conv3x3_pp_kernel");
-        return WISE_OK;
-    }
-#endif
-    const int tiles_m = (int)((M + 127) / 128);
-    if (Cout % 128 == 0) {
-        const size_t lds = 2 * (TILE_BYTES + 128 * BK * 2);   // 64 KiB
-        if (pool) conv_launch(conv3x3_kernel<4, true>, lds, tiles_m * (Cout / 128), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-        else conv_launch(conv3x3_kernel<4, false>, lds, tiles_m * (Cout / 128), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-    } else if (g_conv_variant != 1 && M >= 256 * 512) {
-        // 64-channel steps (block 1 of Cnn14): 256 x 64 tiles, every wave a 64 x 64 sub-tile (tools/conv_bench.py)
-        const size_t lds = 2 * (2 * TILE_BYTES + 64 * BK * 2);    // 80 KiB: two blocks fill a CU's LDS exactly
-        if (pool) conv_launch(conv3x3_kernel<4, true, 4>, lds, tiles256 * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-        else conv_launch(conv3x3_kernel<4, false, 4>, lds, tiles256 * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-    } else {
-        const size_t lds = 2 * (TILE_BYTES + 64 * BK * 2);    // 48 KiB
-        if (pool) conv_launch(conv3x3_kernel<2, true>, lds, tiles_m * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
-        else conv_launch(conv3x3_kernel<2, false>, lds, tiles_m * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+    const int tiles256 = (int)((M + 255) / 256), tiles_m = (int)((M + 127) / 128);
+    switch (conv_plan(M, Cout)) {
+        case CONV_PP256: {
+            const size_t lds = (size_t)4 * (256 + 256) * 64;   // 128 KiB
+            const int grid = tiles256 * (Cout / 256);
+            if (pool) conv_launch(conv3x3_pp_kernel<true>, lds, grid, 512, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            else conv_launch(conv3x3_pp_kernel<false>, lds, grid, 512, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            WISE_LAUNCH_CHECK("conv3x3_pp_kernel");
+            return WISE_OK;
+        }
+        case CONV_128x128: {
+            const size_t lds = 2 * (TILE_BYTES + 128 * BK * 2);   // 64 KiB
+            if (pool) conv_launch(conv3x3_kernel<4, true>, lds, tiles_m * (Cout / 128), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            else conv_launch(conv3x3_kernel<4, false>, lds, tiles_m * (Cout / 128), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            break;
+        }
+        case CONV_256x64: {
+            const size_t lds = 2 * (2 * TILE_BYTES + 64 * BK * 2);    // 80 KiB: two blocks fill a CU's LDS exactly
+            if (pool) conv_launch(conv3x3_kernel<4, true, 4>, lds, tiles256 * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            else conv_launch(conv3x3_kernel<4, false, 4>, lds, tiles256 * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            break;
+        }
+        case CONV_128x64: {
+            const size_t lds = 2 * (TILE_BYTES + 64 * BK * 2);    // 48 KiB
+            if (pool) conv_launch(conv3x3_kernel<2, true>, lds, tiles_m * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            else conv_launch(conv3x3_kernel<2, false>, lds, tiles_m * (Cout / 64), 256, X, Wt, bias, zeros, T, F, Cin, (int)M, Cout, out, st);
+            break;
+        }
     }
     WISE_LAUNCH_CHECK("conv3x3_kernel");
     return WISE_OK;
@@ -2745,39 +2217,33 @@ extern "C" int wise_gemm_bf16(const uint16_t* A, const uint16_t* Wt, const float
     return wise::gemm_bf16(A, Wt, bias, M, N, K, mode, out, (hipStream_t)stream);
 }
 
-namespace wise { int g_ablate = 0; }  // timing-only ablations: bit 1 = skip LayerNorm launches, bit 2 = skip attention
-
 #ifdef WISE_DEBUG_KNOBS
-extern "C" int wise_debug_set_gemm_stamps(unsigned long long* buf /*device, 8192 entries, or null*/, int block) {
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_stamp_buf), &buf, sizeof(buf));
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_stamp_block), &block, sizeof(int));
-    return 0;
-}
-extern "C" int wise_debug_set_gemm_flags(int flags) {
-    wise::g_tile320 = (flags & 1) ? 0 : 1;
-    wise::g_mlp96_resident = (flags >> 7) & 1 ? 0 : 1;   // bit 7: the staged MLP kernel instead of the weight-resident one
-    wise::g_overlap_policy = (flags >> 4) & 7;     // bits 4-6: tiles under overlap (0 lone-stream tiles, 1 = 128x128, 2 = mixed, 3 = hint ignored, 4/5/6 = 128x128 for the residual / fc1 / QKV launches only)
-    wise::g_ablate = flags & 6;
-    wise::g_conv_variant = (flags >> 8) & 3;
-    wise::g_splitk_policy = (flags >> 10) & 3;     // bits 10-11: skinny GEMMs (0 product rule, 1 split-K for residual GEMMs only, 2 never)       // bits 8-9: convolution tile (0 by shape, 1 = 128-row tile, 2 = ping-pong)
-    return 0;
-}
-
-// tuning knob for A/B runs (tools/gemm_bench.py); not part of the stable ABI
+// tuning knob for A/B runs (tools/gemm_bench.py); not part of the stable ABI.  v & 0xFF: a variant id (0 = the plan's own
+// choice) that every gemm_bf16 / gemm_bf16_rows call then launches, after the shape fallbacks of resolve_variant.
 extern "C" int wise_debug_set_gemm_variant(int v) {
     wise::g_gemm_variant = v & 0xFF;
-    wise::g_split_m = ((v >> 29) & 1) ? 0 : 1;
-    wise::g_w4_enabled = ((v >> 28) & 1) ? 0 : 1;
-    int skip = (v >> 8) & 1;  // bit 8: skip epilogue stores (timing-only ablation)
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_skip_epilogue), &skip, sizeof(int));
-    int nt = (v >> 9) & 1 ? 0 : 1;   // bit 9: plain (temporal) epilogue stores
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_store_nt), &nt, sizeof(int));
-    int el = ((v >> 30) & 1) ? 0 : 1;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_epi_lds), &el, sizeof(int));
-    int dp = (v >> 24) & 0xF;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_dephase), &dp, sizeof(int));
-    int gm = (v >> 16) & 0xFF;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(wise::g_group_m), &gm, sizeof(int));
+    return 0;
+}
+
+// The tile plan as ints, for tests/test_gemm_plan_cpu.py (no GPU needed).  Returns the number of ints written to out.
+//   kind 0, gemm_plan:  a = M, N, K, mode, m_valid (0: gemm_bf16), overlapped, cus -> splitk, n, v0, rows0, v1, rows1
+//   kind 1, fold_plan:  a = M, N, K, mode, producer, wide96, cus                     -> variant
+//   kind 2, conv_plan:  a = B, T, F, Cin, Cout, pool                                 -> ConvTile
+extern "C" int wise_debug_gemm_plan(int kind, const int* a, int* out) {
+    if (kind == 0) {
+        const wise::GemmPlan p = wise::gemm_plan(a[0], a[1], a[2], a[3], a[4], a[5] != 0, a[6]);
+        const int r[6] = {p.splitk, p.n, p.v[0], p.rows[0], p.v[1], p.rows[1]};
+        for (int i = 0; i < 6; ++i) out[i] = r[i];
+        return 6;
+    }
+    if (kind == 1) {
+        out[0] = wise::fold_plan(a[0], a[1], a[2], a[3], a[4] != 0, a[5] != 0, a[6]);
+        return 1;
+    }
+    if (kind == 2) {
+        out[0] = wise::conv_plan(wise::conv_rows(a[0], a[1], a[2], a[5] != 0), a[4]);
+        return 1;
+    }
     return 0;
 }
 #endif  // WISE_DEBUG_KNOBS

@@ -15,7 +15,13 @@
 #include "gemm_w4.h"   // the volatile-asm MFMA statement and its retire / pin helpers (attn_oproj_fold_kernel)
 
 namespace wise {
-extern int g_ablate;  // timing-only ablation switches (wise_debug_set_gemm_flags)
+// Timing-only ablations of the debug library (wise_debug_set_gemm_flags, tools/vit_bench.py): bit 1 skips the LayerNorm
+// launches, bit 2 the attention launches.
+#ifdef WISE_DEBUG_KNOBS
+static int g_ablate = 0;
+#else
+constexpr int g_ablate = 0;
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm: one wave per row, row in registers, exact two-pass statistics in fp32
@@ -188,8 +194,8 @@ int layernorm_f32_bf16(const float* x, const float* w, const float* b, int rows,
         return WISE_OK;
     }
     const int nv = (W / 4 + 63) / 64;
-    // many rows of a hot width: several rows per wave (same bits as one row per wave; ablation bit 4 = one row per wave)
-    if (nv <= 2 && rows >= 16384 && !(g_ablate & 16)) {
+    // many rows of a hot width: several rows per wave (same bits as one row per wave)
+    if (nv <= 2 && rows >= 16384) {
         const dim3 block(256);
         if (nv == 1) hipLaunchKernelGGL((layernorm_rows_kernel<1, 4>), dim3((rows + 15) / 16), block, 0, st, x, w, b, rows, W, eps, y);
         else hipLaunchKernelGGL((layernorm_rows_kernel<2, 4>), dim3((rows + 15) / 16), block, 0, st, x, w, b, rows, W, eps, y);
@@ -1680,6 +1686,7 @@ extern "C" int wise_attention_bf16(const uint16_t* qkv, int B, int T, int H, uin
 }
 
 #ifdef WISE_DEBUG_KNOBS
+extern "C" int wise_debug_set_gemm_flags(int flags) { wise::g_ablate = flags & 6; return 0; }   // the ablation bits 2 and 4
 extern "C" int wise_debug_ao_set(int flags) { wise::g_ao_dbg = flags & 15; return 0; }
 extern "C" int wise_debug_ao_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(wise::g_ao_stamps), sizeof(unsigned long long) * 96) == hipSuccess ? 0 : -1;
