@@ -33,7 +33,7 @@ const char* wise_last_error(void);
  * caption encoder — and the wise_cnn14_* entry points; 5: wise_ip_shadow_i8 / wise_ip_topk_shadow8_f32 (int8 shadow,
  * norms[4]), wise_ip_topk_shadow_workspace_bytes depends on nq and returns 0 under 2^18 rows, two-stage k up to 1024; and,
  * added within 5: wise_vit_config.ln_fold, the wise_gemm_fold_* entry points, wise_attention_oproj_fold, wise_htsat_forward2,
- * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points). */
+ * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*). */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -138,6 +138,20 @@ size_t wise_ivf_scan_workspace_bytes(int nq, int nprobe, int k);
 int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                       const float* Q, int nq, const int64_t* probes, int nprobe, int k, float* outD, int64_t* outI,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* The same second stage on ONE RANK's slice of a list-major IndexIVFFlat sharded across GPUs (rank r holds rows
+ * shard_range(N_total, r, W) of the lists laid end to end; wise_amd/index/sharded.py):
+ *   X, ids   [N,d] / [N] this rank's rows (ids are the global external ids)
+ *   list_off [nlist+1] the global offsets clipped to the slice (lists outside it are empty)
+ *   probes   [nq,nprobe] GLOBAL list numbers (the coarse stage is replicated on every rank)
+ * Probes whose local segment is empty are dropped on the device first (kept in probe order), so the scan and the merge
+ * only work on the ~nprobe/W lists the rank holds.  probe_count [nq] (optional) receives the number kept per query.
+ * outD/outI as wise_ivf_scan_f32 over the slice; wise_topk_merge of the ranks' answers in rank order then gives the same
+ * bits as wise_ivf_scan_f32 over the whole array, ties included.  Limits: d % 4 == 0, d <= 2048, k <= 2048,
+ * nprobe <= 2048.  Workspace: wise_ivf_scan_local_workspace_bytes(nq, nprobe, k) bytes. */
+size_t wise_ivf_scan_local_workspace_bytes(int nq, int nprobe, int k);
+int wise_ivf_scan_local_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                            const float* Q, int nq, const int64_t* probes, int nprobe, int k, float* outD, int64_t* outI,
+                            int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Dense scores [nq, N] = Q x X^T in exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain per
  * score).  The coarse stage of IndexIVFFlat when nprobe is a sizeable part of nlist — the reference's nprobe = 1024

@@ -85,11 +85,15 @@ struct WaveList {
 // SEG = true is the inverted-list form (IndexIVFFlat, wise_ivf_scan_f32): block b serves query b / nprobe and
 // scans only the rows of the list named by probes[b] (X holds the lists back to back, list_off their bounds);
 // its k keys go to part[(b % nprobe) * nq + b / nprobe] so that merge_keys_kernel folds a query's nprobe lists.
+// With `count` (wise_ivf_scan_local_f32) only the first count[q] probes of query q are live: the grid is then taken
+// probe-major (block b: probe b / nq of query b % nq), a block past its query's count returns before it touches LDS or
+// part, and the merge folds count[q] lists.
 struct SegArgs {
     const long long* probes;    // [nq][nprobe] list numbers, < 0 = nothing to scan
     const long long* list_off;  // [nlist + 1]
     int nprobe, nq;
     const int* gate;            // optional: the launch does nothing unless *gate != 0 (two-stage search fallback)
+    const int* count;           // optional [nq]: live probes per query (the rest of the row is not read)
 };
 
 template <int NV, int NQ, int R, bool SEG = false>
@@ -106,8 +110,18 @@ __global__ __launch_bounds__(256) void ip_scan_kernel(const f32x4* __restrict__ 
     size_t slot = blockIdx.x;     // where the block's keys go
     if constexpr (SEG) {
         static_assert(NQ == 1, "one query per block in the inverted-list form");
-        const int qi = blockIdx.x / seg.nprobe, pi = blockIdx.x - qi * seg.nprobe;
-        const long long l = seg.probes[blockIdx.x];
+        int qi, pi;
+        if (seg.count) {
+            // probe-major: the live blocks (pi < count[qi]) are the head of the grid and spread over every XCD, the dead
+            // ones its tail; block-uniform exit, no barrier has been reached yet
+            pi = blockIdx.x / seg.nq;
+            qi = blockIdx.x - pi * seg.nq;
+            if (pi >= seg.count[qi]) return;
+        } else {
+            qi = blockIdx.x / seg.nprobe;
+            pi = blockIdx.x - qi * seg.nprobe;
+        }
+        const long long l = seg.probes[(size_t)qi * seg.nprobe + pi];
         if (l >= 0) { lo = seg.list_off[l]; N = seg.list_off[l + 1]; } else { N = 0; }
         Q += (size_t)qi * d4 * 4;
         slot = (size_t)pi * seg.nq + qi;
@@ -227,7 +241,8 @@ __global__ __launch_bounds__(1024) void merge_keys_kernel(const u64* __restrict_
                                                           int k, int cap, const long long* __restrict__ ids,
                                                           long long id_base, float* __restrict__ outD,
                                                           long long* __restrict__ outI, int q_off,
-                                                          const int* __restrict__ gate = nullptr, int k_in = 0) {
+                                                          const int* __restrict__ gate = nullptr, int k_in = 0,
+                                                          const int* __restrict__ pcount = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (gate && *gate == 0) return;
     const int kin = k_in > 0 ? k_in : k;   // keys per input list (the lists may be shorter than the k kept)
@@ -240,8 +255,8 @@ __global__ __launch_bounds__(1024) void merge_keys_kernel(const u64* __restrict_
     WaveList wl;
     wl.init(lds + (size_t)wave * cap, cap, k, lane);
     // the P lists of this query hold P*k keys in all: every offer carries 64 of them (one per lane), whatever k
-    // is; waves take 64-key chunks round-robin
-    const long long total = (long long)P * kin;
+    // is; waves take 64-key chunks round-robin.  pcount: query q folds only its first pcount[q] lists
+    const long long total = (long long)(pcount ? pcount[q] : P) * kin;
     for (long long c0 = (long long)wave * 64; c0 < total; c0 += (long long)nwaves * 64) {
         const long long i = c0 + lane;
         u64 key = 0;
@@ -278,6 +293,27 @@ __global__ __launch_bounds__(1024) void merge_keys_kernel(const u64* __restrict_
             outI[(size_t)(q_off + q) * k + i] = id;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// probe compaction (wise_ivf_scan_local_f32): one wave per query keeps, in probe order, the probes whose list holds
+// rows in this rank's slice (list_off clipped to the slice: most lists are empty there) and writes their count
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void compact_probes_kernel(const long long* __restrict__ probes, int nprobe,
+                                                            const long long* __restrict__ list_off, int nlist,
+                                                            long long* __restrict__ out, int* __restrict__ count) {
+    const int lane = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * nprobe;
+    int n = 0;
+    for (int i0 = 0; i0 < nprobe; i0 += 64) {
+        const int i = i0 + lane;
+        const long long l = (i < nprobe) ? probes[base + i] : -1;
+        const bool keep = l >= 0 && l < nlist && list_off[l + 1] > list_off[l];
+        const u64 m = __ballot(keep);
+        if (keep) out[base + n + __popcll(m & ((1ull << lane) - 1ull))] = l;
+        n += __popcll(m);
+    }
+    if (lane == 0) count[blockIdx.x] = n;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1862,6 +1898,72 @@ extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t
     hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, nprobe, nq, k, cap,
                        reinterpret_cast<const long long*>(ids), 0ll, outD, reinterpret_cast<long long*>(outI), 0);
     WISE_LAUNCH_CHECK("merge_keys_kernel");
+    return WISE_OK;
+}
+
+// Rank-local form of wise_ivf_scan_f32 for a slice of the list-major array (list_off clipped to the slice): the probes
+// whose local segment is empty are compacted away on the device first, so the scan blocks past a query's count return
+// at once and the merge folds count[q] lists instead of nprobe.  Workspace: the keys [nprobe][nq][k], the compacted
+// probes [nq][nprobe] and (without probe_count) the counts [nq].
+static size_t ivf_local_part_bytes(int nq, int nprobe, int k) { return align_up((size_t)nq * nprobe * k * sizeof(u64), 256); }
+static size_t ivf_local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
+
+extern "C" size_t wise_ivf_scan_local_workspace_bytes(int nq, int nprobe, int k) {
+    if (nq < 1 || nprobe < 1 || nprobe > 2048 || k < 1 || k > 2048) return 0;
+    return ivf_local_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe) + align_up((size_t)nq * sizeof(int), 256);
+}
+
+extern "C" int wise_ivf_scan_local_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
+                                       const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k,
+                                       float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "ivf_scan_local: d=%d must be a multiple of 4 in [4,2048]", d);
+    WISE_CHECK_ARG(k >= 1 && k <= 2048, "ivf_scan_local: k=%d out of [1,2048]", k);
+    WISE_CHECK_ARG(nq >= 1 && nprobe >= 1 && nprobe <= 2048 && nlist >= 1 && (long long)nq * nprobe < (1ll << 31),
+                   "ivf_scan_local: nq=%d nprobe=%d nlist=%d out of range", nq, nprobe, nlist);
+    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll, "ivf_scan_local: N=%lld out of range", (long long)N);
+    WISE_CHECK_ARG(Q && outD && outI && list_off && probes && (X || N == 0), "ivf_scan_local: null pointer");
+    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "ivf_scan_local: X and Q must be 16-byte aligned");
+    const size_t need = wise_ivf_scan_local_workspace_bytes(nq, nprobe, k);
+    if (!workspace || workspace_bytes < need) {
+        set_error("ivf_scan_local: workspace %zu < %zu bytes", workspace_bytes, need);
+        return WISE_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
+    u64* part = reinterpret_cast<u64*>(wsb);
+    long long* live = reinterpret_cast<long long*>(wsb + ivf_local_part_bytes(nq, nprobe, k));
+    int* count = probe_count ? probe_count
+                             : reinterpret_cast<int*>(wsb + ivf_local_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe));
+    const long long* loff = reinterpret_cast<const long long*>(list_off);
+    hipLaunchKernelGGL(compact_probes_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), nprobe,
+                       loff, nlist, live, count);
+    WISE_LAUNCH_CHECK("compact_probes_kernel");
+    const int cap = list_cap(k);
+    SegArgs seg = {live, loff, nprobe, nq};
+    seg.count = count;
+    switch ((d / 4 + 63) / 64) {
+        case 1: launch_seg_scan<1>(X, d, Q, k, cap, part, seg, st); break;
+        case 2: launch_seg_scan<2>(X, d, Q, k, cap, part, seg, st); break;
+        case 3: launch_seg_scan<3>(X, d, Q, k, cap, part, seg, st); break;
+        case 4: launch_seg_scan<4>(X, d, Q, k, cap, part, seg, st); break;
+        case 5: launch_seg_scan<5>(X, d, Q, k, cap, part, seg, st); break;
+        case 6: launch_seg_scan<6>(X, d, Q, k, cap, part, seg, st); break;
+        case 7: launch_seg_scan<7>(X, d, Q, k, cap, part, seg, st); break;
+        case 8: launch_seg_scan<8>(X, d, Q, k, cap, part, seg, st); break;
+        default: set_error("ivf_scan_local: no kernel for d=%d", d); return WISE_E_INVALID;
+    }
+    WISE_LAUNCH_CHECK("ip_scan_kernel<seg, local>");
+    int mw = 8192 / cap;
+    if (mw < 1) mw = 1;
+    if (mw > 16) mw = 16;
+    const size_t mlds = (size_t)mw * cap * 8;
+    if (mlds > 48 * 1024)
+        raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
+    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, nprobe, nq, k, cap,
+                       reinterpret_cast<const long long*>(ids), 0ll, outD, reinterpret_cast<long long*>(outI), 0,
+                       (const int*)nullptr, 0, (const int*)count);
+    WISE_LAUNCH_CHECK("merge_keys_kernel (local)");
     return WISE_OK;
 }
 

@@ -145,59 +145,116 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
             ids[a:b].tofile(f)
 
 
+def _read_ivf_head(f, p):
+    """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload)."""
+    (cc,) = struct.unpack("<I", f.read(4))
+    if cc != _fourcc("IwFl"):
+        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFFlat")
+    hdr = f.read(_HDR_SIZE + 4)
+    d, n, metric, off = _read_header(hdr, 0)
+    f.seek(4 + off)
+    nlist, nprobe = struct.unpack("<QQ", f.read(16))
+    (cq,) = struct.unpack("<I", f.read(4))
+    if cq != _fourcc("IxFI"):
+        raise RuntimeError(f"{p}: coarse quantizer type 0x{cq:08x}, expected IndexFlatIP")
+    pos = f.tell()
+    hdr = f.read(_HDR_SIZE + 4)
+    dq, nq_, _, off = _read_header(hdr, 0)
+    f.seek(pos + off)
+    (cnt,) = struct.unpack("<Q", f.read(8))
+    if dq != d or nq_ != nlist or cnt != nlist * d:
+        raise RuntimeError(f"{p}: inconsistent quantizer ({cnt} values for {nq_} x {dq})")
+    centroids = np.fromfile(f, dtype=np.float32, count=cnt).reshape(nlist, d)
+    (dm_type,) = struct.unpack("<B", f.read(1))
+    (dm_n,) = struct.unpack("<Q", f.read(8))
+    f.seek(8 * dm_n, 1)
+    if dm_type == 2:  # hashtable pairs
+        (npairs,) = struct.unpack("<Q", f.read(8))
+        f.seek(16 * npairs, 1)
+    il, nl2, code_size = struct.unpack("<IQQ", f.read(20))
+    if il != _fourcc("ilar") or nl2 != nlist or code_size != 4 * d:
+        raise RuntimeError(f"{p}: unexpected inverted lists (type 0x{il:08x}, code size {code_size})")
+    (lt, vn) = struct.unpack("<IQ", f.read(12))
+    sizes = np.zeros(nlist, dtype=np.int64)
+    if lt == _fourcc("full"):
+        sizes[:] = np.fromfile(f, dtype=np.uint64, count=vn).astype(np.int64)
+    elif lt == _fourcc("sprs"):
+        pairs = np.fromfile(f, dtype=np.uint64, count=vn).reshape(-1, 2).astype(np.int64)
+        sizes[pairs[:, 0]] = pairs[:, 1]
+    else:
+        raise RuntimeError(f"{p}: unknown list layout 0x{lt:08x}")
+    list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    if list_off[-1] != n:
+        raise RuntimeError(f"{p}: lists hold {list_off[-1]} rows, header says {n}")
+    return centroids, list_off, int(nprobe), f.tell()
+
+
+def _missing(p):
+    return RuntimeError(f"Error: 'f' failed: could not open {p} for reading: No such file or directory")
+
+
 def read_ivf_flat_ip(path):
     """-> dict(centroids [nlist,d], X [n,d], ids [n], list_off [nlist+1], nprobe).  The lists are returned back to
     back in list order, which is the layout the search kernel wants."""
     p = Path(path)
     if not p.exists():
-        raise RuntimeError(f"Error: 'f' failed: could not open {p} for reading: No such file or directory")
+        raise _missing(p)
+    with open(p, "rb") as f:
+        centroids, list_off, nprobe, _ = _read_ivf_head(f, p)
+        d, n = centroids.shape[1], int(list_off[-1])
+        X = np.empty((n, d), dtype=np.float32)
+        ids = np.empty((n,), dtype=np.int64)
+        for l in np.flatnonzero(np.diff(list_off)):
+            a, b = int(list_off[l]), int(list_off[l + 1])
+            X[a:b] = np.fromfile(f, dtype=np.float32, count=(b - a) * d).reshape(b - a, d)
+            ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
+    return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+
+
+def ivf_flat_ip_ntotal(path) -> int:
+    """Rows of an 'IwFl' file (its header), without reading the lists."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
     with open(p, "rb") as f:
         (cc,) = struct.unpack("<I", f.read(4))
         if cc != _fourcc("IwFl"):
             raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFFlat")
-        hdr = f.read(_HDR_SIZE + 4)
-        d, n, metric, off = _read_header(hdr, 0)
-        f.seek(4 + off)
-        nlist, nprobe = struct.unpack("<QQ", f.read(16))
-        (cq,) = struct.unpack("<I", f.read(4))
-        if cq != _fourcc("IxFI"):
-            raise RuntimeError(f"{p}: coarse quantizer type 0x{cq:08x}, expected IndexFlatIP")
-        pos = f.tell()
-        hdr = f.read(_HDR_SIZE + 4)
-        dq, nq_, _, off = _read_header(hdr, 0)
-        f.seek(pos + off)
-        (cnt,) = struct.unpack("<Q", f.read(8))
-        if dq != d or nq_ != nlist or cnt != nlist * d:
-            raise RuntimeError(f"{p}: inconsistent quantizer ({cnt} values for {nq_} x {dq})")
-        centroids = np.fromfile(f, dtype=np.float32, count=cnt).reshape(nlist, d)
-        (dm_type,) = struct.unpack("<B", f.read(1))
-        (dm_n,) = struct.unpack("<Q", f.read(8))
-        f.seek(8 * dm_n, 1)
-        if dm_type == 2:  # hashtable pairs
-            (npairs,) = struct.unpack("<Q", f.read(8))
-            f.seek(16 * npairs, 1)
-        il, nl2, code_size = struct.unpack("<IQQ", f.read(20))
-        if il != _fourcc("ilar") or nl2 != nlist or code_size != 4 * d:
-            raise RuntimeError(f"{p}: unexpected inverted lists (type 0x{il:08x}, code size {code_size})")
-        (lt, vn) = struct.unpack("<IQ", f.read(12))
-        sizes = np.zeros(nlist, dtype=np.int64)
-        if lt == _fourcc("full"):
-            sizes[:] = np.fromfile(f, dtype=np.uint64, count=vn).astype(np.int64)
-        elif lt == _fourcc("sprs"):
-            pairs = np.fromfile(f, dtype=np.uint64, count=vn).reshape(-1, 2).astype(np.int64)
-            sizes[pairs[:, 0]] = pairs[:, 1]
-        else:
-            raise RuntimeError(f"{p}: unknown list layout 0x{lt:08x}")
-        list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        if list_off[-1] != n:
-            raise RuntimeError(f"{p}: lists hold {list_off[-1]} rows, header says {n}")
-        X = np.empty((n, d), dtype=np.float32)
-        ids = np.empty((n,), dtype=np.int64)
-        for l in np.flatnonzero(sizes):
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            X[a:b] = np.fromfile(f, dtype=np.float32, count=(b - a) * d).reshape(b - a, d)
-            ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
-    return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": int(nprobe)}
+        return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+
+
+def read_ivf_flat_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major array read_ivf_flat_ip returns, reading only the lists that overlap the range
+    (one rank's slice of an index sharded across GPUs: wise_amd/index/sharded.py).
+    -> dict(centroids [nlist,d] (all of them), X [hi-lo,d], ids [hi-lo], list_off [nlist+1] = clip(list_off - lo, 0,
+    hi - lo), nprobe).  List l's payload sits at list_off[l] * (4d + 8) bytes into the payload (rows, then ids)."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        centroids, list_off, nprobe, data = _read_ivf_head(f, p)
+        d, n = centroids.shape[1], int(list_off[-1])
+        lo, hi = int(lo), int(hi)
+        if not (0 <= lo <= hi <= n):
+            raise ValueError(f"read_ivf_flat_ip_range: [{lo}, {hi}) outside [0, {n}]")
+        X = np.empty((hi - lo, d), dtype=np.float32)
+        ids = np.empty((hi - lo,), dtype=np.int64)
+        sizes = np.diff(list_off)
+        first = int(np.searchsorted(list_off, lo, side="right")) - 1     # the list that holds row lo
+        for l in range(max(first, 0), len(sizes)):
+            s0, s1 = int(list_off[l]), int(list_off[l + 1])
+            if s0 >= hi:
+                break
+            a, b = max(s0, lo), min(s1, hi)
+            if a >= b:
+                continue
+            base = data + s0 * (4 * d + 8)
+            f.seek(base + (a - s0) * 4 * d)
+            X[a - lo:b - lo] = np.fromfile(f, dtype=np.float32, count=(b - a) * d).reshape(b - a, d)
+            f.seek(base + (s1 - s0) * 4 * d + (a - s0) * 8)
+            ids[a - lo:b - lo] = np.fromfile(f, dtype=np.int64, count=b - a)
+    return {"centroids": centroids, "X": X, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
+            "nprobe": nprobe}
 
 
 def index_fourcc(path) -> str:

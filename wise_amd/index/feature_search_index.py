@@ -21,7 +21,19 @@ with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the 
     `shard_range(N, r, W)` of the single `.faiss` file — memory-mapped, so a rank touches only its own rows' pages —
     and `self.index` is a `ShardedFlatIPIndex`: `search` / `reconstruct_batch` are then collective (every rank calls
     them with the same arguments and gets the global answer: one all-gather of per-shard top-k + `wise_topk_merge`).
-IndexIVFFlat stays a single-GPU index (every rank loads the whole file; rank 0 alone builds it).
+IndexIVFFlat is sharded too when WISE_SHARDED_IVF=1 is also set (opt-in; without it, and without IVF part files, every
+rank loads the whole file and rank 0 alone builds it).  The index is then one list-major array cut by `shard_range`
+(wise_amd/index/sharded.py: rank r holds the whole centroid table and rows shard_range(N, r, W) of list 0's rows, then
+list 1's, ...):
+  * `create_index('IndexIVFFlat')`: rank r reads only its own store shard files; the ranks train once on a seeded sample
+    of min(N, 100 nlist) rows drawn from all of them (rank 0 trains, the centroids are broadcast), each rank assigns its
+    own rows, one all-gather of the per-rank list counts fixes the global order (within a list: by source rank, then
+    source order), one all_to_all moves rows and ids to the rank that owns their position, and each rank writes
+    `{media_type}-IndexIVFFlat.faiss.part-RRR-of-WWW` — a complete IVF file (all centroids, its clipped lists); the parts
+    laid end to end are the single-file layout;
+  * `load_index('IndexIVFFlat')`: the rank's part file if the parts of this world size exist, otherwise (with the
+    switch on) rows shard_range(N, r, W) of the single file, reading only the lists that overlap them; `self.index` is a
+    `ShardedIVFFlatIPIndex`, whose `search` / `reconstruct_batch` are collective and return the one-GPU IVF answer.
 """
 import os
 from pathlib import Path
@@ -34,7 +46,7 @@ from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .search_index import SearchIndex
-from .sharded import ShardedFlatIPIndex, shard_range
+from .sharded import ShardedFlatIPIndex, ShardedIVFFlatIPIndex, shard_range
 
 
 def _dist_rank_world():
@@ -47,9 +59,22 @@ def _dist_rank_world():
     return 0, 1, False
 
 
+def _sharded_ivf_on():
+    return os.environ.get('WISE_SHARDED_IVF') == '1'
+
+
+def _coll_device():
+    """Where the tensors of a collective live: the current GPU on the nccl (RCCL) backend, the host on gloo."""
+    import torch
+    import torch.distributed as dist
+
+    return torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+
+
 class FeatureSearchIndex(SearchIndex):
-    # the class that holds a rank's rows in HBM; CPU tests of the multi-rank wiring put a stand-in here
+    # the classes that hold a rank's rows in HBM; CPU tests of the multi-rank wiring put stand-ins here
     flat_index_factory = FlatIPIndex
+    ivf_index_factory = IVFFlatIPIndex
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -79,19 +104,27 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        if sharded and index_type == 'IndexFlatIP':
+        sharded_ivf = sharded and index_type == 'IndexIVFFlat' and _sharded_ivf_on()
+        if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
-        if index_fn.exists() and overwrite is False:
+        exists = index_fn.exists()
+        if sharded_ivf:                             # the build is collective: every rank takes the same decision
+            import torch
+            import torch.distributed as dist
+            flag = torch.tensor([int(exists)], dtype=torch.int64, device=_coll_device())
+            dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+            exists = bool(flag.item())
+        if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
         if index_type not in ('IndexFlatIP', 'IndexIVFFlat'):
             raise NotImplementedError(f'{index_type}: IndexFlatIP and IndexIVFFlat are the index types WISE builds')
         self.index_type = index_type
-        if sharded and index_type == 'IndexIVFFlat' and rank != 0:
+        if sharded and index_type == 'IndexIVFFlat' and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
-        if sharded and index_type == 'IndexFlatIP':
+        if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             feature_store.enable_read(shard_shuffle=False, shard_slice=(rank, world))   # this rank's shard files only
         else:
             feature_store.enable_read(shard_shuffle=False)
@@ -108,6 +141,10 @@ class FeatureSearchIndex(SearchIndex):
             X[n:n + m] = feature_vectors_batch
             ids[n:n + m] = feature_ids_batch
             n += m
+        if sharded_ivf:
+            self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world)
+            print(f'  saved index part to {index_fn}')
+            return
         if index_type == 'IndexIVFFlat':
             cell_count = reference_nlist(n)
             train_count = min(n, 100 * cell_count)
@@ -126,6 +163,95 @@ class FeatureSearchIndex(SearchIndex):
             faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
         print(f'  saved index to {index_fn}')
 
+    def _create_sharded_ivf(self, X, ids, part_fn, rank, world):
+        """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows."""
+        import torch
+        import torch.distributed as dist
+
+        dev = _coll_device()
+        n, d = X.shape
+        # global row count and where each rank's rows sit in the concatenation (rank order)
+        ns_t = torch.zeros(world, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(ns_t, torch.tensor([n], dtype=torch.int64, device=dev))
+        ns = ns_t.cpu().numpy()
+        src_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        n_total = int(src_off[-1])
+        cell_count = reference_nlist(n_total)
+        train_count = min(n_total, 100 * cell_count)
+        # the single-file build's seeded sample, drawn over the concatenation of every rank's rows
+        sample = np.random.default_rng(1234).permutation(n_total)[:train_count]
+        sample.sort()
+        bounds = np.searchsorted(sample, src_off)
+        mine = sample[bounds[rank]:bounds[rank + 1]] - src_off[rank]
+        ivf = self.ivf_index_factory(d, cell_count)
+        if rank == 0:                               # k-means once, on rank 0; the centroids' bits go to every rank
+            parts = [X[mine]]
+            for src in range(1, world):
+                m = int(bounds[src + 1] - bounds[src])
+                if m:
+                    buf = torch.empty(m, d, dtype=torch.float32, device=dev)
+                    dist.recv(buf, src=src)
+                    parts.append(buf.cpu().numpy())
+            print(f'  training IndexIVFFlat index with {train_count} features with {cell_count} clusters ...')
+            ivf.train(np.concatenate(parts))
+            c = ivf.centroids if torch.is_tensor(ivf.centroids) else torch.from_numpy(np.asarray(ivf.centroids))
+            c = c.to(dev, torch.float32).contiguous()
+        else:
+            if len(mine):
+                dist.send(torch.from_numpy(np.ascontiguousarray(X[mine])).to(dev), dst=0)
+            c = torch.empty(cell_count, d, dtype=torch.float32, device=dev)
+        dist.broadcast(c, src=0)
+        centroids = c.cpu().numpy()
+        ivf.set_centroids(centroids)
+        # each rank assigns its own rows; the per-rank list counts fix the global list-major order
+        a = ivf.assign(X)
+        cnt = torch.from_numpy(np.bincount(a, minlength=cell_count).astype(np.int64)).to(dev)
+        allc_t = torch.empty(world, cell_count, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(allc_t.view(-1), cnt)
+        allc = allc_t.cpu().numpy()
+        list_off = np.concatenate([[0], np.cumsum(allc.sum(axis=0))]).astype(np.int64)
+        order = np.argsort(a, kind='stable')        # this rank's rows by list, source order within a list
+        a_s = a[order]
+        first = np.concatenate([[0], np.cumsum(allc[rank])[:-1]]).astype(np.int64)
+        gpos = list_off[a_s] + allc[:rank].sum(axis=0)[a_s] + (np.arange(n, dtype=np.int64) - first[a_s])
+        # rows, ids and global positions travel as one int32 buffer per row to the rank that owns the position
+        his = np.array([shard_range(n_total, r, world)[1] for r in range(world)], dtype=np.int64)
+        dest = np.searchsorted(his, gpos, side='right')
+        send_counts = np.bincount(dest, minlength=world).astype(np.int64)
+        packed = np.empty((n, d + 4), dtype=np.int32)
+        packed[:, :d] = X[order].view(np.int32)
+        packed[:, d:d + 2] = ids[order].astype(np.int64).view(np.int32).reshape(n, 2)
+        packed[:, d + 2:] = gpos.view(np.int32).reshape(n, 2)
+        sc = torch.from_numpy(send_counts).to(dev)
+        rc = torch.empty(world, dtype=torch.int64, device=dev)
+        dist.all_to_all_single(rc, sc)
+        recv_counts = rc.cpu().numpy()
+        lo, hi = shard_range(n_total, rank, world)
+        recv = torch.empty(int(recv_counts.sum()), d + 4, dtype=torch.int32, device=dev)
+        dist.all_to_all_single(recv, torch.from_numpy(packed).to(dev), output_split_sizes=recv_counts.tolist(),
+                               input_split_sizes=send_counts.tolist())
+        got = recv.cpu().numpy()
+        pos = np.ascontiguousarray(got[:, d + 2:]).view(np.int64).reshape(-1) - lo
+        if got.shape[0] != hi - lo or not np.array_equal(np.sort(pos), np.arange(hi - lo)):
+            raise RuntimeError(f'sharded IndexIVFFlat build: rank {rank} received rows that do not tile [{lo}, {hi})')
+        X_loc = np.empty((hi - lo, d), dtype=np.float32)
+        ids_loc = np.empty((hi - lo,), dtype=np.int64)
+        X_loc[pos] = np.ascontiguousarray(got[:, :d]).view(np.float32)
+        ids_loc[pos] = np.ascontiguousarray(got[:, d:d + 2]).view(np.int64).reshape(-1)
+        faiss_io.write_ivf_flat_ip(part_fn, centroids, X_loc, ids_loc, np.clip(list_off - lo, 0, hi - lo),
+                                   nprobe=ivf.nprobe)
+
+    def _sharded_ivf_index(self, f):
+        """ShardedIVFFlatIPIndex around a local index holding the slice `f` (a read_ivf_flat_ip(_range) dict)."""
+        import torch
+
+        local = self.ivf_index_factory(f["centroids"].shape[1], f["centroids"].shape[0])
+        local.set_centroids(f["centroids"])
+        local.adopt_lists(torch.from_numpy(f["X"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+        local.nprobe = f["nprobe"]
+        return ShardedIVFFlatIPIndex(local, merge=getattr(local, 'merge_lists', None),
+                                     always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
+
     def is_index_loaded(self):
         return hasattr(self, 'index')
 
@@ -137,7 +263,12 @@ class FeatureSearchIndex(SearchIndex):
             print(f'  index {index_fn} does not exist')
             print(f'  use create-index.py script to create an index')
         # like the reference (App. B.3) a missing file raises from the reader, it does not return False
-        if index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
+        if sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
+            index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip(part_fn))      # built by this many ranks
+        elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
+            lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
+            index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             import torch
             f = faiss_io.read_ivf_flat_ip(index_fn)
             index = IVFFlatIPIndex(f["centroids"].shape[1], f["centroids"].shape[0])

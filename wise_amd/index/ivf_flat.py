@@ -88,6 +88,18 @@ class IVFFlatIPIndex:
             _lib.check(lib.wise_ivf_argmax(scores.data_ptr(), q.shape[0], c.shape[0], out[s:].data_ptr(), st), "wise_ivf_argmax")
         return out
 
+    def assign(self, x, chunk: int = 1 << 20) -> np.ndarray:
+        """[n] int64 (numpy): the list each row of x [n,d] goes to (the assignment add_with_ids makes), streamed to the
+        device `chunk` rows at a time."""
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIPIndex: train() before assign()")
+        x = np.asarray(x, dtype=np.float32)
+        out = np.empty(x.shape[0], dtype=np.int64)
+        for s in range(0, x.shape[0], chunk):
+            xs = torch.from_numpy(np.ascontiguousarray(x[s:s + chunk])).to(self.device)
+            out[s:s + xs.shape[0]] = self._assign(xs, self.centroids).cpu().numpy()
+        return out
+
     def _group(self, assign: torch.Tensor):
         """(order, list_off, counts): the rows grouped by list, stable (wise_ivf_group: a radix sort on the device)"""
         lib = _lib.lib()
@@ -248,6 +260,40 @@ class IVFFlatIPIndex:
                                    self._ids.data_ptr(), q.data_ptr(), nq, probes.data_ptr(), nprobe, k, D.data_ptr(),
                                    I.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr())
         _lib.check(rc, "wise_ivf_scan_f32")
+        return D, I
+
+    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None):
+        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (its
+        list_off clipped to the slice; ShardedIVFFlatIPIndex): the same coarse stage over the full centroid table,
+        then wise_ivf_scan_local_f32, which drops the probes whose local segment is empty before it scans and merges.
+        probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query."""
+        lib = _lib.lib()
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIPIndex: not trained")
+        self._finalize()
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
+        q = q.to(self.device, torch.float32).contiguous()
+        nq = q.shape[0]
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return D, I
+        nprobe = max(1, min(int(self.nprobe), self.nlist, 2048))
+        probes = self.probes_device(q, nprobe).contiguous()
+        need = lib.wise_ivf_scan_local_workspace_bytes(nq, nprobe, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape nq={nq} nprobe={nprobe} k={k}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq
+                                        or probe_count.device != self._ws.device):
+            raise ValueError("search_local_device: probe_count must be an int32 device tensor of nq entries")
+        rc = lib.wise_ivf_scan_local_f32(self._X.data_ptr(), self._n, self.d, self._list_off.data_ptr(), self.nlist,
+                                         self._ids.data_ptr(), q.data_ptr(), nq, probes.data_ptr(), nprobe, k,
+                                         D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), self._ws.data_ptr(),
+                                         self._ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "wise_ivf_scan_local_f32")
         return D, I
 
     def search(self, x, k: int):

@@ -4,6 +4,13 @@ Per query batch: local HIP scan+top-k on every rank -> ONE all-gather of the per
 (score, id)[nq,k] lists packed in one int64 buffer (RCCL over xGMI; 16*nq*k bytes per rank, latency-bound) -> the
 same k-way merge kernel on every rank, so every rank returns the global result.
 The reference has no distributed path; this is the only collective the search needs.
+
+ShardedIVFFlatIPIndex does the same for IndexIVFFlat.  The index is one list-major array (list 0's rows, then list 1's,
+...) and rank r owns rows shard_range(N, r, W) of it; every rank keeps the whole centroid table and list_off clipped to
+its range (a list that straddles a boundary is split, head on the lower rank).  The coarse stage runs on every rank,
+the list scan only over the probed lists the rank holds (wise_ivf_scan_local_f32: ~nprobe / W of them), then the same
+exchange and merge.  A rank's rows are in global order and the merge puts the lower rank first on equal scores, so the
+answer has the bits of the one-GPU IVF search over the same centroids and lists, ties included.
 """
 from __future__ import annotations
 
@@ -115,3 +122,45 @@ class ShardedFlatIPIndex:
         owner = have.to(torch.int8).argmax(dim=0)                 # first rank that holds the id (ids are unique)
         out = allr[owner, torch.arange(mine.shape[0], device=mine.device)]
         return out.cpu().numpy()
+
+
+class ShardedIVFFlatIPIndex(ShardedFlatIPIndex):
+    """Every rank constructs it around its own local IVFFlatIPIndex holding a clipped slice of the list-major array
+    (full centroid table, ids global).  search_device / ntotal / reconstruct_batch are collective as in the flat
+    wrapper; the rest is the surface api/routes.py:899-909 touches, passed on to the local index."""
+
+    def __init__(self, local, group: Optional[dist.ProcessGroup] = None, local_search: Optional[Callable] = None,
+                 merge: Optional[Callable] = None, always_exchange: bool = False):
+        super().__init__(local, group=group, local_search=local_search or local.search_local_device, merge=merge,
+                         always_exchange=always_exchange)
+
+    @property
+    def nprobe(self) -> int:
+        return self.local.nprobe
+
+    @nprobe.setter
+    def nprobe(self, v: int) -> None:
+        self.local.nprobe = int(v)
+
+    @property
+    def parallel_mode(self) -> int:
+        return self.local.parallel_mode
+
+    @parallel_mode.setter
+    def parallel_mode(self, v: int) -> None:
+        self.local.parallel_mode = v
+
+    @property
+    def direct_map(self):
+        return self.local.direct_map
+
+    @property
+    def is_trained(self) -> bool:
+        return self.local.is_trained
+
+    @property
+    def nlist(self) -> int:
+        return self.local.nlist
+
+    def make_direct_map(self, enable: bool = True) -> None:
+        self.local.make_direct_map(enable)
