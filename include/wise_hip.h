@@ -249,7 +249,10 @@ int wise_vit_forward(const wise_vit_config* cfg, const uint16_t* wb, const float
 int wise_vit_forward_single(const wise_vit_config* cfg, const uint16_t* wb, const float* pf, const void* images,
                             int in_kind, int batch, float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Debug/parity tap: copy the residual stream x [B*T, W] fp32 as it stands after `after_layer`
- * blocks (0 = after ln_pre) from the workspace of the LAST forward into dst. */
+ * blocks (0 = after ln_pre) from the workspace of the LAST forward into dst.  With ln_fold != 0 and
+ * head dim 64 the last block's MLP (ln_fold = 1: also its attention half) runs for the class rows
+ * only: those rows hold the last block's output; every other row holds block L-2's output
+ * (ln_fold = 1), or that plus the last block's attention residual (ln_fold = 2). */
 int wise_vit_tap_residual(const wise_vit_config* cfg, int batch, const void* workspace, float* dst,
                           void* stream);
 

@@ -305,14 +305,44 @@ __device__ __forceinline__ void softmax_block(f32x4 (&sacc)[4][QT], bf16x8 (&pf)
 // PF: the K fragments and the V rows of the NEXT key block travel while the current one is computed (64 more registers:
 // the kernel is bound by the latency of those loads, block after block — a wave holding ONE query took as long over a
 // sequence as a wave holding 64).
-template <int QT, bool CAUSAL, int DH = 64, bool PF = false>
+// CLS (QT = 1, DH = 64, no mask): the class query only — the last block of a folded tower, whose caller keeps nothing but
+// the class rows.  One wave per (image, head) computes query tile 0 with every lane of the Q fragment on row 0 (columns
+// 1..15 are discarded) and stores row 0 alone, compact: o[b, W].  Column 0 of every MFMA and of the softmax is the same
+// arithmetic as in the other forms, so the row gets their bits.  The wave of head 0 also copies the frame's class row of
+// the hi + lo stream into the compact one (ClsRows).
+struct ClsRows {
+    const bf16_t* hi = nullptr;   // the [Mp, W] stream; lo at hi + lo_off
+    long long lo_off = 0;
+    bf16_t* hc = nullptr;         // the compact [Bp, W] rows; lc at hc + lc_off
+    long long lc_off = 0;
+    const float* rs = nullptr;    // (optional) the stream's row scales -> rs_c[b] = rs[b T]
+    float* rs_c = nullptr;
+    int* cnt = nullptr;           // the compact statistics' arrival counters, zeroed by frame 0
+    int ncnt = 0;
+};
+__device__ __forceinline__ void cls_row_copy(const ClsRows& cr, int b, int T, int W, int lane) {
+    const uint2* src = reinterpret_cast<const uint2*>(cr.hi + (size_t)b * T * W);
+    uint2* dst = reinterpret_cast<uint2*>(cr.hc + (size_t)b * W);
+    const long long so = cr.lo_off >> 2, dof = cr.lc_off >> 2;   // (both multiples of 4 elements: W % 128 == 0)
+    for (int c = lane; c < (W >> 2); c += 64) {
+        dst[c] = src[c];
+        dst[c + dof] = src[c + so];
+    }
+    if (cr.rs && lane == 0) cr.rs_c[b] = cr.rs[(size_t)b * T];
+    if (b == 0)
+        for (int c = lane; c < cr.ncnt; c += 64) cr.cnt[c] = 0;
+}
+
+template <int QT, bool CAUSAL, int DH = 64, bool PF = false, bool CLS = false>
 __global__ __launch_bounds__(256, (QT == 2 && DH == 64 && !PF) ? 4 : 2) void attention_kernel(const bf16_t* __restrict__ qkv, int B, int T, int H,
-                                                        bf16_t* __restrict__ o, const int* __restrict__ lens = nullptr) {
+                                                        bf16_t* __restrict__ o, const int* __restrict__ lens = nullptr,
+                                                        const ClsRows cr = ClsRows()) {
+    static_assert(!CLS || (QT == 1 && DH == 64 && !CAUSAL && !PF), "attention_kernel: the class-query form is QT = 1, DH = 64, no mask");
     constexpr int NS = (DH + 31) / 32, ND = DH / 16, VRS = DH * 2 + 16;   // k-steps of QK^T, dh tiles of PV, V row stride
     __shared__ __attribute__((aligned(16))) unsigned char v_all[4][64 * VRS];
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
-    const int nqc = (T + 16 * QT - 1) / (16 * QT);
+    const int nqc = CLS ? 1 : (T + 16 * QT - 1) / (16 * QT);
     const long long item = (long long)blockIdx.x * 4 + wave;  // (b, h, qc)
     if (item >= (long long)B * H * nqc) return;
     const int qc = (int)(item % nqc);
@@ -331,7 +361,7 @@ __global__ __launch_bounds__(256, (QT == 2 && DH == 64 && !PF) ? 4 : 2) void att
     bf16x8 qf[QT][NS];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
-        int t = qc * (16 * QT) + qt * 16 + l15;
+        int t = CLS ? 0 : qc * (16 * QT) + qt * 16 + l15;
         if (t >= T) t = T - 1;
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -496,7 +526,17 @@ __global__ __launch_bounds__(256, (QT == 2 && DH == 64 && !PF) ? 4 : 2) void att
         l += __shfl_xor(l, 32, 64);
         const float inv = 1.f / l;
         const int t = qc * (16 * QT) + qt * 16 + l15;
-        if (t < T) {
+        if (CLS) {
+            if (l15 == 0) {
+#pragma unroll
+                for (int dt = 0; dt < ND; ++dt) {
+                    uint2 pk;
+                    pk.x = pack_bf16x2(oacc[dt][qt][0] * inv, oacc[dt][qt][1] * inv);
+                    pk.y = pack_bf16x2(oacc[dt][qt][2] * inv, oacc[dt][qt][3] * inv);
+                    *reinterpret_cast<uint2*>(o + (size_t)b * W + h * DH + dt * 16 + g * 4) = pk;
+                }
+            }
+        } else if (t < T) {
 #pragma unroll
             for (int dt = 0; dt < ND; ++dt) {
                 uint2 pk;
@@ -506,9 +546,31 @@ __global__ __launch_bounds__(256, (QT == 2 && DH == 64 && !PF) ? 4 : 2) void att
             }
         }
     }
+    if constexpr (CLS) {
+        if (h == 0 && cr.hi) cls_row_copy(cr, b, T, W, lane);
+    }
+}
+
+// the class rows alone, for the forms whose attention is not attention_kernel<.., CLS> (ln_fold = 2); wave per frame
+__global__ __launch_bounds__(256) void cls_rows_kernel(int B, int T, int W, const ClsRows cr) {
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b < B) cls_row_copy(cr, b, T, W, threadIdx.x & 63);
 }
 
 static int g_attn_qt = 0;  // query tiles (of 16) per wave; 0 = by sequence length (debug knob overrides)
+
+// the class query of every (image, head) -> o [B, W] compact; the class rows of the stream travel as `cr` says.  Head dim 64
+// only (W = 64 H): the kernel's row strides are 64 H and 3 * 64 H.
+int attention_cls(const bf16_t* qkv, int B, int T, int H, int W, bf16_t* o, const ClsRows& cr, hipStream_t st) {
+    WISE_CHECK_ARG(qkv && o && B > 0 && T > 0 && H > 0 && (!cr.hi || (cr.hc && (!cr.rs || cr.rs_c) && (!cr.ncnt || cr.cnt))),
+                   "attention_cls: bad argument");
+    WISE_CHECK_ARG(W == H * 64, "attention_cls: head dim 64 only (W=%d, H=%d)", W, H);
+    const long long items = (long long)B * H;
+    hipLaunchKernelGGL((attention_kernel<1, false, 64, false, true>), dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, qkv, B, T, H, o,
+                       (const int*)nullptr, cr);
+    WISE_LAUNCH_CHECK("attention_kernel (class query)");
+    return WISE_OK;
+}
 
 int attention_bf16(const bf16_t* qkv, int B, int T, int H, bf16_t* o, hipStream_t st, bool causal, int dh, const int* lens) {
     WISE_CHECK_ARG(qkv && o && B > 0 && T > 0 && H > 0, "attention: bad argument");
@@ -1216,8 +1278,22 @@ int transformer_blocks(const BlockWeights& bw, int L, int W, int H, int F, int a
 // writes 4 bytes per element as before and NOTHING else touches the rows (the LayerNorm's pass over them is gone, and hi is
 // the next GEMM's operand as it stands), and no row's result depends on the batch it sits in (one epilogue implementation,
 // one reduction tree).  The attention output goes to `h`, which the unfolded form uses for the LayerNorm output.
+// The last block, when the caller keeps nothing but the class rows (`tail`, vit_forward_part): its QKV GEMM runs on every row
+// (the class query attends every key), the rest on the Bp compact class rows only — ln_fold = 1: class-query attention (which
+// also copies the class rows of the stream into tail->hc), out-projection, fc1, fc2; ln_fold = 2: the one-kernel attention
+// and out-projection on every row (W_o is stored in tile order, which the plain GEMM cannot read), then the class rows and
+// their row scales gathered, fc1, fc2.  Every GEMM returns a row's bits whatever the row count, so the class rows end as the
+// full block leaves them.
+struct ClsTail {
+    bf16_t* hc;       // [2, Bp, W] the class rows' hi + lo stream
+    bf16_t* o;        // [Bp, W] class attention output; then the fc1 rows [Bp, F]
+    float* stats;     // gemm_fold_stats_bytes(Bp, W): row scales, arrival counters, partial sums
+    bf16_t* hb;       // the head's ln_post rows [round_up(batch, 256), W] (pooled_head; `h` holds hc)
+    int Bp;
+};
 static int transformer_blocks_fold(const BlockWeights& bw, int L, int W, int H, int F, int act, int batch, int T, float* x,
-                                   bf16_t* h, bf16_t* qkv, bf16_t* a, float* stats, hipStream_t st, float eps, bool fuse_attn) {
+                                   bf16_t* h, bf16_t* qkv, bf16_t* a, float* stats, hipStream_t st, float eps, bool fuse_attn,
+                                   const ClsTail* tail) {
     const int M = batch * T, Mp = (M + 255) / 256 * 256;
     int rc;
     float* rstd = stats;                        // [Mp] row scales; arrival counters and partial sums behind them
@@ -1232,6 +1308,26 @@ static int transformer_blocks_fold(const BlockWeights& bw, int L, int W, int H, 
         const bf16_t* lwb = bw.wb + bw.per_layer_b * l;
         const float* lpf = bw.pf + bw.per_layer_f * l;
         if ((rc = gemm_fold_bf16(hi, lwb + bw.in_proj, lpf + bw.in_b, rstd, Mp, 3 * W, W, 0, qkv, st))) return rc;
+        if (tail && l == L - 1) {
+            const int Bp = tail->Bp;
+            const long long lc_off = (long long)Bp * W;
+            ClsRows cr;
+            cr.hi = hi; cr.lo_off = lo_off; cr.hc = tail->hc; cr.lc_off = lc_off;
+            cr.cnt = reinterpret_cast<int*>(tail->stats + Bp); cr.ncnt = (int)(gemm_fold_counters_bytes(Bp) / 4);
+            if (fuse_attn) {
+                if ((rc = attention_oproj_fold(qkv, batch, T, H, lwb + bw.out_proj, lpf + bw.out_b, hi, lo_off, rstd, eps, st))) return rc;
+                cr.rs = rstd; cr.rs_c = tail->stats;
+                hipLaunchKernelGGL(cls_rows_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, st, batch, T, W, cr);
+                WISE_LAUNCH_CHECK("cls_rows_kernel");
+            } else {
+                if ((rc = attention_cls(qkv, batch, T, H, W, tail->o, cr, st))) return rc;
+                if ((rc = gemm_fold_resid(tail->o, lwb + bw.out_proj, lpf + bw.out_b, Bp, W, W, tail->hc, lc_off, tail->stats, eps, st))) return rc;
+            }
+            if ((rc = gemm_fold_bf16(tail->hc, lwb + bw.c_fc, lpf + bw.fc_b, tail->stats, Bp, F, W, act == 0 ? 1 : (act == 1 ? 2 : 5), tail->o, st)))
+                return rc;
+            if ((rc = gemm_fold_resid(tail->o, lwb + bw.c_proj, lpf + bw.proj_b, Bp, W, F, tail->hc, lc_off, tail->stats, eps, st))) return rc;
+            break;
+        }
         if (fuse_attn) {   // ln_fold = 2: attention, out-projection, residual add and statistics of a frame in one workgroup
             if ((rc = attention_oproj_fold(qkv, batch, T, H, lwb + bw.out_proj, lpf + bw.out_b, hi, lo_off, rstd, eps, st))) return rc;
         } else {
@@ -1361,6 +1457,33 @@ static VitWs vit_ws(const VitDims& d, int B) {
     return w;
 }
 
+// (debug twin: wise_debug_set_vit_cls_tail(0) restores the full last block — the equality tests and same-call A/B runs)
+#ifdef WISE_DEBUG_KNOBS
+static int g_cls_tail = 1;
+#else
+constexpr int g_cls_tail = 1;
+#endif
+
+// Where the folded tower's class-row tail (transformer_blocks_fold) lives: in the regions its last block no longer needs at
+// full size — hc / lc in `h`; the class attention output, then the fc1 rows, at the start of `a` and the compact statistics
+// behind them; the head's ln_post rows in `qkv` behind its projection output.  hc / lc outlive the forward (the parity tap
+// reads them).  false: the fold is off, the debug switch says so, the head dim is not 64 (the class-query attention has no
+// head-dim-80 form: ViT-H/14), or a region is too small (mlp much narrower than width): the full last block runs.
+static bool cls_tail_layout(const VitDims& d, const VitWs& ws, int batch, unsigned char* wsb, ClsTail* t) {
+    if (!d.fold || d.arch != 0 || !g_cls_tail || d.W != d.H * 64) return false;
+    const size_t W = d.W, F = d.F, Bp = (size_t)(batch + 127) / 128 * 128, Bh = (size_t)(batch + 255) / 256 * 256;
+    const size_t oa = align_up(Bp * std::max(W, F) * 2, 256), e_b = align_up(Bh * d.D * 4, 256);
+    if (2 * Bp * W * 2 > ws.qkv - ws.h || oa + gemm_fold_stats_bytes((int)Bp, d.W) > ws.rstd - ws.a || (size_t)batch * W * 4 > ws.rstd - ws.a ||
+        e_b + Bh * W * 2 > ws.a - ws.qkv)
+        return false;
+    t->hc = reinterpret_cast<bf16_t*>(wsb + ws.h);
+    t->o = reinterpret_cast<bf16_t*>(wsb + ws.a);
+    t->stats = reinterpret_cast<float*>(wsb + ws.a + oa);
+    t->hb = reinterpret_cast<bf16_t*>(wsb + ws.qkv + e_b);
+    t->Bp = (int)Bp;
+    return true;
+}
+
 template <int NV>
 static void launch_embed(const float* po, const float* cls, const float* pos, const float* w, const float* b, int rows,
                          int T, int W, float* x, hipStream_t st, bf16_t* hcopy, float* rstd_out, long long lo_off) {
@@ -1368,14 +1491,14 @@ static void launch_embed(const float* po, const float* cls, const float* pos, co
                        1e-5f, x, hcopy, rstd_out, lo_off);
 }
 
-// rows r * stride of a hi + lo residual stream -> fp32 [n, W] (the class rows in front of ln_post; the parity tap)
+// rows r * stride of a hi + lo residual stream -> fp32 rows r * ostride of out (the class rows in front of ln_post; the parity tap)
 __global__ __launch_bounds__(256) void hilo_rows_kernel(const bf16_t* __restrict__ hi, long long lo_off, int n, int stride, int W,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, int ostride) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)n * W) return;
     const int r = (int)(i / W), c = (int)(i % W);
     const size_t src = (size_t)r * stride * W + c;
-    out[i] = bf16_to_f32(hi[src]) + bf16_to_f32(hi[src + lo_off]);
+    out[(size_t)r * ostride * W + c] = bf16_to_f32(hi[src]) + bf16_to_f32(hi[src + lo_off]);
 }
 
 // one contiguous part of the batch on one stream; `wsb` is that part's own workspace region
@@ -1445,9 +1568,11 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
     const BlockWeights bw = {wb + o.layer0_b, o.per_layer_b, o.in_proj, o.out_proj, o.c_fc, o.c_proj,
                              pf + o.layer0_f, o.per_layer_f, o.ln1_w, o.ln1_b, o.in_b, o.out_b, o.ln2_w, o.ln2_b,
                              o.fc_b, o.proj_b};
+    ClsTail tail;
+    const bool cls_tail = cls_tail_layout(d, ws, batch, wsb, &tail);
     if (d.fold) {
         if ((rc = transformer_blocks_fold(bw, d.L, W, d.H, d.F, cfg->act, batch, d.T, x, h, qkv, a,
-                                          reinterpret_cast<float*>(wsb + ws.rstd), st, 1e-5f, d.fold == 2)))
+                                          reinterpret_cast<float*>(wsb + ws.rstd), st, 1e-5f, d.fold == 2, cls_tail ? &tail : nullptr)))
             return rc;
     } else if ((rc = transformer_blocks(bw, d.L, W, d.H, d.F, cfg->act, batch, d.T, false, x, h, qkv, a, st,
                                         d.arch == 1 ? 1e-6f : 1e-5f)))
@@ -1474,10 +1599,14 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
     if (d.fold) {   // the class rows of the hi + lo stream as fp32 [batch, W] (in `a`, free now), then the same head with T = 1
         float* xc = reinterpret_cast<float*>(a);
         const long long n = (long long)batch * W;
-        hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(x),
-                           (long long)ws.Mp * W, batch, d.T, W, xc);
+        if (cls_tail)   // the compact rows the last block left
+            hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tail.hc, (long long)tail.Bp * W,
+                               batch, 1, W, xc, 1);
+        else
+            hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(x),
+                               (long long)ws.Mp * W, batch, d.T, W, xc, 1);
         WISE_LAUNCH_CHECK("hilo_rows_kernel");
-        return pooled_head(xc, pf + o.ln_post_w, pf + o.ln_post_b, wb + o.projT, batch, 1, W, d.D, nullptr, h,
+        return pooled_head(xc, pf + o.ln_post_w, pf + o.ln_post_b, wb + o.projT, batch, 1, W, d.D, nullptr, cls_tail ? tail.hb : h,
                            reinterpret_cast<float*>(qkv), out, st);
     }
     if ((rc = pooled_head(x, pf + o.ln_post_w, pf + o.ln_post_b, wb + o.projT, batch, d.T, W, d.D, nullptr, h,
@@ -1663,8 +1792,18 @@ extern "C" int wise_vit_tap_residual(const wise_vit_config* cfg, int batch, cons
         if (d.fold) {
             const long long n = (long long)ws.M * d.W;
             hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                               reinterpret_cast<const bf16_t*>(wsb + base + ws.x), (long long)ws.Mp * d.W, ws.M, 1, d.W, dp);
+                               reinterpret_cast<const bf16_t*>(wsb + base + ws.x), (long long)ws.Mp * d.W, ws.M, 1, d.W, dp, 1);
             WISE_LAUNCH_CHECK("hilo_rows_kernel");
+            ClsTail t;
+            if (cls_tail_layout(d, ws, hi - lo, const_cast<unsigned char*>(wsb + base), &t)) {
+                // the last block ran for the class rows only: theirs come from the compact stream; every other row holds what
+                // block L-2 left (ln_fold = 1), or that plus the last block's attention half (ln_fold = 2: its attention and
+                // out-projection kernel still runs on every row)
+                const long long nc = (long long)(hi - lo) * d.W;
+                hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t.hc,
+                                   (long long)t.Bp * d.W, hi - lo, 1, d.W, dp, d.T);
+                WISE_LAUNCH_CHECK("hilo_rows_kernel");
+            }
         } else {
             hipError_t e = hipMemcpyAsync(dp, wsb + base + ws.x, (size_t)ws.M * d.W * 4, hipMemcpyDeviceToDevice,
                                           (hipStream_t)stream);
@@ -1687,6 +1826,12 @@ extern "C" int wise_attention_bf16(const uint16_t* qkv, int B, int T, int H, uin
 
 #ifdef WISE_DEBUG_KNOBS
 extern "C" int wise_debug_set_gemm_flags(int flags) { wise::g_ablate = flags & 6; return 0; }   // the ablation bits 2 and 4
+// 0: the folded towers run their last block in full (every row); 1 (default): for the class rows only
+extern "C" int wise_debug_set_vit_cls_tail(int on) { wise::g_cls_tail = on ? 1 : 0; return 0; }
+// attention_kernel's class-query form alone: o [B, W] = row 0 of every frame's attention output
+extern "C" int wise_debug_attention_cls_bf16(const uint16_t* qkv, int B, int T, int H, uint16_t* o, void* stream) {
+    return wise::attention_cls(qkv, B, T, H, H * 64, o, wise::ClsRows(), (hipStream_t)stream);
+}
 extern "C" int wise_debug_ao_set(int flags) { wise::g_ao_dbg = flags & 15; return 0; }
 extern "C" int wise_debug_ao_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(wise::g_ao_stamps), sizeof(unsigned long long) * 96) == hipSuccess ? 0 : -1;

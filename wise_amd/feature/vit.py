@@ -369,7 +369,10 @@ class VitEngine:
         return PendingEmbeddings(out, done)
 
     def residual(self, batch: int) -> torch.Tensor:
-        """Residual stream [B*T, W] fp32 left by the last forward (parity tap)."""
+        """Residual stream [B*T, W] fp32 left by the last forward (parity tap).  After a folded forward with head dim 64 the last
+        block ran for the class rows only: those rows hold its output.  Every other row holds block L-2's output (ln_fold = 1),
+        or that plus the last block's attention residual (ln_fold = 2, whose attention + out-projection kernel still runs on
+        every row)."""
         out = torch.empty(batch * self.spec.tokens, self.spec.width, dtype=torch.float32, device=self.device)
         _lib.check(self.lib.wise_vit_tap_residual(C.byref(self.cfg), batch, self._ws.data_ptr(), out.data_ptr(),
                                                   _lib.stream_ptr()), "wise_vit_tap_residual")
