@@ -33,7 +33,8 @@ const char* wise_last_error(void);
  * caption encoder — and the wise_cnn14_* entry points; 5: wise_ip_shadow_i8 / wise_ip_topk_shadow8_f32 (int8 shadow,
  * norms[4]), wise_ip_topk_shadow_workspace_bytes depends on nq and returns 0 under 2^18 rows, two-stage k up to 1024; and,
  * added within 5: wise_vit_config.ln_fold, the wise_gemm_fold_* entry points, wise_attention_oproj_fold, wise_htsat_forward2,
- * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*). */
+ * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points
+ * and wise_ivfpq_scan). */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -184,6 +185,48 @@ int wise_ivf_reseed(float* sums, const int64_t* empty, const int64_t* donor, int
 int wise_ivf_gather_rows(const float* x, const int64_t* idx, int64_t n, int d, float* out, void* stream);
 int wise_ivf_gather_i64(const int64_t* a, const int64_t* idx, int64_t n, int64_t* out, void* stream);
 int wise_ivf_expand_lists(const int64_t* list_off, int nlist, int64_t* out, void* stream);
+/* (ABI 5, additive) IndexIVFPQ: inverted lists of 8-bit product-quantizer codes — faiss.IndexIVFPQ(IndexFlatIP(d), d, nlist, m, 8,
+ * METRIC_INNER_PRODUCT) with by_residual (the index family of docs/Search-Index-Evaluation.md:105-123).  A row x of list l is kept as
+ * m bytes: its residual x - c_l cut into m sub-vectors of dsub = d / m floats, each replaced by the number of its nearest (L2)
+ * codeword.  codebooks [m, 256, dsub] fp32 are shared by all lists.  Limits (WISE_E_UNSUPPORTED otherwise): d % m == 0, m <= 128,
+ * dsub even in [2, 96]; the scan: k <= 2048, nprobe <= 2048, nq <= 65535.  All deterministic: the same inputs give the same bits.
+ *   wise_pq_residuals: out[i, :] = x[i, :] - centroids[assign[i], :] (assign values in [0, nlist)).
+ *   wise_pq_encode: codes[i, j] = argmax_c (r_ij . cb_jc - 1/2 ||cb_jc||^2), both products index-ordered fmaf chains from 0, ties
+ *     to the lowest c.  The encoder of add_with_ids and the assignment step of training.
+ *   wise_pq_update: one Lloyd update; codebooks_out[j, c, :] = the mean of the sub-vectors j of the rows with codes[i, j] == c,
+ *     summed in ascending row order in fp32 and divided by the count; a codeword no row chose copies codebooks_in (which must not
+ *     alias codebooks_out).
+ *   wise_pq_lut: lut[q, j, c] = Q[q, j-th sub-vector] . cb_jc, an index-ordered fmaf chain over dsub starting at 0.
+ *   wise_pq_bias: bias[q, p] = Q[q, :] . centroids[probes[q, p], :] (0 for a probe < 0): the list's share of a row's score.
+ *   wise_pq_gather_codes: out[i, :] = codes[idx[i], :] (rows of m bytes).
+ *   wise_pq_find: pos[i] = the position of query_ids[i] in ids [N] (-1: absent).
+ *   wise_pq_decode: out[i, :] = centroids[l, :] + concat_j cb[j, codes[pos[i], j], :] in fp32, l the list holding position pos[i]
+ *     (list_off [nlist + 1]); a position outside [0, N) gives a row of NaN.  IndexIVFPQ::reconstruct_batch. */
+int wise_pq_residuals(const float* x, const float* centroids, const int64_t* assign, int64_t n, int d, int nlist, float* out,
+                      void* stream);
+int wise_pq_encode(const float* resid, const float* codebooks, int64_t n, int d, int m, uint8_t* codes, void* stream);
+int wise_pq_update(const float* resid, const uint8_t* codes, int64_t n, int d, int m, const float* codebooks_in,
+                   float* codebooks_out, void* stream);
+int wise_pq_lut(const float* Q, const float* codebooks, int nq, int d, int m, float* lut, void* stream);
+int wise_pq_bias(const float* Q, const float* centroids, const int64_t* probes, int nq, int nprobe, int nlist, int d, float* bias,
+                 void* stream);
+int wise_pq_gather_codes(const uint8_t* codes, const int64_t* idx, int64_t n, int m, uint8_t* out, void* stream);
+int wise_pq_find(const int64_t* ids, int64_t N, const int64_t* query_ids, int n, int64_t* pos, void* stream);
+int wise_pq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                   const float* centroids, const float* codebooks, int d, int m, float* out, void* stream);
+/* The second stage of an IndexIVFPQ search (IndexIVFPQ::search behind self.index.search, src/index/feature_search_index.py:113):
+ *   codes    [N,m] uint8 grouped by list (list l occupies rows list_off[l] .. list_off[l+1]-1), 16-byte aligned
+ *   ids      [N] int64 external ids in the same order (NULL => the position)
+ *   lut      [nq,m,256] fp32 from wise_pq_lut, 16-byte aligned;  probes [nq,nprobe] int64, entries < 0 are skipped
+ *   bias     [nq,nprobe] fp32, the coarse score q . c_l of each probed list (wise_pq_bias)
+ * THE ORDER OF THE ARITHMETIC IS PART OF THE CONTRACT: a row's score is acc = bias, then acc += lut[q, j, code_j] for
+ * j = 0 .. m-1, in fp32, in that order — the result is reproducible bit for bit by a float32 loop on the host.
+ * outD/outI as wise_ivf_scan_f32 (descending scores, (-3.4028235e38, -1) padding).  Ties: the row that comes first in codes wins.
+ * Workspace: wise_ivfpq_scan_workspace_bytes(nq, nprobe, k, m) bytes (0: unsupported shape). */
+size_t wise_ivfpq_scan_workspace_bytes(int nq, int nprobe, int k, int m);
+int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids, const float* lut,
+                    int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD, int64_t* outI, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

@@ -105,6 +105,16 @@ SIGNATURES = {
     "wise_ivf_gather_rows": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "wise_ivf_gather_i64": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "wise_ivf_expand_lists": (_i, [_vp, _i, _vp, _vp]),
+    "wise_pq_residuals": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "wise_pq_encode": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "wise_pq_update": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "wise_pq_lut": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "wise_pq_bias": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "wise_pq_gather_codes": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "wise_pq_find": (_i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    "wise_pq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "wise_ivfpq_scan_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wise_ivfpq_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wise_mlp_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "wise_mlp_stream_ln": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -18,67 +18,6 @@
 
 namespace wise {
 
-__device__ __forceinline__ void wave_lds_fence() {
-    // one wave executes its DS instructions in order; this only stops the compiler reordering them
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Sort buf[0..cap) descending by one wave (cap = power of two >= 64).
-__device__ void wave_bitonic_desc(volatile u64* buf, int cap, int lane) {
-    for (int size = 2; size <= cap; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int t = lane; t < (cap >> 1); t += 64) {
-                int pos = ((t / stride) * (stride << 1)) + (t % stride);
-                int par = pos + stride;
-                bool desc = ((pos & size) == 0);
-                u64 a = buf[pos], b = buf[par];
-                bool sw = desc ? (a < b) : (a > b);
-                if (sw) { buf[pos] = b; buf[par] = a; }
-            }
-            wave_lds_fence();
-        }
-    }
-}
-
-// A wave-private running top-k list in LDS.
-struct WaveList {
-    volatile u64* buf;  // cap entries
-    int cap, k, cnt;
-    u64 tau;  // keys <= tau cannot enter the top-k any more
-    __device__ void init(u64* b, int cap_, int k_, int lane) {
-        buf = b; cap = cap_; k = k_; cnt = 0; tau = 0;
-        for (int i = lane; i < cap; i += 64) buf[i] = 0;
-        wave_lds_fence();
-    }
-    __device__ void compact(int lane) {
-        for (int i = cnt + lane; i < cap; i += 64) buf[i] = 0;
-        wave_lds_fence();
-        wave_bitonic_desc(buf, cap, lane);
-        if (cnt >= k) { cnt = k; tau = buf[k - 1]; }
-    }
-    // every lane may carry one candidate key (pass=false -> none); wave-uniform control flow
-    __device__ void offer(bool pass, u64 key, int lane, int max_new) {
-        u64 mask = __ballot(pass);
-        if (mask == 0) return;
-        int n = __popcll(mask);
-        if (cnt + n > cap) {
-            compact(lane);
-            // the threshold moved: re-test
-            pass = pass && (key > tau);
-            mask = __ballot(pass);
-            if (mask == 0) return;
-            n = __popcll(mask);
-        }
-        int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
-        if (pass) buf[pos] = key;
-        cnt += n;
-        wave_lds_fence();
-        (void)max_new;
-    }
-};
-
 // ------------------------------------------------------------------------------------------------
 // scan kernel: NV = float4 chunks per lane per row (ceil(d/256)), NQ queries, R rows per group
 // ------------------------------------------------------------------------------------------------
@@ -1852,6 +1791,22 @@ extern "C" int wise_ip_topk_f32(const float* X, int64_t N, int d, const float* Q
     return WISE_OK;
 }
 
+// the last step of the list scans (wise_ivf_scan_f32, wise_ivfpq_scan): part [P][nq][k] keys -> outD/outI [nq][k]
+int wise::topk_list_cap(int k) { return list_cap(k); }
+int wise::merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
+                       hipStream_t st) {
+    const int cap = list_cap(k);
+    int mw = 8192 / cap;
+    if (mw < 1) mw = 1;
+    if (mw > 16) mw = 16;
+    const size_t mlds = (size_t)mw * cap * 8;
+    if (mlds > 48 * 1024)
+        raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
+    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, P, nq, k, cap, ids, 0ll, outD, outI, 0);
+    WISE_LAUNCH_CHECK("merge_keys_kernel");
+    return WISE_OK;
+}
+
 extern "C" size_t wise_ivf_scan_workspace_bytes(int nq, int nprobe, int k) {
     if (nq < 1 || nprobe < 1 || k < 1 || k > 2048) return 0;
     return align_up((size_t)nq * nprobe * k * sizeof(u64), 256);
@@ -1889,16 +1844,8 @@ extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t
         default: set_error("ivf_scan: no kernel for d=%d", d); return WISE_E_INVALID;
     }
     WISE_LAUNCH_CHECK("ip_scan_kernel<seg>");
-    int mw = 8192 / cap;
-    if (mw < 1) mw = 1;
-    if (mw > 16) mw = 16;
-    const size_t mlds = (size_t)mw * cap * 8;
-    if (mlds > 48 * 1024)
-        raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
-    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, nprobe, nq, k, cap,
-                       reinterpret_cast<const long long*>(ids), 0ll, outD, reinterpret_cast<long long*>(outI), 0);
-    WISE_LAUNCH_CHECK("merge_keys_kernel");
-    return WISE_OK;
+    return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD,
+                              reinterpret_cast<long long*>(outI), st);
 }
 
 // Rank-local form of wise_ivf_scan_f32 for a slice of the list-major array (list_off clipped to the slice): the probes

@@ -19,6 +19,73 @@ __device__ __forceinline__ u64 make_key(float score, unsigned row) {
     return ((u64)f32_order(score) << 32) | (u64)(0xFFFFFFFFu - row);
 }
 
+__device__ __forceinline__ void wave_lds_fence() {
+    // one wave executes its DS instructions in order; this only stops the compiler reordering them
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Sort buf[0..cap) descending by one wave (cap = power of two >= 64).
+__device__ inline void wave_bitonic_desc(volatile u64* buf, int cap, int lane) {
+    for (int size = 2; size <= cap; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int t = lane; t < (cap >> 1); t += 64) {
+                int pos = ((t / stride) * (stride << 1)) + (t % stride);
+                int par = pos + stride;
+                bool desc = ((pos & size) == 0);
+                u64 a = buf[pos], b = buf[par];
+                bool sw = desc ? (a < b) : (a > b);
+                if (sw) { buf[pos] = b; buf[par] = a; }
+            }
+            wave_lds_fence();
+        }
+    }
+}
+
+// A wave-private running top-k list in LDS.
+struct WaveList {
+    volatile u64* buf;  // cap entries
+    int cap, k, cnt;
+    u64 tau;  // keys <= tau cannot enter the top-k any more
+    __device__ void init(u64* b, int cap_, int k_, int lane) {
+        buf = b; cap = cap_; k = k_; cnt = 0; tau = 0;
+        for (int i = lane; i < cap; i += 64) buf[i] = 0;
+        wave_lds_fence();
+    }
+    __device__ void compact(int lane) {
+        for (int i = cnt + lane; i < cap; i += 64) buf[i] = 0;
+        wave_lds_fence();
+        wave_bitonic_desc(buf, cap, lane);
+        if (cnt >= k) { cnt = k; tau = buf[k - 1]; }
+    }
+    // every lane may carry one candidate key (pass=false -> none); wave-uniform control flow
+    __device__ void offer(bool pass, u64 key, int lane, int max_new) {
+        u64 mask = __ballot(pass);
+        if (mask == 0) return;
+        int n = __popcll(mask);
+        if (cnt + n > cap) {
+            compact(lane);
+            // the threshold moved: re-test
+            pass = pass && (key > tau);
+            mask = __ballot(pass);
+            if (mask == 0) return;
+            n = __popcll(mask);
+        }
+        int pos = cnt + __popcll(mask & ((1ull << lane) - 1ull));
+        if (pass) buf[pos] = key;
+        cnt += n;
+        wave_lds_fence();
+        (void)max_new;
+    }
+};
+
+// fold part [P][nq][k] keys (per-block lists of a list scan) into outD/outI [nq][k], ids looked up at the end
+// (merge_keys_kernel, ip_topk.hip); topk_list_cap(k) = entries of a WaveList that keeps k keys
+int topk_list_cap(int k);
+int merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
+                       hipStream_t st);
+
 // batched (MFMA) scan, ip_topk_mfma.hip
 constexpr int MFMA_QB = 32;   // queries per pass (the N of v_mfma_f32_32x32x2_f32)
 constexpr int MFMA_KL = 16;   // per-lane list length: the path serves k <= 16

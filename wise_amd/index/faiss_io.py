@@ -22,6 +22,14 @@ same way (write_ivf_flat_ip / read_ivf_flat_ip below):
     u32  'full' | u64 nlist | u64 sizes[nlist]        (or 'sprs' | u64 2*m | (list, size) pairs when most lists are empty)
     per non-empty list: u8 codes[size*code_size] (the fp32 rows) | i64 ids[size]
 
+The file of index types 'IndexIVFPQ<m>' (write_ivf_pq_ip / read_ivf_pq_ip) restates faiss's IndexIVFPQ record:
+
+    u32  'IwPQ'                                   IndexIVFPQ fourcc
+    header | u64 nlist | u64 nprobe | 'IxFI' quantizer | direct map           exactly as in the 'IwFl' file
+    u8   by_residual (1) | u64 code_size (= m)
+    u64  d | u64 M | u64 nbits (8) | u64 n_floats (= 256*d) | f32[M*256*dsub] the ProductQuantizer record (centroids)
+    'ilar' array inverted lists with code_size = m: per non-empty list u8 codes[size*m] | i64 ids[size]
+
 faiss is not in the container, so these layouts are UNPINNED against a real faiss binary; the round
 trip is pinned by tests/test_feature_store_index_io.py.  The rows are memory-mapped on read so a
 158 GiB index (docs/Search-Index-Evaluation.md:109) streams to the GPU without a host copy.
@@ -145,11 +153,12 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
             ids[a:b].tofile(f)
 
 
-def _read_ivf_head(f, p):
-    """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload)."""
+def _read_ivf_head(f, p, pq: bool = False):
+    """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload).
+    pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks)."""
     (cc,) = struct.unpack("<I", f.read(4))
-    if cc != _fourcc("IwFl"):
-        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFFlat")
+    if cc != _fourcc("IwPQ" if pq else "IwFl"):
+        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {'IndexIVFPQ' if pq else 'IndexIVFFlat'}")
     hdr = f.read(_HDR_SIZE + 4)
     d, n, metric, off = _read_header(hdr, 0)
     f.seek(4 + off)
@@ -171,8 +180,16 @@ def _read_ivf_head(f, p):
     if dm_type == 2:  # hashtable pairs
         (npairs,) = struct.unpack("<Q", f.read(8))
         f.seek(16 * npairs, 1)
+    m = codebooks = None
+    if pq:
+        by_residual, code_size_pq = struct.unpack("<BQ", f.read(9))
+        dp, m, nbits, cnt = struct.unpack("<QQQQ", f.read(32))
+        if by_residual != 1 or nbits != 8 or dp != d or m < 1 or d % m or code_size_pq != m or cnt != 256 * d:
+            raise RuntimeError(f"{p}: unsupported IndexIVFPQ (by_residual={by_residual}, d={dp}, M={m}, nbits={nbits}, "
+                               f"code_size={code_size_pq}, {cnt} codebook values)")
+        codebooks = np.fromfile(f, dtype=np.float32, count=cnt).reshape(m, 256, d // m)
     il, nl2, code_size = struct.unpack("<IQQ", f.read(20))
-    if il != _fourcc("ilar") or nl2 != nlist or code_size != 4 * d:
+    if il != _fourcc("ilar") or nl2 != nlist or code_size != (m if pq else 4 * d):
         raise RuntimeError(f"{p}: unexpected inverted lists (type 0x{il:08x}, code size {code_size})")
     (lt, vn) = struct.unpack("<IQ", f.read(12))
     sizes = np.zeros(nlist, dtype=np.int64)
@@ -186,6 +203,8 @@ def _read_ivf_head(f, p):
     list_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
     if list_off[-1] != n:
         raise RuntimeError(f"{p}: lists hold {list_off[-1]} rows, header says {n}")
+    if pq:
+        return centroids, list_off, int(nprobe), f.tell(), int(m), codebooks
     return centroids, list_off, int(nprobe), f.tell()
 
 
@@ -254,6 +273,64 @@ def read_ivf_flat_ip_range(path, lo: int, hi: int):
             f.seek(base + (s1 - s0) * 4 * d + (a - s0) * 8)
             ids[a - lo:b - lo] = np.fromfile(f, dtype=np.int64, count=b - a)
     return {"centroids": centroids, "X": X, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
+            "nprobe": nprobe}
+
+
+def write_ivf_pq_ip(path, centroids: np.ndarray, codebooks: np.ndarray, codes: np.ndarray, ids: np.ndarray,
+                    list_off: np.ndarray, nprobe: int = 1) -> None:
+    """codes [n,m] uint8 / ids hold the lists back to back; codebooks [m,256,d/m] fp32 (8-bit codes, by_residual)."""
+    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    nlist, d = centroids.shape
+    n, m = codes.shape
+    assert d % m == 0 and codebooks.shape == (m, 256, d // m)
+    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IwPQ")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<QQ", nlist, nprobe))
+        f.write(struct.pack("<I", _fourcc("IxFI")))
+        f.write(_header(d, nlist))
+        f.write(struct.pack("<Q", nlist * d))
+        centroids.tofile(f)
+        f.write(struct.pack("<BQ", 0, 0))
+        f.write(struct.pack("<BQ", 1, m))                        # by_residual, code_size
+        f.write(struct.pack("<QQQQ", d, m, 8, 256 * d))          # ProductQuantizer: d, M, nbits, centroids
+        codebooks.tofile(f)
+        f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, m))
+        nonzero = np.flatnonzero(sizes)
+        if len(nonzero) > nlist // 2:
+            f.write(struct.pack("<IQ", _fourcc("full"), nlist))
+            sizes.tofile(f)
+        else:
+            f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
+            np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
+        for l in nonzero:
+            a, b = int(list_off[l]), int(list_off[l + 1])
+            codes[a:b].tofile(f)
+            ids[a:b].tofile(f)
+
+
+def read_ivf_pq_ip(path):
+    """-> dict(centroids [nlist,d], codebooks [m,256,d/m], codes [n,m] uint8, ids [n], list_off [nlist+1], nprobe), the
+    lists back to back in list order."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        centroids, list_off, nprobe, _, m, codebooks = _read_ivf_head(f, p, pq=True)
+        n = int(list_off[-1])
+        codes = np.empty((n, m), dtype=np.uint8)
+        ids = np.empty((n,), dtype=np.int64)
+        for l in np.flatnonzero(np.diff(list_off)):
+            a, b = int(list_off[l]), int(list_off[l + 1])
+            codes[a:b] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
+            ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
+    return {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off,
             "nprobe": nprobe}
 
 

@@ -11,7 +11,10 @@ Same constructor contract (asserts on 'features_dir'/'index_dir'), prompts, file
 (`{index_dir}/{media_type}-{index_type}.faiss`), skip-if-exists create, `load_index` that also
 builds the FeatureExtractor, and the prompt quirks of `search`.  Both index types the
 reference offers are built: `IndexFlatIP` (exhaustive, the hot path) and `IndexIVFFlat` (approximate; cell count
-and training-sample size chosen as at feature_search_index.py:55-59, k-means and list scan on the GPU).
+and training-sample size chosen as at feature_search_index.py:55-59, k-means and list scan on the GPU).  A third,
+`IndexIVFPQ<m>` (for example `IndexIVFPQ64`; bare `IndexIVFPQ` = m = d / 4), is the IVF+PQ family of the reference's index
+study (docs/Search-Index-Evaluation.md:105-123): the same coarse stage over lists of m-byte codes (wise_amd/index/ivf_pq.py).
+Under a process group it behaves as unsharded IndexIVFFlat does: rank 0 builds, every rank loads the whole (small) file.
 
 **One process per GPU** (the reference has no distributed path).  When `torch.distributed` is initialised
 with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the flat index by rows:
@@ -45,6 +48,7 @@ from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
+from .ivf_pq import IVFPQIPIndex, check_pq_shape
 from .search_index import SearchIndex
 from .sharded import ShardedFlatIPIndex, ShardedIVFFlatIPIndex, shard_range
 
@@ -57,6 +61,28 @@ def _dist_rank_world():
         rank, world = dist.get_rank(), dist.get_world_size()
         return rank, world, world > 1 or os.environ.get('WISE_SHARDED_INDEX') == '1'
     return 0, 1, False
+
+
+def parse_ivfpq_type(index_type, feature_dim=None):
+    """m of 'IndexIVFPQ<m>' ('IndexIVFPQ64' -> 64; the bare name -> d / 4, the finest code the m <= 128 limit allows at
+    d = 512), None for any other index type.  With feature_dim the shape is checked (ValueError)."""
+    if not index_type.startswith('IndexIVFPQ'):
+        return None
+    tail = index_type[len('IndexIVFPQ'):]
+    if tail and not tail.isdigit():
+        return None
+    if tail:
+        m = int(tail)
+    elif feature_dim is None:
+        return 0
+    else:
+        m = feature_dim // 4
+        if m > 128:
+            raise ValueError(f'IndexIVFPQ: the default m = d / 4 = {m} at d = {feature_dim} exceeds the limit m <= 128; '
+                             f'name the code size, IndexIVFPQ<m> (for example IndexIVFPQ{feature_dim // 8})')
+    if feature_dim is not None:
+        check_pq_shape(feature_dim, m)
+    return m
 
 
 def _sharded_ivf_on():
@@ -117,10 +143,12 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        if index_type not in ('IndexFlatIP', 'IndexIVFFlat'):
-            raise NotImplementedError(f'{index_type}: IndexFlatIP and IndexIVFFlat are the index types WISE builds')
+        is_pq = parse_ivfpq_type(index_type) is not None
+        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq:
+            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> are the index types '
+                                      f'WISE builds')
         self.index_type = index_type
-        if sharded and index_type == 'IndexIVFFlat' and not sharded_ivf and rank != 0:
+        if sharded and (index_type == 'IndexIVFFlat' or is_pq) and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
@@ -130,6 +158,7 @@ class FeatureSearchIndex(SearchIndex):
             feature_store.enable_read(shard_shuffle=False)
         feature_count = feature_store.feature_count
         feature_dim = feature_store.feature_dim
+        pq_m = parse_ivfpq_type(index_type, feature_dim) if is_pq else None      # a bad shape is refused before any row is read
 
         # the on-disk index is assembled on the host (I/O-bound: tar + unpickle per vector), 512 at a time
         X = np.empty((feature_count, feature_dim), dtype=np.float32)
@@ -145,7 +174,7 @@ class FeatureSearchIndex(SearchIndex):
             self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world)
             print(f'  saved index part to {index_fn}')
             return
-        if index_type == 'IndexIVFFlat':
+        if index_type == 'IndexIVFFlat' or is_pq:
             cell_count = reference_nlist(n)
             train_count = min(n, 100 * cell_count)
             # the reference trains on the first train_count vectors of a shard-shuffled pass (:62-69); a seeded
@@ -153,12 +182,16 @@ class FeatureSearchIndex(SearchIndex):
             sample = np.random.default_rng(1234).permutation(n)[:train_count]
             sample.sort()
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
-            ivf = IVFFlatIPIndex(feature_dim, cell_count)
-            ivf.train(X[sample])
+            ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
+            ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
-            c, Xs, ids_s, off = ivf.lists_host()
-            faiss_io.write_ivf_flat_ip(index_fn, c, Xs, ids_s, off, nprobe=ivf.nprobe)
+            if is_pq:
+                c, cb, codes, ids_s, off = ivf.lists_host()
+                faiss_io.write_ivf_pq_ip(index_fn, c, cb, codes, ids_s, off, nprobe=ivf.nprobe)
+            else:
+                c, Xs, ids_s, off = ivf.lists_host()
+                faiss_io.write_ivf_flat_ip(index_fn, c, Xs, ids_s, off, nprobe=ivf.nprobe)
         else:
             faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
         print(f'  saved index to {index_fn}')
@@ -268,6 +301,14 @@ class FeatureSearchIndex(SearchIndex):
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwPQ':
+            import torch                             # small: every rank of a process group loads the whole file
+            f = faiss_io.read_ivf_pq_ip(index_fn)
+            index = IVFPQIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            index.nprobe = f["nprobe"]
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             import torch
             f = faiss_io.read_ivf_flat_ip(index_fn)
