@@ -99,7 +99,7 @@ def _emulate(c, X, ids, off, Q, nprobe, k, worlds):
     full.adopt_lists(_dev(X), _dev(ids), _dev(off))
     Qd = _dev(Q)
     probes = full.probes_device(Qd, nprobe).contiguous()
-    Xd, idd, offd = full._X, full._ids, full._list_off
+    Xd, idd, offd = full._lists.data, full._lists.ids, full._lists.list_off
     Df, If = _scan_full(Xd, idd, offd, Qd, probes, k)
     pr = probes.cpu().numpy()
     for W in worlds:

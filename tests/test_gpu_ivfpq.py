@@ -240,7 +240,7 @@ def test_index_search_equals_the_restatement_on_its_own_state():
     for nprobe in (8, nlist):
         idx.nprobe = nprobe
         D, I = idx.search(Q, k)
-        probes = idx._coarse.probes_device(dev(Q), nprobe).cpu().numpy()
+        probes = idx.probes_device(dev(Q), nprobe).cpu().numpy()
         bias = np.take_along_axis(Q.astype(np.float64) @ c.astype(np.float64).T, np.maximum(probes, 0), axis=1).astype(np.float32)
         Do, Io = ivfpq_ref.scan(codes, off, ids_s, ivfpq_ref.lut(Q, cb).astype(np.float32), probes, bias, k)
         check_against(D, I, Do, Io)
@@ -315,7 +315,7 @@ def test_training_quality_against_the_restatement(golden_dir):
     c, _, _, ids_s, off = idx.lists_host()
     Xs = X[ids_s]
     codes_ref = ivfpq_ref.encode(Xs - c[ivfpq_ref.list_of_rows(off)], cb_ref.astype(np.float32))
-    probes = idx._coarse.probes_device(dev(Q), nprobe).cpu().numpy()
+    probes = idx.probes_device(dev(Q), nprobe).cpu().numpy()
     bias = np.take_along_axis(Q.astype(np.float64) @ c.astype(np.float64).T, probes, axis=1).astype(np.float32)
     _, Ir = ivfpq_ref.scan(codes_ref, off, ids_s, ivfpq_ref.lut(Q, cb_ref.astype(np.float32)).astype(np.float32), probes, bias, k)
     rec_gpu = np.mean([len(set(I[q]) & set(If[q])) / k for q in range(64)])

@@ -88,11 +88,11 @@ def main():
     pq._finalize()
     torch.cuda.synchronize()
     print(f"{N} x {d}, nlist {nlist}, m {m}: coarse k-means {t_coarse:.1f} s, codebooks {t_pq:.1f} s, all {time.time() - t0:.1f} s", flush=True)
-    flat_bytes = sum(t.numel() * t.element_size() for t in (flat._X, flat._ids, flat._list_off, flat.centroids))
+    flat_bytes = flat._lists.nbytes() + flat.centroids.numel() * flat.centroids.element_size()
     res = {"rows": N, "dim": d, "nlist": nlist, "m": m, "k": k, "iters": args.iters, "device": torch.cuda.get_device_name(0),
            "train_seconds": {"coarse_kmeans": t_coarse, "codebooks": t_pq},
            "hbm_bytes": {"IndexIVFFlat": flat_bytes, f"IndexIVFPQ{m}": pq.hbm_bytes()}, "points": []}
-    exact = FlatIPIndex(d).adopt(flat._X, flat._ids, id_base=0)
+    exact = FlatIPIndex(d).adopt(flat._lists.data, flat._lists.ids, id_base=0)
     _, If = exact.search_device(Q, k)
     If = If.cpu().numpy()
     for nprobe in (32, 1024):

@@ -1794,7 +1794,7 @@ extern "C" int wise_ip_topk_f32(const float* X, int64_t N, int d, const float* Q
 // the last step of the list scans (wise_ivf_scan_f32, wise_ivfpq_scan): part [P][nq][k] keys -> outD/outI [nq][k]
 int wise::topk_list_cap(int k) { return list_cap(k); }
 int wise::merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
-                       hipStream_t st) {
+                             hipStream_t st, const int* count) {
     const int cap = list_cap(k);
     int mw = 8192 / cap;
     if (mw < 1) mw = 1;
@@ -1802,36 +1802,60 @@ int wise::merge_lists_launch(const u64* part, int P, int nq, int k, const long l
     const size_t mlds = (size_t)mw * cap * 8;
     if (mlds > 48 * 1024)
         raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
-    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, P, nq, k, cap, ids, 0ll, outD, outI, 0);
+    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, P, nq, k, cap, ids, 0ll, outD, outI, 0,
+                       (const int*)nullptr, 0, count);
     WISE_LAUNCH_CHECK("merge_keys_kernel");
     return WISE_OK;
 }
 
+// Workspace of the list scans: the keys [nprobe][nq][k]; the rank-local form adds the compacted probes [nq][nprobe] and
+// (for a call without probe_count) the counts [nq].
+static size_t ivf_part_bytes(int nq, int nprobe, int k) { return align_up((size_t)nq * nprobe * k * sizeof(u64), 256); }
+static size_t ivf_local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
+
 extern "C" size_t wise_ivf_scan_workspace_bytes(int nq, int nprobe, int k) {
     if (nq < 1 || nprobe < 1 || k < 1 || k > 2048) return 0;
-    return align_up((size_t)nq * nprobe * k * sizeof(u64), 256);
+    return ivf_part_bytes(nq, nprobe, k);
 }
 
-extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
-                                 const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k,
-                                 float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
-    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "ivf_scan: d=%d must be a multiple of 4 in [4,2048]", d);
-    WISE_CHECK_ARG(k >= 1 && k <= 2048, "ivf_scan: k=%d out of [1,2048]", k);
-    WISE_CHECK_ARG(nq >= 1 && nprobe >= 1 && nlist >= 1 && (long long)nq * nprobe < (1ll << 31),
-                   "ivf_scan: nq=%d nprobe=%d nlist=%d out of range", nq, nprobe, nlist);
-    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll, "ivf_scan: N=%lld out of range", (long long)N);
-    WISE_CHECK_ARG(Q && outD && outI && list_off && probes && (X || N == 0), "ivf_scan: null pointer");
-    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "ivf_scan: X and Q must be 16-byte aligned");
-    const size_t need = wise_ivf_scan_workspace_bytes(nq, nprobe, k);
+extern "C" size_t wise_ivf_scan_local_workspace_bytes(int nq, int nprobe, int k) {
+    if (nq < 1 || nprobe < 1 || nprobe > 2048 || k < 1 || k > 2048) return 0;
+    return ivf_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe) + align_up((size_t)nq * sizeof(int), 256);
+}
+
+// Both list scans.  local: the rank-local form for a slice of the list-major array (list_off clipped to the slice): the
+// probes whose local segment is empty are compacted away on the device first, so the scan blocks past a query's count
+// return at once and the merge folds count[q] lists instead of nprobe.
+static int ivf_scan_impl(const char* what, const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
+                         const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k, float* outD,
+                         int64_t* outI, bool local, int32_t* probe_count, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "%s: d=%d must be a multiple of 4 in [4,2048]", what, d);
+    WISE_CHECK_ARG(k >= 1 && k <= 2048, "%s: k=%d out of [1,2048]", what, k);
+    WISE_CHECK_ARG(nq >= 1 && nprobe >= 1 && (!local || nprobe <= 2048) && nlist >= 1 && (long long)nq * nprobe < (1ll << 31),
+                   "%s: nq=%d nprobe=%d nlist=%d out of range", what, nq, nprobe, nlist);
+    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld out of range", what, (long long)N);
+    WISE_CHECK_ARG(Q && outD && outI && list_off && probes && (X || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "%s: X and Q must be 16-byte aligned", what);
+    const size_t need = local ? wise_ivf_scan_local_workspace_bytes(nq, nprobe, k) : wise_ivf_scan_workspace_bytes(nq, nprobe, k);
     if (!workspace || workspace_bytes < need) {
-        set_error("ivf_scan: workspace %zu < %zu bytes", workspace_bytes, need);
+        set_error("%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
         return WISE_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    u64* part = reinterpret_cast<u64*>(workspace);
+    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
+    u64* part = reinterpret_cast<u64*>(wsb);
+    SegArgs seg = {reinterpret_cast<const long long*>(probes), reinterpret_cast<const long long*>(list_off), nprobe, nq};
+    if (local) {
+        long long* live = reinterpret_cast<long long*>(wsb + ivf_part_bytes(nq, nprobe, k));
+        int* count = probe_count ? probe_count
+                                 : reinterpret_cast<int*>(wsb + ivf_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe));
+        hipLaunchKernelGGL(compact_probes_kernel, dim3(nq), dim3(64), 0, st, seg.probes, nprobe, seg.list_off, nlist, live, count);
+        WISE_LAUNCH_CHECK("compact_probes_kernel");
+        seg.probes = live;
+        seg.count = count;
+    }
     const int cap = list_cap(k);
-    const SegArgs seg = {reinterpret_cast<const long long*>(probes), reinterpret_cast<const long long*>(list_off), nprobe,
-                         nq};
     switch ((d / 4 + 63) / 64) {
         case 1: launch_seg_scan<1>(X, d, Q, k, cap, part, seg, st); break;
         case 2: launch_seg_scan<2>(X, d, Q, k, cap, part, seg, st); break;
@@ -1841,77 +1865,26 @@ extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t
         case 6: launch_seg_scan<6>(X, d, Q, k, cap, part, seg, st); break;
         case 7: launch_seg_scan<7>(X, d, Q, k, cap, part, seg, st); break;
         case 8: launch_seg_scan<8>(X, d, Q, k, cap, part, seg, st); break;
-        default: set_error("ivf_scan: no kernel for d=%d", d); return WISE_E_INVALID;
+        default: set_error("%s: no kernel for d=%d", what, d); return WISE_E_INVALID;
     }
     WISE_LAUNCH_CHECK("ip_scan_kernel<seg>");
     return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD,
-                              reinterpret_cast<long long*>(outI), st);
+                              reinterpret_cast<long long*>(outI), st, seg.count);
 }
 
-// Rank-local form of wise_ivf_scan_f32 for a slice of the list-major array (list_off clipped to the slice): the probes
-// whose local segment is empty are compacted away on the device first, so the scan blocks past a query's count return
-// at once and the merge folds count[q] lists instead of nprobe.  Workspace: the keys [nprobe][nq][k], the compacted
-// probes [nq][nprobe] and (without probe_count) the counts [nq].
-static size_t ivf_local_part_bytes(int nq, int nprobe, int k) { return align_up((size_t)nq * nprobe * k * sizeof(u64), 256); }
-static size_t ivf_local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
-
-extern "C" size_t wise_ivf_scan_local_workspace_bytes(int nq, int nprobe, int k) {
-    if (nq < 1 || nprobe < 1 || nprobe > 2048 || k < 1 || k > 2048) return 0;
-    return ivf_local_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe) + align_up((size_t)nq * sizeof(int), 256);
+extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
+                                 const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k,
+                                 float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    return ivf_scan_impl("ivf_scan", X, N, d, list_off, nlist, ids, Q, nq, probes, nprobe, k, outD, outI, false, nullptr,
+                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int wise_ivf_scan_local_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
                                        const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k,
                                        float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
                                        size_t workspace_bytes, void* stream) {
-    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "ivf_scan_local: d=%d must be a multiple of 4 in [4,2048]", d);
-    WISE_CHECK_ARG(k >= 1 && k <= 2048, "ivf_scan_local: k=%d out of [1,2048]", k);
-    WISE_CHECK_ARG(nq >= 1 && nprobe >= 1 && nprobe <= 2048 && nlist >= 1 && (long long)nq * nprobe < (1ll << 31),
-                   "ivf_scan_local: nq=%d nprobe=%d nlist=%d out of range", nq, nprobe, nlist);
-    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll, "ivf_scan_local: N=%lld out of range", (long long)N);
-    WISE_CHECK_ARG(Q && outD && outI && list_off && probes && (X || N == 0), "ivf_scan_local: null pointer");
-    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "ivf_scan_local: X and Q must be 16-byte aligned");
-    const size_t need = wise_ivf_scan_local_workspace_bytes(nq, nprobe, k);
-    if (!workspace || workspace_bytes < need) {
-        set_error("ivf_scan_local: workspace %zu < %zu bytes", workspace_bytes, need);
-        return WISE_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
-    u64* part = reinterpret_cast<u64*>(wsb);
-    long long* live = reinterpret_cast<long long*>(wsb + ivf_local_part_bytes(nq, nprobe, k));
-    int* count = probe_count ? probe_count
-                             : reinterpret_cast<int*>(wsb + ivf_local_part_bytes(nq, nprobe, k) + ivf_local_probe_bytes(nq, nprobe));
-    const long long* loff = reinterpret_cast<const long long*>(list_off);
-    hipLaunchKernelGGL(compact_probes_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), nprobe,
-                       loff, nlist, live, count);
-    WISE_LAUNCH_CHECK("compact_probes_kernel");
-    const int cap = list_cap(k);
-    SegArgs seg = {live, loff, nprobe, nq};
-    seg.count = count;
-    switch ((d / 4 + 63) / 64) {
-        case 1: launch_seg_scan<1>(X, d, Q, k, cap, part, seg, st); break;
-        case 2: launch_seg_scan<2>(X, d, Q, k, cap, part, seg, st); break;
-        case 3: launch_seg_scan<3>(X, d, Q, k, cap, part, seg, st); break;
-        case 4: launch_seg_scan<4>(X, d, Q, k, cap, part, seg, st); break;
-        case 5: launch_seg_scan<5>(X, d, Q, k, cap, part, seg, st); break;
-        case 6: launch_seg_scan<6>(X, d, Q, k, cap, part, seg, st); break;
-        case 7: launch_seg_scan<7>(X, d, Q, k, cap, part, seg, st); break;
-        case 8: launch_seg_scan<8>(X, d, Q, k, cap, part, seg, st); break;
-        default: set_error("ivf_scan_local: no kernel for d=%d", d); return WISE_E_INVALID;
-    }
-    WISE_LAUNCH_CHECK("ip_scan_kernel<seg, local>");
-    int mw = 8192 / cap;
-    if (mw < 1) mw = 1;
-    if (mw > 16) mw = 16;
-    const size_t mlds = (size_t)mw * cap * 8;
-    if (mlds > 48 * 1024)
-        raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
-    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, nprobe, nq, k, cap,
-                       reinterpret_cast<const long long*>(ids), 0ll, outD, reinterpret_cast<long long*>(outI), 0,
-                       (const int*)nullptr, 0, (const int*)count);
-    WISE_LAUNCH_CHECK("merge_keys_kernel (local)");
-    return WISE_OK;
+    return ivf_scan_impl("ivf_scan_local", X, N, d, list_off, nlist, ids, Q, nq, probes, nprobe, k, outD, outI, true,
+                         probe_count, workspace, workspace_bytes, stream);
 }
 
 // ---- two-stage exact search over a bf16 shadow (see the kernels above)

@@ -83,8 +83,9 @@ struct WaveList {
 // fold part [P][nq][k] keys (per-block lists of a list scan) into outD/outI [nq][k], ids looked up at the end
 // (merge_keys_kernel, ip_topk.hip); topk_list_cap(k) = entries of a WaveList that keeps k keys
 int topk_list_cap(int k);
+// count: optional [nq], the lists of part that hold keys per query (the rank-local scan); default: all P
 int merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
-                       hipStream_t st);
+                       hipStream_t st, const int* count = nullptr);
 
 // batched (MFMA) scan, ip_topk_mfma.hip
 constexpr int MFMA_QB = 32;   // queries per pass (the N of v_mfma_f32_32x32x2_f32)

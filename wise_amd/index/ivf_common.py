@@ -1,0 +1,291 @@
+"""What the inverted-file indexes (ivf_flat.py, ivf_pq.py) are made of: one coarse quantizer, one list store, and the
+faiss-shaped surface around the two.
+
+  CoarseQuantizer     the centroid table and everything that uses it: spherical k-means (10 Lloyd iterations, assignment
+                      by inner product — what faiss's Clustering does for an inner-product IVF), run on the GPU as dense
+                      products; deterministic (seeded sample for the initial centroids, empty cells re-seeded from the
+                      fullest cell); the assignment of rows to lists; the probes of a query
+  ListStore           the payload (fp32 rows or uint8 codes) and the ids grouped by list, with the chunks added since the
+                      last merge
+  IVFIndexBase        nprobe, direct map, numpy search and the other attributes the REST layer touches on either index
+"""
+from __future__ import annotations
+
+from typing import Callable, List, Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .flat_ip import FlatIPIndex
+
+
+def _as_tensor(x, dtype) -> torch.Tensor:
+    """A tensor is passed through as it is; anything else becomes a contiguous host tensor of the numpy `dtype`."""
+    return x if torch.is_tensor(x) else torch.as_tensor(np.ascontiguousarray(x, dtype=dtype))
+
+
+def _rows_f32(x, d: int, what: str) -> torch.Tensor:
+    x = _as_tensor(x, np.float32)
+    if x.dim() != 2 or x.shape[1] != d:
+        raise ValueError(f"{what}: expected [n,{d}], got {tuple(x.shape)}")
+    return x
+
+
+def _ids_i64(ids, n: int) -> torch.Tensor:
+    ids = _as_tensor(ids, np.int64)
+    if ids.shape != (n,):
+        raise ValueError("add_with_ids: ids must have one entry per row")
+    return ids
+
+
+class _DirectMap:
+    """The two attributes api/routes.py:1317 reads."""
+    NoMap, Array, Hashtable = 0, 1, 2
+
+    def __init__(self):
+        self.type = self.NoMap
+
+
+class CoarseQuantizer:
+    # Everything numeric below is this library's own kernels (csrc/ivf_build.hip, wise_ip_scores_f32): torch only allocates,
+    # concatenates and draws the seeding permutation on the host.
+    def __init__(self, d: int, nlist: int, device: str = "cuda"):
+        if d < 4 or d % 4 != 0 or d > 2048:
+            raise ValueError(f"IVFFlatIPIndex: d={d} must be a multiple of 4 in [4, 2048]")
+        if nlist < 1:
+            raise ValueError("IVFFlatIPIndex: nlist must be positive")
+        self.d, self.nlist = int(d), int(nlist)
+        self.device = torch.device(device)
+        self.is_trained = False
+        self.niter = 10
+        self.seed = 1234
+        self.centroids: Optional[torch.Tensor] = None    # [nlist, d] fp32, unit rows
+        self._quantizer: Optional[FlatIPIndex] = None
+
+    @staticmethod
+    def assign_device(x: torch.Tensor, centroids: torch.Tensor, chunk: int = 4096) -> torch.Tensor:
+        """nearest centroid of every row by inner product: the exact-f32 score kernel (the coarse stage's own) + wise_ivf_argmax"""
+        lib = _lib.lib()
+        c = centroids.contiguous()
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+        scores = torch.empty(min(chunk, max(x.shape[0], 1)), c.shape[0], dtype=torch.float32, device=x.device)
+        st = _lib.stream_ptr()
+        for s in range(0, x.shape[0], chunk):
+            q = x[s:s + chunk]                       # (a slice of whole rows of a contiguous tensor: contiguous)
+            _lib.check(lib.wise_ip_scores_f32(c.data_ptr(), c.shape[0], c.shape[1], q.data_ptr(), q.shape[0],
+                                              scores.data_ptr(), st), "wise_ip_scores_f32")
+            _lib.check(lib.wise_ivf_argmax(scores.data_ptr(), q.shape[0], c.shape[0], out[s:].data_ptr(), st), "wise_ivf_argmax")
+        return out
+
+    def assign(self, x, chunk: int = 1 << 20) -> np.ndarray:
+        """[n] int64 (numpy): the list each row of x [n,d] goes to (the assignment add_with_ids makes), streamed to the
+        device `chunk` rows at a time."""
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIPIndex: train() before assign()")
+        x = np.asarray(x, dtype=np.float32)
+        out = np.empty(x.shape[0], dtype=np.int64)
+        for s in range(0, x.shape[0], chunk):
+            xs = torch.from_numpy(np.ascontiguousarray(x[s:s + chunk])).to(self.device)
+            out[s:s + xs.shape[0]] = self.assign_device(xs, self.centroids).cpu().numpy()
+        return out
+
+    def _group(self, assign: torch.Tensor):
+        """(order, list_off, counts): the rows grouped by list, stable (wise_ivf_group: a radix sort on the device)"""
+        lib = _lib.lib()
+        n = assign.shape[0]
+        order = torch.empty(n, dtype=torch.int64, device=self.device)
+        list_off = torch.empty(self.nlist + 1, dtype=torch.int64, device=self.device)
+        counts = torch.empty(self.nlist, dtype=torch.int64, device=self.device)
+        ws = torch.empty(lib.wise_ivf_group_workspace_bytes(n, self.nlist), dtype=torch.uint8, device=self.device)
+        _lib.check(lib.wise_ivf_group(assign.data_ptr(), n, self.nlist, order.data_ptr(), list_off.data_ptr(), counts.data_ptr(),
+                                      ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "wise_ivf_group")
+        return order, list_off, counts
+
+    @staticmethod
+    def _gather_rows(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+        out = torch.empty(idx.shape[0], x.shape[1], dtype=torch.float32, device=x.device)
+        _lib.check(_lib.lib().wise_ivf_gather_rows(x.data_ptr(), idx.data_ptr(), idx.shape[0], x.shape[1], out.data_ptr(),
+                                                   _lib.stream_ptr()), "wise_ivf_gather_rows")
+        return out
+
+    def train(self, x) -> None:
+        lib = _lib.lib()  # raises without a gfx950 device: there is no CPU path
+        x = _as_tensor(x, np.float32).to(self.device, torch.float32).contiguous()
+        _rows_f32(x, self.d, "train")
+        n = x.shape[0]
+        if n < self.nlist:
+            raise ValueError(f"train: {n} training vectors for {self.nlist} cells")
+        g = torch.Generator(device="cpu").manual_seed(self.seed)
+        perm = torch.randperm(n, generator=g)[: self.nlist].to(self.device)
+        st = _lib.stream_ptr()
+        c = self._gather_rows(x, perm)
+        _lib.check(lib.wise_ivf_normalize_rows(c.data_ptr(), self.nlist, self.d, c.data_ptr(), st), "wise_ivf_normalize_rows")
+        sums = torch.empty(self.nlist, self.d, dtype=torch.float32, device=self.device)
+        for _ in range(self.niter):
+            a = self.assign_device(x, c)
+            order, list_off, counts = self._group(a)
+            _lib.check(lib.wise_ivf_list_sums(x.data_ptr(), order.data_ptr(), list_off.data_ptr(), self.nlist, self.d,
+                                              sums.data_ptr(), st), "wise_ivf_list_sums")
+            cnt = counts.cpu().numpy()                       # nlist numbers: which cells are empty is decided on the host
+            empty = np.flatnonzero(cnt == 0)
+            if empty.size:
+                # re-seed every empty cell with a slightly perturbed copy of the fullest cells' sums (ties: the lower cell first)
+                donors = np.argsort(-cnt, kind="stable")[: empty.size]
+                e_d = torch.from_numpy(empty.astype(np.int64)).to(self.device)
+                d_d = torch.from_numpy(donors.astype(np.int64)).to(self.device)
+                _lib.check(lib.wise_ivf_reseed(sums.data_ptr(), e_d.data_ptr(), d_d.data_ptr(), int(empty.size), self.d, st),
+                           "wise_ivf_reseed")
+            _lib.check(lib.wise_ivf_normalize_rows(sums.data_ptr(), self.nlist, self.d, c.data_ptr(), st),
+                       "wise_ivf_normalize_rows")    # spherical: unit centroids
+        self._install(c)
+
+    def set_centroids(self, centroids) -> None:
+        """Install a trained quantizer (file load, tests)."""
+        c = _as_tensor(centroids, np.float32)
+        if c.shape != (self.nlist, self.d):
+            raise ValueError(f"set_centroids: expected [{self.nlist},{self.d}]")
+        self._install(c.to(self.device, torch.float32))
+
+    def _install(self, c: torch.Tensor) -> None:
+        self.centroids = c.contiguous()
+        self._quantizer = FlatIPIndex(self.d, device=str(self.device)).adopt(self.centroids, None, id_base=0)
+        self.is_trained = True
+
+    def probes_device(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """[nq, nprobe] int64 list numbers: the nprobe centroids of largest inner product (-1 padding when
+        nprobe > nlist).  Few probes: the flat top-k kernel over the centroid table.  Many probes (threshold lists
+        stop filtering when k is a sizeable fraction of nlist): all centroid scores in exact fp32 on the matrix
+        cores (wise_ip_scores_f32), then the radix-select kernel; the probes then come in list order, which the
+        list scan does not care about."""
+        if nprobe <= 64:
+            _, I = self._quantizer.search_device(q, nprobe)
+            return I
+        lib = _lib.lib()
+        scores = torch.empty(q.shape[0], self.nlist, dtype=torch.float32, device=self.device)
+        rc = lib.wise_ip_scores_f32(self.centroids.data_ptr(), self.nlist, self.d, q.data_ptr(), q.shape[0],
+                                    scores.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, "wise_ip_scores_f32")
+        out = torch.empty(q.shape[0], nprobe, dtype=torch.int64, device=self.device)
+        rc = lib.wise_select_topk_f32(scores.data_ptr(), q.shape[0], self.nlist, nprobe, out.data_ptr(),
+                                      _lib.stream_ptr())
+        _lib.check(rc, "wise_select_topk_f32")
+        return out
+
+
+class ListStore:
+    """`data` [N, width] (fp32 rows or uint8 codes) and `ids` [N] grouped by list, `list_off` [nlist + 1] int64; `n` counts
+    the chunks not yet merged too.  Contract: within a list, rows stay in their order of insertion (the grouping is a stable
+    sort and the rows already stored come first) — the sharded index's bit-equality with the one-GPU index rests on it.
+    `gather(data, order)` is the per-dtype row gather (wise_ivf_gather_rows / wise_pq_gather_codes)."""
+
+    def __init__(self, nlist: int, width: int, dtype: torch.dtype, device: torch.device, gather: Callable):
+        self.nlist, self.width, self.dtype, self.device, self._gather = nlist, width, dtype, device, gather
+        self._pending: List[tuple] = []                  # (payload, ids, assign) chunks not yet merged into the lists
+        self.data: Optional[torch.Tensor] = None
+        self.ids: Optional[torch.Tensor] = None
+        self.list_off: Optional[torch.Tensor] = None
+        self.n = 0
+
+    def append(self, payload: torch.Tensor, ids: torch.Tensor, assign: torch.Tensor) -> None:
+        self._pending.append((payload, ids, assign))
+        self.n += payload.shape[0]
+
+    def adopt(self, data: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> None:
+        """Take a payload that is already grouped by list (file load); chunks not yet merged are dropped."""
+        self._pending = []
+        self.data = data.to(self.device, self.dtype).contiguous()
+        self.ids = ids.to(self.device, torch.int64).contiguous()
+        self.list_off = list_off.to(self.device, torch.int64).contiguous()
+        self.n = self.data.shape[0]
+
+    def finalize(self, group: Callable) -> None:
+        """Merge the pending chunks into the lists; `group` is the quantizer's stable grouping (CoarseQuantizer._group)."""
+        if self._pending:
+            lib = _lib.lib()
+            st = _lib.stream_ptr()
+            old = [(self.data, self.ids)] if self.data is not None and self.data.shape[0] else []
+            old_assign = []
+            if old:
+                oa = torch.empty(self.data.shape[0], dtype=torch.int64, device=self.device)     # the rows already grouped: list c, list_off[c] .. [c + 1]
+                _lib.check(lib.wise_ivf_expand_lists(self.list_off.data_ptr(), self.nlist, oa.data_ptr(), st), "wise_ivf_expand_lists")
+                old_assign = [oa]
+            a = torch.cat(old_assign + [p[2] for p in self._pending]).contiguous()
+            order, list_off, _ = group(a)
+            alld = torch.cat([p[0] for p in old + self._pending]).contiguous()
+            allids = torch.cat([p[1] for p in old + self._pending]).contiguous()
+            self.data = self._gather(alld, order)
+            ids = torch.empty_like(allids)
+            _lib.check(lib.wise_ivf_gather_i64(allids.data_ptr(), order.data_ptr(), order.shape[0], ids.data_ptr(), st), "wise_ivf_gather_i64")
+            self.ids, self.list_off, self._pending = ids, list_off, []
+        if self.data is None:
+            self.data = torch.empty(0, self.width, dtype=self.dtype, device=self.device)
+            self.ids = torch.empty(0, dtype=torch.int64, device=self.device)
+            self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
+
+    def nbytes(self) -> int:
+        """Bytes of HBM the merged lists hold: payload, ids, offsets."""
+        return sum(t.numel() * t.element_size() for t in (self.data, self.ids, self.list_off))
+
+
+class IVFIndexBase:
+    """One CoarseQuantizer (`_coarse`), one ListStore (`_lists`), and the surface both indexes show around them."""
+
+    def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable):
+        self._coarse = CoarseQuantizer(d, nlist, device)
+        self.d, self.nlist, self.device = self._coarse.d, self._coarse.nlist, self._coarse.device
+        self._lists = ListStore(self.nlist, width, dtype, self.device, gather)
+        self.nprobe = 1           # faiss default; the REST layer sets it (routes.py:902)
+        self.parallel_mode = 0    # accepted and ignored (routes.py:901)
+        self.direct_map = _DirectMap()
+        self._ws: Optional[torch.Tensor] = None
+
+    @property
+    def ntotal(self) -> int:
+        return self._lists.n
+
+    @property
+    def centroids(self) -> Optional[torch.Tensor]:
+        return self._coarse.centroids
+
+    @property
+    def is_trained(self) -> bool:
+        return self._coarse.is_trained
+
+    def set_centroids(self, centroids) -> None:
+        self._coarse.set_centroids(centroids)
+
+    def probes_device(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        return self._coarse.probes_device(q, nprobe)
+
+    def _finalize(self) -> None:
+        self._lists.finalize(self._coarse._group)
+
+    def _queries(self, q: torch.Tensor) -> torch.Tensor:
+        """The start of every search: the lists merged, q [nq,d] checked and on the device as contiguous fp32."""
+        if not self.is_trained:
+            raise RuntimeError(f"{type(self).__name__}: not trained")
+        self._finalize()
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
+        return q.to(self.device, torch.float32).contiguous()
+
+    def _clamped_nprobe(self) -> int:
+        return max(1, min(int(self.nprobe), self.nlist, 2048))
+
+    def _workspace(self, need: int) -> torch.Tensor:
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def search(self, x, k: int):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("search: x must be 2-D")
+        D, I = self.search_device(torch.from_numpy(x).to(self.device), int(k))
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    def make_direct_map(self, enable: bool = True) -> None:
+        """routes.py:904-909: afterwards reconstruct works by id.  Ids are looked up in the stored id array."""
+        self.direct_map.type = _DirectMap.Hashtable if enable else _DirectMap.NoMap

@@ -4,7 +4,8 @@ Stands where `faiss.IndexIVFPQ(IndexFlatIP(d), d, nlist, m, 8, METRIC_INNER_PROD
 default): the index family of the reference's own index study (docs/Search-Index-Evaluation.md:105-123).  HBM holds
 N * (m + 8) bytes of codes and ids, the centroids [nlist, d] and the codebooks [m, 256, d / m] — and no fp32 rows.
 
-  coarse stage        IVFFlatIPIndex's, by composition: the same spherical k-means, `probes_device`, list bookkeeping
+  coarse stage        the CoarseQuantizer and ListStore IVFFlatIPIndex has (ivf_common.py): the same spherical k-means,
+                      `probes_device`, list bookkeeping
   train(x)            coarse k-means, then per sub-space Lloyd k-means (L2, plain means, 10 iterations) on the residuals of at
                       most 65,536 training rows drawn by a seeded host permutation whose first 256 rows are the initial
                       codewords; an empty codeword keeps its value; deterministic (wise_pq_encode / wise_pq_update)
@@ -17,13 +18,13 @@ What is exact and tested: given the same centroids, codebooks and codes the scan
 """
 from __future__ import annotations
 
-from typing import List, Optional
+from typing import Optional
 
 import numpy as np
 import torch
 
 from .. import _lib
-from .ivf_flat import IVFFlatIPIndex, _DirectMap
+from .ivf_common import IVFIndexBase, _as_tensor, _ids_i64, _rows_f32
 
 KSUB = 256
 MAX_TRAIN_ROWS = 256 * KSUB      # faiss caps a sub-quantizer's training set at 256 rows per codeword
@@ -42,34 +43,22 @@ def check_pq_shape(d: int, m: int, nbits: int = 8) -> None:
         raise ValueError(f"IVFPQIPIndex: d / m = {dsub} must be even and in [2, 96]")
 
 
-class IVFPQIPIndex:
+def _gather_codes(codes: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    out = torch.empty_like(codes)
+    _lib.check(_lib.lib().wise_pq_gather_codes(codes.data_ptr(), idx.data_ptr(), idx.shape[0], codes.shape[1], out.data_ptr(),
+                                               _lib.stream_ptr()), "wise_pq_gather_codes")
+    return out
+
+
+class IVFPQIPIndex(IVFIndexBase):
     def __init__(self, d: int, nlist: int, m: int, nbits: int = 8, device: str = "cuda"):
         check_pq_shape(int(d), int(m), int(nbits))
-        self._coarse = IVFFlatIPIndex(d, nlist, device=device)      # validates d and nlist; owns centroids and quantizer
-        self.d, self.nlist, self.m, self.nbits = int(d), int(nlist), int(m), 8
+        super().__init__(d, nlist, device, width=int(m), dtype=torch.uint8, gather=_gather_codes)
+        self.m, self.nbits = int(m), 8
         self.dsub = self.d // self.m
-        self.device = self._coarse.device
-        self.nprobe = 1
-        self.parallel_mode = 0
-        self.direct_map = _DirectMap()
-        self.niter = 10
+        self.niter = 10           # of the codebook training; the coarse k-means keeps its own
         self.seed = 1234
         self.codebooks: Optional[torch.Tensor] = None      # [m, 256, dsub] fp32
-        self._pending: List[tuple] = []                    # (codes, ids, assign) chunks not yet merged into the lists
-        self._codes: Optional[torch.Tensor] = None         # [N, m] uint8 grouped by list
-        self._ids: Optional[torch.Tensor] = None
-        self._list_off: Optional[torch.Tensor] = None
-        self._n = 0
-        self._ws: Optional[torch.Tensor] = None
-
-    # -- the coarse stage's state, seen through this index ----------------------------------------
-    @property
-    def ntotal(self) -> int:
-        return self._n
-
-    @property
-    def centroids(self) -> Optional[torch.Tensor]:
-        return self._coarse.centroids
 
     @property
     def is_trained(self) -> bool:
@@ -78,7 +67,7 @@ class IVFPQIPIndex:
     def hbm_bytes(self) -> int:
         """Bytes of HBM the index holds once its lists are merged: codes, ids, offsets, centroids, codebooks."""
         self._finalize()
-        return sum(t.numel() * t.element_size() for t in (self._codes, self._ids, self._list_off, self.centroids, self.codebooks))
+        return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.codebooks))
 
     # -- training -------------------------------------------------------------------------------
     def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
@@ -111,7 +100,7 @@ class IVFPQIPIndex:
         n = x.shape[0]
         perm = np.random.default_rng(self.seed).permutation(n)[:MAX_TRAIN_ROWS].astype(np.int64)
         xs = self._coarse._gather_rows(x, torch.from_numpy(perm).to(self.device))
-        return self._residuals(xs, self._coarse._assign(xs, self.centroids))
+        return self._residuals(xs, self._coarse.assign_device(xs, self.centroids))
 
     def train_codebooks(self, resid: torch.Tensor, codebooks: Optional[torch.Tensor] = None) -> torch.Tensor:
         """niter Lloyd iterations from `codebooks` (default: initial_codebooks(resid))."""
@@ -121,21 +110,16 @@ class IVFPQIPIndex:
         return cb
 
     def train(self, x) -> None:
-        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)) if not torch.is_tensor(x) else x
-        if x.dim() != 2 or x.shape[1] != self.d:
-            raise ValueError(f"train: expected [n,{self.d}], got {tuple(x.shape)}")
+        x = _rows_f32(x, self.d, "train")
         if x.shape[0] < KSUB:
             raise ValueError(f"train: {x.shape[0]} training vectors for {KSUB} codewords")
         self._coarse.train(x)
         x = x.to(self.device, torch.float32).contiguous()
         self.codebooks = self.train_codebooks(self.training_residuals(x))
 
-    def set_centroids(self, centroids) -> None:
-        self._coarse.set_centroids(centroids)
-
     def set_codebooks(self, codebooks) -> None:
         """Install trained codebooks [m, 256, dsub] (file load, tests)."""
-        cb = torch.as_tensor(np.ascontiguousarray(codebooks, dtype=np.float32)) if not torch.is_tensor(codebooks) else codebooks
+        cb = _as_tensor(codebooks, np.float32)
         if tuple(cb.shape) != (self.m, KSUB, self.dsub):
             raise ValueError(f"set_codebooks: expected [{self.m},{KSUB},{self.dsub}]")
         self.codebooks = cb.to(self.device, torch.float32).contiguous()
@@ -144,68 +128,29 @@ class IVFPQIPIndex:
     def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
         if not self.is_trained:
             raise RuntimeError("IVFPQIPIndex: train() before add_with_ids()")
-        x = torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)) if not torch.is_tensor(x) else x
-        ids = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)) if not torch.is_tensor(ids) else ids
-        if x.dim() != 2 or x.shape[1] != self.d:
-            raise ValueError(f"add_with_ids: expected [n,{self.d}], got {tuple(x.shape)}")
-        if ids.shape != (x.shape[0],):
-            raise ValueError("add_with_ids: ids must have one entry per row")
+        x = _rows_f32(x, self.d, "add_with_ids")
+        ids = _ids_i64(ids, x.shape[0])
         for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
             xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
-            a = self._coarse._assign(xs, self.centroids)
+            a = self._coarse.assign_device(xs, self.centroids)
             codes = self._encode(self._residuals(xs, a), self.codebooks)
-            self._pending.append((codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a))
-            self._n += xs.shape[0]
+            self._lists.append(codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a)
 
     def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> "IVFPQIPIndex":
         """Take codes that are already grouped by list (file load)."""
         if codes.dim() != 2 or codes.shape[1] != self.m:
             raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
-        self._pending = []
-        self._codes = codes.to(self.device, torch.uint8).contiguous()
-        self._ids = ids.to(self.device, torch.int64).contiguous()
-        self._list_off = list_off.to(self.device, torch.int64).contiguous()
-        self._n = self._codes.shape[0]
+        self._lists.adopt(codes, ids, list_off)
         return self
-
-    def _finalize(self):
-        if self._pending:
-            lib = _lib.lib()
-            st = _lib.stream_ptr()
-            have = self._codes is not None and self._codes.shape[0] > 0
-            cs = ([self._codes] if have else []) + [p[0] for p in self._pending]
-            iss = ([self._ids] if have else []) + [p[1] for p in self._pending]
-            old_assign = []
-            if have:
-                oa = torch.empty(self._codes.shape[0], dtype=torch.int64, device=self.device)
-                _lib.check(lib.wise_ivf_expand_lists(self._list_off.data_ptr(), self.nlist, oa.data_ptr(), st), "wise_ivf_expand_lists")
-                old_assign = [oa]
-            a = torch.cat(old_assign + [p[2] for p in self._pending]).contiguous()
-            order, list_off, _ = self._coarse._group(a)      # stable: rows of a list keep their order of insertion
-            allc, allids = torch.cat(cs).contiguous(), torch.cat(iss).contiguous()
-            codes, ids = torch.empty_like(allc), torch.empty_like(allids)
-            _lib.check(lib.wise_pq_gather_codes(allc.data_ptr(), order.data_ptr(), order.shape[0], self.m, codes.data_ptr(), st),
-                       "wise_pq_gather_codes")
-            _lib.check(lib.wise_ivf_gather_i64(allids.data_ptr(), order.data_ptr(), order.shape[0], ids.data_ptr(), st), "wise_ivf_gather_i64")
-            self._codes, self._ids, self._list_off, self._pending = codes, ids, list_off, []
-        if self._codes is None:
-            self._codes = torch.empty(0, self.m, dtype=torch.uint8, device=self.device)
-            self._ids = torch.empty(0, dtype=torch.int64, device=self.device)
-            self._list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
 
     # -- search ---------------------------------------------------------------------------------
     def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
         lib = _lib.lib()
-        if not self.is_trained:
-            raise RuntimeError("IVFPQIPIndex: not trained")
-        self._finalize()
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
-        q = q.to(self.device, torch.float32).contiguous()
+        q = self._queries(q)
         nq = q.shape[0]
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        nprobe = max(1, min(int(self.nprobe), self.nlist, 2048))
+        nprobe, ls = self._clamped_nprobe(), self._lists
         st = _lib.stream_ptr()
         for s in range(0, nq, chunk):                    # bounds the tables: chunk * m KiB
             qs = q[s:s + chunk]
@@ -213,43 +158,30 @@ class IVFPQIPIndex:
             need = lib.wise_ivfpq_scan_workspace_bytes(n, nprobe, k, self.m)
             if need == 0:
                 raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k} m={self.m}")
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._workspace(need)
             probes = self._coarse.probes_device(qs, nprobe).contiguous()
             bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
             _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
                                         bias.data_ptr(), st), "wise_pq_bias")
             lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
             _lib.check(lib.wise_pq_lut(qs.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
-            rc = lib.wise_ivfpq_scan(self._codes.data_ptr(), self._n, self.m, self._list_off.data_ptr(), self.nlist,
-                                     self._ids.data_ptr(), lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k,
-                                     D[s:].data_ptr(), I[s:].data_ptr(), self._ws.data_ptr(), self._ws.numel(), st)
+            rc = lib.wise_ivfpq_scan(ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist,
+                                     ls.ids.data_ptr(), lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k,
+                                     D[s:].data_ptr(), I[s:].data_ptr(), ws.data_ptr(), ws.numel(), st)
             _lib.check(rc, "wise_ivfpq_scan")
         return D, I
 
-    def search(self, x, k: int):
-        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy."""
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        if x.ndim != 2:
-            raise ValueError("search: x must be 2-D")
-        D, I = self.search_device(torch.from_numpy(x).to(self.device), int(k))
-        return D.cpu().numpy(), I.cpu().numpy()
-
     # -- the rest of the surface the REST layer touches -------------------------------------------
-    def make_direct_map(self, enable: bool = True) -> None:
-        """routes.py:904-909: afterwards reconstruct works by id.  Ids are looked up in the stored id array."""
-        self.direct_map.type = _DirectMap.Hashtable if enable else _DirectMap.NoMap
-
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + its codewords; NaN for an unknown id."""
         lib = _lib.lib()
         self._finalize()
-        st = _lib.stream_ptr()
+        st, ls = _lib.stream_ptr(), self._lists
         qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
         pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
-        _lib.check(lib.wise_pq_find(self._ids.data_ptr(), self._n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
+        _lib.check(lib.wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
         out = torch.empty(qi.numel(), self.d, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_decode(self._codes.data_ptr(), self._n, pos.data_ptr(), qi.numel(), self._list_off.data_ptr(), self.nlist,
+        _lib.check(lib.wise_pq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), qi.numel(), ls.list_off.data_ptr(), self.nlist,
                                       self.centroids.data_ptr(), self.codebooks.data_ptr(), self.d, self.m, out.data_ptr(), st),
                    "wise_pq_decode")
         return out.cpu().numpy()
@@ -257,5 +189,6 @@ class IVFPQIPIndex:
     def lists_host(self):
         """(centroids [nlist,d], codebooks [m,256,dsub], codes [N,m] uint8, ids [N], list_off [nlist+1]) as numpy."""
         self._finalize()
-        return (self.centroids.cpu().numpy(), self.codebooks.cpu().numpy(), self._codes.cpu().numpy(), self._ids.cpu().numpy(),
-                self._list_off.cpu().numpy())
+        ls = self._lists
+        return (self.centroids.cpu().numpy(), self.codebooks.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(),
+                ls.list_off.cpu().numpy())
