@@ -33,8 +33,8 @@ const char* wise_last_error(void);
  * caption encoder — and the wise_cnn14_* entry points; 5: wise_ip_shadow_i8 / wise_ip_topk_shadow8_f32 (int8 shadow,
  * norms[4]), wise_ip_topk_shadow_workspace_bytes depends on nq and returns 0 under 2^18 rows, two-stage k up to 1024; and,
  * added within 5: wise_vit_config.ln_fold, the wise_gemm_fold_* entry points, wise_attention_oproj_fold, wise_htsat_forward2,
- * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points
- * and wise_ivfpq_scan). */
+ * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points,
+ * wise_ivfpq_scan, wise_ivf_refine and wise_ivf_refine_rows). */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -227,6 +227,26 @@ size_t wise_ivfpq_scan_workspace_bytes(int nq, int nprobe, int k, int m);
 int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids, const float* lut,
                     int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD, int64_t* outI, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* (ABI 5, additive) The re-ranking stage of IndexIVFPQ<m>R8 / IndexIVFPQ<m>R16 (faiss IndexRefine): the candidates of a PQ scan
+ * are scored again from compact copies of the rows kept in list order, and the k best are kept.
+ *   rows     kind 8:  [N,d] int8 with scales [N] fp32, as wise_ip_shadow_i8 writes them (a row stands for scales[r] * rows[r,:])
+ *            kind 16: [N,d] bf16 as wise_ip_shadow_bf16 writes them; scales is ignored (may be NULL).  16-byte aligned.
+ *   ids      [N] int64 external ids in the same order (NULL => the position)
+ *   Q        [nq,d] fp32;  cand_pos [nq,kc] int64 positions in [0, N) — what wise_ivfpq_scan returns with ids = NULL;
+ *            entries outside [0, N) (the scan's -1 padding) are skipped.  A position listed twice is returned twice.
+ * THE ORDER OF THE ARITHMETIC IS PART OF THE CONTRACT: with x_i = (float)rows[r,i] (kind 8: the integer's value; kind 16: the
+ * bf16 bits shifted into the upper half of an fp32) a score is acc = +0, then acc = acc + (Q[q,i] * x_i) for i = 0 .. d-1 — the
+ * product and the sum each rounded to fp32, never fused — and, kind 8 only, finally scales[r] * acc rounded once more.  A
+ * float32 loop on the host reproduces it bit for bit.
+ * outD/outI [nq,k] ordered by (-score, position), (-3.4028235e38, -1) padding where fewer than k candidates are valid.
+ * Limits (WISE_E_UNSUPPORTED otherwise): kind 8: d % 16 == 0, 16 <= d <= 1024; kind 16: d % 8 == 0, 8 <= d <= 1024;
+ * 1 <= kc <= 2048, 1 <= k <= 2048, nq >= 0, N < 2^32 - 1.  No workspace: one workgroup per query keeps its keys in LDS.
+ *   wise_ivf_refine_rows: out[i, :] fp32 = the row the store holds at pos[i] — scales[r] * (float)rows[r,c] rounded once
+ *     (kind 8), the widened bf16 (kind 16); a position outside [0, N) gives a row of NaN.  reconstruct_batch of the two types. */
+int wise_ivf_refine(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids, const float* Q, int nq,
+                    const int64_t* cand_pos, int kc, int k, float* outD, int64_t* outI, void* stream);
+int wise_ivf_refine_rows(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* pos, int n, float* out,
+                         void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

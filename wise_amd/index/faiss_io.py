@@ -30,6 +30,14 @@ The file of index types 'IndexIVFPQ<m>' (write_ivf_pq_ip / read_ivf_pq_ip) resta
     u64  d | u64 M | u64 nbits (8) | u64 n_floats (= 256*d) | f32[M*256*dsub] the ProductQuantizer record (centroids)
     'ilar' array inverted lists with code_size = m: per non-empty list u8 codes[size*m] | i64 ids[size]
 
+The file of index types 'IndexIVFPQ<m>R8' / 'IndexIVFPQ<m>R16' (write_ivf_pq_refine_ip / read_ivf_pq_refine_ip) is THIS
+REPOSITORY'S OWN FORMAT, not a faiss layout (faiss's 8-bit refine stores keep a range per dimension, these rows a scale per row):
+
+    u32  'WiPR' | u32 version (1) | u32 kind (8 or 16) | u32 k_factor
+    the complete 'IwPQ' record above
+    u64  n_bytes | the compact rows in list order: i8[N*d] (kind 8) or bf16[N*d] (kind 16)
+    u64  N | f32[N]                                                           the row scales (kind 8 only)
+
 faiss is not in the container, so these layouts are UNPINNED against a real faiss binary; the round
 trip is pinned by tests/test_feature_store_index_io.py.  The rows are memory-mapped on read so a
 158 GiB index (docs/Search-Index-Evaluation.md:109) streams to the GPU without a host copy.
@@ -156,12 +164,13 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
 def _read_ivf_head(f, p, pq: bool = False):
     """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload).
     pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks)."""
+    base = f.tell()                                          # (an 'IwPQ' record may sit inside a 'WiPR' file)
     (cc,) = struct.unpack("<I", f.read(4))
     if cc != _fourcc("IwPQ" if pq else "IwFl"):
         raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {'IndexIVFPQ' if pq else 'IndexIVFFlat'}")
     hdr = f.read(_HDR_SIZE + 4)
     d, n, metric, off = _read_header(hdr, 0)
-    f.seek(4 + off)
+    f.seek(base + 4 + off)
     nlist, nprobe = struct.unpack("<QQ", f.read(16))
     (cq,) = struct.unpack("<I", f.read(4))
     if cq != _fourcc("IxFI"):
@@ -288,31 +297,49 @@ def write_ivf_pq_ip(path, centroids: np.ndarray, codebooks: np.ndarray, codes: n
     n, m = codes.shape
     assert d % m == 0 and codebooks.shape == (m, 256, d // m)
     assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
-    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
     with open(path, "wb") as f:
-        f.write(struct.pack("<I", _fourcc("IwPQ")))
-        f.write(_header(d, n))
-        f.write(struct.pack("<QQ", nlist, nprobe))
-        f.write(struct.pack("<I", _fourcc("IxFI")))
-        f.write(_header(d, nlist))
-        f.write(struct.pack("<Q", nlist * d))
-        centroids.tofile(f)
-        f.write(struct.pack("<BQ", 0, 0))
-        f.write(struct.pack("<BQ", 1, m))                        # by_residual, code_size
-        f.write(struct.pack("<QQQQ", d, m, 8, 256 * d))          # ProductQuantizer: d, M, nbits, centroids
-        codebooks.tofile(f)
-        f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, m))
-        nonzero = np.flatnonzero(sizes)
-        if len(nonzero) > nlist // 2:
-            f.write(struct.pack("<IQ", _fourcc("full"), nlist))
-            sizes.tofile(f)
-        else:
-            f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
-            np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
-        for l in nonzero:
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            codes[a:b].tofile(f)
-            ids[a:b].tofile(f)
+        _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+
+
+def _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe) -> None:
+    (nlist, d), (n, m) = centroids.shape, codes.shape
+    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
+    f.write(struct.pack("<I", _fourcc("IwPQ")))
+    f.write(_header(d, n))
+    f.write(struct.pack("<QQ", nlist, nprobe))
+    f.write(struct.pack("<I", _fourcc("IxFI")))
+    f.write(_header(d, nlist))
+    f.write(struct.pack("<Q", nlist * d))
+    centroids.tofile(f)
+    f.write(struct.pack("<BQ", 0, 0))
+    f.write(struct.pack("<BQ", 1, m))                        # by_residual, code_size
+    f.write(struct.pack("<QQQQ", d, m, 8, 256 * d))          # ProductQuantizer: d, M, nbits, centroids
+    codebooks.tofile(f)
+    f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, m))
+    nonzero = np.flatnonzero(sizes)
+    if len(nonzero) > nlist // 2:
+        f.write(struct.pack("<IQ", _fourcc("full"), nlist))
+        sizes.tofile(f)
+    else:
+        f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
+        np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
+    for l in nonzero:
+        a, b = int(list_off[l]), int(list_off[l + 1])
+        codes[a:b].tofile(f)
+        ids[a:b].tofile(f)
+
+
+def _read_ivf_pq_record(f, p):
+    centroids, list_off, nprobe, _, m, codebooks = _read_ivf_head(f, p, pq=True)
+    n = int(list_off[-1])
+    codes = np.empty((n, m), dtype=np.uint8)
+    ids = np.empty((n,), dtype=np.int64)
+    for l in np.flatnonzero(np.diff(list_off)):
+        a, b = int(list_off[l]), int(list_off[l + 1])
+        codes[a:b] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
+        ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
+    return {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off,
+            "nprobe": nprobe}
 
 
 def read_ivf_pq_ip(path):
@@ -322,16 +349,60 @@ def read_ivf_pq_ip(path):
     if not p.exists():
         raise _missing(p)
     with open(p, "rb") as f:
-        centroids, list_off, nprobe, _, m, codebooks = _read_ivf_head(f, p, pq=True)
-        n = int(list_off[-1])
-        codes = np.empty((n, m), dtype=np.uint8)
-        ids = np.empty((n,), dtype=np.int64)
-        for l in np.flatnonzero(np.diff(list_off)):
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            codes[a:b] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
-            ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
-    return {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off,
-            "nprobe": nprobe}
+        return _read_ivf_pq_record(f, p)
+
+
+def write_ivf_pq_refine_ip(path, centroids, codebooks, codes, ids, list_off, kind: int, k_factor: int, rows: np.ndarray,
+                           scales=None, nprobe: int = 1) -> None:
+    """An 'IwPQ' record plus the compact rows of a re-ranking index in the same list order: rows [n,d] int8 with scales [n]
+    fp32 (kind 8) or rows [n,d] uint16 bf16 bit patterns (kind 16).  This repository's own format (module docstring)."""
+    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    nlist, d = centroids.shape
+    n, m = codes.shape
+    assert kind in (8, 16) and k_factor >= 1
+    rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
+    assert d % m == 0 and codebooks.shape == (m, 256, d // m) and rows.shape == (n, d)
+    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    with open(path, "wb") as f:
+        f.write(struct.pack("<IIII", _fourcc("WiPR"), 1, kind, k_factor))
+        _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+        f.write(struct.pack("<Q", rows.nbytes))
+        rows.tofile(f)
+        if kind == 8:
+            scales = np.ascontiguousarray(scales, dtype=np.float32)
+            assert scales.shape == (n,)
+            f.write(struct.pack("<Q", n))
+            scales.tofile(f)
+
+
+def read_ivf_pq_refine_ip(path):
+    """-> the dict of read_ivf_pq_ip plus kind, k_factor, rows [n,d] (int8 / uint16 bf16 bits) and scales [n] (None for kind 16)."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        cc, version, kind, k_factor = struct.unpack("<IIII", f.read(16))
+        if cc != _fourcc("WiPR") or version != 1 or kind not in (8, 16) or k_factor < 1:
+            raise RuntimeError(f"{p}: not a re-ranking IndexIVFPQ file (type 0x{cc:08x}, version {version}, kind {kind}, "
+                               f"k_factor {k_factor})")
+        out = _read_ivf_pq_record(f, p)
+        n, d = out["codes"].shape[0], out["centroids"].shape[1]
+        (nbytes,) = struct.unpack("<Q", f.read(8))
+        if nbytes != n * d * (1 if kind == 8 else 2):
+            raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
+        rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=n * d).reshape(n, d)
+        scales = None
+        if kind == 8:
+            (ns,) = struct.unpack("<Q", f.read(8))
+            if ns != n:
+                raise RuntimeError(f"{p}: {ns} scales for {n} rows")
+            scales = np.fromfile(f, dtype=np.float32, count=n)
+    out.update(kind=int(kind), k_factor=int(k_factor), rows=rows, scales=scales)
+    return out
 
 
 def index_fourcc(path) -> str:

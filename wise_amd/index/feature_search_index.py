@@ -15,6 +15,9 @@ and training-sample size chosen as at feature_search_index.py:55-59, k-means and
 `IndexIVFPQ<m>` (for example `IndexIVFPQ64`; bare `IndexIVFPQ` = m = d / 4), is the IVF+PQ family of the reference's index
 study (docs/Search-Index-Evaluation.md:105-123): the same coarse stage over lists of m-byte codes (wise_amd/index/ivf_pq.py).
 Under a process group it behaves as unsharded IndexIVFFlat does: rank 0 builds, every rank loads the whole (small) file.
+`IndexIVFPQ<m>R8` / `IndexIVFPQ<m>R16` (for example `IndexIVFPQ64R8`) are that index with a re-ranking stage over compact rows kept
+beside the codes (int8 + a scale per row / bf16; IVFPQRefineIPIndex, faiss's IndexRefine); their file is this repository's own
+format (faiss_io.py, 'WiPR') and they are never sharded either.
 
 **One process per GPU** (the reference has no distributed path).  When `torch.distributed` is initialised
 with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the flat index by rows:
@@ -48,7 +51,7 @@ from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
-from .ivf_pq import IVFPQIPIndex, check_pq_shape
+from .ivf_pq import IVFPQIPIndex, IVFPQRefineIPIndex, check_pq_shape, check_refine_shape
 from .search_index import SearchIndex
 from .sharded import ShardedFlatIPIndex, ShardedIVFFlatIPIndex, shard_range
 
@@ -83,6 +86,24 @@ def parse_ivfpq_type(index_type, feature_dim=None):
     if feature_dim is not None:
         check_pq_shape(feature_dim, m)
     return m
+
+
+def parse_ivfpq_refine_type(index_type, feature_dim=None):
+    """(m, kind) of 'IndexIVFPQ<m>R<kind>' ('IndexIVFPQ64R8' -> (64, 8); m as parse_ivfpq_type reads it, the bare
+    'IndexIVFPQR16' included), None for any other index type.  A kind other than 8 or 16 is a ValueError; with feature_dim
+    the shapes of the codes and of the store are checked (ValueError)."""
+    head, sep, tail = index_type.rpartition('R')
+    if not sep or not tail.isdigit() or not tail.isascii():
+        return None
+    m = parse_ivfpq_type(head, feature_dim)
+    if m is None:
+        return None
+    kind = int(tail)
+    if kind not in (8, 16):
+        raise ValueError(f'{index_type}: the re-ranking stores are R8 (int8 rows and a scale each) and R16 (bf16 rows)')
+    if feature_dim is not None:
+        check_refine_shape(feature_dim, kind)
+    return m, kind
 
 
 def _sharded_ivf_on():
@@ -143,7 +164,8 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        is_pq = parse_ivfpq_type(index_type) is not None
+        refine = parse_ivfpq_refine_type(index_type)
+        is_pq = parse_ivfpq_type(index_type) is not None or refine is not None
         if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq:
             raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> are the index types '
                                       f'WISE builds')
@@ -158,7 +180,10 @@ class FeatureSearchIndex(SearchIndex):
             feature_store.enable_read(shard_shuffle=False)
         feature_count = feature_store.feature_count
         feature_dim = feature_store.feature_dim
-        pq_m = parse_ivfpq_type(index_type, feature_dim) if is_pq else None      # a bad shape is refused before any row is read
+        if refine is not None:                                                    # a bad shape is refused before any row is read
+            pq_m, kind = parse_ivfpq_refine_type(index_type, feature_dim)
+        else:
+            pq_m = parse_ivfpq_type(index_type, feature_dim) if is_pq else None
 
         # the on-disk index is assembled on the host (I/O-bound: tar + unpickle per vector), 512 at a time
         X = np.empty((feature_count, feature_dim), dtype=np.float32)
@@ -182,11 +207,18 @@ class FeatureSearchIndex(SearchIndex):
             sample = np.random.default_rng(1234).permutation(n)[:train_count]
             sample.sort()
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
-            ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
+            if refine is not None:
+                ivf = IVFPQRefineIPIndex(feature_dim, cell_count, pq_m, kind)
+            else:
+                ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
             ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
-            if is_pq:
+            if refine is not None:
+                c, cb, codes, ids_s, off = ivf.lists_host()
+                rows, scales = ivf.store_host()
+                faiss_io.write_ivf_pq_refine_ip(index_fn, c, cb, codes, ids_s, off, kind, ivf.k_factor, rows, scales, nprobe=ivf.nprobe)
+            elif is_pq:
                 c, cb, codes, ids_s, off = ivf.lists_host()
                 faiss_io.write_ivf_pq_ip(index_fn, c, cb, codes, ids_s, off, nprobe=ivf.nprobe)
             else:
@@ -301,6 +333,17 @@ class FeatureSearchIndex(SearchIndex):
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'WiPR':
+            import torch                             # unsharded, as 'IwPQ' below
+            f = faiss_io.read_ivf_pq_refine_ip(index_fn)
+            index = IVFPQRefineIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0], f["kind"],
+                                       k_factor=f["k_factor"])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), rows,
+                              None if f["scales"] is None else torch.from_numpy(f["scales"]))
+            index.nprobe = f["nprobe"]
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwPQ':
             import torch                             # small: every rank of a process group loads the whole file
             f = faiss_io.read_ivf_pq_ip(index_fn)

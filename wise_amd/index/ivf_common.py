@@ -6,12 +6,13 @@ faiss-shaped surface around the two.
                       products; deterministic (seeded sample for the initial centroids, empty cells re-seeded from the
                       fullest cell); the assignment of rows to lists; the probes of a query
   ListStore           the payload (fp32 rows or uint8 codes) and the ids grouped by list, with the chunks added since the
-                      last merge
+                      last merge; optionally further per-row arrays kept in the same order (the compact rows a re-ranking
+                      index scores its candidates from, ivf_pq.py)
   IVFIndexBase        nprobe, direct map, numpy search and the other attributes the REST layer touches on either index
 """
 from __future__ import annotations
 
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -177,23 +178,34 @@ class ListStore:
     """`data` [N, width] (fp32 rows or uint8 codes) and `ids` [N] grouped by list, `list_off` [nlist + 1] int64; `n` counts
     the chunks not yet merged too.  Contract: within a list, rows stay in their order of insertion (the grouping is a stable
     sort and the rows already stored come first) — the sharded index's bit-equality with the one-GPU index rests on it.
-    `gather(data, order)` is the per-dtype row gather (wise_ivf_gather_rows / wise_pq_gather_codes)."""
+    `gather(data, order)` is the per-dtype row gather (wise_ivf_gather_rows / wise_pq_gather_codes).
+    `extra_gathers`: one gather per further per-row array; `extra` then holds those arrays ([N, ...], first dimension = row),
+    passed to `append` / `adopt` in that order, merged under the same stable order as the payload and counted by nbytes()."""
 
-    def __init__(self, nlist: int, width: int, dtype: torch.dtype, device: torch.device, gather: Callable):
+    def __init__(self, nlist: int, width: int, dtype: torch.dtype, device: torch.device, gather: Callable,
+                 extra_gathers: Sequence[Callable] = ()):
         self.nlist, self.width, self.dtype, self.device, self._gather = nlist, width, dtype, device, gather
-        self._pending: List[tuple] = []                  # (payload, ids, assign) chunks not yet merged into the lists
+        self._extra_gathers = tuple(extra_gathers)
+        self._pending: List[tuple] = []                  # (payload, ids, assign, extra) chunks not yet merged into the lists
+        self.extra: List[torch.Tensor] = []
         self.data: Optional[torch.Tensor] = None
         self.ids: Optional[torch.Tensor] = None
         self.list_off: Optional[torch.Tensor] = None
         self.n = 0
 
-    def append(self, payload: torch.Tensor, ids: torch.Tensor, assign: torch.Tensor) -> None:
-        self._pending.append((payload, ids, assign))
+    def _check_extra(self, extra: Sequence[torch.Tensor], n: int) -> tuple:
+        if len(extra) != len(self._extra_gathers) or any(t.shape[0] != n for t in extra):
+            raise ValueError(f"ListStore: expected {len(self._extra_gathers)} extra arrays of {n} rows")
+        return tuple(extra)
+
+    def append(self, payload: torch.Tensor, ids: torch.Tensor, assign: torch.Tensor, extra: Sequence[torch.Tensor] = ()) -> None:
+        self._pending.append((payload, ids, assign, self._check_extra(extra, payload.shape[0])))
         self.n += payload.shape[0]
 
-    def adopt(self, data: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> None:
+    def adopt(self, data: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, extra: Sequence[torch.Tensor] = ()) -> None:
         """Take a payload that is already grouped by list (file load); chunks not yet merged are dropped."""
         self._pending = []
+        self.extra = [t.to(self.device).contiguous() for t in self._check_extra(extra, data.shape[0])]
         self.data = data.to(self.device, self.dtype).contiguous()
         self.ids = ids.to(self.device, torch.int64).contiguous()
         self.list_off = list_off.to(self.device, torch.int64).contiguous()
@@ -204,7 +216,7 @@ class ListStore:
         if self._pending:
             lib = _lib.lib()
             st = _lib.stream_ptr()
-            old = [(self.data, self.ids)] if self.data is not None and self.data.shape[0] else []
+            old = [(self.data, self.ids, None, tuple(self.extra))] if self.data is not None and self.data.shape[0] else []
             old_assign = []
             if old:
                 oa = torch.empty(self.data.shape[0], dtype=torch.int64, device=self.device)     # the rows already grouped: list c, list_off[c] .. [c + 1]
@@ -215,6 +227,8 @@ class ListStore:
             alld = torch.cat([p[0] for p in old + self._pending]).contiguous()
             allids = torch.cat([p[1] for p in old + self._pending]).contiguous()
             self.data = self._gather(alld, order)
+            self.extra = [g(torch.cat([p[3][e] for p in old + self._pending]).contiguous(), order)
+                          for e, g in enumerate(self._extra_gathers)]
             ids = torch.empty_like(allids)
             _lib.check(lib.wise_ivf_gather_i64(allids.data_ptr(), order.data_ptr(), order.shape[0], ids.data_ptr(), st), "wise_ivf_gather_i64")
             self.ids, self.list_off, self._pending = ids, list_off, []
@@ -224,17 +238,18 @@ class ListStore:
             self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
 
     def nbytes(self) -> int:
-        """Bytes of HBM the merged lists hold: payload, ids, offsets."""
-        return sum(t.numel() * t.element_size() for t in (self.data, self.ids, self.list_off))
+        """Bytes of HBM the merged lists hold: payload, ids, offsets, extra arrays."""
+        return sum(t.numel() * t.element_size() for t in (self.data, self.ids, self.list_off, *self.extra))
 
 
 class IVFIndexBase:
     """One CoarseQuantizer (`_coarse`), one ListStore (`_lists`), and the surface both indexes show around them."""
 
-    def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable):
+    def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable,
+                 extra_gathers: Sequence[Callable] = ()):
         self._coarse = CoarseQuantizer(d, nlist, device)
         self.d, self.nlist, self.device = self._coarse.d, self._coarse.nlist, self._coarse.device
-        self._lists = ListStore(self.nlist, width, dtype, self.device, gather)
+        self._lists = ListStore(self.nlist, width, dtype, self.device, gather, extra_gathers)
         self.nprobe = 1           # faiss default; the REST layer sets it (routes.py:902)
         self.parallel_mode = 0    # accepted and ignored (routes.py:901)
         self.direct_map = _DirectMap()

@@ -15,6 +15,12 @@ N * (m + 8) bytes of codes and ids, the centroids [nlist, d] and the codebooks [
   reconstruct_batch   decoded, hence approximate, as in faiss: c_l + concat_j cb[j][code_j]
 What is exact and tested: given the same centroids, codebooks and codes the scan equals a float32 restatement bit for bit
 (tests/ivfpq_ref.py); the trainer is held to the same restatement's distortion.
+
+IVFPQRefineIPIndex (index types IndexIVFPQ<m>R8 / IndexIVFPQ<m>R16) is the same index with a re-ranking stage, faiss's
+IndexRefine: the rows are also kept in list order as compact rows — int8 with a scale per row (d + 4 bytes) or bf16 (2 d bytes),
+built per chunk by wise_ip_shadow_i8 / wise_ip_shadow_bf16 — and a search takes the k * k_factor best positions of the PQ scan
+and scores them again from those rows (wise_ivf_refine, bit-equal to tests/ivfpq_refine_ref.py).  reconstruct_batch returns the
+dequantised stored row.
 """
 from __future__ import annotations
 
@@ -50,10 +56,26 @@ def _gather_codes(codes: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _gather_wide(rows: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """compact rows (whole multiples of 16 bytes) moved as rows of floats: the copy does not look at the values"""
+    out = torch.empty_like(rows)
+    _lib.check(_lib.lib().wise_ivf_gather_rows(rows.data_ptr(), idx.data_ptr(), idx.shape[0], rows.shape[1] * rows.element_size() // 4,
+                                               out.data_ptr(), _lib.stream_ptr()), "wise_ivf_gather_rows")
+    return out
+
+
+def _gather_scales(scales: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """[n] fp32 moved as rows of 4 bytes"""
+    out = torch.empty_like(scales)
+    _lib.check(_lib.lib().wise_pq_gather_codes(scales.data_ptr(), idx.data_ptr(), idx.shape[0], 4, out.data_ptr(), _lib.stream_ptr()),
+               "wise_pq_gather_codes")
+    return out
+
+
 class IVFPQIPIndex(IVFIndexBase):
-    def __init__(self, d: int, nlist: int, m: int, nbits: int = 8, device: str = "cuda"):
+    def __init__(self, d: int, nlist: int, m: int, nbits: int = 8, device: str = "cuda", extra_gathers=()):
         check_pq_shape(int(d), int(m), int(nbits))
-        super().__init__(d, nlist, device, width=int(m), dtype=torch.uint8, gather=_gather_codes)
+        super().__init__(d, nlist, device, width=int(m), dtype=torch.uint8, gather=_gather_codes, extra_gathers=extra_gathers)
         self.m, self.nbits = int(m), 8
         self.dsub = self.d // self.m
         self.niter = 10           # of the codebook training; the coarse k-means keeps its own
@@ -134,7 +156,11 @@ class IVFPQIPIndex(IVFIndexBase):
             xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
             a = self._coarse.assign_device(xs, self.centroids)
             codes = self._encode(self._residuals(xs, a), self.codebooks)
-            self._lists.append(codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a)
+            self._lists.append(codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a, self._extra_rows(xs))
+
+    def _extra_rows(self, xs: torch.Tensor) -> tuple:
+        """What else the lists keep of a chunk of rows (nothing: the codes are all there is)."""
+        return ()
 
     def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> "IVFPQIPIndex":
         """Take codes that are already grouped by list (file load)."""
@@ -144,44 +170,53 @@ class IVFPQIPIndex(IVFIndexBase):
         return self
 
     # -- search ---------------------------------------------------------------------------------
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
+    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False) -> None:
+        """Coarse stage, bias, tables and wise_ivfpq_scan for the queries qs into D / I [n, k]; positions: I receives positions
+        in the lists instead of external ids."""
         lib = _lib.lib()
+        nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
+        need = lib.wise_ivfpq_scan_workspace_bytes(n, nprobe, k, self.m)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k} m={self.m}")
+        ws = self._workspace(need)
+        probes = self._coarse.probes_device(qs, nprobe).contiguous()
+        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
+                                    bias.data_ptr(), st), "wise_pq_bias")
+        lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_lut(qs.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
+        rc = lib.wise_ivfpq_scan(ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist,
+                                 0 if positions else ls.ids.data_ptr(), lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe,
+                                 k, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        _lib.check(rc, "wise_ivfpq_scan")
+
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
         q = self._queries(q)
         nq = q.shape[0]
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        nprobe, ls = self._clamped_nprobe(), self._lists
-        st = _lib.stream_ptr()
         for s in range(0, nq, chunk):                    # bounds the tables: chunk * m KiB
-            qs = q[s:s + chunk]
-            n = qs.shape[0]
-            need = lib.wise_ivfpq_scan_workspace_bytes(n, nprobe, k, self.m)
-            if need == 0:
-                raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k} m={self.m}")
-            ws = self._workspace(need)
-            probes = self._coarse.probes_device(qs, nprobe).contiguous()
-            bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
-            _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
-                                        bias.data_ptr(), st), "wise_pq_bias")
-            lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
-            _lib.check(lib.wise_pq_lut(qs.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
-            rc = lib.wise_ivfpq_scan(ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist,
-                                     ls.ids.data_ptr(), lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k,
-                                     D[s:].data_ptr(), I[s:].data_ptr(), ws.data_ptr(), ws.numel(), st)
-            _lib.check(rc, "wise_ivfpq_scan")
+            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk])
         return D, I
 
     # -- the rest of the surface the REST layer touches -------------------------------------------
+    def _positions(self, ids) -> torch.Tensor:
+        """[n] int64 on the device: where each id sits in the lists (-1: unknown)."""
+        self._finalize()
+        ls = self._lists
+        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
+        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), _lib.stream_ptr()),
+                   "wise_pq_find")
+        return pos
+
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + its codewords; NaN for an unknown id."""
         lib = _lib.lib()
-        self._finalize()
+        pos = self._positions(ids)
         st, ls = _lib.stream_ptr(), self._lists
-        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
-        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
-        _lib.check(lib.wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
-        out = torch.empty(qi.numel(), self.d, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), qi.numel(), ls.list_off.data_ptr(), self.nlist,
+        out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
                                       self.centroids.data_ptr(), self.codebooks.data_ptr(), self.d, self.m, out.data_ptr(), st),
                    "wise_pq_decode")
         return out.cpu().numpy()
@@ -192,3 +227,109 @@ class IVFPQIPIndex(IVFIndexBase):
         ls = self._lists
         return (self.centroids.cpu().numpy(), self.codebooks.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(),
                 ls.list_off.cpu().numpy())
+
+
+REFINE_KINDS = (8, 16)
+MAX_CANDIDATES = 2048            # the most positions one scan returns and one wise_ivf_refine call takes
+# The smallest k_factor of {1, 2, 5, 10, 20, 50, 100, 200} whose recall@10 is within 0.01 of the largest one's.
+# PROVISIONAL: 50 is what the CPU study of tests/golden/ivfpq_refine_quality.json shows (60,000 rows); the sweep of
+# tools/ivfpq_refine_bench.py on an MI355X (profiles/ivfpq_refine_bench.json) has not been run yet.
+DEFAULT_K_FACTOR = 50
+
+
+def check_refine_shape(d: int, kind: int) -> None:
+    """The stores wise_ivf_refine serves, which are the shapes the two builders take (include/wise_hip.h); ValueError otherwise."""
+    if kind not in REFINE_KINDS:
+        raise ValueError(f"IVFPQRefineIPIndex: kind={kind}: the stores are 8 (int8 rows + a scale each) and 16 (bf16 rows)")
+    step = 16 if kind == 8 else 8
+    if d % step or d < step or d > 1024:
+        raise ValueError(f"IVFPQRefineIPIndex: d={d} must be a multiple of {step} in [{step}, 1024] for the {kind}-bit store")
+
+
+class IVFPQRefineIPIndex(IVFPQIPIndex):
+    """IVFPQIPIndex + compact rows in list order + a re-ranking stage (module docstring).  `k_factor` as on faiss's IndexRefine:
+    a search for k re-ranks the min(k * k_factor, 2048) best positions of the PQ scan."""
+
+    def __init__(self, d: int, nlist: int, m: int, kind: int, k_factor: int = DEFAULT_K_FACTOR, device: str = "cuda"):
+        check_refine_shape(int(d), int(kind))
+        super().__init__(d, nlist, m, device=device, extra_gathers=(_gather_wide, _gather_scales) if kind == 8 else (_gather_wide,))
+        self.kind = int(kind)
+        self.k_factor = int(k_factor)
+
+    @property
+    def _row_dtype(self) -> torch.dtype:
+        return torch.int8 if self.kind == 8 else torch.int16          # int16: bf16 bit patterns
+
+    def _extra_rows(self, xs: torch.Tensor) -> tuple:
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        rows = torch.empty(xs.shape, dtype=self._row_dtype, device=self.device)
+        norms = torch.empty(4, dtype=torch.float32, device=self.device)      # the builders' error norms: scratch, not used here
+        if self.kind == 8:
+            scales = torch.empty(xs.shape[0], dtype=torch.float32, device=self.device)
+            _lib.check(lib.wise_ip_shadow_i8(xs.data_ptr(), xs.shape[0], self.d, rows.data_ptr(), scales.data_ptr(), norms.data_ptr(), st),
+                       "wise_ip_shadow_i8")
+            return rows, scales
+        _lib.check(lib.wise_ip_shadow_bf16(xs.data_ptr(), xs.shape[0], self.d, rows.data_ptr(), norms.data_ptr(), st), "wise_ip_shadow_bf16")
+        return (rows,)
+
+    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, rows: torch.Tensor = None,
+                    scales: torch.Tensor = None) -> "IVFPQRefineIPIndex":
+        """Take codes and compact rows that are already grouped by list (file load)."""
+        if codes.dim() != 2 or codes.shape[1] != self.m:
+            raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
+        if rows is None or tuple(rows.shape) != (codes.shape[0], self.d) or rows.dtype != self._row_dtype:
+            raise ValueError(f"adopt_lists: expected rows [{codes.shape[0]},{self.d}] {self._row_dtype}")
+        if self.kind == 8 and (scales is None or tuple(scales.shape) != (codes.shape[0],) or scales.dtype != torch.float32):
+            raise ValueError(f"adopt_lists: expected scales [{codes.shape[0]}] float32")
+        self._lists.adopt(codes, ids, list_off, (rows, scales) if self.kind == 8 else (rows,))
+        return self
+
+    def _store(self):
+        """(rows pointer, scales pointer or 0) of the merged lists"""
+        ex = self._lists.extra
+        return ex[0].data_ptr(), ex[1].data_ptr() if self.kind == 8 else 0
+
+    def candidates(self, k: int) -> int:
+        """How many positions of the PQ scan a search for k re-ranks."""
+        return max(k, min(k * max(self.k_factor, 1), MAX_CANDIDATES))
+
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
+        lib = _lib.lib()
+        q = self._queries(q)
+        if k < 1 or k > MAX_CANDIDATES:
+            raise ValueError(f"search: unsupported k={k} (1 <= k <= {MAX_CANDIDATES})")
+        nq, kc, ls, st = q.shape[0], self.candidates(k), self._lists, _lib.stream_ptr()
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if ls.n == 0:
+            return D.fill_(-3.4028234663852886e38), I.fill_(-1)
+        rows, scales = self._store()
+        for s in range(0, nq, chunk):
+            qs = q[s:s + chunk]
+            n = qs.shape[0]
+            cD = torch.empty(n, kc, dtype=torch.float32, device=self.device)
+            cand = torch.empty(n, kc, dtype=torch.int64, device=self.device)
+            self._scan(qs, kc, cD, cand, positions=True)
+            _lib.check(lib.wise_ivf_refine(rows, self.kind, scales, ls.n, self.d, ls.ids.data_ptr(), qs.data_ptr(), n, cand.data_ptr(),
+                                           kc, k, D[s:s + chunk].data_ptr(), I[s:s + chunk].data_ptr(), st), "wise_ivf_refine")
+        return D, I
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """The stored rows, dequantised (faiss's IndexRefine reconstructs from its refine index too); NaN for an unknown id."""
+        pos = self._positions(ids)
+        out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
+        if self._lists.n == 0:
+            return out.fill_(float("nan")).cpu().numpy()
+        rows, scales = self._store()
+        _lib.check(_lib.lib().wise_ivf_refine_rows(rows, self.kind, scales, self._lists.n, self.d, pos.data_ptr(), pos.numel(),
+                                                   out.data_ptr(), _lib.stream_ptr()), "wise_ivf_refine_rows")
+        return out.cpu().numpy()
+
+    def store_host(self):
+        """(rows [N,d] int8 or uint16 bf16 bits, scales [N] float32 or None) of the merged lists as numpy."""
+        self._finalize()
+        ex = self._lists.extra
+        if self._lists.n == 0:
+            return np.empty((0, self.d), dtype=np.int8 if self.kind == 8 else np.uint16), (np.empty(0, np.float32) if self.kind == 8 else None)
+        rows = ex[0].cpu().numpy()
+        return (rows, ex[1].cpu().numpy()) if self.kind == 8 else (rows.view(np.uint16), None)

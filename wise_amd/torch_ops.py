@@ -41,6 +41,8 @@ SCHEMAS = {
     "ip_scores": "(Tensor X, Tensor Q) -> Tensor",
     "select_topk": "(Tensor scores, int k) -> Tensor",
     "ivf_scan": "(Tensor X, Tensor list_off, Tensor? ids, Tensor Q, Tensor probes, int k) -> (Tensor, Tensor)",
+    # the re-ranking stage of IndexIVFPQ<m>R8 / R16 (faiss IndexRefine): rows int8 with scales, or bf16 bit patterns (int16)
+    "ivf_refine": "(Tensor rows, Tensor? scales, Tensor? ids, Tensor Q, Tensor cand_pos, int k) -> (Tensor, Tensor)",
     # HP-1 (open_clip encode_image / encode_text, msclap audio_encoder; src/feature/*.py)
     "vit_forward": "(Tensor images, Tensor wb, Tensor pf, int[] config) -> Tensor",
     "text_forward": "(Tensor tokens, Tensor wb, Tensor pf, int[] config) -> Tensor",
@@ -238,6 +240,30 @@ def _ivf_scan(X, list_off, ids, Q, probes, k):
     return D, I
 
 
+def _ivf_refine(rows, scales, ids, Q, cand_pos, k):
+    lib = _lib.lib()
+    _dev(rows, scales, ids, Q, cand_pos)
+    if rows.dim() != 2 or rows.dtype not in (torch.int8, torch.int16) or not rows.is_contiguous():
+        raise ValueError("wise_hip::ivf_refine: rows [N,d] contiguous, int8 (with scales [N]) or int16 (bf16 bit patterns)")
+    kind = 8 if rows.dtype == torch.int8 else 16
+    N, d = rows.shape
+    if kind == 8:
+        if scales is None:
+            raise ValueError("wise_hip::ivf_refine: int8 rows need their scales")
+        _req(scales, torch.float32, "scales", "ivf_refine", N)
+    _req(ids, torch.int64, "ids", "ivf_refine", N)
+    _req(cand_pos, torch.int64, "cand_pos", "ivf_refine")
+    Q = _f32c(Q)
+    nq, kc = cand_pos.shape
+    if Q.shape != (nq, d):
+        raise ValueError(f"wise_hip::ivf_refine: Q must be [{nq},{d}]")
+    D = torch.empty(nq, k, dtype=torch.float32, device=rows.device)
+    I = torch.empty(nq, k, dtype=torch.int64, device=rows.device)
+    _check(lib.wise_ivf_refine(rows.data_ptr(), kind, _lib.ptr(scales) if kind == 8 else 0, N, d, _lib.ptr(ids), Q.data_ptr(), nq,
+                               cand_pos.data_ptr(), kc, k, D.data_ptr(), I.data_ptr(), _lib.stream_ptr()), "wise_ivf_refine")
+    return D, I
+
+
 # ---------------------------------------------------------------------------------------------- HP-1
 def _vit_forward(images, wb, pf, config: List[int]):
     lib = _lib.lib()
@@ -358,6 +384,7 @@ _IMPLS = {
     "ip_scores": (_ip_scores, lambda X, Q: X.new_empty((Q.shape[0], X.shape[0]), dtype=torch.float32)),
     "select_topk": (_select_topk, lambda s, k: s.new_empty((s.shape[0], k), dtype=torch.int64)),
     "ivf_scan": (_ivf_scan, lambda X, lo, ids, Q, probes, k: _fake_pair(Q.shape[0], k, X)),
+    "ivf_refine": (_ivf_refine, lambda rows, scales, ids, Q, cand, k: _fake_pair(Q.shape[0], k, rows)),
     "vit_forward": (_vit_forward, lambda im, wb, pf, cfg: im.new_empty((im.shape[0], cfg[6]), dtype=torch.float32)),
     "text_forward": (_text_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[6]), dtype=torch.float32)),
     "xlmr_forward": (_xlmr_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[8]), dtype=torch.float32)),
