@@ -34,7 +34,8 @@ const char* wise_last_error(void);
  * norms[4]), wise_ip_topk_shadow_workspace_bytes depends on nq and returns 0 under 2^18 rows, two-stage k up to 1024; and,
  * added within 5: wise_vit_config.ln_fold, the wise_gemm_fold_* entry points, wise_attention_oproj_fold, wise_htsat_forward2,
  * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points,
- * wise_ivfpq_scan, wise_ivf_refine and wise_ivf_refine_rows). */
+ * wise_ivfpq_scan, wise_ivf_refine and wise_ivf_refine_rows); also added within 5: wise_ivfpq_scan_local and
+ * wise_ivf_refine_local, the last two stages on one rank's slice of an index sharded across GPUs. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -227,6 +228,23 @@ size_t wise_ivfpq_scan_workspace_bytes(int nq, int nprobe, int k, int m);
 int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids, const float* lut,
                     int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD, int64_t* outI, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* (ABI 5, additive) wise_ivfpq_scan on ONE RANK's slice of a list-major IndexIVFPQ sharded across GPUs (rank r holds rows
+ * shard_range(N_total, r, W) of the lists laid end to end; wise_amd/index/sharded.py) — what wise_ivf_scan_local_f32 is to
+ * wise_ivf_scan_f32:
+ *   codes, ids  [N,m] / [N] this rank's rows (ids are the global external ids);  pos_base >= 0: the position of its first row
+ *   list_off    [nlist+1] the global offsets clipped to the slice (lists outside it are empty)
+ *   probes, bias  [nq,nprobe] GLOBAL list numbers and their bias (the coarse stage is replicated on every rank)
+ * Probes whose clipped list is empty are dropped on the device first, in probe order, together with their bias; probe_count [nq]
+ * (optional) receives the number kept per query.  The kept probes are dealt evenly to as many probe groups as they fill and a
+ * workgroup without a group returns before it copies the query's table, so a rank pays for the ~nprobe / W lists it holds.
+ * The score's arithmetic is wise_ivfpq_scan's.  With ids == NULL outI holds pos_base + the local position (a position in the WHOLE
+ * array, what wise_ivf_refine_local takes).  Ties: the row that comes first in codes wins.  wise_topk_merge of the ranks' answers
+ * in rank order gives the bits of wise_ivfpq_scan over the whole array, ties included.  Limits as wise_ivfpq_scan (N is the
+ * slice's).  Workspace: wise_ivfpq_scan_local_workspace_bytes(nq, nprobe, k, m) bytes (0: unsupported shape). */
+size_t wise_ivfpq_scan_local_workspace_bytes(int nq, int nprobe, int k, int m);
+int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                          const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, int64_t pos_base,
+                          float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
 /* (ABI 5, additive) The re-ranking stage of IndexIVFPQ<m>R8 / IndexIVFPQ<m>R16 (faiss IndexRefine): the candidates of a PQ scan
  * are scored again from compact copies of the rows kept in list order, and the k best are kept.
  *   rows     kind 8:  [N,d] int8 with scales [N] fp32, as wise_ip_shadow_i8 writes them (a row stands for scales[r] * rows[r,:])
@@ -247,6 +265,14 @@ int wise_ivf_refine(const void* rows, int kind, const float* scales, int64_t N, 
                     const int64_t* cand_pos, int kc, int k, float* outD, int64_t* outI, void* stream);
 int wise_ivf_refine_rows(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* pos, int n, float* out,
                          void* stream);
+/* (ABI 5, additive) wise_ivf_refine over ONE RANK's slice of the store: rows / scales / ids [N] hold positions
+ * [pos_base, pos_base + N) of the whole array (pos_base >= 0).  cand_pos holds positions in the WHOLE array; an entry outside
+ * [pos_base, pos_base + N) is skipped (as -1 is by wise_ivf_refine), a kept one reads local row pos - pos_base.  outD/outI ordered by
+ * (-score, position); with ids == NULL the position in the whole array is written.  Same arithmetic, same limits, no workspace;
+ * pos_base = 0 is wise_ivf_refine.  wise_topk_merge of the ranks' answers in rank order gives the bits of wise_ivf_refine over the
+ * whole store. */
+int wise_ivf_refine_local(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids, const float* Q, int nq,
+                          const int64_t* cand_pos, int kc, int k, int64_t pos_base, float* outD, int64_t* outI, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

@@ -115,6 +115,9 @@ SIGNATURES = {
     "wise_pq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "wise_ivfpq_scan_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "wise_ivfpq_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfpq_scan_local_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "wise_ivfpq_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivf_refine_local": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp]),
     "wise_ivf_refine": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "wise_ivf_refine_rows": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i, _vp, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1794,7 +1794,7 @@ extern "C" int wise_ip_topk_f32(const float* X, int64_t N, int d, const float* Q
 // the last step of the list scans (wise_ivf_scan_f32, wise_ivfpq_scan): part [P][nq][k] keys -> outD/outI [nq][k]
 int wise::topk_list_cap(int k) { return list_cap(k); }
 int wise::merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
-                             hipStream_t st, const int* count) {
+                             hipStream_t st, const int* count, long long id_base) {
     const int cap = list_cap(k);
     int mw = 8192 / cap;
     if (mw < 1) mw = 1;
@@ -1802,7 +1802,7 @@ int wise::merge_lists_launch(const u64* part, int P, int nq, int k, const long l
     const size_t mlds = (size_t)mw * cap * 8;
     if (mlds > 48 * 1024)
         raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
-    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, P, nq, k, cap, ids, 0ll, outD, outI, 0,
+    hipLaunchKernelGGL(merge_keys_kernel, dim3(nq), dim3(mw * 64), mlds, st, part, P, nq, k, cap, ids, id_base, outD, outI, 0,
                        (const int*)nullptr, 0, count);
     WISE_LAUNCH_CHECK("merge_keys_kernel");
     return WISE_OK;

@@ -17,6 +17,11 @@
 // and walks a contiguous group of that query's probes, its waves taking 64 rows at a time, one lane per row.  Table reads are
 // random ds_read_b32 (bank conflicts are inherent to the method).  Selection is the flat scan's: sortable (score, position)
 // keys against per-wave threshold lists, folded per block, then merge_keys_kernel.
+//   wise_ivfpq_scan_local  the same scan on ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to the
+//                       slice: about nprobe / W of a query's probes hold rows there).  compact_probes_bias_kernel keeps those
+//                       probes and their bias, in probe order, and from the kept count fixes how many probe groups the query
+//                       uses; a block past that number returns before it touches the table, the others share the kept probes
+//                       evenly.  Same kernel body as the whole-index scan (pq_scan_kernel<VEC, true>).
 #include "topk_common.h"
 
 namespace wise {
@@ -158,15 +163,65 @@ __device__ __forceinline__ float pq_row_score(const unsigned char* __restrict__ 
     return acc;
 }
 
+// The least number of kept probes a probe group of the rank-local scan must have before a further group is opened.
+// plan_scan never launches more than about two blocks per CU, so on a device that runs nothing else a further group costs no
+// time, while a longer share lengthens the slowest block of the launch, which is what a caller waits for; what a larger share
+// saves is table traffic (m KiB per group) only.  1 = a group exists exactly when it has a probe with rows to scan: the
+// table is then copied once per kept probe at most — nprobe / W times instead of nprobe times — and the slowest block never
+// has more kept probes than the slowest block of the whole-index kernel run over the clipped offsets.
+constexpr int LOCAL_MIN_SHARE = 1;
+
+// one wave per query (wise_ivfpq_scan_local): keep, in probe order, the probes whose list holds rows in this slice together
+// with their bias; count[q] = the number kept, used[q] = min(G, ceil(count / LOCAL_MIN_SHARE)) = the probe groups the query uses
+__global__ __launch_bounds__(64) void compact_probes_bias_kernel(const long long* __restrict__ probes, const float* __restrict__ bias,
+                                                                 int nprobe, const long long* __restrict__ list_off, int nlist, int G,
+                                                                 long long* __restrict__ out, float* __restrict__ out_bias,
+                                                                 int* __restrict__ count, int* __restrict__ used) {
+    const int lane = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * nprobe;
+    int n = 0;
+    for (int i0 = 0; i0 < nprobe; i0 += 64) {
+        const int i = i0 + lane;
+        const long long l = (i < nprobe) ? probes[base + i] : -1;
+        const bool keep = l >= 0 && l < nlist && list_off[l + 1] > list_off[l];
+        const u64 mask = __ballot(keep);
+        if (keep) {
+            const int o = n + __popcll(mask & ((1ull << lane) - 1ull));
+            out[base + o] = l;
+            out_bias[base + o] = bias[base + i];
+        }
+        n += __popcll(mask);
+    }
+    if (lane == 0) {
+        const int want = (n + LOCAL_MIN_SHARE - 1) / LOCAL_MIN_SHARE;
+        count[blockIdx.x] = n;
+        used[blockIdx.x] = want < G ? want : G;
+    }
+}
+
 // grid (G, nq): block (g, q) scans probes [g * per, (g + 1) * per) of query q; its k keys go to part[g][q][:]
-template <int VEC>
+// LOCAL (wise_ivfpq_scan_local): probes / bias are the compacted ones, count[q] of them live, dealt evenly to used[q] groups;
+// a block past used[q] returns BEFORE the table copy (its slot of part is never read: the merge folds used[q] lists)
+template <int VEC, bool LOCAL>
 __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                       int nlist, const float* __restrict__ lut, const long long* __restrict__ probes,
                                                       const float* __restrict__ bias, int nprobe, int per, int m, int k, int cap,
-                                                      u64* __restrict__ part) {
+                                                      u64* __restrict__ part, const int* __restrict__ count,
+                                                      const int* __restrict__ used) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int q = blockIdx.y, g = blockIdx.x;
+    int p0, p1;
+    if constexpr (LOCAL) {
+        const int groups = used[q];                                         // block-uniform
+        if (g >= groups) return;
+        const long long np = count[q];
+        p0 = (int)(np * g / groups);
+        p1 = (int)(np * (g + 1) / groups);
+    } else {
+        p0 = g * per;
+        p1 = p0 + per < nprobe ? p0 + per : nprobe;
+    }
     float* tab = reinterpret_cast<float*>(smem);
     u64* lists = reinterpret_cast<u64*>(smem + (size_t)m * KSUB * 4);
     {
@@ -177,7 +232,6 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __res
     WaveList wl;
     wl.init(lists + (size_t)wave * cap, cap, k, lane);
     __syncthreads();
-    const int p0 = g * per, p1 = p0 + per < nprobe ? p0 + per : nprobe;
     for (int p = p0; p < p1; ++p) {
         const long long l = probes[(size_t)q * nprobe + p];
         if (l < 0 || l >= nlist) continue;                              // block-uniform
@@ -280,14 +334,22 @@ static bool plan_scan(int nq, int nprobe, int k, int m, ScanShape* s) {
     return s->lds <= (size_t)LDS_MAX;
 }
 
-template <int VEC>
+template <int VEC, bool LOCAL>
 static void launch_pq_scan(const ScanShape& s, int nq, const unsigned char* codes, const long long* list_off, int nlist, const float* lut,
-                           const long long* probes, const float* bias, int nprobe, int m, int k, u64* part, hipStream_t st) {
-    auto kern = pq_scan_kernel<VEC>;
+                           const long long* probes, const float* bias, int nprobe, int m, int k, u64* part, hipStream_t st,
+                           const int* count = nullptr, const int* used = nullptr) {
+    auto kern = pq_scan_kernel<VEC, LOCAL>;
     if (s.lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)s.lds);
     hipLaunchKernelGGL(kern, dim3(s.groups, nq), dim3(s.waves * 64), s.lds, st, codes, list_off, nlist, lut, probes, bias, nprobe,
-                       s.per, m, k, s.cap, part);
+                       s.per, m, k, s.cap, part, count, used);
 }
+
+// Workspace of the rank-local scan: the keys [groups][nq][k], then the kept probes [nq][nprobe], their bias, the kept counts
+// (for a call without probe_count) and the groups used per query
+static size_t local_part_bytes(const ScanShape& s, int nq, int k) { return align_up((size_t)s.groups * nq * k * sizeof(u64), 256); }
+static size_t local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
+static size_t local_bias_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(float), 256); }
+static size_t local_count_bytes(int nq) { return align_up((size_t)nq * sizeof(int), 256); }
 
 }  // namespace ivf_pq
 }  // namespace wise
@@ -384,12 +446,62 @@ extern "C" int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int
     u64* part = reinterpret_cast<u64*>(workspace);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
     const long long* pr = reinterpret_cast<const long long*>(probes);
-    if (m % 16 == 0) launch_pq_scan<16>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else if (m % 8 == 0) launch_pq_scan<8>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else if (m % 4 == 0) launch_pq_scan<4>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else launch_pq_scan<1>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
+    if (m % 16 == 0) launch_pq_scan<16, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
+    else if (m % 8 == 0) launch_pq_scan<8, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
+    else if (m % 4 == 0) launch_pq_scan<4, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
+    else launch_pq_scan<1, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
     WISE_LAUNCH_CHECK("pq_scan_kernel");
     return merge_lists_launch(part, s.groups, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st);
+}
+
+extern "C" size_t wise_ivfpq_scan_local_workspace_bytes(int nq, int nprobe, int k, int m) {
+    ScanShape s;
+    if (!plan_scan(nq, nprobe, k, m, &s) || nq > 65535) return 0;
+    return local_part_bytes(s, nq, k) + local_probe_bytes(nq, nprobe) + local_bias_bytes(nq, nprobe) + 2 * local_count_bytes(nq);
+}
+
+extern "C" int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                                     int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    ScanShape s;
+    if (!plan_scan(nq, nprobe, k, m, &s) || nq > 65535) {
+        set_error("ivfpq_scan_local: nq=%d nprobe=%d k=%d m=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048, m <= 128)", nq, nprobe, k,
+                  m);
+        return WISE_E_UNSUPPORTED;
+    }
+    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "ivfpq_scan_local: N=%lld nlist=%d pos_base=%lld out of range",
+                   (long long)N, nlist, (long long)pos_base);
+    WISE_CHECK_ARG(lut && probes && bias && outD && outI && list_off && (codes || N == 0), "ivfpq_scan_local: null pointer");
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)lut & 15) == 0, "ivfpq_scan_local: codes and lut must be 16-byte aligned");
+    const size_t need = wise_ivfpq_scan_local_workspace_bytes(nq, nprobe, k, m);
+    if (!workspace || workspace_bytes < need) {
+        set_error("ivfpq_scan_local: workspace %zu < %zu bytes", workspace_bytes, need);
+        return WISE_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
+    u64* part = reinterpret_cast<u64*>(wsb);
+    wsb += local_part_bytes(s, nq, k);
+    long long* live = reinterpret_cast<long long*>(wsb);
+    wsb += local_probe_bytes(nq, nprobe);
+    float* lbias = reinterpret_cast<float*>(wsb);
+    wsb += local_bias_bytes(nq, nprobe);
+    int* used = reinterpret_cast<int*>(wsb);
+    wsb += local_count_bytes(nq);
+    int* count = probe_count ? probe_count : reinterpret_cast<int*>(wsb);
+    const long long* lo = reinterpret_cast<const long long*>(list_off);
+    hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
+                       nlist, s.groups, live, lbias, count, used);
+    WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
+    if (m % 16 == 0) launch_pq_scan<16, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
+    else if (m % 8 == 0) launch_pq_scan<8, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
+    else if (m % 4 == 0) launch_pq_scan<4, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
+    else launch_pq_scan<1, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
+    WISE_LAUNCH_CHECK("pq_scan_kernel<local>");
+    // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
+    return merge_lists_launch(part, s.groups, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
+                              used, (long long)pos_base);
 }
 
 extern "C" int wise_pq_gather_codes(const uint8_t* codes, const int64_t* idx, int64_t n, int m, uint8_t* out, void* stream) {

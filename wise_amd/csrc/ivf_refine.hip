@@ -1,6 +1,8 @@
 // HP-2: the re-ranking stage of IndexIVFPQ<m>R8 / IndexIVFPQ<m>R16 (faiss IndexRefine over an IndexIVFPQ).
 //   wise_ivf_refine        the kc <= 2048 candidate positions a PQ scan returns are scored again from compact rows kept in list
 //                          order (int8 + per-row scale, or bf16: what wise_ip_shadow_i8 / wise_ip_shadow_bf16 build), k best kept
+//   wise_ivf_refine_local  the same over ONE RANK's slice of the store of an index sharded across GPUs: the candidates are
+//                          positions in the whole array, those outside the slice are holes (one kernel body, pos_base = 0 above)
 //   wise_ivf_refine_rows   reconstruct_batch: the dequantised row at a position
 // The stage reads kc * d (or 2 d) bytes per query — 51 KB at kc = 100, d = 512 — from rows scattered over the store: it is bound
 // by latency, not by HBM.  One workgroup per query: the query goes to LDS, a thread takes a candidate and walks its row in
@@ -77,12 +79,14 @@ __device__ inline void block_bitonic_desc(u64* buf, int cap) {
     }
 }
 
-// block = query
+// block = query.  rows / scales / ids hold positions [pos_base, pos_base + N) of the whole array; cand are positions in the whole
+// array; keys carry the local row (within a slice the order of local rows is the order of positions)
 template <int KIND>
 __global__ __launch_bounds__(THREADS) void refine_kernel(const unsigned char* __restrict__ rows, const float* __restrict__ scales,
                                                          long long N, int d, const long long* __restrict__ ids,
                                                          const float* __restrict__ Q, const long long* __restrict__ cand, int kc,
-                                                         int cap, int k, float* __restrict__ outD, long long* __restrict__ outI) {
+                                                         int cap, int k, float* __restrict__ outD, long long* __restrict__ outI,
+                                                         long long pos_base) {
     __shared__ __attribute__((aligned(16))) float qs[MAX_D];
     __shared__ u64 keys[MAX_KC];
     const int q = blockIdx.x;
@@ -91,8 +95,11 @@ __global__ __launch_bounds__(THREADS) void refine_kernel(const unsigned char* __
     for (int c = threadIdx.x; c < cap; c += THREADS) {
         u64 key = 0;
         if (c < kc) {
-            const long long r = cand[(size_t)q * kc + c];
-            if (r >= 0 && r < N) key = make_key(score_row<KIND>(rows, scales, r, d, qs), (unsigned)r);
+            const long long p = cand[(size_t)q * kc + c];
+            if (p >= pos_base && p - pos_base < N) {
+                const long long r = p - pos_base;
+                key = make_key(score_row<KIND>(rows, scales, r, d, qs), (unsigned)r);
+            }
         }
         keys[c] = key;
     }
@@ -105,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void refine_kernel(const unsigned char* __
         if (key != 0) {
             const long long r = (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
             s = f32_unorder((unsigned)(key >> 32));
-            id = ids ? ids[r] : r;
+            id = ids ? ids[r] : pos_base + r;
         }
         outD[(size_t)q * k + i] = s;
         outI[(size_t)q * k + i] = id;
@@ -155,17 +162,22 @@ using namespace wise::ivf_refine;
         }                                                                                                                         \
     } while (0)
 
-extern "C" int wise_ivf_refine(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids, const float* Q,
-                               int nq, const int64_t* cand_pos, int kc, int k, float* outD, int64_t* outI, void* stream) {
-    REFINE_CHECK_STORE("ivf_refine");
-    if (kc < 1 || kc > MAX_KC || k < 1 || k > MAX_KC) {
-        set_error("ivf_refine: kc=%d k=%d unsupported (both in [1, %d])", kc, k, MAX_KC);
+static int refine_impl(const char* what, const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids,
+                       const float* Q, int nq, const int64_t* cand_pos, int kc, int k, int64_t pos_base, float* outD, int64_t* outI,
+                       void* stream) {
+    if (!store_shape_ok(kind, d)) {
+        set_error("%s: kind=%d d=%d unsupported (kind 8: d %% 16 == 0 in [16, 1024]; kind 16: d %% 8 == 0 in [8, 1024])", what, kind, d);
         return WISE_E_UNSUPPORTED;
     }
-    WISE_CHECK_ARG(nq >= 0 && N >= 0 && N < 0xFFFFFFFFll, "ivf_refine: nq=%d N=%lld out of range", nq, (long long)N);
+    if (kc < 1 || kc > MAX_KC || k < 1 || k > MAX_KC) {
+        set_error("%s: kc=%d k=%d unsupported (both in [1, %d])", what, kc, k, MAX_KC);
+        return WISE_E_UNSUPPORTED;
+    }
+    WISE_CHECK_ARG(nq >= 0 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "%s: nq=%d N=%lld pos_base=%lld out of range", what, nq,
+                   (long long)N, (long long)pos_base);
     if (nq == 0) return WISE_OK;
-    WISE_CHECK_ARG(Q && cand_pos && outD && outI && (N == 0 || (rows && (kind == 16 || scales))), "ivf_refine: null pointer");
-    WISE_CHECK_ARG(((uintptr_t)rows & 15) == 0, "ivf_refine: rows must be 16-byte aligned");
+    WISE_CHECK_ARG(Q && cand_pos && outD && outI && (N == 0 || (rows && (kind == 16 || scales))), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)rows & 15) == 0, "%s: rows must be 16-byte aligned", what);
     int cap = 64;
     while (cap < kc) cap <<= 1;
     const unsigned char* r8 = reinterpret_cast<const unsigned char*>(rows);
@@ -174,12 +186,23 @@ extern "C" int wise_ivf_refine(const void* rows, int kind, const float* scales, 
     long long* oi = reinterpret_cast<long long*>(outI);
     if (kind == 8)
         hipLaunchKernelGGL(refine_kernel<8>, dim3(nq), dim3(THREADS), 0, (hipStream_t)stream, r8, scales, (long long)N, d, id, Q, cp, kc,
-                           cap, k, outD, oi);
+                           cap, k, outD, oi, (long long)pos_base);
     else
         hipLaunchKernelGGL(refine_kernel<16>, dim3(nq), dim3(THREADS), 0, (hipStream_t)stream, r8, scales, (long long)N, d, id, Q, cp, kc,
-                           cap, k, outD, oi);
+                           cap, k, outD, oi, (long long)pos_base);
     WISE_LAUNCH_CHECK("ivf refine_kernel");
     return WISE_OK;
+}
+
+extern "C" int wise_ivf_refine(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids, const float* Q,
+                               int nq, const int64_t* cand_pos, int kc, int k, float* outD, int64_t* outI, void* stream) {
+    return refine_impl("ivf_refine", rows, kind, scales, N, d, ids, Q, nq, cand_pos, kc, k, 0, outD, outI, stream);
+}
+
+extern "C" int wise_ivf_refine_local(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids,
+                                     const float* Q, int nq, const int64_t* cand_pos, int kc, int k, int64_t pos_base, float* outD,
+                                     int64_t* outI, void* stream) {
+    return refine_impl("ivf_refine_local", rows, kind, scales, N, d, ids, Q, nq, cand_pos, kc, k, pos_base, outD, outI, stream);
 }
 
 extern "C" int wise_ivf_refine_rows(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* pos, int n,

@@ -84,8 +84,9 @@ struct WaveList {
 // (merge_keys_kernel, ip_topk.hip); topk_list_cap(k) = entries of a WaveList that keeps k keys
 int topk_list_cap(int k);
 // count: optional [nq], the lists of part that hold keys per query (the rank-local scan); default: all P
+// id_base: with ids == nullptr the output is id_base + row
 int merge_lists_launch(const u64* part, int P, int nq, int k, const long long* ids, float* outD, long long* outI,
-                       hipStream_t st, const int* count = nullptr);
+                       hipStream_t st, const int* count = nullptr, long long id_base = 0);
 
 // batched (MFMA) scan, ip_topk_mfma.hip
 constexpr int MFMA_QB = 32;   // queries per pass (the N of v_mfma_f32_32x32x2_f32)

@@ -38,6 +38,10 @@ REPOSITORY'S OWN FORMAT, not a faiss layout (faiss's 8-bit refine stores keep a 
     u64  n_bytes | the compact rows in list order: i8[N*d] (kind 8) or bf16[N*d] (kind 16)
     u64  N | f32[N]                                                           the row scales (kind 8 only)
 
+Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' file
+of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
+the lists that overlap it.
+
 faiss is not in the container, so these layouts are UNPINNED against a real faiss binary; the round
 trip is pinned by tests/test_feature_store_index_io.py.  The rows are memory-mapped on read so a
 158 GiB index (docs/Search-Index-Evaluation.md:109) streams to the GPU without a host copy.
@@ -340,6 +344,109 @@ def _read_ivf_pq_record(f, p):
         ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
     return {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off,
             "nprobe": nprobe}
+
+
+def _read_ivf_pq_record_range(f, p, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major arrays of an 'IwPQ' record, reading only the lists that overlap the range.  List l's
+    payload sits at list_off[l] * (m + 8) bytes into the payload (codes, then ids).  -> (dict with list_off clipped, n, end of the
+    record)."""
+    centroids, list_off, nprobe, data, m, codebooks = _read_ivf_head(f, p, pq=True)
+    n = int(list_off[-1])
+    lo, hi = int(lo), int(hi)
+    if not (0 <= lo <= hi <= n):
+        raise ValueError(f"read_ivf_pq_ip_range: [{lo}, {hi}) outside [0, {n}]")
+    codes = np.empty((hi - lo, m), dtype=np.uint8)
+    ids = np.empty((hi - lo,), dtype=np.int64)
+    first = int(np.searchsorted(list_off, lo, side="right")) - 1         # the list that holds row lo
+    for l in range(max(first, 0), len(list_off) - 1):
+        s0, s1 = int(list_off[l]), int(list_off[l + 1])
+        if s0 >= hi:
+            break
+        a, b = max(s0, lo), min(s1, hi)
+        if a >= b:
+            continue
+        base = data + s0 * (m + 8)
+        f.seek(base + (a - s0) * m)
+        codes[a - lo:b - lo] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
+        f.seek(base + (s1 - s0) * m + (a - s0) * 8)
+        ids[a - lo:b - lo] = np.fromfile(f, dtype=np.int64, count=b - a)
+    out = {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
+           "nprobe": nprobe}
+    return out, n, data + n * (m + 8)
+
+
+def _pq_ntotal(f, p) -> int:
+    (cc,) = struct.unpack("<I", f.read(4))
+    if cc != _fourcc("IwPQ"):
+        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFPQ")
+    return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+
+
+def ivf_pq_ip_ntotal(path) -> int:
+    """Rows of an 'IwPQ' file (its header), without reading the lists."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        return _pq_ntotal(f, p)
+
+
+def read_ivf_pq_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major arrays read_ivf_pq_ip returns, reading only the lists that overlap the range (one rank's
+    slice of an index sharded across GPUs: wise_amd/index/sharded.py).  -> the dict of read_ivf_pq_ip with codes [hi-lo,m],
+    ids [hi-lo] and list_off = clip(list_off - lo, 0, hi - lo); centroids and codebooks are whole."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        return _read_ivf_pq_record_range(f, p, lo, hi)[0]
+
+
+def _read_refine_head(f, p):
+    cc, version, kind, k_factor = struct.unpack("<IIII", f.read(16))
+    if cc != _fourcc("WiPR") or version != 1 or kind not in (8, 16) or k_factor < 1:
+        raise RuntimeError(f"{p}: not a re-ranking IndexIVFPQ file (type 0x{cc:08x}, version {version}, kind {kind}, "
+                           f"k_factor {k_factor})")
+    return int(kind), int(k_factor)
+
+
+def ivf_pq_refine_ip_ntotal(path) -> int:
+    """Rows of a 'WiPR' file (the header of its 'IwPQ' record), without reading the lists."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        _read_refine_head(f, p)
+        return _pq_ntotal(f, p)
+
+
+def read_ivf_pq_refine_ip_range(path, lo: int, hi: int):
+    """read_ivf_pq_ip_range for a 'WiPR' file: also rows [lo, hi) of the compact rows and of the scales, read by position (they
+    are stored in list order as two plain arrays).  -> the dict of read_ivf_pq_refine_ip over the slice."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        kind, k_factor = _read_refine_head(f, p)
+        out, n, end = _read_ivf_pq_record_range(f, p, lo, hi)
+        lo, hi, d = int(lo), int(hi), out["centroids"].shape[1]
+        width = d * (1 if kind == 8 else 2)
+        f.seek(end)
+        (nbytes,) = struct.unpack("<Q", f.read(8))
+        if nbytes != n * width:
+            raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
+        f.seek(end + 8 + lo * width)
+        rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=(hi - lo) * d).reshape(hi - lo, d)
+        scales = None
+        if kind == 8:
+            f.seek(end + 8 + n * width)
+            (ns,) = struct.unpack("<Q", f.read(8))
+            if ns != n:
+                raise RuntimeError(f"{p}: {ns} scales for {n} rows")
+            f.seek(end + 8 + n * width + 8 + lo * 4)
+            scales = np.fromfile(f, dtype=np.float32, count=hi - lo)
+    out.update(kind=kind, k_factor=k_factor, rows=rows, scales=scales)
+    return out
 
 
 def read_ivf_pq_ip(path):

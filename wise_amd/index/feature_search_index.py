@@ -14,10 +14,10 @@ reference offers are built: `IndexFlatIP` (exhaustive, the hot path) and `IndexI
 and training-sample size chosen as at feature_search_index.py:55-59, k-means and list scan on the GPU).  A third,
 `IndexIVFPQ<m>` (for example `IndexIVFPQ64`; bare `IndexIVFPQ` = m = d / 4), is the IVF+PQ family of the reference's index
 study (docs/Search-Index-Evaluation.md:105-123): the same coarse stage over lists of m-byte codes (wise_amd/index/ivf_pq.py).
-Under a process group it behaves as unsharded IndexIVFFlat does: rank 0 builds, every rank loads the whole (small) file.
 `IndexIVFPQ<m>R8` / `IndexIVFPQ<m>R16` (for example `IndexIVFPQ64R8`) are that index with a re-ranking stage over compact rows kept
 beside the codes (int8 + a scale per row / bf16; IVFPQRefineIPIndex, faiss's IndexRefine); their file is this repository's own
-format (faiss_io.py, 'WiPR') and they are never sharded either.
+format (faiss_io.py, 'WiPR').  Under a process group the three behave as IndexIVFFlat does: without WISE_SHARDED_IVF=1 rank 0
+builds and every rank loads the whole file; with it they are sharded by list-major row ranges (below).
 
 **One process per GPU** (the reference has no distributed path).  When `torch.distributed` is initialised
 with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the flat index by rows:
@@ -40,6 +40,16 @@ list 1's, ...):
   * `load_index('IndexIVFFlat')`: the rank's part file if the parts of this world size exist, otherwise (with the
     switch on) rows shard_range(N, r, W) of the single file, reading only the lists that overlap them; `self.index` is a
     `ShardedIVFFlatIPIndex`, whose `search` / `reconstruct_batch` are collective and return the one-GPU IVF answer.
+`IndexIVFPQ<m>` and `IndexIVFPQ<m>R8` / `R16` take the same two paths under the same switch:
+  * `create_index`: the same collective build with a per-row byte payload in place of the fp32 row.  Rank 0 trains the coarse
+    stage AND the codebooks on the seeded sample gathered from all ranks; centroids and codebooks are broadcast; each rank
+    assigns and encodes its own rows on its GPU (and builds their compact rows and scales); the all_to_all moves codes
+    (+ compact rows, scales), ids and positions.  No rank holds fp32 rows other than those of its own store shards.  The part
+    files are complete 'IwPQ' / 'WiPR' files with clipped lists;
+  * `load_index`: the ranks agree ONCE (an all-reduce of "my part exists") whether all of them read part files or all of them
+    read rows shard_range(N, r, W) of the single file, so a missing part cannot mix the two sources; `self.index` is a
+    `ShardedIVFPQIPIndex` (one exchange per search) or a `ShardedIVFPQRefineIPIndex` (two: candidates, then re-ranked answers),
+    both returning the bits of the one-GPU index over the same centroids, codebooks, codes and stores.
 """
 import os
 from pathlib import Path
@@ -53,7 +63,8 @@ from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import IVFPQIPIndex, IVFPQRefineIPIndex, check_pq_shape, check_refine_shape
 from .search_index import SearchIndex
-from .sharded import ShardedFlatIPIndex, ShardedIVFFlatIPIndex, shard_range
+from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
+                      shard_range)
 
 
 def _dist_rank_world():
@@ -122,6 +133,8 @@ class FeatureSearchIndex(SearchIndex):
     # the classes that hold a rank's rows in HBM; CPU tests of the multi-rank wiring put stand-ins here
     flat_index_factory = FlatIPIndex
     ivf_index_factory = IVFFlatIPIndex
+    ivfpq_index_factory = IVFPQIPIndex
+    ivfpq_refine_index_factory = IVFPQRefineIPIndex
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -151,7 +164,9 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        sharded_ivf = sharded and index_type == 'IndexIVFFlat' and _sharded_ivf_on()
+        refine = parse_ivfpq_refine_type(index_type)
+        is_pq = parse_ivfpq_type(index_type) is not None or refine is not None
+        sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq) and _sharded_ivf_on()
         if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
         exists = index_fn.exists()
@@ -164,8 +179,6 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        refine = parse_ivfpq_refine_type(index_type)
-        is_pq = parse_ivfpq_type(index_type) is not None or refine is not None
         if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq:
             raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> are the index types '
                                       f'WISE builds')
@@ -196,7 +209,8 @@ class FeatureSearchIndex(SearchIndex):
             ids[n:n + m] = feature_ids_batch
             n += m
         if sharded_ivf:
-            self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world)
+            self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world, index_type=index_type, pq_m=pq_m,
+                                     kind=kind if refine is not None else None)
             print(f'  saved index part to {index_fn}')
             return
         if index_type == 'IndexIVFFlat' or is_pq:
@@ -228,8 +242,10 @@ class FeatureSearchIndex(SearchIndex):
             faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
         print(f'  saved index to {index_fn}')
 
-    def _create_sharded_ivf(self, X, ids, part_fn, rank, world):
-        """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows."""
+    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None):
+        """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows.  What travels to the
+        rank that owns a row's position is a per-row byte payload: the fp32 row (IndexIVFFlat), or the row's codes followed by its
+        compact row and scale (pq_m / kind given: IndexIVFPQ<m>, IndexIVFPQ<m>R<kind>), encoded where the row was read."""
         import torch
         import torch.distributed as dist
 
@@ -248,7 +264,12 @@ class FeatureSearchIndex(SearchIndex):
         sample.sort()
         bounds = np.searchsorted(sample, src_off)
         mine = sample[bounds[rank]:bounds[rank + 1]] - src_off[rank]
-        ivf = self.ivf_index_factory(d, cell_count)
+        if kind is not None:
+            ivf = self.ivfpq_refine_index_factory(d, cell_count, pq_m, kind)
+        elif pq_m is not None:
+            ivf = self.ivfpq_index_factory(d, cell_count, pq_m)
+        else:
+            ivf = self.ivf_index_factory(d, cell_count)
         if rank == 0:                               # k-means once, on rank 0; the centroids' bits go to every rank
             parts = [X[mine]]
             for src in range(1, world):
@@ -257,8 +278,8 @@ class FeatureSearchIndex(SearchIndex):
                     buf = torch.empty(m, d, dtype=torch.float32, device=dev)
                     dist.recv(buf, src=src)
                     parts.append(buf.cpu().numpy())
-            print(f'  training IndexIVFFlat index with {train_count} features with {cell_count} clusters ...')
-            ivf.train(np.concatenate(parts))
+            print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
+            ivf.train(np.concatenate(parts))        # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
             c = ivf.centroids if torch.is_tensor(ivf.centroids) else torch.from_numpy(np.asarray(ivf.centroids))
             c = c.to(dev, torch.float32).contiguous()
         else:
@@ -268,8 +289,26 @@ class FeatureSearchIndex(SearchIndex):
         dist.broadcast(c, src=0)
         centroids = c.cpu().numpy()
         ivf.set_centroids(centroids)
-        # each rank assigns its own rows; the per-rank list counts fix the global list-major order
-        a = ivf.assign(X)
+        codebooks = None
+        if pq_m is not None:                        # the codebooks' bits go to every rank too
+            if rank == 0:
+                cb = ivf.codebooks if torch.is_tensor(ivf.codebooks) else torch.from_numpy(np.asarray(ivf.codebooks))
+                cb = cb.to(dev, torch.float32).contiguous()
+            else:
+                cb = torch.empty(pq_m, 256, d // pq_m, dtype=torch.float32, device=dev)
+            dist.broadcast(cb, src=0)
+            codebooks = cb.cpu().numpy()
+            ivf.set_codebooks(codebooks)
+        # each rank assigns (and encodes) its own rows; the per-rank list counts fix the global list-major order
+        if pq_m is None:
+            a = ivf.assign(X)
+            fields = [X]
+        else:
+            a, *fields = ivf.encode_rows(X)         # codes [n,m] u8 (+ compact rows [n,d] i8 / bf16 bits, scales [n] f32)
+            a = np.asarray(a, dtype=np.int64)
+        # a row's payload: its fields' bytes back to back, padded to whole int32
+        widths = [int(np.prod(f.shape[1:], dtype=np.int64)) * f.dtype.itemsize for f in fields]
+        w32 = (sum(widths) + 3) // 4
         cnt = torch.from_numpy(np.bincount(a, minlength=cell_count).astype(np.int64)).to(dev)
         allc_t = torch.empty(world, cell_count, dtype=torch.int64, device=dev)
         dist.all_gather_into_tensor(allc_t.view(-1), cnt)
@@ -283,28 +322,42 @@ class FeatureSearchIndex(SearchIndex):
         his = np.array([shard_range(n_total, r, world)[1] for r in range(world)], dtype=np.int64)
         dest = np.searchsorted(his, gpos, side='right')
         send_counts = np.bincount(dest, minlength=world).astype(np.int64)
-        packed = np.empty((n, d + 4), dtype=np.int32)
-        packed[:, :d] = X[order].view(np.int32)
-        packed[:, d:d + 2] = ids[order].astype(np.int64).view(np.int32).reshape(n, 2)
-        packed[:, d + 2:] = gpos.view(np.int32).reshape(n, 2)
+        packed = np.zeros((n, w32 + 4), dtype=np.int32)
+        pbytes, b0 = packed.view(np.uint8), 0
+        for f, w in zip(fields, widths):
+            pbytes[:, b0:b0 + w] = np.ascontiguousarray(f[order]).view(np.uint8).reshape(n, w)
+            b0 += w
+        packed[:, w32:w32 + 2] = ids[order].astype(np.int64).view(np.int32).reshape(n, 2)
+        packed[:, w32 + 2:] = gpos.view(np.int32).reshape(n, 2)
         sc = torch.from_numpy(send_counts).to(dev)
         rc = torch.empty(world, dtype=torch.int64, device=dev)
         dist.all_to_all_single(rc, sc)
         recv_counts = rc.cpu().numpy()
         lo, hi = shard_range(n_total, rank, world)
-        recv = torch.empty(int(recv_counts.sum()), d + 4, dtype=torch.int32, device=dev)
+        recv = torch.empty(int(recv_counts.sum()), w32 + 4, dtype=torch.int32, device=dev)
         dist.all_to_all_single(recv, torch.from_numpy(packed).to(dev), output_split_sizes=recv_counts.tolist(),
                                input_split_sizes=send_counts.tolist())
         got = recv.cpu().numpy()
-        pos = np.ascontiguousarray(got[:, d + 2:]).view(np.int64).reshape(-1) - lo
+        pos = np.ascontiguousarray(got[:, w32 + 2:]).view(np.int64).reshape(-1) - lo
         if got.shape[0] != hi - lo or not np.array_equal(np.sort(pos), np.arange(hi - lo)):
-            raise RuntimeError(f'sharded IndexIVFFlat build: rank {rank} received rows that do not tile [{lo}, {hi})')
-        X_loc = np.empty((hi - lo, d), dtype=np.float32)
+            raise RuntimeError(f'sharded {index_type} build: rank {rank} received rows that do not tile [{lo}, {hi})')
         ids_loc = np.empty((hi - lo,), dtype=np.int64)
-        X_loc[pos] = np.ascontiguousarray(got[:, :d]).view(np.float32)
-        ids_loc[pos] = np.ascontiguousarray(got[:, d:d + 2]).view(np.int64).reshape(-1)
-        faiss_io.write_ivf_flat_ip(part_fn, centroids, X_loc, ids_loc, np.clip(list_off - lo, 0, hi - lo),
-                                   nprobe=ivf.nprobe)
+        ids_loc[pos] = np.ascontiguousarray(got[:, w32:w32 + 2]).view(np.int64).reshape(-1)
+        gbytes, b0, loc = got.view(np.uint8), 0, []
+        for f, w in zip(fields, widths):
+            arr = np.empty((hi - lo,) + f.shape[1:], dtype=f.dtype)
+            arr[pos] = np.ascontiguousarray(gbytes[:, b0:b0 + w]).view(f.dtype).reshape((got.shape[0],) + f.shape[1:])
+            loc.append(arr)
+            b0 += w
+        off_loc = np.clip(list_off - lo, 0, hi - lo)
+        if kind is not None:
+            rows = loc[1] if kind == 8 else loc[1].view(np.uint16)
+            faiss_io.write_ivf_pq_refine_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, kind, ivf.k_factor, rows,
+                                            loc[2] if kind == 8 else None, nprobe=ivf.nprobe)
+        elif pq_m is not None:
+            faiss_io.write_ivf_pq_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
+        else:
+            faiss_io.write_ivf_flat_ip(part_fn, centroids, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
 
     def _sharded_ivf_index(self, f):
         """ShardedIVFFlatIPIndex around a local index holding the slice `f` (a read_ivf_flat_ip(_range) dict)."""
@@ -317,6 +370,51 @@ class FeatureSearchIndex(SearchIndex):
         return ShardedIVFFlatIPIndex(local, merge=getattr(local, 'merge_lists', None),
                                      always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
 
+    def _sharded_ivfpq_index(self, f, pos_base):
+        """ShardedIVFPQIPIndex / ShardedIVFPQRefineIPIndex around a local index holding the slice `f` (a dict of one of the
+        faiss_io PQ readers) that starts at position pos_base of the whole list-major array."""
+        import torch
+
+        nlist, d = f["centroids"].shape
+        lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+        always = os.environ.get('WISE_SHARDED_INDEX') == '1'
+        if "kind" in f:
+            local = self.ivfpq_refine_index_factory(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
+            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
+            lists += (rows, None if f["scales"] is None else torch.from_numpy(f["scales"]))
+            wrapper = ShardedIVFPQRefineIPIndex
+        else:
+            local = self.ivfpq_index_factory(d, nlist, f["codebooks"].shape[0])
+            wrapper = ShardedIVFPQIPIndex
+        local.set_centroids(f["centroids"])
+        local.set_codebooks(f["codebooks"])
+        local.adopt_lists(*lists, pos_base=int(pos_base))
+        local.nprobe = f["nprobe"]
+        return wrapper(local, merge=getattr(local, 'merge_lists', None), always_exchange=always)
+
+    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world):
+        """The sharded load of the IndexIVFPQ family: all ranks read their part files, or all ranks read their range of the
+        single file — decided once for the group."""
+        import torch
+        import torch.distributed as dist
+
+        dev = _coll_device()
+        flag = torch.tensor([int(part_fn.exists())], dtype=torch.int64, device=dev)
+        dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+        read, read_range, ntotal = ((faiss_io.read_ivf_pq_refine_ip, faiss_io.read_ivf_pq_refine_ip_range, faiss_io.ivf_pq_refine_ip_ntotal)
+                                    if refine else (faiss_io.read_ivf_pq_ip, faiss_io.read_ivf_pq_ip_range, faiss_io.ivf_pq_ip_ntotal))
+        if bool(flag.item()):
+            f = read(part_fn)
+            ns = torch.zeros(world, dtype=torch.int64, device=dev)   # a part starts where the lower ranks' parts end
+            dist.all_gather_into_tensor(ns, torch.tensor([f["codes"].shape[0]], dtype=torch.int64, device=dev))
+            return self._sharded_ivfpq_index(f, int(ns.cpu().numpy()[:rank].sum()))
+        if not index_fn.exists():
+            have = 'this rank has its part' if part_fn.exists() else 'this rank has no part'
+            raise RuntimeError(f'{index_fn}: the part files of {world} ranks are not complete ({have}: {part_fn.name}) and there is '
+                               f'no single file to read every rank\'s rows from; parts and a single file are never mixed')
+        lo, hi = shard_range(ntotal(index_fn), rank, world)
+        return self._sharded_ivfpq_index(read_range(index_fn, lo, hi), lo)
+
     def is_index_loaded(self):
         return hasattr(self, 'index')
 
@@ -328,7 +426,10 @@ class FeatureSearchIndex(SearchIndex):
             print(f'  index {index_fn} does not exist')
             print(f'  use create-index.py script to create an index')
         # like the reference (App. B.3) a missing file raises from the reader, it does not return False
-        if sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
+        refine = parse_ivfpq_refine_type(index_type) is not None
+        if sharded and _sharded_ivf_on() and (refine or parse_ivfpq_type(index_type) is not None):
+            index = self._load_sharded_ivfpq(index_fn, part_fn, refine, rank, world)
+        elif sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip(part_fn))      # built by this many ranks
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)

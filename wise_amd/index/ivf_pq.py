@@ -21,6 +21,12 @@ IndexRefine: the rows are also kept in list order as compact rows — int8 with 
 built per chunk by wise_ip_shadow_i8 / wise_ip_shadow_bf16 — and a search takes the k * k_factor best positions of the PQ scan
 and scores them again from those rows (wise_ivf_refine, bit-equal to tests/ivfpq_refine_ref.py).  reconstruct_batch returns the
 dequantised stored row.
+
+Across GPUs (sharded.py: ShardedIVFPQIPIndex / ShardedIVFPQRefineIPIndex) an index holds ONE RANK's slice of the list-major
+arrays: all centroids and codebooks, list_off clipped to the slice, and `pos_base`, the position of its first row in the whole
+array.  `search_local_device` is then the rank's share of a search (wise_ivfpq_scan_local: only the probed lists the rank holds),
+and the re-ranking index offers its two phases separately — `candidates_local_device` (positions in the whole array) and
+`refine_local_device` (wise_ivf_refine_local: candidates outside the slice are holes).
 """
 from __future__ import annotations
 
@@ -81,6 +87,7 @@ class IVFPQIPIndex(IVFIndexBase):
         self.niter = 10           # of the codebook training; the coarse k-means keeps its own
         self.seed = 1234
         self.codebooks: Optional[torch.Tensor] = None      # [m, 256, dsub] fp32
+        self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
 
     @property
     def is_trained(self) -> bool:
@@ -162,20 +169,46 @@ class IVFPQIPIndex(IVFIndexBase):
         """What else the lists keep of a chunk of rows (nothing: the codes are all there is)."""
         return ()
 
-    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> "IVFPQIPIndex":
-        """Take codes that are already grouped by list (file load)."""
+    def encode_rows(self, x, chunk: int = 1 << 18):
+        """(assign [n] int64, codes [n, m] uint8, extra per-row arrays ...) as numpy for the rows x [n, d]: what add_with_ids
+        would put into the lists, handed back instead (the collective build moves it to the rank that owns the row's position)."""
+        if not self.is_trained:
+            raise RuntimeError("IVFPQIPIndex: train() before encode_rows()")
+        x = _rows_f32(x, self.d, "encode_rows")
+        out = None
+        for s in range(0, x.shape[0], chunk):
+            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
+            a = self._coarse.assign_device(xs, self.centroids)
+            parts = [t.cpu().numpy() for t in (a, self._encode(self._residuals(xs, a), self.codebooks), *self._extra_rows(xs))]
+            if out is None:
+                out = [np.empty((x.shape[0],) + t.shape[1:], dtype=t.dtype) for t in parts]
+            for o, t in zip(out, parts):
+                o[s:s + xs.shape[0]] = t
+        if out is None:
+            xs = torch.empty(0, self.d, dtype=torch.float32, device=self.device)
+            out = [np.empty(0, np.int64), np.empty((0, self.m), np.uint8)] + [t.cpu().numpy() for t in self._extra_rows(xs)]
+        return tuple(out)
+
+    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, pos_base: int = 0) -> "IVFPQIPIndex":
+        """Take codes that are already grouped by list (file load).  pos_base: the codes are a slice of a larger list-major
+        array that starts at this position of it (list_off clipped to the slice)."""
         if codes.dim() != 2 or codes.shape[1] != self.m:
             raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
+        if pos_base < 0:
+            raise ValueError("adopt_lists: pos_base must not be negative")
         self._lists.adopt(codes, ids, list_off)
+        self.pos_base = int(pos_base)
         return self
 
     # -- search ---------------------------------------------------------------------------------
-    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False) -> None:
+    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False, local: bool = False,
+              probe_count: Optional[torch.Tensor] = None) -> None:
         """Coarse stage, bias, tables and wise_ivfpq_scan for the queries qs into D / I [n, k]; positions: I receives positions
-        in the lists instead of external ids."""
+        in the lists instead of external ids.  local: wise_ivfpq_scan_local — the probes whose list is empty in this slice are
+        dropped first (their number kept goes to probe_count when given) and positions are those of the whole array."""
         lib = _lib.lib()
         nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
-        need = lib.wise_ivfpq_scan_workspace_bytes(n, nprobe, k, self.m)
+        need = (lib.wise_ivfpq_scan_local_workspace_bytes if local else lib.wise_ivfpq_scan_workspace_bytes)(n, nprobe, k, self.m)
         if need == 0:
             raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k} m={self.m}")
         ws = self._workspace(need)
@@ -185,19 +218,39 @@ class IVFPQIPIndex(IVFIndexBase):
                                     bias.data_ptr(), st), "wise_pq_bias")
         lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
         _lib.check(lib.wise_pq_lut(qs.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
-        rc = lib.wise_ivfpq_scan(ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist,
-                                 0 if positions else ls.ids.data_ptr(), lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe,
-                                 k, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        _lib.check(rc, "wise_ivfpq_scan")
+        head = (ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
+                lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
+        tail = (ws.data_ptr(), ws.numel(), st)
+        if local:
+            _lib.check(lib.wise_ivfpq_scan_local(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
+                       "wise_ivfpq_scan_local")
+        else:
+            _lib.check(lib.wise_ivfpq_scan(*head, D.data_ptr(), I.data_ptr(), *tail), "wise_ivfpq_scan")
 
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
+    def _search(self, q: torch.Tensor, k: int, chunk: int, positions: bool = False, local: bool = False,
+                probe_count: Optional[torch.Tensor] = None):
         q = self._queries(q)
         nq = q.shape[0]
+        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
+                                        or not probe_count.is_contiguous()):
+            raise ValueError("search_local_device: probe_count must be a contiguous int32 device tensor of nq entries")
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         for s in range(0, nq, chunk):                    # bounds the tables: chunk * m KiB
-            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk])
+            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], positions, local,
+                       None if probe_count is None else probe_count[s:s + chunk])
         return D, I
+
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
+        return self._search(q, k, chunk)
+
+    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
+                            chunk: int = 1024):
+        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to
+        the slice, `pos_base` its first position; ShardedIVFPQIPIndex): the same coarse stage, bias and tables, then
+        wise_ivfpq_scan_local.  probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query.
+        positions: I receives positions in the WHOLE array instead of external ids."""
+        return self._search(q, k, chunk, positions, True, probe_count)
 
     # -- the rest of the surface the REST layer touches -------------------------------------------
     def _positions(self, ids) -> torch.Tensor:
@@ -273,15 +326,18 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
         return (rows,)
 
     def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, rows: torch.Tensor = None,
-                    scales: torch.Tensor = None) -> "IVFPQRefineIPIndex":
-        """Take codes and compact rows that are already grouped by list (file load)."""
+                    scales: torch.Tensor = None, pos_base: int = 0) -> "IVFPQRefineIPIndex":
+        """Take codes and compact rows that are already grouped by list (file load); pos_base as on IVFPQIPIndex."""
         if codes.dim() != 2 or codes.shape[1] != self.m:
             raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
+        if pos_base < 0:
+            raise ValueError("adopt_lists: pos_base must not be negative")
         if rows is None or tuple(rows.shape) != (codes.shape[0], self.d) or rows.dtype != self._row_dtype:
             raise ValueError(f"adopt_lists: expected rows [{codes.shape[0]},{self.d}] {self._row_dtype}")
         if self.kind == 8 and (scales is None or tuple(scales.shape) != (codes.shape[0],) or scales.dtype != torch.float32):
             raise ValueError(f"adopt_lists: expected scales [{codes.shape[0]}] float32")
         self._lists.adopt(codes, ids, list_off, (rows, scales) if self.kind == 8 else (rows,))
+        self.pos_base = int(pos_base)
         return self
 
     def _store(self):
@@ -312,6 +368,36 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
             self._scan(qs, kc, cD, cand, positions=True)
             _lib.check(lib.wise_ivf_refine(rows, self.kind, scales, ls.n, self.d, ls.ids.data_ptr(), qs.data_ptr(), n, cand.data_ptr(),
                                            kc, k, D[s:s + chunk].data_ptr(), I[s:s + chunk].data_ptr(), st), "wise_ivf_refine")
+        return D, I
+
+    def search_local_device(self, q, k, probe_count=None, positions=False, chunk: int = 1024):
+        raise NotImplementedError("IVFPQRefineIPIndex: a rank's share of a search is two phases, candidates_local_device and "
+                                  "refine_local_device, with an exchange between them (ShardedIVFPQRefineIPIndex)")
+
+    def candidates_local_device(self, q: torch.Tensor, kc: int, probe_count: Optional[torch.Tensor] = None, chunk: int = 1024):
+        """Phase 1 of a sharded search: this slice's kc best rows of the PQ scan as (scores, positions in the WHOLE array)."""
+        if kc < 1 or kc > MAX_CANDIDATES:
+            raise ValueError(f"candidates_local_device: unsupported kc={kc} (1 <= kc <= {MAX_CANDIDATES})")
+        return self._search(q, kc, chunk, True, True, probe_count)
+
+    def refine_local_device(self, q: torch.Tensor, cand: torch.Tensor, k: int):
+        """Phase 2: the candidates cand [nq, kc] (positions in the whole array, the same on every rank) that lie in this slice,
+        scored again from its compact rows; the k best with external ids (wise_ivf_refine_local)."""
+        q = self._queries(q)
+        nq, ls = q.shape[0], self._lists
+        if cand.dim() != 2 or cand.shape[0] != nq or cand.dtype != torch.int64 or cand.shape[1] > MAX_CANDIDATES:
+            raise ValueError(f"refine_local_device: cand must be int64 [{nq}, kc <= {MAX_CANDIDATES}]")
+        if k < 1 or k > MAX_CANDIDATES:
+            raise ValueError(f"refine_local_device: unsupported k={k} (1 <= k <= {MAX_CANDIDATES})")
+        cand = cand.to(self.device).contiguous()
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if ls.n == 0:
+            return D.fill_(-3.4028234663852886e38), I.fill_(-1)
+        rows, scales = self._store()
+        _lib.check(_lib.lib().wise_ivf_refine_local(rows, self.kind, scales, ls.n, self.d, ls.ids.data_ptr(), q.data_ptr(), nq,
+                                                    cand.data_ptr(), cand.shape[1], k, self.pos_base, D.data_ptr(), I.data_ptr(),
+                                                    _lib.stream_ptr()), "wise_ivf_refine_local")
         return D, I
 
     def reconstruct_batch(self, ids) -> np.ndarray:

@@ -11,6 +11,13 @@ its range (a list that straddles a boundary is split, head on the lower rank).  
 the list scan only over the probed lists the rank holds (wise_ivf_scan_local_f32: ~nprobe / W of them), then the same
 exchange and merge.  A rank's rows are in global order and the merge puts the lower rank first on equal scores, so the
 answer has the bits of the one-GPU IVF search over the same centroids and lists, ties included.
+
+ShardedIVFPQIPIndex is that wrapper around a slice of an IndexIVFPQ<m> (codes instead of rows, all codebooks on every rank,
+wise_ivfpq_scan_local): one exchange.  ShardedIVFPQRefineIPIndex (IndexIVFPQ<m>R8 / R16) needs TWO exchanges to return the
+one-GPU answer, because the one-GPU index re-ranks the kc best positions of the WHOLE PQ scan: (1) every rank's kc best
+positions are gathered and merged into those global kc, (2) every rank re-ranks the ones that lie in its slice
+(wise_ivf_refine_local) and the ranks' k best are gathered and merged.  Re-ranking each rank's own kc would save a collective
+and return a different answer (a pool of W * kc).
 """
 from __future__ import annotations
 
@@ -57,8 +64,8 @@ class ShardedFlatIPIndex:
         # injection points exist for the CPU (gloo) tests only; the product path is the HIP one
         self._local_search = local_search or local.search_device
         self._merge = merge or merge_device
-        self._xchg = None
-        self.last_exchange_bytes = 0    # payload this rank contributed to the last all-gather
+        self._xchg = {}
+        self.last_exchange_bytes = 0    # payload this rank contributed to the all-gather(s) of the last search
 
     @property
     def world(self) -> int:
@@ -73,10 +80,18 @@ class ShardedFlatIPIndex:
             dist.all_reduce(n, group=self.group)
         return int(n.item())
 
+    def _exchanges(self) -> bool:
+        return dist.is_initialized() and (self.world > 1 or self.always_exchange)
+
     def search_device(self, q: torch.Tensor, k: int):
         D, I = self._local_search(q, k)
-        if not dist.is_initialized() or (self.world == 1 and not self.always_exchange):
+        if not self._exchanges():
             return D, I
+        self.last_exchange_bytes = 0
+        return self._exchange_merge(D, I, k)
+
+    def _exchange_merge(self, D: torch.Tensor, I: torch.Tensor, k: int):
+        """All-gather of every rank's (D, I) [nq, k] and the merge in rank order; adds to last_exchange_bytes."""
         W = self.world
         nq = D.shape[0]
         # ONE collective per query batch: scores and ids travel as one int64 buffer per rank — plane 0 the fp32 score
@@ -84,16 +99,18 @@ class ShardedFlatIPIndex:
         # latency-bound (at 8 ranks the local scan of a 10M-row index is ~0.2 ms), so the number of collectives is what
         # counts, not their payload.  Buffers are kept between calls.
         key = (nq, k, D.device)
-        if self._xchg is None or self._xchg[0] != key:
-            self._xchg = (key, torch.empty(2, nq, k, dtype=torch.int64, device=D.device),
-                          torch.empty(W, 2, nq, k, dtype=torch.int64, device=D.device))
-        _, send, recv = self._xchg
+        if key not in self._xchg:
+            if len(self._xchg) >= 4:
+                self._xchg.clear()
+            self._xchg[key] = (torch.empty(2, nq, k, dtype=torch.int64, device=D.device),
+                               torch.empty(W, 2, nq, k, dtype=torch.int64, device=D.device))
+        send, recv = self._xchg[key]
         send[0].copy_(D.contiguous().view(torch.int32))        # exact: int32 -> int64 and back keeps the float's bits
         send[1].copy_(I)
         dist.all_gather_into_tensor(recv.view(W * 2 * nq, k), send.view(2 * nq, k), group=self.group)
         Ds = recv[:, 0].to(torch.int32).view(torch.float32)
         Is = recv[:, 1].contiguous()
-        self.last_exchange_bytes = send.numel() * 8
+        self.last_exchange_bytes += send.numel() * 8
         return self._merge(Ds, Is, k)
 
     def search(self, x, k: int):
@@ -164,3 +181,49 @@ class ShardedIVFFlatIPIndex(ShardedFlatIPIndex):
 
     def make_direct_map(self, enable: bool = True) -> None:
         self.local.make_direct_map(enable)
+
+
+class ShardedIVFPQIPIndex(ShardedIVFFlatIPIndex):
+    """Every rank constructs it around its own local IVFPQIPIndex holding a clipped slice of the list-major codes (all
+    centroids and codebooks, ids global, `pos_base` set).  One exchange per search, the flat wrapper's."""
+
+    @property
+    def is_trained(self) -> bool:
+        return self.local.is_trained
+
+    def hbm_bytes(self) -> int:
+        """Of this rank's slice (local, not collective)."""
+        return self.local.hbm_bytes()
+
+
+MAX_MERGE_KEYS = 65536           # wise_topk_merge: parts * k
+
+
+class ShardedIVFPQRefineIPIndex(ShardedIVFPQIPIndex):
+    """Around a local IVFPQRefineIPIndex slice.  Two exchanges per search (module docstring): the candidates, then the
+    re-ranked answers; last_exchange_bytes is the sum, 16 * nq * (candidates(k) + k) bytes per rank."""
+
+    def __init__(self, local, group: Optional[dist.ProcessGroup] = None, merge: Optional[Callable] = None,
+                 always_exchange: bool = False):
+        super().__init__(local, group=group, local_search=local.search_device, merge=merge, always_exchange=always_exchange)
+
+    @property
+    def k_factor(self) -> int:
+        return self.local.k_factor
+
+    @k_factor.setter
+    def k_factor(self, v: int) -> None:
+        self.local.k_factor = int(v)
+
+    def search_device(self, q: torch.Tensor, k: int):
+        if not self._exchanges():
+            return self.local.search_device(q, k)
+        kc = self.local.candidates(k)
+        if self.world * kc > MAX_MERGE_KEYS:
+            raise ValueError(f"ShardedIVFPQRefineIPIndex: {self.world} ranks x {kc} candidates exceed the {MAX_MERGE_KEYS} keys one "
+                             f"merge takes (at most {MAX_MERGE_KEYS // kc} ranks at k = {k}, k_factor = {self.local.k_factor})")
+        self.last_exchange_bytes = 0
+        cD, cP = self.local.candidates_local_device(q, kc)
+        _, cand = self._exchange_merge(cD, cP, kc)                   # the kc positions the one-GPU PQ scan returns
+        D, I = self.local.refine_local_device(q, cand, k)
+        return self._exchange_merge(D, I, k)

@@ -43,6 +43,10 @@ SCHEMAS = {
     "ivf_scan": "(Tensor X, Tensor list_off, Tensor? ids, Tensor Q, Tensor probes, int k) -> (Tensor, Tensor)",
     # the re-ranking stage of IndexIVFPQ<m>R8 / R16 (faiss IndexRefine): rows int8 with scales, or bf16 bit patterns (int16)
     "ivf_refine": "(Tensor rows, Tensor? scales, Tensor? ids, Tensor Q, Tensor cand_pos, int k) -> (Tensor, Tensor)",
+    # the same two stages on one rank's slice of an index sharded across GPUs (wise_amd/index/sharded.py): positions are global
+    "ivfpq_scan_local": "(Tensor codes, Tensor list_off, Tensor? ids, Tensor lut, Tensor probes, Tensor bias, int k, int pos_base) "
+                        "-> (Tensor, Tensor, Tensor)",
+    "ivf_refine_local": "(Tensor rows, Tensor? scales, Tensor? ids, Tensor Q, Tensor cand_pos, int k, int pos_base) -> (Tensor, Tensor)",
     # HP-1 (open_clip encode_image / encode_text, msclap audio_encoder; src/feature/*.py)
     "vit_forward": "(Tensor images, Tensor wb, Tensor pf, int[] config) -> Tensor",
     "text_forward": "(Tensor tokens, Tensor wb, Tensor pf, int[] config) -> Tensor",
@@ -240,28 +244,64 @@ def _ivf_scan(X, list_off, ids, Q, probes, k):
     return D, I
 
 
-def _ivf_refine(rows, scales, ids, Q, cand_pos, k):
+def _ivf_refine(rows, scales, ids, Q, cand_pos, k, pos_base=None):
+    """pos_base None: wise_ivf_refine; an int: wise_ivf_refine_local (cand_pos are positions in the whole array)"""
     lib = _lib.lib()
+    op = "ivf_refine" if pos_base is None else "ivf_refine_local"
     _dev(rows, scales, ids, Q, cand_pos)
     if rows.dim() != 2 or rows.dtype not in (torch.int8, torch.int16) or not rows.is_contiguous():
-        raise ValueError("wise_hip::ivf_refine: rows [N,d] contiguous, int8 (with scales [N]) or int16 (bf16 bit patterns)")
+        raise ValueError(f"wise_hip::{op}: rows [N,d] contiguous, int8 (with scales [N]) or int16 (bf16 bit patterns)")
     kind = 8 if rows.dtype == torch.int8 else 16
     N, d = rows.shape
     if kind == 8:
         if scales is None:
-            raise ValueError("wise_hip::ivf_refine: int8 rows need their scales")
-        _req(scales, torch.float32, "scales", "ivf_refine", N)
-    _req(ids, torch.int64, "ids", "ivf_refine", N)
-    _req(cand_pos, torch.int64, "cand_pos", "ivf_refine")
+            raise ValueError(f"wise_hip::{op}: int8 rows need their scales")
+        _req(scales, torch.float32, "scales", op, N)
+    _req(ids, torch.int64, "ids", op, N)
+    _req(cand_pos, torch.int64, "cand_pos", op)
     Q = _f32c(Q)
     nq, kc = cand_pos.shape
     if Q.shape != (nq, d):
-        raise ValueError(f"wise_hip::ivf_refine: Q must be [{nq},{d}]")
+        raise ValueError(f"wise_hip::{op}: Q must be [{nq},{d}]")
     D = torch.empty(nq, k, dtype=torch.float32, device=rows.device)
     I = torch.empty(nq, k, dtype=torch.int64, device=rows.device)
-    _check(lib.wise_ivf_refine(rows.data_ptr(), kind, _lib.ptr(scales) if kind == 8 else 0, N, d, _lib.ptr(ids), Q.data_ptr(), nq,
-                               cand_pos.data_ptr(), kc, k, D.data_ptr(), I.data_ptr(), _lib.stream_ptr()), "wise_ivf_refine")
+    head = (rows.data_ptr(), kind, _lib.ptr(scales) if kind == 8 else 0, N, d, _lib.ptr(ids), Q.data_ptr(), nq, cand_pos.data_ptr(), kc, k)
+    tail = (D.data_ptr(), I.data_ptr(), _lib.stream_ptr())
+    if pos_base is None:
+        _check(lib.wise_ivf_refine(*head, *tail), "wise_ivf_refine")
+    else:
+        _check(lib.wise_ivf_refine_local(*head, int(pos_base), *tail), "wise_ivf_refine_local")
     return D, I
+
+
+def _ivf_refine_local(rows, scales, ids, Q, cand_pos, k, pos_base):
+    return _ivf_refine(rows, scales, ids, Q, cand_pos, k, int(pos_base))
+
+
+def _ivfpq_scan_local(codes, list_off, ids, lut, probes, bias, k, pos_base):
+    """-> (D, I, probe_count [nq] int32)"""
+    lib = _lib.lib()
+    _dev(codes, list_off, ids, lut, probes, bias)
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise ValueError("wise_hip::ivfpq_scan_local: codes [N,m] contiguous uint8")
+    N, m = codes.shape
+    _req(list_off, torch.int64, "list_off", "ivfpq_scan_local", 2)
+    _req(ids, torch.int64, "ids", "ivfpq_scan_local", N)
+    _req(probes, torch.int64, "probes", "ivfpq_scan_local")
+    nq, nprobe = probes.shape
+    _req(bias, torch.float32, "bias", "ivfpq_scan_local", nq * nprobe)
+    _req(lut, torch.float32, "lut", "ivfpq_scan_local", nq * m * 256)
+    D = torch.empty(nq, k, dtype=torch.float32, device=codes.device)
+    I = torch.empty(nq, k, dtype=torch.int64, device=codes.device)
+    count = torch.empty(nq, dtype=torch.int32, device=codes.device)
+    need = lib.wise_ivfpq_scan_local_workspace_bytes(nq, nprobe, k, m)
+    if need == 0:
+        raise ValueError(f"wise_hip::ivfpq_scan_local: unsupported shape nq={nq} nprobe={nprobe} k={k} m={m}")
+    ws = torch.empty(need, dtype=torch.uint8, device=codes.device)
+    _check(lib.wise_ivfpq_scan_local(codes.data_ptr(), N, m, list_off.data_ptr(), list_off.numel() - 1, _lib.ptr(ids), lut.data_ptr(), nq,
+                                     probes.data_ptr(), bias.data_ptr(), nprobe, k, int(pos_base), D.data_ptr(), I.data_ptr(),
+                                     count.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "wise_ivfpq_scan_local")
+    return D, I, count
 
 
 # ---------------------------------------------------------------------------------------------- HP-1
@@ -385,6 +425,9 @@ _IMPLS = {
     "select_topk": (_select_topk, lambda s, k: s.new_empty((s.shape[0], k), dtype=torch.int64)),
     "ivf_scan": (_ivf_scan, lambda X, lo, ids, Q, probes, k: _fake_pair(Q.shape[0], k, X)),
     "ivf_refine": (_ivf_refine, lambda rows, scales, ids, Q, cand, k: _fake_pair(Q.shape[0], k, rows)),
+    "ivfpq_scan_local": (_ivfpq_scan_local, lambda codes, lo, ids, lut, probes, bias, k, pb:
+                         _fake_pair(probes.shape[0], k, codes) + (codes.new_empty((probes.shape[0],), dtype=torch.int32),)),
+    "ivf_refine_local": (_ivf_refine_local, lambda rows, scales, ids, Q, cand, k, pb: _fake_pair(Q.shape[0], k, rows)),
     "vit_forward": (_vit_forward, lambda im, wb, pf, cfg: im.new_empty((im.shape[0], cfg[6]), dtype=torch.float32)),
     "text_forward": (_text_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[6]), dtype=torch.float32)),
     "xlmr_forward": (_xlmr_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[8]), dtype=torch.float32)),
