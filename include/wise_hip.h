@@ -35,7 +35,8 @@ const char* wise_last_error(void);
  * added within 5: wise_vit_config.ln_fold, the wise_gemm_fold_* entry points, wise_attention_oproj_fold, wise_htsat_forward2,
  * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points,
  * wise_ivfpq_scan, wise_ivf_refine and wise_ivf_refine_rows); also added within 5: wise_ivfpq_scan_local and
- * wise_ivf_refine_local, the last two stages on one rank's slice of an index sharded across GPUs. */
+ * wise_ivf_refine_local, the last two stages on one rank's slice of an index sharded across GPUs; and wise_opq_rotate,
+ * wise_opq_corr (with wise_opq_corr_workspace_bytes) and wise_opq_decode, the learned rotation of IndexIVFOPQ<m>. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -273,6 +274,28 @@ int wise_ivf_refine_rows(const void* rows, int kind, const float* scales, int64_
  * whole store. */
 int wise_ivf_refine_local(const void* rows, int kind, const float* scales, int64_t N, int d, const int64_t* ids, const float* Q, int nq,
                           const int64_t* cand_pos, int kc, int k, int64_t pos_base, float* outD, int64_t* outI, void* stream);
+/* (ABI 5, additive) IndexIVFOPQ<m>: an orthonormal rotation R [d, d] fp32 (row-major) in front of the product quantizer — faiss's
+ * OPQMatrix before IndexIVFPQ.  With r = x - c_l, q . x = q . c_l + (R q) . (R r): rows are encoded from R r (wise_pq_encode) and the
+ * per-query table is built from R q (wise_pq_lut); wise_pq_bias, wise_ivfpq_scan(_local) and wise_ivf_refine(_local) are unchanged.
+ * Limits (WISE_E_UNSUPPORTED otherwise): d % 4 == 0, 4 <= d <= 1024, and where codes are read the wise_pq_* limits on (d, m).
+ * All deterministic: the same inputs give the same bits.
+ *   wise_opq_rotate: out[i, a] = sum_b x[i, b] * R[a, b] — acc = +0, then acc = fmaf(x[i, b], R[a, b], acc) for b = 0 .. d-1, in fp32,
+ *     in that order, so the result depends on nothing but its inputs (not on n, the tiling or the device's load).  x [n, d], out [n, d]
+ *     (must not alias x), all three 16-byte aligned.  Passing the transpose of R applies the inverse rotation.
+ *   wise_opq_corr: M[a, b] = sum_i cw_i[a] * x[i, b] in fp64 (row-major [d, d] on the device), cw_i = concat_j codebooks[j, codes[i, j], :]
+ *     looked up from the m code bytes of row i; x [n, d] fp32 are the UNROTATED rows.  The products are exact in fp64; the sum runs
+ *     over the rows in ascending order inside blocks of 4096 rows (fma from +0), and the blocks' partial sums are then added in
+ *     ascending order.  The SVD M = U S V^T gives the rotation U V^T that best maps x onto the codewords (orthogonal Procrustes).
+ *     Workspace: wise_opq_corr_workspace_bytes(n, d) bytes (0: unsupported shape).
+ *   wise_opq_decode: wise_pq_decode with the rotation undone — out[i, c] = centroids[l, c] + s_c, s_c = sum_a R[a, c] * cw[a] as an
+ *     fmaf chain over a = 0 .. d-1 from +0 in fp32, cw = concat_j cb[j, codes[pos[i], j], :]; a position outside [0, N) gives a row
+ *     of NaN.  IndexIVFOPQ::reconstruct_batch. */
+int wise_opq_rotate(const float* x, const float* R, int64_t n, int d, float* out, void* stream);
+size_t wise_opq_corr_workspace_bytes(int64_t n, int d);
+int wise_opq_corr(const uint8_t* codes, const float* codebooks, const float* x, int64_t n, int d, int m, double* M, void* workspace,
+                  size_t workspace_bytes, void* stream);
+int wise_opq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                    const float* centroids, const float* codebooks, const float* R, int d, int m, float* out, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

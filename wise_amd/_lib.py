@@ -120,6 +120,10 @@ SIGNATURES = {
     "wise_ivf_refine_local": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp]),
     "wise_ivf_refine": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "wise_ivf_refine_rows": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i, _vp, _vp]),
+    "wise_opq_rotate": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "wise_opq_corr_workspace_bytes": (_sz, [_i64, _i]),
+    "wise_opq_corr": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
+    "wise_opq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wise_mlp_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "wise_mlp_stream_ln": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),

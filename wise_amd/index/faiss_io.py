@@ -38,7 +38,15 @@ REPOSITORY'S OWN FORMAT, not a faiss layout (faiss's 8-bit refine stores keep a 
     u64  n_bytes | the compact rows in list order: i8[N*d] (kind 8) or bf16[N*d] (kind 16)
     u64  N | f32[N]                                                           the row scales (kind 8 only)
 
-Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' file
+The file of index types 'IndexIVFOPQ<m>' and 'IndexIVFOPQ<m>R8' / 'R16' (write_ivf_opq_ip / read_ivf_opq_ip) is a wrapper of the same
+kind, again THIS REPOSITORY'S OWN FORMAT (faiss writes an OPQMatrix inside an IndexPreTransform, which rotates the whole vector; this
+rotation acts on the residual, after the coarse stage):
+
+    u32  'WiOP' | u32 version (1) | u32 d
+    f32[d*d]                                      the rotation R, row-major: a residual r is encoded as R r
+    a complete 'IwPQ' record (IndexIVFOPQ<m>) or a complete 'WiPR' record (IndexIVFOPQ<m>R8 / R16)
+
+Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
 
@@ -427,24 +435,29 @@ def read_ivf_pq_refine_ip_range(path, lo: int, hi: int):
     if not p.exists():
         raise _missing(p)
     with open(p, "rb") as f:
-        kind, k_factor = _read_refine_head(f, p)
-        out, n, end = _read_ivf_pq_record_range(f, p, lo, hi)
-        lo, hi, d = int(lo), int(hi), out["centroids"].shape[1]
-        width = d * (1 if kind == 8 else 2)
-        f.seek(end)
-        (nbytes,) = struct.unpack("<Q", f.read(8))
-        if nbytes != n * width:
-            raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
-        f.seek(end + 8 + lo * width)
-        rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=(hi - lo) * d).reshape(hi - lo, d)
-        scales = None
-        if kind == 8:
-            f.seek(end + 8 + n * width)
-            (ns,) = struct.unpack("<Q", f.read(8))
-            if ns != n:
-                raise RuntimeError(f"{p}: {ns} scales for {n} rows")
-            f.seek(end + 8 + n * width + 8 + lo * 4)
-            scales = np.fromfile(f, dtype=np.float32, count=hi - lo)
+        return _read_refine_record_range(f, p, lo, hi)
+
+
+def _read_refine_record_range(f, p, lo: int, hi: int):
+    """read_ivf_pq_refine_ip_range on an open file that stands at a 'WiPR' record"""
+    kind, k_factor = _read_refine_head(f, p)
+    out, n, end = _read_ivf_pq_record_range(f, p, lo, hi)
+    lo, hi, d = int(lo), int(hi), out["centroids"].shape[1]
+    width = d * (1 if kind == 8 else 2)
+    f.seek(end)
+    (nbytes,) = struct.unpack("<Q", f.read(8))
+    if nbytes != n * width:
+        raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
+    f.seek(end + 8 + lo * width)
+    rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=(hi - lo) * d).reshape(hi - lo, d)
+    scales = None
+    if kind == 8:
+        f.seek(end + 8 + n * width)
+        (ns,) = struct.unpack("<Q", f.read(8))
+        if ns != n:
+            raise RuntimeError(f"{p}: {ns} scales for {n} rows")
+        f.seek(end + 8 + n * width + 8 + lo * 4)
+        scales = np.fromfile(f, dtype=np.float32, count=hi - lo)
     out.update(kind=kind, k_factor=k_factor, rows=rows, scales=scales)
     return out
 
@@ -474,16 +487,21 @@ def write_ivf_pq_refine_ip(path, centroids, codebooks, codes, ids, list_off, kin
     rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
     assert d % m == 0 and codebooks.shape == (m, 256, d // m) and rows.shape == (n, d)
     assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    if kind == 8:
+        scales = np.ascontiguousarray(scales, dtype=np.float32)
+        assert scales.shape == (n,)
     with open(path, "wb") as f:
-        f.write(struct.pack("<IIII", _fourcc("WiPR"), 1, kind, k_factor))
-        _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
-        f.write(struct.pack("<Q", rows.nbytes))
-        rows.tofile(f)
-        if kind == 8:
-            scales = np.ascontiguousarray(scales, dtype=np.float32)
-            assert scales.shape == (n,)
-            f.write(struct.pack("<Q", n))
-            scales.tofile(f)
+        _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe)
+
+
+def _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe) -> None:
+    f.write(struct.pack("<IIII", _fourcc("WiPR"), 1, kind, k_factor))
+    _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+    f.write(struct.pack("<Q", rows.nbytes))
+    rows.tofile(f)
+    if kind == 8:
+        f.write(struct.pack("<Q", rows.shape[0]))
+        scales.tofile(f)
 
 
 def read_ivf_pq_refine_ip(path):
@@ -492,24 +510,115 @@ def read_ivf_pq_refine_ip(path):
     if not p.exists():
         raise _missing(p)
     with open(p, "rb") as f:
-        cc, version, kind, k_factor = struct.unpack("<IIII", f.read(16))
-        if cc != _fourcc("WiPR") or version != 1 or kind not in (8, 16) or k_factor < 1:
-            raise RuntimeError(f"{p}: not a re-ranking IndexIVFPQ file (type 0x{cc:08x}, version {version}, kind {kind}, "
-                               f"k_factor {k_factor})")
-        out = _read_ivf_pq_record(f, p)
-        n, d = out["codes"].shape[0], out["centroids"].shape[1]
-        (nbytes,) = struct.unpack("<Q", f.read(8))
-        if nbytes != n * d * (1 if kind == 8 else 2):
-            raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
-        rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=n * d).reshape(n, d)
-        scales = None
-        if kind == 8:
-            (ns,) = struct.unpack("<Q", f.read(8))
-            if ns != n:
-                raise RuntimeError(f"{p}: {ns} scales for {n} rows")
-            scales = np.fromfile(f, dtype=np.float32, count=n)
+        return _read_refine_record(f, p)
+
+
+def _read_refine_record(f, p):
+    """read_ivf_pq_refine_ip on an open file that stands at a 'WiPR' record"""
+    kind, k_factor = _read_refine_head(f, p)
+    out = _read_ivf_pq_record(f, p)
+    n, d = out["codes"].shape[0], out["centroids"].shape[1]
+    (nbytes,) = struct.unpack("<Q", f.read(8))
+    if nbytes != n * d * (1 if kind == 8 else 2):
+        raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
+    rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=n * d).reshape(n, d)
+    scales = None
+    if kind == 8:
+        (ns,) = struct.unpack("<Q", f.read(8))
+        if ns != n:
+            raise RuntimeError(f"{p}: {ns} scales for {n} rows")
+        scales = np.fromfile(f, dtype=np.float32, count=n)
     out.update(kind=int(kind), k_factor=int(k_factor), rows=rows, scales=scales)
     return out
+
+
+# ---------------------------------------------------------------------------------------------- 'WiOP': a rotation + a PQ record
+def write_ivf_opq_ip(path, rotation: np.ndarray, centroids, codebooks, codes, ids, list_off, nprobe: int = 1, kind=None,
+                     k_factor=None, rows=None, scales=None) -> None:
+    """The file of IndexIVFOPQ<m> (kind None: wraps an 'IwPQ' record) and IndexIVFOPQ<m>R8 / R16 (kind 8 / 16 with k_factor, rows
+    and scales as write_ivf_pq_refine_ip takes them: wraps a 'WiPR' record).  rotation [d,d] fp32, row-major.  This repository's own
+    format (module docstring)."""
+    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    rotation = np.ascontiguousarray(rotation, dtype=np.float32)
+    nlist, d = centroids.shape
+    n, m = codes.shape
+    assert rotation.shape == (d, d) and d % m == 0 and codebooks.shape == (m, 256, d // m)
+    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    if kind is not None:
+        assert kind in (8, 16) and k_factor is not None and k_factor >= 1
+        rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
+        assert rows.shape == (n, d)
+        if kind == 8:
+            scales = np.ascontiguousarray(scales, dtype=np.float32)
+            assert scales.shape == (n,)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<III", _fourcc("WiOP"), 1, d))
+        rotation.tofile(f)
+        if kind is None:
+            _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+        else:
+            _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe)
+
+
+def _read_opq_head(f, p):
+    """-> (rotation [d,d], fourcc of the wrapped record); the file then stands at that record"""
+    cc, version, d = struct.unpack("<III", f.read(12))
+    if cc != _fourcc("WiOP") or version != 1 or d < 1 or d > 1 << 16:
+        raise RuntimeError(f"{p}: not an IndexIVFOPQ file (type 0x{cc:08x}, version {version}, d {d})")
+    rotation = np.fromfile(f, dtype=np.float32, count=d * d)
+    if rotation.size != d * d:
+        raise RuntimeError(f"{p}: the rotation of an IndexIVFOPQ file is cut short ({rotation.size} of {d} x {d} values)")
+    here = f.tell()
+    (inner,) = struct.unpack("<I", f.read(4))
+    f.seek(here)
+    if inner not in (_fourcc("IwPQ"), _fourcc("WiPR")):
+        raise RuntimeError(f"{p}: an IndexIVFOPQ file wraps record type 0x{inner:08x}, expected 'IwPQ' or 'WiPR'")
+    return rotation.reshape(d, d), inner
+
+
+def _with_rotation(out, rotation, p):
+    if out["centroids"].shape[1] != rotation.shape[0]:
+        raise RuntimeError(f"{p}: a rotation of d = {rotation.shape[0]} in front of an index of d = {out['centroids'].shape[1]}")
+    out["rotation"] = rotation
+    return out
+
+
+def read_ivf_opq_ip(path):
+    """-> the dict of read_ivf_pq_ip or of read_ivf_pq_refine_ip (the latter has 'kind'), plus rotation [d,d] fp32."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        rotation, inner = _read_opq_head(f, p)
+        return _with_rotation(_read_ivf_pq_record(f, p) if inner == _fourcc("IwPQ") else _read_refine_record(f, p), rotation, p)
+
+
+def ivf_opq_ip_ntotal(path) -> int:
+    """Rows of a 'WiOP' file (the header of its 'IwPQ' record), without reading the lists."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        _, inner = _read_opq_head(f, p)
+        if inner == _fourcc("WiPR"):
+            _read_refine_head(f, p)
+        return _pq_ntotal(f, p)
+
+
+def read_ivf_opq_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major arrays read_ivf_opq_ip returns, as read_ivf_pq_ip_range / read_ivf_pq_refine_ip_range cut them
+    out of the wrapped record; the rotation is whole."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        rotation, inner = _read_opq_head(f, p)
+        out = _read_ivf_pq_record_range(f, p, lo, hi)[0] if inner == _fourcc("IwPQ") else _read_refine_record_range(f, p, lo, hi)
+        return _with_rotation(out, rotation, p)
 
 
 def index_fourcc(path) -> str:

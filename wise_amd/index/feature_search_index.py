@@ -50,6 +50,11 @@ list 1's, ...):
     read rows shard_range(N, r, W) of the single file, so a missing part cannot mix the two sources; `self.index` is a
     `ShardedIVFPQIPIndex` (one exchange per search) or a `ShardedIVFPQRefineIPIndex` (two: candidates, then re-ranked answers),
     both returning the bits of the one-GPU index over the same centroids, codebooks, codes and stores.
+`IndexIVFOPQ<m>` and `IndexIVFOPQ<m>R8` / `R16` are the three IVF+PQ types behind a learned rotation of the residuals (faiss's OPQ;
+ivf_pq.py: IVFOPQIPIndex, IVFOPQRefineIPIndex); their file wraps the PQ record in a 'WiOP' record that carries the rotation
+(faiss_io.py).  They take every path above as their IndexIVFPQ counterparts do: in the collective build rank 0 also trains the
+rotation, which is broadcast with the codebooks; each rank rotates its own rows and, in a search, the query — the rotation is
+replicated, so the sharded classes and their exchanges are the same.
 """
 import os
 from pathlib import Path
@@ -61,7 +66,8 @@ from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
-from .ivf_pq import IVFPQIPIndex, IVFPQRefineIPIndex, check_pq_shape, check_refine_shape
+from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
+                     check_refine_shape)
 from .search_index import SearchIndex
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
                       shard_range)
@@ -77,12 +83,13 @@ def _dist_rank_world():
     return 0, 1, False
 
 
-def parse_ivfpq_type(index_type, feature_dim=None):
+def parse_ivfpq_type(index_type, feature_dim=None, family='IndexIVFPQ'):
     """m of 'IndexIVFPQ<m>' ('IndexIVFPQ64' -> 64; the bare name -> d / 4, the finest code the m <= 128 limit allows at
-    d = 512), None for any other index type.  With feature_dim the shape is checked (ValueError)."""
-    if not index_type.startswith('IndexIVFPQ'):
+    d = 512), None for any other index type.  With feature_dim the shape is checked (ValueError).  family: the name's stem
+    (parse_ivfopq_type reads 'IndexIVFOPQ<m>' through here)."""
+    if not index_type.startswith(family):
         return None
-    tail = index_type[len('IndexIVFPQ'):]
+    tail = index_type[len(family):]
     if tail and not tail.isdigit():
         return None
     if tail:
@@ -92,21 +99,21 @@ def parse_ivfpq_type(index_type, feature_dim=None):
     else:
         m = feature_dim // 4
         if m > 128:
-            raise ValueError(f'IndexIVFPQ: the default m = d / 4 = {m} at d = {feature_dim} exceeds the limit m <= 128; '
-                             f'name the code size, IndexIVFPQ<m> (for example IndexIVFPQ{feature_dim // 8})')
+            raise ValueError(f'{family}: the default m = d / 4 = {m} at d = {feature_dim} exceeds the limit m <= 128; '
+                             f'name the code size, {family}<m> (for example {family}{feature_dim // 8})')
     if feature_dim is not None:
-        check_pq_shape(feature_dim, m)
+        (check_opq_shape if family == 'IndexIVFOPQ' else check_pq_shape)(feature_dim, m)
     return m
 
 
-def parse_ivfpq_refine_type(index_type, feature_dim=None):
+def parse_ivfpq_refine_type(index_type, feature_dim=None, family='IndexIVFPQ'):
     """(m, kind) of 'IndexIVFPQ<m>R<kind>' ('IndexIVFPQ64R8' -> (64, 8); m as parse_ivfpq_type reads it, the bare
     'IndexIVFPQR16' included), None for any other index type.  A kind other than 8 or 16 is a ValueError; with feature_dim
     the shapes of the codes and of the store are checked (ValueError)."""
     head, sep, tail = index_type.rpartition('R')
     if not sep or not tail.isdigit() or not tail.isascii():
         return None
-    m = parse_ivfpq_type(head, feature_dim)
+    m = parse_ivfpq_type(head, feature_dim, family)
     if m is None:
         return None
     kind = int(tail)
@@ -115,6 +122,24 @@ def parse_ivfpq_refine_type(index_type, feature_dim=None):
     if feature_dim is not None:
         check_refine_shape(feature_dim, kind)
     return m, kind
+
+
+def parse_ivfopq_type(index_type, feature_dim=None):
+    """m of 'IndexIVFOPQ<m>' — IndexIVFPQ<m> behind a learned rotation (ivf_pq.py: IVFOPQIPIndex) — read as parse_ivfpq_type reads
+    its names (the bare 'IndexIVFOPQ' -> d / 4 under the same m <= 128 rule); None for any other index type."""
+    return parse_ivfpq_type(index_type, feature_dim, 'IndexIVFOPQ')
+
+
+def parse_ivfopq_refine_type(index_type, feature_dim=None):
+    """(m, kind) of 'IndexIVFOPQ<m>R<kind>', as parse_ivfpq_refine_type; None for any other index type."""
+    return parse_ivfpq_refine_type(index_type, feature_dim, 'IndexIVFOPQ')
+
+
+def _pq_parsers(index_type):
+    """(parse m, parse (m, kind), opq?) for the family index_type belongs to"""
+    if index_type.startswith('IndexIVFOPQ'):
+        return parse_ivfopq_type, parse_ivfopq_refine_type, True
+    return parse_ivfpq_type, parse_ivfpq_refine_type, False
 
 
 def _sharded_ivf_on():
@@ -135,6 +160,8 @@ class FeatureSearchIndex(SearchIndex):
     ivf_index_factory = IVFFlatIPIndex
     ivfpq_index_factory = IVFPQIPIndex
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
+    ivfopq_index_factory = IVFOPQIPIndex
+    ivfopq_refine_index_factory = IVFOPQRefineIPIndex
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -164,8 +191,9 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        refine = parse_ivfpq_refine_type(index_type)
-        is_pq = parse_ivfpq_type(index_type) is not None or refine is not None
+        parse_m, parse_refine, opq = _pq_parsers(index_type)
+        refine = parse_refine(index_type)
+        is_pq = parse_m(index_type) is not None or refine is not None
         sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq) and _sharded_ivf_on()
         if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
@@ -180,8 +208,8 @@ class FeatureSearchIndex(SearchIndex):
             print(f'{index_type} for {self.media_type} already exists')
             return
         if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq:
-            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> are the index types '
-                                      f'WISE builds')
+            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
+                                      f'IndexIVFOPQ<m> forms) are the index types WISE builds')
         self.index_type = index_type
         if sharded and (index_type == 'IndexIVFFlat' or is_pq) and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
@@ -194,9 +222,9 @@ class FeatureSearchIndex(SearchIndex):
         feature_count = feature_store.feature_count
         feature_dim = feature_store.feature_dim
         if refine is not None:                                                    # a bad shape is refused before any row is read
-            pq_m, kind = parse_ivfpq_refine_type(index_type, feature_dim)
+            pq_m, kind = parse_refine(index_type, feature_dim)
         else:
-            pq_m = parse_ivfpq_type(index_type, feature_dim) if is_pq else None
+            pq_m = parse_m(index_type, feature_dim) if is_pq else None
 
         # the on-disk index is assembled on the host (I/O-bound: tar + unpickle per vector), 512 at a time
         X = np.empty((feature_count, feature_dim), dtype=np.float32)
@@ -210,7 +238,7 @@ class FeatureSearchIndex(SearchIndex):
             n += m
         if sharded_ivf:
             self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world, index_type=index_type, pq_m=pq_m,
-                                     kind=kind if refine is not None else None)
+                                     kind=kind if refine is not None else None, opq=opq)
             print(f'  saved index part to {index_fn}')
             return
         if index_type == 'IndexIVFFlat' or is_pq:
@@ -222,13 +250,22 @@ class FeatureSearchIndex(SearchIndex):
             sample.sort()
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
             if refine is not None:
-                ivf = IVFPQRefineIPIndex(feature_dim, cell_count, pq_m, kind)
+                ivf = (IVFOPQRefineIPIndex if opq else IVFPQRefineIPIndex)(feature_dim, cell_count, pq_m, kind)
+            elif opq:
+                ivf = IVFOPQIPIndex(feature_dim, cell_count, pq_m)
             else:
                 ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
             ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
-            if refine is not None:
+            if opq:
+                c, cb, codes, ids_s, off = ivf.lists_host()
+                store = {}
+                if refine is not None:
+                    rows, scales = ivf.store_host()
+                    store = dict(kind=kind, k_factor=ivf.k_factor, rows=rows, scales=scales)
+                faiss_io.write_ivf_opq_ip(index_fn, ivf.rotation.cpu().numpy(), c, cb, codes, ids_s, off, nprobe=ivf.nprobe, **store)
+            elif refine is not None:
                 c, cb, codes, ids_s, off = ivf.lists_host()
                 rows, scales = ivf.store_host()
                 faiss_io.write_ivf_pq_refine_ip(index_fn, c, cb, codes, ids_s, off, kind, ivf.k_factor, rows, scales, nprobe=ivf.nprobe)
@@ -242,10 +279,11 @@ class FeatureSearchIndex(SearchIndex):
             faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
         print(f'  saved index to {index_fn}')
 
-    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None):
+    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None, opq=False):
         """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows.  What travels to the
         rank that owns a row's position is a per-row byte payload: the fp32 row (IndexIVFFlat), or the row's codes followed by its
-        compact row and scale (pq_m / kind given: IndexIVFPQ<m>, IndexIVFPQ<m>R<kind>), encoded where the row was read."""
+        compact row and scale (pq_m / kind given: IndexIVFPQ<m>, IndexIVFPQ<m>R<kind>), encoded where the row was read.  opq: the
+        IndexIVFOPQ forms of the two — rank 0 also trains the rotation, which is broadcast with the codebooks."""
         import torch
         import torch.distributed as dist
 
@@ -265,9 +303,9 @@ class FeatureSearchIndex(SearchIndex):
         bounds = np.searchsorted(sample, src_off)
         mine = sample[bounds[rank]:bounds[rank + 1]] - src_off[rank]
         if kind is not None:
-            ivf = self.ivfpq_refine_index_factory(d, cell_count, pq_m, kind)
+            ivf = (self.ivfopq_refine_index_factory if opq else self.ivfpq_refine_index_factory)(d, cell_count, pq_m, kind)
         elif pq_m is not None:
-            ivf = self.ivfpq_index_factory(d, cell_count, pq_m)
+            ivf = (self.ivfopq_index_factory if opq else self.ivfpq_index_factory)(d, cell_count, pq_m)
         else:
             ivf = self.ivf_index_factory(d, cell_count)
         if rank == 0:                               # k-means once, on rank 0; the centroids' bits go to every rank
@@ -299,6 +337,16 @@ class FeatureSearchIndex(SearchIndex):
             dist.broadcast(cb, src=0)
             codebooks = cb.cpu().numpy()
             ivf.set_codebooks(codebooks)
+        rotation = None
+        if opq:                                     # ... and the rotation's: every rank rotates its own rows and queries
+            if rank == 0:
+                rot = ivf.rotation if torch.is_tensor(ivf.rotation) else torch.from_numpy(np.asarray(ivf.rotation))
+                rot = rot.to(dev, torch.float32).contiguous()
+            else:
+                rot = torch.empty(d, d, dtype=torch.float32, device=dev)
+            dist.broadcast(rot, src=0)
+            rotation = rot.cpu().numpy()
+            ivf.set_rotation(rotation)
         # each rank assigns (and encodes) its own rows; the per-rank list counts fix the global list-major order
         if pq_m is None:
             a = ivf.assign(X)
@@ -350,7 +398,13 @@ class FeatureSearchIndex(SearchIndex):
             loc.append(arr)
             b0 += w
         off_loc = np.clip(list_off - lo, 0, hi - lo)
-        if kind is not None:
+        if opq:
+            store = {}
+            if kind is not None:
+                store = dict(kind=kind, k_factor=ivf.k_factor, rows=loc[1] if kind == 8 else loc[1].view(np.uint16),
+                             scales=loc[2] if kind == 8 else None)
+            faiss_io.write_ivf_opq_ip(part_fn, rotation, centroids, codebooks, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe, **store)
+        elif kind is not None:
             rows = loc[1] if kind == 8 else loc[1].view(np.uint16)
             faiss_io.write_ivf_pq_refine_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, kind, ivf.k_factor, rows,
                                             loc[2] if kind == 8 else None, nprobe=ivf.nprobe)
@@ -378,21 +432,25 @@ class FeatureSearchIndex(SearchIndex):
         nlist, d = f["centroids"].shape
         lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
         always = os.environ.get('WISE_SHARDED_INDEX') == '1'
+        opq = "rotation" in f                       # a 'WiOP' file: the same wrappers around the rotating local classes
         if "kind" in f:
-            local = self.ivfpq_refine_index_factory(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
+            factory = self.ivfopq_refine_index_factory if opq else self.ivfpq_refine_index_factory
+            local = factory(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
             rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
             lists += (rows, None if f["scales"] is None else torch.from_numpy(f["scales"]))
             wrapper = ShardedIVFPQRefineIPIndex
         else:
-            local = self.ivfpq_index_factory(d, nlist, f["codebooks"].shape[0])
+            local = (self.ivfopq_index_factory if opq else self.ivfpq_index_factory)(d, nlist, f["codebooks"].shape[0])
             wrapper = ShardedIVFPQIPIndex
         local.set_centroids(f["centroids"])
         local.set_codebooks(f["codebooks"])
+        if opq:
+            local.set_rotation(f["rotation"])
         local.adopt_lists(*lists, pos_base=int(pos_base))
         local.nprobe = f["nprobe"]
         return wrapper(local, merge=getattr(local, 'merge_lists', None), always_exchange=always)
 
-    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world):
+    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world, opq=False):
         """The sharded load of the IndexIVFPQ family: all ranks read their part files, or all ranks read their range of the
         single file — decided once for the group."""
         import torch
@@ -401,8 +459,12 @@ class FeatureSearchIndex(SearchIndex):
         dev = _coll_device()
         flag = torch.tensor([int(part_fn.exists())], dtype=torch.int64, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        read, read_range, ntotal = ((faiss_io.read_ivf_pq_refine_ip, faiss_io.read_ivf_pq_refine_ip_range, faiss_io.ivf_pq_refine_ip_ntotal)
-                                    if refine else (faiss_io.read_ivf_pq_ip, faiss_io.read_ivf_pq_ip_range, faiss_io.ivf_pq_ip_ntotal))
+        if opq:
+            read, read_range, ntotal = faiss_io.read_ivf_opq_ip, faiss_io.read_ivf_opq_ip_range, faiss_io.ivf_opq_ip_ntotal
+        elif refine:
+            read, read_range, ntotal = faiss_io.read_ivf_pq_refine_ip, faiss_io.read_ivf_pq_refine_ip_range, faiss_io.ivf_pq_refine_ip_ntotal
+        else:
+            read, read_range, ntotal = faiss_io.read_ivf_pq_ip, faiss_io.read_ivf_pq_ip_range, faiss_io.ivf_pq_ip_ntotal
         if bool(flag.item()):
             f = read(part_fn)
             ns = torch.zeros(world, dtype=torch.int64, device=dev)   # a part starts where the lower ranks' parts end
@@ -426,14 +488,31 @@ class FeatureSearchIndex(SearchIndex):
             print(f'  index {index_fn} does not exist')
             print(f'  use create-index.py script to create an index')
         # like the reference (App. B.3) a missing file raises from the reader, it does not return False
-        refine = parse_ivfpq_refine_type(index_type) is not None
-        if sharded and _sharded_ivf_on() and (refine or parse_ivfpq_type(index_type) is not None):
-            index = self._load_sharded_ivfpq(index_fn, part_fn, refine, rank, world)
+        parse_m, parse_refine, opq = _pq_parsers(index_type)
+        refine = parse_refine(index_type) is not None
+        if sharded and _sharded_ivf_on() and (refine or parse_m(index_type) is not None):
+            index = self._load_sharded_ivfpq(index_fn, part_fn, refine, rank, world, opq)
         elif sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip(part_fn))      # built by this many ranks
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'WiOP':
+            import torch                             # unsharded, as 'WiPR' / 'IwPQ' below, plus the rotation
+            f = faiss_io.read_ivf_opq_ip(index_fn)
+            nlist, d = f["centroids"].shape
+            lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            if "kind" in f:
+                index = IVFOPQRefineIPIndex(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
+                lists += (torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16)),
+                          None if f["scales"] is None else torch.from_numpy(f["scales"]))
+            else:
+                index = IVFOPQIPIndex(d, nlist, f["codebooks"].shape[0])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            index.set_rotation(f["rotation"])
+            index.adopt_lists(*lists)
+            index.nprobe = f["nprobe"]
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'WiPR':
             import torch                             # unsharded, as 'IwPQ' below
             f = faiss_io.read_ivf_pq_refine_ip(index_fn)

@@ -22,6 +22,17 @@ built per chunk by wise_ip_shadow_i8 / wise_ip_shadow_bf16 — and a search take
 and scores them again from those rows (wise_ivf_refine, bit-equal to tests/ivfpq_refine_ref.py).  reconstruct_batch returns the
 dequantised stored row.
 
+IVFOPQIPIndex / IVFOPQRefineIPIndex (index types IndexIVFOPQ<m>, IndexIVFOPQ<m>R8 / R16) put a learned orthonormal rotation R
+[d, d] in front of the product quantizer — faiss's OPQMatrix, as in 'OPQ64,IVF65536,PQ64'.  With r = x - c_l,
+q . x = q . c_l + (R q) . (R r), so only three things change: rows are encoded from R r, the per-query table is built from R q
+(both wise_opq_rotate), and the no-store type's reconstruct_batch undoes the rotation (wise_opq_decode: c_l + R^T cw).  The
+coarse stage, the bias, both scans and the re-ranking stage read what they read before.  Training alternates codebooks and
+rotation on the same training residuals: from R = I, opq_niter = 50 times {rotate; fit the codebooks — the first time exactly
+train_codebooks, later opq_niter_pq = 4 Lloyd iterations from where they stand; encode; M = sum_i cw_i x_i^T (wise_opq_corr,
+fp64); R = U V^T from M = U S V^T}, then one more rotation and fit.  THE SVD IS numpy.linalg.svd IN FLOAT64 ON THE HOST, once
+per outer iteration: d x d work (at most 1024 x 1024), not a hot path, and robust when M is rank-deficient.  It is the one
+place in the index code where a LAPACK routine does arithmetic, and it is there by decision.
+
 Across GPUs (sharded.py: ShardedIVFPQIPIndex / ShardedIVFPQRefineIPIndex) an index holds ONE RANK's slice of the list-major
 arrays: all centroids and codebooks, list_off clipped to the slice, and `pos_base`, the position of its first row in the whole
 array.  `search_local_device` is then the rank's share of a search (wise_ivfpq_scan_local: only the probed lists the rank holds),
@@ -162,12 +173,20 @@ class IVFPQIPIndex(IVFIndexBase):
         for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
             xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
             a = self._coarse.assign_device(xs, self.centroids)
-            codes = self._encode(self._residuals(xs, a), self.codebooks)
+            codes = self._encode(self._code_input(xs, a), self.codebooks)
             self._lists.append(codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a, self._extra_rows(xs))
 
     def _extra_rows(self, xs: torch.Tensor) -> tuple:
         """What else the lists keep of a chunk of rows (nothing: the codes are all there is)."""
         return ()
+
+    def _code_input(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        """What the codes of a chunk of rows are encoded from: the residuals (IVFOPQIPIndex: the rotated residuals)."""
+        return self._residuals(xs, assign)
+
+    def _table_queries(self, qs: torch.Tensor) -> torch.Tensor:
+        """What the per-query tables are built from: the queries (IVFOPQIPIndex: the rotated queries)."""
+        return qs
 
     def encode_rows(self, x, chunk: int = 1 << 18):
         """(assign [n] int64, codes [n, m] uint8, extra per-row arrays ...) as numpy for the rows x [n, d]: what add_with_ids
@@ -179,7 +198,7 @@ class IVFPQIPIndex(IVFIndexBase):
         for s in range(0, x.shape[0], chunk):
             xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
             a = self._coarse.assign_device(xs, self.centroids)
-            parts = [t.cpu().numpy() for t in (a, self._encode(self._residuals(xs, a), self.codebooks), *self._extra_rows(xs))]
+            parts = [t.cpu().numpy() for t in (a, self._encode(self._code_input(xs, a), self.codebooks), *self._extra_rows(xs))]
             if out is None:
                 out = [np.empty((x.shape[0],) + t.shape[1:], dtype=t.dtype) for t in parts]
             for o, t in zip(out, parts):
@@ -217,7 +236,8 @@ class IVFPQIPIndex(IVFIndexBase):
         _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
                                     bias.data_ptr(), st), "wise_pq_bias")
         lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_lut(qs.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
+        tq = self._table_queries(qs)
+        _lib.check(lib.wise_pq_lut(tq.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
         head = (ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
                 lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
         tail = (ws.data_ptr(), ws.numel(), st)
@@ -419,3 +439,121 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
             return np.empty((0, self.d), dtype=np.int8 if self.kind == 8 else np.uint16), (np.empty(0, np.float32) if self.kind == 8 else None)
         rows = ex[0].cpu().numpy()
         return (rows, ex[1].cpu().numpy()) if self.kind == 8 else (rows.view(np.uint16), None)
+
+
+MAX_OPQ_D = 1024                 # wise_opq_rotate keeps 32 rows of d floats in LDS
+
+
+def check_opq_shape(d: int, m: int) -> None:
+    """The shapes wise_opq_* serve on top of check_pq_shape (include/wise_hip.h); ValueError otherwise."""
+    check_pq_shape(d, m)
+    if d % 4 or d < 4 or d > MAX_OPQ_D:
+        raise ValueError(f"IVFOPQIPIndex: d={d} must be a multiple of 4 in [4, {MAX_OPQ_D}] (the rotation is d x d)")
+
+
+class _OPQRotation:
+    """What turns an IVFPQ index into its OPQ form: the rotation, its trainer, and the two places it enters — the rows are
+    encoded from R (x - c_l), the per-query tables are built from R q.  Mixed in front of IVFPQIPIndex / IVFPQRefineIPIndex."""
+
+    def _init_rotation(self) -> None:
+        check_opq_shape(self.d, self.m)
+        self.opq_niter = 50          # outer iterations (faiss OPQMatrix.niter)
+        self.opq_niter_pq = 4        # Lloyd iterations per outer iteration after the first (faiss OPQMatrix.niter_pq)
+        self.rotation: Optional[torch.Tensor] = None      # [d, d] fp32, orthonormal: y = R r
+
+    @property
+    def is_trained(self) -> bool:
+        return super().is_trained and self.rotation is not None
+
+    def hbm_bytes(self) -> int:
+        return super().hbm_bytes() + self.rotation.numel() * self.rotation.element_size()
+
+    def set_rotation(self, rotation) -> None:
+        """Install a trained rotation [d, d] (file load, the sharded build's broadcast, tests)."""
+        r = _as_tensor(rotation, np.float32)
+        if tuple(r.shape) != (self.d, self.d):
+            raise ValueError(f"set_rotation: expected [{self.d},{self.d}]")
+        self.rotation = r.to(self.device, torch.float32).contiguous()
+
+    def _rotate(self, x: torch.Tensor, rotation: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [n, d] R^T: row i becomes R x_i (wise_opq_rotate)."""
+        r = self.rotation if rotation is None else rotation
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().wise_opq_rotate(x.data_ptr(), r.data_ptr(), x.shape[0], self.d, out.data_ptr(), _lib.stream_ptr()),
+                   "wise_opq_rotate")
+        return out
+
+    def _code_input(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        return self._rotate(self._residuals(xs, assign))
+
+    def _table_queries(self, qs: torch.Tensor) -> torch.Tensor:
+        return self._rotate(qs)
+
+    def _correlation(self, codes: torch.Tensor, codebooks: torch.Tensor, resid: torch.Tensor) -> np.ndarray:
+        """M = sum_i cw_i x_i^T [d, d] float64 on the host (wise_opq_corr): cw_i the codewords of row i, x_i its unrotated residual."""
+        lib = _lib.lib()
+        n = resid.shape[0]
+        M = torch.empty(self.d, self.d, dtype=torch.float64, device=self.device)
+        ws = self._workspace(lib.wise_opq_corr_workspace_bytes(n, self.d))
+        _lib.check(lib.wise_opq_corr(codes.data_ptr(), codebooks.data_ptr(), resid.data_ptr(), n, self.d, self.m, M.data_ptr(),
+                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr()), "wise_opq_corr")
+        return M.cpu().numpy()
+
+    def train_rotation(self, resid: torch.Tensor):
+        """(rotation [d, d], codebooks [m, 256, dsub]) from the training residuals: from R = I, opq_niter times {rotate, fit the
+        codebooks, encode, M = sum cw x^T, R = U V^T of M's SVD}, then one more rotation and fit.  The first fit is
+        train_codebooks as IVFPQIPIndex runs it (R = I: iteration 0 is plain PQ); the later ones are opq_niter_pq Lloyd
+        iterations from the codebooks they find.  The SVD is numpy's, in float64 on the host."""
+        rot = torch.eye(self.d, dtype=torch.float32, device=self.device)
+        cb = None
+        for t in range(max(int(self.opq_niter), 1)):
+            xr = self._rotate(resid, rot)
+            if cb is None:
+                cb = self.train_codebooks(xr)
+            else:
+                for _ in range(self.opq_niter_pq):
+                    cb = self._update(xr, self._encode(xr, cb), cb)
+            u, _, vt = np.linalg.svd(self._correlation(self._encode(xr, cb), cb, resid))
+            rot = torch.from_numpy(np.ascontiguousarray((u @ vt).astype(np.float32))).to(self.device)
+        xr = self._rotate(resid, rot)
+        for _ in range(self.opq_niter_pq):
+            cb = self._update(xr, self._encode(xr, cb), cb)
+        return rot, cb
+
+    def train(self, x) -> None:
+        x = _rows_f32(x, self.d, "train")
+        if x.shape[0] < KSUB:
+            raise ValueError(f"train: {x.shape[0]} training vectors for {KSUB} codewords")
+        self._coarse.train(x)
+        x = x.to(self.device, torch.float32).contiguous()
+        self.rotation, self.codebooks = self.train_rotation(self.training_residuals(x))
+
+
+class IVFOPQIPIndex(_OPQRotation, IVFPQIPIndex):
+    """IVFPQIPIndex behind a learned rotation (index types IndexIVFOPQ<m>; module docstring)."""
+
+    def __init__(self, d: int, nlist: int, m: int, nbits: int = 8, device: str = "cuda"):
+        check_opq_shape(int(d), int(m))
+        super().__init__(d, nlist, m, nbits, device)
+        self._init_rotation()
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """Decoded rows with the rotation undone: c_l + R^T concat_j cb[j][code_j]; NaN for an unknown id."""
+        lib = _lib.lib()
+        pos = self._positions(ids)
+        st, ls = _lib.stream_ptr(), self._lists
+        out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_opq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
+                                       self.centroids.data_ptr(), self.codebooks.data_ptr(), self.rotation.data_ptr(), self.d, self.m,
+                                       out.data_ptr(), st), "wise_opq_decode")
+        return out.cpu().numpy()
+
+
+class IVFOPQRefineIPIndex(_OPQRotation, IVFPQRefineIPIndex):
+    """IVFPQRefineIPIndex behind a learned rotation (index types IndexIVFOPQ<m>R8 / R16): the codes come from the rotated
+    residuals, the compact rows and the re-ranking stage from the rows and queries as they are."""
+
+    def __init__(self, d: int, nlist: int, m: int, kind: int, k_factor: int = DEFAULT_K_FACTOR, device: str = "cuda"):
+        check_opq_shape(int(d), int(m))
+        super().__init__(d, nlist, m, kind, k_factor, device)
+        self._init_rotation()

@@ -47,6 +47,9 @@ SCHEMAS = {
     "ivfpq_scan_local": "(Tensor codes, Tensor list_off, Tensor? ids, Tensor lut, Tensor probes, Tensor bias, int k, int pos_base) "
                         "-> (Tensor, Tensor, Tensor)",
     "ivf_refine_local": "(Tensor rows, Tensor? scales, Tensor? ids, Tensor Q, Tensor cand_pos, int k, int pos_base) -> (Tensor, Tensor)",
+    # IndexIVFOPQ<m> (faiss OPQMatrix before IndexIVFPQ): the rotation of rows / queries, and the matrix its trainer factorises
+    "opq_rotate": "(Tensor x, Tensor R) -> Tensor",
+    "opq_corr": "(Tensor codes, Tensor codebooks, Tensor x) -> Tensor",
     # HP-1 (open_clip encode_image / encode_text, msclap audio_encoder; src/feature/*.py)
     "vit_forward": "(Tensor images, Tensor wb, Tensor pf, int[] config) -> Tensor",
     "text_forward": "(Tensor tokens, Tensor wb, Tensor pf, int[] config) -> Tensor",
@@ -304,6 +307,39 @@ def _ivfpq_scan_local(codes, list_off, ids, lut, probes, bias, k, pos_base):
     return D, I, count
 
 
+def _opq_rotate(x, R):
+    """out[i, :] = R x[i, :] (wise_opq_rotate: index-ordered fmaf chains)"""
+    lib = _lib.lib()
+    _dev(x, R)
+    x, R = _f32c(x), _f32c(R)
+    if x.dim() != 2 or R.shape != (x.shape[1], x.shape[1]):
+        raise ValueError("wise_hip::opq_rotate: x [n,d], R [d,d]")
+    out = torch.empty_like(x)
+    _check(lib.wise_opq_rotate(x.data_ptr(), R.data_ptr(), x.shape[0], x.shape[1], out.data_ptr(), _lib.stream_ptr()), "wise_opq_rotate")
+    return out
+
+
+def _opq_corr(codes, codebooks, x):
+    """-> M [d,d] float64 = sum_i cw_i x_i^T (wise_opq_corr)"""
+    lib = _lib.lib()
+    _dev(codes, codebooks, x)
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise ValueError("wise_hip::opq_corr: codes [n,m] contiguous uint8")
+    n, m = codes.shape
+    x, codebooks = _f32c(x), _f32c(codebooks)
+    if x.dim() != 2 or x.shape[0] != n or codebooks.numel() != 256 * x.shape[1] or codebooks.shape[0] != m:
+        raise ValueError("wise_hip::opq_corr: x [n,d], codebooks [m,256,d/m]")
+    d = x.shape[1]
+    need = lib.wise_opq_corr_workspace_bytes(n, d)
+    if need == 0:
+        raise ValueError(f"wise_hip::opq_corr: unsupported shape n={n} d={d}")
+    ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+    M = torch.empty(d, d, dtype=torch.float64, device=x.device)
+    _check(lib.wise_opq_corr(codes.data_ptr(), codebooks.data_ptr(), x.data_ptr(), n, d, m, M.data_ptr(), ws.data_ptr(), ws.numel(),
+                             _lib.stream_ptr()), "wise_opq_corr")
+    return M
+
+
 # ---------------------------------------------------------------------------------------------- HP-1
 def _vit_forward(images, wb, pf, config: List[int]):
     lib = _lib.lib()
@@ -428,6 +464,8 @@ _IMPLS = {
     "ivfpq_scan_local": (_ivfpq_scan_local, lambda codes, lo, ids, lut, probes, bias, k, pb:
                          _fake_pair(probes.shape[0], k, codes) + (codes.new_empty((probes.shape[0],), dtype=torch.int32),)),
     "ivf_refine_local": (_ivf_refine_local, lambda rows, scales, ids, Q, cand, k, pb: _fake_pair(Q.shape[0], k, rows)),
+    "opq_rotate": (_opq_rotate, lambda x, R: x.new_empty(x.shape, dtype=torch.float32)),
+    "opq_corr": (_opq_corr, lambda codes, cb, x: x.new_empty((x.shape[1], x.shape[1]), dtype=torch.float64)),
     "vit_forward": (_vit_forward, lambda im, wb, pf, cfg: im.new_empty((im.shape[0], cfg[6]), dtype=torch.float32)),
     "text_forward": (_text_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[6]), dtype=torch.float32)),
     "xlmr_forward": (_xlmr_forward, lambda t, wb, pf, cfg: t.new_empty((t.shape[0], cfg[8]), dtype=torch.float32)),
