@@ -36,7 +36,9 @@ const char* wise_last_error(void);
  * wise_mlp_stream, wise_mlp_stream_ln, wise_swin_qkv_attn, the wise_ivf_* build entry points, wise_ivf_scan_local_*, the wise_pq_* entry points,
  * wise_ivfpq_scan, wise_ivf_refine and wise_ivf_refine_rows); also added within 5: wise_ivfpq_scan_local and
  * wise_ivf_refine_local, the last two stages on one rank's slice of an index sharded across GPUs; and wise_opq_rotate,
- * wise_opq_corr (with wise_opq_corr_workspace_bytes) and wise_opq_decode, the learned rotation of IndexIVFOPQ<m>. */
+ * wise_opq_corr (with wise_opq_corr_workspace_bytes) and wise_opq_decode, the learned rotation of IndexIVFOPQ<m>; and
+ * wise_sel_bitmap, wise_sel_positions (with wise_sel_positions_workspace_bytes), wise_ip_topk_pos_f32, wise_ivf_scan_sel_f32 and
+ * wise_ivfpq_scan_sel, the searches restricted to a set of ids. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -296,6 +298,45 @@ int wise_opq_corr(const uint8_t* codes, const float* codebooks, const float* x, 
                   size_t workspace_bytes, void* stream);
 int wise_opq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
                     const float* centroids, const float* codebooks, const float* R, int d, int m, float* out, void* stream);
+
+/* (ABI 5, additive) Search restricted to a set of ids — faiss's SearchParameters(sel = IDSelectorBatch / IDSelectorRange /
+ * IDSelectorNot).  The set is resolved per index into a bitmap over row POSITIONS (rows of X; rows in list order for the
+ * inverted-file indexes) and tested inside the scans, so a selective filter still returns k hits where k selected rows exist;
+ * the entry points above are untouched and a search without a selector runs the kernels it ran before.
+ *   wise_sel_bitmap: bit (p & 31) of bitmap[p >> 5] = 1 iff the external id of row p — ids[p], or id_base + p with ids == NULL —
+ *     is selected.  mode 0: the id occurs in sel_ids [n_sel] int64, SORTED ASCENDING AND WITHOUT DUPLICATES (binary search; ids
+ *     that no row carries select nothing; n_sel = 0 selects nothing); mode 1: imin <= id < imax.  invert != 0 complements the
+ *     answer within the index.  bitmap has (N + 31) / 32 words, all written; the bits past N are zero, also when inverted.  One
+ *     lane per row, a wave's 64 answers written by one lane from a ballot: no atomics, the same bits run after run.
+ *   wise_sel_positions: pos[0 .. count) = the set positions of bitmap in ascending order, count[0] (device int64) their number
+ *     (per-block popcount, scan, scatter: deterministic).  At most `capacity` entries of pos are written — capacity = N always
+ *     suffices; count reports the full number either way.  Workspace: wise_sel_positions_workspace_bytes(N) bytes.
+ *   wise_ip_topk_pos_f32: the fp32 scan of wise_ip_topk_f32 over the rows X[pos[i]], i < n_pos, in place of X[i] (pos ascending,
+ *     entries in [0, N): what wise_sel_positions writes).  Always the single-pass VALU scan, whatever nq: every score is an fp32
+ *     fmaf chain.  A selected row is one contiguous 4 d-byte burst, so the scan reads n_pos * d * 4 bytes.  Keys carry pos[i]:
+ *     ties (the lower position wins), the id translation and the (-3.4028235e38, -1) padding are wise_ip_topk_f32's; n_pos == 0
+ *     gives all padding.  Limits as wise_ip_topk_f32.  Workspace: wise_ip_topk_workspace_bytes(n_pos, d, nq, k) bytes.
+ *   wise_ivf_scan_sel_f32: wise_ivf_scan_f32 in which only the rows whose bit of keep is set compete (same probes, same
+ *     arithmetic, same ties and padding; fewer than k selected rows in the probed lists give padded slots).  A group of rows
+ *     without a set bit is not loaded.  keep: (N + 31) / 32 words.  Workspace: wise_ivf_scan_workspace_bytes.
+ *   wise_ivfpq_scan_sel: wise_ivfpq_scan under the same filter; the score of a selected row is the contract's — acc = bias, then
+ *     acc += lut[q, j, code_j] for j ascending, in fp32 — bit for bit the unfiltered scan's score of that row, and with every bit
+ *     set the output is wise_ivfpq_scan's.  With ids == NULL outI holds positions (the candidates wise_ivf_refine takes).
+ *     Limits and ties as wise_ivfpq_scan.  Workspace: wise_ivfpq_scan_workspace_bytes. */
+int wise_sel_bitmap(const int64_t* ids, int64_t id_base, int64_t N, int mode, const int64_t* sel_ids, int64_t n_sel, int64_t imin,
+                    int64_t imax, int invert, uint32_t* bitmap, void* stream);
+size_t wise_sel_positions_workspace_bytes(int64_t N);
+int wise_sel_positions(const uint32_t* bitmap, int64_t N, int64_t* pos, int64_t capacity, int64_t* count, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int wise_ip_topk_pos_f32(const float* X, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq, int k,
+                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int wise_ivf_scan_sel_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                          int nq, const int64_t* probes, int nprobe, int k, const uint32_t* keep, float* outD, int64_t* outI,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfpq_scan_sel(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                        const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, const uint32_t* keep,
+                        float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

@@ -117,6 +117,12 @@ SIGNATURES = {
     "wise_ivfpq_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfpq_scan_local_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "wise_ivfpq_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_sel_bitmap": (_i, [_vp, _i64, _i64, _i, _vp, _i64, _i64, _i64, _i, _vp, _vp]),
+    "wise_sel_positions_workspace_bytes": (_sz, [_i64]),
+    "wise_sel_positions": (_i, [_vp, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "wise_ip_topk_pos_f32": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivf_scan_sel_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfpq_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivf_refine_local": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp]),
     "wise_ivf_refine": (_i, [_vp, _i, _vp, _i64, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "wise_ivf_refine_rows": (_i, [_vp, _i, _vp, _i64, _i, _vp, _i, _vp, _vp]),

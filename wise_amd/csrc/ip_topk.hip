@@ -27,15 +27,22 @@ namespace wise {
 // With `count` (wise_ivf_scan_local_f32) only the first count[q] probes of query q are live: the grid is then taken
 // probe-major (block b: probe b / nq of query b % nq), a block past its query's count returns before it touches LDS or
 // part, and the merge folds count[q] lists.
+// SEL = true restricts either form to a set of rows (IDSelector: csrc/ivf_select.hip builds both descriptions of the set).
+// The flat form (wise_ip_topk_pos_f32) scans the rows X[pos[i]], i < N, instead of X[i]: pos is ascending and a key carries
+// pos[i], so ties, the merge and the id translation are the unfiltered scan's.  The inverted-list form
+// (wise_ivf_scan_sel_f32) tests bit `row` of keep before a row is offered, and a wave whose R rows are all clear skips
+// their loads (a ballot: the branch is wave-uniform).  With SEL = false neither field is read.
 struct SegArgs {
     const long long* probes;    // [nq][nprobe] list numbers, < 0 = nothing to scan
     const long long* list_off;  // [nlist + 1]
     int nprobe, nq;
     const int* gate;            // optional: the launch does nothing unless *gate != 0 (two-stage search fallback)
     const int* count;           // optional [nq]: live probes per query (the rest of the row is not read)
+    const unsigned* keep;       // SEL, inverted-list form: bit (row & 31) of keep[row >> 5] set = the row competes
+    const long long* pos;       // SEL, flat form: [N] ascending rows of X to scan
 };
 
-template <int NV, int NQ, int R, bool SEG = false>
+template <int NV, int NQ, int R, bool SEG = false, bool SEL = false>
 __global__ __launch_bounds__(256) void ip_scan_kernel(const f32x4* __restrict__ X, long long N, int d4,
                                                       const float* __restrict__ Q, int k, int cap,
                                                       u64* __restrict__ part /*[grid][NQ][k]*/, SegArgs seg) {
@@ -96,11 +103,18 @@ __global__ __launch_bounds__(256) void ip_scan_kernel(const f32x4* __restrict__ 
 
     for (long long g = gw; g < ngroups; g += nw) {
         const long long row0 = lo + g * R;
+        bool chosen = true;
+        if constexpr (SEL && SEG) {
+            const long long r = row0 + myr;
+            chosen = r < N && ((seg.keep[r >> 5] >> (r & 31)) & 1u) != 0;
+            if (__ballot(chosen) == 0) continue;   // none of the R rows is selected: nothing to load (wave-uniform)
+        }
         f32x4 x[R][NV];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             long long row = row0 + r;
             if (row >= N) row = N - 1;  // stay in bounds; masked below
+            if constexpr (SEL && !SEG) row = seg.pos[row];   // the selected row: still one contiguous 4 d-byte burst
 #pragma unroll
             for (int v = 0; v < NV; ++v) {
                 int c = v * 64 + lane;
@@ -144,8 +158,10 @@ __global__ __launch_bounds__(256) void ip_scan_kernel(const f32x4* __restrict__ 
             for (int m = (32 >> LOGR); m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
 
             const long long row = row0 + myr;
-            const u64 key = make_key(s, (unsigned)row);
-            const bool pass = owner && (row < N) && (key > wl[q].tau);
+            long long krow = row;                  // what the key carries: the row's true position in X
+            if constexpr (SEL && !SEG) krow = seg.pos[row < N ? row : N - 1];
+            const u64 key = make_key(s, (unsigned)krow);
+            const bool pass = owner && (row < N) && (key > wl[q].tau) && chosen;
             wl[q].offer(pass, key, lane, R);
         }
     }
@@ -1570,9 +1586,19 @@ static ScanPlan plan_scan(long long N, int d, int nq, int k) {
 
 template <int NV, int NQ>
 static void launch_scan(const ScanPlan& p, const float* X, long long N, int d, const float* Q, int k, u64* part,
-                        hipStream_t st, const int* gate = nullptr) {
+                        hipStream_t st, const int* gate = nullptr, const long long* pos = nullptr) {
     SegArgs sa{};
     sa.gate = gate;
+    if (pos) {
+        // wise_ip_topk_pos_f32: N counts the entries of pos; always groups of 4 rows
+        sa.pos = pos;
+        auto kern = ip_scan_kernel<NV, NQ, 4, false, true>;
+        if (p.lds > 48 * 1024)
+            raise_lds_limit(reinterpret_cast<const void*>(kern), (int)p.lds);
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, reinterpret_cast<const f32x4*>(X), N, d / 4, Q, k,
+                           p.cap, part, sa);
+        return;
+    }
     if constexpr (NQ == 1 && NV <= 2) {
         if (p.rows == 8) {
             hipLaunchKernelGGL((ip_scan_kernel<NV, NQ, 8>), dim3(p.grid), dim3(256), p.lds, st,
@@ -1590,7 +1616,7 @@ static void launch_scan(const ScanPlan& p, const float* X, long long N, int d, c
 template <int NV>
 static void launch_seg_scan(const float* X, int d, const float* Q, int k, int cap, u64* part, const SegArgs& seg,
                             hipStream_t st) {
-    auto kern = ip_scan_kernel<NV, 1, 4, true>;
+    auto kern = seg.keep ? ip_scan_kernel<NV, 1, 4, true, true> : ip_scan_kernel<NV, 1, 4, true>;
     const size_t lds = (size_t)4 * cap * 8;
     if (lds > 48 * 1024)
         raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
@@ -1600,14 +1626,14 @@ static void launch_seg_scan(const float* X, int d, const float* Q, int k, int ca
 
 template <int NV>
 static int dispatch_nq(const ScanPlan& p, const float* X, long long N, int d, const float* Q, int k, u64* part,
-                       hipStream_t st) {
+                       hipStream_t st, const long long* pos = nullptr) {
     switch (p.nq_per_pass) {
-        case 1: launch_scan<NV, 1>(p, X, N, d, Q, k, part, st); return 0;
+        case 1: launch_scan<NV, 1>(p, X, N, d, Q, k, part, st, nullptr, pos); return 0;
         case 2:
-            if constexpr (NV * 2 <= 8) { launch_scan<NV, 2>(p, X, N, d, Q, k, part, st); return 0; }
+            if constexpr (NV * 2 <= 8) { launch_scan<NV, 2>(p, X, N, d, Q, k, part, st, nullptr, pos); return 0; }
             break;
         case 4:
-            if constexpr (NV * 4 <= 8) { launch_scan<NV, 4>(p, X, N, d, Q, k, part, st); return 0; }
+            if constexpr (NV * 4 <= 8) { launch_scan<NV, 4>(p, X, N, d, Q, k, part, st, nullptr, pos); return 0; }
             break;
     }
     return WISE_E_INVALID;
@@ -1633,6 +1659,61 @@ extern "C" int wise_debug_set_scan(int rows, int blocks_per_cu) {
     return 0;
 }
 #endif
+
+// The single-pass VALU scan and its merge, up to 4 queries per pass: the fp32 path of wise_ip_topk_f32 and, with pos (N
+// then counts its entries), all of wise_ip_topk_pos_f32.  workspace: keys [grid][nq_per_pass][k], then a padded query block.
+static int valu_topk(const float* X, long long N, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base,
+                     float* outD, int64_t* outI, void* workspace, hipStream_t st, const long long* pos = nullptr) {
+    ScanPlan p = plan_scan(N, d, nq, k);
+    u64* part = reinterpret_cast<u64*>(workspace);
+    float* qpad = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) +
+                                           align_up((size_t)p.grid * p.nq_per_pass * k * sizeof(u64), 256));
+    const int nv = (d / 4 + 63) / 64;
+    // merge geometry
+    int mw = 8192 / p.cap;
+    if (mw < 1) mw = 1;
+    if (mw > 16) mw = 16;
+    const size_t mlds = (size_t)mw * p.cap * 8;
+
+    for (int q0 = 0; q0 < nq; q0 += p.nq_per_pass) {
+        const int nqa = (nq - q0 < p.nq_per_pass) ? nq - q0 : p.nq_per_pass;
+        const float* qptr = Q + (size_t)q0 * d;
+        if (nqa < p.nq_per_pass) {
+            // ragged tail: replicate the last query so the kernel shape stays fixed (results ignored)
+            for (int j = 0; j < p.nq_per_pass; ++j) {
+                int srcq = q0 + (j < nqa ? j : nqa - 1);
+                hipError_t e = hipMemcpyAsync(qpad + (size_t)j * d, Q + (size_t)srcq * d, (size_t)d * sizeof(float),
+                                              hipMemcpyDeviceToDevice, st);
+                if (e != hipSuccess) { set_error("ip_topk: memcpy: %s", hipGetErrorString(e)); return (int)e; }
+            }
+            qptr = qpad;
+        }
+        if (N > 0) {
+            int rc = 0;
+            ProfScope prof(PROF_SCAN, (double)N * d * 4.0, st);
+            switch (nv) {
+                case 1: rc = dispatch_nq<1>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 2: rc = dispatch_nq<2>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 3: rc = dispatch_nq<3>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 4: rc = dispatch_nq<4>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 5: rc = dispatch_nq<5>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 6: rc = dispatch_nq<6>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 7: rc = dispatch_nq<7>(p, X, N, d, qptr, k, part, st, pos); break;
+                case 8: rc = dispatch_nq<8>(p, X, N, d, qptr, k, part, st, pos); break;
+                default: rc = WISE_E_INVALID;
+            }
+            if (rc) { set_error("ip_topk: no kernel for d=%d", d); return rc; }
+            WISE_LAUNCH_CHECK("ip_scan_kernel");
+        }
+        if (mlds > 48 * 1024)
+            raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
+        hipLaunchKernelGGL(merge_keys_kernel, dim3(nqa), dim3(mw * 64), mlds, st, part, N > 0 ? p.grid : 0,
+                           p.nq_per_pass, k, p.cap, reinterpret_cast<const long long*>(ids), (long long)id_base, outD,
+                           reinterpret_cast<long long*>(outI), q0);
+        WISE_LAUNCH_CHECK("merge_keys_kernel");
+    }
+    return WISE_OK;
+}
 
 extern "C" size_t wise_ip_topk_workspace_bytes(int64_t N, int d, int nq, int k) {
     if (N < 0 || d < 4 || nq < 1 || k < 1 || k > 2048) return 0;
@@ -1740,55 +1821,27 @@ extern "C" int wise_ip_topk_f32(const float* X, int64_t N, int d, const float* Q
         }
         return WISE_OK;
     }
-    ScanPlan p = plan_scan(N, d, nq, k);
-    u64* part = reinterpret_cast<u64*>(workspace);
-    float* qpad = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) +
-                                           align_up((size_t)p.grid * p.nq_per_pass * k * sizeof(u64), 256));
-    const int nv = (d / 4 + 63) / 64;
-    // merge geometry
-    int mw = 8192 / p.cap;
-    if (mw < 1) mw = 1;
-    if (mw > 16) mw = 16;
-    const size_t mlds = (size_t)mw * p.cap * 8;
+    return valu_topk(X, N, d, Q, nq, k, ids, id_base, outD, outI, workspace, st);
+}
 
-    for (int q0 = 0; q0 < nq; q0 += p.nq_per_pass) {
-        const int nqa = (nq - q0 < p.nq_per_pass) ? nq - q0 : p.nq_per_pass;
-        const float* qptr = Q + (size_t)q0 * d;
-        if (nqa < p.nq_per_pass) {
-            // ragged tail: replicate the last query so the kernel shape stays fixed (results ignored)
-            for (int j = 0; j < p.nq_per_pass; ++j) {
-                int srcq = q0 + (j < nqa ? j : nqa - 1);
-                hipError_t e = hipMemcpyAsync(qpad + (size_t)j * d, Q + (size_t)srcq * d, (size_t)d * sizeof(float),
-                                              hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) { set_error("ip_topk: memcpy: %s", hipGetErrorString(e)); return (int)e; }
-            }
-            qptr = qpad;
-        }
-        if (N > 0) {
-            int rc = 0;
-            ProfScope prof(PROF_SCAN, (double)N * d * 4.0, st);
-            switch (nv) {
-                case 1: rc = dispatch_nq<1>(p, X, N, d, qptr, k, part, st); break;
-                case 2: rc = dispatch_nq<2>(p, X, N, d, qptr, k, part, st); break;
-                case 3: rc = dispatch_nq<3>(p, X, N, d, qptr, k, part, st); break;
-                case 4: rc = dispatch_nq<4>(p, X, N, d, qptr, k, part, st); break;
-                case 5: rc = dispatch_nq<5>(p, X, N, d, qptr, k, part, st); break;
-                case 6: rc = dispatch_nq<6>(p, X, N, d, qptr, k, part, st); break;
-                case 7: rc = dispatch_nq<7>(p, X, N, d, qptr, k, part, st); break;
-                case 8: rc = dispatch_nq<8>(p, X, N, d, qptr, k, part, st); break;
-                default: rc = WISE_E_INVALID;
-            }
-            if (rc) { set_error("ip_topk: no kernel for d=%d", d); return rc; }
-            WISE_LAUNCH_CHECK("ip_scan_kernel");
-        }
-        if (mlds > 48 * 1024)
-            raise_lds_limit(reinterpret_cast<const void*>(merge_keys_kernel), (int)mlds);
-        hipLaunchKernelGGL(merge_keys_kernel, dim3(nqa), dim3(mw * 64), mlds, st, part, N > 0 ? p.grid : 0,
-                           p.nq_per_pass, k, p.cap, reinterpret_cast<const long long*>(ids), (long long)id_base, outD,
-                           reinterpret_cast<long long*>(outI), q0);
-        WISE_LAUNCH_CHECK("merge_keys_kernel");
+// wise_ip_topk_f32's fp32 scan over the rows X[pos[i]] (an IDSelector resolved to positions: csrc/ivf_select.hip)
+extern "C" int wise_ip_topk_pos_f32(const float* X, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq,
+                                    int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "ip_topk_pos: d=%d must be a multiple of 4 in [4,2048]", d);
+    WISE_CHECK_ARG(k >= 1 && k <= 2048, "ip_topk_pos: k=%d out of [1,2048]", k);
+    WISE_CHECK_ARG(nq >= 1 && nq <= 1024, "ip_topk_pos: nq=%d out of [1,1024]", nq);
+    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && n_pos >= 0 && n_pos <= N, "ip_topk_pos: N=%lld n_pos=%lld out of range",
+                   (long long)N, (long long)n_pos);
+    WISE_CHECK_ARG(Q && outD && outI && ((X && pos) || n_pos == 0), "ip_topk_pos: null pointer");
+    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "ip_topk_pos: X and Q must be 16-byte aligned");
+    const size_t need = wise_ip_topk_workspace_bytes(n_pos, d, nq, k);
+    if (!workspace || workspace_bytes < need) {
+        set_error("ip_topk_pos: workspace %zu < %zu bytes", workspace_bytes, need);
+        return WISE_E_WORKSPACE;
     }
-    return WISE_OK;
+    return valu_topk(X, n_pos, d, Q, nq, k, ids, id_base, outD, outI, workspace, (hipStream_t)stream,
+                     reinterpret_cast<const long long*>(pos));
 }
 
 // the last step of the list scans (wise_ivf_scan_f32, wise_ivfpq_scan): part [P][nq][k] keys -> outD/outI [nq][k]
@@ -1829,7 +1882,7 @@ extern "C" size_t wise_ivf_scan_local_workspace_bytes(int nq, int nprobe, int k)
 static int ivf_scan_impl(const char* what, const float* X, int64_t N, int d, const int64_t* list_off, int nlist,
                          const int64_t* ids, const float* Q, int nq, const int64_t* probes, int nprobe, int k, float* outD,
                          int64_t* outI, bool local, int32_t* probe_count, void* workspace, size_t workspace_bytes,
-                         void* stream) {
+                         void* stream, const uint32_t* keep = nullptr) {
     WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "%s: d=%d must be a multiple of 4 in [4,2048]", what, d);
     WISE_CHECK_ARG(k >= 1 && k <= 2048, "%s: k=%d out of [1,2048]", what, k);
     WISE_CHECK_ARG(nq >= 1 && nprobe >= 1 && (!local || nprobe <= 2048) && nlist >= 1 && (long long)nq * nprobe < (1ll << 31),
@@ -1846,6 +1899,7 @@ static int ivf_scan_impl(const char* what, const float* X, int64_t N, int d, con
     unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
     u64* part = reinterpret_cast<u64*>(wsb);
     SegArgs seg = {reinterpret_cast<const long long*>(probes), reinterpret_cast<const long long*>(list_off), nprobe, nq};
+    seg.keep = keep;
     if (local) {
         long long* live = reinterpret_cast<long long*>(wsb + ivf_part_bytes(nq, nprobe, k));
         int* count = probe_count ? probe_count
@@ -1877,6 +1931,14 @@ extern "C" int wise_ivf_scan_f32(const float* X, int64_t N, int d, const int64_t
                                  float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
     return ivf_scan_impl("ivf_scan", X, N, d, list_off, nlist, ids, Q, nq, probes, nprobe, k, outD, outI, false, nullptr,
                          workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivf_scan_sel_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* Q, int nq, const int64_t* probes, int nprobe, int k, const uint32_t* keep,
+                                     float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    WISE_CHECK_ARG(keep || N == 0, "ivf_scan_sel: null bitmap");
+    return ivf_scan_impl("ivf_scan_sel", X, N, d, list_off, nlist, ids, Q, nq, probes, nprobe, k, outD, outI, false, nullptr,
+                         workspace, workspace_bytes, stream, keep);
 }
 
 extern "C" int wise_ivf_scan_local_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist,

@@ -202,12 +202,14 @@ __global__ __launch_bounds__(64) void compact_probes_bias_kernel(const long long
 // grid (G, nq): block (g, q) scans probes [g * per, (g + 1) * per) of query q; its k keys go to part[g][q][:]
 // LOCAL (wise_ivfpq_scan_local): probes / bias are the compacted ones, count[q] of them live, dealt evenly to used[q] groups;
 // a block past used[q] returns BEFORE the table copy (its slot of part is never read: the merge folds used[q] lists)
-template <int VEC, bool LOCAL>
+// SEL (wise_ivfpq_scan_sel): only the rows whose bit of `keep` is set are scored and offered — the score of such a row is the
+// unfiltered scan's, bit for bit; a wave whose 64 rows are all clear goes on to its next 64 (offer's ballot: wave-uniform)
+template <int VEC, bool LOCAL, bool SEL = false>
 __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                       int nlist, const float* __restrict__ lut, const long long* __restrict__ probes,
                                                       const float* __restrict__ bias, int nprobe, int per, int m, int k, int cap,
                                                       u64* __restrict__ part, const int* __restrict__ count,
-                                                      const int* __restrict__ used) {
+                                                      const int* __restrict__ used, const unsigned* __restrict__ keep = nullptr) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
     const int q = blockIdx.y, g = blockIdx.x;
@@ -239,7 +241,8 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __res
         const long long lo = list_off[l], hi = list_off[l + 1];
         for (long long r0 = lo + wave * 64; r0 < hi; r0 += (long long)nwaves * 64) {      // wave-uniform
             const long long row = r0 + lane;
-            const bool live = row < hi;
+            bool live = row < hi;
+            if constexpr (SEL) live = live && ((keep[row >> 5] >> (row & 31)) & 1u) != 0;
             float s = b;
             if (live) s = pq_row_score<VEC>(codes + (size_t)row * m, m, tab, b);
             const u64 key = make_key(s, (unsigned)row);
@@ -337,11 +340,14 @@ static bool plan_scan(int nq, int nprobe, int k, int m, ScanShape* s) {
 template <int VEC, bool LOCAL>
 static void launch_pq_scan(const ScanShape& s, int nq, const unsigned char* codes, const long long* list_off, int nlist, const float* lut,
                            const long long* probes, const float* bias, int nprobe, int m, int k, u64* part, hipStream_t st,
-                           const int* count = nullptr, const int* used = nullptr) {
+                           const int* count = nullptr, const int* used = nullptr, const unsigned* keep = nullptr) {
     auto kern = pq_scan_kernel<VEC, LOCAL>;
+    if constexpr (!LOCAL) {
+        if (keep) kern = pq_scan_kernel<VEC, false, true>;
+    }
     if (s.lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)s.lds);
     hipLaunchKernelGGL(kern, dim3(s.groups, nq), dim3(s.waves * 64), s.lds, st, codes, list_off, nlist, lut, probes, bias, nprobe,
-                       s.per, m, k, s.cap, part, count, used);
+                       s.per, m, k, s.cap, part, count, used, keep);
 }
 
 // Workspace of the rank-local scan: the keys [groups][nq][k], then the kept probes [nq][nprobe], their bias, the kept counts
@@ -426,32 +432,49 @@ extern "C" size_t wise_ivfpq_scan_workspace_bytes(int nq, int nprobe, int k, int
     return align_up((size_t)s.groups * nq * k * sizeof(u64), 256);
 }
 
-extern "C" int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
-                               const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
-                               int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+// wise_ivfpq_scan and, with keep, wise_ivfpq_scan_sel
+static int pq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                        const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
+                        int64_t* outI, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* keep) {
     ScanShape s;
     if (!plan_scan(nq, nprobe, k, m, &s) || nq > 65535) {
-        set_error("ivfpq_scan: nq=%d nprobe=%d k=%d m=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048, m <= 128)", nq, nprobe, k, m);
+        set_error("%s: nq=%d nprobe=%d k=%d m=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048, m <= 128)", what, nq, nprobe, k, m);
         return WISE_E_UNSUPPORTED;
     }
-    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll, "ivfpq_scan: N=%lld nlist=%d out of range", (long long)N, nlist);
-    WISE_CHECK_ARG(lut && probes && bias && outD && outI && list_off && (codes || N == 0), "ivfpq_scan: null pointer");
-    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)lut & 15) == 0, "ivfpq_scan: codes and lut must be 16-byte aligned");
+    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld nlist=%d out of range", what, (long long)N, nlist);
+    WISE_CHECK_ARG(lut && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)lut & 15) == 0, "%s: codes and lut must be 16-byte aligned", what);
     const size_t need = wise_ivfpq_scan_workspace_bytes(nq, nprobe, k, m);
     if (!workspace || workspace_bytes < need) {
-        set_error("ivfpq_scan: workspace %zu < %zu bytes", workspace_bytes, need);
+        set_error("%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
         return WISE_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
     u64* part = reinterpret_cast<u64*>(workspace);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
     const long long* pr = reinterpret_cast<const long long*>(probes);
-    if (m % 16 == 0) launch_pq_scan<16, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else if (m % 8 == 0) launch_pq_scan<8, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else if (m % 4 == 0) launch_pq_scan<4, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
-    else launch_pq_scan<1, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st);
+    if (m % 16 == 0) launch_pq_scan<16, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st, nullptr, nullptr, keep);
+    else if (m % 8 == 0) launch_pq_scan<8, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st, nullptr, nullptr, keep);
+    else if (m % 4 == 0) launch_pq_scan<4, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st, nullptr, nullptr, keep);
+    else launch_pq_scan<1, false>(s, nq, codes, lo, nlist, lut, pr, bias, nprobe, m, k, part, st, nullptr, nullptr, keep);
     WISE_LAUNCH_CHECK("pq_scan_kernel");
     return merge_lists_launch(part, s.groups, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st);
+}
+
+extern "C" int wise_ivfpq_scan(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                               const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
+                               int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    return pq_scan_impl("ivfpq_scan", codes, N, m, list_off, nlist, ids, lut, nq, probes, bias, nprobe, k, outD, outI, workspace,
+                        workspace_bytes, stream, nullptr);
+}
+
+extern "C" int wise_ivfpq_scan_sel(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
+                                   const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                                   const uint32_t* keep, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    WISE_CHECK_ARG(keep || N == 0, "ivfpq_scan_sel: null bitmap");
+    return pq_scan_impl("ivfpq_scan_sel", codes, N, m, list_off, nlist, ids, lut, nq, probes, bias, nprobe, k, outD, outI, workspace,
+                        workspace_bytes, stream, keep);
 }
 
 extern "C" size_t wise_ivfpq_scan_local_workspace_bytes(int nq, int nprobe, int k, int m) {

@@ -69,6 +69,7 @@ from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
 from .search_index import SearchIndex
+from .selector import SearchParameters, as_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
                       shard_range)
 
@@ -558,7 +559,10 @@ class FeatureSearchIndex(SearchIndex):
         self.feature_extractor = FeatureExtractorFactory(self.feature_extractor_id)
         return True
 
-    def search(self, media_type, query, topk=5, query_type='text'):
+    def search(self, media_type, query, topk=5, query_type='text', *, within=None):
+        """`within` (not in the reference): an IDSelector (wise_amd/index/selector.py) or an array-like of vector ids — the
+        topk best among THOSE vectors, filtered inside the index scan (the reference intersects after the top-k, search.py's
+        `in` / `not_in` merges, and so returns fewer than topk).  None: the reference's call, unchanged."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
 
@@ -571,14 +575,17 @@ class FeatureSearchIndex(SearchIndex):
             media_query_text = [(self.prompt[media_type] + query)]
 
         query_features = self.feature_extractor.extract_text_features(media_query_text)
-        dist, ids = self.index.search(query_features, topk)
+        if within is None:
+            dist, ids = self.index.search(query_features, topk)
+        else:
+            dist, ids = self.index.search(query_features, topk, params=SearchParameters(sel=as_selector(within)))
         return dist[0], ids[0]
 
-    def search_batch(self, media_type, queries, topk=5, query_type='text'):
+    def search_batch(self, media_type, queries, topk=5, query_type='text', *, within=None):
         """Not in the reference: what `search` returns for every string of `queries`, from ONE text-tower batch and ONE
         batched index search per 256 of them (wise_amd/search/batch_queries.py; the --queries-from loop of search.py:894-950
-        calls `search` row by row)."""
+        calls `search` row by row).  `within`: as on `search`, one selector for all queries."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
         from ..search.batch_queries import batched_text_search
-        return batched_text_search(self, media_type, queries, topk)
+        return batched_text_search(self, media_type, queries, topk, within=within)

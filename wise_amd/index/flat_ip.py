@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .selector import resolve_for, unpack_params
 
 
 class FlatIPIndex:
@@ -125,10 +126,19 @@ class FlatIPIndex:
             self._ids = torch.empty(0, dtype=torch.int64, device=self.device)
 
     # -- search ---------------------------------------------------------------------------------
-    def search_device(self, q: torch.Tensor, k: int):
-        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64) on device, no host sync."""
+    def _selector_rows(self):
+        """(external ids on the device or None, id_base, row count) of the merged rows: what a selector is resolved against."""
+        self._finalize()
+        return self._ids, self.id_base, self._n
+
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64) on device, no host sync.
+        sel: an IDSelector (selector.py) — only the rows it selects compete.  Always the exact fp32 scan, over the ascending
+        list of selected positions (wise_ip_topk_pos_f32); the shadow copies and their counters are not touched."""
         lib = _lib.lib()
         self._finalize()
+        if sel is not None:
+            return self._search_selected(lib, q, k, resolve_for(self, sel))
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
         q = q.to(self.device, torch.float32).contiguous()
@@ -198,6 +208,27 @@ class FlatIPIndex:
         _lib.check(rc, "wise_ip_topk_f32")
         return D, I
 
+    def _search_selected(self, lib, q: torch.Tensor, k: int, res):
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
+        q = q.to(self.device, torch.float32).contiguous()
+        nq = q.shape[0]
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return D, I
+        pos = res.positions()
+        need = lib.wise_ip_topk_workspace_bytes(pos.numel(), self.d, nq, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        rc = lib.wise_ip_topk_pos_f32(self._X.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
+                                      _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), self._ws.data_ptr(),
+                                      self._ws.numel(), _lib.stream_ptr())
+        _lib.check(rc, "wise_ip_topk_pos_f32")
+        return D, I
+
     def _ensure_shadow(self, lib) -> bool:
         """Build the bf16 copy if it is not there; False (and the shadow switched off) when HBM has no room for it."""
         if self._Xb is not None and self._Xb.shape[0] == self._n:
@@ -264,12 +295,15 @@ class FlatIPIndex:
         c = self._counters.cpu()
         return int(c[0]), int(c[1])
 
-    def search(self, x, k: int):
-        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy (feature_search_index.py:113)."""
+    def search(self, x, k: int, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy (feature_search_index.py:113).
+        params: SearchParameters(sel=...) restricts the search to the selected ids (selector.py)."""
+        sel, _ = unpack_params(params, ivf=False)
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2:
             raise ValueError("search: x must be 2-D")
-        D, I = self.search_device(torch.from_numpy(x).to(self.device), int(k))
+        q = torch.from_numpy(x).to(self.device)
+        D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel=sel)
         return D.cpu().numpy(), I.cpu().numpy()
 
     def reconstruct_batch(self, ids) -> np.ndarray:

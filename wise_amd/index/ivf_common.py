@@ -19,6 +19,7 @@ import torch
 
 from .. import _lib
 from .flat_ip import FlatIPIndex
+from .selector import resolve_for, unpack_params
 
 
 def _as_tensor(x, dtype) -> torch.Tensor:
@@ -285,6 +286,17 @@ class IVFIndexBase:
             raise ValueError(f"search: expected [nq,{self.d}], got {tuple(q.shape)}")
         return q.to(self.device, torch.float32).contiguous()
 
+    def _selector_rows(self):
+        """(external ids in list order on the device, id_base = 0, row count) of the merged lists: what a selector is resolved
+        against."""
+        self._finalize()
+        return self._lists.ids, 0, self._lists.n
+
+    def _keep(self, sel) -> Optional[torch.Tensor]:
+        """The bitmap over list positions a scan tests (selector.py), None without a selector."""
+        res = resolve_for(self, sel)
+        return None if res is None else res.bitmap
+
     def _clamped_nprobe(self) -> int:
         return max(1, min(int(self.nprobe), self.nlist, 2048))
 
@@ -293,12 +305,22 @@ class IVFIndexBase:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    def search(self, x, k: int):
-        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy."""
+    def search(self, x, k: int, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy.
+        params: SearchParametersIVF(sel=..., nprobe=...) — the coarse stage probes the same lists, only the selected rows
+        compete; nprobe replaces the index's for this call only."""
+        sel, nprobe = unpack_params(params, ivf=True)
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 2:
             raise ValueError("search: x must be 2-D")
-        D, I = self.search_device(torch.from_numpy(x).to(self.device), int(k))
+        q = torch.from_numpy(x).to(self.device)
+        kept = self.nprobe
+        try:
+            if nprobe is not None:
+                self.nprobe = nprobe
+            D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel=sel)
+        finally:
+            self.nprobe = kept
         return D.cpu().numpy(), I.cpu().numpy()
 
     def make_direct_map(self, enable: bool = True) -> None:

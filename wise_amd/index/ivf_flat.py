@@ -63,11 +63,15 @@ class IVFFlatIPIndex(IVFIndexBase):
         return self
 
     # -- search ---------------------------------------------------------------------------------
-    def _scan(self, q: torch.Tensor, k: int, local: bool, probe_count: Optional[torch.Tensor]):
+    def _scan(self, q: torch.Tensor, k: int, local: bool, probe_count: Optional[torch.Tensor], sel=None):
         """stage 1 + stage 2.  local: wise_ivf_scan_local_f32, which drops the probes whose segment is empty in this
-        index before it scans and merges, and reports the number kept per query in `probe_count` when given."""
+        index before it scans and merges, and reports the number kept per query in `probe_count` when given.
+        sel: an IDSelector — wise_ivf_scan_sel_f32 over the same probes, only the selected rows compete."""
         lib = _lib.lib()
         q = self._queries(q)
+        keep = self._keep(sel)
+        if keep is not None and local:
+            raise NotImplementedError("IVFFlatIPIndex: a rank's share of a search takes no selector")
         nq = q.shape[0]
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
@@ -85,14 +89,16 @@ class IVFFlatIPIndex(IVFIndexBase):
         head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, ls.ids.data_ptr(), q.data_ptr(), nq,
                 probes.data_ptr(), nprobe, k, D.data_ptr(), I.data_ptr())
         tail = (ws.data_ptr(), ws.numel(), _lib.stream_ptr())
-        if local:
+        if keep is not None:
+            _lib.check(lib.wise_ivf_scan_sel_f32(*head[:11], keep.data_ptr(), *head[11:], *tail), "wise_ivf_scan_sel_f32")
+        elif local:
             _lib.check(lib.wise_ivf_scan_local_f32(*head, _lib.ptr(probe_count), *tail), "wise_ivf_scan_local_f32")
         else:
             _lib.check(lib.wise_ivf_scan_f32(*head, *tail), "wise_ivf_scan_f32")
         return D, I
 
-    def search_device(self, q: torch.Tensor, k: int):
-        return self._scan(q, k, False, None)
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        return self._scan(q, k, False, None, sel)
 
     def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None):
         """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (its

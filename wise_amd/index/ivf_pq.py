@@ -221,11 +221,14 @@ class IVFPQIPIndex(IVFIndexBase):
 
     # -- search ---------------------------------------------------------------------------------
     def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False, local: bool = False,
-              probe_count: Optional[torch.Tensor] = None) -> None:
+              probe_count: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None) -> None:
         """Coarse stage, bias, tables and wise_ivfpq_scan for the queries qs into D / I [n, k]; positions: I receives positions
         in the lists instead of external ids.  local: wise_ivfpq_scan_local — the probes whose list is empty in this slice are
-        dropped first (their number kept goes to probe_count when given) and positions are those of the whole array."""
+        dropped first (their number kept goes to probe_count when given) and positions are those of the whole array.
+        keep: a selector's bitmap over the list positions (IVFIndexBase._keep) — wise_ivfpq_scan_sel, only those rows compete."""
         lib = _lib.lib()
+        if keep is not None and local:
+            raise NotImplementedError("IVFPQIPIndex: a rank's share of a search takes no selector")
         nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
         need = (lib.wise_ivfpq_scan_local_workspace_bytes if local else lib.wise_ivfpq_scan_workspace_bytes)(n, nprobe, k, self.m)
         if need == 0:
@@ -241,15 +244,18 @@ class IVFPQIPIndex(IVFIndexBase):
         head = (ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
                 lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
         tail = (ws.data_ptr(), ws.numel(), st)
-        if local:
+        if keep is not None:
+            _lib.check(lib.wise_ivfpq_scan_sel(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), "wise_ivfpq_scan_sel")
+        elif local:
             _lib.check(lib.wise_ivfpq_scan_local(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
                        "wise_ivfpq_scan_local")
         else:
             _lib.check(lib.wise_ivfpq_scan(*head, D.data_ptr(), I.data_ptr(), *tail), "wise_ivfpq_scan")
 
     def _search(self, q: torch.Tensor, k: int, chunk: int, positions: bool = False, local: bool = False,
-                probe_count: Optional[torch.Tensor] = None):
+                probe_count: Optional[torch.Tensor] = None, sel=None):
         q = self._queries(q)
+        keep = self._keep(sel)
         nq = q.shape[0]
         if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
                                         or not probe_count.is_contiguous()):
@@ -258,11 +264,12 @@ class IVFPQIPIndex(IVFIndexBase):
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         for s in range(0, nq, chunk):                    # bounds the tables: chunk * m KiB
             self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], positions, local,
-                       None if probe_count is None else probe_count[s:s + chunk])
+                       None if probe_count is None else probe_count[s:s + chunk], keep)
         return D, I
 
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
-        return self._search(q, k, chunk)
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
+        """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
+        return self._search(q, k, chunk, sel=sel)
 
     def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
                             chunk: int = 1024):
@@ -369,9 +376,11 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
         """How many positions of the PQ scan a search for k re-ranks."""
         return max(k, min(k * max(self.k_factor, 1), MAX_CANDIDATES))
 
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024):
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
+        """sel: an IDSelector — the candidates are the k * k_factor best SELECTED rows of the PQ scan; the re-ranking is unchanged."""
         lib = _lib.lib()
         q = self._queries(q)
+        keep = self._keep(sel)
         if k < 1 or k > MAX_CANDIDATES:
             raise ValueError(f"search: unsupported k={k} (1 <= k <= {MAX_CANDIDATES})")
         nq, kc, ls, st = q.shape[0], self.candidates(k), self._lists, _lib.stream_ptr()
@@ -385,7 +394,7 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
             n = qs.shape[0]
             cD = torch.empty(n, kc, dtype=torch.float32, device=self.device)
             cand = torch.empty(n, kc, dtype=torch.int64, device=self.device)
-            self._scan(qs, kc, cD, cand, positions=True)
+            self._scan(qs, kc, cD, cand, positions=True, keep=keep)
             _lib.check(lib.wise_ivf_refine(rows, self.kind, scales, ls.n, self.d, ls.ids.data_ptr(), qs.data_ptr(), n, cand.data_ptr(),
                                            kc, k, D[s:s + chunk].data_ptr(), I[s:s + chunk].data_ptr(), st), "wise_ivf_refine")
         return D, I

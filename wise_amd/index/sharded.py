@@ -28,6 +28,7 @@ import torch.distributed as dist
 
 from .. import _lib
 from .flat_ip import FlatIPIndex
+from .selector import unpack_params
 
 
 def shard_range(n_total: int, rank: int, world: int) -> Tuple[int, int]:
@@ -46,6 +47,11 @@ def merge_device(Ds: torch.Tensor, Is: torch.Tensor, k: int):
     _lib.check(lib.wise_topk_merge(Ds.contiguous().data_ptr(), Is.contiguous().data_ptr(), parts, nq, kk,
                                    D.data_ptr(), I.data_ptr(), _lib.stream_ptr()), "wise_topk_merge")
     return D, I
+
+
+NO_SELECTOR = ("the sharded indexes take no selector: a collective filtered search is not built (each rank would resolve the "
+               "selector against its own ids and the exchange would stay as it is); search the ranks' local indexes or an "
+               "unsharded index instead")
 
 
 class ShardedFlatIPIndex:
@@ -83,7 +89,9 @@ class ShardedFlatIPIndex:
     def _exchanges(self) -> bool:
         return dist.is_initialized() and (self.world > 1 or self.always_exchange)
 
-    def search_device(self, q: torch.Tensor, k: int):
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        if sel is not None:
+            raise NotImplementedError(NO_SELECTOR)
         D, I = self._local_search(q, k)
         if not self._exchanges():
             return D, I
@@ -113,12 +121,23 @@ class ShardedFlatIPIndex:
         self.last_exchange_bytes += send.numel() * 8
         return self._merge(Ds, Is, k)
 
-    def search(self, x, k: int):
-        """faiss signature, collective: every rank calls it with the same x and gets the global result."""
+    def search(self, x, k: int, params=None):
+        """faiss signature, collective: every rank calls it with the same x and gets the global result.
+        params: a selector is refused (NotImplementedError); SearchParametersIVF(nprobe=...) holds for this call only."""
         import numpy as np
 
+        sel, nprobe = unpack_params(params, ivf=hasattr(self.local, "nprobe"))
+        if sel is not None:
+            raise NotImplementedError(NO_SELECTOR)
         q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.local.device)
-        D, I = self.search_device(q, int(k))
+        kept = getattr(self.local, "nprobe", None)
+        try:
+            if nprobe is not None:
+                self.local.nprobe = nprobe
+            D, I = self.search_device(q, int(k))
+        finally:
+            if nprobe is not None:
+                self.local.nprobe = kept
         return D.cpu().numpy(), I.cpu().numpy()
 
     def reconstruct_batch(self, ids):
@@ -215,7 +234,9 @@ class ShardedIVFPQRefineIPIndex(ShardedIVFPQIPIndex):
     def k_factor(self, v: int) -> None:
         self.local.k_factor = int(v)
 
-    def search_device(self, q: torch.Tensor, k: int):
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        if sel is not None:
+            raise NotImplementedError(NO_SELECTOR)
         if not self._exchanges():
             return self.local.search_device(q, k)
         kc = self.local.candidates(k)

@@ -23,16 +23,22 @@ def prompts_for(search_index, media_type: str, queries: Sequence[str]) -> List[s
 
 
 def batched_text_search(search_index, media_type: str, queries: Sequence[str], topk: int = 5,
-                        batch: int = 256) -> List[Tuple[np.ndarray, np.ndarray]]:
+                        batch: int = 256, within=None) -> List[Tuple[np.ndarray, np.ndarray]]:
     """[(dist [topk] float32, ids [topk] int64)] — entry i equals search_index.search(media_type, queries[i], topk).
+    within: a selector or an array-like of vector ids the answers are restricted to (FeatureSearchIndex.search).
 
     `batch` queries at a time go through the text tower and the index (256 = two 128-query passes over the rows)."""
     if any(not isinstance(q, str) for q in queries):
         raise ValueError('queries must be strings (one CSV row each)')
     out: List[Tuple[np.ndarray, np.ndarray]] = []
     texts = prompts_for(search_index, media_type, queries)
+    params = None
+    if within is not None:
+        from ..index.selector import SearchParameters, as_selector
+        params = SearchParameters(sel=as_selector(within))      # resolved once: the selector keeps its bitmap per index
     for s in range(0, len(texts), batch):
         feats = search_index.feature_extractor.extract_text_features(texts[s:s + batch])
-        dist, ids = search_index.index.search(np.ascontiguousarray(feats, dtype=np.float32), topk)
+        feats = np.ascontiguousarray(feats, dtype=np.float32)
+        dist, ids = search_index.index.search(feats, topk) if params is None else search_index.index.search(feats, topk, params=params)
         out.extend((dist[i], ids[i]) for i in range(dist.shape[0]))
     return out
