@@ -338,6 +338,46 @@ int wise_ivfpq_scan_sel(const uint8_t* codes, int64_t N, int m, const int64_t* l
                         const float* lut, int nq, const int64_t* probes, const float* bias, int nprobe, int k, const uint32_t* keep,
                         float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
 
+/* (ABI 5, additive) IndexIVFSQ8: inverted lists of 8-bit scalar-quantized rows — faiss's IndexIVFScalarQuantizer(IndexFlatIP(d), d,
+ * nlist, QT_8bit, METRIC_INNER_PRODUCT), by_residual.  A row of list l is kept as d bytes, one per dimension of its residual
+ * r = x - c_l (wise_pq_residuals).  trained [2 d] fp32 = vmin [d], then vdiff [d]: one range per dimension, shared by all lists.
+ * Limits (WISE_E_INVALID otherwise): d % 16 == 0, 16 <= d <= 1024; the scan: k <= 2048, nprobe <= 2048, nq <= 65535.  All
+ * deterministic: the same inputs give the same bits.
+ *   wise_sq_train: vmin[i] = min over the n >= 1 rows of resid[:, i], vdiff[i] = max - vmin[i] (one fp32 subtraction) — faiss's
+ *     RS_minmax with argument 0.  min and max are exact, so the result does not depend on the order of the rows.
+ *   wise_sq_encode: codes[r, i] = clamp(floor((resid[r, i] - vmin[i]) * inv[i]), 0, 255) with inv[i] = 255 / vdiff[i] (0 where
+ *     vdiff[i] == 0), the fp32 inputs widened and every operation rounded to fp64 on its own — in fp32 the roundings of the
+ *     difference, the quotient and the product put values next to a bin edge into the neighbouring bin, and a value inside the
+ *     trained range would no longer decode to within half a bin; values outside the trained range clamp.
+ *   wise_sq_query: W[q, i] = (Q[q, i] * vdiff[i]) * (1 / 255) and q0[q] = sum_i Q[q, i] * (vmin[i] + vdiff[i] * (0.5 / 255)), every
+ *     product and sum rounded on its own; the sum: lane l of 64 adds i = l, l + 64, ... in ascending order from +0, then the
+ *     lanes are folded by a butterfly (v = v + v[lane ^ o] for o = 32, 16, 8, 4, 2, 1).  W 16-byte aligned.
+ *   wise_sq_decode: out[i, c] = centroids[l, c] + (vmin[c] + ((codes[pos[i], c] + 0.5) / 255) * vdiff[c]) — faiss's Codec8bit, each
+ *     operation rounded to fp32 on its own — l the list holding position pos[i] (list_off [nlist + 1]); a position outside [0, N)
+ *     gives a row of NaN.  reconstruct_batch.
+ *   wise_ivfsq_scan: the second stage of a search.  codes [N, d] uint8 grouped by list, 16-byte aligned; ids, probes, bias
+ *     (wise_pq_bias), outD / outI, ties, padding, skipped probes and empty lists as wise_ivfpq_scan.
+ *     THE ORDER OF THE ARITHMETIC IS PART OF THE CONTRACT: with C = d / 16, chunk c of a row gives s_c = +0, then
+ *     s_c = fmaf(W[q, 16 c + i], (float)code[16 c + i], s_c) for i = 0 .. 15; then for step = 1, 2, 4, ... < C, at once for every
+ *     c with c + step < C, s_c = s_c + s_{c + step} (the values from before the step); score = (bias[q, p] + q0[q]) + s_0, all in
+ *     fp32.  tests/ivfsq_ref.py reproduces it bit for bit.  Workspace: wise_ivfsq_scan_workspace_bytes(nq, nprobe, k) bytes
+ *     (0: unsupported shape); a shorter one is WISE_E_INVALID.
+ *   wise_ivfsq_scan_sel: the same in which only the rows whose bit of keep ((N + 31) / 32 words over the list positions,
+ *     wise_sel_bitmap) is set compete; a selected row's score is the unfiltered scan's, and with every bit set so is the output.
+ *     Loads that hold no selected row are skipped. */
+int wise_sq_train(const float* resid, int64_t n, int d, float* trained, void* stream);
+int wise_sq_encode(const float* resid, const float* trained, int64_t n, int d, uint8_t* codes, void* stream);
+int wise_sq_query(const float* Q, const float* trained, int nq, int d, float* W, float* q0, void* stream);
+int wise_sq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                   const float* centroids, const float* trained, int d, float* out, void* stream);
+size_t wise_ivfsq_scan_workspace_bytes(int nq, int nprobe, int k);
+int wise_ivfsq_scan(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* W,
+                    const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD, int64_t* outI,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* W,
+                        const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, const uint32_t* keep,
+                        float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].
  * Ties: lower part index first, then the order within the part.  k <= 2048, parts*k <= 65536. */

@@ -130,6 +130,13 @@ SIGNATURES = {
     "wise_opq_corr_workspace_bytes": (_sz, [_i64, _i]),
     "wise_opq_corr": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
     "wise_opq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "wise_sq_train": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_sq_encode": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
+    "wise_sq_query": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "wise_sq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "wise_ivfsq_scan_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wise_ivfsq_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wise_mlp_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "wise_mlp_stream_ln": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -1,0 +1,340 @@
+// HP-2: IndexIVFSQ8 — inverted lists of 8-bit scalar-quantized rows (faiss IndexIVFScalarQuantizer over IndexFlatIP, QT_8bit,
+// by_residual, inner product).  A row x of list l is kept as d bytes: its residual r = x - c_l, every dimension cut into 256
+// bins of the range [vmin[i], vmin[i] + vdiff[i]] the trainer saw.  One range per dimension, shared by all lists; no codebooks
+// and no per-query table.
+//   wise_sq_train    per-dimension min and range of the training residuals (exact: order does not matter)
+//   wise_sq_encode   code_i = clamp(floor((r_i - vmin[i]) * (255 / vdiff[i])), 0, 255), evaluated in double
+//   wise_sq_query    per query the weight row w[i] = q_i vdiff[i] / 255 and q0 = sum_i q_i (vmin[i] + vdiff[i] 0.5 / 255)
+//   wise_sq_decode   reconstruct_batch: c_l + vmin + vdiff (code + 0.5) / 255 (faiss Codec8bit)
+//   wise_ivfsq_scan  THE HOT PATH: score(row) = (bias + q0) + sum_i w[i] * code_i, top-k per query; wise_ivfsq_scan_sel the same
+//                    under a bitmap over the list positions
+// The scan reads d bytes per row where wise_ivf_scan_f32 reads 4 d.  One block per (query, probe), as the inverted-list form of
+// ip_scan_kernel; four waves share the list.  A row is C = d / 16 chunks of 16 bytes and a lane always holds the same chunk
+// c = lane % C of row lane / C of its wave-load, so the 16 weights of the chunk stay in registers: a 64-lane load carries
+// RPL = 64 / C whole rows (four at d = 256, two at d = 512, one from d = 528 on; the lanes past RPL * C idle).  SQ_T loads are in
+// flight per wave.  Per byte: one v_cvt_f32_ubyte and one v_fma_f32, i.e. 2 VALU lane-operations per byte against 64 per clock
+// and CU — 32 B / clock / CU where HBM delivers about 13 (8 TB/s over 256 CUs at 2.4 GHz): the bound is HBM.
+// THE SUMMATION ORDER (tests/ivfsq_ref.py restates it): lane (row, c) runs s = +0, s = fmaf(w[16 c + i], (float)code[16 c + i], s)
+// for i = 0 .. 15; then for step = 1, 2, 4, ... < C every lane with c + step < C adds the value lane c + step held BEFORE the
+// step (s_c = s_c + s_{c + step}); chunk 0 then holds the row's sum and score = (bias + q0) + s_0.  No packed f32 math.
+// Selection is the flat scan's: sortable (score, position) keys, per-wave threshold lists, merge_keys_kernel.
+#include "topk_common.h"
+
+namespace wise {
+namespace ivf_sq {
+
+constexpr int MAX_D = 1024;
+constexpr int SQ_T = 4;                   // wave-loads in flight per wave of the scan
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+static bool sq_shape_ok(int d) { return d >= 16 && d <= MAX_D && d % 16 == 0; }
+
+// trained is used as 2 d ordered-unsigned cells while the reduction runs: min cells start at the largest key, max cells at 0
+__global__ __launch_bounds__(256) void train_init_kernel(unsigned* __restrict__ cells, int d) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * d) cells[i] = i < d ? 0xFFFFFFFFu : 0u;
+}
+
+// block = (64 columns, a stride of rows); thread (column, row phase).  min / max are exact, so neither the order of the rows nor
+// that of the atomics changes a bit of the result.
+__global__ __launch_bounds__(256) void train_minmax_kernel(const float* __restrict__ r, long long n, int d, unsigned* __restrict__ cells) {
+    __shared__ unsigned smin[4][64], smax[4][64];
+    const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + cx;
+    unsigned mn = 0xFFFFFFFFu, mx = 0u;
+    if (col < d) {
+        for (long long row = (long long)blockIdx.y * 4 + ry; row < n; row += (long long)gridDim.y * 4) {
+            const unsigned o = f32_order(r[(size_t)row * d + col]);
+            mn = o < mn ? o : mn;
+            mx = o > mx ? o : mx;
+        }
+    }
+    smin[ry][cx] = mn;
+    smax[ry][cx] = mx;
+    __syncthreads();
+    if (ry == 0 && col < d) {
+        for (int y = 1; y < 4; ++y) {
+            mn = smin[y][cx] < mn ? smin[y][cx] : mn;
+            mx = smax[y][cx] > mx ? smax[y][cx] : mx;
+        }
+        atomicMin(&cells[col], mn);
+        atomicMax(&cells[d + col], mx);
+    }
+}
+
+__global__ __launch_bounds__(256) void train_finish_kernel(float* __restrict__ trained, int d) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d) return;
+    const unsigned* cells = reinterpret_cast<const unsigned*>(trained);
+    const float mn = f32_unorder(cells[i]), mx = f32_unorder(cells[d + i]);
+    trained[i] = mn;
+    trained[d + i] = mx - mn;
+}
+
+// thread = one value
+__global__ __launch_bounds__(256) void encode_kernel(const float* __restrict__ r, const float* __restrict__ trained, long long total, int d,
+                                                     unsigned char* __restrict__ codes) {
+#pragma clang fp contract(off)
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int i = (int)(e % d);
+    // in double: r - vmin is then exact (or as good as) and the bin is the one the real number falls into, so a value inside the
+    // trained range decodes to within half a bin; in float the three roundings put values next to an edge into the wrong bin
+    const double vmin = (double)trained[i], vdiff = (double)trained[d + i];
+    const double inv = vdiff != 0.0 ? 255.0 / vdiff : 0.0;
+    const double t = ((double)r[e] - vmin) * inv;
+    double v = floor(t);
+    v = v > 0.0 ? v : 0.0;                       // (a NaN lands here too)
+    v = v < 255.0 ? v : 255.0;
+    codes[e] = (unsigned char)(int)v;
+}
+
+// block = one wave = one query.  q0: lane l runs acc = +0, acc = acc + q_i * (vmin[i] + vdiff[i] * (0.5 / 255)) over i = l, l + 64,
+// ... with every product and sum rounded on its own, then the butterfly wave_sum (xor 32, 16, ..., 1)
+__global__ __launch_bounds__(64) void query_kernel(const float* __restrict__ Q, const float* __restrict__ trained, int d,
+                                                   float* __restrict__ W, float* __restrict__ q0) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x, q = blockIdx.x;
+    const float inv255 = 1.0f / 255.0f, half255 = 0.5f / 255.0f;
+    float acc = 0.f;
+    for (int i = lane; i < d; i += 64) {
+        const float qi = Q[(size_t)q * d + i], vmin = trained[i], vdiff = trained[d + i];
+        const float qv = qi * vdiff;
+        W[(size_t)q * d + i] = qv * inv255;
+        const float h = vdiff * half255;
+        const float t = vmin + h;
+        const float p = qi * t;
+        acc = acc + p;
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) q0[q] = acc;
+}
+
+// out[i][:] = c_l + (vmin + ((code + 0.5) / 255) * vdiff), l = the list that holds position pos[i]; NaN when pos[i] is out of range
+__global__ __launch_bounds__(256) void decode_kernel(const unsigned char* __restrict__ codes, long long N, const long long* __restrict__ pos,
+                                                     const long long* __restrict__ list_off, int nlist, const float* __restrict__ cent,
+                                                     const float* __restrict__ trained, int d, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long p = pos[blockIdx.x];
+    float* o = out + (size_t)blockIdx.x * d;
+    if (p < 0 || p >= N) {
+        for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = __builtin_nanf("");
+        return;
+    }
+    int a = 0, b = nlist;                        // the last list whose offset is <= p (empty lists share offsets: skip them)
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (list_off[mid] <= p) a = mid; else b = mid;
+    }
+    const float* cr = cent + (size_t)a * d;
+    const unsigned char* code = codes + (size_t)p * d;
+    for (int c = threadIdx.x; c < d; c += blockDim.x) {
+        const float xi = ((float)code[c] + 0.5f) / 255.0f;
+        const float s = xi * trained[d + c];
+        const float y = trained[c] + s;
+        o[c] = cr[c] + y;
+    }
+}
+
+// s = fmaf(w[4 j + b], (float)byte b of word, s) for b = 0 .. 3: the byte-select conversions, one fma each
+__device__ __forceinline__ float chain_word(float s, unsigned word, const float4 w) {
+    s = fmaf(w.x, (float)(word & 0xffu), s);
+    s = fmaf(w.y, (float)((word >> 8) & 0xffu), s);
+    s = fmaf(w.z, (float)((word >> 16) & 0xffu), s);
+    s = fmaf(w.w, (float)(word >> 24), s);
+    return s;
+}
+
+// grid = nq * nprobe: block b scans the list probes[b] of query b / nprobe; its k keys go to part[(b % nprobe) * nq + b / nprobe]
+// SEL: only the rows whose bit of `keep` is set are offered; a wave whose SQ_T loads hold no such row skips them (wave-uniform)
+template <bool SEL>
+__global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
+                                                      int nlist, const float* __restrict__ W, const float* __restrict__ q0,
+                                                      const long long* __restrict__ probes, const float* __restrict__ bias, int nprobe,
+                                                      int nq, int d, int k, int cap, u64* __restrict__ part,
+                                                      const unsigned* __restrict__ keep) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
+    const long long l = probes[(size_t)qi * nprobe + pi];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }          // block-uniform
+    const int C = d >> 4, RPL = 64 / C;
+    const int sub = lane / C, c = lane - sub * C;
+    const bool active = sub < RPL;
+    const float4* wq = reinterpret_cast<const float4*>(W + (size_t)qi * d + 16 * c);
+    const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
+    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
+
+    WaveList wl;
+    wl.init(reinterpret_cast<u64*>(smem) + (size_t)wave * cap, cap, k, lane);
+
+    const long long ngroups = (hi - lo + RPL - 1) / RPL;                            // groups of RPL rows = wave-loads
+    for (long long g = (long long)wave * SQ_T; g < ngroups; g += 4 * SQ_T) {       // wave-uniform
+        long long row[SQ_T];
+        bool live[SQ_T];
+        bool any = false;
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            row[t] = lo + (g + t) * RPL + sub;
+            live[t] = active && row[t] < hi;
+            if constexpr (SEL) live[t] = live[t] && ((keep[row[t] >> 5] >> (row[t] & 31)) & 1u) != 0;
+            any = any || live[t];
+        }
+        if constexpr (SEL) {
+            if (__ballot(any) == 0) continue;
+        }
+        u32x4 x[SQ_T];
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            const long long r = row[t] < hi ? row[t] : hi - 1;                      // stay inside the list; masked below
+            x[t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(codes + (size_t)r * d) + c);
+        }
+        float s[SQ_T];
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            float a = 0.f;
+            a = chain_word(a, x[t][0], w0);
+            a = chain_word(a, x[t][1], w1);
+            a = chain_word(a, x[t][2], w2);
+            a = chain_word(a, x[t][3], w3);
+            s[t] = a;
+        }
+        for (int step = 1; step < C; step <<= 1) {                                  // the chunks of a row: lanes c .. c + C - 1
+            const bool take = c + step < C;
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t) {
+                const float v = __shfl_down(s[t], step, 64);
+                s[t] = take ? s[t] + v : s[t];
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            const u64 key = make_key(base + s[t], (unsigned)row[t]);
+            wl.offer(live[t] && c == 0 && key > wl.tau, key, lane, 64);
+        }
+    }
+
+    wl.compact(lane);
+    __syncthreads();
+    if (wave == 0) {
+        for (int w = 1; w < 4; ++w) {
+            const u64* other = reinterpret_cast<const u64*>(smem) + (size_t)w * cap;
+            for (int i0 = 0; i0 < k; i0 += 64) {
+                const int i = i0 + lane;
+                const u64 key = i < k ? other[i] : 0;
+                wl.offer(key != 0 && key > wl.tau, key, lane, 64);
+            }
+        }
+        wl.compact(lane);
+        u64* dst = part + ((size_t)pi * nq + qi) * k;
+        for (int i = lane; i < k; i += 64) dst[i] = wl.buf[i];
+    }
+}
+
+static bool scan_shape_ok(int nq, int nprobe, int k) {
+    return nq >= 1 && nq <= 65535 && nprobe >= 1 && nprobe <= 2048 && k >= 1 && k <= 2048;
+}
+
+}  // namespace ivf_sq
+}  // namespace wise
+
+using namespace wise;
+using namespace wise::ivf_sq;
+
+#define SQ_CHECK_SHAPE(what) WISE_CHECK_ARG(sq_shape_ok(d), what ": d=%d unsupported (d %% 16 == 0 in [16, 1024])", d)
+
+extern "C" int wise_sq_train(const float* resid, int64_t n, int d, float* trained, void* stream) {
+    SQ_CHECK_SHAPE("sq_train");
+    WISE_CHECK_ARG(n >= 1 && resid && trained, "sq_train: bad argument (n >= 1)");
+    hipStream_t st = (hipStream_t)stream;
+    unsigned* cells = reinterpret_cast<unsigned*>(trained);
+    hipLaunchKernelGGL(train_init_kernel, dim3((2 * d + 255) / 256), dim3(256), 0, st, cells, d);
+    WISE_LAUNCH_CHECK("sq train_init_kernel");
+    long long slabs = (n + 3) / 4;
+    if (slabs > 1024) slabs = 1024;
+    hipLaunchKernelGGL(train_minmax_kernel, dim3((d + 63) / 64, (unsigned)slabs), dim3(256), 0, st, resid, (long long)n, d, cells);
+    WISE_LAUNCH_CHECK("sq train_minmax_kernel");
+    hipLaunchKernelGGL(train_finish_kernel, dim3((d + 255) / 256), dim3(256), 0, st, trained, d);
+    WISE_LAUNCH_CHECK("sq train_finish_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_sq_encode(const float* resid, const float* trained, int64_t n, int d, uint8_t* codes, void* stream) {
+    SQ_CHECK_SHAPE("sq_encode");
+    WISE_CHECK_ARG(n >= 0 && n < (1ll << 31) && trained && (n == 0 || (resid && codes)), "sq_encode: bad argument");
+    if (n == 0) return WISE_OK;
+    const long long total = (long long)n * d;
+    hipLaunchKernelGGL(encode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, resid, trained, total, d,
+                       codes);
+    WISE_LAUNCH_CHECK("sq encode_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_sq_query(const float* Q, const float* trained, int nq, int d, float* W, float* q0, void* stream) {
+    SQ_CHECK_SHAPE("sq_query");
+    WISE_CHECK_ARG(nq >= 0 && nq <= 65535 && trained && (nq == 0 || (Q && W && q0)), "sq_query: bad argument (nq <= 65535)");
+    if (nq == 0) return WISE_OK;
+    hipLaunchKernelGGL(query_kernel, dim3(nq), dim3(64), 0, (hipStream_t)stream, Q, trained, d, W, q0);
+    WISE_LAUNCH_CHECK("sq query_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_sq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                              const float* centroids, const float* trained, int d, float* out, void* stream) {
+    SQ_CHECK_SHAPE("sq_decode");
+    WISE_CHECK_ARG(N >= 0 && rows >= 0 && nlist >= 1 && list_off && centroids && trained && (N == 0 || codes) && (rows == 0 || (pos && out)),
+                   "sq_decode: bad argument");
+    if (rows == 0) return WISE_OK;
+    hipLaunchKernelGGL(decode_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, codes, (long long)N, (const long long*)pos,
+                       (const long long*)list_off, nlist, centroids, trained, d, out);
+    WISE_LAUNCH_CHECK("sq decode_kernel");
+    return WISE_OK;
+}
+
+extern "C" size_t wise_ivfsq_scan_workspace_bytes(int nq, int nprobe, int k) {
+    if (!scan_shape_ok(nq, nprobe, k)) return 0;
+    return align_up((size_t)nq * nprobe * k * sizeof(u64), 256);
+}
+
+// wise_ivfsq_scan and, with keep, wise_ivfsq_scan_sel
+static int sq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                        const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
+                        int64_t* outI, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* keep) {
+    WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
+    WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "%s: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)", what, nq,
+                   nprobe, k);
+    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld nlist=%d out of range", what, (long long)N, nlist);
+    WISE_CHECK_ARG(W && q0 && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
+    const size_t need = wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
+    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    u64* part = reinterpret_cast<u64*>(workspace);
+    const int cap = topk_list_cap(k);
+    const size_t lds = (size_t)4 * cap * 8;
+    auto kern = keep ? sq_scan_kernel<true> : sq_scan_kernel<false>;
+    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, codes, (const long long*)list_off, nlist, W, q0,
+                       (const long long*)probes, bias, nprobe, nq, d, k, cap, part, keep);
+    WISE_LAUNCH_CHECK("sq_scan_kernel");
+    return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st);
+}
+
+extern "C" int wise_ivfsq_scan(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                               const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                               float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_scan_impl("ivfsq_scan", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
+                        workspace_bytes, stream, nullptr);
+}
+
+extern "C" int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                   const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                                   const uint32_t* keep, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    WISE_CHECK_ARG(keep || N == 0, "ivfsq_scan_sel: null bitmap");
+    return sq_scan_impl("ivfsq_scan_sel", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
+                        workspace_bytes, stream, keep);
+}

@@ -46,6 +46,16 @@ rotation acts on the residual, after the coarse stage):
     f32[d*d]                                      the rotation R, row-major: a residual r is encoded as R r
     a complete 'IwPQ' record (IndexIVFOPQ<m>) or a complete 'WiPR' record (IndexIVFOPQ<m>R8 / R16)
 
+The file of index type 'IndexIVFSQ8' (write_ivf_sq_ip / read_ivf_sq_ip) restates faiss's IndexIVFScalarQuantizer record:
+
+    u32  'IwSq'                                   IndexIVFScalarQuantizer fourcc
+    header | u64 nlist | u64 nprobe | 'IxFI' quantizer | direct map           exactly as in the 'IwFl' file
+    i32  qtype (0 = QT_8bit, the first value of faiss's QuantizerType; 1 is QT_4bit) | i32 rangestat (0 = RS_minmax)
+         | f32 rangestat_arg (0) | u64 d | u64 code_size (= d)
+    u64  2d | f32[2d] trained                     vmin [d], then vdiff [d]
+    u64  code_size (= d) | u8 by_residual (1)
+    'ilar' array inverted lists with code_size = d: per non-empty list u8 codes[size*d] | i64 ids[size]
+
 Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
@@ -62,6 +72,7 @@ from pathlib import Path
 import numpy as np
 
 _DUMMY = 1 << 20
+QT_8BIT = 0          # faiss ScalarQuantizer::QuantizerType::QT_8bit
 
 
 def _fourcc(s: str) -> int:
@@ -173,13 +184,15 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
             ids[a:b].tofile(f)
 
 
-def _read_ivf_head(f, p, pq: bool = False):
+def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload).
-    pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks)."""
+    pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks).
+    sq: an 'IwSq' file instead; the ScalarQuantizer record's trained values [2d] are appended."""
     base = f.tell()                                          # (an 'IwPQ' record may sit inside a 'WiPR' file)
     (cc,) = struct.unpack("<I", f.read(4))
-    if cc != _fourcc("IwPQ" if pq else "IwFl"):
-        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {'IndexIVFPQ' if pq else 'IndexIVFFlat'}")
+    want, name = ("IwPQ", "IndexIVFPQ") if pq else ("IwSq", "IndexIVFScalarQuantizer") if sq else ("IwFl", "IndexIVFFlat")
+    if cc != _fourcc(want):
+        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {name}")
     hdr = f.read(_HDR_SIZE + 4)
     d, n, metric, off = _read_header(hdr, 0)
     f.seek(base + 4 + off)
@@ -209,8 +222,18 @@ def _read_ivf_head(f, p, pq: bool = False):
             raise RuntimeError(f"{p}: unsupported IndexIVFPQ (by_residual={by_residual}, d={dp}, M={m}, nbits={nbits}, "
                                f"code_size={code_size_pq}, {cnt} codebook values)")
         codebooks = np.fromfile(f, dtype=np.float32, count=cnt).reshape(m, 256, d // m)
+    trained = None
+    if sq:
+        qtype, rangestat, rangestat_arg, dsq, code_size_sq, cnt = struct.unpack("<iifQQQ", f.read(36))
+        if qtype != QT_8BIT or dsq != d or code_size_sq != d or cnt != 2 * d:
+            raise RuntimeError(f"{p}: unsupported IndexIVFScalarQuantizer (qtype={qtype}, d={dsq}, code_size={code_size_sq}, "
+                               f"{cnt} trained values): QT_8bit with one range per dimension is what is read")
+        trained = np.fromfile(f, dtype=np.float32, count=cnt)
+        code_size_ivf, by_residual = struct.unpack("<QB", f.read(9))
+        if trained.size != cnt or code_size_ivf != d or by_residual != 1:
+            raise RuntimeError(f"{p}: unsupported IndexIVFScalarQuantizer (code_size={code_size_ivf}, by_residual={by_residual})")
     il, nl2, code_size = struct.unpack("<IQQ", f.read(20))
-    if il != _fourcc("ilar") or nl2 != nlist or code_size != (m if pq else 4 * d):
+    if il != _fourcc("ilar") or nl2 != nlist or code_size != (m if pq else d if sq else 4 * d):
         raise RuntimeError(f"{p}: unexpected inverted lists (type 0x{il:08x}, code size {code_size})")
     (lt, vn) = struct.unpack("<IQ", f.read(12))
     sizes = np.zeros(nlist, dtype=np.int64)
@@ -226,6 +249,8 @@ def _read_ivf_head(f, p, pq: bool = False):
         raise RuntimeError(f"{p}: lists hold {list_off[-1]} rows, header says {n}")
     if pq:
         return centroids, list_off, int(nprobe), f.tell(), int(m), codebooks
+    if sq:
+        return centroids, list_off, int(nprobe), f.tell(), trained
     return centroids, list_off, int(nprobe), f.tell()
 
 
@@ -619,6 +644,71 @@ def read_ivf_opq_ip_range(path, lo: int, hi: int):
         rotation, inner = _read_opq_head(f, p)
         out = _read_ivf_pq_record_range(f, p, lo, hi)[0] if inner == _fourcc("IwPQ") else _read_refine_record_range(f, p, lo, hi)
         return _with_rotation(out, rotation, p)
+
+
+# ---------------------------------------------------------------------------------------------- 'IwSq': 8-bit scalar quantizer
+def write_ivf_sq_ip(path, centroids: np.ndarray, trained: np.ndarray, codes: np.ndarray, ids: np.ndarray, list_off: np.ndarray,
+                    nprobe: int = 1) -> None:
+    """codes [n,d] uint8 / ids hold the lists back to back; trained [2d] fp32 = vmin, then vdiff (QT_8bit, by_residual)."""
+    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+    trained = np.ascontiguousarray(trained, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    nlist, d = centroids.shape
+    n = codes.shape[0]
+    assert codes.shape == (n, d) and trained.shape == (2 * d,)
+    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IwSq")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<QQ", nlist, nprobe))
+        f.write(struct.pack("<I", _fourcc("IxFI")))
+        f.write(_header(d, nlist))
+        f.write(struct.pack("<Q", nlist * d))
+        centroids.tofile(f)
+        f.write(struct.pack("<BQ", 0, 0))
+        f.write(struct.pack("<iifQQ", QT_8BIT, 0, 0.0, d, d))          # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
+        f.write(struct.pack("<Q", 2 * d))
+        trained.tofile(f)
+        f.write(struct.pack("<QB", d, 1))                        # code_size, by_residual
+        f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, d))
+        nonzero = np.flatnonzero(sizes)
+        if len(nonzero) > nlist // 2:
+            f.write(struct.pack("<IQ", _fourcc("full"), nlist))
+            sizes.tofile(f)
+        else:
+            f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
+            np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
+        for l in nonzero:
+            a, b = int(list_off[l]), int(list_off[l + 1])
+            codes[a:b].tofile(f)
+            ids[a:b].tofile(f)
+
+
+def read_ivf_sq_ip(path):
+    """-> dict(centroids [nlist,d], trained [2d] (vmin, then vdiff), codes [n,d] uint8, ids [n], list_off [nlist+1], nprobe), the
+    lists back to back in list order.  A file cut short is refused (RuntimeError)."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        try:
+            centroids, list_off, nprobe, _, trained = _read_ivf_head(f, p, sq=True)
+        except (struct.error, ValueError) as e:
+            raise RuntimeError(f"{p}: the head of an IndexIVFScalarQuantizer file is cut short ({e})") from None
+        n, d = int(list_off[-1]), centroids.shape[1]
+        codes = np.empty((n, d), dtype=np.uint8)
+        ids = np.empty((n,), dtype=np.int64)
+        for l in np.flatnonzero(np.diff(list_off)):
+            a, b = int(list_off[l]), int(list_off[l + 1])
+            c = np.fromfile(f, dtype=np.uint8, count=(b - a) * d)
+            i = np.fromfile(f, dtype=np.int64, count=b - a)
+            if c.size != (b - a) * d or i.size != b - a:
+                raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
+            codes[a:b], ids[a:b] = c.reshape(b - a, d), i
+    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
 
 
 def index_fourcc(path) -> str:

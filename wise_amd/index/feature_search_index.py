@@ -55,6 +55,9 @@ ivf_pq.py: IVFOPQIPIndex, IVFOPQRefineIPIndex); their file wraps the PQ record i
 (faiss_io.py).  They take every path above as their IndexIVFPQ counterparts do: in the collective build rank 0 also trains the
 rotation, which is broadcast with the codebooks; each rank rotates its own rows and, in a search, the query — the rotation is
 replicated, so the sharded classes and their exchanges are the same.
+`IndexIVFSQ8` is the inverted file over one byte per dimension (faiss's IndexIVFScalarQuantizer, QT_8bit; ivf_sq.py: IVFSQIPIndex;
+file: faiss's 'IwSq' record, faiss_io.py).  It is not sharded: under a process group, with or without WISE_SHARDED_IVF, rank 0
+builds the one file and every rank loads it, as IndexIVFFlat does without the switch.
 """
 import os
 from pathlib import Path
@@ -68,6 +71,7 @@ from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
+from .ivf_sq import IVFSQIPIndex, check_sq_shape
 from .search_index import SearchIndex
 from .selector import SearchParameters, as_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
@@ -195,6 +199,7 @@ class FeatureSearchIndex(SearchIndex):
         parse_m, parse_refine, opq = _pq_parsers(index_type)
         refine = parse_refine(index_type)
         is_pq = parse_m(index_type) is not None or refine is not None
+        is_sq = index_type == 'IndexIVFSQ8'
         sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq) and _sharded_ivf_on()
         if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
@@ -208,11 +213,11 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq:
+        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq and not is_sq:
             raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
-                                      f'IndexIVFOPQ<m> forms) are the index types WISE builds')
+                                      f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
         self.index_type = index_type
-        if sharded and (index_type == 'IndexIVFFlat' or is_pq) and not sharded_ivf and rank != 0:
+        if sharded and (index_type == 'IndexIVFFlat' or is_pq or is_sq) and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
@@ -226,6 +231,8 @@ class FeatureSearchIndex(SearchIndex):
             pq_m, kind = parse_refine(index_type, feature_dim)
         else:
             pq_m = parse_m(index_type, feature_dim) if is_pq else None
+        if is_sq:
+            check_sq_shape(feature_dim)
 
         # the on-disk index is assembled on the host (I/O-bound: tar + unpickle per vector), 512 at a time
         X = np.empty((feature_count, feature_dim), dtype=np.float32)
@@ -242,7 +249,7 @@ class FeatureSearchIndex(SearchIndex):
                                      kind=kind if refine is not None else None, opq=opq)
             print(f'  saved index part to {index_fn}')
             return
-        if index_type == 'IndexIVFFlat' or is_pq:
+        if index_type == 'IndexIVFFlat' or is_pq or is_sq:
             cell_count = reference_nlist(n)
             train_count = min(n, 100 * cell_count)
             # the reference trains on the first train_count vectors of a shard-shuffled pass (:62-69); a seeded
@@ -254,9 +261,11 @@ class FeatureSearchIndex(SearchIndex):
                 ivf = (IVFOPQRefineIPIndex if opq else IVFPQRefineIPIndex)(feature_dim, cell_count, pq_m, kind)
             elif opq:
                 ivf = IVFOPQIPIndex(feature_dim, cell_count, pq_m)
+            elif is_sq:
+                ivf = IVFSQIPIndex(feature_dim, cell_count)
             else:
                 ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
-            ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
+            ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ / SQ8) the codebooks / ranges on its residuals
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
             if opq:
@@ -273,6 +282,9 @@ class FeatureSearchIndex(SearchIndex):
             elif is_pq:
                 c, cb, codes, ids_s, off = ivf.lists_host()
                 faiss_io.write_ivf_pq_ip(index_fn, c, cb, codes, ids_s, off, nprobe=ivf.nprobe)
+            elif is_sq:
+                c, trained, codes, ids_s, off = ivf.lists_host()
+                faiss_io.write_ivf_sq_ip(index_fn, c, trained, codes, ids_s, off, nprobe=ivf.nprobe)
             else:
                 c, Xs, ids_s, off = ivf.lists_host()
                 faiss_io.write_ivf_flat_ip(index_fn, c, Xs, ids_s, off, nprobe=ivf.nprobe)
@@ -531,6 +543,15 @@ class FeatureSearchIndex(SearchIndex):
             index = IVFPQIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0])
             index.set_centroids(f["centroids"])
             index.set_codebooks(f["codebooks"])
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            index.nprobe = f["nprobe"]
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwSq':
+            import torch                             # never sharded: every rank of a process group loads the whole file
+            f = faiss_io.read_ivf_sq_ip(index_fn)
+            nlist, d = f["centroids"].shape
+            index = IVFSQIPIndex(d, nlist)
+            index.set_centroids(f["centroids"])
+            index.set_trained(f["trained"][:d], f["trained"][d:])
             index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
             index.nprobe = f["nprobe"]
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':

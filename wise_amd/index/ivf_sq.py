@@ -1,0 +1,167 @@
+"""faiss-shaped IVF index (inner product) whose lists hold one byte per dimension: 8-bit scalar-quantized residuals.
+
+Stands where `faiss.IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist, faiss.ScalarQuantizer.QT_8bit, METRIC_INNER_PRODUCT)`
+stands (by_residual = True, the faiss default; index type 'IndexIVFSQ8').  HBM holds N * (d + 8) bytes of codes and ids, the
+centroids [nlist, d] and one range per dimension (vmin, vdiff: 8 d bytes) — no codebooks, no per-query table, no second copy of
+the rows.  It is the one-byte-per-dimension point of the family: IndexIVFPQ<m> stops at m = 128 bytes per row because its
+per-query table is m KiB of LDS.
+
+  coarse stage        the CoarseQuantizer and ListStore of the other inverted-file types (ivf_common.py)
+  train(x)            coarse k-means, then vmin[i] = min r_i, vdiff[i] = max r_i - vmin[i] over the residuals r = x - c_l of the
+                      training rows (wise_sq_train): faiss's RS_minmax with argument 0, an exact reduction
+  add_with_ids(x,ids) code_i = clamp(floor((r_i - vmin[i]) * (255 / vdiff[i])), 0, 255) (wise_sq_encode), only the codes are kept.
+                      The formula is evaluated in float64, so a value inside the trained range lands in the bin it really
+                      falls into and decodes to within half a bin.  faiss computes (int)(255 * ((r - vmin) / vdiff)) in
+                      float32: the two differ only in rounding at a bin edge.  THE DECODER AND THE FILE ARE faiss's (Codec8bit, the 'IwSq' record of faiss_io.py)
+  search(q, k)        probes from the coarse stage, bias = q . c_l (wise_pq_bias), per query w[i] = q_i vdiff[i] / 255 and
+                      q0 = sum_i q_i (vmin[i] + vdiff[i] 0.5 / 255) (wise_sq_query), then wise_ivfsq_scan:
+                      score = (bias + q0) + sum_i w[i] * code_i in the order include/wise_hip.h fixes.  One stage: a selector
+                      (sel=) restricts the same scan (wise_ivfsq_scan_sel)
+  reconstruct_batch   decoded, hence approximate, as in faiss: c_l + vmin + vdiff (code + 0.5) / 255 (wise_sq_decode)
+What is exact and tested: given the same centroids, ranges and codes the scan equals a float32 restatement bit for bit
+(tests/ivfsq_ref.py), and so do the trainer, the encoder and the decoder.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from .. import _lib
+from .ivf_common import IVFIndexBase, _as_tensor, _ids_i64, _rows_f32
+
+MAX_D = 1024
+
+
+def check_sq_shape(d: int) -> None:
+    """The shapes wise_sq_* / wise_ivfsq_scan serve (include/wise_hip.h); ValueError otherwise."""
+    if d % 16 or d < 16 or d > MAX_D:
+        raise ValueError(f"IVFSQIPIndex: d={d} must be a multiple of 16 in [16, {MAX_D}] (a row is read in 16-byte loads)")
+
+
+def _gather_codes(codes: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """rows of d bytes (whole multiples of 16) moved as rows of d / 4 floats: the copy does not look at the values"""
+    out = torch.empty_like(codes)
+    _lib.check(_lib.lib().wise_ivf_gather_rows(codes.data_ptr(), idx.data_ptr(), idx.shape[0], codes.shape[1] // 4, out.data_ptr(),
+                                               _lib.stream_ptr()), "wise_ivf_gather_rows")
+    return out
+
+
+class IVFSQIPIndex(IVFIndexBase):
+    def __init__(self, d: int, nlist: int, device: str = "cuda"):
+        check_sq_shape(int(d))
+        super().__init__(d, nlist, device, width=int(d), dtype=torch.uint8, gather=_gather_codes)
+        self.trained: Optional[torch.Tensor] = None        # [2 d] fp32: vmin, then vdiff
+
+    @property
+    def is_trained(self) -> bool:
+        return self._coarse.is_trained and self.trained is not None
+
+    def hbm_bytes(self) -> int:
+        """Bytes of HBM the index holds once its lists are merged: codes, ids, offsets, centroids, ranges."""
+        self._finalize()
+        return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.trained))
+
+    # -- training -------------------------------------------------------------------------------
+    def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().wise_pq_residuals(x.data_ptr(), self.centroids.data_ptr(), assign.data_ptr(), x.shape[0], self.d,
+                                                self.nlist, out.data_ptr(), _lib.stream_ptr()), "wise_pq_residuals")
+        return out
+
+    def train(self, x) -> None:
+        x = _rows_f32(x, self.d, "train")
+        self._coarse.train(x)
+        x = x.to(self.device, torch.float32).contiguous()
+        resid = self._residuals(x, self._coarse.assign_device(x, self.centroids))
+        trained = torch.empty(2 * self.d, dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().wise_sq_train(resid.data_ptr(), resid.shape[0], self.d, trained.data_ptr(), _lib.stream_ptr()),
+                   "wise_sq_train")
+        self.trained = trained
+
+    def set_trained(self, vmin, vdiff) -> None:
+        """Install trained ranges, vmin [d] and vdiff [d] (file load, tests)."""
+        vmin, vdiff = _as_tensor(vmin, np.float32), _as_tensor(vdiff, np.float32)
+        if tuple(vmin.shape) != (self.d,) or tuple(vdiff.shape) != (self.d,):
+            raise ValueError(f"set_trained: expected vmin [{self.d}] and vdiff [{self.d}]")
+        self.trained = torch.cat([vmin.to(self.device, torch.float32), vdiff.to(self.device, torch.float32)]).contiguous()
+
+    # -- construction ---------------------------------------------------------------------------
+    def _encode(self, resid: torch.Tensor) -> torch.Tensor:
+        codes = torch.empty(resid.shape[0], self.d, dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.lib().wise_sq_encode(resid.data_ptr(), self.trained.data_ptr(), resid.shape[0], self.d, codes.data_ptr(),
+                                             _lib.stream_ptr()), "wise_sq_encode")
+        return codes
+
+    def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IVFSQIPIndex: train() before add_with_ids()")
+        x = _rows_f32(x, self.d, "add_with_ids")
+        ids = _ids_i64(ids, x.shape[0])
+        for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
+            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
+            a = self._coarse.assign_device(xs, self.centroids)
+            self._lists.append(self._encode(self._residuals(xs, a)), ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a)
+
+    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> "IVFSQIPIndex":
+        """Take codes that are already grouped by list (file load)."""
+        if codes.dim() != 2 or codes.shape[1] != self.d:
+            raise ValueError(f"adopt_lists: expected codes [n,{self.d}]")
+        self._lists.adopt(codes, ids, list_off)
+        return self
+
+    # -- search ---------------------------------------------------------------------------------
+    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, keep: Optional[torch.Tensor]) -> None:
+        lib = _lib.lib()
+        nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
+        need = lib.wise_ivfsq_scan_workspace_bytes(n, nprobe, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k}")
+        ws = self._workspace(need)
+        probes = self._coarse.probes_device(qs, nprobe).contiguous()
+        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
+                                    bias.data_ptr(), st), "wise_pq_bias")
+        W = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
+        q0 = torch.empty(n, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), n, self.d, W.data_ptr(), q0.data_ptr(), st), "wise_sq_query")
+        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, ls.ids.data_ptr(), W.data_ptr(), q0.data_ptr(), n,
+                probes.data_ptr(), bias.data_ptr(), nprobe, k)
+        tail = (D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        if keep is not None:
+            _lib.check(lib.wise_ivfsq_scan_sel(*head, keep.data_ptr(), *tail), "wise_ivfsq_scan_sel")
+        else:
+            _lib.check(lib.wise_ivfsq_scan(*head, *tail), "wise_ivfsq_scan")
+
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
+        """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
+        q = self._queries(q)
+        keep = self._keep(sel)
+        nq = q.shape[0]
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        for s in range(0, nq, chunk):                    # bounds the workspace: chunk * nprobe * k keys
+            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], keep)
+        return D, I
+
+    # -- the rest of the surface the REST layer touches -------------------------------------------
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """Decoded rows (approximate, as faiss's): centroid of the row's list + the bin centres; NaN for an unknown id."""
+        lib = _lib.lib()
+        self._finalize()
+        st, ls = _lib.stream_ptr(), self._lists
+        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
+        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
+        _lib.check(lib.wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
+        out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_sq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
+                                      self.centroids.data_ptr(), self.trained.data_ptr(), self.d, out.data_ptr(), st), "wise_sq_decode")
+        return out.cpu().numpy()
+
+    def lists_host(self):
+        """(centroids [nlist,d], trained [2d] = vmin then vdiff, codes [N,d] uint8, ids [N], list_off [nlist+1]) as numpy."""
+        self._finalize()
+        ls = self._lists
+        return (self.centroids.cpu().numpy(), self.trained.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(),
+                ls.list_off.cpu().numpy())
