@@ -38,7 +38,8 @@ const char* wise_last_error(void);
  * wise_ivf_refine_local, the last two stages on one rank's slice of an index sharded across GPUs; and wise_opq_rotate,
  * wise_opq_corr (with wise_opq_corr_workspace_bytes) and wise_opq_decode, the learned rotation of IndexIVFOPQ<m>; and
  * wise_sel_bitmap, wise_sel_positions (with wise_sel_positions_workspace_bytes), wise_ip_topk_pos_f32, wise_ivf_scan_sel_f32 and
- * wise_ivfpq_scan_sel, the searches restricted to a set of ids. */
+ * wise_ivfpq_scan_sel, the searches restricted to a set of ids; and the wise_sq_* entry points with wise_ivfsq_scan,
+ * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -377,6 +378,27 @@ int wise_ivfsq_scan(const uint8_t* codes, int64_t N, int d, const int64_t* list_
 int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* W,
                         const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, const uint32_t* keep,
                         float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+/* (ABI 5, additive) wise_ivfsq_scan on ONE RANK's slice of a list-major IndexIVFSQ8 sharded across GPUs (rank r holds rows
+ * shard_range(N_total, r, W) of the lists laid end to end; wise_amd/index/sharded.py) — what wise_ivfpq_scan_local is to
+ * wise_ivfpq_scan:
+ *   codes, ids  [N,d] / [N] this rank's rows (ids are the global external ids);  pos_base >= 0: the position of its first row
+ *   list_off    [nlist+1] the global offsets clipped to the slice (lists outside it are empty)
+ *   probes, bias  [nq,nprobe] GLOBAL list numbers and their bias;  W, q0 from wise_sq_query (the coarse stage and the ranges are
+ *               replicated on every rank)
+ * Probes whose clipped list is empty are dropped on the device first, in probe order, together with their bias; probe_count [nq]
+ * (optional) receives the number kept per query.  The kept probes are dealt evenly to as many probe groups as they fill — one each,
+ * as the whole scan gives every probe a workgroup — and a workgroup without a group returns before it loads the query's weight
+ * row, so a rank pays for the ~nprobe / W lists it holds.  The score's arithmetic and its order are wise_ivfsq_scan's; a list cut
+ * by a slice boundary scores its rows exactly as the whole scan does (d % 16 == 0: every slice starts 16-byte aligned, and a row's
+ * chunks do not depend on where its list begins).  With ids == NULL outI holds pos_base + the local position (a position in the
+ * WHOLE array).  Ties: the row that comes first in codes wins.  wise_topk_merge of the ranks' answers in rank order gives the bits
+ * of wise_ivfsq_scan over the whole array, ties and padding included.  Limits and errors as wise_ivfsq_scan (N < 2^32 - 1 is the
+ * slice's), and pos_base >= 0.  Workspace: wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k) bytes (0: unsupported shape); a
+ * shorter one is WISE_E_INVALID.  Nothing is allocated and nothing is read back: the call can be captured into a graph. */
+size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int k);
+int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* W,
+                          const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, int64_t pos_base,
+                          float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

@@ -137,6 +137,8 @@ SIGNATURES = {
     "wise_ivfsq_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "wise_ivfsq_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfsq_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq_scan_local_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wise_ivfsq_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wise_mlp_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "wise_mlp_stream_ln": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),

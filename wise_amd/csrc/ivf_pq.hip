@@ -18,11 +18,11 @@
 // random ds_read_b32 (bank conflicts are inherent to the method).  Selection is the flat scan's: sortable (score, position)
 // keys against per-wave threshold lists, folded per block, then merge_keys_kernel.
 //   wise_ivfpq_scan_local  the same scan on ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to the
-//                       slice: about nprobe / W of a query's probes hold rows there).  compact_probes_bias_kernel keeps those
+//                       slice: about nprobe / W of a query's probes hold rows there).  compact_probes_bias_kernel (probe_compact.h) keeps those
 //                       probes and their bias, in probe order, and from the kept count fixes how many probe groups the query
 //                       uses; a block past that number returns before it touches the table, the others share the kept probes
 //                       evenly.  Same kernel body as the whole-index scan (pq_scan_kernel<VEC, true>).
-#include "topk_common.h"
+#include "probe_compact.h"
 
 namespace wise {
 namespace ivf_pq {
@@ -169,35 +169,7 @@ __device__ __forceinline__ float pq_row_score(const unsigned char* __restrict__ 
 // saves is table traffic (m KiB per group) only.  1 = a group exists exactly when it has a probe with rows to scan: the
 // table is then copied once per kept probe at most — nprobe / W times instead of nprobe times — and the slowest block never
 // has more kept probes than the slowest block of the whole-index kernel run over the clipped offsets.
-constexpr int LOCAL_MIN_SHARE = 1;
-
-// one wave per query (wise_ivfpq_scan_local): keep, in probe order, the probes whose list holds rows in this slice together
-// with their bias; count[q] = the number kept, used[q] = min(G, ceil(count / LOCAL_MIN_SHARE)) = the probe groups the query uses
-__global__ __launch_bounds__(64) void compact_probes_bias_kernel(const long long* __restrict__ probes, const float* __restrict__ bias,
-                                                                 int nprobe, const long long* __restrict__ list_off, int nlist, int G,
-                                                                 long long* __restrict__ out, float* __restrict__ out_bias,
-                                                                 int* __restrict__ count, int* __restrict__ used) {
-    const int lane = threadIdx.x;
-    const size_t base = (size_t)blockIdx.x * nprobe;
-    int n = 0;
-    for (int i0 = 0; i0 < nprobe; i0 += 64) {
-        const int i = i0 + lane;
-        const long long l = (i < nprobe) ? probes[base + i] : -1;
-        const bool keep = l >= 0 && l < nlist && list_off[l + 1] > list_off[l];
-        const u64 mask = __ballot(keep);
-        if (keep) {
-            const int o = n + __popcll(mask & ((1ull << lane) - 1ull));
-            out[base + o] = l;
-            out_bias[base + o] = bias[base + i];
-        }
-        n += __popcll(mask);
-    }
-    if (lane == 0) {
-        const int want = (n + LOCAL_MIN_SHARE - 1) / LOCAL_MIN_SHARE;
-        count[blockIdx.x] = n;
-        used[blockIdx.x] = want < G ? want : G;
-    }
-}
+constexpr int LOCAL_MIN_SHARE = 1;      // min_share of compact_probes_bias_kernel (probe_compact.h)
 
 // grid (G, nq): block (g, q) scans probes [g * per, (g + 1) * per) of query q; its k keys go to part[g][q][:]
 // LOCAL (wise_ivfpq_scan_local): probes / bias are the compacted ones, count[q] of them live, dealt evenly to used[q] groups;
@@ -515,7 +487,7 @@ extern "C" int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, con
     int* count = probe_count ? probe_count : reinterpret_cast<int*>(wsb);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
     hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
-                       nlist, s.groups, live, lbias, count, used);
+                       nlist, s.groups, LOCAL_MIN_SHARE, live, lbias, count, used);
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
     if (m % 16 == 0) launch_pq_scan<16, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
     else if (m % 8 == 0) launch_pq_scan<8, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);

@@ -18,7 +18,14 @@
 // for i = 0 .. 15; then for step = 1, 2, 4, ... < C every lane with c + step < C adds the value lane c + step held BEFORE the
 // step (s_c = s_c + s_{c + step}); chunk 0 then holds the row's sum and score = (bias + q0) + s_0.  No packed f32 math.
 // Selection is the flat scan's: sortable (score, position) keys, per-wave threshold lists, merge_keys_kernel.
-#include "topk_common.h"
+//   wise_ivfsq_scan_local  the same scan on ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to the
+//                    slice: about nprobe / W of a query's probes hold rows there).  compact_probes_bias_kernel (probe_compact.h)
+//                    keeps those probes and their bias, in probe order; every kept probe is a probe group of its own, as every
+//                    probe is a block of the whole scan, and a block past the kept count returns before it loads a weight.  A
+//                    block's work on its list is sq_scan_list, the one body of all three kernels: a list cut by the slice scores
+//                    its rows as the whole scan does, because a row's chunks and lanes depend on d alone and d % 16 == 0 keeps
+//                    every row of a slice 16-byte aligned.
+#include "probe_compact.h"
 
 namespace wise {
 namespace ivf_sq {
@@ -147,26 +154,19 @@ __device__ __forceinline__ float chain_word(float s, unsigned word, const float4
     return s;
 }
 
-// grid = nq * nprobe: block b scans the list probes[b] of query b / nprobe; its k keys go to part[(b % nprobe) * nq + b / nprobe]
+// One block's scan of the rows [lo, hi) of codes under the weight row wrow [d]: score = base + s_0; the k best keys go to dst.
 // SEL: only the rows whose bit of `keep` is set are offered; a wave whose SQ_T loads hold no such row skips them (wave-uniform)
 template <bool SEL>
-__global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
-                                                      int nlist, const float* __restrict__ W, const float* __restrict__ q0,
-                                                      const long long* __restrict__ probes, const float* __restrict__ bias, int nprobe,
-                                                      int nq, int d, int k, int cap, u64* __restrict__ part,
-                                                      const unsigned* __restrict__ keep) {
+__device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ codes, long long lo, long long hi,
+                                             const float* __restrict__ wrow, float base, int d, int k, int cap, u64* __restrict__ dst,
+                                             const unsigned* __restrict__ keep) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
-    const long long l = probes[(size_t)qi * nprobe + pi];
-    long long lo = 0, hi = 0;
-    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }          // block-uniform
     const int C = d >> 4, RPL = 64 / C;
     const int sub = lane / C, c = lane - sub * C;
     const bool active = sub < RPL;
-    const float4* wq = reinterpret_cast<const float4*>(W + (size_t)qi * d + 16 * c);
+    const float4* wq = reinterpret_cast<const float4*>(wrow + 16 * c);
     const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
-    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
 
     WaveList wl;
     wl.init(reinterpret_cast<u64*>(smem) + (size_t)wave * cap, cap, k, lane);
@@ -229,9 +229,43 @@ __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __res
             }
         }
         wl.compact(lane);
-        u64* dst = part + ((size_t)pi * nq + qi) * k;
         for (int i = lane; i < k; i += 64) dst[i] = wl.buf[i];
     }
+}
+
+// grid = nq * nprobe: block b scans the list probes[b] of query b / nprobe; its k keys go to part[(b % nprobe) * nq + b / nprobe]
+template <bool SEL>
+__global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
+                                                      int nlist, const float* __restrict__ W, const float* __restrict__ q0,
+                                                      const long long* __restrict__ probes, const float* __restrict__ bias, int nprobe,
+                                                      int nq, int d, int k, int cap, u64* __restrict__ part,
+                                                      const unsigned* __restrict__ keep) {
+    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
+    const long long l = probes[(size_t)qi * nprobe + pi];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }          // block-uniform
+    sq_scan_list<SEL>(codes, lo, hi, W + (size_t)qi * d, bias[(size_t)qi * nprobe + pi] + q0[qi], d, k, cap,
+                      part + ((size_t)pi * nq + qi) * k, keep);
+}
+
+// wise_ivfsq_scan_local.  grid = nq * nprobe: block b is probe group b / nq of query b % nq — group-major, so the blocks that
+// have a group are the first ones of the grid and follow each other: workgroups go to the XCDs round-robin by number, and with
+// the groups innermost the few live blocks of every query (numbers q * nprobe + 0 .. used - 1) would land on the same few XCDs.
+// probes / bias are the compacted ones (compact_probes_bias_kernel with G = nprobe and a share of 1: used[q] = the probes kept =
+// the groups of query q, one kept probe each); a block past used[q] returns BEFORE it loads the query's weight row, and its slot
+// of part is never read: the merge folds used[q] lists.  list_off is clipped to the slice, rows are positions in the slice.
+__global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
+                                                            int nlist, const float* __restrict__ W, const float* __restrict__ q0,
+                                                            const long long* __restrict__ probes, const float* __restrict__ bias,
+                                                            int nprobe, int nq, int d, int k, int cap, u64* __restrict__ part,
+                                                            const int* __restrict__ used) {
+    const int g = blockIdx.x / nq, qi = blockIdx.x - g * nq;
+    if (g >= used[qi]) return;                                                      // block-uniform
+    const long long l = probes[(size_t)qi * nprobe + g];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }
+    sq_scan_list<false>(codes, lo, hi, W + (size_t)qi * d, bias[(size_t)qi * nprobe + g] + q0[qi], d, k, cap,
+                        part + ((size_t)g * nq + qi) * k, nullptr);
 }
 
 static bool scan_shape_ok(int nq, int nprobe, int k) {
@@ -299,6 +333,18 @@ extern "C" size_t wise_ivfsq_scan_workspace_bytes(int nq, int nprobe, int k) {
     return align_up((size_t)nq * nprobe * k * sizeof(u64), 256);
 }
 
+// Workspace of the rank-local scan: the keys [nprobe][nq][k], then the kept probes [nq][nprobe], their bias, the groups used per
+// query and (for a call without probe_count) the kept counts
+static size_t local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
+static size_t local_bias_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(float), 256); }
+static size_t local_count_bytes(int nq) { return align_up((size_t)nq * sizeof(int), 256); }
+
+extern "C" size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int k) {
+    const size_t part = wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
+    if (part == 0) return 0;
+    return part + local_probe_bytes(nq, nprobe) + local_bias_bytes(nq, nprobe) + 2 * local_count_bytes(nq);
+}
+
 // wise_ivfsq_scan and, with keep, wise_ivfsq_scan_sel
 static int sq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                         const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
@@ -337,4 +383,43 @@ extern "C" int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const
     WISE_CHECK_ARG(keep || N == 0, "ivfsq_scan_sel: null bitmap");
     return sq_scan_impl("ivfsq_scan_sel", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
                         workspace_bytes, stream, keep);
+}
+
+extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
+                                     int k, int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    SQ_CHECK_SHAPE("ivfsq_scan_local");
+    WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "ivfsq_scan_local: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)",
+                   nq, nprobe, k);
+    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "ivfsq_scan_local: N=%lld nlist=%d pos_base=%lld out of range",
+                   (long long)N, nlist, (long long)pos_base);
+    WISE_CHECK_ARG(W && q0 && probes && bias && outD && outI && list_off && (codes || N == 0), "ivfsq_scan_local: null pointer");
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "ivfsq_scan_local: codes and W must be 16-byte aligned");
+    const size_t need = wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k);
+    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "ivfsq_scan_local: workspace %zu < %zu bytes", workspace_bytes, need);
+    hipStream_t st = (hipStream_t)stream;
+    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
+    u64* part = reinterpret_cast<u64*>(wsb);
+    wsb += wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
+    long long* live = reinterpret_cast<long long*>(wsb);
+    wsb += local_probe_bytes(nq, nprobe);
+    float* lbias = reinterpret_cast<float*>(wsb);
+    wsb += local_bias_bytes(nq, nprobe);
+    int* used = reinterpret_cast<int*>(wsb);
+    wsb += local_count_bytes(nq);
+    int* count = probe_count ? probe_count : reinterpret_cast<int*>(wsb);
+    const long long* lo = reinterpret_cast<const long long*>(list_off);
+    hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
+                       nlist, nprobe, 1, live, lbias, count, used);
+    WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
+    const int cap = topk_list_cap(k);
+    const size_t lds = (size_t)4 * cap * 8;
+    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel), (int)lds);
+    hipLaunchKernelGGL(sq_scan_local_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, codes, lo, nlist, W, q0, live,
+                       lbias, nprobe, nq, d, k, cap, part, used);
+    WISE_LAUNCH_CHECK("sq_scan_local_kernel");
+    // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
+    return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
+                              used, (long long)pos_base);
 }

@@ -56,7 +56,7 @@ The file of index type 'IndexIVFSQ8' (write_ivf_sq_ip / read_ivf_sq_ip) restates
     u64  code_size (= d) | u8 by_residual (1)
     'ilar' array inverted lists with code_size = d: per non-empty list u8 codes[size*d] | i64 ids[size]
 
-Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' file
+Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' / 'IwSq' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
 
@@ -709,6 +709,57 @@ def read_ivf_sq_ip(path):
                 raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
             codes[a:b], ids[a:b] = c.reshape(b - a, d), i
     return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+
+
+def ivf_sq_ip_ntotal(path) -> int:
+    """Rows of an 'IwSq' file (its header), without reading the lists."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        (cc,) = struct.unpack("<I", f.read(4))
+        if cc != _fourcc("IwSq"):
+            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFScalarQuantizer")
+        return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+
+
+def read_ivf_sq_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major arrays read_ivf_sq_ip returns, reading only the lists that overlap the range (one rank's
+    slice of an index sharded across GPUs: wise_amd/index/sharded.py).  -> the dict of read_ivf_sq_ip with codes [hi-lo,d],
+    ids [hi-lo] and list_off = clip(list_off - lo, 0, hi - lo); centroids and trained are whole.  List l's payload sits at
+    list_off[l] * (d + 8) bytes into the payload (codes, then ids)."""
+    p = Path(path)
+    if not p.exists():
+        raise _missing(p)
+    with open(p, "rb") as f:
+        try:
+            centroids, list_off, nprobe, data, trained = _read_ivf_head(f, p, sq=True)
+        except (struct.error, ValueError) as e:
+            raise RuntimeError(f"{p}: the head of an IndexIVFScalarQuantizer file is cut short ({e})") from None
+        n, d = int(list_off[-1]), centroids.shape[1]
+        lo, hi = int(lo), int(hi)
+        if not (0 <= lo <= hi <= n):
+            raise ValueError(f"read_ivf_sq_ip_range: [{lo}, {hi}) outside [0, {n}]")
+        codes = np.empty((hi - lo, d), dtype=np.uint8)
+        ids = np.empty((hi - lo,), dtype=np.int64)
+        first = int(np.searchsorted(list_off, lo, side="right")) - 1         # the list that holds row lo
+        for l in range(max(first, 0), len(list_off) - 1):
+            s0, s1 = int(list_off[l]), int(list_off[l + 1])
+            if s0 >= hi:
+                break
+            a, b = max(s0, lo), min(s1, hi)
+            if a >= b:
+                continue
+            base = data + s0 * (d + 8)
+            f.seek(base + (a - s0) * d)
+            c = np.fromfile(f, dtype=np.uint8, count=(b - a) * d)
+            f.seek(base + (s1 - s0) * d + (a - s0) * 8)
+            i = np.fromfile(f, dtype=np.int64, count=b - a)
+            if c.size != (b - a) * d or i.size != b - a:
+                raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
+            codes[a - lo:b - lo], ids[a - lo:b - lo] = c.reshape(b - a, d), i
+    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
+            "nprobe": nprobe}
 
 
 def index_fourcc(path) -> str:

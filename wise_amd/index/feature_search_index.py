@@ -56,8 +56,14 @@ ivf_pq.py: IVFOPQIPIndex, IVFOPQRefineIPIndex); their file wraps the PQ record i
 rotation, which is broadcast with the codebooks; each rank rotates its own rows and, in a search, the query — the rotation is
 replicated, so the sharded classes and their exchanges are the same.
 `IndexIVFSQ8` is the inverted file over one byte per dimension (faiss's IndexIVFScalarQuantizer, QT_8bit; ivf_sq.py: IVFSQIPIndex;
-file: faiss's 'IwSq' record, faiss_io.py).  It is not sharded: under a process group, with or without WISE_SHARDED_IVF, rank 0
-builds the one file and every rank loads it, as IndexIVFFlat does without the switch.
+file: faiss's 'IwSq' record, faiss_io.py).  Under a process group it behaves as the types above: without WISE_SHARDED_IVF=1 rank 0
+builds the one file and every rank loads it; with it
+  * `create_index`: the same collective build.  Rank 0 trains the coarse stage AND the per-dimension ranges on the seeded sample
+    the single-file build draws; the [2d] ranges are broadcast with the centroids; each rank assigns and encodes its own rows on
+    its GPU; the payload that travels is the row's d code bytes; each rank writes a complete 'IwSq' part with clipped lists.  The
+    parts laid end to end are the codes, ids and offsets of the one-process build, byte for byte;
+  * `load_index`: parts or ranges of the single file, decided once for the group as for IndexIVFPQ; `self.index` is a
+    `ShardedIVFSQIPIndex` (one exchange per search) that returns the bits of the one-GPU index.
 """
 import os
 from pathlib import Path
@@ -75,7 +81,7 @@ from .ivf_sq import IVFSQIPIndex, check_sq_shape
 from .search_index import SearchIndex
 from .selector import SearchParameters, as_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
-                      shard_range)
+                      ShardedIVFSQIPIndex, shard_range)
 
 
 def _dist_rank_world():
@@ -167,6 +173,7 @@ class FeatureSearchIndex(SearchIndex):
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
     ivfopq_index_factory = IVFOPQIPIndex
     ivfopq_refine_index_factory = IVFOPQRefineIPIndex
+    ivfsq_index_factory = IVFSQIPIndex
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -200,7 +207,7 @@ class FeatureSearchIndex(SearchIndex):
         refine = parse_refine(index_type)
         is_pq = parse_m(index_type) is not None or refine is not None
         is_sq = index_type == 'IndexIVFSQ8'
-        sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq) and _sharded_ivf_on()
+        sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq or is_sq) and _sharded_ivf_on()
         if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
         exists = index_fn.exists()
@@ -246,7 +253,7 @@ class FeatureSearchIndex(SearchIndex):
             n += m
         if sharded_ivf:
             self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world, index_type=index_type, pq_m=pq_m,
-                                     kind=kind if refine is not None else None, opq=opq)
+                                     kind=kind if refine is not None else None, opq=opq, sq=is_sq)
             print(f'  saved index part to {index_fn}')
             return
         if index_type == 'IndexIVFFlat' or is_pq or is_sq:
@@ -292,11 +299,12 @@ class FeatureSearchIndex(SearchIndex):
             faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
         print(f'  saved index to {index_fn}')
 
-    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None, opq=False):
+    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None, opq=False, sq=False):
         """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows.  What travels to the
         rank that owns a row's position is a per-row byte payload: the fp32 row (IndexIVFFlat), or the row's codes followed by its
         compact row and scale (pq_m / kind given: IndexIVFPQ<m>, IndexIVFPQ<m>R<kind>), encoded where the row was read.  opq: the
-        IndexIVFOPQ forms of the two — rank 0 also trains the rotation, which is broadcast with the codebooks."""
+        IndexIVFOPQ forms of the two — rank 0 also trains the rotation, which is broadcast with the codebooks.  sq: IndexIVFSQ8 —
+        rank 0 also trains the [2d] ranges, which are broadcast with the centroids; the payload is the row's d code bytes."""
         import torch
         import torch.distributed as dist
 
@@ -319,6 +327,8 @@ class FeatureSearchIndex(SearchIndex):
             ivf = (self.ivfopq_refine_index_factory if opq else self.ivfpq_refine_index_factory)(d, cell_count, pq_m, kind)
         elif pq_m is not None:
             ivf = (self.ivfopq_index_factory if opq else self.ivfpq_index_factory)(d, cell_count, pq_m)
+        elif sq:
+            ivf = self.ivfsq_index_factory(d, cell_count)
         else:
             ivf = self.ivf_index_factory(d, cell_count)
         if rank == 0:                               # k-means once, on rank 0; the centroids' bits go to every rank
@@ -330,7 +340,7 @@ class FeatureSearchIndex(SearchIndex):
                     dist.recv(buf, src=src)
                     parts.append(buf.cpu().numpy())
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
-            ivf.train(np.concatenate(parts))        # the coarse stage, then (IndexIVFPQ) the codebooks on its residuals
+            ivf.train(np.concatenate(parts))        # the coarse stage, then (IndexIVFPQ / SQ8) the codebooks / ranges on its residuals
             c = ivf.centroids if torch.is_tensor(ivf.centroids) else torch.from_numpy(np.asarray(ivf.centroids))
             c = c.to(dev, torch.float32).contiguous()
         else:
@@ -360,12 +370,22 @@ class FeatureSearchIndex(SearchIndex):
             dist.broadcast(rot, src=0)
             rotation = rot.cpu().numpy()
             ivf.set_rotation(rotation)
+        trained = None
+        if sq:                                      # ... and, IndexIVFSQ8, the ranges': vmin [d], then vdiff [d]
+            if rank == 0:
+                tr = ivf.trained if torch.is_tensor(ivf.trained) else torch.from_numpy(np.asarray(ivf.trained))
+                tr = tr.to(dev, torch.float32).contiguous()
+            else:
+                tr = torch.empty(2 * d, dtype=torch.float32, device=dev)
+            dist.broadcast(tr, src=0)
+            trained = tr.cpu().numpy()
+            ivf.set_trained(trained[:d], trained[d:])
         # each rank assigns (and encodes) its own rows; the per-rank list counts fix the global list-major order
-        if pq_m is None:
+        if pq_m is None and not sq:
             a = ivf.assign(X)
             fields = [X]
         else:
-            a, *fields = ivf.encode_rows(X)         # codes [n,m] u8 (+ compact rows [n,d] i8 / bf16 bits, scales [n] f32)
+            a, *fields = ivf.encode_rows(X)         # codes [n,m] u8 (+ compact rows [n,d] i8 / bf16 bits, scales [n] f32); SQ8: [n,d] u8
             a = np.asarray(a, dtype=np.int64)
         # a row's payload: its fields' bytes back to back, padded to whole int32
         widths = [int(np.prod(f.shape[1:], dtype=np.int64)) * f.dtype.itemsize for f in fields]
@@ -423,6 +443,8 @@ class FeatureSearchIndex(SearchIndex):
                                             loc[2] if kind == 8 else None, nprobe=ivf.nprobe)
         elif pq_m is not None:
             faiss_io.write_ivf_pq_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
+        elif sq:
+            faiss_io.write_ivf_sq_ip(part_fn, centroids, trained, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
         else:
             faiss_io.write_ivf_flat_ip(part_fn, centroids, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
 
@@ -463,16 +485,33 @@ class FeatureSearchIndex(SearchIndex):
         local.nprobe = f["nprobe"]
         return wrapper(local, merge=getattr(local, 'merge_lists', None), always_exchange=always)
 
-    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world, opq=False):
-        """The sharded load of the IndexIVFPQ family: all ranks read their part files, or all ranks read their range of the
-        single file — decided once for the group."""
+    def _sharded_ivfsq_index(self, f, pos_base):
+        """ShardedIVFSQIPIndex around a local index holding the slice `f` (a read_ivf_sq_ip(_range) dict) that starts at
+        position pos_base of the whole list-major array."""
+        import torch
+
+        nlist, d = f["centroids"].shape
+        local = self.ivfsq_index_factory(d, nlist)
+        local.set_centroids(f["centroids"])
+        local.set_trained(f["trained"][:d], f["trained"][d:])
+        local.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), pos_base=int(pos_base))
+        local.nprobe = f["nprobe"]
+        return ShardedIVFSQIPIndex(local, merge=getattr(local, 'merge_lists', None),
+                                   always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
+
+    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world, opq=False, sq=False):
+        """The sharded load of the IndexIVFPQ family and (sq) of IndexIVFSQ8: all ranks read their part files, or all ranks read
+        their range of the single file — decided once for the group."""
         import torch
         import torch.distributed as dist
 
         dev = _coll_device()
         flag = torch.tensor([int(part_fn.exists())], dtype=torch.int64, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        if opq:
+        wrap = self._sharded_ivfsq_index if sq else self._sharded_ivfpq_index
+        if sq:
+            read, read_range, ntotal = faiss_io.read_ivf_sq_ip, faiss_io.read_ivf_sq_ip_range, faiss_io.ivf_sq_ip_ntotal
+        elif opq:
             read, read_range, ntotal = faiss_io.read_ivf_opq_ip, faiss_io.read_ivf_opq_ip_range, faiss_io.ivf_opq_ip_ntotal
         elif refine:
             read, read_range, ntotal = faiss_io.read_ivf_pq_refine_ip, faiss_io.read_ivf_pq_refine_ip_range, faiss_io.ivf_pq_refine_ip_ntotal
@@ -482,13 +521,13 @@ class FeatureSearchIndex(SearchIndex):
             f = read(part_fn)
             ns = torch.zeros(world, dtype=torch.int64, device=dev)   # a part starts where the lower ranks' parts end
             dist.all_gather_into_tensor(ns, torch.tensor([f["codes"].shape[0]], dtype=torch.int64, device=dev))
-            return self._sharded_ivfpq_index(f, int(ns.cpu().numpy()[:rank].sum()))
+            return wrap(f, int(ns.cpu().numpy()[:rank].sum()))
         if not index_fn.exists():
             have = 'this rank has its part' if part_fn.exists() else 'this rank has no part'
             raise RuntimeError(f'{index_fn}: the part files of {world} ranks are not complete ({have}: {part_fn.name}) and there is '
                                f'no single file to read every rank\'s rows from; parts and a single file are never mixed')
         lo, hi = shard_range(ntotal(index_fn), rank, world)
-        return self._sharded_ivfpq_index(read_range(index_fn, lo, hi), lo)
+        return wrap(read_range(index_fn, lo, hi), lo)
 
     def is_index_loaded(self):
         return hasattr(self, 'index')
@@ -505,6 +544,8 @@ class FeatureSearchIndex(SearchIndex):
         refine = parse_refine(index_type) is not None
         if sharded and _sharded_ivf_on() and (refine or parse_m(index_type) is not None):
             index = self._load_sharded_ivfpq(index_fn, part_fn, refine, rank, world, opq)
+        elif sharded and _sharded_ivf_on() and index_type == 'IndexIVFSQ8':
+            index = self._load_sharded_ivfpq(index_fn, part_fn, False, rank, world, sq=True)
         elif sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip(part_fn))      # built by this many ranks
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
@@ -546,7 +587,7 @@ class FeatureSearchIndex(SearchIndex):
             index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
             index.nprobe = f["nprobe"]
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwSq':
-            import torch                             # never sharded: every rank of a process group loads the whole file
+            import torch                             # unsharded: every rank of a process group loads the whole file
             f = faiss_io.read_ivf_sq_ip(index_fn)
             nlist, d = f["centroids"].shape
             index = IVFSQIPIndex(d, nlist)

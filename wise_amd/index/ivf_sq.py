@@ -20,6 +20,11 @@ per-query table is m KiB of LDS.
   reconstruct_batch   decoded, hence approximate, as in faiss: c_l + vmin + vdiff (code + 0.5) / 255 (wise_sq_decode)
 What is exact and tested: given the same centroids, ranges and codes the scan equals a float32 restatement bit for bit
 (tests/ivfsq_ref.py), and so do the trainer, the encoder and the decoder.
+
+Across GPUs (sharded.py: ShardedIVFSQIPIndex) an index holds ONE RANK's slice of the list-major arrays: all centroids and the
+ranges, list_off clipped to the slice, and `pos_base`, the position of its first row in the whole array.  `search_local_device`
+is then the rank's share of a search (wise_ivfsq_scan_local: only the probed lists the rank holds), `encode_rows` hands a rank's
+rows back as codes for the collective build, and `reconstruct_batch` decodes the ids the slice holds (NaN for the others).
 """
 from __future__ import annotations
 
@@ -53,6 +58,7 @@ class IVFSQIPIndex(IVFIndexBase):
         check_sq_shape(int(d))
         super().__init__(d, nlist, device, width=int(d), dtype=torch.uint8, gather=_gather_codes)
         self.trained: Optional[torch.Tensor] = None        # [2 d] fp32: vmin, then vdiff
+        self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
 
     @property
     def is_trained(self) -> bool:
@@ -104,18 +110,41 @@ class IVFSQIPIndex(IVFIndexBase):
             a = self._coarse.assign_device(xs, self.centroids)
             self._lists.append(self._encode(self._residuals(xs, a)), ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a)
 
-    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor) -> "IVFSQIPIndex":
-        """Take codes that are already grouped by list (file load)."""
+    def encode_rows(self, x, chunk: int = 1 << 18):
+        """(assign [n] int64, codes [n, d] uint8) as numpy for the rows x [n, d]: what add_with_ids would put into the lists,
+        handed back instead (the collective build moves it to the rank that owns the row's position)."""
+        if not self.is_trained:
+            raise RuntimeError("IVFSQIPIndex: train() before encode_rows()")
+        x = _rows_f32(x, self.d, "encode_rows")
+        assign = np.empty(x.shape[0], dtype=np.int64)
+        codes = np.empty((x.shape[0], self.d), dtype=np.uint8)
+        for s in range(0, x.shape[0], chunk):
+            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
+            a = self._coarse.assign_device(xs, self.centroids)
+            assign[s:s + xs.shape[0]] = a.cpu().numpy()
+            codes[s:s + xs.shape[0]] = self._encode(self._residuals(xs, a)).cpu().numpy()
+        return assign, codes
+
+    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, pos_base: int = 0) -> "IVFSQIPIndex":
+        """Take codes that are already grouped by list (file load).  pos_base: the codes are a slice of a larger list-major
+        array that starts at this position of it (list_off clipped to the slice)."""
         if codes.dim() != 2 or codes.shape[1] != self.d:
             raise ValueError(f"adopt_lists: expected codes [n,{self.d}]")
+        if pos_base < 0:
+            raise ValueError("adopt_lists: pos_base must not be negative")
         self._lists.adopt(codes, ids, list_off)
+        self.pos_base = int(pos_base)
         return self
 
     # -- search ---------------------------------------------------------------------------------
-    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, keep: Optional[torch.Tensor]) -> None:
+    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, keep: Optional[torch.Tensor], local: bool = False,
+              probe_count: Optional[torch.Tensor] = None, positions: bool = False) -> None:
+        """Coarse stage, bias, weights and the scan for the queries qs into D / I [n, k].  local: wise_ivfsq_scan_local — the
+        probes whose list is empty in this slice are dropped first (the number kept goes to probe_count when given); positions:
+        I then receives positions in the WHOLE array instead of external ids."""
         lib = _lib.lib()
         nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
-        need = lib.wise_ivfsq_scan_workspace_bytes(n, nprobe, k)
+        need = (lib.wise_ivfsq_scan_local_workspace_bytes if local else lib.wise_ivfsq_scan_workspace_bytes)(n, nprobe, k)
         if need == 0:
             raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k}")
         ws = self._workspace(need)
@@ -126,13 +155,16 @@ class IVFSQIPIndex(IVFIndexBase):
         W = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
         q0 = torch.empty(n, dtype=torch.float32, device=self.device)
         _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), n, self.d, W.data_ptr(), q0.data_ptr(), st), "wise_sq_query")
-        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, ls.ids.data_ptr(), W.data_ptr(), q0.data_ptr(), n,
-                probes.data_ptr(), bias.data_ptr(), nprobe, k)
-        tail = (D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st)
-        if keep is not None:
-            _lib.check(lib.wise_ivfsq_scan_sel(*head, keep.data_ptr(), *tail), "wise_ivfsq_scan_sel")
+        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(), W.data_ptr(),
+                q0.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
+        tail = (ws.data_ptr(), ws.numel(), st)
+        if local:
+            _lib.check(lib.wise_ivfsq_scan_local(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
+                       "wise_ivfsq_scan_local")
+        elif keep is not None:
+            _lib.check(lib.wise_ivfsq_scan_sel(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), "wise_ivfsq_scan_sel")
         else:
-            _lib.check(lib.wise_ivfsq_scan(*head, *tail), "wise_ivfsq_scan")
+            _lib.check(lib.wise_ivfsq_scan(*head, D.data_ptr(), I.data_ptr(), *tail), "wise_ivfsq_scan")
 
     def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
         """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
@@ -143,6 +175,24 @@ class IVFSQIPIndex(IVFIndexBase):
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         for s in range(0, nq, chunk):                    # bounds the workspace: chunk * nprobe * k keys
             self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], keep)
+        return D, I
+
+    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
+                            chunk: int = 1024):
+        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to
+        the slice, `pos_base` its first position; ShardedIVFSQIPIndex): the same coarse stage, bias and weights, then
+        wise_ivfsq_scan_local.  probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query.
+        positions: I receives positions in the WHOLE array instead of external ids."""
+        q = self._queries(q)
+        nq = q.shape[0]
+        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
+                                        or not probe_count.is_contiguous()):
+            raise ValueError("search_local_device: probe_count must be a contiguous int32 device tensor of nq entries")
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        for s in range(0, nq, chunk):
+            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], None, True,
+                       None if probe_count is None else probe_count[s:s + chunk], positions)
         return D, I
 
     # -- the rest of the surface the REST layer touches -------------------------------------------

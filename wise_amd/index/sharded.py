@@ -18,6 +18,10 @@ one-GPU answer, because the one-GPU index re-ranks the kc best positions of the 
 positions are gathered and merged into those global kc, (2) every rank re-ranks the ones that lie in its slice
 (wise_ivf_refine_local) and the ranks' k best are gathered and merged.  Re-ranking each rank's own kc would save a collective
 and return a different answer (a pool of W * kc).
+
+ShardedIVFSQIPIndex wraps a slice of an IndexIVFSQ8 (d code bytes per row, the centroids and the [2 d] ranges on every rank,
+wise_ivfsq_scan_local): one exchange, as ShardedIVFPQIPIndex.  reconstruct_batch is the flat wrapper's: the rank that holds an id
+decodes it (wise_sq_decode against its clipped offsets), the others answer NaN.
 """
 from __future__ import annotations
 
@@ -209,6 +213,15 @@ class ShardedIVFPQIPIndex(ShardedIVFFlatIPIndex):
     @property
     def is_trained(self) -> bool:
         return self.local.is_trained
+
+    def hbm_bytes(self) -> int:
+        """Of this rank's slice (local, not collective)."""
+        return self.local.hbm_bytes()
+
+
+class ShardedIVFSQIPIndex(ShardedIVFFlatIPIndex):
+    """Every rank constructs it around its own local IVFSQIPIndex holding a clipped slice of the list-major codes (all
+    centroids and the ranges, ids global, `pos_base` set).  One exchange per search, the flat wrapper's."""
 
     def hbm_bytes(self) -> int:
         """Of this rank's slice (local, not collective)."""
