@@ -39,7 +39,8 @@ const char* wise_last_error(void);
  * wise_opq_corr (with wise_opq_corr_workspace_bytes) and wise_opq_decode, the learned rotation of IndexIVFOPQ<m>; and
  * wise_sel_bitmap, wise_sel_positions (with wise_sel_positions_workspace_bytes), wise_ip_topk_pos_f32, wise_ivf_scan_sel_f32 and
  * wise_ivfpq_scan_sel, the searches restricted to a set of ids; and the wise_sq_* entry points with wise_ivfsq_scan,
- * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it. */
+ * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it; and the count / fill pairs of
+ * range_search, wise_ip_range_*, wise_ivf_range_* and wise_ivfsq_range_*.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -399,6 +400,55 @@ size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int k);
 int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* W,
                           const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, int64_t pos_base,
                           float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) range_search — faiss's Index::range_search for METRIC_INNER_PRODUCT: EVERY row with score > radius, strictly,
+ * instead of the k best.  One count / fill pair per family; a hit's score is, bit for bit, the score the family's fp32 scan gives
+ * that row (the same device routines in the same files): wise_ip_topk_pos_f32's single-pass VALU scan for wise_ip_range_*
+ * (lane l of 64 chains fmaf over the row's float4 chunks l, l + 64, ... from +0, then a butterfly over the lane masks 32 .. 1),
+ * wise_ivf_scan_f32's for wise_ivf_range_*, and the wise_ivfsq_scan contract above for wise_ivfsq_range_*.
+ *   radius    finite (NaN or infinite: WISE_E_INVALID); -3.4028235e38 makes every candidate row a hit
+ *   keep      optional bitmap over row positions, (N + 31) / 32 words as wise_sel_bitmap writes them: only the rows whose bit is
+ *             set can be hits; a load that holds no kept row is skipped.  NULL: every row may be a hit.  (The flat count pass
+ *             tests the bitmap too; it does not go through a position list.)
+ *   candidates  flat: the N rows of X.  Inverted-file: the rows of the lists probes [nq, nprobe] names, entries < 0 (or >= nlist)
+ *             and empty lists skipped, as in the scans; a list named twice by one query is reported twice.
+ *   count     writes counts [nq] int64 (device) and leaves in the workspace what fill needs, so that the rows are read in full
+ *             once: per query a hit bitmap (one bit per candidate position) and the hit count of every SEGMENT — 2048
+ *             consecutive rows of X (flat), one probed list (inverted-file) — turned into exclusive offsets by a scan.
+ *   fill      takes lims [nq + 1] int64 (device), the exclusive scan of counts (lims[0] = 0), the workspace count wrote and the
+ *             same other arguments, and writes query q's hits to outD / outI [lims[q], lims[q + 1]) in a FIXED order: ascending
+ *             position (flat); probe order, then ascending position within a list (inverted-file).  outI: ids[position], or with
+ *             ids == NULL id_base + position (flat) / the position (inverted-file).  Only the hit rows are read, and their
+ *             scores recomputed by the routine count used.  A caller whose counts are all 0 need not call it.
+ *   order     no atomic touches global memory and none decides where a hit lands: a hit's bit is set at its row's place (an LDS
+ *             OR, published as plain word stores), offsets come from popcounts and scans.  The same inputs give the same bytes.
+ *   neither call allocates or reads back; both can be captured into a graph.  The caller sizes outD / outI from counts.
+ * Limits, those of the family's scan: flat and wise_ivf_range_*: d % 4 == 0, 4 <= d <= 2048, X and Q 16-byte aligned;
+ * wise_ivfsq_range_*: d % 16 == 0, 16 <= d <= 1024, codes and W 16-byte aligned; all: 1 <= nq <= 65535, 1 <= nprobe <= 2048,
+ * 0 <= N < 2^32 - 1 (N = 0: all counts 0).  Anything else is WISE_E_INVALID with a wise_last_error text.
+ * Workspace: *_range_workspace_bytes bytes (0: unsupported shape); a shorter one is WISE_E_INVALID.  It grows with nq — about
+ * nq * (N / 8 + 8 * segments) bytes — so a caller with many queries runs them in chunks (wise_amd/index/range_search.py). */
+size_t wise_ip_range_workspace_bytes(int64_t N, int d, int nq);
+int wise_ip_range_count_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
+                            int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ip_range_fill_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
+                           int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t wise_ivf_range_workspace_bytes(int64_t N, int nlist, int nq, int nprobe);
+int wise_ivf_range_count_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                             const int64_t* probes, int nprobe, float radius, const uint32_t* keep, int64_t* counts,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivf_range_fill_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                            const float* Q, int nq, const int64_t* probes, int nprobe, float radius, const int64_t* lims,
+                            float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+size_t wise_ivfsq_range_workspace_bytes(int64_t N, int nlist, int nq, int nprobe);
+int wise_ivfsq_range_count(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                           const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                           const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfsq_range_fill(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                          const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
+                          float radius, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

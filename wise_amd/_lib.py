@@ -139,6 +139,15 @@ SIGNATURES = {
     "wise_ivfsq_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfsq_scan_local_workspace_bytes": (_sz, [_i, _i, _i]),
     "wise_ivfsq_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ip_range_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wise_ip_range_count_f32": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ip_range_fill_f32": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivf_range_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ivf_range_count_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivf_range_fill_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq_range_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ivfsq_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_swin_qkv_attn": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "wise_mlp_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "wise_mlp_stream_ln": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -26,6 +26,7 @@
 //                    its rows as the whole scan does, because a row's chunks and lanes depend on d alone and d % 16 == 0 keeps
 //                    every row of a slice 16-byte aligned.
 #include "probe_compact.h"
+#include "range_common.h"
 
 namespace wise {
 namespace ivf_sq {
@@ -154,6 +155,33 @@ __device__ __forceinline__ float chain_word(float s, unsigned word, const float4
     return s;
 }
 
+// THE SUM OF THE CONTRACT for SQ_T wave-loads at once (the scan and the range_search kernels): lane (sub, c) reads chunk c of row
+// r[t] (an existing row: callers clamp), runs its fmaf chain, and the chunks of a row are folded into its lane c = 0
+__device__ __forceinline__ void sq_score_loads(const unsigned char* __restrict__ codes, int d, int C, int c, const long long (&r)[SQ_T],
+                                               const float4 w0, const float4 w1, const float4 w2, const float4 w3, float (&s)[SQ_T]) {
+    u32x4 x[SQ_T];
+#pragma unroll
+    for (int t = 0; t < SQ_T; ++t)
+        x[t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(codes + (size_t)r[t] * d) + c);
+#pragma unroll
+    for (int t = 0; t < SQ_T; ++t) {
+        float a = 0.f;
+        a = chain_word(a, x[t][0], w0);
+        a = chain_word(a, x[t][1], w1);
+        a = chain_word(a, x[t][2], w2);
+        a = chain_word(a, x[t][3], w3);
+        s[t] = a;
+    }
+    for (int step = 1; step < C; step <<= 1) {                                      // the chunks of a row: lanes c .. c + C - 1
+        const bool take = c + step < C;
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            const float v = __shfl_down(s[t], step, 64);
+            s[t] = take ? s[t] + v : s[t];
+        }
+    }
+}
+
 // One block's scan of the rows [lo, hi) of codes under the weight row wrow [d]: score = base + s_0; the k best keys go to dst.
 // SEL: only the rows whose bit of `keep` is set are offered; a wave whose SQ_T loads hold no such row skips them (wave-uniform)
 template <bool SEL>
@@ -186,30 +214,11 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
         if constexpr (SEL) {
             if (__ballot(any) == 0) continue;
         }
-        u32x4 x[SQ_T];
+        long long r[SQ_T];
 #pragma unroll
-        for (int t = 0; t < SQ_T; ++t) {
-            const long long r = row[t] < hi ? row[t] : hi - 1;                      // stay inside the list; masked below
-            x[t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(codes + (size_t)r * d) + c);
-        }
+        for (int t = 0; t < SQ_T; ++t) r[t] = row[t] < hi ? row[t] : hi - 1;        // stay inside the list; masked below
         float s[SQ_T];
-#pragma unroll
-        for (int t = 0; t < SQ_T; ++t) {
-            float a = 0.f;
-            a = chain_word(a, x[t][0], w0);
-            a = chain_word(a, x[t][1], w1);
-            a = chain_word(a, x[t][2], w2);
-            a = chain_word(a, x[t][3], w3);
-            s[t] = a;
-        }
-        for (int step = 1; step < C; step <<= 1) {                                  // the chunks of a row: lanes c .. c + C - 1
-            const bool take = c + step < C;
-#pragma unroll
-            for (int t = 0; t < SQ_T; ++t) {
-                const float v = __shfl_down(s[t], step, 64);
-                s[t] = take ? s[t] + v : s[t];
-            }
-        }
+        sq_score_loads(codes, d, C, c, r, w0, w1, w2, w3, s);
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t) {
             const u64 key = make_key(base + s[t], (unsigned)row[t]);
@@ -266,6 +275,120 @@ __global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char*
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }
     sq_scan_list<false>(codes, lo, hi, W + (size_t)qi * d, bias[(size_t)qi * nprobe + g] + q0[qi], d, k, cap,
                         part + ((size_t)g * nq + qi) * k, nullptr);
+}
+
+// ---- range_search (wise_ivfsq_range_*): every row of the probed lists with (bias + q0) + s_0 > radius, s_0 from sq_score_loads.
+// One block per (query, probe) as sq_scan_kernel; structure, workspace and the determinism argument: range_common.h
+struct SqLane {
+    int C, RPL, sub, c;
+    bool active;
+    float4 w0, w1, w2, w3;
+    __device__ __forceinline__ void init(const float* __restrict__ wrow, int d, int lane) {
+        C = d >> 4; RPL = 64 / C; sub = lane / C; c = lane - sub * C; active = sub < RPL;
+        const float4* wq = reinterpret_cast<const float4*>(wrow + 16 * c);
+        w0 = wq[0]; w1 = wq[1]; w2 = wq[2]; w3 = wq[3];
+    }
+};
+
+__global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
+                                                             int nlist, const float* __restrict__ W, const float* __restrict__ q0,
+                                                             const long long* __restrict__ probes, const float* __restrict__ bias,
+                                                             int nprobe, int d, float radius, const unsigned* __restrict__ keep,
+                                                             unsigned* __restrict__ hit, long long wstride, long long* __restrict__ seg) {
+    __shared__ unsigned hb[RANGE_WORDS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
+    const long long l = probes[(size_t)qi * nprobe + pi];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }            // block-uniform
+    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
+    SqLane L;
+    L.init(W + (size_t)qi * d, d, lane);
+    unsigned* dst = hit + (size_t)qi * wstride + (lo >> 5) + (l > 0 ? l : 0);
+    long long total = 0;
+    for (long long clo = lo; clo < hi; clo += RANGE_ROWS, dst += RANGE_WORDS) {
+        const long long chi = clo + RANGE_ROWS < hi ? clo + RANGE_ROWS : hi;
+        if (wave == 0) hb[lane] = 0u;
+        __syncthreads();
+        const int ngroups = (int)((chi - clo + L.RPL - 1) / L.RPL);
+        for (int g = wave * SQ_T; g < ngroups; g += 4 * SQ_T) {                     // wave-uniform
+            long long r[SQ_T];
+            bool live[SQ_T];
+            bool any = false;
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t) {
+                r[t] = clo + (long long)(g + t) * L.RPL + L.sub;
+                live[t] = L.active && r[t] < chi;
+                if (keep) live[t] = live[t] && ((keep[r[t] >> 5] >> (r[t] & 31)) & 1u) != 0;
+                any = any || live[t];
+                if (r[t] >= chi) r[t] = chi - 1;                                    // stay inside the list; masked by live
+            }
+            if (keep && __ballot(any) == 0) continue;
+            float s[SQ_T];
+            sq_score_loads(codes, d, L.C, L.c, r, L.w0, L.w1, L.w2, L.w3, s);
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t)
+                if (live[t] && L.c == 0 && base + s[t] > radius) range_mark(hb, (int)(r[t] - clo));
+        }
+        __syncthreads();
+        if (wave == 0) total += range_publish(hb, dst, (int)((chi - clo + 31) >> 5), lane);
+    }
+    if (threadIdx.x == 0) seg[(size_t)qi * (nprobe + 1) + pi] = total;
+}
+
+__global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
+                                                            int nlist, const long long* __restrict__ ids, const float* __restrict__ W,
+                                                            const float* __restrict__ q0, const long long* __restrict__ probes,
+                                                            const float* __restrict__ bias, int nprobe, int d,
+                                                            const unsigned* __restrict__ hit, long long wstride,
+                                                            const long long* __restrict__ seg, const long long* __restrict__ lims,
+                                                            float* __restrict__ outD, long long* __restrict__ outI) {
+    __shared__ unsigned short lst[RANGE_ROWS];
+    __shared__ int s_cnt;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
+    const long long* so = seg + (size_t)qi * (nprobe + 1) + pi;
+    long long left = so[1] - so[0];                              // hits count found in this segment: never more are written
+    if (left <= 0) return;                                                     // no hit in this list (block-uniform)
+    long long dest = lims[qi] + so[0];
+    const long long l = probes[(size_t)qi * nprobe + pi];
+    if (l < 0 || l >= nlist) return;                                                // not the probes count saw: nothing to read
+    const long long lo = list_off[l], hi = list_off[l + 1];
+    const unsigned* words = hit + (size_t)qi * wstride + (lo >> 5) + l;
+    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
+    SqLane L;
+    L.init(W + (size_t)qi * d, d, lane);
+    for (long long clo = lo; clo < hi; clo += RANGE_ROWS, words += RANGE_WORDS) {
+        const long long chi = clo + RANGE_ROWS < hi ? clo + RANGE_ROWS : hi;
+        if (wave == 0) {
+            const int n = range_list(words, (int)((chi - clo + 31) >> 5), lst, lane);
+            if (lane == 0) s_cnt = n;
+        }
+        __syncthreads();
+        const int cnt = s_cnt < left ? s_cnt : (int)left;
+        const int ngroups = (cnt + L.RPL - 1) / L.RPL;
+        for (int g = wave * SQ_T; g < ngroups; g += 4 * SQ_T) {
+            long long r[SQ_T];
+            int e[SQ_T];
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t) {
+                e[t] = (g + t) * L.RPL + L.sub;
+                if (!L.active || e[t] >= cnt) e[t] = -1;
+                r[t] = clo + lst[e[t] >= 0 ? e[t] : cnt - 1];
+            }
+            float s[SQ_T];
+            sq_score_loads(codes, d, L.C, L.c, r, L.w0, L.w1, L.w2, L.w3, s);
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t)
+                if (e[t] >= 0 && L.c == 0) {
+                    outD[dest + e[t]] = base + s[t];
+                    outI[dest + e[t]] = ids ? ids[r[t]] : r[t];
+                }
+        }
+        __syncthreads();
+        dest += cnt;
+        left -= cnt;
+    }
 }
 
 static bool scan_shape_ok(int nq, int nprobe, int k) {
@@ -422,4 +545,64 @@ extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, con
     // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
     return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
                               used, (long long)pos_base);
+}
+
+static bool sq_range_shape_ok(int64_t N, int nlist, int nq, int nprobe) {
+    return N >= 0 && N < 0xFFFFFFFFll && nlist >= 1 && nq >= 1 && nq <= 65535 && nprobe >= 1 && nprobe <= 2048;
+}
+
+extern "C" size_t wise_ivfsq_range_workspace_bytes(int64_t N, int nlist, int nq, int nprobe) {
+    if (!sq_range_shape_ok(N, nlist, nq, nprobe)) return 0;
+    return range_workspace_bytes(nq, range_ivf_wstride(N, nlist), nprobe);
+}
+
+static int sq_range_args(const char* what, const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                         const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius, void* workspace,
+                         size_t workspace_bytes) {
+    WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
+    WISE_CHECK_ARG(sq_range_shape_ok(N, nlist, nq, nprobe), "%s: N=%lld nlist=%d nq=%d nprobe=%d unsupported (nq <= 65535, nprobe <= 2048)",
+                   what, (long long)N, nlist, nq, nprobe);
+    WISE_CHECK_ARG(W && q0 && probes && bias && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
+    WISE_CHECK_ARG(radius == radius && radius - radius == 0.f, "%s: radius must be finite", what);
+    const size_t need = wise_ivfsq_range_workspace_bytes(N, nlist, nq, nprobe);
+    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    return WISE_OK;
+}
+
+extern "C" int wise_ivfsq_range_count(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                                      const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                                      const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = sq_range_args("ivfsq_range_count", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
+                               workspace_bytes))
+        return rc;
+    WISE_CHECK_ARG(counts, "ivfsq_range_count: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const long long wstride = range_ivf_wstride(N, nlist);
+    unsigned* hit = reinterpret_cast<unsigned*>(workspace);
+    long long* seg = reinterpret_cast<long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
+    hipLaunchKernelGGL(sq_range_count_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st, codes, (const long long*)list_off,
+                       nlist, W, q0, (const long long*)probes, bias, nprobe, d, radius, keep, hit, wstride, seg);
+    WISE_LAUNCH_CHECK("sq_range_count_kernel");
+    hipLaunchKernelGGL(range_scan_kernel, dim3(nq), dim3(1024), 0, st, seg, (long long)nprobe, reinterpret_cast<long long*>(counts));
+    WISE_LAUNCH_CHECK("range_scan_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_ivfsq_range_fill(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
+                                     float radius, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    if (int rc = sq_range_args("ivfsq_range_fill", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
+                               workspace_bytes))
+        return rc;
+    WISE_CHECK_ARG(lims && outD && outI, "ivfsq_range_fill: null pointer");
+    const long long wstride = range_ivf_wstride(N, nlist);
+    const unsigned* hit = reinterpret_cast<const unsigned*>(workspace);
+    const long long* seg = reinterpret_cast<const long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
+    hipLaunchKernelGGL(sq_range_fill_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, (hipStream_t)stream, codes,
+                       (const long long*)list_off, nlist, reinterpret_cast<const long long*>(ids), W, q0, (const long long*)probes, bias, nprobe, d,
+                       hit, wstride, seg, reinterpret_cast<const long long*>(lims), outD, reinterpret_cast<long long*>(outI));
+    WISE_LAUNCH_CHECK("sq_range_fill_kernel");
+    return WISE_OK;
 }

@@ -643,6 +643,27 @@ class FeatureSearchIndex(SearchIndex):
             dist, ids = self.index.search(query_features, topk, params=SearchParameters(sel=as_selector(within)))
         return dist[0], ids[0]
 
+    def search_range(self, media_type, query, threshold, query_type='text', *, within=None):
+        """Not in the reference: EVERY vector that scores above `threshold` for the query (faiss's range_search: score > threshold,
+        strictly) instead of the topk best — exhaustive retrieval, near-duplicate sweeps, full positive sets.  Same prompt rules
+        as `search`; returns (dist, ids) of the first query, by descending score.  On an inverted-file index the hits come from
+        the probed lists.  `within`: as on `search`."""
+        if query_type != 'text':
+            raise ValueError('query_type={query_type} not implemented')
+
+        if media_type == 'audio':
+            if isinstance(query, str):
+                media_query_text = [query]
+            else:
+                media_query_text = [(self.prompt[media_type] + x) for x in query]
+        else:
+            media_query_text = [(self.prompt[media_type] + query)]
+
+        query_features = self.feature_extractor.extract_text_features(media_query_text)
+        params = None if within is None else SearchParameters(sel=as_selector(within))
+        lims, dist, ids = self.index.range_search(query_features, threshold, params=params)
+        return dist[lims[0]:lims[1]], ids[lims[0]:lims[1]]
+
     def search_batch(self, media_type, queries, topk=5, query_type='text', *, within=None):
         """Not in the reference: what `search` returns for every string of `queries`, from ONE text-tower batch and ONE
         batched index search per 256 of them (wise_amd/search/batch_queries.py; the --queries-from loop of search.py:894-950

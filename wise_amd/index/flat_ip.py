@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import range_search as _range
 from .selector import resolve_for, unpack_params
 
 
@@ -305,6 +306,45 @@ class FlatIPIndex:
         q = torch.from_numpy(x).to(self.device)
         D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel=sel)
         return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- range search ---------------------------------------------------------------------------
+    def range_search_device(self, q: torch.Tensor, thresh: float, sel=None, chunk: Optional[int] = None):
+        """q [nq,d] fp32 on device -> (lims [nq+1] int64, D fp32, I int64) on the device: every row with score > thresh, each
+        query's segment by descending score, ties by ascending row (range_search.py).  The score is the fp32 VALU scan's
+        (wise_ip_topk_pos_f32), never a shadow copy's.  sel: only the selected rows can be hits (their bitmap is tested in the
+        count pass).  chunk: queries per workspace chunk (default: what range_search.WORKSPACE_BYTES allows)."""
+        lib = _lib.lib()
+        self._finalize()
+        radius = _range.check_threshold(thresh)
+        res = resolve_for(self, sel)
+        keep = None if res is None else res.bitmap
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"range_search: expected [nq,{self.d}], got {tuple(q.shape)}")
+        q = q.to(self.device, torch.float32).contiguous()
+        X, n, d, st = self._X, self._n, self.d, _lib.stream_ptr()
+
+        def stage(qs):
+            def count(counts, ws):
+                _lib.check(lib.wise_ip_range_count_f32(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, _lib.ptr(keep),
+                                                       counts.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ip_range_count_f32")
+
+            def fill(lims, D, P, ws):
+                _lib.check(lib.wise_ip_range_fill_f32(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, 0, 0, lims.data_ptr(),
+                                                      D.data_ptr(), P.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ip_range_fill_f32")
+            return count, fill
+
+        def workspace(need):
+            if self._ws is None or self._ws.numel() < need:
+                self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            return self._ws
+
+        return _range.run(q, lambda m: lib.wise_ip_range_workspace_bytes(n, d, m), stage, workspace, self._ids, self.id_base, chunk)
+
+    def range_search(self, x, thresh: float, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (lims, D, I) numpy.  params: SearchParameters(sel=...)."""
+        sel, _ = unpack_params(params, ivf=False)
+        lims, D, I = self.range_search_device(_range.to_numpy(x).to(self.device), thresh, sel=sel)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
     def reconstruct_batch(self, ids) -> np.ndarray:
         """rows stored under the given external ids (api/routes.py:1078)."""

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import range_search as _range
 from .flat_ip import FlatIPIndex
 from .selector import resolve_for, unpack_params
 
@@ -322,6 +323,45 @@ class IVFIndexBase:
         finally:
             self.nprobe = kept
         return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- range search: the part every inverted-file type shares (range_search.py) ----------------
+    def _range_workspace_bytes(self, nq: int, nprobe: int) -> int:
+        """The type's *_range_workspace_bytes; the types without a range search (product-quantized) do not override it."""
+        raise NotImplementedError(_range.UNSUPPORTED.format(type(self).__name__))
+
+    def _range_stage(self, qs: torch.Tensor, probes: torch.Tensor, nprobe: int, radius: float, keep: Optional[torch.Tensor]):
+        """(count, fill) of range_search.run for the queries qs and their probes: the type's count / fill pair of the C ABI."""
+        raise NotImplementedError(_range.UNSUPPORTED.format(type(self).__name__))
+
+    def range_search_device(self, q: torch.Tensor, thresh: float, sel=None, chunk: Optional[int] = None):
+        """q [nq,d] fp32 on device -> (lims [nq+1] int64, D fp32, I int64) on the device: every row OF THE PROBED LISTS with
+        score > thresh (faiss's IVF range search), each query's segment by descending score, ties by ascending list position.
+        sel: only the selected rows can be hits.  chunk: queries per workspace chunk."""
+        self._range_workspace_bytes(1, 1)                # NotImplementedError on the types without a range search
+        radius = _range.check_threshold(thresh)
+        q = self._queries(q)
+        keep = self._keep(sel)
+        nprobe = self._clamped_nprobe()
+
+        def stage(qs):
+            return self._range_stage(qs, self._coarse.probes_device(qs, nprobe).contiguous(), nprobe, radius, keep)
+
+        return _range.run(q, lambda m: self._range_workspace_bytes(m, nprobe), stage, self._workspace, self._lists.ids, 0, chunk)
+
+    def range_search(self, x, thresh: float, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (lims, D, I) numpy.  params: SearchParametersIVF(sel=..., nprobe=...);
+        nprobe replaces the index's for this call only."""
+        self._range_workspace_bytes(1, 1)
+        sel, nprobe = unpack_params(params, ivf=True)
+        q = _range.to_numpy(x).to(self.device)
+        kept = self.nprobe
+        try:
+            if nprobe is not None:
+                self.nprobe = nprobe
+            lims, D, I = self.range_search_device(q, thresh, sel=sel)
+        finally:
+            self.nprobe = kept
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
 
     def make_direct_map(self, enable: bool = True) -> None:
         """routes.py:904-909: afterwards reconstruct works by id.  Ids are looked up in the stored id array."""

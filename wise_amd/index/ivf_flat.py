@@ -107,6 +107,22 @@ class IVFFlatIPIndex(IVFIndexBase):
         per query."""
         return self._scan(q, k, True, probe_count)
 
+    def _range_workspace_bytes(self, nq: int, nprobe: int) -> int:
+        return _lib.lib().wise_ivf_range_workspace_bytes(self._lists.n, self.nlist, nq, nprobe)
+
+    def _range_stage(self, qs, probes, nprobe, radius, keep):
+        lib, ls, st, n = _lib.lib(), self._lists, _lib.stream_ptr(), qs.shape[0]
+        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist)
+
+        def count(counts, ws):
+            _lib.check(lib.wise_ivf_range_count_f32(*head, qs.data_ptr(), n, probes.data_ptr(), nprobe, radius, _lib.ptr(keep),
+                                                    counts.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ivf_range_count_f32")
+
+        def fill(lims, D, P, ws):
+            _lib.check(lib.wise_ivf_range_fill_f32(*head, 0, qs.data_ptr(), n, probes.data_ptr(), nprobe, radius, lims.data_ptr(),
+                                                   D.data_ptr(), P.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ivf_range_fill_f32")
+        return count, fill
+
     # -- the rest of the surface the REST layer touches -------------------------------------------
     def reconstruct_batch(self, ids) -> np.ndarray:
         lib = _lib.lib()

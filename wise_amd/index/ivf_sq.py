@@ -195,6 +195,32 @@ class IVFSQIPIndex(IVFIndexBase):
                        None if probe_count is None else probe_count[s:s + chunk], positions)
         return D, I
 
+    def _range_workspace_bytes(self, nq: int, nprobe: int) -> int:
+        return _lib.lib().wise_ivfsq_range_workspace_bytes(self._lists.n, self.nlist, nq, nprobe)
+
+    def _range_stage(self, qs, probes, nprobe, radius, keep):
+        """bias and weights as _scan computes them, then wise_ivfsq_range_count / _fill over the same probes"""
+        lib, ls, st, n = _lib.lib(), self._lists, _lib.stream_ptr(), qs.shape[0]
+        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
+                                    bias.data_ptr(), st), "wise_pq_bias")
+        W = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
+        q0 = torch.empty(n, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), n, self.d, W.data_ptr(), q0.data_ptr(), st), "wise_sq_query")
+        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist)
+
+        def mid():       # built inside the closures: they, not this frame, keep W, q0, probes and bias alive until fill has run
+            return (W.data_ptr(), q0.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, radius)
+
+        def count(counts, ws):
+            _lib.check(lib.wise_ivfsq_range_count(*head, *mid(), _lib.ptr(keep), counts.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       "wise_ivfsq_range_count")
+
+        def fill(lims, D, P, ws):
+            _lib.check(lib.wise_ivfsq_range_fill(*head, 0, *mid(), lims.data_ptr(), D.data_ptr(), P.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 st), "wise_ivfsq_range_fill")
+        return count, fill
+
     # -- the rest of the surface the REST layer touches -------------------------------------------
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + the bin centres; NaN for an unknown id."""

@@ -144,6 +144,13 @@ class ShardedFlatIPIndex:
                 self.local.nprobe = kept
         return D.cpu().numpy(), I.cpu().numpy()
 
+    def range_search(self, x, thresh: float, params=None):
+        """Not built: the result is variable-length and nothing exchanges it between the ranks."""
+        from .range_search import NO_SHARDED
+        raise NotImplementedError(NO_SHARDED)
+
+    range_search_device = range_search
+
     def reconstruct_batch(self, ids):
         """IndexIDMap::reconstruct_batch over the shards (api/routes.py:1078), collective: every rank looks the ids up in
         its own rows (a row of NaN where it does not hold the id — wise_reconstruct_batch), ONE all-gather of the [n,d]
