@@ -40,7 +40,8 @@ const char* wise_last_error(void);
  * wise_sel_bitmap, wise_sel_positions (with wise_sel_positions_workspace_bytes), wise_ip_topk_pos_f32, wise_ivf_scan_sel_f32 and
  * wise_ivfpq_scan_sel, the searches restricted to a set of ids; and the wise_sq_* entry points with wise_ivfsq_scan,
  * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it; and the count / fill pairs of
- * range_search, wise_ip_range_*, wise_ivf_range_* and wise_ivfsq_range_*.  The version is 5. */
+ * range_search, wise_ip_range_*, wise_ivf_range_* and wise_ivfsq_range_*; and wise_compact_plan (with wise_compact_plan_entries),
+ * wise_compact_rank and wise_compact_rows, the in-place compaction behind remove_ids.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -449,6 +450,32 @@ int wise_ivfsq_range_fill(const uint8_t* codes, int64_t N, int d, const int64_t*
                           const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
                           float radius, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* (ABI 5, additive) remove_ids — stable, in-place compaction of an index's per-row arrays under a bitmap over row positions.
+ *   keep      (N + 31) / 32 words as wise_sel_bitmap writes them, bit p set = row p STAYS.  The bits past N are ignored, whatever
+ *             they hold.
+ *   plan      wise_compact_plan_entries(N) = ceil(N / 2048) + 1 int64 (device), written by wise_compact_plan: plan[s] = the number
+ *             of kept rows before row 2048 s; the last entry is the total, which also goes to count[0] (device int64).
+ *   rank      out[i] = the number of kept rows strictly before position pos[i], 0 <= pos[i] <= N (values outside are clamped):
+ *             list_off [nlist + 1] becomes the offsets after the removal in one launch.  pos and out may be the same array.
+ *   rows      the kept rows of data [N, width_bytes] (row-major, no padding) move to rows 0 .. kept - 1 in their order, in
+ *             place; what lies behind them afterwards is unspecified.  The only other memory written is scratch: the array is
+ *             worked through in ascending chunks of scratch_bytes / width_bytes rows (whole multiples of 2048 when more than
+ *             2048 fit), each gathered into the scratch and then copied down, in two launches, so that every source of a chunk
+ *             is read before any of its destinations is written; a chunk whose destinations all lie below it is written in
+ *             place, and a chunk in front of the first removed row is left alone.  1 <= width_bytes <= 65536; accesses are 16
+ *             bytes wide when width_bytes, data and scratch are multiples of 16, else the largest power of two dividing all three.
+ *             The same plan serves every array of the index (payload, ids, compact rows, scales).
+ * No atomic decides where a row lands (ranks are popcounts and scans), so the same inputs give the same bytes.  Nothing is
+ * allocated and nothing is read back: all three calls can be captured into a graph.  0 <= N < 2^32 - 1; N = 0, keep-all and
+ * keep-none are valid.  A scratch smaller than one row, a null pointer or a size out of range is WISE_E_INVALID with a
+ * wise_last_error text. */
+int64_t wise_compact_plan_entries(int64_t N);
+int wise_compact_plan(const uint32_t* keep, int64_t N, int64_t* plan, int64_t* count, void* stream);
+int wise_compact_rank(const uint32_t* keep, int64_t N, const int64_t* plan, const int64_t* pos, int64_t n, int64_t* out,
+                      void* stream);
+int wise_compact_rows(void* data, int64_t N, int64_t width_bytes, const uint32_t* keep, const int64_t* plan, void* scratch,
+                      size_t scratch_bytes, void* stream);
 
 /* Merge `parts` partial top-k lists (e.g. one per GPU after the RCCL all-gather) into one.
  * inD [parts,nq,k] fp32, inI [parts,nq,k] int64 (entries with id -1 are padding) -> outD/outI [nq,k].

@@ -78,6 +78,7 @@ from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
 from .ivf_sq import IVFSQIPIndex, check_sq_shape
+from .mutate import plan_update
 from .search_index import SearchIndex
 from .selector import SearchParameters, as_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
@@ -529,6 +530,153 @@ class FeatureSearchIndex(SearchIndex):
         lo, hi = shard_range(ntotal(index_fn), rank, world)
         return wrap(read_range(index_fn, lo, hi), lo)
 
+    IVF_FOURCCS = ('WiOP', 'WiPR', 'IwPQ', 'IwSq', 'IwFl')
+
+    def _index_from_file(self, fn, shard=None):
+        """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
+        Anything that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
+        shard = (rank, world): only rows shard_range(N, rank, world) of a flat file."""
+        import torch
+
+        fourcc = faiss_io.index_fourcc(fn) if fn.exists() else None
+        if fourcc == 'WiOP':
+            f = faiss_io.read_ivf_opq_ip(fn)
+            nlist, d = f["centroids"].shape
+            lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            if "kind" in f:
+                index = IVFOPQRefineIPIndex(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
+                lists += (torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16)),
+                          None if f["scales"] is None else torch.from_numpy(f["scales"]))
+            else:
+                index = IVFOPQIPIndex(d, nlist, f["codebooks"].shape[0])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            index.set_rotation(f["rotation"])
+            index.adopt_lists(*lists)
+            index.nprobe = f["nprobe"]
+        elif fourcc == 'WiPR':
+            f = faiss_io.read_ivf_pq_refine_ip(fn)
+            index = IVFPQRefineIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0], f["kind"],
+                                       k_factor=f["k_factor"])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), rows,
+                              None if f["scales"] is None else torch.from_numpy(f["scales"]))
+            index.nprobe = f["nprobe"]
+        elif fourcc == 'IwPQ':
+            f = faiss_io.read_ivf_pq_ip(fn)
+            index = IVFPQIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0])
+            index.set_centroids(f["centroids"])
+            index.set_codebooks(f["codebooks"])
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            index.nprobe = f["nprobe"]
+        elif fourcc == 'IwSq':
+            f = faiss_io.read_ivf_sq_ip(fn)
+            nlist, d = f["centroids"].shape
+            index = IVFSQIPIndex(d, nlist)
+            index.set_centroids(f["centroids"])
+            index.set_trained(f["trained"][:d], f["trained"][d:])
+            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            index.nprobe = f["nprobe"]
+        elif fourcc == 'IwFl':
+            f = faiss_io.read_ivf_flat_ip(fn)
+            index = IVFFlatIPIndex(f["centroids"].shape[1], f["centroids"].shape[0])
+            index.set_centroids(f["centroids"])
+            index.adopt_lists(torch.from_numpy(f["X"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
+            index.nprobe = f["nprobe"]
+        else:
+            X, ids = faiss_io.read_idmap_flat_ip(fn)                 # rows memory-mapped: only [lo, hi) is ever touched
+            lo, hi = shard_range(X.shape[0], *shard) if shard is not None else (0, X.shape[0])
+            index = self.flat_index_factory(X.shape[1])
+            index.reserve(hi - lo)                   # one [n,d] device tensor, filled slice by slice
+            for s in range(lo, hi, 1 << 20):         # stream the memory-mapped rows into HBM
+                e = min(s + (1 << 20), hi)
+                index.add_with_ids(np.ascontiguousarray(X[s:e]), ids[s:e])
+        return index
+
+    @staticmethod
+    def _write_index_file(index, fn):
+        """index object -> file, by the faiss_io writer of its type (the inverse of _index_from_file)."""
+        if isinstance(index, FlatIPIndex):
+            index._finalize()
+            faiss_io.write_idmap_flat_ip(fn, index._X.cpu().numpy(), index._ids.cpu().numpy())
+            return
+        refine = isinstance(index, IVFPQRefineIPIndex)
+        store = {}
+        if refine:
+            rows, scales = index.store_host()
+            store = dict(kind=index.kind, k_factor=index.k_factor, rows=rows, scales=scales)
+        if isinstance(index, (IVFOPQIPIndex, IVFOPQRefineIPIndex)):
+            c, cb, codes, ids_s, off = index.lists_host()
+            faiss_io.write_ivf_opq_ip(fn, index.rotation.cpu().numpy(), c, cb, codes, ids_s, off, nprobe=index.nprobe, **store)
+        elif refine:
+            c, cb, codes, ids_s, off = index.lists_host()
+            faiss_io.write_ivf_pq_refine_ip(fn, c, cb, codes, ids_s, off, store["kind"], store["k_factor"], store["rows"],
+                                            store["scales"], nprobe=index.nprobe)
+        elif isinstance(index, IVFPQIPIndex):
+            c, cb, codes, ids_s, off = index.lists_host()
+            faiss_io.write_ivf_pq_ip(fn, c, cb, codes, ids_s, off, nprobe=index.nprobe)
+        elif isinstance(index, IVFSQIPIndex):
+            c, trained, codes, ids_s, off = index.lists_host()
+            faiss_io.write_ivf_sq_ip(fn, c, trained, codes, ids_s, off, nprobe=index.nprobe)
+        elif isinstance(index, IVFFlatIPIndex):
+            c, Xs, ids_s, off = index.lists_host()
+            faiss_io.write_ivf_flat_ip(fn, c, Xs, ids_s, off, nprobe=index.nprobe)
+        else:
+            raise TypeError(f'{type(index).__name__}: no index file format')
+
+    def update_index(self, index_type):
+        """Not in the reference: bring the EXISTING index file of `index_type` in line with the feature store without
+        retraining.  The vectors the index holds and the store no longer has are removed (remove_ids: an in-place compaction
+        on the GPU); the store's vectors the index lacks are added in store order (add_with_ids: assigned and encoded against
+        the centroids, codebooks, rotation and ranges AS TRAINED — nprobe and k_factor stay too); the file is written to a
+        temporary name beside it and renamed over it.  Returns (n_added, n_removed); with nothing to do the file is left
+        alone.  The feature extractor is not built.  A `self.index` loaded from that file before the call is stale
+        afterwards: call load_index again.  Lists are not rebalanced and nothing is retrained, however many updates pile up."""
+        parse_m, parse_refine, _ = _pq_parsers(index_type)
+        is_pq = parse_m(index_type) is not None or parse_refine(index_type) is not None
+        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq and index_type != 'IndexIVFSQ8':
+            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
+                                      f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
+        if _dist_rank_world()[2]:
+            raise NotImplementedError('update_index under a sharded process group is not built (a collective removal is not): '
+                                      'update the single file in one process and shard it again')
+        index_fn = self.get_index_filename(index_type)
+        if not index_fn.exists():
+            raise FileNotFoundError(f'index {index_fn} does not exist; use create_index (the create-index.py script) first')
+        index = self._index_from_file(index_fn)
+        index_ids = (index._selector_rows()[0]).cpu().numpy()
+        feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
+        feature_store.enable_read(shard_shuffle=False)
+        if feature_store.feature_dim != index.d:
+            raise ValueError(f'update_index: the store holds {feature_store.feature_dim}-d vectors, the index {index.d}-d')
+        X = np.empty((feature_store.feature_count, feature_store.feature_dim), dtype=np.float32)
+        store_ids = np.empty((feature_store.feature_count,), dtype=np.int64)
+        n = 0
+        for feature_ids_batch, feature_vectors_batch in feature_store.iter_batch():
+            m = len(feature_ids_batch)
+            X[n:n + m] = feature_vectors_batch
+            store_ids[n:n + m] = feature_ids_batch
+            n += m
+        remove, add_mask = plan_update(index_ids, store_ids[:n])
+        n_removed = index.remove_ids(remove) if remove.size else 0
+        add_rows = np.flatnonzero(add_mask)
+        for s0 in range(0, add_rows.size, 1 << 20):
+            sel = add_rows[s0:s0 + (1 << 20)]
+            index.add_with_ids(X[sel], store_ids[sel])
+        n_added = int(add_rows.size)
+        if n_added or n_removed:
+            tmp_fn = index_fn.with_name(index_fn.name + '.tmp-%d' % os.getpid())
+            try:
+                self._write_index_file(index, tmp_fn)
+                os.replace(tmp_fn, index_fn)
+            finally:
+                if tmp_fn.exists():
+                    tmp_fn.unlink()
+        print(f'{index_type} for {self.media_type}: added {n_added}, removed {n_removed} vectors')
+        return n_added, n_removed
+
     def is_index_loaded(self):
         return hasattr(self, 'index')
 
@@ -551,69 +699,13 @@ class FeatureSearchIndex(SearchIndex):
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
             index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'WiOP':
-            import torch                             # unsharded, as 'WiPR' / 'IwPQ' below, plus the rotation
-            f = faiss_io.read_ivf_opq_ip(index_fn)
-            nlist, d = f["centroids"].shape
-            lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            if "kind" in f:
-                index = IVFOPQRefineIPIndex(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
-                lists += (torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16)),
-                          None if f["scales"] is None else torch.from_numpy(f["scales"]))
-            else:
-                index = IVFOPQIPIndex(d, nlist, f["codebooks"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            index.set_rotation(f["rotation"])
-            index.adopt_lists(*lists)
-            index.nprobe = f["nprobe"]
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'WiPR':
-            import torch                             # unsharded, as 'IwPQ' below
-            f = faiss_io.read_ivf_pq_refine_ip(index_fn)
-            index = IVFPQRefineIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0], f["kind"],
-                                       k_factor=f["k_factor"])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), rows,
-                              None if f["scales"] is None else torch.from_numpy(f["scales"]))
-            index.nprobe = f["nprobe"]
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwPQ':
-            import torch                             # small: every rank of a process group loads the whole file
-            f = faiss_io.read_ivf_pq_ip(index_fn)
-            index = IVFPQIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwSq':
-            import torch                             # unsharded: every rank of a process group loads the whole file
-            f = faiss_io.read_ivf_sq_ip(index_fn)
-            nlist, d = f["centroids"].shape
-            index = IVFSQIPIndex(d, nlist)
-            index.set_centroids(f["centroids"])
-            index.set_trained(f["trained"][:d], f["trained"][d:])
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
-            import torch
-            f = faiss_io.read_ivf_flat_ip(index_fn)
-            index = IVFFlatIPIndex(f["centroids"].shape[1], f["centroids"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.adopt_lists(torch.from_numpy(f["X"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
+        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) in self.IVF_FOURCCS:
+            index = self._index_from_file(index_fn)   # unsharded: every rank of a process group loads the whole file
         else:
             if sharded and part_fn.exists():         # built by this many ranks: a rank's part is its shard
-                X, ids = faiss_io.read_idmap_flat_ip(part_fn)
-                lo, hi = 0, X.shape[0]
+                index = self._index_from_file(part_fn)
             else:
-                X, ids = faiss_io.read_idmap_flat_ip(index_fn)      # rows memory-mapped: only [lo, hi) is ever touched
-                lo, hi = shard_range(X.shape[0], rank, world) if sharded else (0, X.shape[0])
-            index = self.flat_index_factory(X.shape[1])
-            index.reserve(hi - lo)                   # one [n,d] device tensor, filled slice by slice
-            for s in range(lo, hi, 1 << 20):         # stream the memory-mapped rows into HBM
-                e = min(s + (1 << 20), hi)
-                index.add_with_ids(np.ascontiguousarray(X[s:e]), ids[s:e])
+                index = self._index_from_file(index_fn, shard=(rank, world) if sharded else None)
             if sharded:
                 index = ShardedFlatIPIndex(index, merge=getattr(index, 'merge_lists', None),
                                            always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import mutate as _mutate
 from . import range_search as _range
 from .selector import resolve_for, unpack_params
 
@@ -125,6 +126,28 @@ class FlatIPIndex:
         if self._X is None:
             self._X = torch.empty(0, self.d, dtype=torch.float32, device=self.device)
             self._ids = torch.empty(0, dtype=torch.int64, device=self.device)
+
+    REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
+
+    def remove_ids(self, sel, scratch_bytes: Optional[int] = None) -> int:
+        """faiss's Index::remove_ids: drop the rows `sel` selects (an IDSelector, or an array of ids); returns how many went.
+        The rows and ids are compacted in place, in order (csrc/compact.hip), through a scratch of `scratch_bytes` (default
+        REMOVE_SCRATCH_BYTES); a reserved tensor keeps its capacity and later add_with_ids calls fill it from the new end.
+        The bf16 / int8 shadows are dropped and rebuilt by the next search that wants them, so they and their norms are what
+        a fresh index over the kept rows builds; the two-stage counters go on counting."""
+        self._finalize()
+        if self._ids is None and self._n:              # implicit ids stop being id_base + row once a row goes
+            self._ids = torch.arange(self._n, device=self.device, dtype=torch.int64) + self.id_base
+        c = _mutate.start(self, sel, scratch_bytes)
+        if c is None:
+            return 0
+        self._X, self._ids = c.rows(self._X), c.rows(self._ids)
+        self._n = c.kept
+        if getattr(self, "_rX", None) is not None:
+            self._rfill = c.kept
+        self._Xb = self._Xq = self._scales8 = self._norms = self._norms8 = None
+        self._mutations = getattr(self, "_mutations", 0) + 1
+        return c.n - c.kept
 
     # -- search ---------------------------------------------------------------------------------
     def _selector_rows(self):

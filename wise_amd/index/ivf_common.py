@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import mutate as _mutate
 from . import range_search as _range
 from .flat_ip import FlatIPIndex
 from .selector import resolve_for, unpack_params
@@ -239,6 +240,17 @@ class ListStore:
             self.ids = torch.empty(0, dtype=torch.int64, device=self.device)
             self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
 
+    def compact(self, c) -> None:
+        """remove_ids on the merged lists (no pending chunks): every per-row array compacted in place under the one plan of
+        `c` (mutate.RowCompaction) and narrowed to the kept rows — views of the same allocations, nothing is copied or given
+        back —, list_off re-ranked.  Within a list the rows keep their order."""
+        if self._pending or self.data is None or self.data.shape[0] != c.n:
+            raise RuntimeError("ListStore.compact: merge the pending chunks first")
+        self.list_off = c.rank(self.list_off)
+        self.data, self.ids = c.rows(self.data), c.rows(self.ids)
+        self.extra = [c.rows(t) for t in self.extra]
+        self.n = c.kept
+
     def nbytes(self) -> int:
         """Bytes of HBM the merged lists hold: payload, ids, offsets, extra arrays."""
         return sum(t.numel() * t.element_size() for t in (self.data, self.ids, self.list_off, *self.extra))
@@ -362,6 +374,24 @@ class IVFIndexBase:
         finally:
             self.nprobe = kept
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
+
+    def remove_ids(self, sel, scratch_bytes: Optional[int] = None) -> int:
+        """faiss's Index::remove_ids: drop the rows `sel` selects (an IDSelector, or an array of ids); returns how many went.
+        Afterwards the index is, byte for byte, the one with the same trained state that was given only the kept rows in the
+        same order.  Pending rows are merged first; the arrays are compacted in place (csrc/compact.hip) through a scratch of
+        `scratch_bytes` (default REMOVE_SCRATCH_BYTES), so the extra memory does not grow with the index.  The direct map is a
+        lookup in the stored id array, which is compacted too: a removed id reconstructs to NaN."""
+        if getattr(self, "pos_base", 0) != 0:
+            raise NotImplementedError(f"{type(self).__name__}.remove_ids: this index is a slice of a sharded index "
+                                      f"(pos_base = {self.pos_base}); a collective removal is not built")
+        c = _mutate.start(self, sel, scratch_bytes)      # resolves against the merged lists (_selector_rows finalizes)
+        if c is None:
+            return 0
+        self._lists.compact(c)
+        self._mutations = getattr(self, "_mutations", 0) + 1
+        return c.n - c.kept
 
     def make_direct_map(self, enable: bool = True) -> None:
         """routes.py:904-909: afterwards reconstruct works by id.  Ids are looked up in the stored id array."""

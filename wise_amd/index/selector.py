@@ -61,10 +61,11 @@ class IDSelector:
 
     def resolve(self, index) -> ResolvedSelector:
         """The bitmap of this selector over the rows of `index` (anything with `_selector_rows()`: the merged external ids on the
-        device or None, id_base, row count), cached until the index's row count changes."""
+        device or None, id_base, row count), cached until the index's row count changes or rows are removed."""
         ids, id_base, n = index._selector_rows()
         hit = self._resolved.get(index)
-        if hit is not None and hit.n == n and hit.ids_ptr == _lib.ptr(ids):
+        gen = getattr(index, "_mutations", 0)              # remove_ids moves rows under an unchanged array: resolve again
+        if hit is not None and hit.n == n and hit.ids_ptr == _lib.ptr(ids) and hit.gen == gen:
             return hit
         lib = _lib.lib()
         device = index.device
@@ -74,7 +75,7 @@ class IDSelector:
                                        0 if sorted_ids is None else sorted_ids.numel(), imin, imax, int(invert), bitmap.data_ptr(),
                                        _lib.stream_ptr()), "wise_sel_bitmap")
         res = ResolvedSelector(bitmap, n)
-        res.ids_ptr = _lib.ptr(ids)
+        res.ids_ptr, res.gen = _lib.ptr(ids), gen
         self._resolved[index] = res
         return res
 

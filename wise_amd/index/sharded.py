@@ -58,6 +58,11 @@ NO_SELECTOR = ("the sharded indexes take no selector: a collective filtered sear
                "unsharded index instead")
 
 
+NO_COLLECTIVE_REMOVAL = ("the sharded indexes have no remove_ids: a collective removal is not built (every rank would compact its "
+                         "slice and the slices' row ranges would have to be agreed on again); remove from the unsharded index "
+                         "and shard it again")
+
+
 class ShardedFlatIPIndex:
     """Every rank constructs it around its own local FlatIPIndex (rows [lo,hi) of the global index,
     ids already global).  `search_device` is collective: all ranks call it with the same queries."""
@@ -150,6 +155,10 @@ class ShardedFlatIPIndex:
         raise NotImplementedError(NO_SHARDED)
 
     range_search_device = range_search
+
+    def remove_ids(self, sel, scratch_bytes=None) -> int:
+        """Not built: every rank would have to compact its slice and the ranks agree on the new row ranges."""
+        raise NotImplementedError(NO_COLLECTIVE_REMOVAL)
 
     def reconstruct_batch(self, ids):
         """IndexIDMap::reconstruct_batch over the shards (api/routes.py:1078), collective: every rank looks the ids up in
