@@ -172,6 +172,26 @@ def test_gemm_plan_matches_table():
     assert not moved, f"{len(moved)} shapes plan another tile:\n" + "\n".join(moved[:20])
 
 
+def test_splitk_scratch_bytes_follow_the_plan():
+    """Every row of the table with m_valid > 0 (gemm_bf16_rows): the scratch a call asks for is the plan's S partial tiles
+    of 128 rows, fp32 — 0 where the plan does not split."""
+    lib = _load()
+    lib.wise_debug_gemm_splitk_bytes.argtypes = [C.c_int] * 4
+    lib.wise_debug_gemm_splitk_bytes.restype = C.c_size_t
+    out = (C.c_int * 8)()
+    rows = split = 0
+    for kind, label, args in cases():
+        if kind != "gemm" or args[4] <= 0:
+            continue
+        M, N, K, mode, m_valid = args
+        for ov in (0, 1):
+            assert lib.wise_debug_gemm_plan(0, (C.c_int * 7)(*args, ov, CUS), out) == 6
+            assert lib.wise_debug_gemm_splitk_bytes(M, m_valid, N, K) == out[0] * 128 * N * 4, label
+        rows += 1
+        split += out[0] > 0
+    assert rows and 0 < split < rows      # the table has both kinds
+
+
 if __name__ == "__main__":
     lib = C.CDLL(str(LIB_DEBUG))
     lib.wise_debug_gemm_plan.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]

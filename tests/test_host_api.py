@@ -44,7 +44,8 @@ def test_debug_switches_live_only_in_the_debug_library():
 
     assert _lib.DEBUG_LIB_PATH.exists(), "python -m wise_amd.build builds libwise_hip_debug.so beside the product"
     dbg = _lib.load_debug()
-    for name in ("wise_debug_neighbour", "wise_debug_set_gemm_variant", "wise_debug_pk_overlap_probe"):
+    for name in ("wise_debug_neighbour", "wise_debug_set_gemm_variant", "wise_debug_pk_overlap_probe",
+                 "wise_debug_gemm_splitk_bytes", "wise_debug_gemm_rows", "wise_debug_gemm_resid_ln_rows"):
         assert hasattr(dbg, name)
         assert not hasattr(_lib.load(), name)
     assert "debug_probe.hip" not in build.HIP_SOURCES

@@ -981,19 +981,22 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // 4 columns (and per 1024 columns of the row): the S partials of a thread's columns are independent loads, as many
 // threads in flight as the plain reduction has — a wave per row, with the S x N/256 loads of a lane in sequence, measured
 // SLOWER than the two launches it replaced (XLM-R-large, one query: 2.04 -> 2.78 ms).  x_new = x + (bias + p_0 + p_1 + ...)
-// in that fixed order; exact two-pass statistics over the row (wave sums, then the four waves' sums in a fixed order):
-// deterministic, call-to-call bit-stable.  write_norm: post-LN blocks (BERT family) keep the NORMALISED row as the residual.
+// in that fixed order; exact two-pass statistics over the row, summed in layernorm_kernel's order (vit.hip) so that a row
+// gets the bits the two launches give it, whichever path its batch size selects: there lane l of ONE wave owns the float4
+// columns l, l + 64, l + 128, ... and adds their sums one after the other before the butterfly.  Here thread t owns columns
+// t, t + 256, ...: the per-column sums go through LDS in column order, and every wave walks its lane's columns as that one
+// wave would (4 NV dependent adds, <= 16) and runs the same butterfly.  Deterministic, call-to-call bit-stable.
+// write_norm: post-LN blocks (BERT family) keep the NORMALISED row as the residual.
 template <int NV>
 __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* __restrict__ part, int S, int rows, int N,
                                                                const float* __restrict__ bias, float* __restrict__ x,
                                                                const float* __restrict__ lw, const float* __restrict__ lb,
                                                                float eps, bf16_t* __restrict__ y, int write_norm) {
-    __shared__ float red[2][4];
-    const int row = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    __shared__ float col[2][NV * 256];     // per float4 column: its sum, then its sum of squared deviations
+    const int row = blockIdx.x, t = threadIdx.x, lane = t & 63;
     const int w4 = N >> 2;
     float4* xr = reinterpret_cast<float4*>(x + (size_t)row * N);
     float4 v[NV];
-    float s = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = i * 256 + t;
@@ -1018,25 +1021,28 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* __re
             }
             v[i] = make_float4(r.x + a.x, r.y + a.y, r.z + a.z, r.w + a.w);
         }
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        col[0][c] = (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    s = wave_sum(s);
-    if (lane == 0) red[0][wv] = s;
     __syncthreads();
-    const float mean = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / (float)N;
-    float q = 0.f;
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4 * NV; ++k) s += col[0][k * 64 + lane];
+    const float mean = wave_sum(s) / (float)N;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = i * 256 + t;
+        float e = 0.f;
         if (c < w4) {
             float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
+            e = (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
         }
+        col[1][c] = e;
     }
-    q = wave_sum(q);
-    if (lane == 0) red[1][wv] = q;
     __syncthreads();
-    const float rstd = rsqrtf(((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / (float)N + eps);
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4 * NV; ++k) q += col[1][k * 64 + lane];
+    const float rstd = rsqrtf(wave_sum(q) / (float)N + eps);
     uint2* yr = reinterpret_cast<uint2*>(y + (size_t)row * N);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -1976,6 +1982,7 @@ static bool gemm_splitk(const bf16_t* A, const bf16_t* Wt, const float* bias, in
         case EPI_QUICKGELU: launch_reduce<EPI_QUICKGELU>(part, S, m_valid, N, bias, out, st); break;
         case EPI_GELU: launch_reduce<EPI_GELU>(part, S, m_valid, N, bias, out, st); break;
         case EPI_GELU_TANH: launch_reduce<EPI_GELU_TANH>(part, S, m_valid, N, bias, out, st); break;
+        case EPI_RELU: launch_reduce<EPI_RELU>(part, S, m_valid, N, bias, out, st); break;
         case EPI_RESID: launch_reduce<EPI_RESID>(part, S, m_valid, N, bias, out, st); break;
         default: launch_reduce<EPI_F32>(part, S, m_valid, N, bias, out, st); break;
     }
@@ -1998,12 +2005,18 @@ int gemm_bf16_rows(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, 
 
 // x[M,N] += A @ Wt^T + bias (the residual GEMM of a block), then the LayerNorm that follows it: h = LN(x) as bf16, and for
 // post-LN blocks (post_ln) x = LN(x) as well.  Skinny calls (the text towers' single queries) run the split-K partial
-// kernel and ONE kernel for reduction + residual + LayerNorm; everything else is the two launches it stands for.  The same
-// bits either way.
+// kernel and ONE kernel for reduction + residual + LayerNorm; everything else is the two launches it stands for.
+// The same bits either way, x and h (and the normalised x of post_ln): the reduction adds in the split-K residual GEMM's
+// order and the fused kernel sums the row's statistics in layernorm_kernel's (tests/test_gpu_gemm_skinny.py holds both to
+// it).  It used not to: with the statistics summed per wave and then over the four waves, mean and rstd had other last bits,
+// a few elements in 10^5 of h landed on the neighbouring bf16 value, and one that ln_b cancelled to 9e-7 four values away.
+// The LayerNorm's width is checked here, before the first launch: a refused call leaves x as it was.
 int gemm_resid_ln_rows(const bf16_t* A, const bf16_t* Wt, const float* bias, int M, int m_valid, int ln_rows, int N, int K,
                        float* x, const float* ln_w, const float* ln_b, float eps, bool post_ln, bf16_t* h, hipStream_t st,
                        float* sk, size_t sk_bytes) {
     WISE_CHECK_ARG(A && Wt && x && ln_w && ln_b && h, "gemm_resid_ln: null pointer");
+    WISE_CHECK_ARG(N >= 4 && N % 4 == 0 && N <= 4096 && (!post_ln || N > 128),
+                   "gemm_resid_ln: N=%d must be a multiple of 4, <= 4096%s", N, post_ln ? " and > 128 (post-LN)" : "");
     // (ln_rows: the rows the LayerNorm covers — the caller's real rows; m_valid may include tile padding.  The fused
     // reduction holds a row of up to 4096 columns.)
     const GemmPlan p = gemm_plan(M, N, K, EPI_RESID, m_valid, g_overlapped != 0, device_cus(), g_gemm_variant);
@@ -2245,5 +2258,19 @@ extern "C" int wise_debug_gemm_plan(int kind, const int* a, int* out) {
         return 1;
     }
     return 0;
+}
+
+// The skinny-GEMM entry points as the towers call them (m_valid rows of data, the caller's split-K scratch), for
+// tests/test_gpu_gemm_skinny.py: the split-K pair and the fused reduction + LayerNorm have no other way in.
+extern "C" size_t wise_debug_gemm_splitk_bytes(int M, int m_valid, int N, int K) { return wise::gemm_splitk_bytes(M, m_valid, N, K); }
+extern "C" int wise_debug_gemm_rows(const uint16_t* A, const uint16_t* Wt, const float* bias, int M, int m_valid, int N, int K,
+                                    int mode, void* out, float* sk, size_t sk_bytes, void* stream) {
+    return wise::gemm_bf16_rows(A, Wt, bias, M, m_valid, N, K, mode, out, (hipStream_t)stream, sk, sk_bytes);
+}
+extern "C" int wise_debug_gemm_resid_ln_rows(const uint16_t* A, const uint16_t* Wt, const float* bias, int M, int m_valid,
+                                             int ln_rows, int N, int K, float* x, const float* ln_w, const float* ln_b, float eps,
+                                             int post_ln, uint16_t* h, float* sk, size_t sk_bytes, void* stream) {
+    return wise::gemm_resid_ln_rows(A, Wt, bias, M, m_valid, ln_rows, N, K, x, ln_w, ln_b, eps, post_ln != 0, h,
+                                    (hipStream_t)stream, sk, sk_bytes);
 }
 #endif  // WISE_DEBUG_KNOBS
