@@ -60,6 +60,11 @@ Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
 
+Every IVF record ends in the same inverted-list block, written and read by one piece of code (_write_lists, _read_lists,
+_read_lists_range) that the payload's row width and dtype parameterise.  read_index / read_index_range / index_ntotal pick the named
+reader by the file's fourcc and write_index the named writer by the state's keys; callers that do not care which family they hold
+(feature_search_index.py) use those four.
+
 faiss is not in the container, so these layouts are UNPINNED against a real faiss binary; the round
 trip is pinned by tests/test_feature_store_index_io.py.  The rows are memory-mapped on read so a
 158 GiB index (docs/Search-Index-Evaluation.md:109) streams to the GPU without a host copy.
@@ -150,38 +155,120 @@ def read_idmap_flat_ip(path, mmap: bool = True):
     return X, ids
 
 
+_IVF_RECORDS = {"IwFl": "IndexIVFFlat", "IwPQ": "IndexIVFPQ", "IwSq": "IndexIVFScalarQuantizer"}
+
+
+def _existing(path) -> Path:
+    """path as a Path; RuntimeError like faiss on a missing file"""
+    p = Path(path)
+    if not p.exists():
+        raise RuntimeError(f"Error: 'f' failed: could not open {p} for reading: No such file or directory")
+    return p
+
+
+def _expect_record(f, p, want: str) -> None:
+    """Read the fourcc the file stands at; RuntimeError unless it is the IVF record `want`."""
+    (cc,) = struct.unpack("<I", f.read(4))
+    if cc != _fourcc(want):
+        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {_IVF_RECORDS[want]}")
+
+
+def _record_ntotal(f, p, want: str) -> int:
+    """Rows of the IVF record `want` the file stands at (its header), without reading the lists."""
+    _expect_record(f, p, want)
+    return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+
+
+def _ivf_arrays(centroids, ids, list_off, n: int):
+    """What every IVF writer takes, as the contiguous arrays it writes: centroids [nlist,d] fp32, ids [n] and list_off [nlist+1]
+    int64 (list l is rows list_off[l] .. list_off[l+1]-1 of the payload)."""
+    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    assert ids.shape == (n,) and list_off.shape == (centroids.shape[0] + 1,) and list_off[-1] == n
+    return centroids, ids, list_off
+
+
+def _write_ivf_head(f, record: str, centroids, n: int, nprobe: int) -> None:
+    """What the 'IwFl', 'IwPQ' and 'IwSq' records open with: fourcc, header, nlist, nprobe, the 'IxFI' quantizer, an empty direct map."""
+    nlist, d = centroids.shape
+    f.write(struct.pack("<I", _fourcc(record)))
+    f.write(_header(d, n))
+    f.write(struct.pack("<QQ", nlist, nprobe))
+    f.write(struct.pack("<I", _fourcc("IxFI")))
+    f.write(_header(d, nlist))
+    f.write(struct.pack("<Q", nlist * d))
+    centroids.tofile(f)
+    f.write(struct.pack("<BQ", 0, 0))
+
+
+def _write_lists(f, payload, ids, list_off) -> None:
+    """The inverted-list block of every IVF record: the 'ilar' header with the payload's bytes per row as code_size, the 'full'
+    (or, when most lists are empty, 'sprs') size table, then per non-empty list its payload rows followed by its ids."""
+    nlist = list_off.shape[0] - 1
+    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
+    f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, payload.shape[1] * payload.dtype.itemsize))
+    nonzero = np.flatnonzero(sizes)
+    if len(nonzero) > nlist // 2:
+        f.write(struct.pack("<IQ", _fourcc("full"), nlist))
+        sizes.tofile(f)
+    else:
+        f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
+        np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
+    for l in nonzero:
+        a, b = int(list_off[l]), int(list_off[l + 1])
+        payload[a:b].tofile(f)
+        ids[a:b].tofile(f)
+
+
+def _read_lists_range(f, p, list_off, data: int, cols: int, dtype, lo: int, hi: int, who: str, strict: bool = False):
+    """Rows [lo, hi) of the list-major (payload [n,cols] dtype, ids [n]) of a list block whose first list starts at byte `data`,
+    reading only the lists that overlap the range: list l sits list_off[l] * (row bytes + 8) bytes in, its rows before its ids.
+    who: the reader's name, for the ValueError of a range outside [0, n].  strict: a list cut short is a RuntimeError that names
+    it ('IwSq'; the other records leave it to numpy's ValueError)."""
+    n, lo, hi = int(list_off[-1]), int(lo), int(hi)
+    if not (0 <= lo <= hi <= n):
+        raise ValueError(f"{who}: [{lo}, {hi}) outside [0, {n}]")
+    width = cols * np.dtype(dtype).itemsize
+    payload = np.empty((hi - lo, cols), dtype=dtype)
+    ids = np.empty((hi - lo,), dtype=np.int64)
+    first = int(np.searchsorted(list_off, lo, side="right")) - 1         # the list that holds row lo
+    for l in range(max(first, 0), len(list_off) - 1):
+        s0, s1 = int(list_off[l]), int(list_off[l + 1])
+        if s0 >= hi:
+            break
+        a, b = max(s0, lo), min(s1, hi)
+        if a >= b:
+            continue
+        base = data + s0 * (width + 8)
+        f.seek(base + (a - s0) * width)
+        c = np.fromfile(f, dtype=dtype, count=(b - a) * cols)
+        f.seek(base + (s1 - s0) * width + (a - s0) * 8)
+        i = np.fromfile(f, dtype=np.int64, count=b - a)
+        if strict and (c.size != (b - a) * cols or i.size != b - a):
+            raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
+        payload[a - lo:b - lo], ids[a - lo:b - lo] = c.reshape(b - a, cols), i
+    return payload, ids, np.clip(list_off - lo, 0, hi - lo)
+
+
+def _read_lists(f, p, list_off, data: int, cols: int, dtype, strict: bool = False):
+    """The whole list block: (payload [n,cols], ids [n]), the lists back to back in list order; the file is left at the block's end."""
+    n = int(list_off[-1])
+    payload, ids, _ = _read_lists_range(f, p, list_off, data, cols, dtype, 0, n, "", strict)
+    f.seek(data + n * (cols * np.dtype(dtype).itemsize + 8))
+    return payload, ids
+
+
+# ---------------------------------------------------------------------------------------------- 'IwFl': fp32 rows
 def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarray, list_off: np.ndarray,
                       nprobe: int = 1) -> None:
     """X / ids hold the lists back to back; list l is rows list_off[l] .. list_off[l+1]-1."""
-    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
     X = np.ascontiguousarray(X, dtype=np.float32)
-    ids = np.ascontiguousarray(ids, dtype=np.int64)
-    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
-    nlist, d = centroids.shape
-    n = X.shape[0]
-    assert X.shape == (n, d) and ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
-    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
+    centroids, ids, list_off = _ivf_arrays(centroids, ids, list_off, X.shape[0])
+    assert X.shape == (X.shape[0], centroids.shape[1])
     with open(path, "wb") as f:
-        f.write(struct.pack("<I", _fourcc("IwFl")))
-        f.write(_header(d, n))
-        f.write(struct.pack("<QQ", nlist, nprobe))
-        f.write(struct.pack("<I", _fourcc("IxFI")))
-        f.write(_header(d, nlist))
-        f.write(struct.pack("<Q", nlist * d))
-        centroids.tofile(f)
-        f.write(struct.pack("<BQ", 0, 0))
-        f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, 4 * d))
-        nonzero = np.flatnonzero(sizes)
-        if len(nonzero) > nlist // 2:
-            f.write(struct.pack("<IQ", _fourcc("full"), nlist))
-            sizes.tofile(f)
-        else:
-            f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
-            np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
-        for l in nonzero:
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            X[a:b].tofile(f)
-            ids[a:b].tofile(f)
+        _write_ivf_head(f, "IwFl", centroids, X.shape[0], nprobe)
+        _write_lists(f, X, ids, list_off)
 
 
 def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
@@ -189,10 +276,7 @@ def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks).
     sq: an 'IwSq' file instead; the ScalarQuantizer record's trained values [2d] are appended."""
     base = f.tell()                                          # (an 'IwPQ' record may sit inside a 'WiPR' file)
-    (cc,) = struct.unpack("<I", f.read(4))
-    want, name = ("IwPQ", "IndexIVFPQ") if pq else ("IwSq", "IndexIVFScalarQuantizer") if sq else ("IwFl", "IndexIVFFlat")
-    if cc != _fourcc(want):
-        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not {name}")
+    _expect_record(f, p, "IwPQ" if pq else "IwSq" if sq else "IwFl")
     hdr = f.read(_HDR_SIZE + 4)
     d, n, metric, off = _read_header(hdr, 0)
     f.seek(base + 4 + off)
@@ -254,38 +338,21 @@ def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     return centroids, list_off, int(nprobe), f.tell()
 
 
-def _missing(p):
-    return RuntimeError(f"Error: 'f' failed: could not open {p} for reading: No such file or directory")
-
-
 def read_ivf_flat_ip(path):
     """-> dict(centroids [nlist,d], X [n,d], ids [n], list_off [nlist+1], nprobe).  The lists are returned back to
     back in list order, which is the layout the search kernel wants."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        centroids, list_off, nprobe, _ = _read_ivf_head(f, p)
-        d, n = centroids.shape[1], int(list_off[-1])
-        X = np.empty((n, d), dtype=np.float32)
-        ids = np.empty((n,), dtype=np.int64)
-        for l in np.flatnonzero(np.diff(list_off)):
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            X[a:b] = np.fromfile(f, dtype=np.float32, count=(b - a) * d).reshape(b - a, d)
-            ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
+        centroids, list_off, nprobe, data = _read_ivf_head(f, p)
+        X, ids = _read_lists(f, p, list_off, data, centroids.shape[1], np.float32)
     return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe}
 
 
 def ivf_flat_ip_ntotal(path) -> int:
     """Rows of an 'IwFl' file (its header), without reading the lists."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        (cc,) = struct.unpack("<I", f.read(4))
-        if cc != _fourcc("IwFl"):
-            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFFlat")
-        return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+        return _record_ntotal(f, p, "IwFl")
 
 
 def read_ivf_flat_ip_range(path, lo: int, hi: int):
@@ -293,88 +360,54 @@ def read_ivf_flat_ip_range(path, lo: int, hi: int):
     (one rank's slice of an index sharded across GPUs: wise_amd/index/sharded.py).
     -> dict(centroids [nlist,d] (all of them), X [hi-lo,d], ids [hi-lo], list_off [nlist+1] = clip(list_off - lo, 0,
     hi - lo), nprobe).  List l's payload sits at list_off[l] * (4d + 8) bytes into the payload (rows, then ids)."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         centroids, list_off, nprobe, data = _read_ivf_head(f, p)
-        d, n = centroids.shape[1], int(list_off[-1])
-        lo, hi = int(lo), int(hi)
-        if not (0 <= lo <= hi <= n):
-            raise ValueError(f"read_ivf_flat_ip_range: [{lo}, {hi}) outside [0, {n}]")
-        X = np.empty((hi - lo, d), dtype=np.float32)
-        ids = np.empty((hi - lo,), dtype=np.int64)
-        sizes = np.diff(list_off)
-        first = int(np.searchsorted(list_off, lo, side="right")) - 1     # the list that holds row lo
-        for l in range(max(first, 0), len(sizes)):
-            s0, s1 = int(list_off[l]), int(list_off[l + 1])
-            if s0 >= hi:
-                break
-            a, b = max(s0, lo), min(s1, hi)
-            if a >= b:
-                continue
-            base = data + s0 * (4 * d + 8)
-            f.seek(base + (a - s0) * 4 * d)
-            X[a - lo:b - lo] = np.fromfile(f, dtype=np.float32, count=(b - a) * d).reshape(b - a, d)
-            f.seek(base + (s1 - s0) * 4 * d + (a - s0) * 8)
-            ids[a - lo:b - lo] = np.fromfile(f, dtype=np.int64, count=b - a)
-    return {"centroids": centroids, "X": X, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
-            "nprobe": nprobe}
+        X, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1], np.float32, lo, hi, "read_ivf_flat_ip_range")
+    return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+
+
+# ---------------------------------------------------------------------------------------------- 'IwPQ': m code bytes a row
+def _pq_arrays(centroids, codebooks, codes, ids, list_off):
+    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    n, m = codes.shape
+    centroids, ids, list_off = _ivf_arrays(centroids, ids, list_off, n)
+    d = centroids.shape[1]
+    assert d % m == 0 and codebooks.shape == (m, 256, d // m)
+    return centroids, codebooks, codes, ids, list_off
+
+
+def _refine_arrays(n: int, d: int, kind, k_factor, rows, scales):
+    assert kind in (8, 16) and k_factor is not None and k_factor >= 1
+    rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
+    assert rows.shape == (n, d)
+    if kind == 8:
+        scales = np.ascontiguousarray(scales, dtype=np.float32)
+        assert scales.shape == (n,)
+    return rows, scales
 
 
 def write_ivf_pq_ip(path, centroids: np.ndarray, codebooks: np.ndarray, codes: np.ndarray, ids: np.ndarray,
                     list_off: np.ndarray, nprobe: int = 1) -> None:
     """codes [n,m] uint8 / ids hold the lists back to back; codebooks [m,256,d/m] fp32 (8-bit codes, by_residual)."""
-    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
-    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-    codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    ids = np.ascontiguousarray(ids, dtype=np.int64)
-    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
-    nlist, d = centroids.shape
-    n, m = codes.shape
-    assert d % m == 0 and codebooks.shape == (m, 256, d // m)
-    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    pq = _pq_arrays(centroids, codebooks, codes, ids, list_off)
     with open(path, "wb") as f:
-        _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+        _write_ivf_pq_record(f, *pq, nprobe)
 
 
 def _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe) -> None:
-    (nlist, d), (n, m) = centroids.shape, codes.shape
-    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
-    f.write(struct.pack("<I", _fourcc("IwPQ")))
-    f.write(_header(d, n))
-    f.write(struct.pack("<QQ", nlist, nprobe))
-    f.write(struct.pack("<I", _fourcc("IxFI")))
-    f.write(_header(d, nlist))
-    f.write(struct.pack("<Q", nlist * d))
-    centroids.tofile(f)
-    f.write(struct.pack("<BQ", 0, 0))
+    d, (n, m) = centroids.shape[1], codes.shape
+    _write_ivf_head(f, "IwPQ", centroids, n, nprobe)
     f.write(struct.pack("<BQ", 1, m))                        # by_residual, code_size
     f.write(struct.pack("<QQQQ", d, m, 8, 256 * d))          # ProductQuantizer: d, M, nbits, centroids
     codebooks.tofile(f)
-    f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, m))
-    nonzero = np.flatnonzero(sizes)
-    if len(nonzero) > nlist // 2:
-        f.write(struct.pack("<IQ", _fourcc("full"), nlist))
-        sizes.tofile(f)
-    else:
-        f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
-        np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
-    for l in nonzero:
-        a, b = int(list_off[l]), int(list_off[l + 1])
-        codes[a:b].tofile(f)
-        ids[a:b].tofile(f)
+    _write_lists(f, codes, ids, list_off)
 
 
 def _read_ivf_pq_record(f, p):
-    centroids, list_off, nprobe, _, m, codebooks = _read_ivf_head(f, p, pq=True)
-    n = int(list_off[-1])
-    codes = np.empty((n, m), dtype=np.uint8)
-    ids = np.empty((n,), dtype=np.int64)
-    for l in np.flatnonzero(np.diff(list_off)):
-        a, b = int(list_off[l]), int(list_off[l + 1])
-        codes[a:b] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
-        ids[a:b] = np.fromfile(f, dtype=np.int64, count=b - a)
+    centroids, list_off, nprobe, data, m, codebooks = _read_ivf_head(f, p, pq=True)
+    codes, ids = _read_lists(f, p, list_off, data, m, np.uint8)
     return {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off,
             "nprobe": nprobe}
 
@@ -385,56 +418,36 @@ def _read_ivf_pq_record_range(f, p, lo: int, hi: int):
     record)."""
     centroids, list_off, nprobe, data, m, codebooks = _read_ivf_head(f, p, pq=True)
     n = int(list_off[-1])
-    lo, hi = int(lo), int(hi)
-    if not (0 <= lo <= hi <= n):
-        raise ValueError(f"read_ivf_pq_ip_range: [{lo}, {hi}) outside [0, {n}]")
-    codes = np.empty((hi - lo, m), dtype=np.uint8)
-    ids = np.empty((hi - lo,), dtype=np.int64)
-    first = int(np.searchsorted(list_off, lo, side="right")) - 1         # the list that holds row lo
-    for l in range(max(first, 0), len(list_off) - 1):
-        s0, s1 = int(list_off[l]), int(list_off[l + 1])
-        if s0 >= hi:
-            break
-        a, b = max(s0, lo), min(s1, hi)
-        if a >= b:
-            continue
-        base = data + s0 * (m + 8)
-        f.seek(base + (a - s0) * m)
-        codes[a - lo:b - lo] = np.fromfile(f, dtype=np.uint8, count=(b - a) * m).reshape(b - a, m)
-        f.seek(base + (s1 - s0) * m + (a - s0) * 8)
-        ids[a - lo:b - lo] = np.fromfile(f, dtype=np.int64, count=b - a)
-    out = {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
-           "nprobe": nprobe}
+    codes, ids, list_off = _read_lists_range(f, p, list_off, data, m, np.uint8, lo, hi, "read_ivf_pq_ip_range")
+    out = {"centroids": centroids, "codebooks": codebooks, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
     return out, n, data + n * (m + 8)
-
-
-def _pq_ntotal(f, p) -> int:
-    (cc,) = struct.unpack("<I", f.read(4))
-    if cc != _fourcc("IwPQ"):
-        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFPQ")
-    return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
 
 
 def ivf_pq_ip_ntotal(path) -> int:
     """Rows of an 'IwPQ' file (its header), without reading the lists."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        return _pq_ntotal(f, p)
+        return _record_ntotal(f, p, "IwPQ")
 
 
 def read_ivf_pq_ip_range(path, lo: int, hi: int):
     """Rows [lo, hi) of the list-major arrays read_ivf_pq_ip returns, reading only the lists that overlap the range (one rank's
     slice of an index sharded across GPUs: wise_amd/index/sharded.py).  -> the dict of read_ivf_pq_ip with codes [hi-lo,m],
     ids [hi-lo] and list_off = clip(list_off - lo, 0, hi - lo); centroids and codebooks are whole."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         return _read_ivf_pq_record_range(f, p, lo, hi)[0]
 
 
+def read_ivf_pq_ip(path):
+    """-> dict(centroids [nlist,d], codebooks [m,256,d/m], codes [n,m] uint8, ids [n], list_off [nlist+1], nprobe), the
+    lists back to back in list order."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        return _read_ivf_pq_record(f, p)
+
+
+# ---------------------------------------------------------------------------------------------- 'WiPR': a PQ record + compact rows
 def _read_refine_head(f, p):
     cc, version, kind, k_factor = struct.unpack("<IIII", f.read(16))
     if cc != _fourcc("WiPR") or version != 1 or kind not in (8, 16) or k_factor < 1:
@@ -445,20 +458,16 @@ def _read_refine_head(f, p):
 
 def ivf_pq_refine_ip_ntotal(path) -> int:
     """Rows of a 'WiPR' file (the header of its 'IwPQ' record), without reading the lists."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         _read_refine_head(f, p)
-        return _pq_ntotal(f, p)
+        return _record_ntotal(f, p, "IwPQ")
 
 
 def read_ivf_pq_refine_ip_range(path, lo: int, hi: int):
     """read_ivf_pq_ip_range for a 'WiPR' file: also rows [lo, hi) of the compact rows and of the scales, read by position (they
     are stored in list order as two plain arrays).  -> the dict of read_ivf_pq_refine_ip over the slice."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         return _read_refine_record_range(f, p, lo, hi)
 
@@ -487,36 +496,14 @@ def _read_refine_record_range(f, p, lo: int, hi: int):
     return out
 
 
-def read_ivf_pq_ip(path):
-    """-> dict(centroids [nlist,d], codebooks [m,256,d/m], codes [n,m] uint8, ids [n], list_off [nlist+1], nprobe), the
-    lists back to back in list order."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
-    with open(p, "rb") as f:
-        return _read_ivf_pq_record(f, p)
-
-
 def write_ivf_pq_refine_ip(path, centroids, codebooks, codes, ids, list_off, kind: int, k_factor: int, rows: np.ndarray,
                            scales=None, nprobe: int = 1) -> None:
     """An 'IwPQ' record plus the compact rows of a re-ranking index in the same list order: rows [n,d] int8 with scales [n]
     fp32 (kind 8) or rows [n,d] uint16 bf16 bit patterns (kind 16).  This repository's own format (module docstring)."""
-    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
-    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-    codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    ids = np.ascontiguousarray(ids, dtype=np.int64)
-    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
-    nlist, d = centroids.shape
-    n, m = codes.shape
-    assert kind in (8, 16) and k_factor >= 1
-    rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
-    assert d % m == 0 and codebooks.shape == (m, 256, d // m) and rows.shape == (n, d)
-    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
-    if kind == 8:
-        scales = np.ascontiguousarray(scales, dtype=np.float32)
-        assert scales.shape == (n,)
+    pq = _pq_arrays(centroids, codebooks, codes, ids, list_off)
+    rows, scales = _refine_arrays(pq[2].shape[0], pq[0].shape[1], kind, k_factor, rows, scales)
     with open(path, "wb") as f:
-        _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe)
+        _write_refine_record(f, *pq, kind, k_factor, rows, scales, nprobe)
 
 
 def _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe) -> None:
@@ -531,9 +518,7 @@ def _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_
 
 def read_ivf_pq_refine_ip(path):
     """-> the dict of read_ivf_pq_ip plus kind, k_factor, rows [n,d] (int8 / uint16 bf16 bits) and scales [n] (None for kind 16)."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         return _read_refine_record(f, p)
 
@@ -563,30 +548,19 @@ def write_ivf_opq_ip(path, rotation: np.ndarray, centroids, codebooks, codes, id
     """The file of IndexIVFOPQ<m> (kind None: wraps an 'IwPQ' record) and IndexIVFOPQ<m>R8 / R16 (kind 8 / 16 with k_factor, rows
     and scales as write_ivf_pq_refine_ip takes them: wraps a 'WiPR' record).  rotation [d,d] fp32, row-major.  This repository's own
     format (module docstring)."""
-    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
-    codebooks = np.ascontiguousarray(codebooks, dtype=np.float32)
-    codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    ids = np.ascontiguousarray(ids, dtype=np.int64)
-    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
+    pq = _pq_arrays(centroids, codebooks, codes, ids, list_off)
     rotation = np.ascontiguousarray(rotation, dtype=np.float32)
-    nlist, d = centroids.shape
-    n, m = codes.shape
-    assert rotation.shape == (d, d) and d % m == 0 and codebooks.shape == (m, 256, d // m)
-    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
+    n, d = pq[2].shape[0], pq[0].shape[1]
+    assert rotation.shape == (d, d)
     if kind is not None:
-        assert kind in (8, 16) and k_factor is not None and k_factor >= 1
-        rows = np.ascontiguousarray(rows, dtype=np.int8 if kind == 8 else np.uint16)
-        assert rows.shape == (n, d)
-        if kind == 8:
-            scales = np.ascontiguousarray(scales, dtype=np.float32)
-            assert scales.shape == (n,)
+        rows, scales = _refine_arrays(n, d, kind, k_factor, rows, scales)
     with open(path, "wb") as f:
         f.write(struct.pack("<III", _fourcc("WiOP"), 1, d))
         rotation.tofile(f)
         if kind is None:
-            _write_ivf_pq_record(f, centroids, codebooks, codes, ids, list_off, nprobe)
+            _write_ivf_pq_record(f, *pq, nprobe)
         else:
-            _write_refine_record(f, centroids, codebooks, codes, ids, list_off, kind, k_factor, rows, scales, nprobe)
+            _write_refine_record(f, *pq, kind, k_factor, rows, scales, nprobe)
 
 
 def _read_opq_head(f, p):
@@ -614,9 +588,7 @@ def _with_rotation(out, rotation, p):
 
 def read_ivf_opq_ip(path):
     """-> the dict of read_ivf_pq_ip or of read_ivf_pq_refine_ip (the latter has 'kind'), plus rotation [d,d] fp32."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         rotation, inner = _read_opq_head(f, p)
         return _with_rotation(_read_ivf_pq_record(f, p) if inner == _fourcc("IwPQ") else _read_refine_record(f, p), rotation, p)
@@ -624,22 +596,18 @@ def read_ivf_opq_ip(path):
 
 def ivf_opq_ip_ntotal(path) -> int:
     """Rows of a 'WiOP' file (the header of its 'IwPQ' record), without reading the lists."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         _, inner = _read_opq_head(f, p)
         if inner == _fourcc("WiPR"):
             _read_refine_head(f, p)
-        return _pq_ntotal(f, p)
+        return _record_ntotal(f, p, "IwPQ")
 
 
 def read_ivf_opq_ip_range(path, lo: int, hi: int):
     """Rows [lo, hi) of the list-major arrays read_ivf_opq_ip returns, as read_ivf_pq_ip_range / read_ivf_pq_refine_ip_range cut them
     out of the wrapped record; the rotation is whole."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
         rotation, inner = _read_opq_head(f, p)
         out = _read_ivf_pq_record_range(f, p, lo, hi)[0] if inner == _fourcc("IwPQ") else _read_refine_record_range(f, p, lo, hi)
@@ -650,77 +618,43 @@ def read_ivf_opq_ip_range(path, lo: int, hi: int):
 def write_ivf_sq_ip(path, centroids: np.ndarray, trained: np.ndarray, codes: np.ndarray, ids: np.ndarray, list_off: np.ndarray,
                     nprobe: int = 1) -> None:
     """codes [n,d] uint8 / ids hold the lists back to back; trained [2d] fp32 = vmin, then vdiff (QT_8bit, by_residual)."""
-    centroids = np.ascontiguousarray(centroids, dtype=np.float32)
     trained = np.ascontiguousarray(trained, dtype=np.float32)
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
-    ids = np.ascontiguousarray(ids, dtype=np.int64)
-    list_off = np.ascontiguousarray(list_off, dtype=np.int64)
-    nlist, d = centroids.shape
     n = codes.shape[0]
+    centroids, ids, list_off = _ivf_arrays(centroids, ids, list_off, n)
+    d = centroids.shape[1]
     assert codes.shape == (n, d) and trained.shape == (2 * d,)
-    assert ids.shape == (n,) and list_off.shape == (nlist + 1,) and list_off[-1] == n
-    sizes = (list_off[1:] - list_off[:-1]).astype(np.uint64)
     with open(path, "wb") as f:
-        f.write(struct.pack("<I", _fourcc("IwSq")))
-        f.write(_header(d, n))
-        f.write(struct.pack("<QQ", nlist, nprobe))
-        f.write(struct.pack("<I", _fourcc("IxFI")))
-        f.write(_header(d, nlist))
-        f.write(struct.pack("<Q", nlist * d))
-        centroids.tofile(f)
-        f.write(struct.pack("<BQ", 0, 0))
+        _write_ivf_head(f, "IwSq", centroids, n, nprobe)
         f.write(struct.pack("<iifQQ", QT_8BIT, 0, 0.0, d, d))          # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
         f.write(struct.pack("<Q", 2 * d))
         trained.tofile(f)
         f.write(struct.pack("<QB", d, 1))                        # code_size, by_residual
-        f.write(struct.pack("<IQQ", _fourcc("ilar"), nlist, d))
-        nonzero = np.flatnonzero(sizes)
-        if len(nonzero) > nlist // 2:
-            f.write(struct.pack("<IQ", _fourcc("full"), nlist))
-            sizes.tofile(f)
-        else:
-            f.write(struct.pack("<IQ", _fourcc("sprs"), 2 * len(nonzero)))
-            np.stack([nonzero.astype(np.uint64), sizes[nonzero]], axis=1).tofile(f)
-        for l in nonzero:
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            codes[a:b].tofile(f)
-            ids[a:b].tofile(f)
+        _write_lists(f, codes, ids, list_off)
+
+
+def _read_ivf_sq_head(f, p):
+    try:
+        return _read_ivf_head(f, p, sq=True)
+    except (struct.error, ValueError) as e:
+        raise RuntimeError(f"{p}: the head of an IndexIVFScalarQuantizer file is cut short ({e})") from None
 
 
 def read_ivf_sq_ip(path):
     """-> dict(centroids [nlist,d], trained [2d] (vmin, then vdiff), codes [n,d] uint8, ids [n], list_off [nlist+1], nprobe), the
     lists back to back in list order.  A file cut short is refused (RuntimeError)."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        try:
-            centroids, list_off, nprobe, _, trained = _read_ivf_head(f, p, sq=True)
-        except (struct.error, ValueError) as e:
-            raise RuntimeError(f"{p}: the head of an IndexIVFScalarQuantizer file is cut short ({e})") from None
-        n, d = int(list_off[-1]), centroids.shape[1]
-        codes = np.empty((n, d), dtype=np.uint8)
-        ids = np.empty((n,), dtype=np.int64)
-        for l in np.flatnonzero(np.diff(list_off)):
-            a, b = int(list_off[l]), int(list_off[l + 1])
-            c = np.fromfile(f, dtype=np.uint8, count=(b - a) * d)
-            i = np.fromfile(f, dtype=np.int64, count=b - a)
-            if c.size != (b - a) * d or i.size != b - a:
-                raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
-            codes[a:b], ids[a:b] = c.reshape(b - a, d), i
+        centroids, list_off, nprobe, data, trained = _read_ivf_sq_head(f, p)
+        codes, ids = _read_lists(f, p, list_off, data, centroids.shape[1], np.uint8, strict=True)
     return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
 
 
 def ivf_sq_ip_ntotal(path) -> int:
     """Rows of an 'IwSq' file (its header), without reading the lists."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        (cc,) = struct.unpack("<I", f.read(4))
-        if cc != _fourcc("IwSq"):
-            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIVFScalarQuantizer")
-        return int(_read_header(f.read(_HDR_SIZE + 4), 0)[1])
+        return _record_ntotal(f, p, "IwSq")
 
 
 def read_ivf_sq_ip_range(path, lo: int, hi: int):
@@ -728,40 +662,68 @@ def read_ivf_sq_ip_range(path, lo: int, hi: int):
     slice of an index sharded across GPUs: wise_amd/index/sharded.py).  -> the dict of read_ivf_sq_ip with codes [hi-lo,d],
     ids [hi-lo] and list_off = clip(list_off - lo, 0, hi - lo); centroids and trained are whole.  List l's payload sits at
     list_off[l] * (d + 8) bytes into the payload (codes, then ids)."""
-    p = Path(path)
-    if not p.exists():
-        raise _missing(p)
+    p = _existing(path)
     with open(p, "rb") as f:
-        try:
-            centroids, list_off, nprobe, data, trained = _read_ivf_head(f, p, sq=True)
-        except (struct.error, ValueError) as e:
-            raise RuntimeError(f"{p}: the head of an IndexIVFScalarQuantizer file is cut short ({e})") from None
-        n, d = int(list_off[-1]), centroids.shape[1]
-        lo, hi = int(lo), int(hi)
-        if not (0 <= lo <= hi <= n):
-            raise ValueError(f"read_ivf_sq_ip_range: [{lo}, {hi}) outside [0, {n}]")
-        codes = np.empty((hi - lo, d), dtype=np.uint8)
-        ids = np.empty((hi - lo,), dtype=np.int64)
-        first = int(np.searchsorted(list_off, lo, side="right")) - 1         # the list that holds row lo
-        for l in range(max(first, 0), len(list_off) - 1):
-            s0, s1 = int(list_off[l]), int(list_off[l + 1])
-            if s0 >= hi:
-                break
-            a, b = max(s0, lo), min(s1, hi)
-            if a >= b:
-                continue
-            base = data + s0 * (d + 8)
-            f.seek(base + (a - s0) * d)
-            c = np.fromfile(f, dtype=np.uint8, count=(b - a) * d)
-            f.seek(base + (s1 - s0) * d + (a - s0) * 8)
-            i = np.fromfile(f, dtype=np.int64, count=b - a)
-            if c.size != (b - a) * d or i.size != b - a:
-                raise RuntimeError(f"{p}: list {l} is cut short ({c.size} code bytes and {i.size} ids for {b - a} rows)")
-            codes[a - lo:b - lo], ids[a - lo:b - lo] = c.reshape(b - a, d), i
-    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": np.clip(list_off - lo, 0, hi - lo),
-            "nprobe": nprobe}
+        centroids, list_off, nprobe, data, trained = _read_ivf_sq_head(f, p)
+        codes, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1], np.uint8, lo, hi, "read_ivf_sq_ip_range",
+                                                 strict=True)
+    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
 
 
 def index_fourcc(path) -> str:
     with open(path, "rb") as f:
         return f.read(4).decode("ascii", errors="replace")
+
+
+# ---------------------------------------------------------------------------------------------- any IVF file, by its fourcc
+_BY_FOURCC = {                                    # fourcc -> (reader, range reader, ntotal)
+    "IwFl": (read_ivf_flat_ip, read_ivf_flat_ip_range, ivf_flat_ip_ntotal),
+    "IwPQ": (read_ivf_pq_ip, read_ivf_pq_ip_range, ivf_pq_ip_ntotal),
+    "WiPR": (read_ivf_pq_refine_ip, read_ivf_pq_refine_ip_range, ivf_pq_refine_ip_ntotal),
+    "WiOP": (read_ivf_opq_ip, read_ivf_opq_ip_range, ivf_opq_ip_ntotal),
+    "IwSq": (read_ivf_sq_ip, read_ivf_sq_ip_range, ivf_sq_ip_ntotal),
+}
+
+
+def _by_fourcc(path, which: int):
+    p = _existing(path)
+    cc = index_fourcc(p)
+    if cc not in _BY_FOURCC:
+        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(_BY_FOURCC)})")
+    return _BY_FOURCC[cc][which]
+
+
+def read_index(path):
+    """The dict of the named reader of the file's record: read_ivf_flat_ip ('IwFl'), read_ivf_pq_ip ('IwPQ'), read_ivf_pq_refine_ip
+    ('WiPR'), read_ivf_opq_ip ('WiOP') or read_ivf_sq_ip ('IwSq').  (The flat 'IxMp' file holds no lists: read_idmap_flat_ip.)"""
+    return _by_fourcc(path, 0)(path)
+
+
+def read_index_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major arrays read_index returns, by the range reader of the file's record."""
+    return _by_fourcc(path, 1)(path, lo, hi)
+
+
+def index_ntotal(path) -> int:
+    """Rows of an IVF file of any record (its header), without reading the lists."""
+    return _by_fourcc(path, 2)(path)
+
+
+def write_index(path, state, nprobe=None) -> None:
+    """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
+    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'X': 'IwFl'.  nprobe: state's own unless given."""
+    nprobe = state.get("nprobe", 1) if nprobe is None else nprobe
+    lists = (state["ids"], state["list_off"])
+    store = {k: state[k] for k in ("kind", "k_factor", "rows", "scales") if k in state}
+    if "rotation" in state:
+        write_ivf_opq_ip(path, state["rotation"], state["centroids"], state["codebooks"], state["codes"], *lists, nprobe=nprobe, **store)
+    elif "kind" in state:
+        write_ivf_pq_refine_ip(path, state["centroids"], state["codebooks"], state["codes"], *lists, nprobe=nprobe, **store)
+    elif "codebooks" in state:
+        write_ivf_pq_ip(path, state["centroids"], state["codebooks"], state["codes"], *lists, nprobe=nprobe)
+    elif "trained" in state:
+        write_ivf_sq_ip(path, state["centroids"], state["trained"], state["codes"], *lists, nprobe=nprobe)
+    elif "X" in state:
+        write_ivf_flat_ip(path, state["centroids"], state["X"], *lists, nprobe=nprobe)
+    else:
+        raise TypeError(f"write_index: no record for a state of {sorted(state)}")

@@ -11,13 +11,26 @@ Same constructor contract (asserts on 'features_dir'/'index_dir'), prompts, file
 (`{index_dir}/{media_type}-{index_type}.faiss`), skip-if-exists create, `load_index` that also
 builds the FeatureExtractor, and the prompt quirks of `search`.  Both index types the
 reference offers are built: `IndexFlatIP` (exhaustive, the hot path) and `IndexIVFFlat` (approximate; cell count
-and training-sample size chosen as at feature_search_index.py:55-59, k-means and list scan on the GPU).  A third,
-`IndexIVFPQ<m>` (for example `IndexIVFPQ64`; bare `IndexIVFPQ` = m = d / 4), is the IVF+PQ family of the reference's index
-study (docs/Search-Index-Evaluation.md:105-123): the same coarse stage over lists of m-byte codes (wise_amd/index/ivf_pq.py).
-`IndexIVFPQ<m>R8` / `IndexIVFPQ<m>R16` (for example `IndexIVFPQ64R8`) are that index with a re-ranking stage over compact rows kept
-beside the codes (int8 + a scale per row / bf16; IVFPQRefineIPIndex, faiss's IndexRefine); their file is this repository's own
-format (faiss_io.py, 'WiPR').  Under a process group the three behave as IndexIVFFlat does: without WISE_SHARDED_IVF=1 rank 0
-builds and every rank loads the whole file; with it they are sharded by list-major row ranges (below).
+and training-sample size chosen as at feature_search_index.py:55-59, k-means and list scan on the GPU).  The other inverted-file
+types are the IVF+PQ family of the reference's index study (docs/Search-Index-Evaluation.md:105-123) and its neighbours.  Each is
+one entry of FAMILIES below: what it adds to IndexIVFFlat is its trained state, its per-row list payload and its file record.
+
+    index type (example)             class (ivf_flat.py, ivf_pq.py, ivf_sq.py)   trained beyond the centroids   a row in its list             file record (faiss_io.py)
+    IndexIVFFlat                     IVFFlatIPIndex          -                              the fp32 row                  'IwFl' (faiss)
+    IndexIVFPQ<m> (IndexIVFPQ64)     IVFPQIPIndex            codebooks [m,256,d/m]          m code bytes                  'IwPQ' (faiss)
+    IndexIVFPQ<m>R8 / R16            IVFPQRefineIPIndex      codebooks                      codes + a compact row to      'WiPR' (own) around 'IwPQ'
+                                                                                            re-rank from: int8 and a
+                                                                                            scale (R8) / bf16 (R16)
+    IndexIVFOPQ<m>, ...R8 / R16      IVFOPQIPIndex,          codebooks, rotation [d,d]      as their IndexIVFPQ forms     'WiOP' (own) around 'IwPQ'
+                                     IVFOPQRefineIPIndex     of the residuals (faiss's OPQ)                               / 'WiPR'
+    IndexIVFSQ8                      IVFSQIPIndex            ranges [2d]: vmin, vdiff       d code bytes (QT_8bit)        'IwSq' (faiss)
+
+The bare names `IndexIVFPQ` / `IndexIVFOPQ` mean m = d / 4.  Everything below is written once and driven by that table.
+
+**One process** builds an IVF index by training on a seeded sample of min(N, 100 nlist) rows, adding every row, and writing
+`index.state_host()` with `faiss_io.write_index`; it loads one with `faiss_io.read_index` and `_local_index`, which rebuilds the
+index object from the reader's dict through the family's `*_index_factory` attribute.  `update_index` is that load, `remove_ids` /
+`add_with_ids` against the state as trained, and that write.
 
 **One process per GPU** (the reference has no distributed path).  When `torch.distributed` is initialised
 with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the flat index by rows:
@@ -27,46 +40,28 @@ with more than one rank (or WISE_SHARDED_INDEX=1), the same two calls shard the 
     `shard_range(N, r, W)` of the single `.faiss` file — memory-mapped, so a rank touches only its own rows' pages —
     and `self.index` is a `ShardedFlatIPIndex`: `search` / `reconstruct_batch` are then collective (every rank calls
     them with the same arguments and gets the global answer: one all-gather of per-shard top-k + `wise_topk_merge`).
-IndexIVFFlat is sharded too when WISE_SHARDED_IVF=1 is also set (opt-in; without it, and without IVF part files, every
-rank loads the whole file and rank 0 alone builds it).  The index is then one list-major array cut by `shard_range`
-(wise_amd/index/sharded.py: rank r holds the whole centroid table and rows shard_range(N, r, W) of list 0's rows, then
-list 1's, ...):
-  * `create_index('IndexIVFFlat')`: rank r reads only its own store shard files; the ranks train once on a seeded sample
-    of min(N, 100 nlist) rows drawn from all of them (rank 0 trains, the centroids are broadcast), each rank assigns its
-    own rows, one all-gather of the per-rank list counts fixes the global order (within a list: by source rank, then
-    source order), one all_to_all moves rows and ids to the rank that owns their position, and each rank writes
-    `{media_type}-IndexIVFFlat.faiss.part-RRR-of-WWW` — a complete IVF file (all centroids, its clipped lists); the parts
-    laid end to end are the single-file layout;
-  * `load_index('IndexIVFFlat')`: the rank's part file if the parts of this world size exist, otherwise (with the
-    switch on) rows shard_range(N, r, W) of the single file, reading only the lists that overlap them; `self.index` is a
-    `ShardedIVFFlatIPIndex`, whose `search` / `reconstruct_batch` are collective and return the one-GPU IVF answer.
-`IndexIVFPQ<m>` and `IndexIVFPQ<m>R8` / `R16` take the same two paths under the same switch:
-  * `create_index`: the same collective build with a per-row byte payload in place of the fp32 row.  Rank 0 trains the coarse
-    stage AND the codebooks on the seeded sample gathered from all ranks; centroids and codebooks are broadcast; each rank
-    assigns and encodes its own rows on its GPU (and builds their compact rows and scales); the all_to_all moves codes
-    (+ compact rows, scales), ids and positions.  No rank holds fp32 rows other than those of its own store shards.  The part
-    files are complete 'IwPQ' / 'WiPR' files with clipped lists;
-  * `load_index`: the ranks agree ONCE (an all-reduce of "my part exists") whether all of them read part files or all of them
-    read rows shard_range(N, r, W) of the single file, so a missing part cannot mix the two sources; `self.index` is a
-    `ShardedIVFPQIPIndex` (one exchange per search) or a `ShardedIVFPQRefineIPIndex` (two: candidates, then re-ranked answers),
-    both returning the bits of the one-GPU index over the same centroids, codebooks, codes and stores.
-`IndexIVFOPQ<m>` and `IndexIVFOPQ<m>R8` / `R16` are the three IVF+PQ types behind a learned rotation of the residuals (faiss's OPQ;
-ivf_pq.py: IVFOPQIPIndex, IVFOPQRefineIPIndex); their file wraps the PQ record in a 'WiOP' record that carries the rotation
-(faiss_io.py).  They take every path above as their IndexIVFPQ counterparts do: in the collective build rank 0 also trains the
-rotation, which is broadcast with the codebooks; each rank rotates its own rows and, in a search, the query — the rotation is
-replicated, so the sharded classes and their exchanges are the same.
-`IndexIVFSQ8` is the inverted file over one byte per dimension (faiss's IndexIVFScalarQuantizer, QT_8bit; ivf_sq.py: IVFSQIPIndex;
-file: faiss's 'IwSq' record, faiss_io.py).  Under a process group it behaves as the types above: without WISE_SHARDED_IVF=1 rank 0
-builds the one file and every rank loads it; with it
-  * `create_index`: the same collective build.  Rank 0 trains the coarse stage AND the per-dimension ranges on the seeded sample
-    the single-file build draws; the [2d] ranges are broadcast with the centroids; each rank assigns and encodes its own rows on
-    its GPU; the payload that travels is the row's d code bytes; each rank writes a complete 'IwSq' part with clipped lists.  The
-    parts laid end to end are the codes, ids and offsets of the one-process build, byte for byte;
-  * `load_index`: parts or ranges of the single file, decided once for the group as for IndexIVFPQ; `self.index` is a
-    `ShardedIVFSQIPIndex` (one exchange per search) that returns the bits of the one-GPU index.
+The inverted-file types are sharded too when WISE_SHARDED_IVF=1 is also set (opt-in; without it, and without part files, rank 0
+alone builds the one file — k-means needs every row — and every rank loads all of it).  The index is then one list-major array cut
+by `shard_range` (wise_amd/index/sharded.py: rank r holds the whole trained state and rows shard_range(N, r, W) of list 0's rows,
+then list 1's, ...):
+  * the build (`_create_sharded_ivf`): rank r reads only its own store shard files; rank 0 trains once on the seeded sample the
+    one-process build draws, gathered from all ranks; the trained fields are broadcast in the table's order (centroids, codebooks,
+    rotation, ranges); each rank assigns and encodes its own rows on its GPU; one all-gather of the per-rank list counts fixes the
+    global order (within a list: by source rank, then source order); one all_to_all moves each row's payload bytes, id and
+    position to the rank that owns the position — no rank holds fp32 rows other than those of its own store shards, unless they
+    are the payload; each rank writes `{media_type}-{index_type}.faiss.part-RRR-of-WWW`, a complete file of its family's record
+    with the list sizes clipped to its rows.  The parts laid end to end are the one-process build's file, byte for byte;
+  * the load (`_load_sharded_ivf`): the ranks agree ONCE (an all-reduce of "my part exists") whether all of them read part files
+    or all of them read rows shard_range(N, r, W) of the single file (`faiss_io.read_index_range` opens only the lists that overlap
+    them), so a missing part cannot mix the two sources.  IndexIVFFlat alone keeps an older, rank-local rule (load_index).
+    `self.index` is the family's `Sharded*` wrapper around the local index: one exchange per search, two for the R8 / R16 forms
+    (candidates, then re-ranked answers), returning the bits of the one-GPU index over the same state.  Rotation, codebooks and
+    ranges are replicated, so every rank rotates and encodes its own rows and queries.
 """
 import os
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Callable
 
 import numpy as np
 
@@ -85,13 +80,17 @@ from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPI
                       ShardedIVFSQIPIndex, shard_range)
 
 
+def _always_exchange():
+    return os.environ.get('WISE_SHARDED_INDEX') == '1'
+
+
 def _dist_rank_world():
     """(rank, world, sharded?) of the default process group; (0, 1, False) outside torch.distributed."""
     import torch.distributed as dist
 
     if dist.is_available() and dist.is_initialized():
         rank, world = dist.get_rank(), dist.get_world_size()
-        return rank, world, world > 1 or os.environ.get('WISE_SHARDED_INDEX') == '1'
+        return rank, world, world > 1 or _always_exchange()
     return 0, 1, False
 
 
@@ -147,11 +146,91 @@ def parse_ivfopq_refine_type(index_type, feature_dim=None):
     return parse_ivfpq_refine_type(index_type, feature_dim, 'IndexIVFOPQ')
 
 
-def _pq_parsers(index_type):
-    """(parse m, parse (m, kind), opq?) for the family index_type belongs to"""
-    if index_type.startswith('IndexIVFOPQ'):
-        return parse_ivfopq_type, parse_ivfopq_refine_type, True
-    return parse_ivfpq_type, parse_ivfpq_refine_type, False
+@dataclass(frozen=True)
+class _Family:
+    """One inverted-file index family (module docstring)."""
+    parse: Callable      # (index_type, feature_dim=None) -> (m, kind) of a name of this family (None where it has none), None for any
+    #                      other name; with feature_dim the shapes are checked (ValueError)
+    cls: Callable        # () -> the class the one-process build constructs: this module's name for it, looked up at the call
+    factory: str         # the FeatureSearchIndex attribute that constructs a rank's index and an index read from a file
+    args: Callable       # (d, nlist, m, kind) -> the constructor's arguments
+    trained: tuple       # the trained fields beyond the centroids, in broadcast order: (state key = index attribute,
+    #                      setter(index, value), shape(d, nlist, m))
+    payload: str         # state key of a row's list payload
+    wrapper: type        # the Sharded* class around a rank's index
+    refine: bool = False  # compact rows beside the codes: 'kind', 'k_factor', 'rows', 'scales' in the state
+
+    @property
+    def marks(self):
+        """the state keys that tell this family's reader dict from the others' (faiss_io.write_index picks the record by them)"""
+        return {k for k, _, _ in self.trained} | ({'kind'} if self.refine else set()) | ({'X'} if self.payload == 'X' else set())
+
+
+_CENTROIDS = ('centroids', lambda index, v: index.set_centroids(v), lambda d, nlist, m: (nlist, d))
+_CODEBOOKS = ('codebooks', lambda index, v: index.set_codebooks(v), lambda d, nlist, m: (m, 256, d // m))
+_ROTATION = ('rotation', lambda index, v: index.set_rotation(v), lambda d, nlist, m: (d, d))
+_RANGES = ('trained', lambda index, v: index.set_trained(v[:v.shape[0] // 2], v[v.shape[0] // 2:]), lambda d, nlist, m: (2 * d,))
+
+
+def _named(name, check=None):
+    """the parser of a family of one name and no parameters"""
+    def parse(index_type, feature_dim=None):
+        if index_type != name:
+            return None
+        if check is not None and feature_dim is not None:
+            check(feature_dim)
+        return None, None
+    return parse
+
+
+def _plain(parse_m):
+    def parse(index_type, feature_dim=None):
+        m = parse_m(index_type, feature_dim)
+        return None if m is None else (m, None)
+    return parse
+
+
+_PQ_ARGS, _REFINE_ARGS = (lambda d, nlist, m, kind: (d, nlist, m)), (lambda d, nlist, m, kind: (d, nlist, m, kind))
+IVF_FLAT = _Family(_named('IndexIVFFlat'), lambda: IVFFlatIPIndex, 'ivf_index_factory', lambda d, nlist, m, kind: (d, nlist), (), 'X',
+                   ShardedIVFFlatIPIndex)
+FAMILIES = (
+    IVF_FLAT,
+    _Family(_plain(parse_ivfpq_type), lambda: IVFPQIPIndex, 'ivfpq_index_factory', _PQ_ARGS, (_CODEBOOKS,), 'codes', ShardedIVFPQIPIndex),
+    _Family(parse_ivfpq_refine_type, lambda: IVFPQRefineIPIndex, 'ivfpq_refine_index_factory', _REFINE_ARGS, (_CODEBOOKS,), 'codes',
+            ShardedIVFPQRefineIPIndex, refine=True),
+    _Family(_plain(parse_ivfopq_type), lambda: IVFOPQIPIndex, 'ivfopq_index_factory', _PQ_ARGS, (_CODEBOOKS, _ROTATION), 'codes',
+            ShardedIVFPQIPIndex),
+    _Family(parse_ivfopq_refine_type, lambda: IVFOPQRefineIPIndex, 'ivfopq_refine_index_factory', _REFINE_ARGS, (_CODEBOOKS, _ROTATION),
+            'codes', ShardedIVFPQRefineIPIndex, refine=True),
+    _Family(_named('IndexIVFSQ8', check_sq_shape), lambda: IVFSQIPIndex, 'ivfsq_index_factory', lambda d, nlist, m, kind: (d, nlist),
+            (_RANGES,), 'codes', ShardedIVFSQIPIndex),
+)
+_MARKS = set().union(*(fam.marks for fam in FAMILIES))
+
+
+def _family(index_type):
+    """The family index_type names, None for 'IndexFlatIP' and for a name WISE does not build (a re-ranking name with a kind other
+    than 8 or 16 is a ValueError)."""
+    return next((fam for fam in FAMILIES if fam.parse(index_type) is not None), None)
+
+
+def _family_of_state(f):
+    """The family of a faiss_io reader's dict."""
+    return next(fam for fam in FAMILIES if fam.marks == _MARKS & f.keys())
+
+
+def _host_state(index, fam):
+    """index.state_host(), the dict faiss_io.write_index takes.  A stand-in that implements no more than the factory contract of
+    the CPU tests has lists_host() alone; its tuple is the family's state in key order."""
+    if hasattr(index, 'state_host'):
+        return index.state_host()
+    keys = ('centroids',) + tuple(k for k, _, _ in fam.trained if k != 'rotation') + (fam.payload, 'ids', 'list_off')
+    return dict(zip(keys, index.lists_host()))
+
+
+def _unknown_index_type(index_type):
+    return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
+                               f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
 
 
 def _sharded_ivf_on():
@@ -164,6 +243,30 @@ def _coll_device():
     import torch.distributed as dist
 
     return torch.device('cuda', torch.cuda.current_device()) if dist.get_backend() == 'nccl' else torch.device('cpu')
+
+
+def _training_plan(n):
+    """(cell count, training rows, their sorted indices) for an IVF index over n rows.  The reference trains on the first
+    min(n, 100 nlist) vectors of a shard-shuffled pass (:62-69); a seeded sample of the same size stands in for it."""
+    cell_count = reference_nlist(n)
+    train_count = min(n, 100 * cell_count)
+    sample = np.random.default_rng(1234).permutation(n)[:train_count]
+    sample.sort()
+    return cell_count, train_count, sample
+
+
+def _read_store(feature_store):
+    """(X [n,d] float32, ids [n]) of every vector the opened store yields, assembled on the host (I/O-bound: tar + unpickle per
+    vector), 512 at a time."""
+    X = np.empty((feature_store.feature_count, feature_store.feature_dim), dtype=np.float32)
+    ids = np.empty((feature_store.feature_count,), dtype=np.int64)
+    n = 0
+    for feature_ids_batch, feature_vectors_batch in feature_store.iter_batch():
+        m = len(feature_ids_batch)
+        X[n:n + m] = feature_vectors_batch
+        ids[n:n + m] = feature_ids_batch
+        n += m
+    return X[:n], ids[:n]
 
 
 class FeatureSearchIndex(SearchIndex):
@@ -204,11 +307,8 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        parse_m, parse_refine, opq = _pq_parsers(index_type)
-        refine = parse_refine(index_type)
-        is_pq = parse_m(index_type) is not None or refine is not None
-        is_sq = index_type == 'IndexIVFSQ8'
-        sharded_ivf = sharded and (index_type == 'IndexIVFFlat' or is_pq or is_sq) and _sharded_ivf_on()
+        fam = _family(index_type)                   # None: IndexFlatIP (or a name refused below)
+        sharded_ivf = sharded and fam is not None and _sharded_ivf_on()
         if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
         exists = index_fn.exists()
@@ -221,11 +321,10 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq and not is_sq:
-            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
-                                      f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
+        if index_type != 'IndexFlatIP' and fam is None:
+            raise _unknown_index_type(index_type)
         self.index_type = index_type
-        if sharded and (index_type == 'IndexIVFFlat' or is_pq or is_sq) and not sharded_ivf and rank != 0:
+        if sharded and fam is not None and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
@@ -233,79 +332,34 @@ class FeatureSearchIndex(SearchIndex):
             feature_store.enable_read(shard_shuffle=False, shard_slice=(rank, world))   # this rank's shard files only
         else:
             feature_store.enable_read(shard_shuffle=False)
-        feature_count = feature_store.feature_count
         feature_dim = feature_store.feature_dim
-        if refine is not None:                                                    # a bad shape is refused before any row is read
-            pq_m, kind = parse_refine(index_type, feature_dim)
-        else:
-            pq_m = parse_m(index_type, feature_dim) if is_pq else None
-        if is_sq:
-            check_sq_shape(feature_dim)
+        if fam is not None:                         # a bad shape is refused before any row is read
+            pq_m, kind = fam.parse(index_type, feature_dim)
 
-        # the on-disk index is assembled on the host (I/O-bound: tar + unpickle per vector), 512 at a time
-        X = np.empty((feature_count, feature_dim), dtype=np.float32)
-        ids = np.empty((feature_count,), dtype=np.int64)
-        n = 0
         print('Adding feature vectors to index')
-        for feature_ids_batch, feature_vectors_batch in feature_store.iter_batch():
-            m = len(feature_ids_batch)
-            X[n:n + m] = feature_vectors_batch
-            ids[n:n + m] = feature_ids_batch
-            n += m
+        X, ids = _read_store(feature_store)
+        n = X.shape[0]
         if sharded_ivf:
-            self._create_sharded_ivf(X[:n], ids[:n], index_fn, rank, world, index_type=index_type, pq_m=pq_m,
-                                     kind=kind if refine is not None else None, opq=opq, sq=is_sq)
+            self._create_sharded_ivf(X, ids, index_fn, rank, world, index_type, fam, pq_m, kind)
             print(f'  saved index part to {index_fn}')
             return
-        if index_type == 'IndexIVFFlat' or is_pq or is_sq:
-            cell_count = reference_nlist(n)
-            train_count = min(n, 100 * cell_count)
-            # the reference trains on the first train_count vectors of a shard-shuffled pass (:62-69); a seeded
-            # sample of the same size stands in for it
-            sample = np.random.default_rng(1234).permutation(n)[:train_count]
-            sample.sort()
+        if fam is not None:
+            cell_count, train_count, sample = _training_plan(n)
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
-            if refine is not None:
-                ivf = (IVFOPQRefineIPIndex if opq else IVFPQRefineIPIndex)(feature_dim, cell_count, pq_m, kind)
-            elif opq:
-                ivf = IVFOPQIPIndex(feature_dim, cell_count, pq_m)
-            elif is_sq:
-                ivf = IVFSQIPIndex(feature_dim, cell_count)
-            else:
-                ivf = IVFPQIPIndex(feature_dim, cell_count, pq_m) if is_pq else IVFFlatIPIndex(feature_dim, cell_count)
-            ivf.train(X[sample])                    # the coarse stage, then (IndexIVFPQ / SQ8) the codebooks / ranges on its residuals
+            ivf = fam.cls()(*fam.args(feature_dim, cell_count, pq_m, kind))
+            ivf.train(X[sample])                    # the coarse stage, then the family's trained fields on its residuals
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
-            if opq:
-                c, cb, codes, ids_s, off = ivf.lists_host()
-                store = {}
-                if refine is not None:
-                    rows, scales = ivf.store_host()
-                    store = dict(kind=kind, k_factor=ivf.k_factor, rows=rows, scales=scales)
-                faiss_io.write_ivf_opq_ip(index_fn, ivf.rotation.cpu().numpy(), c, cb, codes, ids_s, off, nprobe=ivf.nprobe, **store)
-            elif refine is not None:
-                c, cb, codes, ids_s, off = ivf.lists_host()
-                rows, scales = ivf.store_host()
-                faiss_io.write_ivf_pq_refine_ip(index_fn, c, cb, codes, ids_s, off, kind, ivf.k_factor, rows, scales, nprobe=ivf.nprobe)
-            elif is_pq:
-                c, cb, codes, ids_s, off = ivf.lists_host()
-                faiss_io.write_ivf_pq_ip(index_fn, c, cb, codes, ids_s, off, nprobe=ivf.nprobe)
-            elif is_sq:
-                c, trained, codes, ids_s, off = ivf.lists_host()
-                faiss_io.write_ivf_sq_ip(index_fn, c, trained, codes, ids_s, off, nprobe=ivf.nprobe)
-            else:
-                c, Xs, ids_s, off = ivf.lists_host()
-                faiss_io.write_ivf_flat_ip(index_fn, c, Xs, ids_s, off, nprobe=ivf.nprobe)
+            faiss_io.write_index(index_fn, _host_state(ivf, fam), nprobe=ivf.nprobe)
         else:
-            faiss_io.write_idmap_flat_ip(index_fn, X[:n], ids[:n])
+            faiss_io.write_idmap_flat_ip(index_fn, X, ids)
         print(f'  saved index to {index_fn}')
 
-    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type='IndexIVFFlat', pq_m=None, kind=None, opq=False, sq=False):
-        """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows.  What travels to the
-        rank that owns a row's position is a per-row byte payload: the fp32 row (IndexIVFFlat), or the row's codes followed by its
-        compact row and scale (pq_m / kind given: IndexIVFPQ<m>, IndexIVFPQ<m>R<kind>), encoded where the row was read.  opq: the
-        IndexIVFOPQ forms of the two — rank 0 also trains the rotation, which is broadcast with the codebooks.  sq: IndexIVFSQ8 —
-        rank 0 also trains the [2d] ranges, which are broadcast with the centroids; the payload is the row's d code bytes."""
+    def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type, fam, pq_m=None, kind=None):
+        """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows, fam the family of
+        index_type, pq_m / kind what its name carries.  What travels to the rank that owns a row's position is a per-row byte
+        payload, encoded where the row was read: the fp32 row (IndexIVFFlat), else what the family's encode_rows returns after the
+        list — the row's codes, then (re-ranking forms) its compact row and scale."""
         import torch
         import torch.distributed as dist
 
@@ -317,22 +371,12 @@ class FeatureSearchIndex(SearchIndex):
         ns = ns_t.cpu().numpy()
         src_off = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
         n_total = int(src_off[-1])
-        cell_count = reference_nlist(n_total)
-        train_count = min(n_total, 100 * cell_count)
         # the single-file build's seeded sample, drawn over the concatenation of every rank's rows
-        sample = np.random.default_rng(1234).permutation(n_total)[:train_count]
-        sample.sort()
+        cell_count, train_count, sample = _training_plan(n_total)
         bounds = np.searchsorted(sample, src_off)
         mine = sample[bounds[rank]:bounds[rank + 1]] - src_off[rank]
-        if kind is not None:
-            ivf = (self.ivfopq_refine_index_factory if opq else self.ivfpq_refine_index_factory)(d, cell_count, pq_m, kind)
-        elif pq_m is not None:
-            ivf = (self.ivfopq_index_factory if opq else self.ivfpq_index_factory)(d, cell_count, pq_m)
-        elif sq:
-            ivf = self.ivfsq_index_factory(d, cell_count)
-        else:
-            ivf = self.ivf_index_factory(d, cell_count)
-        if rank == 0:                               # k-means once, on rank 0; the centroids' bits go to every rank
+        ivf = getattr(self, fam.factory)(*fam.args(d, cell_count, pq_m, kind))
+        if rank == 0:                               # training once, on rank 0
             parts = [X[mine]]
             for src in range(1, world):
                 m = int(bounds[src + 1] - bounds[src])
@@ -341,48 +385,21 @@ class FeatureSearchIndex(SearchIndex):
                     dist.recv(buf, src=src)
                     parts.append(buf.cpu().numpy())
             print(f'  training {index_type} index with {train_count} features with {cell_count} clusters ...')
-            ivf.train(np.concatenate(parts))        # the coarse stage, then (IndexIVFPQ / SQ8) the codebooks / ranges on its residuals
-            c = ivf.centroids if torch.is_tensor(ivf.centroids) else torch.from_numpy(np.asarray(ivf.centroids))
-            c = c.to(dev, torch.float32).contiguous()
-        else:
-            if len(mine):
-                dist.send(torch.from_numpy(np.ascontiguousarray(X[mine])).to(dev), dst=0)
-            c = torch.empty(cell_count, d, dtype=torch.float32, device=dev)
-        dist.broadcast(c, src=0)
-        centroids = c.cpu().numpy()
-        ivf.set_centroids(centroids)
-        codebooks = None
-        if pq_m is not None:                        # the codebooks' bits go to every rank too
+            ivf.train(np.concatenate(parts))        # the coarse stage, then the family's trained fields on its residuals
+        elif len(mine):
+            dist.send(torch.from_numpy(np.ascontiguousarray(X[mine])).to(dev), dst=0)
+        state = {}
+        for key, setter, shape in (_CENTROIDS,) + fam.trained:     # the trained fields' bits go to every rank
             if rank == 0:
-                cb = ivf.codebooks if torch.is_tensor(ivf.codebooks) else torch.from_numpy(np.asarray(ivf.codebooks))
-                cb = cb.to(dev, torch.float32).contiguous()
+                t = getattr(ivf, key)
+                t = (t if torch.is_tensor(t) else torch.from_numpy(np.asarray(t))).to(dev, torch.float32).contiguous()
             else:
-                cb = torch.empty(pq_m, 256, d // pq_m, dtype=torch.float32, device=dev)
-            dist.broadcast(cb, src=0)
-            codebooks = cb.cpu().numpy()
-            ivf.set_codebooks(codebooks)
-        rotation = None
-        if opq:                                     # ... and the rotation's: every rank rotates its own rows and queries
-            if rank == 0:
-                rot = ivf.rotation if torch.is_tensor(ivf.rotation) else torch.from_numpy(np.asarray(ivf.rotation))
-                rot = rot.to(dev, torch.float32).contiguous()
-            else:
-                rot = torch.empty(d, d, dtype=torch.float32, device=dev)
-            dist.broadcast(rot, src=0)
-            rotation = rot.cpu().numpy()
-            ivf.set_rotation(rotation)
-        trained = None
-        if sq:                                      # ... and, IndexIVFSQ8, the ranges': vmin [d], then vdiff [d]
-            if rank == 0:
-                tr = ivf.trained if torch.is_tensor(ivf.trained) else torch.from_numpy(np.asarray(ivf.trained))
-                tr = tr.to(dev, torch.float32).contiguous()
-            else:
-                tr = torch.empty(2 * d, dtype=torch.float32, device=dev)
-            dist.broadcast(tr, src=0)
-            trained = tr.cpu().numpy()
-            ivf.set_trained(trained[:d], trained[d:])
+                t = torch.empty(*shape(d, cell_count, pq_m), dtype=torch.float32, device=dev)
+            dist.broadcast(t, src=0)
+            state[key] = t.cpu().numpy()
+            setter(ivf, state[key])
         # each rank assigns (and encodes) its own rows; the per-rank list counts fix the global list-major order
-        if pq_m is None and not sq:
+        if fam is IVF_FLAT:
             a = ivf.assign(X)
             fields = [X]
         else:
@@ -431,77 +448,43 @@ class FeatureSearchIndex(SearchIndex):
             arr[pos] = np.ascontiguousarray(gbytes[:, b0:b0 + w]).view(f.dtype).reshape((got.shape[0],) + f.shape[1:])
             loc.append(arr)
             b0 += w
-        off_loc = np.clip(list_off - lo, 0, hi - lo)
-        if opq:
-            store = {}
-            if kind is not None:
-                store = dict(kind=kind, k_factor=ivf.k_factor, rows=loc[1] if kind == 8 else loc[1].view(np.uint16),
-                             scales=loc[2] if kind == 8 else None)
-            faiss_io.write_ivf_opq_ip(part_fn, rotation, centroids, codebooks, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe, **store)
-        elif kind is not None:
-            rows = loc[1] if kind == 8 else loc[1].view(np.uint16)
-            faiss_io.write_ivf_pq_refine_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, kind, ivf.k_factor, rows,
-                                            loc[2] if kind == 8 else None, nprobe=ivf.nprobe)
-        elif pq_m is not None:
-            faiss_io.write_ivf_pq_ip(part_fn, centroids, codebooks, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
-        elif sq:
-            faiss_io.write_ivf_sq_ip(part_fn, centroids, trained, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
-        else:
-            faiss_io.write_ivf_flat_ip(part_fn, centroids, loc[0], ids_loc, off_loc, nprobe=ivf.nprobe)
+        state.update({fam.payload: loc[0], 'ids': ids_loc, 'list_off': np.clip(list_off - lo, 0, hi - lo)})
+        if fam.refine:                              # bf16 rows travel as their bit patterns; the file holds them as uint16
+            state.update(kind=kind, k_factor=ivf.k_factor, rows=loc[1] if kind == 8 else loc[1].view(np.uint16),
+                         scales=loc[2] if kind == 8 else None)
+        faiss_io.write_index(part_fn, state, nprobe=ivf.nprobe)
 
-    def _sharded_ivf_index(self, f):
-        """ShardedIVFFlatIPIndex around a local index holding the slice `f` (a read_ivf_flat_ip(_range) dict)."""
+    def _local_index(self, f, pos_base=None):
+        """(family, index object holding the rows of `f` in HBM): f is a dict of faiss_io.read_index / read_index_range, the object
+        comes from the family's *_index_factory attribute.  pos_base: where the slice f starts in the whole list-major array (the
+        families whose sharded scan reports positions take it)."""
         import torch
 
-        local = self.ivf_index_factory(f["centroids"].shape[1], f["centroids"].shape[0])
-        local.set_centroids(f["centroids"])
-        local.adopt_lists(torch.from_numpy(f["X"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-        local.nprobe = f["nprobe"]
-        return ShardedIVFFlatIPIndex(local, merge=getattr(local, 'merge_lists', None),
-                                     always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
-
-    def _sharded_ivfpq_index(self, f, pos_base):
-        """ShardedIVFPQIPIndex / ShardedIVFPQRefineIPIndex around a local index holding the slice `f` (a dict of one of the
-        faiss_io PQ readers) that starts at position pos_base of the whole list-major array."""
-        import torch
-
+        fam = _family_of_state(f)
         nlist, d = f["centroids"].shape
-        lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-        always = os.environ.get('WISE_SHARDED_INDEX') == '1'
-        opq = "rotation" in f                       # a 'WiOP' file: the same wrappers around the rotating local classes
-        if "kind" in f:
-            factory = self.ivfopq_refine_index_factory if opq else self.ivfpq_refine_index_factory
-            local = factory(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
-            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
-            lists += (rows, None if f["scales"] is None else torch.from_numpy(f["scales"]))
-            wrapper = ShardedIVFPQRefineIPIndex
-        else:
-            local = (self.ivfopq_index_factory if opq else self.ivfpq_index_factory)(d, nlist, f["codebooks"].shape[0])
-            wrapper = ShardedIVFPQIPIndex
-        local.set_centroids(f["centroids"])
-        local.set_codebooks(f["codebooks"])
-        if opq:
-            local.set_rotation(f["rotation"])
-        local.adopt_lists(*lists, pos_base=int(pos_base))
-        local.nprobe = f["nprobe"]
-        return wrapper(local, merge=getattr(local, 'merge_lists', None), always_exchange=always)
+        m = f["codebooks"].shape[0] if "codebooks" in f else None
+        index = getattr(self, fam.factory)(*fam.args(d, nlist, m, f.get("kind")), **({"k_factor": f["k_factor"]} if fam.refine else {}))
+        for key, setter, _ in (_CENTROIDS,) + fam.trained:
+            setter(index, f[key])
+        lists = [torch.from_numpy(f[fam.payload]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"])]
+        if fam.refine:                              # bf16 rows are uint16 bit patterns in the file, int16 in torch
+            lists += [torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16)),
+                      None if f["scales"] is None else torch.from_numpy(f["scales"])]
+        index.adopt_lists(*lists, **({} if pos_base is None else {"pos_base": int(pos_base)}))
+        index.nprobe = f["nprobe"]
+        return fam, index
 
-    def _sharded_ivfsq_index(self, f, pos_base):
-        """ShardedIVFSQIPIndex around a local index holding the slice `f` (a read_ivf_sq_ip(_range) dict) that starts at
-        position pos_base of the whole list-major array."""
-        import torch
+    @staticmethod
+    def _sharded(wrapper, local):
+        return wrapper(local, merge=getattr(local, 'merge_lists', None), always_exchange=_always_exchange())
 
-        nlist, d = f["centroids"].shape
-        local = self.ivfsq_index_factory(d, nlist)
-        local.set_centroids(f["centroids"])
-        local.set_trained(f["trained"][:d], f["trained"][d:])
-        local.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), pos_base=int(pos_base))
-        local.nprobe = f["nprobe"]
-        return ShardedIVFSQIPIndex(local, merge=getattr(local, 'merge_lists', None),
-                                   always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
+    def _sharded_ivf_index(self, f, pos_base=None):
+        """The family's Sharded* wrapper around a local index holding the slice `f` (_local_index)."""
+        fam, local = self._local_index(f, pos_base)
+        return self._sharded(fam.wrapper, local)
 
-    def _load_sharded_ivfpq(self, index_fn, part_fn, refine, rank, world, opq=False, sq=False):
-        """The sharded load of the IndexIVFPQ family and (sq) of IndexIVFSQ8: all ranks read their part files, or all ranks read
+    def _load_sharded_ivf(self, index_fn, part_fn, rank, world):
+        """The sharded load of every inverted-file family but IndexIVFFlat: all ranks read their part files, or all ranks read
         their range of the single file — decided once for the group."""
         import torch
         import torch.distributed as dist
@@ -509,26 +492,17 @@ class FeatureSearchIndex(SearchIndex):
         dev = _coll_device()
         flag = torch.tensor([int(part_fn.exists())], dtype=torch.int64, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
-        wrap = self._sharded_ivfsq_index if sq else self._sharded_ivfpq_index
-        if sq:
-            read, read_range, ntotal = faiss_io.read_ivf_sq_ip, faiss_io.read_ivf_sq_ip_range, faiss_io.ivf_sq_ip_ntotal
-        elif opq:
-            read, read_range, ntotal = faiss_io.read_ivf_opq_ip, faiss_io.read_ivf_opq_ip_range, faiss_io.ivf_opq_ip_ntotal
-        elif refine:
-            read, read_range, ntotal = faiss_io.read_ivf_pq_refine_ip, faiss_io.read_ivf_pq_refine_ip_range, faiss_io.ivf_pq_refine_ip_ntotal
-        else:
-            read, read_range, ntotal = faiss_io.read_ivf_pq_ip, faiss_io.read_ivf_pq_ip_range, faiss_io.ivf_pq_ip_ntotal
         if bool(flag.item()):
-            f = read(part_fn)
+            f = faiss_io.read_index(part_fn)
             ns = torch.zeros(world, dtype=torch.int64, device=dev)   # a part starts where the lower ranks' parts end
-            dist.all_gather_into_tensor(ns, torch.tensor([f["codes"].shape[0]], dtype=torch.int64, device=dev))
-            return wrap(f, int(ns.cpu().numpy()[:rank].sum()))
+            dist.all_gather_into_tensor(ns, torch.tensor([f["ids"].shape[0]], dtype=torch.int64, device=dev))
+            return self._sharded_ivf_index(f, int(ns.cpu().numpy()[:rank].sum()))
         if not index_fn.exists():
             have = 'this rank has its part' if part_fn.exists() else 'this rank has no part'
             raise RuntimeError(f'{index_fn}: the part files of {world} ranks are not complete ({have}: {part_fn.name}) and there is '
                                f'no single file to read every rank\'s rows from; parts and a single file are never mixed')
-        lo, hi = shard_range(ntotal(index_fn), rank, world)
-        return wrap(read_range(index_fn, lo, hi), lo)
+        lo, hi = shard_range(faiss_io.index_ntotal(index_fn), rank, world)
+        return self._sharded_ivf_index(faiss_io.read_index_range(index_fn, lo, hi), lo)
 
     IVF_FOURCCS = ('WiOP', 'WiPR', 'IwPQ', 'IwSq', 'IwFl')
 
@@ -536,93 +510,25 @@ class FeatureSearchIndex(SearchIndex):
         """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
         Anything that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
         shard = (rank, world): only rows shard_range(N, rank, world) of a flat file."""
-        import torch
-
-        fourcc = faiss_io.index_fourcc(fn) if fn.exists() else None
-        if fourcc == 'WiOP':
-            f = faiss_io.read_ivf_opq_ip(fn)
-            nlist, d = f["centroids"].shape
-            lists = (torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            if "kind" in f:
-                index = IVFOPQRefineIPIndex(d, nlist, f["codebooks"].shape[0], f["kind"], k_factor=f["k_factor"])
-                lists += (torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16)),
-                          None if f["scales"] is None else torch.from_numpy(f["scales"]))
-            else:
-                index = IVFOPQIPIndex(d, nlist, f["codebooks"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            index.set_rotation(f["rotation"])
-            index.adopt_lists(*lists)
-            index.nprobe = f["nprobe"]
-        elif fourcc == 'WiPR':
-            f = faiss_io.read_ivf_pq_refine_ip(fn)
-            index = IVFPQRefineIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0], f["kind"],
-                                       k_factor=f["k_factor"])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            rows = torch.from_numpy(f["rows"] if f["kind"] == 8 else f["rows"].view(np.int16))
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]), rows,
-                              None if f["scales"] is None else torch.from_numpy(f["scales"]))
-            index.nprobe = f["nprobe"]
-        elif fourcc == 'IwPQ':
-            f = faiss_io.read_ivf_pq_ip(fn)
-            index = IVFPQIPIndex(f["centroids"].shape[1], f["centroids"].shape[0], f["codebooks"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.set_codebooks(f["codebooks"])
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
-        elif fourcc == 'IwSq':
-            f = faiss_io.read_ivf_sq_ip(fn)
-            nlist, d = f["centroids"].shape
-            index = IVFSQIPIndex(d, nlist)
-            index.set_centroids(f["centroids"])
-            index.set_trained(f["trained"][:d], f["trained"][d:])
-            index.adopt_lists(torch.from_numpy(f["codes"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
-        elif fourcc == 'IwFl':
-            f = faiss_io.read_ivf_flat_ip(fn)
-            index = IVFFlatIPIndex(f["centroids"].shape[1], f["centroids"].shape[0])
-            index.set_centroids(f["centroids"])
-            index.adopt_lists(torch.from_numpy(f["X"]), torch.from_numpy(f["ids"]), torch.from_numpy(f["list_off"]))
-            index.nprobe = f["nprobe"]
-        else:
-            X, ids = faiss_io.read_idmap_flat_ip(fn)                 # rows memory-mapped: only [lo, hi) is ever touched
-            lo, hi = shard_range(X.shape[0], *shard) if shard is not None else (0, X.shape[0])
-            index = self.flat_index_factory(X.shape[1])
-            index.reserve(hi - lo)                   # one [n,d] device tensor, filled slice by slice
-            for s in range(lo, hi, 1 << 20):         # stream the memory-mapped rows into HBM
-                e = min(s + (1 << 20), hi)
-                index.add_with_ids(np.ascontiguousarray(X[s:e]), ids[s:e])
+        if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
+            return self._local_index(faiss_io.read_index(fn))[1]
+        X, ids = faiss_io.read_idmap_flat_ip(fn)                     # rows memory-mapped: only [lo, hi) is ever touched
+        lo, hi = shard_range(X.shape[0], *shard) if shard is not None else (0, X.shape[0])
+        index = self.flat_index_factory(X.shape[1])
+        index.reserve(hi - lo)                       # one [n,d] device tensor, filled slice by slice
+        for s in range(lo, hi, 1 << 20):             # stream the memory-mapped rows into HBM
+            e = min(s + (1 << 20), hi)
+            index.add_with_ids(np.ascontiguousarray(X[s:e]), ids[s:e])
         return index
 
     @staticmethod
     def _write_index_file(index, fn):
-        """index object -> file, by the faiss_io writer of its type (the inverse of _index_from_file)."""
+        """index object -> file (the inverse of _index_from_file)."""
         if isinstance(index, FlatIPIndex):
             index._finalize()
             faiss_io.write_idmap_flat_ip(fn, index._X.cpu().numpy(), index._ids.cpu().numpy())
-            return
-        refine = isinstance(index, IVFPQRefineIPIndex)
-        store = {}
-        if refine:
-            rows, scales = index.store_host()
-            store = dict(kind=index.kind, k_factor=index.k_factor, rows=rows, scales=scales)
-        if isinstance(index, (IVFOPQIPIndex, IVFOPQRefineIPIndex)):
-            c, cb, codes, ids_s, off = index.lists_host()
-            faiss_io.write_ivf_opq_ip(fn, index.rotation.cpu().numpy(), c, cb, codes, ids_s, off, nprobe=index.nprobe, **store)
-        elif refine:
-            c, cb, codes, ids_s, off = index.lists_host()
-            faiss_io.write_ivf_pq_refine_ip(fn, c, cb, codes, ids_s, off, store["kind"], store["k_factor"], store["rows"],
-                                            store["scales"], nprobe=index.nprobe)
-        elif isinstance(index, IVFPQIPIndex):
-            c, cb, codes, ids_s, off = index.lists_host()
-            faiss_io.write_ivf_pq_ip(fn, c, cb, codes, ids_s, off, nprobe=index.nprobe)
-        elif isinstance(index, IVFSQIPIndex):
-            c, trained, codes, ids_s, off = index.lists_host()
-            faiss_io.write_ivf_sq_ip(fn, c, trained, codes, ids_s, off, nprobe=index.nprobe)
-        elif isinstance(index, IVFFlatIPIndex):
-            c, Xs, ids_s, off = index.lists_host()
-            faiss_io.write_ivf_flat_ip(fn, c, Xs, ids_s, off, nprobe=index.nprobe)
+        elif hasattr(index, 'state_host'):
+            faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
         else:
             raise TypeError(f'{type(index).__name__}: no index file format')
 
@@ -634,11 +540,8 @@ class FeatureSearchIndex(SearchIndex):
         temporary name beside it and renamed over it.  Returns (n_added, n_removed); with nothing to do the file is left
         alone.  The feature extractor is not built.  A `self.index` loaded from that file before the call is stale
         afterwards: call load_index again.  Lists are not rebalanced and nothing is retrained, however many updates pile up."""
-        parse_m, parse_refine, _ = _pq_parsers(index_type)
-        is_pq = parse_m(index_type) is not None or parse_refine(index_type) is not None
-        if index_type not in ('IndexFlatIP', 'IndexIVFFlat') and not is_pq and index_type != 'IndexIVFSQ8':
-            raise NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
-                                      f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
+        if index_type != 'IndexFlatIP' and _family(index_type) is None:
+            raise _unknown_index_type(index_type)
         if _dist_rank_world()[2]:
             raise NotImplementedError('update_index under a sharded process group is not built (a collective removal is not): '
                                       'update the single file in one process and shard it again')
@@ -651,15 +554,8 @@ class FeatureSearchIndex(SearchIndex):
         feature_store.enable_read(shard_shuffle=False)
         if feature_store.feature_dim != index.d:
             raise ValueError(f'update_index: the store holds {feature_store.feature_dim}-d vectors, the index {index.d}-d')
-        X = np.empty((feature_store.feature_count, feature_store.feature_dim), dtype=np.float32)
-        store_ids = np.empty((feature_store.feature_count,), dtype=np.int64)
-        n = 0
-        for feature_ids_batch, feature_vectors_batch in feature_store.iter_batch():
-            m = len(feature_ids_batch)
-            X[n:n + m] = feature_vectors_batch
-            store_ids[n:n + m] = feature_ids_batch
-            n += m
-        remove, add_mask = plan_update(index_ids, store_ids[:n])
+        X, store_ids = _read_store(feature_store)
+        remove, add_mask = plan_update(index_ids, store_ids)
         n_removed = index.remove_ids(remove) if remove.size else 0
         add_rows = np.flatnonzero(add_mask)
         for s0 in range(0, add_rows.size, 1 << 20):
@@ -688,17 +584,16 @@ class FeatureSearchIndex(SearchIndex):
             print(f'  index {index_fn} does not exist')
             print(f'  use create-index.py script to create an index')
         # like the reference (App. B.3) a missing file raises from the reader, it does not return False
-        parse_m, parse_refine, opq = _pq_parsers(index_type)
-        refine = parse_refine(index_type) is not None
-        if sharded and _sharded_ivf_on() and (refine or parse_m(index_type) is not None):
-            index = self._load_sharded_ivfpq(index_fn, part_fn, refine, rank, world, opq)
-        elif sharded and _sharded_ivf_on() and index_type == 'IndexIVFSQ8':
-            index = self._load_sharded_ivfpq(index_fn, part_fn, False, rank, world, sq=True)
+        fam = _family(index_type)
+        if sharded and _sharded_ivf_on() and fam is not None and fam is not IVF_FLAT:
+            index = self._load_sharded_ivf(index_fn, part_fn, rank, world)
+        # IndexIVFFlat keeps its own, rank-local rule (no all-reduce, and a part file is taken without the switch): the part if it
+        # is there, else the rank's range of the single file under WISE_SHARDED_IVF=1.  Only the wrapper's construction is shared.
         elif sharded and part_fn.exists() and faiss_io.index_fourcc(part_fn) == 'IwFl':
-            index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip(part_fn))      # built by this many ranks
+            index = self._sharded_ivf_index(faiss_io.read_index(part_fn))             # built by this many ranks
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
-            lo, hi = shard_range(faiss_io.ivf_flat_ip_ntotal(index_fn), rank, world)
-            index = self._sharded_ivf_index(faiss_io.read_ivf_flat_ip_range(index_fn, lo, hi))
+            lo, hi = shard_range(faiss_io.index_ntotal(index_fn), rank, world)
+            index = self._sharded_ivf_index(faiss_io.read_index_range(index_fn, lo, hi))
         elif index_fn.exists() and faiss_io.index_fourcc(index_fn) in self.IVF_FOURCCS:
             index = self._index_from_file(index_fn)   # unsharded: every rank of a process group loads the whole file
         else:
@@ -707,8 +602,7 @@ class FeatureSearchIndex(SearchIndex):
             else:
                 index = self._index_from_file(index_fn, shard=(rank, world) if sharded else None)
             if sharded:
-                index = ShardedFlatIPIndex(index, merge=getattr(index, 'merge_lists', None),
-                                           always_exchange=os.environ.get('WISE_SHARDED_INDEX') == '1')
+                index = self._sharded(ShardedFlatIPIndex, index)
         self.index = index
         self.feature_extractor = FeatureExtractorFactory(self.feature_extractor_id)
         return True

@@ -140,3 +140,7 @@ class IVFFlatIPIndex(IVFIndexBase):
         self._finalize()
         ls = self._lists
         return self.centroids.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(), ls.list_off.cpu().numpy()
+
+    def state_host(self) -> dict:
+        """The index as the dict faiss_io.read_ivf_flat_ip returns and faiss_io.write_index takes."""
+        return dict(zip(("centroids", "X", "ids", "list_off"), self.lists_host()), nprobe=self.nprobe)

@@ -308,6 +308,11 @@ class IVFPQIPIndex(IVFIndexBase):
         return (self.centroids.cpu().numpy(), self.codebooks.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(),
                 ls.list_off.cpu().numpy())
 
+    def state_host(self) -> dict:
+        """The index as the dict the faiss_io reader of its file returns and faiss_io.write_index takes: read_ivf_pq_ip's keys;
+        the re-ranking classes add their store (rows of kind 16 as uint16 bit patterns), the OPQ classes their rotation."""
+        return dict(zip(("centroids", "codebooks", "codes", "ids", "list_off"), self.lists_host()), nprobe=self.nprobe)
+
 
 REFINE_KINDS = (8, 16)
 MAX_CANDIDATES = 2048            # the most positions one scan returns and one wise_ivf_refine call takes
@@ -449,6 +454,10 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
         rows = ex[0].cpu().numpy()
         return (rows, ex[1].cpu().numpy()) if self.kind == 8 else (rows.view(np.uint16), None)
 
+    def state_host(self) -> dict:
+        rows, scales = self.store_host()
+        return dict(super().state_host(), kind=self.kind, k_factor=self.k_factor, rows=rows, scales=scales)
+
 
 MAX_OPQ_D = 1024                 # wise_opq_rotate keeps 32 rows of d floats in LDS
 
@@ -483,6 +492,9 @@ class _OPQRotation:
         if tuple(r.shape) != (self.d, self.d):
             raise ValueError(f"set_rotation: expected [{self.d},{self.d}]")
         self.rotation = r.to(self.device, torch.float32).contiguous()
+
+    def state_host(self) -> dict:
+        return dict(super().state_host(), rotation=self.rotation.cpu().numpy())
 
     def _rotate(self, x: torch.Tensor, rotation: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [n, d] R^T: row i becomes R x_i (wise_opq_rotate)."""

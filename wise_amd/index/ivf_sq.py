@@ -241,3 +241,7 @@ class IVFSQIPIndex(IVFIndexBase):
         ls = self._lists
         return (self.centroids.cpu().numpy(), self.trained.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(),
                 ls.list_off.cpu().numpy())
+
+    def state_host(self) -> dict:
+        """The index as the dict faiss_io.read_ivf_sq_ip returns and faiss_io.write_index takes."""
+        return dict(zip(("centroids", "trained", "codes", "ids", "list_off"), self.lists_host()), nprobe=self.nprobe)
