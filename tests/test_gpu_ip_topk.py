@@ -212,7 +212,39 @@ def test_batched_split_candidates_resolve_near_ties():
     assert np.array_equal(Is[0], I[0])
 
 
-THRESHOLD_FORM_MIN_ROWS = 1 << 18   # csrc/ip_topk.hip COLLECT_MIN_ROWS: smaller indexes go to the fp32 scan directly
+_SAMPLE_PASS_SHAPE = (262_144 + 37, 128)      # just over 8 x 32768 rows (the sample-pass rule of wise_ip_topk_f32), ragged last group
+_SAMPLE_PASS_TIES = (5, 40_000, 262_143, 262_180)   # inside the 32768-row sample, outside it, ..., the last row of the index
+_sample_pass_rows = []
+
+
+def sample_pass_rows():
+    if not _sample_pass_rows:
+        X = unit_rows(*_SAMPLE_PASS_SHAPE, 51)
+        X[list(_SAMPLE_PASS_TIES)] = X[_SAMPLE_PASS_TIES[0]]
+        X.setflags(write=False)
+        _sample_pass_rows.append(X)
+    return _sample_pass_rows[0]
+
+
+@pytest.mark.parametrize("nq,k", [(33, 10), (70, 12), (70, 16)])
+def test_f32_batched_scan_with_sample_pass_against_oracle(nq, k):
+    """wise_ip_topk_f32 on its own (no shadow) with the sample pass of the split-bf16 candidate scan active, against the CPU
+    oracle: 33 queries (one pass, one query more than 32), 70 (a 64-query pass and a 6-query tail) and k = 16 (the f32
+    matrix-core scan, which has no sample pass).  Four identical rows sit on both sides of the sample boundary and in the
+    ragged last group: they tie exactly and come back lowest row first."""
+    N, d = _SAMPLE_PASS_SHAPE
+    X = sample_pass_rows()
+    Q = np.concatenate([X[_SAMPLE_PASS_TIES[0]][None], unit_rows(nq - 1, d, 52)], axis=0)
+    ids = np.arange(N, dtype=np.int64) * 2 + 7
+    idx = FlatIPIndex(d, shadow=False)
+    idx.add_with_ids(X, ids)
+    D, I = idx.search(Q, k)
+    check_against_oracle(X, Q, k, ids, D, I)
+    assert list(I[0, :4]) == [2 * r + 7 for r in _SAMPLE_PASS_TIES]
+    assert np.all(D[0, :4] == D[0, 0])
+
+
+THRESHOLD_FORM_MIN_ROWS = 1 << 18   # csrc/ip_shadow.hip COLLECT_MIN_ROWS: smaller indexes go to the fp32 scan directly
 
 
 def counts_since(idx, before):

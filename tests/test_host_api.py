@@ -48,6 +48,7 @@ def test_debug_switches_live_only_in_the_debug_library():
                  "wise_debug_gemm_splitk_bytes", "wise_debug_gemm_rows", "wise_debug_gemm_resid_ln_rows"):
         assert hasattr(dbg, name)
         assert not hasattr(_lib.load(), name)
+    assert not hasattr(dbg, "wise_debug_set_scan") and not hasattr(_lib.load(), "wise_debug_set_scan")
     assert "debug_probe.hip" not in build.HIP_SOURCES
 
 

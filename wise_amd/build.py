@@ -28,7 +28,7 @@ LIBDIR = PKG / "lib"
 LIB = LIBDIR / "libwise_hip.so"
 LIB_DEBUG = LIBDIR / "libwise_hip_debug.so"
 HEADER = ROOT / "include" / "wise_hip.h"
-HIP_SOURCES = ["common.hip", "ip_topk.hip", "ip_topk_mfma.hip", "gemm_bf16.hip", "vit.hip", "htsat.hip",
+HIP_SOURCES = ["common.hip", "ip_topk.hip", "ip_range.hip", "ip_shadow.hip", "ip_topk_mfma.hip", "gemm_bf16.hip", "vit.hip", "htsat.hip",
                "htsat_frontend.hip", "preprocess.hip", "text.hip", "xlmr_text.hip", "cnn14.hip", "mlp_stream.hip", "swin_stream.hip", "ivf_build.hip", "ivf_pq.hip", "ivf_refine.hip", "opq.hip", "ivf_select.hip", "ivf_sq.hip", "compact.hip"]
 DEBUG_ONLY_SOURCES = ["debug_probe.hip"]
 ARCH = "gfx950"

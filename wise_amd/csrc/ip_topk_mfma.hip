@@ -4,9 +4,8 @@
 // docs/Retrieval-Evaluation.md:36-45) — SURVEY.md §8 f3.  Still an HBM-bound path: the kernels are judged against
 // N*d*4 bytes per pass.
 //
-// Four kernels, newest last (wise_ip_topk_f32 / wise_ip_topk_shadow_f32 in ip_topk.hip pick; wise_debug_set_scan can
-// force each of the first three):
-//   ip_scan_mfma_kernel<false>   f32 operands on v_mfma_f32_32x32x2_f32, X through a per-wave LDS-DMA ring, lists of
+// Four kernels, newest last (wise_ip_topk_f32 in ip_topk.hip and wise_ip_topk_shadow_f32 in ip_shadow.hip pick):
+//   ip_scan_mfma_kernel          f32 operands on v_mfma_f32_32x32x2_f32, X through a per-wave LDS-DMA ring, lists of
 //                                k <= 16 entries per (wave, query); scores final.  4.9 ms per 32 queries at 10M x 512:
 //                                256 MFMAs of 64 cycles per 32 rows x 512 columns on a SIMD are two thirds of the HBM
 //                                time, and loads and MFMAs do not overlap well with one 4 KiB chunk in flight per wave.
@@ -30,7 +29,7 @@
 //                                candidates per query, a dump mode for the threshold pass.  2.5 ms per 64 queries
 //                                end to end (25k queries/s); the kernels above are its gated fallback.
 //
-// Structure shared by all three (block = 8 independent waves, one block per CU, two waves per SIMD):
+// Structure shared by all four (block = 8 independent waves, one block per CU, two waves per SIMD):
 //   Q lives in LDS for the block's lifetime (16-byte chunks XOR-swizzled by query so that the 32 lanes of an MFMA
 //   B-operand read hit distinct banks); no block barrier in the loop;
 //   k-permutation: lane (i, h) holds columns h*16..h*16+15 of row i of a 32-column chunk — the same permutation on
@@ -42,7 +41,9 @@
 //   Measured alternatives that were slower: lists in registers with a branch-free bubble; lists in global memory with
 //   a device-wide atomic threshold (every insert is a chain of dependent global loads: 18-25 ms); 4 waves/block with a
 //   5-deep ring (5.4 ms); fragment reads software-pipelined one chunk ahead; the split products on the DMA ring
-//   (4.7 ms: the ring, not the matrix cores, was the limit).
+//   (4.7 ms: the ring, not the matrix cores, was the limit); the shadow scan with two-piece bf16 queries (hi + lo: twice
+//   the MFMAs, LDS reads and LDS footprint per query, so half the queries per pass).  Those variants and the timing
+//   ablations that measured them (no DMA, no MFMA, no selection) are no longer in the source.
 // The per-list results (part) are folded by merge_keys_kernel.
 #include "topk_common.h"
 
@@ -126,17 +127,10 @@ __device__ __forceinline__ void select_group(f32x16& acc, u64& tau, u64* lists, 
     }
 }
 
-// SPLIT = false: f32 operands on v_mfma_f32_32x32x2_f32, lists of k entries, scores final.
-// SPLIT = true:  candidate generation.  Every f32 operand is split into two bf16 halves and a product is
-//   hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with f32 accumulation (the dropped lo*lo term and the split
-//   residues bound the error of a dot product by 2^-16 * sum |x_c q_c| <= 1.6e-5 for unit rows, typically 1e-6);
-//   6 MFMAs of 32 cycles replace 16 of 64 per chunk, which takes the matrix cores off the critical path, and
-//   the lists always keep MFMA_KL = 16 candidates so that rescore_topk_kernel can put the exact f32 scores of
-//   the best 16 in order and return the first k <= MFMA_KC of them.
-template <bool SPLIT>
+// f32 operands on v_mfma_f32_32x32x2_f32, X through a per-wave LDS-DMA ring, lists of k entries, scores final.
 __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float* __restrict__ X, long long N, int d,
                                                               const float* __restrict__ qpad, int nq, int k,
-                                                              u64* __restrict__ part /*[P][32][k]*/, int abl) {
+                                                              u64* __restrict__ part /*[P][32][k]*/) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;  // MFMA row/query index and k-half
@@ -149,28 +143,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float
     u64* lists = lists_all + (size_t)wave * MFMA_KL * 32;
 
     // ---- Q -> LDS, chunk c of query j stored at chunk (c & ~15) | ((c & 15) ^ (j & 15))
-    // SPLIT: the same 32*d*4 bytes hold Qhi [32][d] bf16 then Qlo [32][d] bf16; 16-byte chunks (8 columns) of a
-    // row swizzled the same way
-    const int d8 = d >> 3;
-    unsigned char* Qh = smem;
-    unsigned char* Ql = smem + (size_t)32 * d * 2;
     for (int idx = threadIdx.x; idx < 32 * d4; idx += WAVES * 64) {
         const int j = idx / d4, c = idx - j * d4;
         const float4 v = reinterpret_cast<const float4*>(qpad)[idx];
-        if (SPLIT) {
-            const unsigned h01 = pack_bf16x2(v.x, v.y), h23 = pack_bf16x2(v.z, v.w);
-            const unsigned l01 = pack_bf16x2(v.x - __uint_as_float(h01 << 16), v.y - __uint_as_float(h01 & 0xFFFF0000u));
-            const unsigned l23 = pack_bf16x2(v.z - __uint_as_float(h23 << 16), v.w - __uint_as_float(h23 & 0xFFFF0000u));
-            const int c8 = c >> 1;
-            const size_t off = ((size_t)j * d8 + ((c8 & ~15) | ((c8 & 15) ^ (j & 15)))) * 16 + (c & 1) * 8;
-            *reinterpret_cast<uint2*>(Qh + off) = make_uint2(h01, h23);
-            *reinterpret_cast<uint2*>(Ql + off) = make_uint2(l01, l23);
-        } else {
-            const int pc = (c & ~15) | ((c & 15) ^ (j & 15));
-            reinterpret_cast<float4*>(Qs)[j * d4 + pc] = v;
-        }
+        const int pc = (c & ~15) | ((c & 15) ^ (j & 15));
+        reinterpret_cast<float4*>(Qs)[j * d4 + pc] = v;
     }
-    const int kl = SPLIT ? MFMA_KL : k;   // list length
+    const int kl = k;   // list length
     for (int e = h; e < MFMA_KL; e += 2) lists[e * 32 + i] = 0;
     __syncthreads();
 
@@ -189,7 +168,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float
         unsigned char* dst = ring + islot * CHUNK_BYTES;
         if (++ic == nch) { ic = 0; ig += nw; }
         if (++islot == RING) islot = 0;
-        if (abl == 1) return;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int row = u * 8 + (lane >> 3);
@@ -217,47 +195,22 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float
         const int c0 = cc * CW;
         if (++cslot == RING) cslot = 0;
         float4 xf[4], qf[4];
-        bf16x8 qh[2], ql[2];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int lc = h * 4 + t;  // logical 16-byte chunk of the 128-byte chunk row
             xf[t] = *reinterpret_cast<const float4*>(buf + i * 128 + ((lc ^ ((i >> 1) & 7)) << 4));
-            if (!SPLIT) {
-                const int qc = (c0 >> 2) + lc;  // chunk index within the query row
-                qf[t] = reinterpret_cast<const float4*>(Qs)[i * d4 + ((qc & ~15) | ((qc & 15) ^ (i & 15)))];
-            }
-        }
-        if (SPLIT) {
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {   // columns c0 + h*16 + g*8 .. +7 of query i
-                const int c8 = (c0 >> 3) + h * 2 + g;
-                const size_t off = ((size_t)i * d8 + ((c8 & ~15) | ((c8 & 15) ^ (i & 15)))) * 16;
-                qh[g] = *reinterpret_cast<const bf16x8*>(Qh + off);
-                ql[g] = *reinterpret_cast<const bf16x8*>(Ql + off);
-            }
+            const int qc = (c0 >> 2) + lc;  // chunk index within the query row
+            qf[t] = reinterpret_cast<const float4*>(Qs)[i * d4 + ((qc & ~15) | ((qc & 15) ^ (i & 15)))];
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         if (s + RING < steps) issue();  // the slot's fragments are in registers: refill it
-        if (abl != 2) {
-            if (SPLIT) {
 #pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    bf16x8 xh, xl;
-                    split_bf16x8(xf[2 * g], xf[2 * g + 1], xh, xl);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl, qh[g], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, ql[g], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh, qh[g], acc, 0, 0, 0);
-                }
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].x, qf[t].x, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].y, qf[t].y, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].z, qf[t].z, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].w, qf[t].w, acc, 0, 0, 0);
-                }
-            }
+        for (int t = 0; t < 4; ++t) {
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].x, qf[t].x, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].y, qf[t].y, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].z, qf[t].z, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xf[t].w, qf[t].w, acc, 0, 0, 0);
         }
         if (++cc == nch) {
             cc = 0;
@@ -274,7 +227,12 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float
 }
 
 // ------------------------------------------------------------------------------------------------
-// split-bf16 candidate scan with X straight into registers.  The LDS-DMA ring above leaves a wave one 4 KiB chunk
+// split-bf16 candidate scan with X straight into registers (k <= MFMA_KC).  Every f32 operand is split into two bf16
+// halves and a product is hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with f32 accumulation (the dropped lo*lo term
+// and the split residues bound the error of a dot product by 2^-16 * sum |x_c q_c| <= 1.6e-5 for unit rows, typically
+// 1e-6); 6 MFMAs of 32 cycles replace 16 of 64 per chunk, which takes the matrix cores off the critical path, and the
+// lists always keep MFMA_KL = 16 candidates so that rescore_topk_kernel can put the exact f32 scores of the best 16 in
+// order and return the first k <= MFMA_KC of them.  The LDS-DMA ring above leaves a wave one 4 KiB chunk
 // in flight while it computes (the LDS is full), i.e. 32 KiB per CU against the ~60 KiB a CU's share of HBM
 // bandwidth needs over the memory latency: scan and load times add up instead of overlapping (4.75 ms with
 // MFMA+selection alone 2.2 ms and loads alone 3.4 ms).  Here a lane loads its 64 bytes of a chunk row with four
@@ -282,13 +240,13 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_mfma_kernel(const float
 // consume every 128-byte line whole) into a PF-deep register queue: PF-1 chunks = 12 KiB in flight per wave, and
 // the freed 64 KiB of LDS is not needed.  Q (hi, lo) and the lists stay in LDS as above.
 // ------------------------------------------------------------------------------------------------
-template <int PF>
+constexpr int SPLIT_PF = 4;   // depth of the register queue: PF - 1 chunks = 12 KiB in flight per wave
 __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_split_direct_kernel(const float* __restrict__ X, long long N,
                                                                       int d, const float* __restrict__ qpad, int nq,
                                                                       u64* __restrict__ part /*[P][32][MFMA_KL]*/,
                                                                       long long row_offset,
-                                                                      const u64* __restrict__ tau0 /*[32] or null*/,
-                                                                      int abl) {
+                                                                      const u64* __restrict__ tau0 /*[32] or null*/) {
+    constexpr int PF = SPLIT_PF;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
@@ -366,27 +324,17 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_split_direct_kernel(con
                 __builtin_amdgcn_sched_barrier(0);
                 prefetch(xq[p]);   // the slot's values are in xh/xl: refill it
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(abl & 2)) {
 #pragma unroll
-                    for (int g = 0; g < 2; ++g) {
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[g], qh[g], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[g], ql[g], acc, 0, 0, 0);
-                        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[g], qh[g], acc, 0, 0, 0);
-                    }
-                } else {
-                    acc[0] += (float)xh[0][0] + (float)xl[1][7] + (float)qh[0][0] + (float)ql[1][0];
+                for (int g = 0; g < 2; ++g) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl[g], qh[g], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[g], ql[g], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh[g], qh[g], acc, 0, 0, 0);
                 }
                 if (++cc == nch) {
                     cc = 0;
                     const long long row0 = cg * 32;
                     cg += nw;
-                    if (!(abl & 1)) select_group(acc, tau, lists, lists_all, kl, i, h, active, row0, N, row_offset);
-                    else {
-                        float t = 0.f;
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) { t += acc[r]; acc[r] = 0.f; }
-                        if (t == 1.2345e-30f) lists[i] = 1;
-                    }
+                    select_group(acc, tau, lists, lists_all, kl, i, h, active, row0, N, row_offset);
                 }
             }
         }
@@ -395,9 +343,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_split_direct_kernel(con
     u64* dst = part + (pidx * MFMA_QB + i) * kl;
     for (int e = h; e < kl; e += 2) dst[e] = active ? lists[e * 32 + i] : 0;
 }
-
-int g_split_direct = 4;  // register-queue depth of the split scan (0 = the LDS-DMA ring variant)
-int g_mfma_abl = 0;  // ablation knob (wise_debug_set_scan): 1 = no DMA, 2 = no MFMA
 
 static int mfma_grid(long long N) {
     long long need = ((N + 31) / 32 + WAVES - 1) / WAVES;
@@ -414,23 +359,11 @@ bool mfma_split_supported(int d, int nq, int k) { return mfma_scan_supported(d, 
 int mfma_scan_lists(long long N) { return mfma_grid(N) * WAVES; }
 size_t mfma_scan_part_bytes(long long N, int k) { return (size_t)mfma_scan_lists(N) * MFMA_QB * k * sizeof(u64); }
 
-int mfma_scan_launch(const float* X, long long N, int d, const float* qpad, int nq, int k, u64* part, bool split,
-                     hipStream_t st) {
+int mfma_scan_launch(const float* X, long long N, int d, const float* qpad, int nq, int k, u64* part, hipStream_t st) {
     const size_t lds = (size_t)32 * d * 4 + (size_t)WAVES * RING * CHUNK_BYTES + (size_t)WAVES * MFMA_KL * 32 * 8;
     static PerDeviceOnce attr_set;
-    attr_set([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_mfma_kernel<false>), 160 * 1024);
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_mfma_kernel<true>), 160 * 1024);
-    });
-    if (split && g_split_direct) {
-        set_error("mfma_scan_launch: the register-queue scan is launched through split_scan_launch");
-        return WISE_E_UNSUPPORTED;
-    } else if (split)
-        hipLaunchKernelGGL(ip_scan_mfma_kernel<true>, dim3(mfma_grid(N)), dim3(WAVES * 64), lds, st, X, N, d, qpad, nq, k,
-                           part, g_mfma_abl);
-    else
-        hipLaunchKernelGGL(ip_scan_mfma_kernel<false>, dim3(mfma_grid(N)), dim3(WAVES * 64), lds, st, X, N, d, qpad, nq,
-                           k, part, g_mfma_abl);
+    attr_set([&] { raise_lds_limit(reinterpret_cast<const void*>(ip_scan_mfma_kernel), 160 * 1024); });
+    hipLaunchKernelGGL(ip_scan_mfma_kernel, dim3(mfma_grid(N)), dim3(WAVES * 64), lds, st, X, N, d, qpad, nq, k, part);
     WISE_LAUNCH_CHECK("ip_scan_mfma_kernel");
     return WISE_OK;
 }
@@ -630,21 +563,22 @@ int split64_scan_launch(const float* X, long long N, long long row_offset, int d
 // 64 (or 32) queries per pass over the bf16 SHADOW of the index (wise_ip_topk_shadow_f32, two or more queries): the
 // pass over the bf16 rows of the batched two-stage exact search.  The rows arrive as bf16, so they are MFMA A-operands
 // as loaded (no split, no VALU work): a lane's four 16-byte loads cover 32 columns of a 64-column chunk, and a product is
-// x*(q_hi + q_lo): 16 MFMAs per 4 KiB chunk and wave for 64 queries.  Half the bytes of the f32 rows per pass; the
-// approximate scores carry the bf16 rounding of x and the 2^-17 left over by the two-piece query (shadow_eps).
-// Two modes (the threshold form of the single-query search, ip_topk.hip, for a whole batch):
+// x*bf16(q): 8 MFMAs per 4 KiB chunk and wave for 64 queries.  Half the bytes of the f32 rows per pass; the approximate
+// scores carry the bf16 rounding of x (shadow_eps) and of the query (query_eps, ip_shadow.hip).
+// Two modes (the threshold form of the single-query search, ip_shadow.hip, for a whole batch):
 //   dump     the SAMPLE pass: evenly spaced chunks of 16 groups of 32 rows (chunk_shift = 4, chunk_stride in groups); the
 //            scores go to dump [QB][n sampled rows] and a per-query threshold comes out of them (batch_threshold_kernel);
 //   collect  the pass over all rows: every (query, row) whose score reaches thr[query] is appended to the query's list
 //            cand [QB][cap] (one atomic per hit; a hit is one score in several thousand), counts in ctl[4 q].
-// LDS: the Q images only (128 KiB at d = 512, 64 queries).
+// LDS: the Q images only (128 KiB at d = 512, 128 queries).
 // ------------------------------------------------------------------------------------------------
 constexpr int CW2 = 64;   // columns per chunk of the bf16 scan
 
-// LO: the query enters as two bf16 pieces (hi + lo: its rounding is negligible, 16 MFMAs per 4-KiB chunk at 64 queries);
-// !LO: as ONE bf16 piece — half the MFMAs, LDS reads and LDS footprint per query, so a pass carries 128 queries at
-// d <= 512 and 64 up to d = 1024; the rounding of the query, ||q - bf16(q)|| (max||x|| + max residual), then enters the
-// error bound of the threshold form (ip_topk.hip, query_eps).  NG = QB / 32 accumulator tiles of 32 rows x 32 queries.
+// The query enters as ONE bf16 piece — against two pieces (hi + lo) half the MFMAs, LDS reads and LDS footprint per query,
+// so a pass carries 128 queries at d <= 512 and 64 up to d = 1024; the rounding of the query, ||q - bf16(q)|| (max||x|| +
+// max residual), then enters the error bound of the threshold form (ip_shadow.hip, query_eps).  NG = QB / 32 accumulator
+// tiles of 32 rows x 32 queries.
+// LO (the two-piece form) is gone; the parameter stays because the benchmark's roofline matches this kernel by its full name.
 template <int PF, int QB, bool LO>
 __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const bf16_t* __restrict__ Xb, long long N, int d,
                                                                   const float* __restrict__ qpad /*[QB][d]*/, int nq,
@@ -652,22 +586,16 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
                                                                   int* __restrict__ ctl /*[QB][4] (collect)*/,
                                                                   u64* __restrict__ cand /*[QB][cap] (collect)*/, int cap,
                                                                   float* __restrict__ dump /*[QB][N] or null*/,
-                                                                  int chunk_shift, long long chunk_stride, int abl,
+                                                                  int chunk_shift, long long chunk_stride,
                                                                   long long row_base /*added to the rows recorded in cand*/) {
-#ifdef WISE_DEBUG_KNOBS
-    const int ab = abl;          // timing ablations exist in the debug library only: in the product build the hot loop has no
-#else                            // branches on them
-    constexpr int ab = 0;
-    (void)abl;
-#endif
+    static_assert(!LO, "one-piece queries only");
     constexpr int NG = QB / 32;
-    static_assert(NG == 1 || NG == 2 || (NG == 4 && !LO), "query groups per pass");
+    static_assert(NG == 2 || NG == 4, "query groups per pass");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
     const int d4 = d >> 2, d8 = d >> 3;
     unsigned char* Qh = smem;
-    unsigned char* Ql = smem + (size_t)QB * d * 2;
 
     for (int idx = threadIdx.x; idx < QB * d4; idx += WAVES * 64) {
         const int j = idx / d4, c = idx - j * d4;
@@ -676,11 +604,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
         const int c8 = c >> 1;
         const size_t off = ((size_t)j * d8 + ((c8 & ~15) | ((c8 & 15) ^ (j & 15)))) * 16 + (c & 1) * 8;
         *reinterpret_cast<uint2*>(Qh + off) = make_uint2(h01, h23);
-        if constexpr (LO) {
-            const unsigned l01 = pack_bf16x2(v.x - __uint_as_float(h01 << 16), v.y - __uint_as_float(h01 & 0xFFFF0000u));
-            const unsigned l23 = pack_bf16x2(v.z - __uint_as_float(h23 << 16), v.w - __uint_as_float(h23 & 0xFFFF0000u));
-            *reinterpret_cast<uint2*>(Ql + off) = make_uint2(l01, l23);
-        }
     }
     __syncthreads();
 
@@ -702,16 +625,8 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
         long long grow = group_row(pg) + i;
         if (grow >= row_limit) grow = row_limit - 1;
         const bf16x8* src = reinterpret_cast<const bf16x8*>(Xb + grow * d + pc * CW2 + h * 32);
-        if (ab & 4) {
-            // (timing experiment, results meaningless) the same bytes read as a TILED shadow would be: the group's chunk
-            // as 4 KiB contiguous, each wave instruction 1 KiB contiguous
-            const bf16x8* tb = reinterpret_cast<const bf16x8*>(Xb + (group_row(pg) * d + (long long)pc * 2048)) + lane;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) dst[t] = tb[t * 64];
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; ++t) dst[t] = src[t];      // (non-temporal loads measured no better here)
-        }
+        for (int t = 0; t < 4; ++t) dst[t] = src[t];      // (non-temporal loads measured no better here)
         if (issued + 1 < steps) {
             ++issued;
             if (++pc == nch) { pc = 0; pg += nw; }
@@ -739,38 +654,23 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
             const int c8 = ((cc + p) * CW2 >> 3) + h * 4;
             bf16x8 x[4] = {xq[p][0], xq[p][1], xq[p][2], xq[p][3]};
             // Q fragments of k-step j+1 are fetched from LDS while the MFMAs of k-step j run (two register sets)
-            bf16x8 qf[2][NG], lf[2][LO ? NG : 1];
-            auto fetch_q = [&](int j, bf16x8 (&qd)[NG], bf16x8 (&ld)[LO ? NG : 1]) {
+            bf16x8 qf[2][NG];
+            auto fetch_q = [&](int j, bf16x8 (&qd)[NG]) {
                 const size_t o = (size_t)(((c8 + j) & ~15) | (((c8 + j) & 15) ^ (i & 15))) * 16;
 #pragma unroll
                 for (int gq = 0; gq < NG; ++gq) {
                     const size_t rq = (size_t)(gq * 32 + i) * d8 * 16;        // (gq*32 + i) & 15 == i & 15: one swizzle for all
                     qd[gq] = *reinterpret_cast<const bf16x8*>(Qh + rq + o);
-                    if constexpr (LO) ld[gq] = *reinterpret_cast<const bf16x8*>(Ql + rq + o);
                 }
             };
-            fetch_q(0, qf[0], lf[0]);
-            if (ab & 2) {   // timing ablation: loads and LDS reads without the matrix products
-                float t = (float)x[0][0] + (float)x[1][1] + (float)x[2][2] + (float)x[3][3];
-#pragma unroll
-                for (int j = 1; j < 4; ++j) {
-                    fetch_q(j, qf[j & 1], lf[j & 1]);
-#pragma unroll
-                    for (int gq = 0; gq < NG; ++gq) { t += (float)qf[j & 1][gq][0]; if constexpr (LO) t += (float)lf[j & 1][gq][0]; }
-                }
-                prefetch(xq[p]);
-                acc[0][0] += t;
-                continue;
-            }
+            fetch_q(0, qf[0]);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                if (j < 3) fetch_q(j + 1, qf[(j + 1) & 1], lf[(j + 1) & 1]);
+                if (j < 3) fetch_q(j + 1, qf[(j + 1) & 1]);
                 if (j == 0) prefetch(xq[p]);        // x[] holds this slot's rows: the slot can take the next chunk
 #pragma unroll
-                for (int gq = 0; gq < NG; ++gq) {
-                    if constexpr (LO) acc[gq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[j], lf[j & 1][gq], acc[gq], 0, 0, 0);
+                for (int gq = 0; gq < NG; ++gq)
                     acc[gq] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[j], qf[j & 1][gq], acc[gq], 0, 0, 0);
-                }
             }
         }
         cc += PF;
@@ -789,13 +689,6 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
                         for (int gq = 0; gq < NG; ++gq) dump[(size_t)(gq * 32 + i) * N + lrow] = acc[gq][r];
                     }
                 }
-            } else if (ab & 1) {
-                float t = 0.f;
-#pragma unroll
-                for (int gq = 0; gq < NG; ++gq)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t += acc[gq][r];
-                if (t == 1.2345e-30f) ctl[0] = 1;
             } else {
                 // collect: a lane holds queries gq*32 + i, 16 rows each
                 bool hit = false;
@@ -825,38 +718,27 @@ __global__ __launch_bounds__(WAVES * 64, 1) void ip_scan_shadow64_kernel(const b
     }
 }
 
-int g_shadow_one_piece = 1;   // (debug knob) 0: two-piece bf16 query in the batched shadow scan
-bool shadow_one_piece() { return g_shadow_one_piece != 0; }
-// queries per pass: their Q images must fit LDS (160 KiB) — two bf16 pieces per query: 64 up to d = 512, 32 up to 1024;
-// one piece: 128 up to d = 512, 64 up to d = 1024
+// queries per pass: their Q images (one bf16 piece per query) must fit LDS (160 KiB): 128 up to d = 512, 64 up to d = 1024
 int shadow_pass_queries(int d) {
     if (d % (4 * CW2) != 0 || d > 1024) return 0;
-    if (g_shadow_one_piece) return d <= 512 ? 128 : 64;
-    return d <= 512 ? 64 : 32;
+    return d <= 512 ? 128 : 64;
 }
 bool shadow64_supported(int d) { return shadow_pass_queries(d) >= 64; }
-bool shadow32_supported(int d) { return shadow_pass_queries(d) >= 32; }
 int shadow64_scan_launch(const bf16_t* Xb, long long N, int d, const float* qpad, int nq, const float* thr, int* ctl,
                          u64* cand, int cap, hipStream_t st, float* dump, int qb, int chunk_shift, long long chunk_stride,
                          long long row_base) {
-    const bool lo = !g_shadow_one_piece;
-    const size_t dl = (size_t)qb * d * (lo ? 4 : 2);
+    const size_t dl = (size_t)qb * d * 2;
     static PerDeviceOnce dattr;
     dattr([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_shadow64_kernel<4, 64, true>), 160 * 1024);
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_shadow64_kernel<4, 32, true>), 160 * 1024);
         raise_lds_limit(reinterpret_cast<const void*>(ip_scan_shadow64_kernel<4, 128, false>), 160 * 1024);
         raise_lds_limit(reinterpret_cast<const void*>(ip_scan_shadow64_kernel<4, 64, false>), 160 * 1024);
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_shadow64_kernel<4, 32, false>), 160 * 1024);
     });
-    WISE_CHECK_ARG(dl <= 160 * 1024 && (qb == 32 || qb == 64 || (qb == 128 && !lo)),
-                   "shadow scan: %d queries per pass at d=%d not served", qb, d);
-#define SH_LAUNCH(QBV, LOV)                                                                                                  \
-    hipLaunchKernelGGL((ip_scan_shadow64_kernel<4, QBV, LOV>), dim3(mfma_grid(N)), dim3(WAVES * 64), dl, st, Xb, N, d, qpad, \
-                       nq, thr, ctl, cand, cap, dump, chunk_shift, chunk_stride, g_mfma_abl, row_base)
-    if (qb == 128) SH_LAUNCH(128, false);
-    else if (qb == 64) { if (lo) SH_LAUNCH(64, true); else SH_LAUNCH(64, false); }
-    else { if (lo) SH_LAUNCH(32, true); else SH_LAUNCH(32, false); }
+    WISE_CHECK_ARG(dl <= 160 * 1024 && (qb == 64 || qb == 128), "shadow scan: %d queries per pass at d=%d not served", qb, d);
+#define SH_LAUNCH(QBV)                                                                                                         \
+    hipLaunchKernelGGL((ip_scan_shadow64_kernel<4, QBV, false>), dim3(mfma_grid(N)), dim3(WAVES * 64), dl, st, Xb, N, d, qpad, \
+                       nq, thr, ctl, cand, cap, dump, chunk_shift, chunk_stride, row_base)
+    if (qb == 128) SH_LAUNCH(128);
+    else SH_LAUNCH(64);
 #undef SH_LAUNCH
     WISE_LAUNCH_CHECK("ip_scan_shadow64_kernel");
     return WISE_OK;
@@ -868,20 +750,12 @@ int split_scan_launch(const float* X, long long N, long long row_offset, int d, 
                       const u64* tau0, hipStream_t st) {
     const size_t dl = (size_t)32 * d * 4 + (size_t)WAVES * MFMA_KL * 32 * 8;
     static PerDeviceOnce dattr;
-    dattr([&] {
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_split_direct_kernel<4>), 160 * 1024);
-        raise_lds_limit(reinterpret_cast<const void*>(ip_scan_split_direct_kernel<3>), 160 * 1024);
-    });
-    if (g_split_direct == 3)
-        hipLaunchKernelGGL(ip_scan_split_direct_kernel<3>, dim3(mfma_grid(N)), dim3(WAVES * 64), dl, st, X, N, d, qpad, nq,
-                           part, row_offset, tau0, g_mfma_abl);
-    else
-        hipLaunchKernelGGL(ip_scan_split_direct_kernel<4>, dim3(mfma_grid(N)), dim3(WAVES * 64), dl, st, X, N, d, qpad, nq,
-                           part, row_offset, tau0, g_mfma_abl);
+    dattr([&] { raise_lds_limit(reinterpret_cast<const void*>(ip_scan_split_direct_kernel), 160 * 1024); });
+    hipLaunchKernelGGL(ip_scan_split_direct_kernel, dim3(mfma_grid(N)), dim3(WAVES * 64), dl, st, X, N, d, qpad, nq, part,
+                       row_offset, tau0);
     WISE_LAUNCH_CHECK("ip_scan_split_direct_kernel");
     return WISE_OK;
 }
-bool split_direct_enabled() { return g_split_direct != 0; }
 
 // tau0[q] = the key of the last of the MFMA_KL sample candidates of query q (0 while the sample holds fewer)
 __global__ void sample_threshold_kernel(const float* __restrict__ cand_scores, const long long* __restrict__ cand_rows,

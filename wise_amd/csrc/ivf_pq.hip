@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __res
             float s = b;
             if (live) s = pq_row_score<VEC>(codes + (size_t)row * m, m, tab, b);
             const u64 key = make_key(s, (unsigned)row);
-            wl.offer(live && key > wl.tau, key, lane, 64);
+            wl.offer(live && key > wl.tau, key, lane);
         }
     }
     wl.compact(lane);
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256) void pq_scan_kernel(const unsigned char* __res
             for (int i0 = 0; i0 < k; i0 += 64) {
                 const int i = i0 + lane;
                 const u64 key = i < k ? other[i] : 0;
-                wl.offer(key != 0 && key > wl.tau, key, lane, 64);
+                wl.offer(key != 0 && key > wl.tau, key, lane);
             }
         }
         wl.compact(lane);

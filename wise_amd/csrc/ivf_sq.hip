@@ -222,7 +222,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t) {
             const u64 key = make_key(base + s[t], (unsigned)row[t]);
-            wl.offer(live[t] && c == 0 && key > wl.tau, key, lane, 64);
+            wl.offer(live[t] && c == 0 && key > wl.tau, key, lane);
         }
     }
 
@@ -234,7 +234,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
             for (int i0 = 0; i0 < k; i0 += 64) {
                 const int i = i0 + lane;
                 const u64 key = i < k ? other[i] : 0;
-                wl.offer(key != 0 && key > wl.tau, key, lane, 64);
+                wl.offer(key != 0 && key > wl.tau, key, lane);
             }
         }
         wl.compact(lane);

@@ -1,5 +1,5 @@
 // range_search ("every row that scores above a radius"): what the count / fill pairs of the three families share
-// (wise_ip_range_*, wise_ivf_range_* in ip_topk.hip, wise_ivfsq_range_* in ivf_sq.hip).  `static`: each file gets its own copy.
+// (wise_ip_range_*, wise_ivf_range_* in ip_range.hip, wise_ivfsq_range_* in ivf_sq.hip).  `static`: each file gets its own copy.
 //
 // A SEGMENT is what one workgroup of the count pass owns: RANGE_ROWS consecutive rows of X for the flat index, one probed list
 // for the inverted-file types.  The count pass scores a segment in chunks of RANGE_ROWS rows, sets a bit per hit in an LDS
