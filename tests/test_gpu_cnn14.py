@@ -139,3 +139,22 @@ def test_microsoft_clap_2022_plugin_surface(golden_dir):
     assert long.shape == (1, 1024)
     h = fx.extract_audio_features_async(pre)
     assert np.array_equal(h.result(), feats)
+
+
+@pytest.mark.parametrize("order", ["SLSLSL", "SSLLSS"])
+def test_slot_workspace_regrows_between_batches(order):
+    """The 104-frame and the 4-s batch (S, L) through forward_pipelined, six submitted and none collected in between; every result
+    is forward()'s, bit for bit.  The two slots take the submissions in turn.  SLSLSL: slot 0 gets every short batch and
+    slot 1 every long one, each sized once.  SSLLSS: each slot gets short, long, short, so its workspace is too small
+    for its second batch and is replaced while its first and the other slot's batch may still run, and is kept, larger than
+    needed, for its third."""
+    w4, w1 = golden_clips()
+    short, long = torch.cat([w1, w4[1:2, :w1.shape[1]]]).cuda(), w4.cuda()
+    eng = Cnn14Engine(random_cnn14_state_dict(0), max_batch=2, max_samples=short.shape[1])
+    want = {"S": eng.forward(short).clone(), "L": eng.forward(long).clone()}
+    torch.cuda.synchronize()
+    handles = [eng.forward_pipelined(short if c == "S" else long) for c in order]
+    sizes = [sl["ws"].numel() for sl in eng._slots]
+    assert (sizes[0] == sizes[1]) == (order == "SSLLSS")        # both slots grew to the long batch's size, or neither did
+    for c, h in zip(order, handles):
+        assert torch.equal(h.result(), want[c])

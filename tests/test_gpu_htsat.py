@@ -258,3 +258,22 @@ def test_frontend_beside_matrix_kernels():
         torch.cuda.synchronize()
         wrong = sum(0 if torch.equal(mel_of(ws), alone) else 1 for ws in wss)
         assert wrong == 0, f"{wrong} of {len(wss)} front ends differ beside {name}"
+
+
+@pytest.mark.parametrize("order", ["SLSLSL", "SSLLSS"])
+def test_slot_workspace_regrows_between_batches(waves, order):
+    """4-s and 10-s batches (S, L) through forward_pipelined, six submitted and none collected in between; every result
+    is forward()'s, bit for bit.  The two slots take the submissions in turn.  SLSLSL: slot 0 gets every short batch and
+    slot 1 every long one, each sized once.  SSLLSS: each slot gets short, long, short, so its workspace is too small
+    for its second batch and is replaced while its first and the other slot's batch may still run, and is kept, larger than
+    needed, for its third."""
+    w4, w10 = waves
+    short, long = w4.cuda(), torch.cat([w10, w10.flip(1)]).cuda()
+    eng = HtsatEngine(random_htsat_state_dict(0), max_batch=2, max_samples=short.shape[1])
+    want = {"S": eng.forward(short).clone(), "L": eng.forward(long).clone()}
+    torch.cuda.synchronize()
+    handles = [eng.forward_pipelined(short if c == "S" else long) for c in order]
+    sizes = [sl["ws"].numel() for sl in eng._slots]
+    assert (sizes[0] == sizes[1]) == (order == "SSLLSS")        # both slots grew to the long batch's size, or neither did
+    for c, h in zip(order, handles):
+        assert torch.equal(h.result(), want[c])

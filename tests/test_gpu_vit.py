@@ -324,3 +324,29 @@ def test_pipelined_batches_equal_one_at_a_time():
     assert torch.equal(eng.forward_pipelined(u8).result(), eng.forward(u8))
     with pytest.raises(ValueError):
         eng.forward_pipelined(torch.zeros(2, 3, 32, 32, device="cuda"))
+
+
+def test_depth_raised_on_a_live_engine():
+    """`batches_in_flight` is read on every call: raised from 2 to 3 between calls, the slots are rebuilt (three new
+    streams, nothing of the old ones still running) and every batch still comes back as forward() returns it."""
+    spec = spec_for("ViT-B-32", "openai")
+    eng = VitEngine(spec, random_state_dict(spec, 0), max_batch=8)
+    g = torch.Generator().manual_seed(9)
+    batches = [torch.randn(8, 3, 224, 224, generator=g).cuda() for _ in range(3)]
+    want = [eng.forward(b).clone() for b in batches]
+    torch.cuda.synchronize()
+    assert len(eng._slots) == 0
+    handles = [eng.forward_pipelined(b) for b in batches]
+    assert len(eng._slots) == 2
+    for w, h in zip(want, handles):
+        assert torch.equal(h.result(), w)
+    eng.batches_in_flight = 3
+    handles = [eng.forward_pipelined(b) for b in batches + batches[:1]]
+    assert len(eng._slots) == 3
+    for w, h in reversed(list(zip(want + want[:1], handles))):
+        assert torch.equal(h.result(), w)
+    # a result handle keeps its embeddings and a copy stream, not the engine: weights and workspaces go with the last name
+    import weakref
+    alive = weakref.ref(eng)
+    del eng
+    assert alive() is None and handles[0].result().shape == (8, 512)

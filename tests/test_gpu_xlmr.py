@@ -121,3 +121,23 @@ def test_default_model_pair_end_to_end(tmp_path, monkeypatch):
     with torch.no_grad():
         want = xlmr_text_ref.xlmr_text_forward(rsd(fx.text_spec, 0), tok, heads=fx.text_spec.heads)
     assert cosine(torch.from_numpy(feats), want) > 1 - COS_TOL
+
+
+def test_graph_replay_equals_direct_launch():
+    """Small batches run from a captured hipGraph; the result must be the direct launch's, bit for bit, the graph must
+    pick up new token ids on every replay, and a grown workspace drops the graphs that hold the old one's address."""
+    spec = TINY
+    eng = XlmrTextEngine(spec, random_xlmr_state_dict(spec, 0), max_batch=8)
+    toks = torch.from_numpy(seeded_tokens(6, spec, 41))
+    eng.graph_max_batch = 0
+    direct = [eng.forward(toks[i:i + 1]).cpu() for i in range(6)]
+    direct2 = eng.forward(toks[:2]).cpu()
+    eng.graph_max_batch = 4
+    for rep in range(2):
+        for i in range(6):
+            assert torch.equal(eng.forward(toks[i:i + 1]).cpu(), direct[i])
+    assert torch.equal(eng.forward(toks[:2]).cpu(), direct2)
+    assert len(eng._graphs) == 2
+    eng.reserve(64)
+    assert len(eng._graphs) == 0
+    assert torch.equal(eng.forward(toks[:1]).cpu(), direct[0])

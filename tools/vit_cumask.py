@@ -46,11 +46,8 @@ def run(eng, batches, steps, streams=None):
 
 
 def _run(eng, batches, steps, streams=None):
-    if streams is not None:
-        eng._slots = [{"stream": s, "ws": None} for s in streams]
-        eng._next_slot = 0
-    elif hasattr(eng, "_slots"):
-        del eng._slots
+    # the engine's slots are one list object (wise_amd/feature/_engine.py InFlight): emptied, the next call takes new streams
+    eng._slots[:] = [{"stream": s, "ws": None} for s in streams or ()]
     for i in range(8):
         h = eng.forward_pipelined(batches[i % len(batches)])
     torch.cuda.synchronize()

@@ -1,4 +1,4 @@
-"""ViT-B/32 bs=256 forward_pipelined with 2, 3 and 4 batches in flight (VitEngine.pipeline_depth): python tools/vit_depth.py"""
+"""ViT-B/32 bs=256 forward_pipelined with 2, 3 and 4 batches in flight (VitEngine.batches_in_flight): python tools/vit_depth.py"""
 import sys
 import time
 
@@ -14,7 +14,7 @@ xs = [torch.randn(256, 3, 224, 224, generator=g, device="cuda") for _ in range(4
 for rnd in range(2):
     for depth in (2, 3, 4):
         eng = VitEngine(spec, sd, max_batch=256)
-        eng.pipeline_depth = depth
+        eng.batches_in_flight = depth
         for i in range(8):
             h = eng.forward_pipelined(xs[i % 4])
         torch.cuda.synchronize()

@@ -7,12 +7,12 @@ loads, reference call site src/feature/microsoft_clap.py:31), so a real checkpoi
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Dict, List, Tuple
 
 import torch
 
 from .. import _lib
+from ._engine import Engine, InFlight
 
 N_FFT, HOP, N_MELS = 1024, 320, 64
 FMAX = 14000.0                       # msclap config_2022 (the 2023 config stops at 8000)
@@ -125,79 +125,49 @@ def pack_cnn14_weights(sd: Dict[str, torch.Tensor]):
     return torch.cat(wb).to(torch.bfloat16).contiguous(), torch.cat(pf).contiguous()
 
 
-class Cnn14Engine:
+class Cnn14Engine(Engine):
     """Device copies of the packed weights + workspace; forward(wave [B,N] fp32) -> [B,1024] fp32 device tensor,
     L2-normalised (microsoft_clap.py:49-50).  Same interface as HtsatEngine."""
 
     def __init__(self, sd: Dict[str, torch.Tensor], device: str = "cuda", max_batch: int = 8,
                  max_samples: int = 480000):
-        self.lib = _lib.lib()
-        self.device = torch.device(device)
-        nb, nf = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.wise_cnn14_layout(C.byref(nb), C.byref(nf)), "wise_cnn14_layout")
-        wb, pf = pack_cnn14_weights(sd)
-        if wb.numel() != nb.value or pf.numel() != nf.value:
-            raise RuntimeError(f"Cnn14 blob size mismatch: packed {wb.numel()}/{pf.numel()}, "
-                               f"library expects {nb.value}/{nf.value}")
-        self.wb, self.pf = wb.to(self.device), pf.to(self.device)
-        self._ws = None
-        self._ws_bytes = 0
+        self._load(device, "wise_cnn14_layout", lambda: pack_cnn14_weights(sd))
+        self.batches_in_flight = 2      # what forward_pipelined keeps on the GPU; read on every call
+        self._inflight = InFlight()
         self._last = (0, 0)
         self.reserve(max_batch, max_samples)
 
     def reserve(self, batch: int, samples: int):
-        n = self.lib.wise_cnn14_workspace_bytes(batch, samples)
-        if n == 0:
-            raise ValueError(f"Cnn14: batch {batch} x {samples} samples unsupported "
-                             f"(at least {MIN_FRAMES} STFT frames = {(MIN_FRAMES - 1) * HOP} samples)")
-        if n > self._ws_bytes:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._ws_bytes = n
+        self._fit(self.lib.wise_cnn14_workspace_bytes(batch, samples), self._unsupported(batch, samples))
 
-    def forward(self, wave: torch.Tensor) -> torch.Tensor:
+    def _unsupported(self, batch: int, samples: int) -> Exception:
+        """what a zero byte count from the library becomes"""
+        return ValueError(f"Cnn14: batch {batch} x {samples} samples unsupported "
+                          f"(at least {MIN_FRAMES} STFT frames = {(MIN_FRAMES - 1) * HOP} samples)")
+
+    def _check_wave(self, wave: torch.Tensor) -> torch.Tensor:
         if wave.dim() != 2:
             raise ValueError(f"expected [B, samples], got {tuple(wave.shape)}")
-        x = wave.to(self.device, torch.float32).contiguous()
-        B, N = x.shape
-        self.reserve(B, N)
-        out = torch.empty(B, OUT_DIM, dtype=torch.float32, device=self.device)
-        rc = self.lib.wise_cnn14_forward(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), B, N, out.data_ptr(),
-                                         self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, "wise_cnn14_forward")
-        self._last = (B, N)
+        return wave.to(self.device, torch.float32).contiguous()
+
+    def _call(self, x, out, ws, stream) -> int:
+        return self.lib.wise_cnn14_forward(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1],
+                                           out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+
+    def forward(self, wave: torch.Tensor) -> torch.Tensor:
+        x = self._check_wave(wave)
+        self.reserve(*x.shape)
+        out = torch.empty(x.shape[0], OUT_DIM, dtype=torch.float32, device=self.device)
+        _lib.check(self._call(x, out, self._ws, _lib.stream_ptr()), "wise_cnn14_forward")
+        self._last = tuple(x.shape)
         return out
 
     def forward_pipelined(self, wave: torch.Tensor):
-        """Enqueue one batch of clips and return a handle at once (`.result()` -> embeddings): successive calls
-        alternate between two slots, each with its own stream and workspace (the scheme of HtsatEngine)."""
-        from .vit import PendingEmbeddings
-        if wave.dim() != 2:
-            raise ValueError(f"expected [B, samples], got {tuple(wave.shape)}")
-        x = wave.to(self.device, torch.float32).contiguous()
-        B, N = x.shape
-        need = self.lib.wise_cnn14_workspace_bytes(B, N)
-        if need == 0:
-            raise ValueError(f"Cnn14: batch {B} x {N} samples unsupported")
-        if not hasattr(self, "_slots"):
-            from .._streams import concurrent_streams   # streams SEEN to run side by side (two on one hardware queue: no overlap)
-            self._slots, self._next_slot = [{"stream": st, "ws": None} for st in concurrent_streams(2, self.device)], 0
-        slot = self._slots[self._next_slot]
-        self._next_slot ^= 1
-        if slot["ws"] is None or slot["ws"].numel() < need:
-            slot["stream"].synchronize()
-            slot["ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        slot["stream"].wait_stream(torch.cuda.current_stream(self.device))
-        out = torch.empty(B, OUT_DIM, dtype=torch.float32, device=self.device)
-        x.record_stream(slot["stream"])
-        out.record_stream(slot["stream"])
-        self.lib.wise_overlap_hint(1)
-        rc = self.lib.wise_cnn14_forward(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), B, N, out.data_ptr(),
-                                         slot["ws"].data_ptr(), slot["ws"].numel(), slot["stream"].cuda_stream)
-        self.lib.wise_overlap_hint(0)
-        _lib.check(rc, "wise_cnn14_forward")
-        done = torch.cuda.Event()
-        done.record(slot["stream"])
-        return PendingEmbeddings(out, done)
+        """Enqueue one batch of clips and return a handle at once (`.result()` -> embeddings): `batches_in_flight` (2)
+        batches are kept on the GPU (the scheme of HtsatEngine)."""
+        x = self._check_wave(wave)
+        return self._inflight.submit(self, x, OUT_DIM, self.lib.wise_cnn14_workspace_bytes(*x.shape),
+                                     self._unsupported(*x.shape), "wise_cnn14_forward", self._call)
 
     def tap(self, what: int) -> torch.Tensor:
         """parity taps of the last forward: 0 = log-mel+bn fp32 [B, frames, 64], 1 = pooled latent bf16 [B, 2048],

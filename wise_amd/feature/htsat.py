@@ -7,13 +7,13 @@ checkpoint is a pure data problem.
 """
 from __future__ import annotations
 
-import ctypes as C
 import os
 from typing import Dict, List, Tuple
 
 import torch
 
 from .. import _lib
+from ._engine import Engine, InFlight
 
 N_FFT, HOP, N_MELS = 1024, 320, 64
 SPEC_SIZE, FREQ_RATIO, WINDOW = 256, 4, 8
@@ -124,7 +124,7 @@ DEFAULT_ATTN_STREAM = True   # what HtsatEngine picks for attn_stream=None
 DEFAULT_MLP_STREAM = True    # what HtsatEngine picks for mlp_stream=None (see its docstring)
 
 
-class HtsatEngine:
+class HtsatEngine(Engine):
     """Device copies of the packed weights + workspace; forward(wave [B,N] fp32) -> [B,1024] fp32 device
     tensor, L2-normalised (microsoft_clap.py:49-50)."""
 
@@ -150,8 +150,6 @@ class HtsatEngine:
         flags bit 2; the qkv slots then hold that kernel's stream).  None = WISE_HTSAT_ATTN_STREAM (0 / 1), default ON: bs=128 x
         10 s 3.46 -> 3.31 ms one batch at a time, 3.13 -> 3.10 ms with two in flight (profiles/r04_swin_stream_study.txt).  Not
         together with ln_fold."""
-        self.lib = _lib.lib()
-        self.device = torch.device(device)
         if ln_fold is None:
             ln_fold = os.environ.get("WISE_HTSAT_LN_FOLD", "0") == "1"
         self.ln_fold = bool(ln_fold)
@@ -164,78 +162,45 @@ class HtsatEngine:
             attn_stream = (env == "1") if env in ("0", "1") else DEFAULT_ATTN_STREAM
         self.attn_stream = bool(attn_stream) and not self.ln_fold
         self._flags = (1 if self.ln_fold else 0) | (2 if self.mlp_stream else 0) | (4 if self.attn_stream else 0)
-        nb, nf = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.wise_htsat_layout(C.byref(nb), C.byref(nf)), "wise_htsat_layout")
-        wb, pf = pack_htsat_weights(sd, fold=self.ln_fold, mlp_stream=self.mlp_stream, attn_stream=self.attn_stream)
-        if wb.numel() != nb.value or pf.numel() != nf.value:
-            raise RuntimeError(f"HTSAT blob size mismatch: packed {wb.numel()}/{pf.numel()}, "
-                               f"library expects {nb.value}/{nf.value}")
-        self.wb, self.pf = wb.to(self.device), pf.to(self.device)
-        self._ws = None
-        self._ws_key = (0, 0)
+        self._load(device, "wise_htsat_layout", lambda: pack_htsat_weights(
+            sd, fold=self.ln_fold, mlp_stream=self.mlp_stream, attn_stream=self.attn_stream))
+        self.batches_in_flight = 2      # what forward_pipelined keeps on the GPU; read on every call
+        self._inflight = InFlight()
         self._last = (0, 0)
         self.reserve(max_batch, max_samples)
 
     def reserve(self, batch: int, samples: int):
-        if batch <= self._ws_key[0] and samples <= self._ws_key[1]:
-            return
-        batch, samples = max(batch, self._ws_key[0]), max(samples, self._ws_key[1])
-        n = self.lib.wise_htsat_workspace_bytes(batch, samples)
-        if n == 0:
-            raise RuntimeError("wise_htsat_workspace_bytes: bad shape")
-        self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._ws_key = (batch, samples)
+        self._fit(self.lib.wise_htsat_workspace_bytes(batch, samples), self._unsupported())
 
-    def forward(self, wave: torch.Tensor) -> torch.Tensor:
+    def _unsupported(self) -> Exception:
+        """what a zero byte count from the library becomes"""
+        return RuntimeError("wise_htsat_workspace_bytes: bad shape")
+
+    def _check_wave(self, wave: torch.Tensor) -> torch.Tensor:
         if wave.dim() != 2:
             raise ValueError(f"expected [B, samples], got {tuple(wave.shape)}")
-        x = wave.to(self.device, torch.float32).contiguous()
-        B, N = x.shape
-        if N < N_FFT // 2 + 1:
-            raise ValueError(f"audio too short for a reflect-padded STFT: {N} samples")
-        self.reserve(B, N)
-        out = torch.empty(B, OUT_DIM, dtype=torch.float32, device=self.device)
-        rc = self.lib.wise_htsat_forward2(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), B, N, out.data_ptr(),
-                                          self._ws.data_ptr(), self._ws.numel(), self._flags, _lib.stream_ptr())
-        _lib.check(rc, "wise_htsat_forward")
-        self._last = (B, N)
+        if wave.shape[1] < N_FFT // 2 + 1:
+            raise ValueError(f"audio too short for a reflect-padded STFT: {wave.shape[1]} samples")
+        return wave.to(self.device, torch.float32).contiguous()
+
+    def _call(self, x, out, ws, stream) -> int:
+        return self.lib.wise_htsat_forward2(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), x.shape[0], x.shape[1],
+                                            out.data_ptr(), ws.data_ptr(), ws.numel(), self._flags, stream)
+
+    def forward(self, wave: torch.Tensor) -> torch.Tensor:
+        x = self._check_wave(wave)
+        self.reserve(*x.shape)
+        out = torch.empty(x.shape[0], OUT_DIM, dtype=torch.float32, device=self.device)
+        _lib.check(self._call(x, out, self._ws, _lib.stream_ptr()), "wise_htsat_forward")
+        self._last = tuple(x.shape)
         return out
 
     def forward_pipelined(self, wave: torch.Tensor):
-        """Enqueue one batch of clips and return a handle at once (`.result()` -> embeddings): successive calls
-        alternate between two slots, each with its own stream and workspace, so two batches are in flight (same
-        scheme and same caveats as VitEngine.forward_pipelined)."""
-        from .vit import PendingEmbeddings
-        if wave.dim() != 2:
-            raise ValueError(f"expected [B, samples], got {tuple(wave.shape)}")
-        x = wave.to(self.device, torch.float32).contiguous()
-        B, N = x.shape
-        if N < N_FFT // 2 + 1:
-            raise ValueError(f"audio too short for a reflect-padded STFT: {N} samples")
-        if not hasattr(self, "_slots"):
-            from .._streams import concurrent_streams   # streams SEEN to run side by side (two on one hardware queue: no overlap)
-            self._slots, self._next_slot = [{"stream": st, "ws": None} for st in concurrent_streams(
-                max(2, int(getattr(self, "batches_in_flight", 2))), self.device)], 0
-        need = self.lib.wise_htsat_workspace_bytes(B, N)
-        slot = self._slots[self._next_slot]
-        self._next_slot = (self._next_slot + 1) % len(self._slots)
-        if slot["ws"] is None or slot["ws"].numel() < need:
-            # the slot's previous forward may still be running in the old workspace (allocated on the caller's stream,
-            # used on the slot's): wait for it before the allocator may reuse that block
-            slot["stream"].synchronize()
-            slot["ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        slot["stream"].wait_stream(torch.cuda.current_stream(self.device))
-        out = torch.empty(B, OUT_DIM, dtype=torch.float32, device=self.device)
-        x.record_stream(slot["stream"])
-        out.record_stream(slot["stream"])
-        self.lib.wise_overlap_hint(1)      # this batch runs beside the other slot's: tile for co-residency
-        rc = self.lib.wise_htsat_forward2(self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), B, N, out.data_ptr(),
-                                          slot["ws"].data_ptr(), slot["ws"].numel(), self._flags, slot["stream"].cuda_stream)
-        self.lib.wise_overlap_hint(0)
-        _lib.check(rc, "wise_htsat_forward")
-        done = torch.cuda.Event()
-        done.record(slot["stream"])
-        return PendingEmbeddings(out, done)
+        """Enqueue one batch of clips and return a handle at once (`.result()` -> embeddings): `batches_in_flight` (2)
+        batches are kept on the GPU (same scheme and same caveats as VitEngine.forward_pipelined)."""
+        x = self._check_wave(wave)
+        return self._inflight.submit(self, x, OUT_DIM, self.lib.wise_htsat_workspace_bytes(*x.shape), self._unsupported(),
+                                     "wise_htsat_forward", self._call)
 
     def tap(self, what: int, rows: int, cols: int) -> torch.Tensor:
         """parity taps: 0 = log-mel+bn [B*frames,64] fp32, 1 = residual stream x fp32 [rows, cols]."""

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from ._engine import _AsyncFeatures
 from .feature_extractor import FeatureExtractor
 from .clip_tokenizer import ClipTokenizer
 from .text import TextEngine, random_text_state_dict, text_spec_for
@@ -91,32 +92,6 @@ def to_pil_image(pic: torch.Tensor) -> Image.Image:
     if arr.shape[2] == 1:
         return Image.fromarray(arr[:, :, 0], mode="L")
     return Image.fromarray(arr, mode="RGB")
-
-
-class _AsyncFeatures:
-    """Embeddings on their way to the host: copy queued behind the forward on a side stream, `.result()` waits for it."""
-
-    def __init__(self, pending, engine=None):
-        dev = pending.device
-        holder = engine if engine is not None else _AsyncFeatures
-        cs = getattr(holder, "_d2h_stream", None)
-        if cs is None:
-            # a stream SEEN to run beside the engine's own (on the hardware queue of one of them the copy of batch i would
-            # sit behind batch i + 1's forward)
-            from .._streams import concurrent_streams
-            cs = concurrent_streams(1, dev, beside=[sl["stream"] for sl in getattr(engine, "_slots", [])])[0]
-            holder._d2h_stream = cs
-        with torch.cuda.stream(cs):
-            out = pending.result()                     # orders the copy stream after the forward
-            self._host = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
-            self._host.copy_(out, non_blocking=True)
-            out.record_stream(cs)
-            self._done = torch.cuda.Event()
-            self._done.record(cs)
-
-    def result(self) -> np.ndarray:
-        self._done.synchronize()
-        return self._host.numpy()
 
 
 class MlfoundationOpenClip(FeatureExtractor):
@@ -229,7 +204,7 @@ class MlfoundationOpenClip(FeatureExtractor):
             raise ValueError('input to extract_features() must be an instance of torch.Tensor')
         eng = self._get_engine()
         pending = eng.forward_pipelined(images.to(torch.float32) if images.dtype != torch.uint8 else images)
-        return _AsyncFeatures(pending, eng)
+        return _AsyncFeatures(pending)
 
     @property
     def tokenizer(self):

@@ -14,6 +14,7 @@ from typing import Dict
 import torch
 
 from .. import _lib
+from ._engine import Engine, GraphReplay
 
 SOT_TOKEN = 49406  # <start_of_text>
 EOT_TOKEN = 49407  # <end_of_text>: the largest id, which is why open_clip pools at argmax(tokens)
@@ -135,7 +136,7 @@ def pack_text_weights(spec: TextSpec, sd: Dict[str, torch.Tensor]):
     return torch.cat(wb).to(torch.bfloat16).contiguous(), torch.cat(pf).contiguous()
 
 
-class TextEngine:
+class TextEngine(Engine):
     """Device copies of the weight blobs + a workspace; `forward(tokens)` launches the HIP pipeline on the current
     torch stream and returns a device tensor [B, D] fp32 (L2-normalised)."""
 
@@ -144,35 +145,15 @@ class TextEngine:
         """`pack(spec, sd) -> (bf16 blob, fp32 blob)` defaults to the open_clip layout (pack_text_weights);
         the CLAP caption encoder passes its own (clap_text.pack_caption_weights)."""
         self.spec = spec
-        self.lib = _lib.lib()
-        self.device = torch.device(device)
         self.cfg = spec.c_config()
-        nb, nf = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.wise_text_layout(C.byref(self.cfg), C.byref(nb), C.byref(nf)), "wise_text_layout")
-        wb, pf = (pack or pack_text_weights)(spec, sd)
-        if wb.numel() != nb.value or pf.numel() != nf.value:
-            raise RuntimeError(f"weight blob size mismatch: packed {wb.numel()}/{pf.numel()}, "
-                               f"library expects {nb.value}/{nf.value}")
-        self.wb = wb.to(self.device)
-        self.pf = pf.to(self.device)
-        self._ws = None
-        self._ws_batch = 0
+        self.graph_max_batch = 4        # larger batches are launched directly; 0 turns graph replay off
+        self._graphs = GraphReplay()
+        self._load(device, "wise_text_layout", lambda: (pack or pack_text_weights)(spec, sd), C.byref(self.cfg))
         self.reserve(max_batch)
-        # A single query is ~86 launches of a few microseconds each: launch-bound.  Small batches are therefore
-        # captured once into a hipGraph (the C ABI allocates and synchronises nothing, so it is capturable) and
-        # replayed; `graph_max_batch = 0` turns this off.
-        self.graph_max_batch = 4
-        self._graphs = {}
 
     def reserve(self, batch: int):
-        if batch <= self._ws_batch:
-            return
-        n = self.lib.wise_text_workspace_bytes(C.byref(self.cfg), batch)
-        if n == 0:
-            raise RuntimeError("wise_text_workspace_bytes: bad config")
-        self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._ws_batch = batch
-        self._graphs = {}  # captured graphs hold the old workspace address
+        self._fit(self.lib.wise_text_workspace_bytes(C.byref(self.cfg), batch),
+                  RuntimeError("wise_text_workspace_bytes: bad config"), self._graphs.clear)
 
     def _launch(self, t: torch.Tensor, out: torch.Tensor):
         rc = self.lib.wise_text_forward(C.byref(self.cfg), self.wb.data_ptr(), self.pf.data_ptr(), t.data_ptr(),
@@ -180,26 +161,8 @@ class TextEngine:
                                         _lib.stream_ptr())
         _lib.check(rc, "wise_text_forward")
 
-    def _graph_for(self, B: int):
-        hit = self._graphs.get(B)
-        if hit is None:
-            tok = torch.zeros(B, self.spec.context, dtype=torch.int32, device=self.device)
-            out = torch.empty(B, self.spec.embed_dim, dtype=torch.float32, device=self.device)
-            self._launch(tok, out)  # warm-up outside the capture (first-call kernel attributes)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                # thread-local capture mode: other threads of the process (e.g. the RCCL watchdog) may call the
-                # runtime while this thread captures
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._launch(tok, out)
-            except RuntimeError:
-                self.graph_max_batch = 0   # capture not possible here: keep launching directly (same kernels)
-                torch.cuda.synchronize()
-                return None
-            hit = (g, tok, out)
-            self._graphs[B] = hit
-        return hit
+    def _placeholder(self, B: int) -> torch.Tensor:
+        return torch.zeros(B, self.spec.context, dtype=torch.int32, device=self.device)
 
     def forward(self, tokens: torch.Tensor) -> torch.Tensor:
         if tokens.dim() != 2 or tokens.shape[1] != self.spec.context or tokens.dtype not in (torch.int32, torch.int64):
@@ -207,18 +170,8 @@ class TextEngine:
         if int(tokens.min()) < 0 or int(tokens.max()) >= self.spec.vocab:
             raise ValueError("token id outside the vocabulary")
         t = tokens.to(device=self.device, dtype=torch.int32).contiguous()
-        B = t.shape[0]
-        self.reserve(B)
-        if B <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing():
-            hit = self._graph_for(B)
-            if hit is not None:
-                g, tok, gout = hit
-                tok.copy_(t)
-                g.replay()
-                return gout.clone()
-        out = torch.empty(B, self.spec.embed_dim, dtype=torch.float32, device=self.device)
-        self._launch(t, out)
-        return out
+        self.reserve(t.shape[0])
+        return self._graphs.forward(self, t)
 
     def residual(self, batch: int) -> torch.Tensor:
         out = torch.empty(batch * self.spec.context, self.spec.width, dtype=torch.float32, device=self.device)

@@ -15,6 +15,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import _lib
+from ._engine import Engine, InFlight, PendingEmbeddings  # noqa: F401  (PendingEmbeddings: importable from here as before)
 
 
 @dataclass(frozen=True)
@@ -219,22 +220,6 @@ def pack_weights(spec: VitSpec, sd: Dict[str, torch.Tensor]):
     return wb_t, pf_t
 
 
-class PendingEmbeddings:
-    """Handle of a batch enqueued by VitEngine.forward_pipelined."""
-
-    def __init__(self, out: torch.Tensor, done: "torch.cuda.Event"):
-        self._out, self._done = out, done
-
-    @property
-    def device(self) -> torch.device:
-        return self._out.device
-
-    def result(self) -> torch.Tensor:
-        """The embeddings [B, D], ordered after the batch on the caller's current stream (no host sync)."""
-        torch.cuda.current_stream(self._out.device).wait_event(self._done)
-        return self._out
-
-
 def tile_out_proj(w: torch.Tensor) -> torch.Tensor:
     """W_o [W, W] (out, in) -> the same elements in the order wise_attention_oproj_fold streams them (include/wise_hip.h):
     [wave = out // 64][K-step = in // 64][k-half][column tile j][lane = 16 * g + l][8], the element being
@@ -248,7 +233,7 @@ def tile_out_proj(w: torch.Tensor) -> torch.Tensor:
 DEFAULT_FOLD_B32 = 1   # what VitEngine picks for the ViT-B/32 shape (see its ln_fold argument)
 
 
-class VitEngine:
+class VitEngine(Engine):
     """Owns the device copies of the two weight blobs and a workspace; `forward` launches the HIP
     pipeline on the current torch stream and returns a device tensor [B, D] fp32 (L2-normalised)."""
 
@@ -271,33 +256,25 @@ class VitEngine:
         if ln_fold != spec.ln_fold:
             spec = VitSpec(**{**spec.__dict__, "ln_fold": ln_fold})
         self.spec = spec
-        self.lib = _lib.lib()
-        self.device = torch.device(device)
         self.cfg = spec.c_config()
-        nb, nf = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.wise_vit_layout(C.byref(self.cfg), C.byref(nb), C.byref(nf)), "wise_vit_layout")
         if spec.arch == 1:
-            from .siglip import pack_siglip_vision
-            wb, pf = pack_siglip_vision(spec, sd)
+            from .siglip import pack_siglip_vision as pack
         else:
-            wb, pf = pack_weights(spec, sd)
-        if wb.numel() != nb.value or pf.numel() != nf.value:
-            raise RuntimeError(f"weight blob size mismatch: packed {wb.numel()}/{pf.numel()}, "
-                               f"library expects {nb.value}/{nf.value}")
-        self.wb = wb.to(self.device)
-        self.pf = pf.to(self.device)
-        self._ws = None
-        self._ws_batch = 0
+            pack = pack_weights
+        self._load(device, "wise_vit_layout", lambda: pack(spec, sd), C.byref(self.cfg))
+        self.batches_in_flight = 2      # what forward_pipelined keeps on the GPU; read on every call
+        self._inflight = InFlight()
         self.reserve(max_batch)
 
+    def _need(self, batch: int) -> int:
+        return self.lib.wise_vit_workspace_bytes(C.byref(self.cfg), batch)
+
     def reserve(self, batch: int):
-        if batch <= self._ws_batch:
-            return
-        n = self.lib.wise_vit_workspace_bytes(C.byref(self.cfg), batch)
-        if n == 0:
-            raise RuntimeError("wise_vit_workspace_bytes: bad config")
-        self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._ws_batch = batch
+        self._fit(self._need(batch), self._unsupported())
+
+    def _unsupported(self) -> Exception:
+        """what a zero byte count from the library becomes"""
+        return RuntimeError("wise_vit_workspace_bytes: bad config")
 
     def _check_images(self, images: torch.Tensor):
         S = self.spec.image_size
@@ -311,62 +288,30 @@ class VitEngine:
             raise ValueError(f"images must be float32 or uint8, got {images.dtype}")
         return images.to(self.device).contiguous(), kind
 
+    def _call(self, kind, single_stream: bool, x, out, ws, stream) -> int:
+        fn = self.lib.wise_vit_forward_single if single_stream else self.lib.wise_vit_forward
+        return fn(C.byref(self.cfg), self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), kind, x.shape[0],
+                  out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
+
     def forward(self, images: torch.Tensor, single_stream: bool = False) -> torch.Tensor:
         """One batch -> [B, D] fp32 unit rows on the current torch stream.  By default the library overlaps two half
         batches on two streams (wise_vit_forward); single_stream=True keeps every launch on the caller's stream
         (wise_vit_forward_single: what a profiler or an event-bracketed measurement wants)."""
         x, kind = self._check_images(images)
-        B = x.shape[0]
-        self.reserve(B)
-        out = torch.empty(B, self.spec.embed_dim, dtype=torch.float32, device=self.device)
-        fn = self.lib.wise_vit_forward_single if single_stream else self.lib.wise_vit_forward
-        rc = fn(C.byref(self.cfg), self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(), kind, B,
-                out.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, "wise_vit_forward")
+        self.reserve(x.shape[0])
+        out = torch.empty(x.shape[0], self.spec.embed_dim, dtype=torch.float32, device=self.device)
+        _lib.check(self._call(kind, single_stream, x, out, self._ws, _lib.stream_ptr()), "wise_vit_forward")
         return out
 
-    # -- two whole batches in flight ---------------------------------------------------------------
-    def forward_pipelined(self, images: torch.Tensor) -> "PendingEmbeddings":
+    def forward_pipelined(self, images: torch.Tensor) -> PendingEmbeddings:
         """Enqueue one batch and return at once; `.result()` of the returned handle gives the embeddings.
 
-        Successive calls alternate between two slots, each with its own stream and workspace, so the GPU always
-        holds two whole batches: a batch runs with full-batch GEMM shapes (which tile the chip better than the
-        half batches of `forward`) and the other batch's kernels fill its LayerNorm / attention phases and tails.
-        Use it where batches arrive in a stream (extract-features style loops) and a result is consumed one batch
-        later; `forward` stays the call for a single batch."""
+        `batches_in_flight` (2) whole batches are kept on the GPU, each on a stream and in a workspace of its own
+        (_engine.InFlight).  Use it where batches arrive in a stream (extract-features style loops) and a result is
+        consumed one batch later; `forward` stays the call for a single batch."""
         x, kind = self._check_images(images)
-        B = x.shape[0]
-        if not hasattr(self, "_slots"):
-            self._slots, self._next_slot = [], 0
-        need = self.lib.wise_vit_workspace_bytes(C.byref(self.cfg), B)
-        nslots = getattr(self, "pipeline_depth", 2)
-        if len(self._slots) < nslots:
-            from .._streams import concurrent_streams   # streams SEEN to run side by side (two on one hardware queue: no overlap)
-            if self._slots:
-                torch.cuda.synchronize(self.device)      # (depth raised on a live engine: nothing may still run in the old slots)
-            self._slots = [{"stream": st, "ws": None} for st in concurrent_streams(nslots, self.device)]
-            self._next_slot = 0
-        slot = self._slots[self._next_slot]
-        self._next_slot = (self._next_slot + 1) % nslots
-        if slot["ws"] is None or slot["ws"].numel() < need:
-            # the old workspace may still be in use by this slot's previous forward, and it was allocated on another
-            # stream than the one that uses it: wait for that forward before the allocator may hand the block out again
-            slot["stream"].synchronize()
-            slot["ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        cur = torch.cuda.current_stream(self.device)
-        slot["stream"].wait_stream(cur)              # the batch was produced on the caller's stream
-        out = torch.empty(B, self.spec.embed_dim, dtype=torch.float32, device=self.device)
-        x.record_stream(slot["stream"])
-        out.record_stream(slot["stream"])
-        self.lib.wise_overlap_hint(1)   # this batch runs beside the other slot's: GEMM tiles chosen for co-residency
-        rc = self.lib.wise_vit_forward_single(C.byref(self.cfg), self.wb.data_ptr(), self.pf.data_ptr(), x.data_ptr(),
-                                              kind, B, out.data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel(),
-                                              slot["stream"].cuda_stream)
-        self.lib.wise_overlap_hint(0)
-        _lib.check(rc, "wise_vit_forward_single")
-        done = torch.cuda.Event()
-        done.record(slot["stream"])
-        return PendingEmbeddings(out, done)
+        return self._inflight.submit(self, x, self.spec.embed_dim, self._need(x.shape[0]), self._unsupported(),
+                                     "wise_vit_forward_single", lambda *args: self._call(kind, True, *args))
 
     def residual(self, batch: int) -> torch.Tensor:
         """Residual stream [B*T, W] fp32 left by the last forward (parity tap).  After a folded forward with head dim 64 the last

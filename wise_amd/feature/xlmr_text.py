@@ -19,6 +19,7 @@ from typing import Dict, List, Union
 import torch
 
 from .. import _lib
+from ._engine import Engine, GraphReplay
 
 
 @dataclass(frozen=True)
@@ -123,7 +124,7 @@ def pack_xlmr_weights(spec: XlmrSpec, sd: Dict[str, torch.Tensor]):
     return torch.cat(wb).to(torch.bfloat16).contiguous(), torch.cat(pf).contiguous()
 
 
-class XlmrTextEngine:
+class XlmrTextEngine(Engine):
     """Device copies of the weight blobs + a workspace; `forward(tokens)` launches the HIP pipeline on the current torch
     stream and returns a device tensor [B, D] fp32 (L2-normalised)."""
 
@@ -132,61 +133,26 @@ class XlmrTextEngine:
         """`spec`: anything with the XlmrSpec surface (`c_config`, context, vocab, pad_id, embed_dim, width);
         `pack(spec, sd)` -> (bf16 blob, fp32 blob), default pack_xlmr_weights"""
         self.spec = spec
-        self.lib = _lib.lib()
-        self.device = torch.device(device)
         self.cfg = spec.c_config()
-        nb, nf = C.c_int64(), C.c_int64()
-        _lib.check(self.lib.wise_xlmr_layout(C.byref(self.cfg), C.byref(nb), C.byref(nf)), "wise_xlmr_layout")
-        wb, pf = (pack or pack_xlmr_weights)(spec, sd)
-        if wb.numel() != nb.value or pf.numel() != nf.value:
-            raise RuntimeError(f"weight blob size mismatch: packed {wb.numel()}/{pf.numel()}, "
-                               f"library expects {nb.value}/{nf.value}")
-        self.wb = wb.to(self.device)
-        self.pf = pf.to(self.device)
-        self._ws = None
-        self._ws_batch = 0
+        self.graph_max_batch = 4        # larger batches are launched directly; 0 turns graph replay off
+        self._graphs = GraphReplay()
+        self._load(device, "wise_xlmr_layout", lambda: (pack or pack_xlmr_weights)(spec, sd), C.byref(self.cfg))
         self.reserve(max_batch)
-        # One query is ~175 launches of a few microseconds each (24 layers x 7 + head): launch-bound.  Small batches are
-        # captured once into a hipGraph (the C ABI allocates and synchronises nothing) and replayed, as TextEngine does.
-        self.graph_max_batch = 4
-        self._graphs = {}
 
     def reserve(self, batch: int):
-        if batch <= self._ws_batch:
-            return
-        n = self.lib.wise_xlmr_workspace_bytes(C.byref(self.cfg), batch)
-        if n == 0:
-            raise RuntimeError("wise_xlmr_workspace_bytes: bad config")
-        self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        self._ws_batch = batch
-        self._graphs = {}  # captured graphs hold the old workspace address
+        self._fit(self.lib.wise_xlmr_workspace_bytes(C.byref(self.cfg), batch),
+                  RuntimeError("wise_xlmr_workspace_bytes: bad config"), self._graphs.clear)
 
     def _launch(self, t: torch.Tensor, out: torch.Tensor):
         _lib.check(self.lib.wise_xlmr_forward(C.byref(self.cfg), self.wb.data_ptr(), self.pf.data_ptr(), t.data_ptr(),
                                               t.shape[0], out.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
                                               _lib.stream_ptr()), "wise_xlmr_forward")
 
-    def _graph_for(self, B: int):
-        hit = self._graphs.get(B)
-        if hit is None:
-            s = self.spec
-            tok = torch.full((B, s.context), s.pad_id, dtype=torch.int32, device=self.device)
-            tok[:, 0] = 0
-            tok[:, 1] = 2
-            out = torch.empty(B, s.embed_dim, dtype=torch.float32, device=self.device)
-            self._launch(tok, out)  # warm-up outside the capture (first-call kernel attributes)
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    self._launch(tok, out)
-            except RuntimeError:
-                self.graph_max_batch = 0   # capture not possible here: keep launching directly (same kernels)
-                torch.cuda.synchronize()
-                return None
-            hit = (g, tok, out)
-            self._graphs[B] = hit
-        return hit
+    def _placeholder(self, B: int) -> torch.Tensor:
+        tok = torch.full((B, self.spec.context), self.spec.pad_id, dtype=torch.int32, device=self.device)
+        tok[:, 0] = 0
+        tok[:, 1] = 2
+        return tok
 
     def forward(self, tokens: torch.Tensor) -> torch.Tensor:
         s = self.spec
@@ -199,18 +165,8 @@ class XlmrTextEngine:
         if bool((n == 0).any()) or not bool((live == (torch.arange(s.context, device=tokens.device)[None, :] < n)).all()):
             raise ValueError("token rows must be right-padded and non-empty (the HF tokenizer's padding='max_length')")
         t = tokens.to(device=self.device, dtype=torch.int32).contiguous()
-        B = t.shape[0]
-        self.reserve(B)
-        if B <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing():
-            hit = self._graph_for(B)
-            if hit is not None:
-                g, tok, gout = hit
-                tok.copy_(t)
-                g.replay()
-                return gout.clone()
-        out = torch.empty(B, s.embed_dim, dtype=torch.float32, device=self.device)
-        self._launch(t, out)
-        return out
+        self.reserve(t.shape[0])
+        return self._graphs.forward(self, t)
 
     def residual(self, batch: int) -> torch.Tensor:
         out = torch.empty(batch * self.spec.context, self.spec.width, dtype=torch.float32, device=self.device)
