@@ -41,7 +41,8 @@ const char* wise_last_error(void);
  * wise_ivfpq_scan_sel, the searches restricted to a set of ids; and the wise_sq_* entry points with wise_ivfsq_scan,
  * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it; and the count / fill pairs of
  * range_search, wise_ip_range_*, wise_ivf_range_* and wise_ivfsq_range_*; and wise_compact_plan (with wise_compact_plan_entries),
- * wise_compact_rank and wise_compact_rows, the in-place compaction behind remove_ids.  The version is 5. */
+ * wise_compact_rank and wise_compact_rows, the in-place compaction behind remove_ids; and wise_sq16_encode, wise_sq16_decode,
+ * wise_ivfsq16_scan (with _sel and _local) and wise_ivfsq16_range_count / _fill, IndexIVFSQfp16.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -450,6 +451,47 @@ int wise_ivfsq_range_fill(const uint8_t* codes, int64_t N, int d, const int64_t*
                           const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
                           float radius, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* (ABI 5, additive) IndexIVFSQfp16: inverted lists of half-precision rows — faiss's IndexIVFScalarQuantizer(IndexFlatIP(d), d, nlist,
+ * QT_fp16, METRIC_INNER_PRODUCT), by_residual.  A row of list l is kept as d IEEE binary16 values (2 d bytes, little endian), one per
+ * dimension of its residual r = x - c_l (wise_pq_residuals).  Nothing is trained beyond the centroids: there is no range, no weight
+ * row and no q0 — the query itself is the weight.  `halves` are passed as their 16-bit patterns.  Limits, errors and determinism as
+ * the wise_sq_* / wise_ivfsq_* entry points above (d % 16 == 0, 16 <= d <= 1024; k, nprobe <= 2048; nq <= 65535; halves and Q
+ * 16-byte aligned).
+ *   wise_sq16_encode: halves[i, c] = binary16(resid[i, c]), round to nearest even — subnormal results (|r| < 2^-14) are kept, not
+ *     flushed, zeros keep their sign, |r| >= 65520 becomes +-inf: exactly numpy's float32 -> float16 cast.
+ *   wise_sq16_decode: out[i, c] = centroids[l, c] + (float)halves[pos[i], c], one fp32 addition, l the list holding position pos[i];
+ *     a position outside [0, N) gives a row of NaN.  reconstruct_batch.
+ *   wise_ivfsq16_scan, _scan_sel, _scan_local: wise_ivfsq_scan, wise_ivfsq_scan_sel and wise_ivfsq_scan_local with the score
+ *     score(row) = bias[q, p] + sum_i Q[q, i] * (float)h_i; everything else — ids == NULL, ties, padding, skipped probes, keep,
+ *     pos_base, probe_count, the grids, graph capture — is theirs, from the same device code.
+ *     THE ORDER OF THE ARITHMETIC IS PART OF THE CONTRACT: with C = d / 16, chunk c of a row is its elements
+ *     e(c, i) = 8 c + i for i = 0 .. 7 and d / 2 + 8 c + (i - 8) for i = 8 .. 15 (the 16-byte pieces c and c + C of the row, so that
+ *     a wave's 16-byte loads read contiguous runs); s_c = +0, then s_c = fmaf(Q[q, e(c, i)], (float)h[e(c, i)], s_c) for i = 0 .. 15
+ *     (binary16 -> fp32 is exact, subnormals included); then for step = 1, 2, 4, ... < C, at once for every c with c + step < C,
+ *     s_c = s_c + s_{c + step} (the values from before the step); score = bias[q, p] + s_0, all in fp32.  tests/ivfsqfp16_ref.py
+ *     reproduces it bit for bit.  Workspaces: wise_ivfsq_scan_workspace_bytes / wise_ivfsq_scan_local_workspace_bytes.
+ *   wise_ivfsq16_range_count / _fill: the count / fill pair of range_search above for this family; a hit's score is, bit for bit,
+ *     wise_ivfsq16_scan's score of that row.  Workspace: wise_ivfsq_range_workspace_bytes.  As for wise_ivfsq_range_*, a list that
+ *     one query names twice must come with the same bias both times (bias = q . c_l is): its hit words are kept once. */
+int wise_sq16_encode(const float* resid, int64_t n, int d, uint16_t* halves, void* stream);
+int wise_sq16_decode(const uint16_t* halves, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                     const float* centroids, int d, float* out, void* stream);
+int wise_ivfsq16_scan(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                      int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD, int64_t* outI, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int wise_ivfsq16_scan_sel(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                          const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, int k, const uint32_t* keep,
+                          float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfsq16_scan_local(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                            const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, int k, int64_t pos_base,
+                            float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfsq16_range_count(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                             const int64_t* probes, const float* bias, int nprobe, float radius, const uint32_t* keep, int64_t* counts,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int wise_ivfsq16_range_fill(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                            const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                            const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 5, additive) remove_ids — stable, in-place compaction of an index's per-row arrays under a bitmap over row positions.
  *   keep      (N + 31) / 32 words as wise_sel_bitmap writes them, bit p set = row p STAYS.  The bits past N are ignored, whatever

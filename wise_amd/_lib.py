@@ -148,6 +148,13 @@ SIGNATURES = {
     "wise_ivfsq_range_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_ivfsq_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfsq_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_sq16_encode": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_sq16_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "wise_ivfsq16_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq16_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq16_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq16_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfsq16_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_compact_plan_entries": (_i64, [_i64]),
     "wise_compact_plan": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "wise_compact_rank": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),

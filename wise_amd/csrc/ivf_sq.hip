@@ -25,6 +25,13 @@
 //                    block's work on its list is sq_scan_list, the one body of all three kernels: a list cut by the slice scores
 //                    its rows as the whole scan does, because a row's chunks and lanes depend on d alone and d % 16 == 0 keeps
 //                    every row of a slice 16-byte aligned.
+// IndexIVFSQfp16 (faiss QT_fp16) is the SAME kernels under a second codec (Codec16 below): a row is d IEEE binary16 values of its
+// residual, nothing is trained, the query itself is the weight row and there is no q0.
+//   wise_sq16_encode  halves = (binary16)r, round to nearest even, subnormals kept (the hardware conversion: numpy's cast)
+//   wise_sq16_decode  reconstruct_batch: c_l + (float)h, one fp32 addition
+//   wise_ivfsq16_scan / _scan_sel / _scan_local / wise_ivfsq16_range_*  score(row) = bias + sum_i Q[i] * (float)h_i, one
+//                    v_fma_mix_f32 per element (1 VALU lane-operation per 2 bytes); chunk c = the row's 16-byte pieces c and c + C
+// The SQ8 entry points instantiate the bodies with Codec8 and keep their arithmetic and their bits.
 #include "probe_compact.h"
 #include "range_common.h"
 
@@ -120,6 +127,16 @@ __global__ __launch_bounds__(64) void query_kernel(const float* __restrict__ Q, 
     if (lane == 0) q0[q] = acc;
 }
 
+// the decoders: the list that holds position p — the last list whose offset is <= p (empty lists share offsets: skip them)
+__device__ __forceinline__ int list_of_position(const long long* __restrict__ list_off, int nlist, long long p) {
+    int a = 0, b = nlist;
+    while (b - a > 1) {
+        const int mid = (a + b) >> 1;
+        if (list_off[mid] <= p) a = mid; else b = mid;
+    }
+    return a;
+}
+
 // out[i][:] = c_l + (vmin + ((code + 0.5) / 255) * vdiff), l = the list that holds position pos[i]; NaN when pos[i] is out of range
 __global__ __launch_bounds__(256) void decode_kernel(const unsigned char* __restrict__ codes, long long N, const long long* __restrict__ pos,
                                                      const long long* __restrict__ list_off, int nlist, const float* __restrict__ cent,
@@ -131,12 +148,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const unsigned char* __rest
         for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = __builtin_nanf("");
         return;
     }
-    int a = 0, b = nlist;                        // the last list whose offset is <= p (empty lists share offsets: skip them)
-    while (b - a > 1) {
-        const int mid = (a + b) >> 1;
-        if (list_off[mid] <= p) a = mid; else b = mid;
-    }
-    const float* cr = cent + (size_t)a * d;
+    const float* cr = cent + (size_t)list_of_position(list_off, nlist, p) * d;
     const unsigned char* code = codes + (size_t)p * d;
     for (int c = threadIdx.x; c < d; c += blockDim.x) {
         const float xi = ((float)code[c] + 0.5f) / 255.0f;
@@ -144,6 +156,28 @@ __global__ __launch_bounds__(256) void decode_kernel(const unsigned char* __rest
         const float y = trained[c] + s;
         o[c] = cr[c] + y;
     }
+}
+
+// wise_sq16_encode: thread = one value; the conversion is the hardware's round-to-nearest-even with binary16 subnormals kept
+__global__ __launch_bounds__(256) void encode16_kernel(const float* __restrict__ r, long long total, _Float16* __restrict__ halves) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) halves[e] = (_Float16)r[e];
+}
+
+// wise_sq16_decode: out[i][:] = c_l + (float)halves[pos[i]][:], one fp32 addition; NaN when pos[i] is out of range
+__global__ __launch_bounds__(256) void decode16_kernel(const _Float16* __restrict__ halves, long long N, const long long* __restrict__ pos,
+                                                       const long long* __restrict__ list_off, int nlist, const float* __restrict__ cent,
+                                                       int d, float* __restrict__ out) {
+#pragma clang fp contract(off)
+    const long long p = pos[blockIdx.x];
+    float* o = out + (size_t)blockIdx.x * d;
+    if (p < 0 || p >= N) {
+        for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = __builtin_nanf("");
+        return;
+    }
+    const float* cr = cent + (size_t)list_of_position(list_off, nlist, p) * d;
+    const _Float16* h = halves + (size_t)p * d;
+    for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = cr[c] + (float)h[c];
 }
 
 // s = fmaf(w[4 j + b], (float)byte b of word, s) for b = 0 .. 3: the byte-select conversions, one fma each
@@ -155,23 +189,82 @@ __device__ __forceinline__ float chain_word(float s, unsigned word, const float4
     return s;
 }
 
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+
+// s = fmaf(wa, (float)low half of word, s), then s = fmaf(wb, (float)high half, s): binary16 -> fp32 is exact, subnormals kept
+__device__ __forceinline__ float chain_halves(float s, unsigned word, float wa, float wb) {
+    const f16x2 h = __builtin_bit_cast(f16x2, word);
+    s = fmaf(wa, (float)h.x, s);
+    s = fmaf(wb, (float)h.y, s);
+    return s;
+}
+
+// THE CODECS: what a lane (row, c) of the bodies below loads of its row, which 16 weights it holds, and how the two become its
+// s_c.  Everything else — the lanes of a wave-load, the fold over the chunks, the list walk, the selection, the range passes — is
+// written once and takes the codec as a template parameter; it never branches on it.
+//   Codec8   IndexIVFSQ8: d bytes a row.  Chunk c is bytes 16 c .. 16 c + 15, ONE 16-byte load; the weights are W[q, 16 c ..] of
+//            wise_sq_query and the score's base is bias + q0.
+//   Codec16  IndexIVFSQfp16: d binary16 values a row, 2 d bytes = 2 C 16-byte pieces.  Chunk c is piece c and piece c + C, i.e.
+//            elements 8 c .. 8 c + 7 (i = 0 .. 7 of the chain) and d / 2 + 8 c .. d / 2 + 8 c + 7 (i = 8 .. 15): each of the TWO
+//            load instructions of a wave-load then reads, per row, C consecutive pieces — a contiguous run of d bytes — and whole
+//            rows are consumed.  The weights are the query's own values at those elements; there is no q0: base = bias.
+struct Codec8 {
+    static constexpr int PIECES = 1;
+    static __device__ __forceinline__ size_t row_bytes(int d) { return (size_t)d; }
+    static __device__ __forceinline__ float base(float bias, const float* __restrict__ q0, int qi) { return bias + q0[qi]; }
+    static __device__ __forceinline__ void weights(const float* __restrict__ wrow, int d, int c, float4 (&w)[4]) {
+        const float4* wq = reinterpret_cast<const float4*>(wrow + 16 * c);
+        w[0] = wq[0]; w[1] = wq[1]; w[2] = wq[2]; w[3] = wq[3];
+    }
+    static __device__ __forceinline__ void load(const unsigned char* __restrict__ row, int C, int c, u32x4 (&x)[PIECES]) {
+        x[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row) + c);
+    }
+    static __device__ __forceinline__ float chain(const u32x4 (&x)[PIECES], const float4 (&w)[4]) {
+        float a = 0.f;
+        a = chain_word(a, x[0][0], w[0]);
+        a = chain_word(a, x[0][1], w[1]);
+        a = chain_word(a, x[0][2], w[2]);
+        a = chain_word(a, x[0][3], w[3]);
+        return a;
+    }
+};
+
+struct Codec16 {
+    static constexpr int PIECES = 2;
+    static __device__ __forceinline__ size_t row_bytes(int d) { return (size_t)2 * d; }
+    static __device__ __forceinline__ float base(float bias, const float* __restrict__, int) { return bias; }
+    static __device__ __forceinline__ void weights(const float* __restrict__ wrow, int d, int c, float4 (&w)[4]) {
+        const float4* lo = reinterpret_cast<const float4*>(wrow + 8 * c);
+        const float4* hi = reinterpret_cast<const float4*>(wrow + (d >> 1) + 8 * c);
+        w[0] = lo[0]; w[1] = lo[1]; w[2] = hi[0]; w[3] = hi[1];
+    }
+    static __device__ __forceinline__ void load(const unsigned char* __restrict__ row, int C, int c, u32x4 (&x)[PIECES]) {
+        x[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row) + c);
+        x[1] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row) + C + c);
+    }
+    static __device__ __forceinline__ float chain(const u32x4 (&x)[PIECES], const float4 (&w)[4]) {
+        float a = 0.f;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            a = chain_halves(a, x[p][0], w[2 * p].x, w[2 * p].y);
+            a = chain_halves(a, x[p][1], w[2 * p].z, w[2 * p].w);
+            a = chain_halves(a, x[p][2], w[2 * p + 1].x, w[2 * p + 1].y);
+            a = chain_halves(a, x[p][3], w[2 * p + 1].z, w[2 * p + 1].w);
+        }
+        return a;
+    }
+};
+
 // THE SUM OF THE CONTRACT for SQ_T wave-loads at once (the scan and the range_search kernels): lane (sub, c) reads chunk c of row
 // r[t] (an existing row: callers clamp), runs its fmaf chain, and the chunks of a row are folded into its lane c = 0
+template <class Codec>
 __device__ __forceinline__ void sq_score_loads(const unsigned char* __restrict__ codes, int d, int C, int c, const long long (&r)[SQ_T],
-                                               const float4 w0, const float4 w1, const float4 w2, const float4 w3, float (&s)[SQ_T]) {
-    u32x4 x[SQ_T];
+                                               const float4 (&w)[4], float (&s)[SQ_T]) {
+    u32x4 x[SQ_T][Codec::PIECES];
 #pragma unroll
-    for (int t = 0; t < SQ_T; ++t)
-        x[t] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(codes + (size_t)r[t] * d) + c);
+    for (int t = 0; t < SQ_T; ++t) Codec::load(codes + (size_t)r[t] * Codec::row_bytes(d), C, c, x[t]);
 #pragma unroll
-    for (int t = 0; t < SQ_T; ++t) {
-        float a = 0.f;
-        a = chain_word(a, x[t][0], w0);
-        a = chain_word(a, x[t][1], w1);
-        a = chain_word(a, x[t][2], w2);
-        a = chain_word(a, x[t][3], w3);
-        s[t] = a;
-    }
+    for (int t = 0; t < SQ_T; ++t) s[t] = Codec::chain(x[t], w);
     for (int step = 1; step < C; step <<= 1) {                                      // the chunks of a row: lanes c .. c + C - 1
         const bool take = c + step < C;
 #pragma unroll
@@ -184,7 +277,7 @@ __device__ __forceinline__ void sq_score_loads(const unsigned char* __restrict__
 
 // One block's scan of the rows [lo, hi) of codes under the weight row wrow [d]: score = base + s_0; the k best keys go to dst.
 // SEL: only the rows whose bit of `keep` is set are offered; a wave whose SQ_T loads hold no such row skips them (wave-uniform)
-template <bool SEL>
+template <class Codec, bool SEL>
 __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ codes, long long lo, long long hi,
                                              const float* __restrict__ wrow, float base, int d, int k, int cap, u64* __restrict__ dst,
                                              const unsigned* __restrict__ keep) {
@@ -193,8 +286,8 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
     const int C = d >> 4, RPL = 64 / C;
     const int sub = lane / C, c = lane - sub * C;
     const bool active = sub < RPL;
-    const float4* wq = reinterpret_cast<const float4*>(wrow + 16 * c);
-    const float4 w0 = wq[0], w1 = wq[1], w2 = wq[2], w3 = wq[3];
+    float4 w[4];
+    Codec::weights(wrow, d, c, w);
 
     WaveList wl;
     wl.init(reinterpret_cast<u64*>(smem) + (size_t)wave * cap, cap, k, lane);
@@ -218,7 +311,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t) r[t] = row[t] < hi ? row[t] : hi - 1;        // stay inside the list; masked below
         float s[SQ_T];
-        sq_score_loads(codes, d, C, c, r, w0, w1, w2, w3, s);
+        sq_score_loads<Codec>(codes, d, C, c, r, w, s);
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t) {
             const u64 key = make_key(base + s[t], (unsigned)row[t]);
@@ -243,7 +336,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
 }
 
 // grid = nq * nprobe: block b scans the list probes[b] of query b / nprobe; its k keys go to part[(b % nprobe) * nq + b / nprobe]
-template <bool SEL>
+template <class Codec, bool SEL>
 __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                       int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                       const long long* __restrict__ probes, const float* __restrict__ bias, int nprobe,
@@ -253,8 +346,8 @@ __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __res
     const long long l = probes[(size_t)qi * nprobe + pi];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }          // block-uniform
-    sq_scan_list<SEL>(codes, lo, hi, W + (size_t)qi * d, bias[(size_t)qi * nprobe + pi] + q0[qi], d, k, cap,
-                      part + ((size_t)pi * nq + qi) * k, keep);
+    sq_scan_list<Codec, SEL>(codes, lo, hi, W + (size_t)qi * d, Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi), d, k, cap,
+                             part + ((size_t)pi * nq + qi) * k, keep);
 }
 
 // wise_ivfsq_scan_local.  grid = nq * nprobe: block b is probe group b / nq of query b % nq — group-major, so the blocks that
@@ -263,6 +356,7 @@ __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __res
 // probes / bias are the compacted ones (compact_probes_bias_kernel with G = nprobe and a share of 1: used[q] = the probes kept =
 // the groups of query q, one kept probe each); a block past used[q] returns BEFORE it loads the query's weight row, and its slot
 // of part is never read: the merge folds used[q] lists.  list_off is clipped to the slice, rows are positions in the slice.
+template <class Codec>
 __global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                             int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                             const long long* __restrict__ probes, const float* __restrict__ bias,
@@ -273,23 +367,24 @@ __global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char*
     const long long l = probes[(size_t)qi * nprobe + g];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }
-    sq_scan_list<false>(codes, lo, hi, W + (size_t)qi * d, bias[(size_t)qi * nprobe + g] + q0[qi], d, k, cap,
-                        part + ((size_t)g * nq + qi) * k, nullptr);
+    sq_scan_list<Codec, false>(codes, lo, hi, W + (size_t)qi * d, Codec::base(bias[(size_t)qi * nprobe + g], q0, qi), d, k, cap,
+                               part + ((size_t)g * nq + qi) * k, nullptr);
 }
 
 // ---- range_search (wise_ivfsq_range_*): every row of the probed lists with (bias + q0) + s_0 > radius, s_0 from sq_score_loads.
 // One block per (query, probe) as sq_scan_kernel; structure, workspace and the determinism argument: range_common.h
+template <class Codec>
 struct SqLane {
     int C, RPL, sub, c;
     bool active;
-    float4 w0, w1, w2, w3;
+    float4 w[4];
     __device__ __forceinline__ void init(const float* __restrict__ wrow, int d, int lane) {
         C = d >> 4; RPL = 64 / C; sub = lane / C; c = lane - sub * C; active = sub < RPL;
-        const float4* wq = reinterpret_cast<const float4*>(wrow + 16 * c);
-        w0 = wq[0]; w1 = wq[1]; w2 = wq[2]; w3 = wq[3];
+        Codec::weights(wrow, d, c, w);
     }
 };
 
+template <class Codec>
 __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                              int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                              const long long* __restrict__ probes, const float* __restrict__ bias,
@@ -301,8 +396,8 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
     const long long l = probes[(size_t)qi * nprobe + pi];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }            // block-uniform
-    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
-    SqLane L;
+    const float base = Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi);
+    SqLane<Codec> L;
     L.init(W + (size_t)qi * d, d, lane);
     unsigned* dst = hit + (size_t)qi * wstride + (lo >> 5) + (l > 0 ? l : 0);
     long long total = 0;
@@ -325,7 +420,7 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
             }
             if (keep && __ballot(any) == 0) continue;
             float s[SQ_T];
-            sq_score_loads(codes, d, L.C, L.c, r, L.w0, L.w1, L.w2, L.w3, s);
+            sq_score_loads<Codec>(codes, d, L.C, L.c, r, L.w, s);
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t)
                 if (live[t] && L.c == 0 && base + s[t] > radius) range_mark(hb, (int)(r[t] - clo));
@@ -336,6 +431,7 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
     if (threadIdx.x == 0) seg[(size_t)qi * (nprobe + 1) + pi] = total;
 }
 
+template <class Codec>
 __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                             int nlist, const long long* __restrict__ ids, const float* __restrict__ W,
                                                             const float* __restrict__ q0, const long long* __restrict__ probes,
@@ -355,8 +451,8 @@ __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char*
     if (l < 0 || l >= nlist) return;                                                // not the probes count saw: nothing to read
     const long long lo = list_off[l], hi = list_off[l + 1];
     const unsigned* words = hit + (size_t)qi * wstride + (lo >> 5) + l;
-    const float base = bias[(size_t)qi * nprobe + pi] + q0[qi];
-    SqLane L;
+    const float base = Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi);
+    SqLane<Codec> L;
     L.init(W + (size_t)qi * d, d, lane);
     for (long long clo = lo; clo < hi; clo += RANGE_ROWS, words += RANGE_WORDS) {
         const long long chi = clo + RANGE_ROWS < hi ? clo + RANGE_ROWS : hi;
@@ -377,7 +473,7 @@ __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char*
                 r[t] = clo + lst[e[t] >= 0 ? e[t] : cnt - 1];
             }
             float s[SQ_T];
-            sq_score_loads(codes, d, L.C, L.c, r, L.w0, L.w1, L.w2, L.w3, s);
+            sq_score_loads<Codec>(codes, d, L.C, L.c, r, L.w, s);
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t)
                 if (e[t] >= 0 && L.c == 0) {
@@ -468,15 +564,17 @@ extern "C" size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int 
     return part + local_probe_bytes(nq, nprobe) + local_bias_bytes(nq, nprobe) + 2 * local_count_bytes(nq);
 }
 
-// wise_ivfsq_scan and, with keep, wise_ivfsq_scan_sel
-static int sq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+// wise_ivfsq_scan / wise_ivfsq16_scan and, with keep, their _sel forms.  Codec16 has no q0
+template <class Codec>
+static int sq_scan_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                         const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
                         int64_t* outI, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* keep) {
+    constexpr bool HAS_Q0 = Codec::PIECES == 1;
     WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
     WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "%s: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)", what, nq,
                    nprobe, k);
     WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld nlist=%d out of range", what, (long long)N, nlist);
-    WISE_CHECK_ARG(W && q0 && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
     WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
     const size_t need = wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
@@ -484,10 +582,10 @@ static int sq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int d
     u64* part = reinterpret_cast<u64*>(workspace);
     const int cap = topk_list_cap(k);
     const size_t lds = (size_t)4 * cap * 8;
-    auto kern = keep ? sq_scan_kernel<true> : sq_scan_kernel<false>;
+    auto kern = keep ? sq_scan_kernel<Codec, true> : sq_scan_kernel<Codec, false>;
     if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, codes, (const long long*)list_off, nlist, W, q0,
-                       (const long long*)probes, bias, nprobe, nq, d, k, cap, part, keep);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, reinterpret_cast<const unsigned char*>(codes),
+                       (const long long*)list_off, nlist, W, q0, (const long long*)probes, bias, nprobe, nq, d, k, cap, part, keep);
     WISE_LAUNCH_CHECK("sq_scan_kernel");
     return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st);
 }
@@ -495,8 +593,8 @@ static int sq_scan_impl(const char* what, const uint8_t* codes, int64_t N, int d
 extern "C" int wise_ivfsq_scan(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                                const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
                                float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
-    return sq_scan_impl("ivfsq_scan", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
-                        workspace_bytes, stream, nullptr);
+    return sq_scan_impl<Codec8>("ivfsq_scan", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
+                                workspace_bytes, stream, nullptr);
 }
 
 extern "C" int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
@@ -504,23 +602,41 @@ extern "C" int wise_ivfsq_scan_sel(const uint8_t* codes, int64_t N, int d, const
                                    const uint32_t* keep, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     WISE_CHECK_ARG(keep || N == 0, "ivfsq_scan_sel: null bitmap");
-    return sq_scan_impl("ivfsq_scan_sel", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI, workspace,
-                        workspace_bytes, stream, keep);
+    return sq_scan_impl<Codec8>("ivfsq_scan_sel", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, outD, outI,
+                                workspace, workspace_bytes, stream, keep);
 }
 
-extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
-                                     const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
-                                     int k, int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
-                                     size_t workspace_bytes, void* stream) {
-    SQ_CHECK_SHAPE("ivfsq_scan_local");
-    WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "ivfsq_scan_local: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)",
-                   nq, nprobe, k);
-    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "ivfsq_scan_local: N=%lld nlist=%d pos_base=%lld out of range",
+extern "C" int wise_ivfsq16_scan(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                 const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
+                                 int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_scan_impl<Codec16>("ivfsq16_scan", halves, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, bias, nprobe, k, outD, outI,
+                                 workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int wise_ivfsq16_scan_sel(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                                     const uint32_t* keep, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    WISE_CHECK_ARG(keep || N == 0, "ivfsq16_scan_sel: null bitmap");
+    return sq_scan_impl<Codec16>("ivfsq16_scan_sel", halves, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, bias, nprobe, k, outD,
+                                 outI, workspace, workspace_bytes, stream, keep);
+}
+
+template <class Codec>
+static int sq_scan_local_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                              const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                              int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    constexpr bool HAS_Q0 = Codec::PIECES == 1;
+    WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
+    WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "%s: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)", what, nq,
+                   nprobe, k);
+    WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "%s: N=%lld nlist=%d pos_base=%lld out of range", what,
                    (long long)N, nlist, (long long)pos_base);
-    WISE_CHECK_ARG(W && q0 && probes && bias && outD && outI && list_off && (codes || N == 0), "ivfsq_scan_local: null pointer");
-    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "ivfsq_scan_local: codes and W must be 16-byte aligned");
+    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
     const size_t need = wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k);
-    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "ivfsq_scan_local: workspace %zu < %zu bytes", workspace_bytes, need);
+    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
     u64* part = reinterpret_cast<u64*>(wsb);
@@ -538,13 +654,29 @@ extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, con
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
     const int cap = topk_list_cap(k);
     const size_t lds = (size_t)4 * cap * 8;
-    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel), (int)lds);
-    hipLaunchKernelGGL(sq_scan_local_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, codes, lo, nlist, W, q0, live,
-                       lbias, nprobe, nq, d, k, cap, part, used);
+    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel<Codec>), (int)lds);
+    hipLaunchKernelGGL(sq_scan_local_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st,
+                       reinterpret_cast<const unsigned char*>(codes), lo, nlist, W, q0, live, lbias, nprobe, nq, d, k, cap, part, used);
     WISE_LAUNCH_CHECK("sq_scan_local_kernel");
     // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
     return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
                               used, (long long)pos_base);
+}
+
+extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
+                                     int k, int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return sq_scan_local_impl<Codec8>("ivfsq_scan_local", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, k, pos_base,
+                                      outD, outI, probe_count, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivfsq16_scan_local(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                       const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
+                                       int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return sq_scan_local_impl<Codec16>("ivfsq16_scan_local", halves, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, bias, nprobe, k,
+                                       pos_base, outD, outI, probe_count, workspace, workspace_bytes, stream);
 }
 
 static bool sq_range_shape_ok(int64_t N, int nlist, int nq, int nprobe) {
@@ -556,13 +688,13 @@ extern "C" size_t wise_ivfsq_range_workspace_bytes(int64_t N, int nlist, int nq,
     return range_workspace_bytes(nq, range_ivf_wstride(N, nlist), nprobe);
 }
 
-static int sq_range_args(const char* what, const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
-                         const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius, void* workspace,
-                         size_t workspace_bytes) {
+static int sq_range_args(const char* what, bool has_q0, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist,
+                         const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                         void* workspace, size_t workspace_bytes) {
     WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
     WISE_CHECK_ARG(sq_range_shape_ok(N, nlist, nq, nprobe), "%s: N=%lld nlist=%d nq=%d nprobe=%d unsupported (nq <= 65535, nprobe <= 2048)",
                    what, (long long)N, nlist, nq, nprobe);
-    WISE_CHECK_ARG(W && q0 && probes && bias && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(W && (q0 || !has_q0) && probes && bias && list_off && (codes || N == 0), "%s: null pointer", what);
     WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
     WISE_CHECK_ARG(radius == radius && radius - radius == 0.f, "%s: radius must be finite", what);
     const size_t need = wise_ivfsq_range_workspace_bytes(N, nlist, nq, nprobe);
@@ -570,39 +702,95 @@ static int sq_range_args(const char* what, const uint8_t* codes, int64_t N, int 
     return WISE_OK;
 }
 
-extern "C" int wise_ivfsq_range_count(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
-                                      const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
-                                      const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = sq_range_args("ivfsq_range_count", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
+template <class Codec>
+static int sq_range_count_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                               const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                               const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = sq_range_args(what, Codec::PIECES == 1, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
                                workspace_bytes))
         return rc;
-    WISE_CHECK_ARG(counts, "ivfsq_range_count: null pointer");
+    WISE_CHECK_ARG(counts, "%s: null pointer", what);
     hipStream_t st = (hipStream_t)stream;
     const long long wstride = range_ivf_wstride(N, nlist);
     unsigned* hit = reinterpret_cast<unsigned*>(workspace);
     long long* seg = reinterpret_cast<long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
-    hipLaunchKernelGGL(sq_range_count_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st, codes, (const long long*)list_off,
-                       nlist, W, q0, (const long long*)probes, bias, nprobe, d, radius, keep, hit, wstride, seg);
+    hipLaunchKernelGGL(sq_range_count_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned char*>(codes), (const long long*)list_off, nlist, W, q0, (const long long*)probes, bias,
+                       nprobe, d, radius, keep, hit, wstride, seg);
     WISE_LAUNCH_CHECK("sq_range_count_kernel");
     hipLaunchKernelGGL(range_scan_kernel, dim3(nq), dim3(1024), 0, st, seg, (long long)nprobe, reinterpret_cast<long long*>(counts));
     WISE_LAUNCH_CHECK("range_scan_kernel");
     return WISE_OK;
 }
 
+template <class Codec>
+static int sq_range_fill_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                              const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                              const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = sq_range_args(what, Codec::PIECES == 1, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
+                               workspace_bytes))
+        return rc;
+    WISE_CHECK_ARG(lims && outD && outI, "%s: null pointer", what);
+    const long long wstride = range_ivf_wstride(N, nlist);
+    const unsigned* hit = reinterpret_cast<const unsigned*>(workspace);
+    const long long* seg = reinterpret_cast<const long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
+    hipLaunchKernelGGL(sq_range_fill_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned char*>(codes), (const long long*)list_off, nlist, reinterpret_cast<const long long*>(ids),
+                       W, q0, (const long long*)probes, bias, nprobe, d, hit, wstride, seg, reinterpret_cast<const long long*>(lims), outD,
+                       reinterpret_cast<long long*>(outI));
+    WISE_LAUNCH_CHECK("sq_range_fill_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_ivfsq_range_count(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                                      const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                                      const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_range_count_impl<Codec8>("ivfsq_range_count", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, keep,
+                                       counts, workspace, workspace_bytes, stream);
+}
+
 extern "C" int wise_ivfsq_range_fill(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                                      const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe,
                                      float radius, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-    if (int rc = sq_range_args("ivfsq_range_fill", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
-                               workspace_bytes))
-        return rc;
-    WISE_CHECK_ARG(lims && outD && outI, "ivfsq_range_fill: null pointer");
-    const long long wstride = range_ivf_wstride(N, nlist);
-    const unsigned* hit = reinterpret_cast<const unsigned*>(workspace);
-    const long long* seg = reinterpret_cast<const long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
-    hipLaunchKernelGGL(sq_range_fill_kernel, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, (hipStream_t)stream, codes,
-                       (const long long*)list_off, nlist, reinterpret_cast<const long long*>(ids), W, q0, (const long long*)probes, bias, nprobe, d,
-                       hit, wstride, seg, reinterpret_cast<const long long*>(lims), outD, reinterpret_cast<long long*>(outI));
-    WISE_LAUNCH_CHECK("sq_range_fill_kernel");
+    return sq_range_fill_impl<Codec8>("ivfsq_range_fill", codes, N, d, list_off, nlist, ids, W, q0, nq, probes, bias, nprobe, radius, lims,
+                                      outD, outI, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivfsq16_range_count(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                                        const int64_t* probes, const float* bias, int nprobe, float radius, const uint32_t* keep,
+                                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_range_count_impl<Codec16>("ivfsq16_range_count", halves, N, d, list_off, nlist, Q, nullptr, nq, probes, bias, nprobe, radius,
+                                        keep, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivfsq16_range_fill(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                       const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
+                                       const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    return sq_range_fill_impl<Codec16>("ivfsq16_range_fill", halves, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, bias, nprobe,
+                                       radius, lims, outD, outI, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_sq16_encode(const float* resid, int64_t n, int d, uint16_t* halves, void* stream) {
+    SQ_CHECK_SHAPE("sq16_encode");
+    WISE_CHECK_ARG(n >= 0 && n < (1ll << 31) && (n == 0 || (resid && halves)), "sq16_encode: bad argument");
+    if (n == 0) return WISE_OK;
+    const long long total = (long long)n * d;
+    hipLaunchKernelGGL(encode16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, resid, total,
+                       reinterpret_cast<_Float16*>(halves));
+    WISE_LAUNCH_CHECK("sq encode16_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_sq16_decode(const uint16_t* halves, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
+                                const float* centroids, int d, float* out, void* stream) {
+    SQ_CHECK_SHAPE("sq16_decode");
+    WISE_CHECK_ARG(N >= 0 && rows >= 0 && nlist >= 1 && list_off && centroids && (N == 0 || halves) && (rows == 0 || (pos && out)),
+                   "sq16_decode: bad argument");
+    if (rows == 0) return WISE_OK;
+    hipLaunchKernelGGL(decode16_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const _Float16*>(halves),
+                       (long long)N, (const long long*)pos, (const long long*)list_off, nlist, centroids, d, out);
+    WISE_LAUNCH_CHECK("sq decode16_kernel");
     return WISE_OK;
 }

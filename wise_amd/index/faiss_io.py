@@ -56,6 +56,18 @@ The file of index type 'IndexIVFSQ8' (write_ivf_sq_ip / read_ivf_sq_ip) restates
     u64  code_size (= d) | u8 by_residual (1)
     'ilar' array inverted lists with code_size = d: per non-empty list u8 codes[size*d] | i64 ids[size]
 
+The file of index type 'IndexIVFSQfp16' (write_ivf_sq16_ip; read by the same readers) is the same faiss record with the other
+quantizer type WISE builds — faiss's QT_fp16, which trains nothing:
+
+    u32  'IwSq' ... direct map                                                 as above
+    i32  qtype (4 = QT_fp16) | i32 rangestat (0) | f32 rangestat_arg (0) | u64 d | u64 code_size (= 2d)
+    u64  0                                        the trained vector: empty
+    u64  code_size (= 2d) | u8 by_residual (1)
+    'ilar' array inverted lists with code_size = 2d: per non-empty list f16[size*d] (IEEE binary16, little endian) | i64 ids[size]
+
+Its reader's dict has 'halves' [n,d] float16 where the QT_8bit dict has 'codes' and 'trained'.  Like the other records this one
+is restated from the format and unpinned against a faiss-written file.
+
 Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' / 'IwSq' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
@@ -78,6 +90,7 @@ import numpy as np
 
 _DUMMY = 1 << 20
 QT_8BIT = 0          # faiss ScalarQuantizer::QuantizerType::QT_8bit
+QT_FP16 = 4          # ... QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16
 
 
 def _fourcc(s: str) -> int:
@@ -274,7 +287,7 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
 def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload).
     pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks).
-    sq: an 'IwSq' file instead; the ScalarQuantizer record's trained values [2d] are appended."""
+    sq: an 'IwSq' file instead; the ScalarQuantizer record's trained values [2d] are appended (QT_8bit), None for QT_fp16."""
     base = f.tell()                                          # (an 'IwPQ' record may sit inside a 'WiPR' file)
     _expect_record(f, p, "IwPQ" if pq else "IwSq" if sq else "IwFl")
     hdr = f.read(_HDR_SIZE + 4)
@@ -309,15 +322,19 @@ def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     trained = None
     if sq:
         qtype, rangestat, rangestat_arg, dsq, code_size_sq, cnt = struct.unpack("<iifQQQ", f.read(36))
-        if qtype != QT_8BIT or dsq != d or code_size_sq != d or cnt != 2 * d:
+        sq_bytes = {QT_8BIT: d, QT_FP16: 2 * d}.get(qtype)
+        if sq_bytes is None or dsq != d or code_size_sq != sq_bytes or cnt != (2 * d if qtype == QT_8BIT else 0):
             raise RuntimeError(f"{p}: unsupported IndexIVFScalarQuantizer (qtype={qtype}, d={dsq}, code_size={code_size_sq}, "
-                               f"{cnt} trained values): QT_8bit with one range per dimension is what is read")
+                               f"{cnt} trained values): QT_8bit with one range per dimension is what is read, and qtype 4 "
+                               f"(QT_fp16) with no trained value")
         trained = np.fromfile(f, dtype=np.float32, count=cnt)
         code_size_ivf, by_residual = struct.unpack("<QB", f.read(9))
-        if trained.size != cnt or code_size_ivf != d or by_residual != 1:
+        if trained.size != cnt or code_size_ivf != sq_bytes or by_residual != 1:
             raise RuntimeError(f"{p}: unsupported IndexIVFScalarQuantizer (code_size={code_size_ivf}, by_residual={by_residual})")
+        if qtype == QT_FP16:
+            trained = None
     il, nl2, code_size = struct.unpack("<IQQ", f.read(20))
-    if il != _fourcc("ilar") or nl2 != nlist or code_size != (m if pq else d if sq else 4 * d):
+    if il != _fourcc("ilar") or nl2 != nlist or code_size != (m if pq else (d if trained is not None else 2 * d) if sq else 4 * d):
         raise RuntimeError(f"{p}: unexpected inverted lists (type 0x{il:08x}, code size {code_size})")
     (lt, vn) = struct.unpack("<IQ", f.read(12))
     sizes = np.zeros(nlist, dtype=np.int64)
@@ -633,6 +650,28 @@ def write_ivf_sq_ip(path, centroids: np.ndarray, trained: np.ndarray, codes: np.
         _write_lists(f, codes, ids, list_off)
 
 
+def write_ivf_sq16_ip(path, centroids: np.ndarray, halves: np.ndarray, ids: np.ndarray, list_off: np.ndarray, nprobe: int = 1) -> None:
+    """halves [n,d] float16 / ids hold the lists back to back (QT_fp16, by_residual: nothing trained)."""
+    halves = np.ascontiguousarray(halves, dtype="<f2")
+    n = halves.shape[0]
+    centroids, ids, list_off = _ivf_arrays(centroids, ids, list_off, n)
+    d = centroids.shape[1]
+    assert halves.shape == (n, d)
+    with open(path, "wb") as f:
+        _write_ivf_head(f, "IwSq", centroids, n, nprobe)
+        f.write(struct.pack("<iifQQ", QT_FP16, 0, 0.0, d, 2 * d))      # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
+        f.write(struct.pack("<Q", 0))                            # trained: empty
+        f.write(struct.pack("<QB", 2 * d, 1))                    # code_size, by_residual
+        _write_lists(f, halves, ids, list_off)
+
+
+def _sq_state(centroids, trained, payload, ids, list_off, nprobe) -> dict:
+    """the dict of the 'IwSq' readers: 'trained' and 'codes' (QT_8bit), or 'halves' alone (QT_fp16: trained is None)"""
+    if trained is None:
+        return {"centroids": centroids, "halves": payload, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+    return {"centroids": centroids, "trained": trained, "codes": payload, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+
+
 def _read_ivf_sq_head(f, p):
     try:
         return _read_ivf_head(f, p, sq=True)
@@ -642,12 +681,14 @@ def _read_ivf_sq_head(f, p):
 
 def read_ivf_sq_ip(path):
     """-> dict(centroids [nlist,d], trained [2d] (vmin, then vdiff), codes [n,d] uint8, ids [n], list_off [nlist+1], nprobe), the
-    lists back to back in list order.  A file cut short is refused (RuntimeError)."""
+    lists back to back in list order; for a QT_fp16 file dict(centroids, halves [n,d] float16, ids, list_off, nprobe).  A file cut
+    short is refused (RuntimeError)."""
     p = _existing(path)
     with open(p, "rb") as f:
         centroids, list_off, nprobe, data, trained = _read_ivf_sq_head(f, p)
-        codes, ids = _read_lists(f, p, list_off, data, centroids.shape[1], np.uint8, strict=True)
-    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+        payload, ids = _read_lists(f, p, list_off, data, centroids.shape[1], np.uint8 if trained is not None else np.dtype("<f2"),
+                                   strict=True)
+    return _sq_state(centroids, trained, payload, ids, list_off, nprobe)
 
 
 def ivf_sq_ip_ntotal(path) -> int:
@@ -661,13 +702,14 @@ def read_ivf_sq_ip_range(path, lo: int, hi: int):
     """Rows [lo, hi) of the list-major arrays read_ivf_sq_ip returns, reading only the lists that overlap the range (one rank's
     slice of an index sharded across GPUs: wise_amd/index/sharded.py).  -> the dict of read_ivf_sq_ip with codes [hi-lo,d],
     ids [hi-lo] and list_off = clip(list_off - lo, 0, hi - lo); centroids and trained are whole.  List l's payload sits at
-    list_off[l] * (d + 8) bytes into the payload (codes, then ids)."""
+    list_off[l] * (d + 8) bytes into the payload (codes, then ids); 2d + 8 and 'halves' for a QT_fp16 file."""
     p = _existing(path)
     with open(p, "rb") as f:
         centroids, list_off, nprobe, data, trained = _read_ivf_sq_head(f, p)
-        codes, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1], np.uint8, lo, hi, "read_ivf_sq_ip_range",
-                                                 strict=True)
-    return {"centroids": centroids, "trained": trained, "codes": codes, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+        payload, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1],
+                                                   np.uint8 if trained is not None else np.dtype("<f2"), lo, hi, "read_ivf_sq_ip_range",
+                                                   strict=True)
+    return _sq_state(centroids, trained, payload, ids, list_off, nprobe)
 
 
 def index_fourcc(path) -> str:
@@ -711,7 +753,8 @@ def index_ntotal(path) -> int:
 
 def write_index(path, state, nprobe=None) -> None:
     """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
-    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'X': 'IwFl'.  nprobe: state's own unless given."""
+    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl'.  nprobe:
+    state's own unless given."""
     nprobe = state.get("nprobe", 1) if nprobe is None else nprobe
     lists = (state["ids"], state["list_off"])
     store = {k: state[k] for k in ("kind", "k_factor", "rows", "scales") if k in state}
@@ -723,6 +766,8 @@ def write_index(path, state, nprobe=None) -> None:
         write_ivf_pq_ip(path, state["centroids"], state["codebooks"], state["codes"], *lists, nprobe=nprobe)
     elif "trained" in state:
         write_ivf_sq_ip(path, state["centroids"], state["trained"], state["codes"], *lists, nprobe=nprobe)
+    elif "halves" in state:
+        write_ivf_sq16_ip(path, state["centroids"], state["halves"], *lists, nprobe=nprobe)
     elif "X" in state:
         write_ivf_flat_ip(path, state["centroids"], state["X"], *lists, nprobe=nprobe)
     else:

@@ -24,6 +24,7 @@ one entry of FAMILIES below: what it adds to IndexIVFFlat is its trained state, 
     IndexIVFOPQ<m>, ...R8 / R16      IVFOPQIPIndex,          codebooks, rotation [d,d]      as their IndexIVFPQ forms     'WiOP' (own) around 'IwPQ'
                                      IVFOPQRefineIPIndex     of the residuals (faiss's OPQ)                               / 'WiPR'
     IndexIVFSQ8                      IVFSQIPIndex            ranges [2d]: vmin, vdiff       d code bytes (QT_8bit)        'IwSq' (faiss)
+    IndexIVFSQfp16                   IVFSQfp16IPIndex        -                              d binary16 values (QT_fp16)   'IwSq' (faiss), qtype 4
 
 The bare names `IndexIVFPQ` / `IndexIVFOPQ` mean m = d / 4.  Everything below is written once and driven by that table.
 
@@ -72,12 +73,12 @@ from .flat_ip import FlatIPIndex
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
-from .ivf_sq import IVFSQIPIndex, check_sq_shape
+from .ivf_sq import IVFSQfp16IPIndex, IVFSQIPIndex, check_sq_shape
 from .mutate import plan_update
 from .search_index import SearchIndex
 from .selector import SearchParameters, as_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
-                      ShardedIVFSQIPIndex, shard_range)
+                      ShardedIVFSQfp16IPIndex, ShardedIVFSQIPIndex, shard_range)
 
 
 def _always_exchange():
@@ -163,7 +164,7 @@ class _Family:
     @property
     def marks(self):
         """the state keys that tell this family's reader dict from the others' (faiss_io.write_index picks the record by them)"""
-        return {k for k, _, _ in self.trained} | ({'kind'} if self.refine else set()) | ({'X'} if self.payload == 'X' else set())
+        return {k for k, _, _ in self.trained} | ({'kind'} if self.refine else set()) | ({self.payload} - {'codes'})
 
 
 _CENTROIDS = ('centroids', lambda index, v: index.set_centroids(v), lambda d, nlist, m: (nlist, d))
@@ -204,6 +205,8 @@ FAMILIES = (
             'codes', ShardedIVFPQRefineIPIndex, refine=True),
     _Family(_named('IndexIVFSQ8', check_sq_shape), lambda: IVFSQIPIndex, 'ivfsq_index_factory', lambda d, nlist, m, kind: (d, nlist),
             (_RANGES,), 'codes', ShardedIVFSQIPIndex),
+    _Family(_named('IndexIVFSQfp16', check_sq_shape), lambda: IVFSQfp16IPIndex, 'ivfsqfp16_index_factory',
+            lambda d, nlist, m, kind: (d, nlist), (), 'halves', ShardedIVFSQfp16IPIndex),
 )
 _MARKS = set().union(*(fam.marks for fam in FAMILIES))
 
@@ -230,7 +233,7 @@ def _host_state(index, fam):
 
 def _unknown_index_type(index_type):
     return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
-                               f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds')
+                               f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16')
 
 
 def _sharded_ivf_on():
@@ -278,6 +281,7 @@ class FeatureSearchIndex(SearchIndex):
     ivfopq_index_factory = IVFOPQIPIndex
     ivfopq_refine_index_factory = IVFOPQRefineIPIndex
     ivfsq_index_factory = IVFSQIPIndex
+    ivfsqfp16_index_factory = IVFSQfp16IPIndex
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -403,7 +407,7 @@ class FeatureSearchIndex(SearchIndex):
             a = ivf.assign(X)
             fields = [X]
         else:
-            a, *fields = ivf.encode_rows(X)         # codes [n,m] u8 (+ compact rows [n,d] i8 / bf16 bits, scales [n] f32); SQ8: [n,d] u8
+            a, *fields = ivf.encode_rows(X)         # codes [n,m] u8 (+ compact rows [n,d] i8 / bf16 bits, scales [n] f32); SQ8: [n,d] u8; SQfp16: [n,d] f16
             a = np.asarray(a, dtype=np.int64)
         # a row's payload: its fields' bytes back to back, padded to whole int32
         widths = [int(np.prod(f.shape[1:], dtype=np.int64)) * f.dtype.itemsize for f in fields]

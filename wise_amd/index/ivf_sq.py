@@ -25,6 +25,13 @@ Across GPUs (sharded.py: ShardedIVFSQIPIndex) an index holds ONE RANK's slice of
 ranges, list_off clipped to the slice, and `pos_base`, the position of its first row in the whole array.  `search_local_device`
 is then the rank's share of a search (wise_ivfsq_scan_local: only the probed lists the rank holds), `encode_rows` hands a rank's
 rows back as codes for the collective build, and `reconstruct_batch` decodes the ids the slice holds (NaN for the others).
+
+IVFSQfp16IPIndex (index type 'IndexIVFSQfp16') is the two-bytes-per-dimension point of the same family: faiss's QT_fp16.  A row is
+its residual cast to IEEE binary16 (wise_sq16_encode: numpy's float32 -> float16 cast), N * (2 d + 8) bytes in all.  Nothing is
+trained beyond the centroids, so there is no `trained` state, no weight row and no q0: the query itself is the weight and a search
+has one launch fewer — probes, bias, then wise_ivfsq16_scan with score = bias + sum_i q_i * (float)h_i in the order
+include/wise_hip.h fixes (tests/ivfsqfp16_ref.py restates it).  It is IVFSQIPIndex with those differences and nothing else: the
+list store, the selector, range_search, remove_ids, the rank-local scan and the sharded wrapper are shared.
 """
 from __future__ import annotations
 
@@ -46,17 +53,22 @@ def check_sq_shape(d: int) -> None:
 
 
 def _gather_codes(codes: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-    """rows of d bytes (whole multiples of 16) moved as rows of d / 4 floats: the copy does not look at the values"""
+    """rows of d bytes or 2 d bytes (whole multiples of 16) moved as rows of floats: the copy does not look at the values"""
     out = torch.empty_like(codes)
-    _lib.check(_lib.lib().wise_ivf_gather_rows(codes.data_ptr(), idx.data_ptr(), idx.shape[0], codes.shape[1] // 4, out.data_ptr(),
-                                               _lib.stream_ptr()), "wise_ivf_gather_rows")
+    _lib.check(_lib.lib().wise_ivf_gather_rows(codes.data_ptr(), idx.data_ptr(), idx.shape[0], codes.shape[1] * codes.element_size() // 4,
+                                               out.data_ptr(), _lib.stream_ptr()), "wise_ivf_gather_rows")
     return out
 
 
 class IVFSQIPIndex(IVFIndexBase):
+    # what IVFSQfp16IPIndex replaces: the payload's dtype and the entry points of the C ABI
+    PAYLOAD_DTYPE, PAYLOAD_NP = torch.uint8, np.uint8
+    SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq_scan", "wise_ivfsq_scan_sel", "wise_ivfsq_scan_local"
+    RANGE_COUNT, RANGE_FILL = "wise_ivfsq_range_count", "wise_ivfsq_range_fill"
+
     def __init__(self, d: int, nlist: int, device: str = "cuda"):
         check_sq_shape(int(d))
-        super().__init__(d, nlist, device, width=int(d), dtype=torch.uint8, gather=_gather_codes)
+        super().__init__(d, nlist, device, width=int(d), dtype=self.PAYLOAD_DTYPE, gather=_gather_codes)
         self.trained: Optional[torch.Tensor] = None        # [2 d] fp32: vmin, then vdiff
         self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
 
@@ -67,7 +79,7 @@ class IVFSQIPIndex(IVFIndexBase):
     def hbm_bytes(self) -> int:
         """Bytes of HBM the index holds once its lists are merged: codes, ids, offsets, centroids, ranges."""
         self._finalize()
-        return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.trained))
+        return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.trained) if t is not None)   # (fp16: no ranges)
 
     # -- training -------------------------------------------------------------------------------
     def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
@@ -102,7 +114,7 @@ class IVFSQIPIndex(IVFIndexBase):
 
     def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
         if not self.is_trained:
-            raise RuntimeError("IVFSQIPIndex: train() before add_with_ids()")
+            raise RuntimeError(f"{type(self).__name__}: train() before add_with_ids()")
         x = _rows_f32(x, self.d, "add_with_ids")
         ids = _ids_i64(ids, x.shape[0])
         for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
@@ -114,10 +126,10 @@ class IVFSQIPIndex(IVFIndexBase):
         """(assign [n] int64, codes [n, d] uint8) as numpy for the rows x [n, d]: what add_with_ids would put into the lists,
         handed back instead (the collective build moves it to the rank that owns the row's position)."""
         if not self.is_trained:
-            raise RuntimeError("IVFSQIPIndex: train() before encode_rows()")
+            raise RuntimeError(f"{type(self).__name__}: train() before encode_rows()")
         x = _rows_f32(x, self.d, "encode_rows")
         assign = np.empty(x.shape[0], dtype=np.int64)
-        codes = np.empty((x.shape[0], self.d), dtype=np.uint8)
+        codes = np.empty((x.shape[0], self.d), dtype=self.PAYLOAD_NP)
         for s in range(0, x.shape[0], chunk):
             xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
             a = self._coarse.assign_device(xs, self.centroids)
@@ -152,19 +164,25 @@ class IVFSQIPIndex(IVFIndexBase):
         bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
         _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
                                     bias.data_ptr(), st), "wise_pq_bias")
-        W = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
-        q0 = torch.empty(n, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), n, self.d, W.data_ptr(), q0.data_ptr(), st), "wise_sq_query")
-        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(), W.data_ptr(),
-                q0.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
+        weights = self._weights(qs)
+        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
+                *(t.data_ptr() for t in weights), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
         tail = (ws.data_ptr(), ws.numel(), st)
         if local:
-            _lib.check(lib.wise_ivfsq_scan_local(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
-                       "wise_ivfsq_scan_local")
+            _lib.check(getattr(lib, self.SCAN_LOCAL)(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
+                       self.SCAN_LOCAL)
         elif keep is not None:
-            _lib.check(lib.wise_ivfsq_scan_sel(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), "wise_ivfsq_scan_sel")
+            _lib.check(getattr(lib, self.SCAN_SEL)(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), self.SCAN_SEL)
         else:
-            _lib.check(lib.wise_ivfsq_scan(*head, D.data_ptr(), I.data_ptr(), *tail), "wise_ivfsq_scan")
+            _lib.check(getattr(lib, self.SCAN)(*head, D.data_ptr(), I.data_ptr(), *tail), self.SCAN)
+
+    def _weights(self, qs: torch.Tensor) -> tuple:
+        """What the scan entry points take between ids and nq: (W, q0) of wise_sq_query."""
+        W = torch.empty(qs.shape[0], self.d, dtype=torch.float32, device=self.device)
+        q0 = torch.empty(qs.shape[0], dtype=torch.float32, device=self.device)
+        _lib.check(_lib.lib().wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), qs.shape[0], self.d, W.data_ptr(), q0.data_ptr(),
+                                            _lib.stream_ptr()), "wise_sq_query")
+        return W, q0
 
     def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
         """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
@@ -204,21 +222,19 @@ class IVFSQIPIndex(IVFIndexBase):
         bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
         _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
                                     bias.data_ptr(), st), "wise_pq_bias")
-        W = torch.empty(n, self.d, dtype=torch.float32, device=self.device)
-        q0 = torch.empty(n, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), n, self.d, W.data_ptr(), q0.data_ptr(), st), "wise_sq_query")
+        weights = self._weights(qs)
         head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist)
 
-        def mid():       # built inside the closures: they, not this frame, keep W, q0, probes and bias alive until fill has run
-            return (W.data_ptr(), q0.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, radius)
+        def mid():       # built inside the closures: they, not this frame, keep the weights, probes and bias alive until fill has run
+            return (*(t.data_ptr() for t in weights), n, probes.data_ptr(), bias.data_ptr(), nprobe, radius)
 
         def count(counts, ws):
-            _lib.check(lib.wise_ivfsq_range_count(*head, *mid(), _lib.ptr(keep), counts.data_ptr(), ws.data_ptr(), ws.numel(), st),
-                       "wise_ivfsq_range_count")
+            _lib.check(getattr(lib, self.RANGE_COUNT)(*head, *mid(), _lib.ptr(keep), counts.data_ptr(), ws.data_ptr(), ws.numel(), st),
+                       self.RANGE_COUNT)
 
         def fill(lims, D, P, ws):
-            _lib.check(lib.wise_ivfsq_range_fill(*head, 0, *mid(), lims.data_ptr(), D.data_ptr(), P.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                 st), "wise_ivfsq_range_fill")
+            _lib.check(getattr(lib, self.RANGE_FILL)(*head, 0, *mid(), lims.data_ptr(), D.data_ptr(), P.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), st), self.RANGE_FILL)
         return count, fill
 
     # -- the rest of the surface the REST layer touches -------------------------------------------
@@ -231,9 +247,14 @@ class IVFSQIPIndex(IVFIndexBase):
         pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
         _lib.check(lib.wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
         out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_sq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
-                                      self.centroids.data_ptr(), self.trained.data_ptr(), self.d, out.data_ptr(), st), "wise_sq_decode")
+        self._decode(pos, out)
         return out.cpu().numpy()
+
+    def _decode(self, pos: torch.Tensor, out: torch.Tensor) -> None:
+        ls = self._lists
+        _lib.check(_lib.lib().wise_sq_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
+                                             self.centroids.data_ptr(), self.trained.data_ptr(), self.d, out.data_ptr(),
+                                             _lib.stream_ptr()), "wise_sq_decode")
 
     def lists_host(self):
         """(centroids [nlist,d], trained [2d] = vmin then vdiff, codes [N,d] uint8, ids [N], list_off [nlist+1]) as numpy."""
@@ -245,3 +266,45 @@ class IVFSQIPIndex(IVFIndexBase):
     def state_host(self) -> dict:
         """The index as the dict faiss_io.read_ivf_sq_ip returns and faiss_io.write_index takes."""
         return dict(zip(("centroids", "trained", "codes", "ids", "list_off"), self.lists_host()), nprobe=self.nprobe)
+
+
+class IVFSQfp16IPIndex(IVFSQIPIndex):
+    """Index type 'IndexIVFSQfp16' (module docstring): the rows as binary16 residuals, `halves` [N, d] float16.  No `trained`
+    state: is_trained is the coarse quantizer's alone, train() runs the coarse k-means only."""
+    PAYLOAD_DTYPE, PAYLOAD_NP = torch.float16, np.float16
+    SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq16_scan", "wise_ivfsq16_scan_sel", "wise_ivfsq16_scan_local"
+    RANGE_COUNT, RANGE_FILL = "wise_ivfsq16_range_count", "wise_ivfsq16_range_fill"
+
+    @property
+    def is_trained(self) -> bool:
+        return self._coarse.is_trained
+
+    def train(self, x) -> None:
+        self._coarse.train(_rows_f32(x, self.d, "train"))
+
+    def set_trained(self, vmin, vdiff) -> None:
+        raise TypeError("IVFSQfp16IPIndex has no trained ranges")
+
+    def _encode(self, resid: torch.Tensor) -> torch.Tensor:
+        halves = torch.empty(resid.shape[0], self.d, dtype=torch.float16, device=self.device)
+        _lib.check(_lib.lib().wise_sq16_encode(resid.data_ptr(), resid.shape[0], self.d, halves.data_ptr(), _lib.stream_ptr()),
+                   "wise_sq16_encode")
+        return halves
+
+    def _weights(self, qs: torch.Tensor) -> tuple:
+        return (qs,)                                     # the query is the weight row; there is no q0
+
+    def _decode(self, pos: torch.Tensor, out: torch.Tensor) -> None:
+        ls = self._lists
+        _lib.check(_lib.lib().wise_sq16_decode(ls.data.data_ptr(), ls.n, pos.data_ptr(), pos.numel(), ls.list_off.data_ptr(), self.nlist,
+                                               self.centroids.data_ptr(), self.d, out.data_ptr(), _lib.stream_ptr()), "wise_sq16_decode")
+
+    def lists_host(self):
+        """(centroids [nlist,d], halves [N,d] float16, ids [N], list_off [nlist+1]) as numpy."""
+        self._finalize()
+        ls = self._lists
+        return self.centroids.cpu().numpy(), ls.data.cpu().numpy(), ls.ids.cpu().numpy(), ls.list_off.cpu().numpy()
+
+    def state_host(self) -> dict:
+        """The index as the dict faiss_io.read_ivf_sq_ip returns for a QT_fp16 file and faiss_io.write_index takes."""
+        return dict(zip(("centroids", "halves", "ids", "list_off"), self.lists_host()), nprobe=self.nprobe)

@@ -21,7 +21,8 @@ and return a different answer (a pool of W * kc).
 
 ShardedIVFSQIPIndex wraps a slice of an IndexIVFSQ8 (d code bytes per row, the centroids and the [2 d] ranges on every rank,
 wise_ivfsq_scan_local): one exchange, as ShardedIVFPQIPIndex.  reconstruct_batch is the flat wrapper's: the rank that holds an id
-decodes it (wise_sq_decode against its clipped offsets), the others answer NaN.
+decodes it (wise_sq_decode against its clipped offsets), the others answer NaN.  ShardedIVFSQfp16IPIndex is the same wrapper around
+a slice of an IndexIVFSQfp16 (2 d bytes per row, only the centroids replicated, wise_ivfsq16_scan_local).
 """
 from __future__ import annotations
 
@@ -242,6 +243,10 @@ class ShardedIVFSQIPIndex(ShardedIVFFlatIPIndex):
     def hbm_bytes(self) -> int:
         """Of this rank's slice (local, not collective)."""
         return self.local.hbm_bytes()
+
+
+class ShardedIVFSQfp16IPIndex(ShardedIVFSQIPIndex):
+    """Around a local IVFSQfp16IPIndex slice (binary16 rows, all centroids, ids global, `pos_base` set): nothing differs."""
 
 
 MAX_MERGE_KEYS = 65536           # wise_topk_merge: parts * k
