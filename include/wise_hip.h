@@ -42,7 +42,9 @@ const char* wise_last_error(void);
  * wise_ivfsq_scan_sel and wise_ivfsq_scan_local, IndexIVFSQ8 and one rank's slice of it; and the count / fill pairs of
  * range_search, wise_ip_range_*, wise_ivf_range_* and wise_ivfsq_range_*; and wise_compact_plan (with wise_compact_plan_entries),
  * wise_compact_rank and wise_compact_rows, the in-place compaction behind remove_ids; and wise_sq16_encode, wise_sq16_decode,
- * wise_ivfsq16_scan (with _sel and _local) and wise_ivfsq16_range_count / _fill, IndexIVFSQfp16.  The version is 5. */
+ * wise_ivfsq16_scan (with _sel and _local) and wise_ivfsq16_range_count / _fill, IndexIVFSQfp16; and the wise_ipsq16_* entry points
+ * (wise_ipsq16_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and the wise_ipsqfp16_*_workspace_bytes),
+ * IndexSQfp16.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -492,6 +494,64 @@ int wise_ivfsq16_range_count(const uint16_t* halves, int64_t N, int d, const int
 int wise_ivfsq16_range_fill(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                             const float* Q, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
                             const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexSQfp16: exhaustive inner-product search over rows kept as IEEE binary16 — faiss's IndexScalarQuantizer(d,
+ * QT_fp16, METRIC_INNER_PRODUCT) under an IndexIDMap.  The whole index is rows [N, d] binary16 bit patterns (2 d bytes a row, little
+ * endian, 16-byte aligned) plus the ids: no fp32 rows and no shadow copy; the same array serves the single-query scan and, as matrix-core
+ * operands as loaded, the batched passes.  Rows are encoded by wise_sq16_encode applied to the rows themselves.  Limits of every entry
+ * point: d % 16 == 0, 16 <= d <= 1024, 0 <= N < 2^32 - 1, rows and Q 16-byte aligned.  Anything outside an entry point's limits, a null
+ * pointer, a misaligned pointer or a workspace shorter than its *_workspace_bytes is WISE_E_INVALID with a wise_last_error text, and
+ * nothing is written.  No call allocates or reads back: all can be captured into a graph.  All deterministic.
+ * THE SCORE IS A CONTRACT: score(q, r) = s_0 of the wise_ivfsq16_scan arithmetic above — chunks e(c, i), one fmaf chain of 16 per
+ * chunk over the exact binary16 -> fp32 conversions, the tree of adds over steps 1, 2, 4, ... — with NO bias term added (the value s_0
+ * itself, a -0 included).  tests/sqfp16_flat_ref.py restates it; every entry point below returns exactly these bits.  Non-finite
+ * stored values are outside the contract.  (The three workspace functions are spelled wise_ipsqfp16_*: no symbol pairs "sq16" with
+ * "workspace", which the IndexIVFSQfp16 entry points established — they share the SQ8 sizes — and the tests hold.)
+ *   wise_ipsq16_topk: the exact scan.  1 <= nq <= 1024, 1 <= k <= 2048; ids / id_base as wise_ip_topk_f32 (ids == NULL: id_base + row);
+ *     outD descending, ties: the lower position wins, (-3.4028235e38, -1) padding when N < k; N = 0 gives all padding.  The grid runs
+ *     over row ranges and a pass carries up to 4 queries; a pass reads N d 2 bytes.  Workspace: wise_ipsqfp16_topk_workspace_bytes.
+ *   wise_ipsq16_topk_pos: the same scan over the rows rows[pos[i]], i < n_pos (pos ascending, entries in [0, N): what
+ *     wise_sel_positions writes) — the counterpart of wise_ip_topk_pos_f32.  Keys carry pos[i]; n_pos == 0 gives all padding.
+ *     Workspace: wise_ipsqfp16_topk_workspace_bytes(n_pos, d, nq, k).
+ *   wise_ipsq16_range_count / _fill: the count / fill pair of range_search above over the N rows (a segment is 2048 consecutive rows;
+ *     keep, radius, counts, lims, the fixed order — ascending position —, ids == NULL => id_base + position: as wise_ip_range_*);
+ *     a hit iff score > radius, strictly, and a hit's score is the exact scan's, from the same device routine.  1 <= nq <= 65535.
+ *     Workspace: wise_ipsqfp16_range_workspace_bytes.
+ *   wise_ipsq16_reconstruct: out[i, :] = (float)rows[p, :] for the row p that carries the id query_ids[i] (ids == NULL: p = id -
+ *     id_base), a row of NaN where no row does — wise_reconstruct_batch for this payload.
+ *   wise_ipsq16_prepare: norms[0] (device float) = max_r |(float)rows[r, :]|_2, 0 for N = 0.  A row's norm is a fixed-order fp32 sum
+ *     and the maximum is exact: the same rows give the same bits.  What the batched search's error band needs.
+ *   wise_ipsq16_topk_batched: 3 or more queries in passes of 128 (d <= 512) or 64 on the matrix cores, in the threshold form of
+ *     wise_ip_topk_shadow_f32's batched passes: the queries are rounded to ONE binary16 piece; per query the exact scan's k-th score
+ *     over a sample of evenly spaced rows is a lower bound t of the index's exact k-th score; collect rounds on
+ *     v_mfma_f32_32x32x16_f16 (the stored rows are the A operands as loaded) list EVERY (query, row) whose approximate score reaches
+ *     t - eps, over growing shares of the rows first, which tightens t, then over all rows; the listed rows are re-scored by the exact
+ *     scan's routine and the k best written.  eps = |q - f16(q)|_2 norms[0] (Cauchy-Schwarz on the query's rounding; the rows are not
+ *     rounded again, so there is no row-side term) + d 2^-22 |q|_2 norms[0] (fp32 accumulation of both sums): no assumption on the data
+ *     (DESIGN.md section 4).  A query whose list (4096 rows) overflows has its pass redone by the exact scan queued behind and gated on
+ *     the device.  The answer has the bits of wise_ipsq16_topk on any data.  norms: what wise_ipsq16_prepare wrote for these rows.
+ *     counters (device, two int32, may be NULL): [0] += queries answered from the lists, [1] += queries handed to the exact scan.
+ *     Served: d % 128 == 0 in [256, 1024], 3 <= nq <= 1024, k <= 128, 4096 <= N < 2^31 — no floor beyond that: routing by size is the
+ *     caller's.  Workspace: wise_ipsqfp16_topk_batched_workspace_bytes (0: shape not served). */
+size_t wise_ipsqfp16_topk_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_ipsq16_topk(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base,
+                     float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ipsq16_topk_pos(const uint16_t* rows, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq, int k,
+                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t wise_ipsqfp16_range_workspace_bytes(int64_t N, int d, int nq);
+int wise_ipsq16_range_count(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
+                            int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ipsq16_range_fill(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
+                           int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int wise_ipsq16_reconstruct(const uint16_t* rows, int64_t N, int d, const int64_t* ids, int64_t id_base, const int64_t* query_ids,
+                            int n, float* out, void* stream);
+int wise_ipsq16_prepare(const uint16_t* rows, int64_t N, int d, float* norms /*[1]*/, void* stream);
+size_t wise_ipsqfp16_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_ipsq16_topk_batched(const uint16_t* rows, const float* norms /*[1]*/, int64_t N, int d, const float* Q, int nq, int k,
+                             const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters, void* workspace,
+                             size_t workspace_bytes, void* stream);
 
 /* (ABI 5, additive) remove_ids — stable, in-place compaction of an index's per-row arrays under a bitmap over row positions.
  *   keep      (N + 31) / 32 words as wise_sel_bitmap writes them, bit p set = row p STAYS.  The bits past N are ignored, whatever

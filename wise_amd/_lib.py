@@ -155,6 +155,16 @@ SIGNATURES = {
     "wise_ivfsq16_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfsq16_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfsq16_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsqfp16_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ipsq16_topk": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq16_topk_pos": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsqfp16_range_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wise_ipsq16_range_count": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq16_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq16_reconstruct": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _vp, _vp]),
+    "wise_ipsq16_prepare": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_ipsqfp16_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ipsq16_topk_batched": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_compact_plan_entries": (_i64, [_i64]),
     "wise_compact_plan": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "wise_compact_rank": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),

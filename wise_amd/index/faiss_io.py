@@ -68,6 +68,20 @@ quantizer type WISE builds — faiss's QT_fp16, which trains nothing:
 Its reader's dict has 'halves' [n,d] float16 where the QT_8bit dict has 'codes' and 'trained'.  Like the other records this one
 is restated from the format and unpinned against a faiss-written file.
 
+The file of index type 'IndexSQfp16' (write_idmap_sq16_ip / read_idmap_sq16_ip) is the flat file above with faiss's
+IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT) in the place of the IndexFlatIP:
+
+    u32  'IxMp' | header                          IndexIDMap, as in the flat file
+    u32  'IxSQ' | header                          IndexScalarQuantizer fourcc
+    i32  qtype (4 = QT_fp16) | i32 rangestat (0) | f32 rangestat_arg (0) | u64 d | u64 code_size (= 2d)
+    u64  0                                        the trained vector: empty          (the ScalarQuantizer record of 'IwSq', qtype 4)
+    u64  n_bytes (= ntotal*2d) | f16[ntotal*d]    the codes vector: the rows as IEEE binary16, little endian
+    u64  ntotal | i64[ntotal]                     id_map
+
+A bare 'IxSQ' file (no id map) reads with ids equal to positions.  index_fourcc(path, inner=True) names the index an 'IxMp' file
+wraps ('IxFI' or 'IxSQ'); read_index / read_index_range / index_ntotal serve this file too (dict(halves, ids)), and write_index
+writes it for a state of 'halves' and 'ids' alone.  A rank's part of a row-sharded index is a complete file of its rows.
+
 Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' / 'IwSq' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
@@ -712,9 +726,124 @@ def read_ivf_sq_ip_range(path, lo: int, hi: int):
     return _sq_state(centroids, trained, payload, ids, list_off, nprobe)
 
 
-def index_fourcc(path) -> str:
+def index_fourcc(path, inner: bool = False) -> str:
+    """The fourcc the file opens with; inner: for an 'IxMp' (IndexIDMap) file the fourcc of the index it wraps — 'IxFI' for
+    IndexFlatIP, 'IxSQ' for IndexSQfp16 — ('' where the file ends before it), for any other file its own."""
     with open(path, "rb") as f:
-        return f.read(4).decode("ascii", errors="replace")
+        cc = f.read(4).decode("ascii", errors="replace")
+        if inner and cc == "IxMp":
+            head = f.read(_HDR_SIZE + 4 + 4)
+            try:
+                off = _read_header(head, 0)[3]
+            except struct.error:
+                return ""
+            return head[off:off + 4].decode("ascii", errors="replace")
+        return cc
+
+
+# ---------------------------------------------------------------------------------------------- 'IxMp' around 'IxSQ': binary16 rows
+def write_idmap_sq16_ip(path, halves: np.ndarray, ids: np.ndarray) -> None:
+    """halves [n,d] float16 (IEEE binary16), ids [n] int64: IndexIDMap around IndexScalarQuantizer(d, QT_fp16, inner product)."""
+    halves = np.ascontiguousarray(halves, dtype="<f2")
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    n, d = halves.shape
+    assert ids.shape == (n,)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IxMp")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<I", _fourcc("IxSQ")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<iifQQ", QT_FP16, 0, 0.0, d, 2 * d))      # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
+        f.write(struct.pack("<Q", 0))                            # trained: empty
+        f.write(struct.pack("<Q", n * 2 * d))                    # codes
+        halves.tofile(f)
+        f.write(struct.pack("<Q", n))
+        ids.tofile(f)
+
+
+def _sq16_flat_head(p):
+    """(d, n, byte offset of the rows, id map present?) of an 'IxMp'-around-'IxSQ' or bare 'IxSQ' file; RuntimeError naming the
+    file for anything else, a record other than QT_fp16 / code_size 2d, or a file shorter than its header promises."""
+    size = p.stat().st_size
+    with open(p, "rb") as f:
+        head = f.read(4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8)
+    try:
+        (cc,) = struct.unpack_from("<I", head, 0)
+        off, idmap = 4, cc == _fourcc("IxMp")
+        d0 = n0 = None
+        if idmap:
+            d0, n0, _, off = _read_header(head, off)
+            (cc,) = struct.unpack_from("<I", head, off)
+            off += 4
+        if cc != _fourcc("IxSQ"):
+            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexScalarQuantizer (IndexSQfp16: 'IxSQ', bare or inside 'IxMp')")
+        d, n, _, off = _read_header(head, off)
+        qtype, rangestat, rangestat_arg, dsq, code_size, ntrained = struct.unpack_from("<iifQQQ", head, off)
+        off += 36
+        (nbytes,) = struct.unpack_from("<Q", head, off)
+        off += 8
+    except struct.error as e:
+        raise RuntimeError(f"{p}: the head of an IndexSQfp16 file is cut short ({e})") from None
+    if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
+        raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, code_size={code_size}, "
+                           f"{ntrained} trained values): qtype 4 (QT_fp16) with code_size 2 d and no trained value is what is read")
+    if n < 0 or nbytes != n * 2 * d:
+        raise RuntimeError(f"{p}: {nbytes} code bytes for {n} x {d} binary16 values")
+    need = off + nbytes + ((8 + 8 * n) if idmap else 0)
+    if size < need:
+        raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {need} promised by its header)")
+    return int(d), int(n), int(off), idmap
+
+
+def _sq16_flat_ids(p, d, n, off, idmap, lo, hi):
+    if not idmap:
+        return np.arange(lo, hi, dtype=np.int64)
+    with open(p, "rb") as f:
+        f.seek(off + n * 2 * d)
+        (nid,) = struct.unpack("<Q", f.read(8))
+        if nid != n:
+            raise RuntimeError(f"{p}: id_map has {nid} entries for {n} rows")
+        f.seek(8 * lo, 1)
+        ids = np.fromfile(f, dtype=np.int64, count=hi - lo)
+    if ids.size != hi - lo:
+        raise RuntimeError(f"{p}: the id_map is cut short ({ids.size} of {hi - lo} ids)")
+    return ids
+
+
+def read_idmap_sq16_ip(path, mmap: bool = True):
+    """-> (halves [n,d] float16 (a memmap view unless mmap is False), ids int64[n]) of an IndexSQfp16 file; a bare 'IxSQ' file
+    (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated or foreign file."""
+    p = _existing(path)
+    d, n, off, idmap = _sq16_flat_head(p)
+    H = np.memmap(p, dtype="<f2", mode="r", offset=off, shape=(n, d)) if mmap and n else \
+        np.fromfile(p, dtype="<f2", count=n * d, offset=off).reshape(n, d)
+    return H, _sq16_flat_ids(p, d, n, off, idmap, 0, n)
+
+
+def read_idmap_sq16_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of what read_idmap_sq16_ip returns, reading only those rows and ids (one rank's shard_range of the file)."""
+    p = _existing(path)
+    d, n, off, idmap = _sq16_flat_head(p)
+    lo, hi = int(lo), int(hi)
+    if not (0 <= lo <= hi <= n):
+        raise ValueError(f"read_idmap_sq16_ip_range: [{lo}, {hi}) outside [0, {n}]")
+    H = np.fromfile(p, dtype="<f2", count=(hi - lo) * d, offset=off + lo * 2 * d).reshape(hi - lo, d)
+    return H, _sq16_flat_ids(p, d, n, off, idmap, lo, hi)
+
+
+def idmap_sq16_ip_ntotal(path) -> int:
+    """Rows of an IndexSQfp16 file (its header)."""
+    return _sq16_flat_head(_existing(path))[1]
+
+
+def _read_sq16_state(path):
+    H, ids = read_idmap_sq16_ip(path, mmap=False)
+    return {"halves": H, "ids": ids}
+
+
+def _read_sq16_state_range(path, lo, hi):
+    H, ids = read_idmap_sq16_ip_range(path, lo, hi)
+    return {"halves": H, "ids": ids}
 
 
 # ---------------------------------------------------------------------------------------------- any IVF file, by its fourcc
@@ -724,14 +853,18 @@ _BY_FOURCC = {                                    # fourcc -> (reader, range rea
     "WiPR": (read_ivf_pq_refine_ip, read_ivf_pq_refine_ip_range, ivf_pq_refine_ip_ntotal),
     "WiOP": (read_ivf_opq_ip, read_ivf_opq_ip_range, ivf_opq_ip_ntotal),
     "IwSq": (read_ivf_sq_ip, read_ivf_sq_ip_range, ivf_sq_ip_ntotal),
+    "IxSQ": (_read_sq16_state, _read_sq16_state_range, idmap_sq16_ip_ntotal),      # IndexSQfp16: no lists, dict(halves, ids)
 }
 
 
 def _by_fourcc(path, which: int):
     p = _existing(path)
     cc = index_fourcc(p)
+    if cc == "IxMp" and index_fourcc(p, inner=True) == "IxSQ":
+        cc = "IxSQ"
     if cc not in _BY_FOURCC:
-        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(_BY_FOURCC)})")
+        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(k for k in _BY_FOURCC if k != 'IxSQ')}) "
+                           f"nor an IndexSQfp16 file ('IxSQ', bare or inside 'IxMp')")
     return _BY_FOURCC[cc][which]
 
 
@@ -753,8 +886,10 @@ def index_ntotal(path) -> int:
 
 def write_index(path, state, nprobe=None) -> None:
     """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
-    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl'.  nprobe:
-    state's own unless given."""
+    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl'; 'halves'
+    without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ').  nprobe: state's own unless given."""
+    if "halves" in state and "centroids" not in state:       # IndexSQfp16: rows and ids, no lists
+        return write_idmap_sq16_ip(path, state["halves"], state["ids"])
     nprobe = state.get("nprobe", 1) if nprobe is None else nprobe
     lists = (state["ids"], state["list_off"])
     store = {k: state[k] for k in ("kind", "k_factor", "rows", "scales") if k in state}

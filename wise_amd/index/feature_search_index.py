@@ -26,6 +26,15 @@ one entry of FAMILIES below: what it adds to IndexIVFFlat is its trained state, 
     IndexIVFSQ8                      IVFSQIPIndex            ranges [2d]: vmin, vdiff       d code bytes (QT_8bit)        'IwSq' (faiss)
     IndexIVFSQfp16                   IVFSQfp16IPIndex        -                              d binary16 values (QT_fp16)   'IwSq' (faiss), qtype 4
 
+and beside IndexFlatIP a second exhaustive type, which has no lists and is no entry of that table (FLAT_TYPES below):
+
+    IndexSQfp16                      FlatSQfp16IPIndex       -                              (no lists) d binary16 values  'IxMp' around 'IxSQ' (faiss), qtype 4
+                                     (flat_sq.py)                                           a row, 2 d bytes, no fp32 rows
+
+Wherever IndexFlatIP is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
+ShardedFlatIPIndex wrapper — IndexSQfp16 goes the same way; its file holds the rows rounded to binary16 (numpy's float32 ->
+float16 cast, which is what the GPU encoder of add_with_ids computes bit for bit).
+
 The bare names `IndexIVFPQ` / `IndexIVFOPQ` mean m = d / 4.  Everything below is written once and driven by that table.
 
 **One process** builds an IVF index by training on a seeded sample of min(N, 100 nlist) rows, adding every row, and writing
@@ -70,6 +79,7 @@ from ..feature.feature_extractor_factory import FeatureExtractorFactory
 from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
+from .flat_sq import FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
@@ -231,9 +241,19 @@ def _host_state(index, fam):
     return dict(zip(keys, index.lists_host()))
 
 
+FLAT_TYPES = ('IndexFlatIP', 'IndexSQfp16')       # the exhaustive types: no training, no lists, row-sharded across ranks
+
+
 def _unknown_index_type(index_type):
     return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
-                               f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16')
+                               f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16, '
+                               f'and IndexSQfp16')
+
+
+def _to_halves(X):
+    """[n,d] float16 of float32 rows: numpy's cast — round to nearest even, subnormals kept — the bits wise_sq16_encode gives"""
+    with np.errstate(over='ignore'):
+        return np.asarray(X, dtype=np.float32).astype(np.float16)
 
 
 def _sharded_ivf_on():
@@ -275,6 +295,7 @@ def _read_store(feature_store):
 class FeatureSearchIndex(SearchIndex):
     # the classes that hold a rank's rows in HBM; CPU tests of the multi-rank wiring put stand-ins here
     flat_index_factory = FlatIPIndex
+    flat_sqfp16_index_factory = FlatSQfp16IPIndex
     ivf_index_factory = IVFFlatIPIndex
     ivfpq_index_factory = IVFPQIPIndex
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
@@ -311,9 +332,9 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        fam = _family(index_type)                   # None: IndexFlatIP (or a name refused below)
+        fam = _family(index_type)                   # None: IndexFlatIP, IndexSQfp16 (or a name refused below)
         sharded_ivf = sharded and fam is not None and _sharded_ivf_on()
-        if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
+        if sharded and (index_type in FLAT_TYPES or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
         exists = index_fn.exists()
         if sharded_ivf:                             # the build is collective: every rank takes the same decision
@@ -325,20 +346,22 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        if index_type != 'IndexFlatIP' and fam is None:
+        if index_type not in FLAT_TYPES and fam is None:
             raise _unknown_index_type(index_type)
         self.index_type = index_type
         if sharded and fam is not None and not sharded_ivf and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
-        if sharded and (index_type == 'IndexFlatIP' or sharded_ivf):
+        if sharded and (index_type in FLAT_TYPES or sharded_ivf):
             feature_store.enable_read(shard_shuffle=False, shard_slice=(rank, world))   # this rank's shard files only
         else:
             feature_store.enable_read(shard_shuffle=False)
         feature_dim = feature_store.feature_dim
         if fam is not None:                         # a bad shape is refused before any row is read
             pq_m, kind = fam.parse(index_type, feature_dim)
+        elif index_type == 'IndexSQfp16':
+            check_sqfp16_flat_shape(feature_dim)
 
         print('Adding feature vectors to index')
         X, ids = _read_store(feature_store)
@@ -355,6 +378,8 @@ class FeatureSearchIndex(SearchIndex):
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
             faiss_io.write_index(index_fn, _host_state(ivf, fam), nprobe=ivf.nprobe)
+        elif index_type == 'IndexSQfp16':
+            faiss_io.write_idmap_sq16_ip(index_fn, _to_halves(X), ids)
         else:
             faiss_io.write_idmap_flat_ip(index_fn, X, ids)
         print(f'  saved index to {index_fn}')
@@ -512,10 +537,20 @@ class FeatureSearchIndex(SearchIndex):
 
     def _index_from_file(self, fn, shard=None):
         """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
-        Anything that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
-        shard = (rank, world): only rows shard_range(N, rank, world) of a flat file."""
+        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16;
+        anything else that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
+        shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
         if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
             return self._local_index(faiss_io.read_index(fn))[1]
+        if fn.exists() and faiss_io.index_fourcc(fn, inner=True) == 'IxSQ':
+            H, ids = faiss_io.read_idmap_sq16_ip(fn)                     # rows memory-mapped: only [lo, hi) is ever touched
+            lo, hi = shard_range(H.shape[0], *shard) if shard is not None else (0, H.shape[0])
+            index = self.flat_sqfp16_index_factory(H.shape[1])
+            index.reserve(hi - lo)
+            for s in range(lo, hi, 1 << 20):             # the halves go to HBM as they are: nothing is converted
+                e = min(s + (1 << 20), hi)
+                index.add_halves_with_ids(np.ascontiguousarray(H[s:e]), ids[s:e])
+            return index
         X, ids = faiss_io.read_idmap_flat_ip(fn)                     # rows memory-mapped: only [lo, hi) is ever touched
         lo, hi = shard_range(X.shape[0], *shard) if shard is not None else (0, X.shape[0])
         index = self.flat_index_factory(X.shape[1])
@@ -531,6 +566,8 @@ class FeatureSearchIndex(SearchIndex):
         if isinstance(index, FlatIPIndex):
             index._finalize()
             faiss_io.write_idmap_flat_ip(fn, index._X.cpu().numpy(), index._ids.cpu().numpy())
+        elif hasattr(index, 'rows_host'):                # IndexSQfp16: (halves, ids)
+            faiss_io.write_idmap_sq16_ip(fn, *index.rows_host())
         elif hasattr(index, 'state_host'):
             faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
         else:
@@ -544,7 +581,7 @@ class FeatureSearchIndex(SearchIndex):
         temporary name beside it and renamed over it.  Returns (n_added, n_removed); with nothing to do the file is left
         alone.  The feature extractor is not built.  A `self.index` loaded from that file before the call is stale
         afterwards: call load_index again.  Lists are not rebalanced and nothing is retrained, however many updates pile up."""
-        if index_type != 'IndexFlatIP' and _family(index_type) is None:
+        if index_type not in FLAT_TYPES and _family(index_type) is None:
             raise _unknown_index_type(index_type)
         if _dist_rank_world()[2]:
             raise NotImplementedError('update_index under a sharded process group is not built (a collective removal is not): '
