@@ -32,10 +32,10 @@ def cosine(a, b):
                                     (32768, 256, 192),
                                     # HTSAT shapes: N edge (N % 128 != 0) and K % 64 != 0
                                     (256, 288, 96), (128, 96, 384), (384, 192, 96), (256, 576, 192), (128, 36, 32)])
-@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4, 5, 6])
 def test_gemm_modes(M, N, K, mode):
-    if M > 2000 and mode not in (0, 3) and (M, N, K) != (8192, 1536, 384):
-        pytest.skip("large shapes: bf16-out and residual modes only")
+    if M > 2000 and mode not in (0, 3, 5, 6) and (M, N, K) != (8192, 1536, 384):
+        pytest.skip("large shapes: bf16-out, residual, tanh-GELU and ReLU modes only")
     lib = _lib.lib()
     g = torch.Generator().manual_seed(M + N + K + mode)
     A = bf16_round(torch.randn(M, K, generator=g))
@@ -55,6 +55,10 @@ def test_gemm_modes(M, N, K, mode):
             ref = ref * torch.sigmoid(1.702 * ref)
         elif mode == 2:
             ref = 0.5 * ref * (1 + torch.erf(ref / 2 ** 0.5))
+        elif mode == 5:
+            ref = 0.5 * ref * (1 + torch.tanh(0.7978845608028654 * (ref + 0.044715 * ref ** 3)))
+        elif mode == 6:
+            ref = ref.clamp(min=0)
     _lib.check(lib.wise_gemm_bf16(Ad.data_ptr(), Wd.data_ptr(), bd.data_ptr(), M, N, K, mode, out.data_ptr(),
                                   _lib.stream_ptr()), "gemm")
     torch.cuda.synchronize()

@@ -2242,6 +2242,8 @@ extern "C" int wise_debug_set_gemm_variant(int v) {
 //   kind 0, gemm_plan:  a = M, N, K, mode, m_valid (0: gemm_bf16), overlapped, cus -> splitk, n, v0, rows0, v1, rows1
 //   kind 1, fold_plan:  a = M, N, K, mode, producer, wide96, cus                     -> variant
 //   kind 2, conv_plan:  a = B, T, F, Cin, Cout, pool                                 -> ConvTile
+//   kind 3, gemm_plan under wise_debug_set_gemm_variant(force) (force = 0: the plan's own choice, as kind 0 with
+//           m_valid = 0):  a = force, M, N, K, mode, cus                             -> as kind 0
 extern "C" int wise_debug_gemm_plan(int kind, const int* a, int* out) {
     if (kind == 0) {
         const wise::GemmPlan p = wise::gemm_plan(a[0], a[1], a[2], a[3], a[4], a[5] != 0, a[6]);
@@ -2252,6 +2254,12 @@ extern "C" int wise_debug_gemm_plan(int kind, const int* a, int* out) {
     if (kind == 1) {
         out[0] = wise::fold_plan(a[0], a[1], a[2], a[3], a[4] != 0, a[5] != 0, a[6]);
         return 1;
+    }
+    if (kind == 3) {
+        const wise::GemmPlan p = wise::gemm_plan(a[1], a[2], a[3], a[4], 0, false, a[5], a[0] & 0xFF);
+        const int r[6] = {p.splitk, p.n, p.v[0], p.rows[0], p.v[1], p.rows[1]};
+        for (int i = 0; i < 6; ++i) out[i] = r[i];
+        return 6;
     }
     if (kind == 2) {
         out[0] = wise::conv_plan(wise::conv_rows(a[0], a[1], a[2], a[5] != 0), a[4]);
