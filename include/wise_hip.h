@@ -906,7 +906,9 @@ int wise_attention_bf16(const uint16_t* qkv, int B, int T, int H, uint16_t* o, v
 /* the same at head dim dh = 64 or 80 (ViT-H/14: width 1280 over 16 heads): qkv [B*T, 3*H*dh], softmax(QK^T/sqrt(dh))V */
 int wise_attention_dh_bf16(const uint16_t* qkv, int B, int T, int H, int dh, uint16_t* o, void* stream);
 /* head dim 64, right-padded sequences: sequence b has lens[b] (device int32 [B], 1..T) keys; keys past it are masked for
- * every query of that sequence (the BERT-family text towers, wise_xlmr_forward) */
+ * every query of that sequence (the BERT-family text towers, wise_xlmr_forward).  lens[b] outside 1..T is clamped into it:
+ * 0 (or less) counts as one key, more than T as T.  Every query row is written, rows past lens[b] included: they attend
+ * the same lens[b] keys (tests/test_gpu_attention_exact.py pins both). */
 int wise_attention_lens_bf16(const uint16_t* qkv, int B, int T, int H, const int32_t* lens, uint16_t* o, void* stream);
 /* head dim 64 with the causal mask of the text tower: query t attends keys <= t */
 int wise_attention_causal_bf16(const uint16_t* qkv, int B, int T, int H, uint16_t* o, void* stream);

@@ -4,6 +4,7 @@ torch restatement of the shifted-window attention (roll, window partition, relat
 import pytest
 import torch
 
+from tests.swin_window_ref import window_attention
 from tests.test_gpu_vit import bf16_round
 from wise_amd import _lib
 from wise_amd.feature.htsat import swin_qkv_stream
@@ -12,33 +13,12 @@ pytestmark = pytest.mark.gpu
 
 
 def _reference(x, lnw, lnb, w, bq, relb, B, H, C, shift):
-    heads = C // 24
     xd = x.double().reshape(B, H, H, C)
     hn = (xd - xd.mean(-1, keepdim=True)) / torch.sqrt(xd.var(-1, unbiased=False, keepdim=True) + 1e-5) * lnw.double() + lnb.double()
     hn = bf16_round(hn.float()).double()
     qkv = bf16_round((hn @ w.double().t() + bq.double()).float()).double()             # [B,H,H,3C] (the GEMM's bf16 output)
-    if shift:
-        qkv = torch.roll(qkv, shifts=(-shift, -shift), dims=(1, 2))
-    nw = H // 8
-    win = qkv.reshape(B, nw, 8, nw, 8, 3, heads, 24).permute(0, 1, 3, 5, 6, 2, 4, 7).reshape(B * nw * nw, 3, heads, 64, 24)
-    q, k, v = win[:, 0], win[:, 1], win[:, 2]
-    att = q @ k.transpose(-1, -2) * 24 ** -0.5 + relb.double()[None]
-    if shift:
-        img = torch.zeros(H, H)
-        cnt = 0
-        for hs in (slice(0, -8), slice(-8, -shift), slice(-shift, None)):
-            for wsl in (slice(0, -8), slice(-8, -shift), slice(-shift, None)):
-                img[hs, wsl] = cnt
-                cnt += 1
-        mw = img.reshape(nw, 8, nw, 8).permute(0, 2, 1, 3).reshape(nw * nw, 64)
-        mask = (mw[:, None, :] != mw[:, :, None]).double() * -100.0                         # [nwin, 64, 64]
-        att = att.reshape(B, nw * nw, heads, 64, 64) + mask[None, :, None]
-        att = att.reshape(B * nw * nw, heads, 64, 64)
-    o = torch.softmax(att, dim=-1) @ v                                                      # [Bw, heads, 64, 24]
-    o = o.reshape(B, nw, nw, heads, 8, 8, 24).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, H, H, C)
-    if shift:
-        o = torch.roll(o, shifts=(shift, shift), dims=(1, 2))
-    return o.reshape(B * H * H, C)
+    # the roll, the window partition, the bias, the region mask and the softmax: tests/swin_window_ref.py (shared with the exact suite)
+    return torch.from_numpy(window_attention(qkv.reshape(B * H * H, 3 * C).numpy(), relb.double().numpy(), B, H, C, shift))
 
 
 @pytest.mark.parametrize("B,H,C,shift", [(2, 16, 384, 0), (2, 16, 384, 4), (1, 32, 192, 0), (2, 32, 192, 4), (128, 16, 384, 4), (64, 32, 192, 4), (3, 16, 192, 4), (2, 8, 192, 0), (6, 8, 192, 4)])

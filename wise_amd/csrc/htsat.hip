@@ -1096,6 +1096,20 @@ extern "C" int wise_debug_set_htsat(int flags) {
     wise::htsat::frontend_set_variant((flags >> 5) & 1);   // bit 5: the full-length FFT front end
     return 0;
 }
+// the window attention alone, launched as htsat_forward_impl launches it (tests/test_gpu_attention_exact.py): qkv [B*H*H, 3C] bf16
+// in original token order, relb [C/24][64][64] fp32, o [B*H*H, C] bf16; C = 96 / 192 / 384 on an H x H grid of 8 x 8 windows
+extern "C" int wise_debug_swin_attention(const uint16_t* qkv, int B, int H, int C, int shift, const float* relb, uint16_t* o,
+                                         void* stream) {
+    WISE_CHECK_ARG(qkv && relb && o && B > 0, "debug_swin_attention: bad argument");
+    WISE_CHECK_ARG(H >= 8 && H % 8 == 0 && C > 0 && C % 24 == 0 && (shift == 0 || shift == 4),
+                   "debug_swin_attention: H=%d C=%d shift=%d", H, C, shift);
+    const int heads = C / 24;
+    hipStream_t st = (hipStream_t)stream;
+    const long long items = (long long)B * (H / 8) * (H / 8) * heads;
+    hipLaunchKernelGGL(swin_attention_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, qkv, B, H, H, C, heads, shift, relb, o);
+    WISE_LAUNCH_CHECK("htsat swin_attention_kernel");
+    return WISE_OK;
+}
 #endif
 
 extern "C" int wise_htsat_tap(int what, const void* workspace_ptr, int batch, int samples, float* dst, int64_t count,
