@@ -120,10 +120,10 @@ def test_reserved_rows_are_filled_in_place():
     one.add_with_ids(X, ids)
     res = FlatIPIndex(d)
     res.reserve(N)
-    base = res._rX.data_ptr()
+    base = res._store.reserved.data_ptr()
     for s0 in range(0, N, 1024):
         res.add_with_ids(X[s0:s0 + 1024], ids[s0:s0 + 1024])
-    assert res.ntotal == N and not res._chunks and res._X.data_ptr() == base
+    assert res.ntotal == N and not res._store.chunks and res._X.data_ptr() == base
     Da, Ia = one.search(Q, k)
     Db, Ib = res.search(Q, k)
     assert np.array_equal(Ia, Ib) and np.array_equal(Da, Db)

@@ -207,10 +207,10 @@ def test_flat_reserved_capacity_and_implicit_ids():
     a = FlatIPIndex(D)
     a.reserve(N)
     a.add_with_ids(X, ids)
-    store = a._rX.data_ptr()
+    store = a._store.reserved.data_ptr()
     gone = np.isin(ids, ids[100:900])
     assert a.remove_ids(ids[100:900], scratch_bytes=SMALL_SCRATCH) == 800
-    assert a._rX.data_ptr() == store and a._rX.shape[0] == N and a._X.data_ptr() == store      # the capacity stays
+    assert a._store.reserved.data_ptr() == store and a._store.reserved.shape[0] == N and a._X.data_ptr() == store      # the capacity stays
     a.add_with_ids(X[100:500], ids[100:500])                                                 # ... and is filled from the new end
     assert a._X.data_ptr() == store and a.ntotal == N - 400
     order = np.concatenate([np.flatnonzero(~gone), np.arange(100, 500)])

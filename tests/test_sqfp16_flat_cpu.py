@@ -174,6 +174,43 @@ def test_corrupt_files_are_refused_by_name(tmp_path):
         faiss_io.read_idmap_flat_ip(good)
 
 
+def test_the_fp32_flat_reader_shares_the_head_checks(tmp_path):
+    """One parser reads the head of either flat file, so the fp32 reader refuses a file cut short by name as well, and reads a
+    bare 'IxFI' record with ids equal to positions."""
+    n, d = 6, 8
+    X, ids = np.random.default_rng(6).standard_normal((n, d)).astype(np.float32), np.arange(n, dtype=np.int64) * 3 + 1
+    good = tmp_path / "flat.faiss"
+    faiss_io.write_idmap_flat_ip(good, X, ids)
+    raw = good.read_bytes()
+    for mmap in (True, False):
+        X2, ids2 = faiss_io.read_idmap_flat_ip(good, mmap=mmap)
+        assert X2.dtype == np.float32 and X2.tobytes() == X.tobytes() and np.array_equal(ids2, ids) and isinstance(X2, np.memmap) == mmap
+    for cut in (2, 8 * n, 8 * n + 8, 8 * n + 8 + 5, len(raw) - 50, len(raw) - 10):
+        fn = tmp_path / f"short_{cut}.faiss"
+        fn.write_bytes(raw[:len(raw) - cut])
+        with pytest.raises(RuntimeError, match=re.escape(str(fn))):
+            faiss_io.read_idmap_flat_ip(fn)
+    fn = tmp_path / "bad_count.faiss"
+    fn.write_bytes(raw[:4 + 33 + 4 + 33] + struct.pack("<Q", n * d - 1) + raw[4 + 33 + 4 + 33 + 8:])
+    with pytest.raises(RuntimeError, match="inconsistent flat payload"):
+        faiss_io.read_idmap_flat_ip(fn)
+    bare = tmp_path / "bare.faiss"
+    bare.write_bytes(raw[4 + 33:len(raw) - 8 - 8 * n])                   # the 'IxFI' record alone
+    Xb, idb = faiss_io.read_idmap_flat_ip(bare)
+    assert Xb.tobytes() == X.tobytes() and np.array_equal(idb, np.arange(n))
+    assert faiss_io.index_fourcc(bare, inner=True) == "IxFI" and faiss_io.index_fourcc(good, inner=True) == "IxFI"
+    assert faiss_io.index_fourcc(good) == "IxMp"
+    short = tmp_path / "head.faiss"
+    short.write_bytes(raw[:4 + 20])                                      # ends inside the id map's header: no inner fourcc
+    assert faiss_io.index_fourcc(short, inner=True) == "" and faiss_io.index_fourcc(short) == "IxMp"
+    with pytest.raises(RuntimeError, match="is not IndexScalarQuantizer"):
+        faiss_io.read_idmap_sq16_ip(good)
+    other = tmp_path / "ivf.faiss"
+    other.write_bytes(b"IwFl" + raw[4:])
+    with pytest.raises(RuntimeError, match="not IndexIDMap/IndexFlatIP"):
+        faiss_io.read_idmap_flat_ip(other)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # a numpy stand-in for FlatSQfp16IPIndex: what FeatureSearchIndex.flat_sqfp16_index_factory must offer
 def _selected(sel, ids):

@@ -89,7 +89,9 @@ the lists that overlap it.
 Every IVF record ends in the same inverted-list block, written and read by one piece of code (_write_lists, _read_lists,
 _read_lists_range) that the payload's row width and dtype parameterise.  read_index / read_index_range / index_ntotal pick the named
 reader by the file's fourcc and write_index the named writer by the state's keys; callers that do not care which family they hold
-(feature_search_index.py) use those four.
+(feature_search_index.py) use those four.  The two flat files share their head too — the optional id map's header, the inner
+fourcc and header, the ScalarQuantizer record of 'IxSQ', the payload's length — and one parser (_flat_head) and one id reader
+(_flat_ids) serve every reader of either.
 
 faiss is not in the container, so these layouts are UNPINNED against a real faiss binary; the round
 trip is pinned by tests/test_feature_store_index_io.py.  The rows are memory-mapped on read so a
@@ -99,6 +101,7 @@ from __future__ import annotations
 
 import struct
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -143,43 +146,103 @@ def _read_header(buf, off):
     return d, ntotal, metric, off
 
 
-def read_idmap_flat_ip(path, mmap: bool = True):
-    """-> (X [n,d] float32 (memmap view), ids int64[n]).  Raises RuntimeError like faiss on a missing file."""
-    p = Path(path)
-    if not p.exists():
-        raise RuntimeError(f"Error: 'f' failed: could not open {p} for reading: No such file or directory")
-    with open(p, "rb") as f:
-        head = f.read(4 + _HDR_SIZE + 4 + 4 + _HDR_SIZE + 4 + 8)
+class _FlatHead(NamedTuple):
+    """The head of a flat file, 'IxFI' or 'IxSQ', bare or inside 'IxMp' (_flat_head)."""
+    inner: str           # 'IxFI' (fp32 rows) or 'IxSQ' (binary16 rows, QT_fp16)
+    d: int
+    n: int
+    off: int             # byte offset of the payload
+    dtype: object        # of a payload value
+    idmap: bool          # an id map follows the payload (else ids are the positions)
+
+
+_FLAT_HEAD_BYTES = 4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8     # the most a flat head takes: both headers with a metric_arg
+_FLAT_NAMES = {"IxFI": "IndexFlatIP", "IxSQ": "IndexSQfp16"}
+
+
+def _flat_outer(head: bytes):
+    """(the fourcc the file opens with, the fourcc of the index — the one an 'IxMp' id map wraps, else the same —, the offset behind
+    it, d and n of the id map's header or None); struct.error where the bytes end before that."""
     (cc,) = struct.unpack_from("<I", head, 0)
-    if cc == _fourcc("IxFI"):  # a bare IndexFlatIP: ids are the positions
-        d, n, metric, off = _read_header(head, 4)
-        (cnt,) = struct.unpack_from("<Q", head, off)
-        off += 8
-        X = np.memmap(p, dtype=np.float32, mode="r", offset=off, shape=(n, d)) if mmap else \
-            np.fromfile(p, dtype=np.float32, count=n * d, offset=off).reshape(n, d)
-        return X, np.arange(n, dtype=np.int64)
     if cc != _fourcc("IxMp"):
-        raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIDMap/IndexFlatIP; only flat IP indexes are "
-                           f"supported by the MI355X search path")
-    d, n, metric, off = _read_header(head, 4)
-    (cc2,) = struct.unpack_from("<I", head, off)
-    if cc2 != _fourcc("IxFI"):
-        raise RuntimeError(f"{p}: IndexIDMap wraps index type 0x{cc2:08x}, expected IndexFlatIP")
-    d2, n2, metric2, off = _read_header(head, off + 4)
-    (cnt,) = struct.unpack_from("<Q", head, off)
-    off += 8
-    if cnt != n2 * d2 or d2 != d:
-        raise RuntimeError(f"{p}: inconsistent flat payload ({cnt} values for {n2} x {d2})")
-    X = np.memmap(p, dtype=np.float32, mode="r", offset=off, shape=(n2, d2)) if mmap else \
-        np.fromfile(p, dtype=np.float32, count=n2 * d2, offset=off).reshape(n2, d2)
-    off += cnt * 4
+        return cc, cc, 4, None, None
+    d0, n0, _, off = _read_header(head, 4)
+    (inner,) = struct.unpack_from("<I", head, off)
+    return cc, inner, off + 4, d0, n0
+
+
+def _flat_head(p, want: str) -> _FlatHead:
+    """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxSQ'), bare or inside 'IxMp'.  RuntimeError naming
+    the file for anything else, a ScalarQuantizer record other than QT_fp16 / code_size 2d, a payload length that is not n x d
+    values, or a file shorter than its header promises."""
+    size = p.stat().st_size
     with open(p, "rb") as f:
-        f.seek(off)
+        head = f.read(_FLAT_HEAD_BYTES)
+    try:
+        cc, inner, off, d0, n0 = _flat_outer(head)
+        idmap = cc == _fourcc("IxMp")
+        if inner != _fourcc(want):
+            if want == "IxSQ":
+                raise RuntimeError(f"{p}: index type 0x{inner:08x} is not IndexScalarQuantizer (IndexSQfp16: 'IxSQ', bare or inside 'IxMp')")
+            if idmap:
+                raise RuntimeError(f"{p}: IndexIDMap wraps index type 0x{inner:08x}, expected IndexFlatIP")
+            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIDMap/IndexFlatIP; only flat IP indexes are "
+                               f"supported by the MI355X search path")
+        d, n, _, off = _read_header(head, off)
+        if want == "IxSQ":
+            qtype, rangestat, rangestat_arg, dsq, code_size, ntrained = struct.unpack_from("<iifQQQ", head, off)
+            off += 36
+        (count,) = struct.unpack_from("<Q", head, off)
+        off += 8
+    except struct.error as e:
+        raise RuntimeError(f"{p}: the head of an {_FLAT_NAMES[want]} file is cut short ({e})") from None
+    if want == "IxSQ":
+        if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
+            raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, "
+                               f"code_size={code_size}, {ntrained} trained values): qtype 4 (QT_fp16) with code_size 2 d and no trained "
+                               f"value is what is read")
+        if n < 0 or count != n * 2 * d:
+            raise RuntimeError(f"{p}: {count} code bytes for {n} x {d} binary16 values")
+        dtype = np.dtype("<f2")
+    else:
+        if n < 0 or d < 1 or count != n * d or (idmap and d0 != d):
+            raise RuntimeError(f"{p}: inconsistent flat payload ({count} values for {n} x {d})")
+        dtype = np.dtype(np.float32)
+    need = off + n * d * dtype.itemsize + ((8 + 8 * n) if idmap else 0)
+    if size < need:
+        raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {need} promised by its header)")
+    return _FlatHead(want, int(d), int(n), int(off), dtype, idmap)
+
+
+def _flat_rows(p, head: _FlatHead, mmap: bool):
+    """[n,d] payload of a flat file: a memmap view unless mmap is False (or there is no row to map)"""
+    if mmap and head.n:
+        return np.memmap(p, dtype=head.dtype, mode="r", offset=head.off, shape=(head.n, head.d))
+    return np.fromfile(p, dtype=head.dtype, count=head.n * head.d, offset=head.off).reshape(head.n, head.d)
+
+
+def _flat_ids(p, head: _FlatHead, lo: int, hi: int):
+    """ids [lo, hi) of a flat file: the id map behind the payload, or the positions where the file has none"""
+    if not head.idmap:
+        return np.arange(lo, hi, dtype=np.int64)
+    with open(p, "rb") as f:
+        f.seek(head.off + head.n * head.d * head.dtype.itemsize)
         (nid,) = struct.unpack("<Q", f.read(8))
-        ids = np.fromfile(f, dtype=np.int64, count=nid)
-    if nid != n2:
-        raise RuntimeError(f"{p}: id_map has {nid} entries for {n2} rows")
-    return X, ids
+        if nid != head.n:
+            raise RuntimeError(f"{p}: id_map has {nid} entries for {head.n} rows")
+        f.seek(8 * lo, 1)
+        ids = np.fromfile(f, dtype=np.int64, count=hi - lo)
+    if ids.size != hi - lo:
+        raise RuntimeError(f"{p}: the id_map is cut short ({ids.size} of {hi - lo} ids)")
+    return ids
+
+
+def read_idmap_flat_ip(path, mmap: bool = True):
+    """-> (X [n,d] float32 (a memmap view unless mmap is False), ids int64[n]); a bare 'IxFI' file (no id map) gives ids = positions.
+    Raises RuntimeError like faiss on a missing file, and naming the file for a truncated or foreign one."""
+    p = _existing(path)
+    head = _flat_head(p, "IxFI")
+    return _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
 
 
 _IVF_RECORDS = {"IwFl": "IndexIVFFlat", "IwPQ": "IndexIVFPQ", "IwSq": "IndexIVFScalarQuantizer"}
@@ -730,15 +793,13 @@ def index_fourcc(path, inner: bool = False) -> str:
     """The fourcc the file opens with; inner: for an 'IxMp' (IndexIDMap) file the fourcc of the index it wraps — 'IxFI' for
     IndexFlatIP, 'IxSQ' for IndexSQfp16 — ('' where the file ends before it), for any other file its own."""
     with open(path, "rb") as f:
-        cc = f.read(4).decode("ascii", errors="replace")
-        if inner and cc == "IxMp":
-            head = f.read(_HDR_SIZE + 4 + 4)
-            try:
-                off = _read_header(head, 0)[3]
-            except struct.error:
-                return ""
-            return head[off:off + 4].decode("ascii", errors="replace")
-        return cc
+        head = f.read(_FLAT_HEAD_BYTES if inner else 4)
+    if not inner or head[:4] != b"IxMp":
+        return head[:4].decode("ascii", errors="replace")
+    try:
+        return struct.pack("<I", _flat_outer(head)[1]).decode("ascii", errors="replace")
+    except struct.error:
+        return ""
 
 
 # ---------------------------------------------------------------------------------------------- 'IxMp' around 'IxSQ': binary16 rows
@@ -761,79 +822,28 @@ def write_idmap_sq16_ip(path, halves: np.ndarray, ids: np.ndarray) -> None:
         ids.tofile(f)
 
 
-def _sq16_flat_head(p):
-    """(d, n, byte offset of the rows, id map present?) of an 'IxMp'-around-'IxSQ' or bare 'IxSQ' file; RuntimeError naming the
-    file for anything else, a record other than QT_fp16 / code_size 2d, or a file shorter than its header promises."""
-    size = p.stat().st_size
-    with open(p, "rb") as f:
-        head = f.read(4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8)
-    try:
-        (cc,) = struct.unpack_from("<I", head, 0)
-        off, idmap = 4, cc == _fourcc("IxMp")
-        d0 = n0 = None
-        if idmap:
-            d0, n0, _, off = _read_header(head, off)
-            (cc,) = struct.unpack_from("<I", head, off)
-            off += 4
-        if cc != _fourcc("IxSQ"):
-            raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexScalarQuantizer (IndexSQfp16: 'IxSQ', bare or inside 'IxMp')")
-        d, n, _, off = _read_header(head, off)
-        qtype, rangestat, rangestat_arg, dsq, code_size, ntrained = struct.unpack_from("<iifQQQ", head, off)
-        off += 36
-        (nbytes,) = struct.unpack_from("<Q", head, off)
-        off += 8
-    except struct.error as e:
-        raise RuntimeError(f"{p}: the head of an IndexSQfp16 file is cut short ({e})") from None
-    if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
-        raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, code_size={code_size}, "
-                           f"{ntrained} trained values): qtype 4 (QT_fp16) with code_size 2 d and no trained value is what is read")
-    if n < 0 or nbytes != n * 2 * d:
-        raise RuntimeError(f"{p}: {nbytes} code bytes for {n} x {d} binary16 values")
-    need = off + nbytes + ((8 + 8 * n) if idmap else 0)
-    if size < need:
-        raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {need} promised by its header)")
-    return int(d), int(n), int(off), idmap
-
-
-def _sq16_flat_ids(p, d, n, off, idmap, lo, hi):
-    if not idmap:
-        return np.arange(lo, hi, dtype=np.int64)
-    with open(p, "rb") as f:
-        f.seek(off + n * 2 * d)
-        (nid,) = struct.unpack("<Q", f.read(8))
-        if nid != n:
-            raise RuntimeError(f"{p}: id_map has {nid} entries for {n} rows")
-        f.seek(8 * lo, 1)
-        ids = np.fromfile(f, dtype=np.int64, count=hi - lo)
-    if ids.size != hi - lo:
-        raise RuntimeError(f"{p}: the id_map is cut short ({ids.size} of {hi - lo} ids)")
-    return ids
-
-
 def read_idmap_sq16_ip(path, mmap: bool = True):
     """-> (halves [n,d] float16 (a memmap view unless mmap is False), ids int64[n]) of an IndexSQfp16 file; a bare 'IxSQ' file
     (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated or foreign file."""
     p = _existing(path)
-    d, n, off, idmap = _sq16_flat_head(p)
-    H = np.memmap(p, dtype="<f2", mode="r", offset=off, shape=(n, d)) if mmap and n else \
-        np.fromfile(p, dtype="<f2", count=n * d, offset=off).reshape(n, d)
-    return H, _sq16_flat_ids(p, d, n, off, idmap, 0, n)
+    head = _flat_head(p, "IxSQ")
+    return _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
 
 
 def read_idmap_sq16_ip_range(path, lo: int, hi: int):
     """Rows [lo, hi) of what read_idmap_sq16_ip returns, reading only those rows and ids (one rank's shard_range of the file)."""
     p = _existing(path)
-    d, n, off, idmap = _sq16_flat_head(p)
+    head = _flat_head(p, "IxSQ")
     lo, hi = int(lo), int(hi)
-    if not (0 <= lo <= hi <= n):
-        raise ValueError(f"read_idmap_sq16_ip_range: [{lo}, {hi}) outside [0, {n}]")
-    H = np.fromfile(p, dtype="<f2", count=(hi - lo) * d, offset=off + lo * 2 * d).reshape(hi - lo, d)
-    return H, _sq16_flat_ids(p, d, n, off, idmap, lo, hi)
+    if not (0 <= lo <= hi <= head.n):
+        raise ValueError(f"read_idmap_sq16_ip_range: [{lo}, {hi}) outside [0, {head.n}]")
+    H = np.fromfile(p, dtype=head.dtype, count=(hi - lo) * head.d, offset=head.off + lo * 2 * head.d).reshape(hi - lo, head.d)
+    return H, _flat_ids(p, head, lo, hi)
 
 
 def idmap_sq16_ip_ntotal(path) -> int:
     """Rows of an IndexSQfp16 file (its header)."""
-    return _sq16_flat_head(_existing(path))[1]
+    return _flat_head(_existing(path), "IxSQ").n
 
 
 def _read_sq16_state(path):

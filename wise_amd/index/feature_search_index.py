@@ -26,12 +26,15 @@ one entry of FAMILIES below: what it adds to IndexIVFFlat is its trained state, 
     IndexIVFSQ8                      IVFSQIPIndex            ranges [2d]: vmin, vdiff       d code bytes (QT_8bit)        'IwSq' (faiss)
     IndexIVFSQfp16                   IVFSQfp16IPIndex        -                              d binary16 values (QT_fp16)   'IwSq' (faiss), qtype 4
 
-and beside IndexFlatIP a second exhaustive type, which has no lists and is no entry of that table (FLAT_TYPES below):
+and the exhaustive types, which have no lists and no training and are the entries of a table of their own (FLAT_TYPES below: the
+factory attribute, the shape check, the file's payload, its writer and reader, and the method that takes a file's rows):
 
-    IndexSQfp16                      FlatSQfp16IPIndex       -                              (no lists) d binary16 values  'IxMp' around 'IxSQ' (faiss), qtype 4
-                                     (flat_sq.py)                                           a row, 2 d bytes, no fp32 rows
+    index type                       class (flat_ip.py, flat_sq.py)              a row in HBM and in the file                            file record (faiss_io.py)
+    IndexFlatIP                      FlatIPIndex                                 the fp32 row                                            'IxMp' around 'IxFI' (faiss)
+    IndexSQfp16                      FlatSQfp16IPIndex                           d binary16 values, 2 d bytes, no fp32 rows              'IxMp' around 'IxSQ' (faiss), qtype 4
 
-Wherever IndexFlatIP is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
+Both classes are one row store and one shared surface (flat_common.py) around their own payload and search.  Wherever IndexFlatIP
+is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
 ShardedFlatIPIndex wrapper — IndexSQfp16 goes the same way; its file holds the rows rounded to binary16 (numpy's float32 ->
 float16 cast, which is what the GPU encoder of add_with_ids computes bit for bit).
 
@@ -241,9 +244,6 @@ def _host_state(index, fam):
     return dict(zip(keys, index.lists_host()))
 
 
-FLAT_TYPES = ('IndexFlatIP', 'IndexSQfp16')       # the exhaustive types: no training, no lists, row-sharded across ranks
-
-
 def _unknown_index_type(index_type):
     return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
                                f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16, '
@@ -254,6 +254,27 @@ def _to_halves(X):
     """[n,d] float16 of float32 rows: numpy's cast — round to nearest even, subnormals kept — the bits wise_sq16_encode gives"""
     with np.errstate(over='ignore'):
         return np.asarray(X, dtype=np.float32).astype(np.float16)
+
+
+@dataclass(frozen=True)
+class _FlatType:
+    """One exhaustive index type (module docstring): no training, no lists, row-sharded across ranks."""
+    factory: str         # the FeatureSearchIndex attribute that constructs the index a file's rows go to
+    check: Callable      # (feature_dim) -> ValueError for a shape the type does not take, before any row is read; None: none
+    fourcc: str          # of the index inside the file's id map (faiss_io.index_fourcc(fn, inner=True))
+    dtype: type          # of a value of the file's payload, which is the index's own rows_host()[0]
+    encode: Callable     # store rows [n,d] float32 -> that payload, on the host
+    writer: Callable     # (path, payload, ids) -> the file
+    reader: Callable     # path -> (payload [N,d], memory-mapped; ids [N])
+    add: str             # the index method that takes rows of the file's payload and their ids
+
+
+FLAT_TYPES = {
+    'IndexFlatIP': _FlatType('flat_index_factory', None, 'IxFI', np.float32, lambda X: X, faiss_io.write_idmap_flat_ip,
+                             faiss_io.read_idmap_flat_ip, 'add_with_ids'),
+    'IndexSQfp16': _FlatType('flat_sqfp16_index_factory', check_sqfp16_flat_shape, 'IxSQ', np.float16, _to_halves,
+                             faiss_io.write_idmap_sq16_ip, faiss_io.read_idmap_sq16_ip, 'add_halves_with_ids'),
+}
 
 
 def _sharded_ivf_on():
@@ -332,7 +353,8 @@ class FeatureSearchIndex(SearchIndex):
         self.index_dir.mkdir(parents=True, exist_ok=True)
         index_fn = self.get_index_filename(index_type)
         rank, world, sharded = _dist_rank_world()
-        fam = _family(index_type)                   # None: IndexFlatIP, IndexSQfp16 (or a name refused below)
+        fam = _family(index_type)                   # None: an exhaustive type (or a name refused below)
+        flat = FLAT_TYPES.get(index_type)
         sharded_ivf = sharded and fam is not None and _sharded_ivf_on()
         if sharded and (index_type in FLAT_TYPES or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
@@ -360,8 +382,8 @@ class FeatureSearchIndex(SearchIndex):
         feature_dim = feature_store.feature_dim
         if fam is not None:                         # a bad shape is refused before any row is read
             pq_m, kind = fam.parse(index_type, feature_dim)
-        elif index_type == 'IndexSQfp16':
-            check_sqfp16_flat_shape(feature_dim)
+        elif flat.check is not None:
+            flat.check(feature_dim)
 
         print('Adding feature vectors to index')
         X, ids = _read_store(feature_store)
@@ -378,10 +400,8 @@ class FeatureSearchIndex(SearchIndex):
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
             faiss_io.write_index(index_fn, _host_state(ivf, fam), nprobe=ivf.nprobe)
-        elif index_type == 'IndexSQfp16':
-            faiss_io.write_idmap_sq16_ip(index_fn, _to_halves(X), ids)
         else:
-            faiss_io.write_idmap_flat_ip(index_fn, X, ids)
+            flat.writer(index_fn, flat.encode(X), ids)
         print(f'  saved index to {index_fn}')
 
     def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type, fam, pq_m=None, kind=None):
@@ -542,36 +562,28 @@ class FeatureSearchIndex(SearchIndex):
         shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
         if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
             return self._local_index(faiss_io.read_index(fn))[1]
-        if fn.exists() and faiss_io.index_fourcc(fn, inner=True) == 'IxSQ':
-            H, ids = faiss_io.read_idmap_sq16_ip(fn)                     # rows memory-mapped: only [lo, hi) is ever touched
-            lo, hi = shard_range(H.shape[0], *shard) if shard is not None else (0, H.shape[0])
-            index = self.flat_sqfp16_index_factory(H.shape[1])
-            index.reserve(hi - lo)
-            for s in range(lo, hi, 1 << 20):             # the halves go to HBM as they are: nothing is converted
-                e = min(s + (1 << 20), hi)
-                index.add_halves_with_ids(np.ascontiguousarray(H[s:e]), ids[s:e])
-            return index
-        X, ids = faiss_io.read_idmap_flat_ip(fn)                     # rows memory-mapped: only [lo, hi) is ever touched
-        lo, hi = shard_range(X.shape[0], *shard) if shard is not None else (0, X.shape[0])
-        index = self.flat_index_factory(X.shape[1])
+        inner = faiss_io.index_fourcc(fn, inner=True) if fn.exists() else None
+        flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner), FLAT_TYPES['IndexFlatIP'])
+        rows, ids = flat.reader(fn)                  # rows memory-mapped: only [lo, hi) is ever touched
+        lo, hi = shard_range(rows.shape[0], *shard) if shard is not None else (0, rows.shape[0])
+        index = getattr(self, flat.factory)(rows.shape[1])
         index.reserve(hi - lo)                       # one [n,d] device tensor, filled slice by slice
+        add = getattr(index, flat.add)               # binary16 rows go to HBM as they are: nothing is converted
         for s in range(lo, hi, 1 << 20):             # stream the memory-mapped rows into HBM
             e = min(s + (1 << 20), hi)
-            index.add_with_ids(np.ascontiguousarray(X[s:e]), ids[s:e])
+            add(np.ascontiguousarray(rows[s:e]), ids[s:e])
         return index
 
     @staticmethod
     def _write_index_file(index, fn):
         """index object -> file (the inverse of _index_from_file)."""
-        if isinstance(index, FlatIPIndex):
-            index._finalize()
-            faiss_io.write_idmap_flat_ip(fn, index._X.cpu().numpy(), index._ids.cpu().numpy())
-        elif hasattr(index, 'rows_host'):                # IndexSQfp16: (halves, ids)
-            faiss_io.write_idmap_sq16_ip(fn, *index.rows_host())
-        elif hasattr(index, 'state_host'):
-            faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
-        else:
+        if hasattr(index, 'state_host'):                 # an inverted-file index
+            return faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
+        payload, ids = index.rows_host()                 # an exhaustive one: its payload's dtype names the type
+        flat = next((t for t in FLAT_TYPES.values() if t.dtype == payload.dtype), None)
+        if flat is None:
             raise TypeError(f'{type(index).__name__}: no index file format')
+        flat.writer(fn, payload, ids)
 
     def update_index(self, index_type):
         """Not in the reference: bring the EXISTING index file of `index_type` in line with the feature store without

@@ -1,0 +1,273 @@
+"""What the exhaustive indexes (flat_ip.py, flat_sq.py) are made of: one row store and the faiss-shaped surface around it.
+
+  RowStore        ONE [N, d] payload tensor of one dtype (fp32 rows, binary16 rows) and its ids: the tensors reserved up front and
+                  their fill mark, the chunks added since the last merge, rows adopted as they are, the implicit ids
+                  (id_base + row) of adopted rows, and the compaction of a removal.  Pure torch: it works on the host too.
+  FlatIndexBase   everything that does not depend on the payload: ntotal, reserve, adopt, remove_ids, the argument handling of
+                  add_with_ids, the numpy search / range_search, range_search_device and reconstruct_batch over the entry points
+                  a subclass names, rows_host, and the grow-only workspaces.
+
+A subclass keeps the constructor's shape check, how rows enter their slot (`_fill`: a copy, or the binary16 encoder),
+`search_device` with its dispatch rules, and whatever it derives from the rows — which it drops in `_rows_changed`.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+from . import mutate as _mutate
+from . import range_search as _range
+from .selector import resolve_for, unpack_params
+
+
+class RowStore:
+    def __init__(self, d: int, dtype: torch.dtype, device="cuda", what: Optional[str] = None):
+        """what: how adopt's ValueError describes the rows it takes"""
+        self.d, self.dtype, self.device = int(d), dtype, torch.device(device)
+        self.what = what or f"rows must be contiguous {dtype} [N,{self.d}] on the store's device"
+        self.rows: Optional[torch.Tensor] = None     # [n,d] of the merged rows; None before the first merge of an empty store
+        self.ids: Optional[torch.Tensor] = None      # [n] int64, None => id_base + row (adopt only)
+        self.id_base = 0
+        self.n = 0                                   # merged rows and chunks
+        self.chunks: List[torch.Tensor] = []
+        self.id_chunks: List[torch.Tensor] = []
+        self.reserved: Optional[torch.Tensor] = None      # reserve(): the tensors slot() hands out slice by slice
+        self.reserved_ids: Optional[torch.Tensor] = None
+        self.fill = 0
+
+    @property
+    def has_ids(self) -> bool:
+        """explicit ids are held (8 bytes a row): always, except over rows adopted without any"""
+        return self.ids is not None or bool(self.id_chunks)
+
+    def reserve(self, n: int) -> None:
+        """Room for n rows up front: slot() then hands out slices of ONE [n,d] tensor instead of queueing chunks that the merge
+        would have to duplicate (an index larger than ~40 % of HBM could not be loaded through chunks; load_index knows the row
+        count from the file header)."""
+        if self.n or self.chunks:
+            raise ValueError("reserve: the index already holds rows")
+        self.reserved = torch.empty(int(n), self.d, dtype=self.dtype, device=self.device)
+        self.reserved_ids = torch.empty(int(n), dtype=torch.int64, device=self.device)
+        self.fill = 0
+
+    def slot(self, n: int, ids, what: str = "add_with_ids") -> torch.Tensor:
+        """The [n,d] destination of n new rows, which the caller fills: their slice of the reserved tensor where they fit, else a
+        fresh chunk (and the reservation is given up: chunks from here on).  ids [n] int64 go in with them."""
+        ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64))
+        if ids.shape != (n,):
+            raise ValueError(f"{what}: ids must have one entry per row")
+        if self.reserved is not None and self.fill + n <= self.reserved.shape[0]:
+            a, b = self.fill, self.fill + n
+            self.reserved_ids[a:b].copy_(ids)
+            self.rows, self.ids = self.reserved[:b], self.reserved_ids[:b]
+            self.fill = self.n = b
+            return self.reserved[a:b]
+        self.reserved = self.reserved_ids = None
+        dst = torch.empty(n, self.d, dtype=self.dtype, device=self.device)
+        self.chunks.append(dst)
+        self.id_chunks.append(ids.to(self.device, torch.int64))
+        self.n += n
+        return dst
+
+    def adopt(self, rows: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: int = 0) -> None:
+        """Take ownership of rows already resident on the device (no copy).  ids None => id = id_base + row.  Whatever the store
+        held — chunks, a reservation — is gone."""
+        if (rows.dtype != self.dtype or rows.dim() != 2 or rows.shape[1] != self.d or not rows.is_contiguous() or
+                rows.device.type != self.device.type):
+            raise ValueError(f"adopt: {self.what}")
+        if ids is not None and (ids.dtype != torch.int64 or ids.shape != (rows.shape[0],)):
+            raise ValueError("adopt: ids must be int64 [N]")
+        self.chunks, self.id_chunks = [], []
+        self.reserved = self.reserved_ids = None
+        self.rows, self.ids, self.id_base, self.n = rows, ids, int(id_base), rows.shape[0]
+
+    def finalize(self) -> None:
+        """Merge the chunks behind the rows held so far (implicit ids become explicit once rows with ids follow them); an empty
+        store gets empty tensors."""
+        if self.chunks:
+            held = self.rows is not None
+            self.ids = torch.cat(([self.explicit_ids()] if held else []) + self.id_chunks, dim=0).contiguous()
+            self.rows = torch.cat(([self.rows] if held else []) + self.chunks, dim=0).contiguous()
+            self.chunks, self.id_chunks = [], []
+            self.reserved = self.reserved_ids = None
+        if self.rows is None:
+            self.rows = torch.empty(0, self.d, dtype=self.dtype, device=self.device)
+            self.ids = torch.empty(0, dtype=torch.int64, device=self.device)
+
+    def explicit_ids(self) -> torch.Tensor:
+        """[rows] int64 ids of the merged rows, the implicit ones written out"""
+        if self.ids is not None:
+            return self.ids
+        return torch.arange(self.rows.shape[0], device=self.device, dtype=torch.int64) + self.id_base
+
+    def compact(self, c: "_mutate.RowCompaction") -> None:
+        """One removal over the merged rows and their (explicit) ids, in place: reserved tensors keep their capacity and are filled
+        from the new end."""
+        self.rows, self.ids = c.rows(self.rows), c.rows(self.ids)
+        self.n = c.kept
+        if self.reserved is not None:
+            self.fill = c.kept
+
+
+class FlatIndexBase:
+    REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
+    # entry points of the subclass's payload: (workspace bytes, count pass, fill pass) of range_search, and reconstruct_batch's
+    _RANGE: Tuple[str, str, str]
+    _RECONSTRUCT: str
+
+    def __init__(self, d: int, device, dtype: torch.dtype, what: str):
+        self.d = int(d)
+        self.device = torch.device(device)
+        self._store = RowStore(self.d, dtype, self.device, what)
+        self._ws: Optional[torch.Tensor] = None
+        self.is_trained = True
+
+    # -- the store, under the names the search paths use ---------------------------------------------
+    @property
+    def ntotal(self) -> int:
+        return self._store.n
+
+    _n = ntotal
+
+    @property
+    def _ids(self) -> Optional[torch.Tensor]:
+        """[N] int64 on device, None => id_base + row"""
+        return self._store.ids
+
+    @property
+    def id_base(self) -> int:
+        return self._store.id_base
+
+    # -- construction ---------------------------------------------------------------------------
+    def reserve(self, n: int) -> None:
+        """Room for n rows in HBM up front (RowStore.reserve): later adds fill their slice of ONE [n,d] tensor."""
+        self._store.reserve(n)
+
+    def _slot(self, n: int, ids, what: str) -> torch.Tensor:
+        dst = self._store.slot(n, ids, what)
+        self._rows_changed()
+        return dst
+
+    def add_with_ids(self, x, ids) -> None:
+        """x [n,d] float32, ids [n] int64 (feature_search_index.py:81)."""
+        if not torch.is_tensor(x):
+            x = np.ascontiguousarray(x, dtype=np.float32)
+            if not x.flags.writeable:   # e.g. a read-only memory map of an index file: torch wants a writable buffer
+                x = x.copy()
+            x = torch.from_numpy(x)
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError(f"add_with_ids: expected [n,{self.d}], got {tuple(x.shape)}")
+        self._fill(self._slot(x.shape[0], ids, "add_with_ids"), x)
+
+    def adopt(self, rows: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: int = 0):
+        """Take ownership of rows already resident in HBM (no copy, no conversion). ids None => id = id_base + row."""
+        self._store.adopt(rows, ids, id_base)
+        self._rows_changed()
+        return self
+
+    def _finalize(self) -> None:
+        self._store.finalize()
+
+    def remove_ids(self, sel, scratch_bytes: Optional[int] = None) -> int:
+        """faiss's Index::remove_ids: drop the rows `sel` selects (an IDSelector, or an array of ids); returns how many went.
+        The payload and the ids are compacted in place, in order (csrc/compact.hip: mutate.start), through a scratch of
+        `scratch_bytes` (default REMOVE_SCRATCH_BYTES), so the index is byte for byte the one that received only the kept rows; a
+        reserved tensor keeps its capacity and later adds fill it from the new end.  What the subclass derived from the rows is
+        dropped and rebuilt by the next search that wants it; its counters go on counting."""
+        self._finalize()
+        if self._store.n:                              # implicit ids stop being id_base + row once a row goes
+            self._store.ids = self._store.explicit_ids()
+        c = _mutate.start(self, sel, scratch_bytes)
+        if c is None:
+            return 0
+        self._store.compact(c)
+        self._rows_changed()
+        self._mutations = getattr(self, "_mutations", 0) + 1
+        return c.n - c.kept
+
+    def rows_host(self):
+        """(payload [N,d], ids [N] int64) on the host: what the index file holds."""
+        self._finalize()
+        return self._store.rows.cpu().numpy(), self._store.explicit_ids().cpu().numpy()
+
+    # -- search ---------------------------------------------------------------------------------
+    def _selector_rows(self):
+        """(external ids on the device or None, id_base, row count) of the merged rows: what a selector is resolved against."""
+        self._finalize()
+        return self._store.ids, self._store.id_base, self._store.n
+
+    def _queries(self, q: torch.Tensor, what: str) -> torch.Tensor:
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"{what}: expected [nq,{self.d}], got {tuple(q.shape)}")
+        return q.to(self.device, torch.float32).contiguous()
+
+    def _grown(self, name: str, need: int) -> torch.Tensor:
+        """The byte workspace kept under the attribute `name`, at least `need` bytes: it only ever grows."""
+        ws = getattr(self, name)
+        if ws is None or ws.numel() < need:
+            ws = None
+            setattr(self, name, None)                  # release before the larger one is taken
+            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            setattr(self, name, ws)
+        return ws
+
+    def search(self, x, k: int, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy (feature_search_index.py:113).
+        params: SearchParameters(sel=...) restricts the search to the selected ids (selector.py)."""
+        sel, _ = unpack_params(params, ivf=False)
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.ndim != 2:
+            raise ValueError("search: x must be 2-D")
+        q = torch.from_numpy(x).to(self.device)
+        D, I = self.search_device(q, int(k)) if sel is None else self.search_device(q, int(k), sel=sel)
+        return D.cpu().numpy(), I.cpu().numpy()
+
+    # -- range search ---------------------------------------------------------------------------
+    def range_search_device(self, q: torch.Tensor, thresh: float, sel=None, chunk: Optional[int] = None):
+        """q [nq,d] fp32 on device -> (lims [nq+1] int64, D fp32, I int64) on the device: every row with score > thresh, each
+        query's segment by descending score, ties by ascending row (range_search.py).  The score is the exact scan's over the
+        payload, never a shadow copy's.  sel: only the selected rows can be hits (their bitmap is tested in the count pass).
+        chunk: queries per workspace chunk (default: what range_search.WORKSPACE_BYTES allows)."""
+        lib = _lib.lib()
+        self._finalize()
+        radius = _range.check_threshold(thresh)
+        res = resolve_for(self, sel)
+        keep = None if res is None else res.bitmap
+        q = self._queries(q, "range_search")
+        X, n, d, st = self._store.rows, self._store.n, self.d, _lib.stream_ptr()
+        bytes_name, count_name, fill_name = self._RANGE
+        bytes_fn, count_fn, fill_fn = getattr(lib, bytes_name), getattr(lib, count_name), getattr(lib, fill_name)
+
+        def stage(qs):
+            def count(counts, ws):
+                _lib.check(count_fn(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, _lib.ptr(keep), counts.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), st), count_name)
+
+            def fill(lims, D, P, ws):
+                _lib.check(fill_fn(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, 0, 0, lims.data_ptr(), D.data_ptr(),
+                                   P.data_ptr(), ws.data_ptr(), ws.numel(), st), fill_name)
+            return count, fill
+
+        return _range.run(q, lambda m: bytes_fn(n, d, m), stage, lambda need: self._grown("_ws", need), self._store.ids,
+                          self._store.id_base, chunk)
+
+    def range_search(self, x, thresh: float, params=None):
+        """faiss signature: x np.ndarray [nq,d] float32 -> (lims, D, I) numpy.  params: SearchParameters(sel=...)."""
+        sel, _ = unpack_params(params, ivf=False)
+        lims, D, I = self.range_search_device(_range.to_numpy(x).to(self.device), thresh, sel=sel)
+        return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        """the stored rows under the given external ids as float32 (api/routes.py:1078); NaN rows for ids the index does not
+        hold."""
+        lib = _lib.lib()
+        self._finalize()
+        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
+        out = torch.empty(qi.numel(), self.d, dtype=torch.float32, device=self.device)
+        rc = getattr(lib, self._RECONSTRUCT)(self._store.rows.data_ptr(), self._store.n, self.d, _lib.ptr(self._store.ids),
+                                             self._store.id_base, qi.data_ptr(), qi.numel(), out.data_ptr(), _lib.stream_ptr())
+        _lib.check(rc, self._RECONSTRUCT)
+        return out.cpu().numpy()

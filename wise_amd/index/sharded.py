@@ -32,7 +32,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib
-from .flat_ip import FlatIPIndex
+from .flat_common import FlatIndexBase
 from .selector import unpack_params
 
 
@@ -65,10 +65,10 @@ NO_COLLECTIVE_REMOVAL = ("the sharded indexes have no remove_ids: a collective r
 
 
 class ShardedFlatIPIndex:
-    """Every rank constructs it around its own local FlatIPIndex (rows [lo,hi) of the global index,
+    """Every rank constructs it around its own local FlatIPIndex or FlatSQfp16IPIndex (rows [lo,hi) of the global index,
     ids already global).  `search_device` is collective: all ranks call it with the same queries."""
 
-    def __init__(self, local: FlatIPIndex, group: Optional[dist.ProcessGroup] = None,
+    def __init__(self, local: FlatIndexBase, group: Optional[dist.ProcessGroup] = None,
                  local_search: Optional[Callable] = None, merge: Optional[Callable] = None,
                  always_exchange: bool = False):
         """always_exchange: run the all-gather and the merge even when the group has ONE rank (the collective and the
