@@ -44,7 +44,8 @@ const char* wise_last_error(void);
  * wise_compact_rank and wise_compact_rows, the in-place compaction behind remove_ids; and wise_sq16_encode, wise_sq16_decode,
  * wise_ivfsq16_scan (with _sel and _local) and wise_ivfsq16_range_count / _fill, IndexIVFSQfp16; and the wise_ipsq16_* entry points
  * (wise_ipsq16_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and the wise_ipsqfp16_*_workspace_bytes),
- * IndexSQfp16.  The version is 5. */
+ * IndexSQfp16; and the wise_l2_* entry points (wise_l2_topk_f32, wise_l2_topk_pos_f32, wise_l2_range_count_f32 / _fill_f32,
+ * wise_l2_prepare, wise_l2_topk_batched and their three workspace functions), IndexFlatL2.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -552,6 +553,65 @@ size_t wise_ipsqfp16_topk_batched_workspace_bytes(int64_t N, int d, int nq, int 
 int wise_ipsq16_topk_batched(const uint16_t* rows, const float* norms /*[1]*/, int64_t N, int d, const float* Q, int nq, int k,
                              const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexFlatL2: exhaustive squared-L2 search over fp32 rows — faiss's IndexFlatL2(d) under an IndexIDMap.  The index
+ * is X [N, d] fp32 row-major (4 d bytes a row, 16-byte aligned), the array IndexFlatIP keeps, plus the ids.  Returned distances are
+ * SQUARED L2, ascending; ties: the lower position wins; the padding when fewer than k rows compete is (+3.4028235e38, -1), faiss's L2
+ * convention.  Limits of every entry point: d % 16 == 0, 16 <= d <= 1024, 0 <= N < 2^32 - 1, X and Q 16-byte aligned.  Anything
+ * outside an entry point's limits, a null pointer, a misaligned pointer or a workspace shorter than its *_workspace_bytes is
+ * WISE_E_INVALID with a wise_last_error text, and nothing is written.  No call allocates or reads back: all can be captured into a
+ * graph.  All deterministic.
+ * THE DISTANCE IS A CONTRACT.  With C = d / 16, a row is 4 C sixteen-byte pieces of four floats; chunk c = 0 .. C - 1 uses the pieces
+ * c, C + c, 2 C + c and 3 C + c: element i = 0 .. 15 of the chunk is e = (i / 4) (d / 4) + 4 c + i % 4.  Start with s_c = +0; for
+ * i = 0 .. 15 in order: t = q[e] - x[e], ONE rounded fp32 subtraction, then s_c = fmaf(t, t, s_c).  Then for step = 1, 2, 4, ... < C,
+ * at once for every c with c + step < C: s_c = s_c + s_{c + step}.  dist(q, x) = s_0.  tests/l2_flat_ref.py restates it; every entry
+ * point below returns exactly these bits.  Non-finite inputs are outside the contract.  On the device the selection runs on the
+ * score -dist (negating an fp32 value is exact), so keys, ties and merges are the inner-product types'; the sign flips back on output.
+ *   wise_l2_topk_f32: the exact scan.  1 <= nq <= 1024, 1 <= k <= 2048; ids / id_base as wise_ip_topk_f32 (ids == NULL: id_base + row);
+ *     N = 0 gives all padding.  The grid runs over row ranges and a pass carries up to 4 queries; a pass reads N d 4 bytes, what
+ *     wise_ip_topk_f32 reads.  Workspace: wise_l2_topk_workspace_bytes (0: shape not served; answers without a device).
+ *   wise_l2_topk_pos_f32: the same scan over the rows X[pos[i]], i < n_pos (pos ascending, entries in [0, N): what wise_sel_positions
+ *     writes) — the counterpart of wise_ipsq16_topk_pos.  Keys carry pos[i]; n_pos == 0 gives all padding.
+ *     Workspace: wise_l2_topk_workspace_bytes(n_pos, d, nq, k).
+ *   wise_l2_range_count_f32 / _fill_f32: the count / fill pair of range_search above over the N rows (a segment is 2048 consecutive
+ *     rows; keep, counts, lims, the fixed order — ascending position —, no global atomics, ids == NULL => id_base + position: as
+ *     wise_ipsq16_range_*); a hit iff dist < radius, strictly (faiss's rule for METRIC_L2), and a hit's distance is the exact scan's,
+ *     from the same device routine.  1 <= nq <= 65535, radius finite.  Workspace: wise_l2_range_workspace_bytes.
+ *   wise_l2_prepare: what the batched search keeps beside the rows.  Xb [N, d] bf16 and norms[0] = max_r |x_r|, norms[1] =
+ *     max_r |x_r - xb_r| are wise_ip_shadow_bf16's (that entry point is called for them); half[r] (N device floats) =
+ *     0.5f * |x_r|^2 as a fixed-order fp32 sum: lane l of 64 runs s = fmaf(x, x, s) from +0 over the elements of the row's
+ *     16-byte pieces l, l + 64, ... in ascending order, then s = s + s[lane ^ o] for o = 32, 16, 8, 4, 2, 1, then the exact halving.
+ *   wise_l2_topk_batched: 3 or more queries in passes of 128 (d <= 512) or 64 on the matrix cores, the threshold form of
+ *     wise_ipsq16_topk_batched for distances.  With qb = bf16(q), |q - x|^2 / 2 = |q|^2 / 2 + |x|^2 / 2 - q . x is approximated by
+ *     |q|^2 / 2 + a(r), a(r) = half[r] - qb . xb_r on v_mfma_f32_32x32x16_bf16 (the bf16 rows are the A operands as loaded).  Per
+ *     query the exact scan's k-th smallest distance over a sample of evenly spaced rows is an upper bound t of the index's exact
+ *     k-th distance; collect rounds list EVERY (query, row) with a(r) <= (t - |q|^2) / 2 + eps, over growing shares of the rows
+ *     first, which tightens t, then over all rows; the listed rows are re-scored by the exact scan's routine and the k best
+ *     written.  eps = |q - qb| norms[0] (the query's rounding) + |qb| norms[1] (the rows' rounding) + d 2^-22 |q| (norms[0] +
+ *     norms[1]) (fp32 accumulation of the matrix-core sum) + d 2^-24 norms[0]^2 / 2 (the rounding of half[r]) + (d + 2) 2^-24
+ *     (|q| + norms[0])^2 (the contract distance against the real one, and the threshold's own arithmetic) + a term for values
+ *     below the normal range: no assumption on the data.  A query whose list (4096 rows) overflows, or whose
+ *     bf16 image or eps is not finite, has its pass redone by the exact scan queued behind and gated on the device.  The answer
+ *     has the bits of wise_l2_topk_f32 on any finite data.  Xb, half, norms: what wise_l2_prepare wrote for these rows.
+ *     counters (device, two int32, may be NULL): [0] += queries answered from the lists, [1] += queries handed to the exact scan.
+ *     Served: d % 128 == 0 in [256, 1024], 3 <= nq <= 1024, k <= 128, 4096 <= N < 2^31 — no floor beyond that: routing by size is
+ *     the caller's.  Workspace: wise_l2_topk_batched_workspace_bytes (0: shape not served). */
+size_t wise_l2_topk_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_l2_topk_f32(const float* X, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD,
+                     int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2_topk_pos_f32(const float* X, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq, int k,
+                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t wise_l2_range_workspace_bytes(int64_t N, int d, int nq);
+int wise_l2_range_count_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
+                            int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2_range_fill_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids, int64_t id_base,
+                           const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2_prepare(const float* X, int64_t N, int d, uint16_t* Xb, float* half /*[N]*/, float* norms /*[2]*/, void* stream);
+size_t wise_l2_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_l2_topk_batched(const float* X, const uint16_t* Xb, const float* half, const float* norms /*[2]*/, int64_t N, int d,
+                         const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
+                         int32_t* counters, void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 5, additive) remove_ids — stable, in-place compaction of an index's per-row arrays under a bitmap over row positions.
  *   keep      (N + 31) / 32 words as wise_sel_bitmap writes them, bit p set = row p STAYS.  The bits past N are ignored, whatever

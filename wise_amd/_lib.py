@@ -165,6 +165,15 @@ SIGNATURES = {
     "wise_ipsq16_prepare": (_i, [_vp, _i64, _i, _vp, _vp]),
     "wise_ipsqfp16_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_ipsq16_topk_batched": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_l2_topk_f32": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_topk_pos_f32": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_range_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wise_l2_range_count_f32": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_range_fill_f32": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_prepare": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "wise_l2_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_l2_topk_batched": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_compact_plan_entries": (_i64, [_i64]),
     "wise_compact_plan": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "wise_compact_rank": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),

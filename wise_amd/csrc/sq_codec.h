@@ -86,6 +86,40 @@ struct Codec16 {
     }
 };
 
+//   CodecL2  IndexFlatL2 (l2_topk.hip): d fp32 values a row, 4 d bytes = 4 C 16-byte pieces of four floats.  Chunk c is the pieces
+//            c, C + c, 2 C + c and 3 C + c, i.e. element i = 0 .. 15 of the chain is e = (i / 4) (d / 4) + 4 c + i % 4: Codec16's
+//            load shape with four pieces — each of the FOUR load instructions of a wave-load reads, per row, a contiguous run of
+//            d bytes.  The "weights" are the query's own values at those elements and the chain is the squared DISTANCE:
+//            t = q[e] - x[e] (one rounded fp32 subtraction), s = fmaf(t, t, s).  No bias; s_0 after the fold is the distance.
+struct CodecL2 {
+    static constexpr int PIECES = 4;
+    static __device__ __forceinline__ size_t row_bytes(int d) { return (size_t)4 * d; }
+    static __device__ __forceinline__ float base(float bias, const float* __restrict__, int) { return bias; }
+    static __device__ __forceinline__ void weights(const float* __restrict__ wrow, int d, int c, float4 (&w)[4]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) w[p] = *reinterpret_cast<const float4*>(wrow + p * (d >> 2) + 4 * c);
+    }
+    static __device__ __forceinline__ void load(const unsigned char* __restrict__ row, int C, int c, u32x4 (&x)[PIECES]) {
+#pragma unroll
+        for (int p = 0; p < 4; ++p) x[p] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(row) + p * C + c);
+    }
+    static __device__ __forceinline__ float sq_step(float s, float q, unsigned word) {
+        const float t = q - __uint_as_float(word);
+        return fmaf(t, t, s);
+    }
+    static __device__ __forceinline__ float chain(const u32x4 (&x)[PIECES], const float4 (&w)[4]) {
+        float a = 0.f;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            a = sq_step(a, w[p].x, x[p][0]);
+            a = sq_step(a, w[p].y, x[p][1]);
+            a = sq_step(a, w[p].z, x[p][2]);
+            a = sq_step(a, w[p].w, x[p][3]);
+        }
+        return a;
+    }
+};
+
 // THE SUM OF THE CONTRACT for SQ_T wave-loads at once (the scan and the range_search kernels): lane (sub, c) reads chunk c of row
 // r[t] (an existing row: callers clamp), runs its fmaf chain, and the chunks of a row are folded into its lane c = 0
 template <class Codec>

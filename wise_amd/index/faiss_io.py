@@ -82,6 +82,11 @@ A bare 'IxSQ' file (no id map) reads with ids equal to positions.  index_fourcc(
 wraps ('IxFI' or 'IxSQ'); read_index / read_index_range / index_ntotal serve this file too (dict(halves, ids)), and write_index
 writes it for a state of 'halves' and 'ids' alone.  A rank's part of a row-sharded index is a complete file of its rows.
 
+The file of index type 'IndexFlatL2' (write_idmap_flat_l2 / read_idmap_flat_l2, _range, idmap_flat_l2_ntotal) is the flat file at the
+top with faiss's IndexFlatL2 in the place of the IndexFlatIP: the inner fourcc is 'IxF2' and metric_type is 1 (METRIC_L2) in both
+headers; everything else is the 'IxFI' layout, a bare 'IxF2' file reads with ids equal to positions, and _flat_head refuses by name
+an 'IxFI' file whose metric_type is 1 and an 'IxF2' file whose metric_type is 0.
+
 Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' / 'IwSq' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
@@ -147,8 +152,8 @@ def _read_header(buf, off):
 
 
 class _FlatHead(NamedTuple):
-    """The head of a flat file, 'IxFI' or 'IxSQ', bare or inside 'IxMp' (_flat_head)."""
-    inner: str           # 'IxFI' (fp32 rows) or 'IxSQ' (binary16 rows, QT_fp16)
+    """The head of a flat file, 'IxFI', 'IxF2' or 'IxSQ', bare or inside 'IxMp' (_flat_head)."""
+    inner: str           # 'IxFI' / 'IxF2' (fp32 rows, inner product / L2) or 'IxSQ' (binary16 rows, QT_fp16)
     d: int
     n: int
     off: int             # byte offset of the payload
@@ -157,7 +162,8 @@ class _FlatHead(NamedTuple):
 
 
 _FLAT_HEAD_BYTES = 4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8     # the most a flat head takes: both headers with a metric_arg
-_FLAT_NAMES = {"IxFI": "IndexFlatIP", "IxSQ": "IndexSQfp16"}
+_FLAT_NAMES = {"IxFI": "IndexFlatIP", "IxSQ": "IndexSQfp16", "IxF2": "IndexFlatL2"}
+_FLAT_METRIC = {"IxFI": 0, "IxF2": 1}     # faiss METRIC_INNER_PRODUCT / METRIC_L2: what the headers of an fp32 flat file must say
 
 
 def _flat_outer(head: bytes):
@@ -172,8 +178,8 @@ def _flat_outer(head: bytes):
 
 
 def _flat_head(p, want: str) -> _FlatHead:
-    """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxSQ'), bare or inside 'IxMp'.  RuntimeError naming
-    the file for anything else, a ScalarQuantizer record other than QT_fp16 / code_size 2d, a payload length that is not n x d
+    """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxF2' / 'IxSQ'), bare or inside 'IxMp'.  RuntimeError naming
+    the file for anything else, a metric_type that is not the fourcc's ('IxFI': 0, 'IxF2': 1, in either header), a ScalarQuantizer record other than QT_fp16 / code_size 2d, a payload length that is not n x d
     values, or a file shorter than its header promises."""
     size = p.stat().st_size
     with open(p, "rb") as f:
@@ -181,14 +187,17 @@ def _flat_head(p, want: str) -> _FlatHead:
     try:
         cc, inner, off, d0, n0 = _flat_outer(head)
         idmap = cc == _fourcc("IxMp")
+        metric0 = struct.unpack_from("<i", head, 4 + _HDR_SIZE - 4)[0] if idmap else None
         if inner != _fourcc(want):
             if want == "IxSQ":
                 raise RuntimeError(f"{p}: index type 0x{inner:08x} is not IndexScalarQuantizer (IndexSQfp16: 'IxSQ', bare or inside 'IxMp')")
+            if want == "IxF2":
+                raise RuntimeError(f"{p}: index type 0x{inner:08x} is not IndexFlatL2 ('IxF2', bare or inside 'IxMp')")
             if idmap:
                 raise RuntimeError(f"{p}: IndexIDMap wraps index type 0x{inner:08x}, expected IndexFlatIP")
             raise RuntimeError(f"{p}: index type 0x{cc:08x} is not IndexIDMap/IndexFlatIP; only flat IP indexes are "
                                f"supported by the MI355X search path")
-        d, n, _, off = _read_header(head, off)
+        d, n, metric, off = _read_header(head, off)
         if want == "IxSQ":
             qtype, rangestat, rangestat_arg, dsq, code_size, ntrained = struct.unpack_from("<iifQQQ", head, off)
             off += 36
@@ -196,6 +205,10 @@ def _flat_head(p, want: str) -> _FlatHead:
         off += 8
     except struct.error as e:
         raise RuntimeError(f"{p}: the head of an {_FLAT_NAMES[want]} file is cut short ({e})") from None
+    if want in _FLAT_METRIC and (metric != _FLAT_METRIC[want] or (idmap and metric0 != _FLAT_METRIC[want])):
+        raise RuntimeError(f"{p}: an {_FLAT_NAMES[want]} file ('{want}') with metric_type {metric}"
+                           + (f" under an IndexIDMap of metric_type {metric0}" if idmap else "")
+                           + f": {_FLAT_NAMES[want]} is metric_type {_FLAT_METRIC[want]}")
     if want == "IxSQ":
         if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
             raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, "
@@ -246,6 +259,46 @@ def read_idmap_flat_ip(path, mmap: bool = True):
 
 
 _IVF_RECORDS = {"IwFl": "IndexIVFFlat", "IwPQ": "IndexIVFPQ", "IwSq": "IndexIVFScalarQuantizer"}
+
+
+def write_idmap_flat_l2(path, X: np.ndarray, ids: np.ndarray) -> None:
+    """'IxMp' around 'IxF2' with metric_type 1 (METRIC_L2) in both headers; otherwise the 'IxFI' layout."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    n, d = X.shape
+    assert ids.shape == (n,)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IxMp")))
+        f.write(_header(d, n, 1))
+        f.write(struct.pack("<I", _fourcc("IxF2")))
+        f.write(_header(d, n, 1))
+        f.write(struct.pack("<Q", n * d))
+        X.tofile(f)
+        f.write(struct.pack("<Q", n))
+        ids.tofile(f)
+
+
+def read_idmap_flat_l2(path, mmap: bool = True):
+    """-> (X [n,d] float32 (a memmap view unless mmap is False), ids int64[n]) of an IndexFlatL2 file; a bare 'IxF2' file (no id map)
+    gives ids = positions.  RuntimeError naming the file for a truncated or foreign one, or one whose metric_type is not 1."""
+    p = _existing(path)
+    head = _flat_head(p, "IxF2")
+    return _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
+
+
+def read_idmap_flat_l2_range(path, lo: int, hi: int):
+    """-> (X [hi - lo, d] float32, ids int64[hi - lo]): the rows [lo, hi) of an IndexFlatL2 file, read without mapping the rest."""
+    p = _existing(path)
+    head = _flat_head(p, "IxF2")
+    if not (0 <= lo <= hi <= head.n):
+        raise ValueError(f"{p}: rows [{lo}, {hi}) outside the file's {head.n}")
+    X = np.fromfile(p, dtype=head.dtype, count=(hi - lo) * head.d, offset=head.off + lo * head.d * 4).reshape(hi - lo, head.d)
+    return X, _flat_ids(p, head, lo, hi)
+
+
+def idmap_flat_l2_ntotal(path) -> int:
+    """ntotal of an IndexFlatL2 file, from its head alone."""
+    return _flat_head(_existing(path), "IxF2").n
 
 
 def _existing(path) -> Path:
@@ -791,7 +844,7 @@ def read_ivf_sq_ip_range(path, lo: int, hi: int):
 
 def index_fourcc(path, inner: bool = False) -> str:
     """The fourcc the file opens with; inner: for an 'IxMp' (IndexIDMap) file the fourcc of the index it wraps — 'IxFI' for
-    IndexFlatIP, 'IxSQ' for IndexSQfp16 — ('' where the file ends before it), for any other file its own."""
+    IndexFlatIP, 'IxF2' for IndexFlatL2, 'IxSQ' for IndexSQfp16 — ('' where the file ends before it), for any other file its own."""
     with open(path, "rb") as f:
         head = f.read(_FLAT_HEAD_BYTES if inner else 4)
     if not inner or head[:4] != b"IxMp":

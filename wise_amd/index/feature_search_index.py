@@ -32,10 +32,13 @@ factory attribute, the shape check, the file's payload, its writer and reader, a
     index type                       class (flat_ip.py, flat_sq.py)              a row in HBM and in the file                            file record (faiss_io.py)
     IndexFlatIP                      FlatIPIndex                                 the fp32 row                                            'IxMp' around 'IxFI' (faiss)
     IndexSQfp16                      FlatSQfp16IPIndex                           d binary16 values, 2 d bytes, no fp32 rows              'IxMp' around 'IxSQ' (faiss), qtype 4
+    IndexFlatL2 (flat_l2.py)         FlatL2Index                                 the fp32 row; squared-L2 distances, ascending           'IxMp' around 'IxF2' (faiss), metric_type 1
 
-Both classes are one row store and one shared surface (flat_common.py) around their own payload and search.  Wherever IndexFlatIP
+The classes are one row store and one shared surface (flat_common.py) around their own payload and search.  Wherever IndexFlatIP
 is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
-ShardedFlatIPIndex wrapper — IndexSQfp16 goes the same way; its file holds the rows rounded to binary16 (numpy's float32 ->
+ShardedFlatIPIndex wrapper — IndexSQfp16 and IndexFlatL2 go the same way (the wrapper exchanges and merges an L2 index's negated
+distances).  IndexFlatIP and IndexFlatL2 hold the same fp32 payload: the fourcc inside the file's id map tells their files apart,
+and an index object's `metric` its type.  The IndexSQfp16 file holds the rows rounded to binary16 (numpy's float32 ->
 float16 cast, which is what the GPU encoder of add_with_ids computes bit for bit).
 
 The bare names `IndexIVFPQ` / `IndexIVFOPQ` mean m = d / 4.  Everything below is written once and driven by that table.
@@ -82,6 +85,7 @@ from ..feature.feature_extractor_factory import FeatureExtractorFactory
 from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
+from .flat_l2 import FlatL2Index, check_shape as check_flat_l2_shape
 from .flat_sq import FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
@@ -247,7 +251,7 @@ def _host_state(index, fam):
 def _unknown_index_type(index_type):
     return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
                                f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16, '
-                               f'and IndexSQfp16')
+                               f'and IndexSQfp16, and IndexFlatL2')
 
 
 def _to_halves(X):
@@ -267,6 +271,7 @@ class _FlatType:
     writer: Callable     # (path, payload, ids) -> the file
     reader: Callable     # path -> (payload [N,d], memory-mapped; ids [N])
     add: str             # the index method that takes rows of the file's payload and their ids
+    metric: str = 'ip'   # the index object's `metric` (flat_common.py): tells the types apart that share a payload dtype
 
 
 FLAT_TYPES = {
@@ -274,6 +279,8 @@ FLAT_TYPES = {
                              faiss_io.read_idmap_flat_ip, 'add_with_ids'),
     'IndexSQfp16': _FlatType('flat_sqfp16_index_factory', check_sqfp16_flat_shape, 'IxSQ', np.float16, _to_halves,
                              faiss_io.write_idmap_sq16_ip, faiss_io.read_idmap_sq16_ip, 'add_halves_with_ids'),
+    'IndexFlatL2': _FlatType('flat_l2_index_factory', check_flat_l2_shape, 'IxF2', np.float32, lambda X: X, faiss_io.write_idmap_flat_l2,
+                             faiss_io.read_idmap_flat_l2, 'add_with_ids', metric='l2'),
 }
 
 
@@ -317,6 +324,7 @@ class FeatureSearchIndex(SearchIndex):
     # the classes that hold a rank's rows in HBM; CPU tests of the multi-rank wiring put stand-ins here
     flat_index_factory = FlatIPIndex
     flat_sqfp16_index_factory = FlatSQfp16IPIndex
+    flat_l2_index_factory = FlatL2Index
     ivf_index_factory = IVFFlatIPIndex
     ivfpq_index_factory = IVFPQIPIndex
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
@@ -557,7 +565,8 @@ class FeatureSearchIndex(SearchIndex):
 
     def _index_from_file(self, fn, shard=None):
         """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
-        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16;
+        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16, an
+        'IxF2' file an IndexFlatL2;
         anything else that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
         shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
         if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
@@ -579,8 +588,9 @@ class FeatureSearchIndex(SearchIndex):
         """index object -> file (the inverse of _index_from_file)."""
         if hasattr(index, 'state_host'):                 # an inverted-file index
             return faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
-        payload, ids = index.rows_host()                 # an exhaustive one: its payload's dtype names the type
-        flat = next((t for t in FLAT_TYPES.values() if t.dtype == payload.dtype), None)
+        payload, ids = index.rows_host()                 # an exhaustive one: its payload's dtype and its metric name the type
+        metric = getattr(index, 'metric', 'ip')
+        flat = next((t for t in FLAT_TYPES.values() if t.dtype == payload.dtype and t.metric == metric), None)
         if flat is None:
             raise TypeError(f'{type(index).__name__}: no index file format')
         flat.writer(fn, payload, ids)

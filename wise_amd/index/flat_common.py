@@ -1,4 +1,4 @@
-"""What the exhaustive indexes (flat_ip.py, flat_sq.py) are made of: one row store and the faiss-shaped surface around it.
+"""What the exhaustive indexes (flat_ip.py, flat_sq.py, flat_l2.py) are made of: one row store and the faiss-shaped surface around it.
 
   RowStore        ONE [N, d] payload tensor of one dtype (fp32 rows, binary16 rows) and its ids: the tensors reserved up front and
                   their fill mark, the chunks added since the last merge, rows adopted as they are, the implicit ids
@@ -114,6 +114,7 @@ class RowStore:
 
 class FlatIndexBase:
     REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
+    metric = "ip"        # "l2" (flat_l2.py): D holds squared distances, ascending; a range hit is dist < thresh
     # entry points of the subclass's payload: (workspace bytes, count pass, fill pass) of range_search, and reconstruct_batch's
     _RANGE: Tuple[str, str, str]
     _RECONSTRUCT: str
@@ -252,7 +253,7 @@ class FlatIndexBase:
             return count, fill
 
         return _range.run(q, lambda m: bytes_fn(n, d, m), stage, lambda need: self._grown("_ws", need), self._store.ids,
-                          self._store.id_base, chunk)
+                          self._store.id_base, chunk, ascending=self.metric == "l2")
 
     def range_search(self, x, thresh: float, params=None):
         """faiss signature: x np.ndarray [nq,d] float32 -> (lims, D, I) numpy.  params: SearchParameters(sel=...)."""

@@ -41,13 +41,15 @@ def check_threshold(thresh) -> float:
     return t
 
 
-def order_segments(D: torch.Tensor, P: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+def order_segments(D: torch.Tensor, P: torch.Tensor, counts: torch.Tensor, ascending: bool = False) -> torch.Tensor:
     """The permutation that puts every query's segment of (D, P) — scores and positions as a fill pass wrote them, query after
     query — into descending score, ties by ascending position.  Two device sorts: one of a 64-bit key per hit (the score's bits
     mapped to a signed integer of the same order — -0.0 below +0.0, as the scans' keys have it — above 2^32 - 1 - position), then a
-    stable one by query.  Positions are unique within a query, so the order is total and the same on every run."""
+    stable one by query.  Positions are unique within a query, so the order is total and the same on every run.
+    ascending (the L2 metric: D holds distances): the same order on the scores -D — negating a float is exact —, that is ascending
+    distance, ties by ascending position."""
     total = D.numel()
-    bits = D.view(torch.int32)
+    bits = (-D if ascending else D).view(torch.int32)
     okey = bits ^ ((bits >> 31) & 0x7FFFFFFF)
     key = (okey.to(torch.int64) << 32) | (0xFFFFFFFF - P)
     qid = torch.repeat_interleave(torch.arange(counts.numel(), device=D.device), counts, output_size=total)
@@ -57,12 +59,13 @@ def order_segments(D: torch.Tensor, P: torch.Tensor, counts: torch.Tensor) -> to
 
 
 def run(q: torch.Tensor, workspace_bytes: Callable[[int], int], stage: Callable, workspace: Callable[[int], torch.Tensor],
-        ids: Optional[torch.Tensor], id_base: int, chunk: Optional[int] = None):
+        ids: Optional[torch.Tensor], id_base: int, chunk: Optional[int] = None, ascending: bool = False):
     """(lims [nq + 1], D, I) on the device for the queries q [nq, d].
     workspace_bytes(n): the *_range_workspace_bytes of n queries (0: unsupported shape).
     stage(qs) -> (count, fill) for a chunk of queries: count(counts, ws) runs the count pass into counts [n] int64, fill(lims, D, P,
     ws) the fill pass with ids == NULL, so that P receives POSITIONS — the tie key; ids are looked up after the ordering.
-    chunk: queries per chunk (default: as many as WORKSPACE_BYTES allows)."""
+    chunk: queries per chunk (default: as many as WORKSPACE_BYTES allows).
+    ascending: D holds distances (the L2 metric); every segment comes by ascending distance (order_segments)."""
     nq, dev = q.shape[0], q.device
     lims = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
     Ds, Ps = [], []
@@ -93,7 +96,7 @@ def run(q: torch.Tensor, workspace_bytes: Callable[[int], int], stage: Callable,
         D = torch.empty(total, dtype=torch.float32, device=dev)
         P = torch.empty(total, dtype=torch.int64, device=dev)
         fill(sub, D, P, ws)
-        perm = order_segments(D, P, counts)
+        perm = order_segments(D, P, counts, ascending)
         Ds.append(D[perm])
         Ps.append(P[perm])
     if not Ds:

@@ -65,8 +65,8 @@ NO_COLLECTIVE_REMOVAL = ("the sharded indexes have no remove_ids: a collective r
 
 
 class ShardedFlatIPIndex:
-    """Every rank constructs it around its own local FlatIPIndex or FlatSQfp16IPIndex (rows [lo,hi) of the global index,
-    ids already global).  `search_device` is collective: all ranks call it with the same queries."""
+    """Every rank constructs it around its own local FlatIPIndex, FlatSQfp16IPIndex or FlatL2Index (rows [lo,hi) of the global
+    index, ids already global).  `search_device` is collective: all ranks call it with the same queries."""
 
     def __init__(self, local: FlatIndexBase, group: Optional[dist.ProcessGroup] = None,
                  local_search: Optional[Callable] = None, merge: Optional[Callable] = None,
@@ -106,6 +106,11 @@ class ShardedFlatIPIndex:
         if not self._exchanges():
             return D, I
         self.last_exchange_bytes = 0
+        if getattr(self.local, "metric", "ip") == "l2":
+            # the exchange and the merge keep the larger score: they run on the negated distances (exact; the local padding
+            # +3.4028235e38 travels as the merge's own -3.4028235e38) and the sign flips back on the result
+            D, I = self._exchange_merge(-D, I, k)
+            return -D, I
         return self._exchange_merge(D, I, k)
 
     def _exchange_merge(self, D: torch.Tensor, I: torch.Tensor, k: int):
