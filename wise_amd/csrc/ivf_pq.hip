@@ -322,12 +322,8 @@ static void launch_pq_scan(const ScanShape& s, int nq, const unsigned char* code
                        s.per, m, k, s.cap, part, count, used, keep);
 }
 
-// Workspace of the rank-local scan: the keys [groups][nq][k], then the kept probes [nq][nprobe], their bias, the kept counts
-// (for a call without probe_count) and the groups used per query
+// Workspace of the rank-local scan (LocalWorkspace, probe_compact.h): the keys are [groups][nq][k]
 static size_t local_part_bytes(const ScanShape& s, int nq, int k) { return align_up((size_t)s.groups * nq * k * sizeof(u64), 256); }
-static size_t local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
-static size_t local_bias_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(float), 256); }
-static size_t local_count_bytes(int nq) { return align_up((size_t)nq * sizeof(int), 256); }
 
 }  // namespace ivf_pq
 }  // namespace wise
@@ -452,7 +448,7 @@ extern "C" int wise_ivfpq_scan_sel(const uint8_t* codes, int64_t N, int m, const
 extern "C" size_t wise_ivfpq_scan_local_workspace_bytes(int nq, int nprobe, int k, int m) {
     ScanShape s;
     if (!plan_scan(nq, nprobe, k, m, &s) || nq > 65535) return 0;
-    return local_part_bytes(s, nq, k) + local_probe_bytes(nq, nprobe) + local_bias_bytes(nq, nprobe) + 2 * local_count_bytes(nq);
+    return LocalWorkspace::bytes(local_part_bytes(s, nq, k), nq, nprobe);
 }
 
 extern "C" int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, const int64_t* list_off, int nlist, const int64_t* ids,
@@ -475,28 +471,19 @@ extern "C" int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, con
         return WISE_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
-    u64* part = reinterpret_cast<u64*>(wsb);
-    wsb += local_part_bytes(s, nq, k);
-    long long* live = reinterpret_cast<long long*>(wsb);
-    wsb += local_probe_bytes(nq, nprobe);
-    float* lbias = reinterpret_cast<float*>(wsb);
-    wsb += local_bias_bytes(nq, nprobe);
-    int* used = reinterpret_cast<int*>(wsb);
-    wsb += local_count_bytes(nq);
-    int* count = probe_count ? probe_count : reinterpret_cast<int*>(wsb);
+    const LocalWorkspace lw = LocalWorkspace::carve(workspace, local_part_bytes(s, nq, k), nq, nprobe, probe_count);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
     hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
-                       nlist, s.groups, LOCAL_MIN_SHARE, live, lbias, count, used);
+                       nlist, s.groups, LOCAL_MIN_SHARE, lw.live, lw.lbias, lw.count, lw.used);
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
-    if (m % 16 == 0) launch_pq_scan<16, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
-    else if (m % 8 == 0) launch_pq_scan<8, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
-    else if (m % 4 == 0) launch_pq_scan<4, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
-    else launch_pq_scan<1, true>(s, nq, codes, lo, nlist, lut, live, lbias, nprobe, m, k, part, st, count, used);
+    if (m % 16 == 0) launch_pq_scan<16, true>(s, nq, codes, lo, nlist, lut, lw.live, lw.lbias, nprobe, m, k, lw.part, st, lw.count, lw.used);
+    else if (m % 8 == 0) launch_pq_scan<8, true>(s, nq, codes, lo, nlist, lut, lw.live, lw.lbias, nprobe, m, k, lw.part, st, lw.count, lw.used);
+    else if (m % 4 == 0) launch_pq_scan<4, true>(s, nq, codes, lo, nlist, lut, lw.live, lw.lbias, nprobe, m, k, lw.part, st, lw.count, lw.used);
+    else launch_pq_scan<1, true>(s, nq, codes, lo, nlist, lut, lw.live, lw.lbias, nprobe, m, k, lw.part, st, lw.count, lw.used);
     WISE_LAUNCH_CHECK("pq_scan_kernel<local>");
     // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
-    return merge_lists_launch(part, s.groups, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
-                              used, (long long)pos_base);
+    return merge_lists_launch(lw.part, s.groups, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI),
+                              st, lw.used, (long long)pos_base);
 }
 
 extern "C" int wise_pq_gather_codes(const uint8_t* codes, const int64_t* idx, int64_t n, int m, uint8_t* out, void* stream) {

@@ -457,16 +457,11 @@ extern "C" size_t wise_ivfsq_scan_workspace_bytes(int nq, int nprobe, int k) {
     return align_up((size_t)nq * nprobe * k * sizeof(u64), 256);
 }
 
-// Workspace of the rank-local scan: the keys [nprobe][nq][k], then the kept probes [nq][nprobe], their bias, the groups used per
-// query and (for a call without probe_count) the kept counts
-static size_t local_probe_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(long long), 256); }
-static size_t local_bias_bytes(int nq, int nprobe) { return align_up((size_t)nq * nprobe * sizeof(float), 256); }
-static size_t local_count_bytes(int nq) { return align_up((size_t)nq * sizeof(int), 256); }
-
+// Workspace of the rank-local scan (LocalWorkspace, probe_compact.h): the keys are [nprobe][nq][k]
 extern "C" size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int k) {
     const size_t part = wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
     if (part == 0) return 0;
-    return part + local_probe_bytes(nq, nprobe) + local_bias_bytes(nq, nprobe) + 2 * local_count_bytes(nq);
+    return LocalWorkspace::bytes(part, nq, nprobe);
 }
 
 // wise_ivfsq_scan / wise_ivfsq16_scan and, with keep, their _sel forms.  Codec16 has no q0
@@ -543,29 +538,21 @@ static int sq_scan_local_impl(const char* what, const void* codes, int64_t N, in
     const size_t need = wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
-    unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
-    u64* part = reinterpret_cast<u64*>(wsb);
-    wsb += wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
-    long long* live = reinterpret_cast<long long*>(wsb);
-    wsb += local_probe_bytes(nq, nprobe);
-    float* lbias = reinterpret_cast<float*>(wsb);
-    wsb += local_bias_bytes(nq, nprobe);
-    int* used = reinterpret_cast<int*>(wsb);
-    wsb += local_count_bytes(nq);
-    int* count = probe_count ? probe_count : reinterpret_cast<int*>(wsb);
+    const LocalWorkspace lw = LocalWorkspace::carve(workspace, wise_ivfsq_scan_workspace_bytes(nq, nprobe, k), nq, nprobe, probe_count);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
     hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
-                       nlist, nprobe, 1, live, lbias, count, used);
+                       nlist, nprobe, 1, lw.live, lw.lbias, lw.count, lw.used);
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
     const int cap = topk_list_cap(k);
     const size_t lds = (size_t)4 * cap * 8;
     if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel<Codec>), (int)lds);
     hipLaunchKernelGGL(sq_scan_local_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st,
-                       reinterpret_cast<const unsigned char*>(codes), lo, nlist, W, q0, live, lbias, nprobe, nq, d, k, cap, part, used);
+                       reinterpret_cast<const unsigned char*>(codes), lo, nlist, W, q0, lw.live, lw.lbias, nprobe, nq, d, k, cap, lw.part,
+                       lw.used);
     WISE_LAUNCH_CHECK("sq_scan_local_kernel");
     // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
-    return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
-                              used, (long long)pos_base);
+    return merge_lists_launch(lw.part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
+                              lw.used, (long long)pos_base);
 }
 
 extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,

@@ -1,5 +1,5 @@
-"""What the inverted-file indexes (ivf_flat.py, ivf_pq.py) are made of: one coarse quantizer, one list store, and the
-faiss-shaped surface around the two.
+"""What the inverted-file indexes (ivf_flat.py, ivf_sq.py, ivf_pq.py) are made of: one coarse quantizer, one list store, and
+the faiss-shaped surface around the two.
 
   CoarseQuantizer     the centroid table and everything that uses it: spherical k-means (10 Lloyd iterations, assignment
                       by inner product — what faiss's Clustering does for an inner-product IVF), run on the GPU as dense
@@ -9,6 +9,8 @@ faiss-shaped surface around the two.
                       last merge; optionally further per-row arrays kept in the same order (the compact rows a re-ranking
                       index scores its candidates from, ivf_pq.py)
   IVFIndexBase        nprobe, direct map, numpy search and the other attributes the REST layer touches on either index
+  CodedIVFIndexBase   the indexes whose lists hold encoded residuals (ivf_sq.py, ivf_pq.py): add_with_ids, encode_rows,
+                      adopt_lists with pos_base, the one-stage search with its selector and rank-local forms, id lookup
 """
 from __future__ import annotations
 
@@ -396,3 +398,164 @@ class IVFIndexBase:
     def make_direct_map(self, enable: bool = True) -> None:
         """routes.py:904-909: afterwards reconstruct works by id.  Ids are looked up in the stored id array."""
         self.direct_map.type = _DirectMap.Hashtable if enable else _DirectMap.NoMap
+
+
+class CodedIVFIndexBase(IVFIndexBase):
+    """An inverted-file index whose lists hold ENCODED RESIDUALS (ivf_sq.py, ivf_pq.py): building the lists, the one-stage
+    search with its selector and rank-local forms, and the id lookup, once.  Across GPUs an index holds one rank's slice of
+    the list-major arrays: list_off clipped to the slice and `pos_base`, the position of its first row in the whole array.
+    A codec supplies its scan entry points and workspace functions by name (below) and
+      _payload(xs, assign)   the encoded rows of a chunk (what the lists keep of it)
+      _operands(lib, st, qs) the per-query tensors its scan takes between `ids` and `nq`
+    and, where it has them, _extra_rows / _adopted_extra (further per-row arrays), `_workspace_extra` with `_shape_suffix`
+    (further arguments of its workspace functions) and WHO (a fixed class name for its error texts).
+    `lib` and `st` are the handle and the stream the caller has from _lib.lib() and _lib.stream_ptr(): a search of one query
+    is a handful of launches, and the device and the stream are asked for once per scan, not once per helper."""
+    SCAN = SCAN_SEL = SCAN_LOCAL = WORKSPACE = WORKSPACE_LOCAL = None       # names of the C ABI
+    WHO: Optional[str] = None                                                # None: the class's own name
+
+    def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable,
+                 extra_gathers: Sequence[Callable] = ()):
+        super().__init__(d, nlist, device, width, dtype, gather, extra_gathers)
+        self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
+        self._workspace_extra: tuple = ()                # what the workspace functions take after (nq, nprobe, k) ...
+        self._shape_suffix = ""                          # ... and how an "unsupported shape" text names it
+
+    def _payload(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError
+
+    def _operands(self, lib, st: int, qs: torch.Tensor) -> tuple:
+        raise NotImplementedError
+
+    def _extra_rows(self, xs: torch.Tensor) -> tuple:
+        """What else the lists keep of a chunk of rows (nothing: the codes are all there is)."""
+        return ()
+
+    def _adopted_extra(self, n: int, *extra) -> tuple:
+        """adopt_lists: the further per-row arrays of n adopted rows, checked (none here)."""
+        return ()
+
+    def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        out = torch.empty_like(x)
+        _lib.check(_lib.lib().wise_pq_residuals(x.data_ptr(), self.centroids.data_ptr(), assign.data_ptr(), x.shape[0], self.d,
+                                                self.nlist, out.data_ptr(), _lib.stream_ptr()), "wise_pq_residuals")
+        return out
+
+    def _bias(self, lib, st: int, qs: torch.Tensor, probes: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """[n, nprobe] fp32: q . c_l for every probe of every query."""
+        bias = torch.empty(qs.shape[0], nprobe, dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), qs.shape[0], nprobe, self.nlist,
+                                    self.d, bias.data_ptr(), st), "wise_pq_bias")
+        return bias
+
+    # -- construction ---------------------------------------------------------------------------
+    def _encoded_chunks(self, x: torch.Tensor, chunk: int):
+        """(start, assign, payload, extra rows) per chunk: the fp32 rows live on the device one chunk at a time, never longer"""
+        for s in range(0, x.shape[0], chunk):
+            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
+            a = self._coarse.assign_device(xs, self.centroids)
+            yield s, a, self._payload(xs, a), self._extra_rows(xs)
+
+    def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"{self.WHO or type(self).__name__}: train() before add_with_ids()")
+        x = _rows_f32(x, self.d, "add_with_ids")
+        ids = _ids_i64(ids, x.shape[0])
+        for s, a, payload, extra in self._encoded_chunks(x, chunk):
+            self._lists.append(payload, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a, extra)
+
+    def encode_rows(self, x, chunk: int = 1 << 18):
+        """(assign [n] int64, payload [n, width], extra per-row arrays ...) as numpy for the rows x [n, d]: what add_with_ids
+        would put into the lists, handed back instead (the collective build moves it to the rank that owns the row's position)."""
+        if not self.is_trained:
+            raise RuntimeError(f"{self.WHO or type(self).__name__}: train() before encode_rows()")
+        x = _rows_f32(x, self.d, "encode_rows")
+        out = None
+        for s, *parts in self._encoded_chunks(x, chunk):
+            parts = [t.cpu().numpy() for t in (parts[0], parts[1], *parts[2])]
+            if out is None:
+                out = [np.empty((x.shape[0],) + t.shape[1:], dtype=t.dtype) for t in parts]
+            for o, t in zip(out, parts):
+                o[s:s + t.shape[0]] = t
+        if out is None:
+            ls = self._lists
+            xs = torch.empty(0, self.d, dtype=torch.float32, device=self.device)
+            out = [np.empty(0, np.int64), torch.empty(0, ls.width, dtype=ls.dtype).numpy()] + [t.cpu().numpy() for t in self._extra_rows(xs)]
+        return tuple(out)
+
+    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, pos_base: int = 0,
+                    extra: Sequence[torch.Tensor] = ()):
+        """Take codes that are already grouped by list (file load).  pos_base: the codes are a slice of a larger list-major
+        array that starts at this position of it (list_off clipped to the slice).  extra: what the class's _adopted_extra
+        takes, checked after the codes and pos_base."""
+        if codes.dim() != 2 or codes.shape[1] != self._lists.width:
+            raise ValueError(f"adopt_lists: expected codes [n,{self._lists.width}]")
+        if pos_base < 0:
+            raise ValueError("adopt_lists: pos_base must not be negative")
+        self._lists.adopt(codes, ids, list_off, self._adopted_extra(codes.shape[0], *extra))
+        self.pos_base = int(pos_base)
+        return self
+
+    # -- search ---------------------------------------------------------------------------------
+    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False, local: bool = False,
+              probe_count: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None) -> None:
+        """Coarse stage, bias, the codec's operands and its scan for the queries qs into D / I [n, k]; positions: I receives
+        positions in the lists instead of external ids.  local: SCAN_LOCAL — the probes whose list is empty in this slice are
+        dropped first (the number kept goes to probe_count when given) and positions are those of the WHOLE array.
+        keep: a selector's bitmap over the list positions (IVFIndexBase._keep) — SCAN_SEL, only those rows compete."""
+        lib = _lib.lib()
+        nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
+        need = getattr(lib, self.WORKSPACE_LOCAL if local else self.WORKSPACE)(n, nprobe, k, *self._workspace_extra)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k}{self._shape_suffix}")
+        ws = self._workspace(need)
+        probes = self._coarse.probes_device(qs, nprobe).contiguous()
+        bias = self._bias(lib, st, qs, probes, nprobe)
+        operands = self._operands(lib, st, qs)
+        head = (ls.data.data_ptr(), ls.n, ls.width, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
+                *[t.data_ptr() for t in operands], n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
+        tail = (ws.data_ptr(), ws.numel(), st)
+        if local:
+            _lib.check(getattr(lib, self.SCAN_LOCAL)(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
+                       self.SCAN_LOCAL)
+        elif keep is not None:
+            _lib.check(getattr(lib, self.SCAN_SEL)(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), self.SCAN_SEL)
+        else:
+            _lib.check(getattr(lib, self.SCAN)(*head, D.data_ptr(), I.data_ptr(), *tail), self.SCAN)
+
+    def _search(self, q: torch.Tensor, k: int, chunk: int, positions: bool = False, local: bool = False,
+                probe_count: Optional[torch.Tensor] = None, sel=None):
+        q = self._queries(q)
+        keep = self._keep(sel)
+        nq = q.shape[0]
+        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
+                                        or not probe_count.is_contiguous()):
+            raise ValueError("search_local_device: probe_count must be a contiguous int32 device tensor of nq entries")
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        for s in range(0, nq, chunk):                    # bounds the workspace and the operands: chunk queries at a time
+            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], positions, local,
+                       None if probe_count is None else probe_count[s:s + chunk], keep)
+        return D, I
+
+    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
+        """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
+        return self._search(q, k, chunk, sel=sel)
+
+    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
+                            chunk: int = 1024):
+        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to
+        the slice, `pos_base` its first position; sharded.py): the same coarse stage, bias and operands, then SCAN_LOCAL.
+        probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query.
+        positions: I receives positions in the WHOLE array instead of external ids."""
+        return self._search(q, k, chunk, positions, True, probe_count)
+
+    def _positions(self, ids) -> torch.Tensor:
+        """[n] int64 on the device: where each id sits in the lists (-1: unknown)."""
+        self._finalize()
+        ls = self._lists
+        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
+        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), _lib.stream_ptr()),
+                   "wise_pq_find")
+        return pos

@@ -5,7 +5,8 @@ default): the index family of the reference's own index study (docs/Search-Index
 N * (m + 8) bytes of codes and ids, the centroids [nlist, d] and the codebooks [m, 256, d / m] — and no fp32 rows.
 
   coarse stage        the CoarseQuantizer and ListStore IVFFlatIPIndex has (ivf_common.py): the same spherical k-means,
-                      `probes_device`, list bookkeeping
+                      `probes_device`, list bookkeeping; building the lists, the search around the scan and its rank-local
+                      form are CodedIVFIndexBase's, shared with ivf_sq.py
   train(x)            coarse k-means, then per sub-space Lloyd k-means (L2, plain means, 10 iterations) on the residuals of at
                       most 65,536 training rows drawn by a seeded host permutation whose first 256 rows are the initial
                       codewords; an empty codeword keeps its value; deterministic (wise_pq_encode / wise_pq_update)
@@ -47,7 +48,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .ivf_common import IVFIndexBase, _as_tensor, _ids_i64, _rows_f32
+from .ivf_common import CodedIVFIndexBase, _as_tensor, _rows_f32
 
 KSUB = 256
 MAX_TRAIN_ROWS = 256 * KSUB      # faiss caps a sub-quantizer's training set at 256 rows per codeword
@@ -89,16 +90,20 @@ def _gather_scales(scales: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class IVFPQIPIndex(IVFIndexBase):
+class IVFPQIPIndex(CodedIVFIndexBase):
+    SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfpq_scan", "wise_ivfpq_scan_sel", "wise_ivfpq_scan_local"
+    WORKSPACE, WORKSPACE_LOCAL = "wise_ivfpq_scan_workspace_bytes", "wise_ivfpq_scan_local_workspace_bytes"
+    WHO = "IVFPQIPIndex"                                 # the subclasses' "train() before ..." texts carry this name too
+
     def __init__(self, d: int, nlist: int, m: int, nbits: int = 8, device: str = "cuda", extra_gathers=()):
         check_pq_shape(int(d), int(m), int(nbits))
         super().__init__(d, nlist, device, width=int(m), dtype=torch.uint8, gather=_gather_codes, extra_gathers=extra_gathers)
         self.m, self.nbits = int(m), 8
+        self._workspace_extra, self._shape_suffix = (self.m,), f" m={self.m}"
         self.dsub = self.d // self.m
         self.niter = 10           # of the codebook training; the coarse k-means keeps its own
         self.seed = 1234
         self.codebooks: Optional[torch.Tensor] = None      # [m, 256, dsub] fp32
-        self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
 
     @property
     def is_trained(self) -> bool:
@@ -110,12 +115,6 @@ class IVFPQIPIndex(IVFIndexBase):
         return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.codebooks))
 
     # -- training -------------------------------------------------------------------------------
-    def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
-        out = torch.empty_like(x)
-        _lib.check(_lib.lib().wise_pq_residuals(x.data_ptr(), self.centroids.data_ptr(), assign.data_ptr(), x.shape[0], self.d,
-                                                self.nlist, out.data_ptr(), _lib.stream_ptr()), "wise_pq_residuals")
-        return out
-
     def _encode(self, resid: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
         codes = torch.empty(resid.shape[0], self.m, dtype=torch.uint8, device=self.device)
         _lib.check(_lib.lib().wise_pq_encode(resid.data_ptr(), codebooks.data_ptr(), resid.shape[0], self.d, self.m, codes.data_ptr(),
@@ -164,21 +163,9 @@ class IVFPQIPIndex(IVFIndexBase):
             raise ValueError(f"set_codebooks: expected [{self.m},{KSUB},{self.dsub}]")
         self.codebooks = cb.to(self.device, torch.float32).contiguous()
 
-    # -- construction ---------------------------------------------------------------------------
-    def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
-        if not self.is_trained:
-            raise RuntimeError("IVFPQIPIndex: train() before add_with_ids()")
-        x = _rows_f32(x, self.d, "add_with_ids")
-        ids = _ids_i64(ids, x.shape[0])
-        for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
-            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
-            a = self._coarse.assign_device(xs, self.centroids)
-            codes = self._encode(self._code_input(xs, a), self.codebooks)
-            self._lists.append(codes, ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a, self._extra_rows(xs))
-
-    def _extra_rows(self, xs: torch.Tensor) -> tuple:
-        """What else the lists keep of a chunk of rows (nothing: the codes are all there is)."""
-        return ()
+    # -- construction (add_with_ids, encode_rows, adopt_lists: CodedIVFIndexBase) ------------------
+    def _payload(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        return self._encode(self._code_input(xs, assign), self.codebooks)
 
     def _code_input(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
         """What the codes of a chunk of rows are encoded from: the residuals (IVFOPQIPIndex: the rotated residuals)."""
@@ -188,108 +175,16 @@ class IVFPQIPIndex(IVFIndexBase):
         """What the per-query tables are built from: the queries (IVFOPQIPIndex: the rotated queries)."""
         return qs
 
-    def encode_rows(self, x, chunk: int = 1 << 18):
-        """(assign [n] int64, codes [n, m] uint8, extra per-row arrays ...) as numpy for the rows x [n, d]: what add_with_ids
-        would put into the lists, handed back instead (the collective build moves it to the rank that owns the row's position)."""
-        if not self.is_trained:
-            raise RuntimeError("IVFPQIPIndex: train() before encode_rows()")
-        x = _rows_f32(x, self.d, "encode_rows")
-        out = None
-        for s in range(0, x.shape[0], chunk):
-            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
-            a = self._coarse.assign_device(xs, self.centroids)
-            parts = [t.cpu().numpy() for t in (a, self._encode(self._code_input(xs, a), self.codebooks), *self._extra_rows(xs))]
-            if out is None:
-                out = [np.empty((x.shape[0],) + t.shape[1:], dtype=t.dtype) for t in parts]
-            for o, t in zip(out, parts):
-                o[s:s + xs.shape[0]] = t
-        if out is None:
-            xs = torch.empty(0, self.d, dtype=torch.float32, device=self.device)
-            out = [np.empty(0, np.int64), np.empty((0, self.m), np.uint8)] + [t.cpu().numpy() for t in self._extra_rows(xs)]
-        return tuple(out)
-
-    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, pos_base: int = 0) -> "IVFPQIPIndex":
-        """Take codes that are already grouped by list (file load).  pos_base: the codes are a slice of a larger list-major
-        array that starts at this position of it (list_off clipped to the slice)."""
-        if codes.dim() != 2 or codes.shape[1] != self.m:
-            raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
-        if pos_base < 0:
-            raise ValueError("adopt_lists: pos_base must not be negative")
-        self._lists.adopt(codes, ids, list_off)
-        self.pos_base = int(pos_base)
-        return self
-
-    # -- search ---------------------------------------------------------------------------------
-    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, positions: bool = False, local: bool = False,
-              probe_count: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None) -> None:
-        """Coarse stage, bias, tables and wise_ivfpq_scan for the queries qs into D / I [n, k]; positions: I receives positions
-        in the lists instead of external ids.  local: wise_ivfpq_scan_local — the probes whose list is empty in this slice are
-        dropped first (their number kept goes to probe_count when given) and positions are those of the whole array.
-        keep: a selector's bitmap over the list positions (IVFIndexBase._keep) — wise_ivfpq_scan_sel, only those rows compete."""
-        lib = _lib.lib()
-        if keep is not None and local:
-            raise NotImplementedError("IVFPQIPIndex: a rank's share of a search takes no selector")
-        nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
-        need = (lib.wise_ivfpq_scan_local_workspace_bytes if local else lib.wise_ivfpq_scan_workspace_bytes)(n, nprobe, k, self.m)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k} m={self.m}")
-        ws = self._workspace(need)
-        probes = self._coarse.probes_device(qs, nprobe).contiguous()
-        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
-                                    bias.data_ptr(), st), "wise_pq_bias")
-        lut = torch.empty(n, self.m, KSUB, dtype=torch.float32, device=self.device)
+    # -- search (_scan, search_device, search_local_device: CodedIVFIndexBase) ---------------------
+    def _operands(self, lib, st: int, qs: torch.Tensor) -> tuple:
+        """What the scan entry points take between ids and nq: one table per query (wise_pq_lut), [n, m, 256] fp32."""
+        lut = torch.empty(qs.shape[0], self.m, KSUB, dtype=torch.float32, device=self.device)
         tq = self._table_queries(qs)
-        _lib.check(lib.wise_pq_lut(tq.data_ptr(), self.codebooks.data_ptr(), n, self.d, self.m, lut.data_ptr(), st), "wise_pq_lut")
-        head = (ls.data.data_ptr(), ls.n, self.m, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
-                lut.data_ptr(), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
-        tail = (ws.data_ptr(), ws.numel(), st)
-        if keep is not None:
-            _lib.check(lib.wise_ivfpq_scan_sel(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), "wise_ivfpq_scan_sel")
-        elif local:
-            _lib.check(lib.wise_ivfpq_scan_local(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
-                       "wise_ivfpq_scan_local")
-        else:
-            _lib.check(lib.wise_ivfpq_scan(*head, D.data_ptr(), I.data_ptr(), *tail), "wise_ivfpq_scan")
-
-    def _search(self, q: torch.Tensor, k: int, chunk: int, positions: bool = False, local: bool = False,
-                probe_count: Optional[torch.Tensor] = None, sel=None):
-        q = self._queries(q)
-        keep = self._keep(sel)
-        nq = q.shape[0]
-        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
-                                        or not probe_count.is_contiguous()):
-            raise ValueError("search_local_device: probe_count must be a contiguous int32 device tensor of nq entries")
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        for s in range(0, nq, chunk):                    # bounds the tables: chunk * m KiB
-            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], positions, local,
-                       None if probe_count is None else probe_count[s:s + chunk], keep)
-        return D, I
-
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
-        """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
-        return self._search(q, k, chunk, sel=sel)
-
-    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
-                            chunk: int = 1024):
-        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to
-        the slice, `pos_base` its first position; ShardedIVFPQIPIndex): the same coarse stage, bias and tables, then
-        wise_ivfpq_scan_local.  probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query.
-        positions: I receives positions in the WHOLE array instead of external ids."""
-        return self._search(q, k, chunk, positions, True, probe_count)
+        _lib.check(lib.wise_pq_lut(tq.data_ptr(), self.codebooks.data_ptr(), qs.shape[0], self.d, self.m, lut.data_ptr(), st),
+                   "wise_pq_lut")
+        return (lut,)
 
     # -- the rest of the surface the REST layer touches -------------------------------------------
-    def _positions(self, ids) -> torch.Tensor:
-        """[n] int64 on the device: where each id sits in the lists (-1: unknown)."""
-        self._finalize()
-        ls = self._lists
-        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
-        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
-        _lib.check(_lib.lib().wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), _lib.stream_ptr()),
-                   "wise_pq_find")
-        return pos
-
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + its codewords; NaN for an unknown id."""
         lib = _lib.lib()
@@ -360,17 +255,14 @@ class IVFPQRefineIPIndex(IVFPQIPIndex):
     def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, rows: torch.Tensor = None,
                     scales: torch.Tensor = None, pos_base: int = 0) -> "IVFPQRefineIPIndex":
         """Take codes and compact rows that are already grouped by list (file load); pos_base as on IVFPQIPIndex."""
-        if codes.dim() != 2 or codes.shape[1] != self.m:
-            raise ValueError(f"adopt_lists: expected codes [n,{self.m}]")
-        if pos_base < 0:
-            raise ValueError("adopt_lists: pos_base must not be negative")
-        if rows is None or tuple(rows.shape) != (codes.shape[0], self.d) or rows.dtype != self._row_dtype:
-            raise ValueError(f"adopt_lists: expected rows [{codes.shape[0]},{self.d}] {self._row_dtype}")
-        if self.kind == 8 and (scales is None or tuple(scales.shape) != (codes.shape[0],) or scales.dtype != torch.float32):
-            raise ValueError(f"adopt_lists: expected scales [{codes.shape[0]}] float32")
-        self._lists.adopt(codes, ids, list_off, (rows, scales) if self.kind == 8 else (rows,))
-        self.pos_base = int(pos_base)
-        return self
+        return super().adopt_lists(codes, ids, list_off, pos_base, (rows, scales))
+
+    def _adopted_extra(self, n: int, rows, scales) -> tuple:
+        if rows is None or tuple(rows.shape) != (n, self.d) or rows.dtype != self._row_dtype:
+            raise ValueError(f"adopt_lists: expected rows [{n},{self.d}] {self._row_dtype}")
+        if self.kind == 8 and (scales is None or tuple(scales.shape) != (n,) or scales.dtype != torch.float32):
+            raise ValueError(f"adopt_lists: expected scales [{n}] float32")
+        return (rows, scales) if self.kind == 8 else (rows,)
 
     def _store(self):
         """(rows pointer, scales pointer or 0) of the merged lists"""

@@ -6,7 +6,8 @@ centroids [nlist, d] and one range per dimension (vmin, vdiff: 8 d bytes) — no
 the rows.  It is the one-byte-per-dimension point of the family: IndexIVFPQ<m> stops at m = 128 bytes per row because its
 per-query table is m KiB of LDS.
 
-  coarse stage        the CoarseQuantizer and ListStore of the other inverted-file types (ivf_common.py)
+  coarse stage        the CoarseQuantizer and ListStore of the other inverted-file types (ivf_common.py); building the lists,
+                      the search around the scan and its rank-local form are CodedIVFIndexBase's, shared with ivf_pq.py
   train(x)            coarse k-means, then vmin[i] = min r_i, vdiff[i] = max r_i - vmin[i] over the residuals r = x - c_l of the
                       training rows (wise_sq_train): faiss's RS_minmax with argument 0, an exact reduction
   add_with_ids(x,ids) code_i = clamp(floor((r_i - vmin[i]) * (255 / vdiff[i])), 0, 255) (wise_sq_encode), only the codes are kept.
@@ -41,7 +42,7 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .ivf_common import IVFIndexBase, _as_tensor, _ids_i64, _rows_f32
+from .ivf_common import CodedIVFIndexBase, _as_tensor, _rows_f32
 
 MAX_D = 1024
 
@@ -60,17 +61,17 @@ def _gather_codes(codes: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class IVFSQIPIndex(IVFIndexBase):
+class IVFSQIPIndex(CodedIVFIndexBase):
     # what IVFSQfp16IPIndex replaces: the payload's dtype and the entry points of the C ABI
-    PAYLOAD_DTYPE, PAYLOAD_NP = torch.uint8, np.uint8
+    PAYLOAD_DTYPE = torch.uint8
     SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq_scan", "wise_ivfsq_scan_sel", "wise_ivfsq_scan_local"
+    WORKSPACE, WORKSPACE_LOCAL = "wise_ivfsq_scan_workspace_bytes", "wise_ivfsq_scan_local_workspace_bytes"
     RANGE_COUNT, RANGE_FILL = "wise_ivfsq_range_count", "wise_ivfsq_range_fill"
 
     def __init__(self, d: int, nlist: int, device: str = "cuda"):
         check_sq_shape(int(d))
         super().__init__(d, nlist, device, width=int(d), dtype=self.PAYLOAD_DTYPE, gather=_gather_codes)
         self.trained: Optional[torch.Tensor] = None        # [2 d] fp32: vmin, then vdiff
-        self.pos_base = 0         # position of the first row in the whole list-major array (a rank's slice: adopt_lists)
 
     @property
     def is_trained(self) -> bool:
@@ -82,12 +83,6 @@ class IVFSQIPIndex(IVFIndexBase):
         return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.trained) if t is not None)   # (fp16: no ranges)
 
     # -- training -------------------------------------------------------------------------------
-    def _residuals(self, x: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
-        out = torch.empty_like(x)
-        _lib.check(_lib.lib().wise_pq_residuals(x.data_ptr(), self.centroids.data_ptr(), assign.data_ptr(), x.shape[0], self.d,
-                                                self.nlist, out.data_ptr(), _lib.stream_ptr()), "wise_pq_residuals")
-        return out
-
     def train(self, x) -> None:
         x = _rows_f32(x, self.d, "train")
         self._coarse.train(x)
@@ -105,124 +100,33 @@ class IVFSQIPIndex(IVFIndexBase):
             raise ValueError(f"set_trained: expected vmin [{self.d}] and vdiff [{self.d}]")
         self.trained = torch.cat([vmin.to(self.device, torch.float32), vdiff.to(self.device, torch.float32)]).contiguous()
 
-    # -- construction ---------------------------------------------------------------------------
+    # -- construction (add_with_ids, encode_rows, adopt_lists: CodedIVFIndexBase) ------------------
     def _encode(self, resid: torch.Tensor) -> torch.Tensor:
         codes = torch.empty(resid.shape[0], self.d, dtype=torch.uint8, device=self.device)
         _lib.check(_lib.lib().wise_sq_encode(resid.data_ptr(), self.trained.data_ptr(), resid.shape[0], self.d, codes.data_ptr(),
                                              _lib.stream_ptr()), "wise_sq_encode")
         return codes
 
-    def add_with_ids(self, x, ids, chunk: int = 1 << 18) -> None:
-        if not self.is_trained:
-            raise RuntimeError(f"{type(self).__name__}: train() before add_with_ids()")
-        x = _rows_f32(x, self.d, "add_with_ids")
-        ids = _ids_i64(ids, x.shape[0])
-        for s in range(0, x.shape[0], chunk):            # the fp32 rows live on the device one chunk at a time, never longer
-            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
-            a = self._coarse.assign_device(xs, self.centroids)
-            self._lists.append(self._encode(self._residuals(xs, a)), ids[s:s + chunk].to(self.device, torch.int64).contiguous(), a)
+    def _payload(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
+        return self._encode(self._residuals(xs, assign))
 
-    def encode_rows(self, x, chunk: int = 1 << 18):
-        """(assign [n] int64, codes [n, d] uint8) as numpy for the rows x [n, d]: what add_with_ids would put into the lists,
-        handed back instead (the collective build moves it to the rank that owns the row's position)."""
-        if not self.is_trained:
-            raise RuntimeError(f"{type(self).__name__}: train() before encode_rows()")
-        x = _rows_f32(x, self.d, "encode_rows")
-        assign = np.empty(x.shape[0], dtype=np.int64)
-        codes = np.empty((x.shape[0], self.d), dtype=self.PAYLOAD_NP)
-        for s in range(0, x.shape[0], chunk):
-            xs = x[s:s + chunk].to(self.device, torch.float32).contiguous()
-            a = self._coarse.assign_device(xs, self.centroids)
-            assign[s:s + xs.shape[0]] = a.cpu().numpy()
-            codes[s:s + xs.shape[0]] = self._encode(self._residuals(xs, a)).cpu().numpy()
-        return assign, codes
-
-    def adopt_lists(self, codes: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, pos_base: int = 0) -> "IVFSQIPIndex":
-        """Take codes that are already grouped by list (file load).  pos_base: the codes are a slice of a larger list-major
-        array that starts at this position of it (list_off clipped to the slice)."""
-        if codes.dim() != 2 or codes.shape[1] != self.d:
-            raise ValueError(f"adopt_lists: expected codes [n,{self.d}]")
-        if pos_base < 0:
-            raise ValueError("adopt_lists: pos_base must not be negative")
-        self._lists.adopt(codes, ids, list_off)
-        self.pos_base = int(pos_base)
-        return self
-
-    # -- search ---------------------------------------------------------------------------------
-    def _scan(self, qs: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, keep: Optional[torch.Tensor], local: bool = False,
-              probe_count: Optional[torch.Tensor] = None, positions: bool = False) -> None:
-        """Coarse stage, bias, weights and the scan for the queries qs into D / I [n, k].  local: wise_ivfsq_scan_local — the
-        probes whose list is empty in this slice are dropped first (the number kept goes to probe_count when given); positions:
-        I then receives positions in the WHOLE array instead of external ids."""
-        lib = _lib.lib()
-        nprobe, ls, st, n = self._clamped_nprobe(), self._lists, _lib.stream_ptr(), qs.shape[0]
-        need = (lib.wise_ivfsq_scan_local_workspace_bytes if local else lib.wise_ivfsq_scan_workspace_bytes)(n, nprobe, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape nq={n} nprobe={nprobe} k={k}")
-        ws = self._workspace(need)
-        probes = self._coarse.probes_device(qs, nprobe).contiguous()
-        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
-                                    bias.data_ptr(), st), "wise_pq_bias")
-        weights = self._weights(qs)
-        head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, 0 if positions else ls.ids.data_ptr(),
-                *(t.data_ptr() for t in weights), n, probes.data_ptr(), bias.data_ptr(), nprobe, k)
-        tail = (ws.data_ptr(), ws.numel(), st)
-        if local:
-            _lib.check(getattr(lib, self.SCAN_LOCAL)(*head, self.pos_base, D.data_ptr(), I.data_ptr(), _lib.ptr(probe_count), *tail),
-                       self.SCAN_LOCAL)
-        elif keep is not None:
-            _lib.check(getattr(lib, self.SCAN_SEL)(*head, keep.data_ptr(), D.data_ptr(), I.data_ptr(), *tail), self.SCAN_SEL)
-        else:
-            _lib.check(getattr(lib, self.SCAN)(*head, D.data_ptr(), I.data_ptr(), *tail), self.SCAN)
-
-    def _weights(self, qs: torch.Tensor) -> tuple:
+    # -- search (_scan, search_device, search_local_device: CodedIVFIndexBase) ---------------------
+    def _operands(self, lib, st: int, qs: torch.Tensor) -> tuple:
         """What the scan entry points take between ids and nq: (W, q0) of wise_sq_query."""
         W = torch.empty(qs.shape[0], self.d, dtype=torch.float32, device=self.device)
         q0 = torch.empty(qs.shape[0], dtype=torch.float32, device=self.device)
-        _lib.check(_lib.lib().wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), qs.shape[0], self.d, W.data_ptr(), q0.data_ptr(),
-                                            _lib.stream_ptr()), "wise_sq_query")
+        _lib.check(lib.wise_sq_query(qs.data_ptr(), self.trained.data_ptr(), qs.shape[0], self.d, W.data_ptr(), q0.data_ptr(), st),
+                   "wise_sq_query")
         return W, q0
-
-    def search_device(self, q: torch.Tensor, k: int, chunk: int = 1024, sel=None):
-        """sel: an IDSelector (selector.py) — the same probes, only the selected rows compete."""
-        q = self._queries(q)
-        keep = self._keep(sel)
-        nq = q.shape[0]
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        for s in range(0, nq, chunk):                    # bounds the workspace: chunk * nprobe * k keys
-            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], keep)
-        return D, I
-
-    def search_local_device(self, q: torch.Tensor, k: int, probe_count: Optional[torch.Tensor] = None, positions: bool = False,
-                            chunk: int = 1024):
-        """search_device for an index that holds ONE RANK's slice of a list-major index sharded across GPUs (list_off clipped to
-        the slice, `pos_base` its first position; ShardedIVFSQIPIndex): the same coarse stage, bias and weights, then
-        wise_ivfsq_scan_local.  probe_count: optional [nq] int32 device tensor that receives the number of probes kept per query.
-        positions: I receives positions in the WHOLE array instead of external ids."""
-        q = self._queries(q)
-        nq = q.shape[0]
-        if probe_count is not None and (probe_count.dtype != torch.int32 or probe_count.numel() < nq or probe_count.device != q.device
-                                        or not probe_count.is_contiguous()):
-            raise ValueError("search_local_device: probe_count must be a contiguous int32 device tensor of nq entries")
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        for s in range(0, nq, chunk):
-            self._scan(q[s:s + chunk], k, D[s:s + chunk], I[s:s + chunk], None, True,
-                       None if probe_count is None else probe_count[s:s + chunk], positions)
-        return D, I
 
     def _range_workspace_bytes(self, nq: int, nprobe: int) -> int:
         return _lib.lib().wise_ivfsq_range_workspace_bytes(self._lists.n, self.nlist, nq, nprobe)
 
     def _range_stage(self, qs, probes, nprobe, radius, keep):
-        """bias and weights as _scan computes them, then wise_ivfsq_range_count / _fill over the same probes"""
+        """bias and operands as _scan computes them, then wise_ivfsq_range_count / _fill over the same probes"""
         lib, ls, st, n = _lib.lib(), self._lists, _lib.stream_ptr(), qs.shape[0]
-        bias = torch.empty(n, nprobe, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_pq_bias(qs.data_ptr(), self.centroids.data_ptr(), probes.data_ptr(), n, nprobe, self.nlist, self.d,
-                                    bias.data_ptr(), st), "wise_pq_bias")
-        weights = self._weights(qs)
+        bias = self._bias(lib, st, qs, probes, nprobe)
+        weights = self._operands(lib, st, qs)
         head = (ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist)
 
         def mid():       # built inside the closures: they, not this frame, keep the weights, probes and bias alive until fill has run
@@ -240,12 +144,7 @@ class IVFSQIPIndex(IVFIndexBase):
     # -- the rest of the surface the REST layer touches -------------------------------------------
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + the bin centres; NaN for an unknown id."""
-        lib = _lib.lib()
-        self._finalize()
-        st, ls = _lib.stream_ptr(), self._lists
-        qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
-        pos = torch.empty(qi.numel(), dtype=torch.int64, device=self.device)
-        _lib.check(lib.wise_pq_find(ls.ids.data_ptr(), ls.n, qi.data_ptr(), qi.numel(), pos.data_ptr(), st), "wise_pq_find")
+        pos = self._positions(ids)
         out = torch.empty(pos.numel(), self.d, dtype=torch.float32, device=self.device)
         self._decode(pos, out)
         return out.cpu().numpy()
@@ -271,7 +170,7 @@ class IVFSQIPIndex(IVFIndexBase):
 class IVFSQfp16IPIndex(IVFSQIPIndex):
     """Index type 'IndexIVFSQfp16' (module docstring): the rows as binary16 residuals, `halves` [N, d] float16.  No `trained`
     state: is_trained is the coarse quantizer's alone, train() runs the coarse k-means only."""
-    PAYLOAD_DTYPE, PAYLOAD_NP = torch.float16, np.float16
+    PAYLOAD_DTYPE = torch.float16
     SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq16_scan", "wise_ivfsq16_scan_sel", "wise_ivfsq16_scan_local"
     RANGE_COUNT, RANGE_FILL = "wise_ivfsq16_range_count", "wise_ivfsq16_range_fill"
 
@@ -291,7 +190,7 @@ class IVFSQfp16IPIndex(IVFSQIPIndex):
                    "wise_sq16_encode")
         return halves
 
-    def _weights(self, qs: torch.Tensor) -> tuple:
+    def _operands(self, lib, st: int, qs: torch.Tensor) -> tuple:
         return (qs,)                                     # the query is the weight row; there is no q0
 
     def _decode(self, pos: torch.Tensor, out: torch.Tensor) -> None:
