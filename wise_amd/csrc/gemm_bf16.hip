@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "transformer.h"
+#include "ln_row.h"
 #include "gemm_shared.h"
 #include "gemm_w4.h"
 
@@ -981,7 +982,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // 4 columns (and per 1024 columns of the row): the S partials of a thread's columns are independent loads, as many
 // threads in flight as the plain reduction has — a wave per row, with the S x N/256 loads of a lane in sequence, measured
 // SLOWER than the two launches it replaced (XLM-R-large, one query: 2.04 -> 2.78 ms).  x_new = x + (bias + p_0 + p_1 + ...)
-// in that fixed order; exact two-pass statistics over the row, summed in layernorm_kernel's order (vit.hip) so that a row
+// in that fixed order; exact two-pass statistics over the row from ln_row.h's primitives, summed in LnRow's order so that a row
 // gets the bits the two launches give it, whichever path its batch size selects: there lane l of ONE wave owns the float4
 // columns l, l + 64, l + 128, ... and adds their sums one after the other before the butterfly.  Here thread t owns columns
 // t, t + 256, ...: the per-column sums go through LDS in column order, and every wave walks its lane's columns as that one
@@ -1021,42 +1022,33 @@ __global__ __launch_bounds__(256) void splitk_reduce_ln_kernel(const float* __re
             }
             v[i] = make_float4(r.x + a.x, r.y + a.y, r.z + a.z, r.w + a.w);
         }
-        col[0][c] = (v[i].x + v[i].y) + (v[i].z + v[i].w);
+        col[0][c] = ln_sum4(v[i]);
     }
     __syncthreads();
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 4 * NV; ++k) s += col[0][k * 64 + lane];
-    const float mean = wave_sum(s) / (float)N;
+    const float mean = ln_mean(wave_sum(s), N);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = i * 256 + t;
-        float e = 0.f;
-        if (c < w4) {
-            float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            e = (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-        col[1][c] = e;
+        col[1][c] = c < w4 ? ln_sqdev4(v[i], mean) : 0.f;
     }
     __syncthreads();
     float q = 0.f;
 #pragma unroll
     for (int k = 0; k < 4 * NV; ++k) q += col[1][k * 64 + lane];
-    const float rstd = rsqrtf(wave_sum(q) / (float)N + eps);
+    const float rstd = ln_rstd(wave_sum(q), N, eps);
     uint2* yr = reinterpret_cast<uint2*>(y + (size_t)row * N);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
         const int c = i * 256 + t;
         if (c < w4) {
-            const float4 ww = reinterpret_cast<const float4*>(lw)[c];
-            const float4 bb = reinterpret_cast<const float4*>(lb)[c];
-            const float y0 = (v[i].x - mean) * rstd * ww.x + bb.x, y1 = (v[i].y - mean) * rstd * ww.y + bb.y;
-            const float y2 = (v[i].z - mean) * rstd * ww.z + bb.z, y3 = (v[i].w - mean) * rstd * ww.w + bb.w;
-            uint2 pk;
-            pk.x = pack_bf16x2(y0, y1);
-            pk.y = pack_bf16x2(y2, y3);
-            yr[c] = pk;
-            xr[c] = write_norm ? make_float4(y0, y1, y2, y3) : v[i];
+            const float4 n = ln_affine4(v[i], mean, rstd, reinterpret_cast<const float4*>(lw)[c], reinterpret_cast<const float4*>(lb)[c]);
+            yr[c] = ln_pack4(n);
+            float4 o = v[i];     // (not `write_norm ? n : v[i]`: a choice between two lvalues takes v's address and sends it to scratch)
+            if (write_norm) o = n;
+            xr[c] = o;
         }
     }
 }
@@ -2027,15 +2019,10 @@ int gemm_resid_ln_rows(const bf16_t* A, const bf16_t* Wt, const float* bias, int
             ProfScope prof(PROF_GEMM, 2.0 * (double)m_valid * (double)N * (double)K, st);
             splitk_partials(A, Wt, N, K, S, part, st);
         }
-        const int nv = (N / 4 + 255) / 256;
-        const dim3 grid(m_valid), block(256);
-#define RL_CASE(n) \
-    case n: hipLaunchKernelGGL(splitk_reduce_ln_kernel<n>, grid, block, 0, st, part, S, m_valid, N, bias, x, ln_w, ln_b, eps, h, \
-                               post_ln ? 1 : 0); break;
-        switch (nv) {
-            RL_CASE(1) RL_CASE(2) RL_CASE(3) RL_CASE(4)
-        }
-#undef RL_CASE
+        with_nv<4>((N / 4 + 255) / 256, [&](auto n) {      // (float4s per THREAD here: N <= 4096)
+            hipLaunchKernelGGL(splitk_reduce_ln_kernel<decltype(n)::value>, dim3(m_valid), dim3(256), 0, st, part, S, m_valid, N, bias,
+                               x, ln_w, ln_b, eps, h, post_ln ? 1 : 0);
+        });
         WISE_LAUNCH_CHECK("splitk_reduce_ln_kernel");
         return WISE_OK;
     }

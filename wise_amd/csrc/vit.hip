@@ -12,7 +12,8 @@
 //   qkv  bf16 [Mp, 3W]   in_proj output;       also patch-embed fp32 output [Mpp, W] before layer 0
 //   a    bf16 [Mp, F]    MLP hidden;           also the im2col patches bf16 [Mpp, Kp] before layer 0
 #include "transformer.h"
-#include "gemm_w4.h"   // the volatile-asm MFMA statement and its retire / pin helpers (attn_oproj_fold_kernel)
+#include "ln_row.h"
+#include "gemm_w4.h"  // the volatile-asm MFMA statement and its retire / pin helpers (attn_oproj_fold_kernel)
 
 namespace wise {
 // Timing-only ablations of the debug library (wise_debug_set_gemm_flags, tools/vit_bench.py): bit 1 skips the LayerNorm
@@ -24,7 +25,7 @@ constexpr int g_ablate = 0;
 #endif
 
 // ------------------------------------------------------------------------------------------------
-// LayerNorm: one wave per row, row in registers, exact two-pass statistics in fp32
+// LayerNorm: one wave per row, row in registers, exact two-pass statistics in fp32 (ln_row.h)
 // ------------------------------------------------------------------------------------------------
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x /* may be xo: no restrict */, const float* __restrict__ w,
@@ -35,50 +36,22 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x /* may be
     if (row >= rows) return;
     const int w4 = W >> 2;
     const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * W);
-    float4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        v[i] = (c < w4) ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)W + eps);
+    LnRow<NV> r;
+    r.stats(lane, w4, W, eps, [&](int c) { return xr[c]; });
     uint2* yr = reinterpret_cast<uint2*>(y + (size_t)row * W);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            const float4 ww = reinterpret_cast<const float4*>(w)[c];
-            const float4 bb = reinterpret_cast<const float4*>(b)[c];
-            uint2 pk;
-            const float y0 = (v[i].x - mean) * rstd * ww.x + bb.x, y1 = (v[i].y - mean) * rstd * ww.y + bb.y;
-            const float y2 = (v[i].z - mean) * rstd * ww.z + bb.z, y3 = (v[i].w - mean) * rstd * ww.w + bb.w;
-            pk.x = pack_bf16x2(y0, y1);
-            pk.y = pack_bf16x2(y2, y3);
-            yr[c] = pk;
-            // post-LN blocks (BERT family): the normalised row is also the fp32 residual stream (xo may alias x: a wave
-            // owns its row and has read all of it)
-            if (xo) reinterpret_cast<float4*>(xo + (size_t)row * W)[c] = make_float4(y0, y1, y2, y3);
-        }
-    }
+    r.affine(lane, w4, w, b, [&](int c, const float4& n) {
+        yr[c] = ln_pack4(n);
+        // post-LN blocks (BERT family): the normalised row is also the fp32 residual stream (xo may alias x: a wave
+        // owns its row and has read all of it)
+        if (xo) reinterpret_cast<float4*>(xo + (size_t)row * W)[c] = n;
+    });
 }
 
 // The same, R rows per wave (W <= 512 with many rows: HTSAT's stages 2-3, the CLIP text tower): a wave that normalises ONE row
 // of 192 floats has a single 768-byte load in flight and lives for two butterflies — 131072 such waves per launch ran at
 // 4.5 TB/s (33 -> 28.6 us with four rows per wave; at W = 768 / 12800 rows the one-row form is as fast: 11.4 vs 11.6 us).
 // Here a wave takes R consecutive rows, all R x NV loads issued before the first sum and the R butterflies interleaved.
-// Per row the arithmetic is layernorm_kernel's, operation for operation (same bits).
+// Per row the arithmetic is layernorm_kernel's (ln_row.h's primitives in LnRow's order: same bits).
 template <int NV, int R>
 __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ b, int rows, int W, float eps,
@@ -103,7 +76,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
     for (int r = 0; r < R; ++r) {
         s[r] = 0.f;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) s[r] += (v[r][i].x + v[r][i].y) + (v[r][i].z + v[r][i].w);
+        for (int i = 0; i < NV; ++i) s[r] += ln_sum4(v[r][i]);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1)
@@ -112,16 +85,11 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
     float mean[R], q[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        mean[r] = s[r] / (float)W;
+        mean[r] = ln_mean(s[r], W);
         q[r] = 0.f;
 #pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = i * 64 + lane;
-            if (c < w4) {
-                float a0 = v[r][i].x - mean[r], a1 = v[r][i].y - mean[r], a2 = v[r][i].z - mean[r], a3 = v[r][i].w - mean[r];
-                q[r] += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-            }
-        }
+        for (int i = 0; i < NV; ++i)
+            if (i * 64 + lane < w4) q[r] += ln_sqdev4(v[r][i], mean[r]);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1)
@@ -135,15 +103,9 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const float* __rest
             const float4 bb = reinterpret_cast<const float4*>(b)[c];
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                if (row0 + r < rows) {
-                    const float rstd = rsqrtf(q[r] / (float)W + eps);
-                    uint2 pk;
-                    const float y0 = (v[r][i].x - mean[r]) * rstd * ww.x + bb.x, y1 = (v[r][i].y - mean[r]) * rstd * ww.y + bb.y;
-                    const float y2 = (v[r][i].z - mean[r]) * rstd * ww.z + bb.z, y3 = (v[r][i].w - mean[r]) * rstd * ww.w + bb.w;
-                    pk.x = pack_bf16x2(y0, y1);
-                    pk.y = pack_bf16x2(y2, y3);
-                    reinterpret_cast<uint2*>(y + (size_t)(row0 + r) * W)[c] = pk;
-                }
+                if (row0 + r < rows)
+                    reinterpret_cast<uint2*>(y + (size_t)(row0 + r) * W)[c] =
+                        ln_pack4(ln_affine4(v[r][i], mean[r], ln_rstd(q[r], W, eps), ww, bb));
             }
         }
     }
@@ -161,26 +123,27 @@ __global__ __launch_bounds__(256) void layernorm_narrow_kernel(const float* __re
     const bool on = live && lane < w4;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (on) v = reinterpret_cast<const float4*>(x + (size_t)row * W)[lane];
-    float s = (v.x + v.y) + (v.z + v.w);
+    float s = ln_sum4(v);
 #pragma unroll
     for (int off = 16; off >= 1; off >>= 1) s += __shfl_xor(s, off, 64);
-    const float mean = s / (float)W;
-    float q = 0.f;
-    if (on) {
-        const float a0 = v.x - mean, a1 = v.y - mean, a2 = v.z - mean, a3 = v.w - mean;
-        q = (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-    }
+    const float mean = ln_mean(s, W);
+    float q = on ? ln_sqdev4(v, mean) : 0.f;
 #pragma unroll
     for (int off = 16; off >= 1; off >>= 1) q += __shfl_xor(q, off, 64);
-    const float rstd = rsqrtf(q / (float)W + eps);
-    if (on) {
-        const float4 ww = reinterpret_cast<const float4*>(w)[lane];
-        const float4 bb = reinterpret_cast<const float4*>(b)[lane];
-        uint2 pk;
-        pk.x = pack_bf16x2((v.x - mean) * rstd * ww.x + bb.x, (v.y - mean) * rstd * ww.y + bb.y);
-        pk.y = pack_bf16x2((v.z - mean) * rstd * ww.z + bb.z, (v.w - mean) * rstd * ww.w + bb.w);
-        reinterpret_cast<uint2*>(y + (size_t)row * W)[lane] = pk;
-    }
+    const float rstd = ln_rstd(q, W, eps);
+    if (on)
+        reinterpret_cast<uint2*>(y + (size_t)row * W)[lane] =
+            ln_pack4(ln_affine4(v, mean, rstd, reinterpret_cast<const float4*>(w)[lane], reinterpret_cast<const float4*>(b)[lane]));
+}
+
+// one row per wave, any width the entry points admit (W <= 4096: nv <= 16); xo may be null
+static int layernorm_launch(const float* x, const float* w, const float* b, int rows, int W, float eps, bf16_t* y, float* xo,
+                            hipStream_t st, const char* what) {
+    with_nv<16>((W / 4 + 63) / 64, [&](auto n) {
+        hipLaunchKernelGGL(layernorm_kernel<decltype(n)::value>, dim3((rows + 3) / 4), dim3(256), 0, st, x, w, b, rows, W, eps, y, xo);
+    });
+    WISE_LAUNCH_CHECK(what);
+    return WISE_OK;
 }
 
 int layernorm_f32_bf16(const float* x, const float* w, const float* b, int rows, int W, float eps, bf16_t* y,
@@ -202,16 +165,7 @@ int layernorm_f32_bf16(const float* x, const float* w, const float* b, int rows,
         WISE_LAUNCH_CHECK("layernorm_rows_kernel");
         return WISE_OK;
     }
-    const dim3 grid((rows + 3) / 4), block(256);
-#define LN_CASE(n) \
-    case n: hipLaunchKernelGGL(layernorm_kernel<n>, grid, block, 0, st, x, w, b, rows, W, eps, y, (float*)nullptr); break;
-    switch (nv) {
-        LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
-        LN_CASE(9) LN_CASE(10) LN_CASE(11) LN_CASE(12) LN_CASE(13) LN_CASE(14) LN_CASE(15) LN_CASE(16)
-    }
-#undef LN_CASE
-    WISE_LAUNCH_CHECK("layernorm_kernel");
-    return WISE_OK;
+    return layernorm_launch(x, w, b, rows, W, eps, y, nullptr, st, "layernorm_kernel");
 }
 
 // the same with a second output: xo fp32 [rows, W] = the normalised rows (may be x itself) — post-LN blocks
@@ -220,17 +174,7 @@ int layernorm_f32_dual(const float* x, const float* w, const float* b, int rows,
     WISE_CHECK_ARG(x && w && b && y && xo, "layernorm_dual: null pointer");
     WISE_CHECK_ARG(rows >= 0 && W > 128 && W % 4 == 0 && W <= 4096, "layernorm_dual: W=%d must be a multiple of 4 in (128, 4096]", W);
     if (rows == 0) return WISE_OK;
-    const int nv = (W / 4 + 63) / 64;
-    const dim3 grid((rows + 3) / 4), block(256);
-#define LN_CASE(n) \
-    case n: hipLaunchKernelGGL(layernorm_kernel<n>, grid, block, 0, st, x, w, b, rows, W, eps, y, xo); break;
-    switch (nv) {
-        LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
-        LN_CASE(9) LN_CASE(10) LN_CASE(11) LN_CASE(12) LN_CASE(13) LN_CASE(14) LN_CASE(15) LN_CASE(16)
-    }
-#undef LN_CASE
-    WISE_LAUNCH_CHECK("layernorm_kernel (dual)");
-    return WISE_OK;
+    return layernorm_launch(x, w, b, rows, W, eps, y, xo, st, "layernorm_kernel (dual)");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1099,65 +1043,28 @@ __global__ __launch_bounds__(256) void embed_lnpre_kernel(const float* __restric
     const float4* src = (t == 0) ? reinterpret_cast<const float4*>(cls)
                                  : reinterpret_cast<const float4*>(patch_out + ((size_t)b * (T - 1) + (t - 1)) * W);
     const float4* pr = reinterpret_cast<const float4*>(pos + (size_t)t * W);
-    float4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            float4 a = src[c], p = pr[c];
-            v[i] = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
-        } else
-            v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)W + eps);
+    LnRow<NV> r;
+    r.stats(lane, w4, W, eps, [&](int c) {
+        const float4 a = src[c], p = pr[c];
+        return make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+    });
     float4* xr = reinterpret_cast<float4*>(x + (size_t)row * W);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            const float4 ww = reinterpret_cast<const float4*>(w)[c];
-            const float4 b4 = reinterpret_cast<const float4*>(bb)[c];
-            v[i] = make_float4((v[i].x - mean) * rstd * ww.x + b4.x, (v[i].y - mean) * rstd * ww.y + b4.y,
-                               (v[i].z - mean) * rstd * ww.z + b4.z, (v[i].w - mean) * rstd * ww.w + b4.w);
-            if (!hcopy) xr[c] = v[i];
+    // fold mode (gemm_w4.h FoldArgs): the residual stream is hi + lo (two bf16 arrays where the fp32 rows would be); the
+    // first block's QKV GEMM takes hi as its operand and the normalised row's own rstd as a scale
+    r.affine(lane, w4, w, bb, [&](int c, const float4& n) {
+        if (!hcopy) {
+            xr[c] = n;
+            return;
         }
-    }
+        const uint2 h = ln_pack4(n);
+        reinterpret_cast<uint2*>(hcopy + (size_t)row * W)[c] = h;
+        reinterpret_cast<uint2*>(hcopy + lo_off + (size_t)row * W)[c] =
+            ln_pack4(make_float4(n.x - __uint_as_float(h.x << 16), n.y - __uint_as_float(h.x & 0xffff0000u),
+                                 n.z - __uint_as_float(h.y << 16), n.w - __uint_as_float(h.y & 0xffff0000u)));
+    });
     if (hcopy) {
-        // fold mode (gemm_w4.h FoldArgs): the residual stream is hi + lo (two bf16 arrays where the fp32 rows would be); the
-        // first block's QKV GEMM takes hi as its operand and the row's rstd as a scale
-        float s2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i)
-            if (i * 64 + lane < w4) s2 += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-        const float mean2 = wave_sum(s2) / (float)W;
-        float q2 = 0.f;
-#pragma unroll
-        for (int i = 0; i < NV; ++i) {
-            const int c = i * 64 + lane;
-            if (c < w4) {
-                float a0 = v[i].x - mean2, a1 = v[i].y - mean2, a2 = v[i].z - mean2, a3 = v[i].w - mean2;
-                q2 += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-                const unsigned h0 = pack_bf16x2(v[i].x, v[i].y), h1 = pack_bf16x2(v[i].z, v[i].w);
-                reinterpret_cast<uint2*>(hcopy + (size_t)row * W)[c] = make_uint2(h0, h1);
-                reinterpret_cast<uint2*>(hcopy + lo_off + (size_t)row * W)[c] =
-                    make_uint2(pack_bf16x2(v[i].x - __uint_as_float(h0 << 16), v[i].y - __uint_as_float(h0 & 0xffff0000u)),
-                               pack_bf16x2(v[i].z - __uint_as_float(h1 << 16), v[i].w - __uint_as_float(h1 & 0xffff0000u)));
-            }
-        }
-        const float r2 = rsqrtf(wave_sum(q2) / (float)W + eps);
-        if (lane == 0) rstd_out[row] = r2;
+        r.restat(lane, w4, W, eps);
+        if (lane == 0) rstd_out[row] = r.rstd;
     }
 }
 
@@ -1172,37 +1079,10 @@ __global__ __launch_bounds__(256) void cls_ln_kernel(const float* __restrict__ x
     if (img >= B) return;
     const int w4 = W >> 2;
     const float4* xr = reinterpret_cast<const float4*>(x + ((size_t)img * T + (pos ? pos[img] : 0)) * W);
-    float4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        v[i] = (c < w4) ? xr[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-        s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
-    }
-    const float mean = wave_sum(s) / (float)W;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        if (i * 64 + lane < w4) {
-            float a0 = v[i].x - mean, a1 = v[i].y - mean, a2 = v[i].z - mean, a3 = v[i].w - mean;
-            q += (a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3);
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)W + eps);
+    LnRow<NV> r;
+    r.stats(lane, w4, W, eps, [&](int c) { return xr[c]; });
     uint2* yr = reinterpret_cast<uint2*>(y + (size_t)img * W);
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-        const int c = i * 64 + lane;
-        if (c < w4) {
-            const float4 ww = reinterpret_cast<const float4*>(w)[c];
-            const float4 bb = reinterpret_cast<const float4*>(b)[c];
-            uint2 pk;
-            pk.x = pack_bf16x2((v[i].x - mean) * rstd * ww.x + bb.x, (v[i].y - mean) * rstd * ww.y + bb.y);
-            pk.y = pack_bf16x2((v[i].z - mean) * rstd * ww.z + bb.z, (v[i].w - mean) * rstd * ww.w + bb.w);
-            yr[c] = pk;
-        }
-    }
+    r.affine(lane, w4, w, b, [&](int c, const float4& n) { yr[c] = ln_pack4(n); });
 }
 
 // out[r,:] = e[r,:] / ||e[r,:]||_2 (no epsilon: mlfoundation_openclip.py:100) ; wave per row
@@ -1343,15 +1223,13 @@ static int transformer_blocks_fold(const BlockWeights& bw, int L, int W, int H, 
 // out[b,:] = normalize( LN(x[b*T + pos[b], :]) @ proj ), projT bf16 [D,W]; hb bf16 [Bp,W] and e fp32 [Bp,D] scratch
 int pooled_ln(const float* x, const float* ln_w, const float* ln_b, int batch, int T, int W, const int* pos,
               bf16_t* hb, hipStream_t st, float eps) {
-    const int nv = (W / 4 + 63) / 64;
-    const dim3 grid((batch + 3) / 4), block(256);
-#define CLS_CASE(n) case n: hipLaunchKernelGGL(cls_ln_kernel<n>, grid, block, 0, st, x, ln_w, ln_b, batch, T, W, eps, \
-                                               hb, pos); break;
-    switch (nv) {
-        CLS_CASE(1) CLS_CASE(2) CLS_CASE(3) CLS_CASE(4) CLS_CASE(5) CLS_CASE(6) CLS_CASE(7) CLS_CASE(8)
-        default: set_error("pooled_ln: width %d too large", W); return WISE_E_UNSUPPORTED;
+    if (!with_nv<8>((W / 4 + 63) / 64, [&](auto n) {
+            hipLaunchKernelGGL(cls_ln_kernel<decltype(n)::value>, dim3((batch + 3) / 4), dim3(256), 0, st, x, ln_w, ln_b, batch, T, W,
+                               eps, hb, pos);
+        })) {
+        set_error("pooled_ln: width %d too large", W);
+        return WISE_E_UNSUPPORTED;
     }
-#undef CLS_CASE
     WISE_LAUNCH_CHECK("cls_ln_kernel");
     return WISE_OK;
 }
@@ -1362,9 +1240,7 @@ int pooled_head(const float* x, const float* ln_w, const float* ln_b, const bf16
     int rc;
     if ((rc = pooled_ln(x, ln_w, ln_b, batch, T, W, pos, hb, st, eps))) return rc;
     if ((rc = gemm_bf16(hb, projT, proj_bias, Bp, D, W, 4, e, st))) return rc;
-    hipLaunchKernelGGL(l2norm_rows_kernel, dim3((batch + 3) / 4), dim3(256), 0, st, e, batch, D, out);
-    WISE_LAUNCH_CHECK("l2norm_rows_kernel");
-    return WISE_OK;
+    return l2norm_rows(e, batch, D, out, st);
 }
 
 struct VitDims {
@@ -1484,13 +1360,6 @@ static bool cls_tail_layout(const VitDims& d, const VitWs& ws, int batch, unsign
     return true;
 }
 
-template <int NV>
-static void launch_embed(const float* po, const float* cls, const float* pos, const float* w, const float* b, int rows,
-                         int T, int W, float* x, hipStream_t st, bf16_t* hcopy, float* rstd_out, long long lo_off) {
-    hipLaunchKernelGGL(embed_lnpre_kernel<NV>, dim3((rows + 3) / 4), dim3(256), 0, st, po, cls, pos, w, b, rows, T, W,
-                       1e-5f, x, hcopy, rstd_out, lo_off);
-}
-
 // rows r * stride of a hi + lo residual stream -> fp32 rows r * ostride of out (the class rows in front of ln_post; the parity tap)
 __global__ __launch_bounds__(256) void hilo_rows_kernel(const bf16_t* __restrict__ hi, long long lo_off, int n, int stride, int W,
                                                         float* __restrict__ out, int ostride) {
@@ -1543,24 +1412,16 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
                            total4, d.T, W, x);
         WISE_LAUNCH_CHECK("embed_pos_kernel");
     } else {
-
-        const int nv = (W / 4 + 63) / 64;
         // fold mode: the fp32 rows' region holds the residual stream as hi [Mp, W] bf16, then lo [Mp, W] bf16
         bf16_t* fh = d.fold ? reinterpret_cast<bf16_t*>(x) : nullptr;
         float* frs = d.fold ? reinterpret_cast<float*>(wsb + ws.rstd) : nullptr;
         const long long flo = (long long)ws.Mp * W;
-        const float* cls = pf + o.cls; const float* pos = pf + o.pos;
-        const float* lw = pf + o.ln_pre_w; const float* lb = pf + o.ln_pre_b;
-        switch (nv) {
-            case 1: launch_embed<1>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 2: launch_embed<2>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 3: launch_embed<3>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 4: launch_embed<4>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 5: launch_embed<5>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 6: launch_embed<6>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 7: launch_embed<7>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            case 8: launch_embed<8>(patch_out, cls, pos, lw, lb, ws.M, d.T, W, x, st, fh, frs, flo); break;
-            default: set_error("vit_forward: width %d too large", W); return WISE_E_UNSUPPORTED;
+        if (!with_nv<8>((W / 4 + 63) / 64, [&](auto n) {
+                hipLaunchKernelGGL(embed_lnpre_kernel<decltype(n)::value>, dim3((ws.M + 3) / 4), dim3(256), 0, st, patch_out,
+                                   pf + o.cls, pf + o.pos, pf + o.ln_pre_w, pf + o.ln_pre_b, ws.M, d.T, W, 1e-5f, x, fh, frs, flo);
+            })) {
+            set_error("vit_forward: width %d too large", W);
+            return WISE_E_UNSUPPORTED;
         }
         WISE_LAUNCH_CHECK("embed_lnpre_kernel");
     }
