@@ -45,7 +45,9 @@ const char* wise_last_error(void);
  * wise_ivfsq16_scan (with _sel and _local) and wise_ivfsq16_range_count / _fill, IndexIVFSQfp16; and the wise_ipsq16_* entry points
  * (wise_ipsq16_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and the wise_ipsqfp16_*_workspace_bytes),
  * IndexSQfp16; and the wise_l2_* entry points (wise_l2_topk_f32, wise_l2_topk_pos_f32, wise_l2_range_count_f32 / _fill_f32,
- * wise_l2_prepare, wise_l2_topk_batched and their three workspace functions), IndexFlatL2.  The version is 5. */
+ * wise_l2_prepare, wise_l2_topk_batched and their three workspace functions), IndexFlatL2; and wise_sq_minmax and the wise_ipsq8_*
+ * entry points (wise_ipsq8_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and their three workspace
+ * functions), IndexSQ8bit.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -373,6 +375,11 @@ int wise_ivfpq_scan_sel(const uint8_t* codes, int64_t N, int m, const int64_t* l
  *     wise_sel_bitmap) is set compete; a selected row's score is the unfiltered scan's, and with every bit set so is the output.
  *     Loads that hold no selected row are skipped. */
 int wise_sq_train(const float* resid, int64_t n, int d, float* trained, void* stream);
+/* (ABI 5, additive) wise_sq_train's reduction over rows that arrive in chunks, or on several ranks: lo [d] and hi [d] (device, distinct)
+ * receive the per-dimension minimum and maximum of the n >= 0 rows — and of what lo / hi held before when accumulate != 0; with
+ * accumulate == 0 and n == 0 they are +3.4028235e38 / -3.4028235e38, the minimum and maximum of no rows.  min and max are exact and
+ * order-free: vmin = lo, vdiff = hi - lo (one fp32 subtraction) are wise_sq_train's bits over the same rows under any chunking. */
+int wise_sq_minmax(const float* rows, int64_t n, int d, float* lo, float* hi, int accumulate, void* stream);
 int wise_sq_encode(const float* resid, const float* trained, int64_t n, int d, uint8_t* codes, void* stream);
 int wise_sq_query(const float* Q, const float* trained, int nq, int d, float* W, float* q0, void* stream);
 int wise_sq_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const int64_t* list_off, int nlist,
@@ -553,6 +560,65 @@ size_t wise_ipsqfp16_topk_batched_workspace_bytes(int64_t N, int d, int nq, int 
 int wise_ipsq16_topk_batched(const uint16_t* rows, const float* norms /*[1]*/, int64_t N, int d, const float* Q, int nq, int k,
                              const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexSQ8bit: exhaustive inner-product search over 8-bit scalar-quantized rows — faiss's IndexScalarQuantizer(d,
+ * QT_8bit, METRIC_INNER_PRODUCT) with RS_minmax (argument 0) under an IndexIDMap.  The whole index is codes [N, d] uint8 (d bytes a row,
+ * 16-byte aligned), trained [2 d] fp32 (vmin [d], then vdiff [d]: wise_sq_train, or wise_sq_minmax and one subtraction) and the ids:
+ * no fp32 rows and no shadow copy; the same array serves the single-query scan and, expanded in registers, the batched passes.  Rows
+ * are encoded by wise_sq_encode applied to the rows themselves.  Every entry point takes the QUERIES Q [nq, d] fp32 and trained: W and
+ * q0 of wise_sq_query are computed into the head of the call's workspace.  Limits of every entry point: d % 16 == 0, 16 <= d <= 1024,
+ * 0 <= N < 2^32 - 1, codes, Q and the workspace 16-byte aligned.  Anything outside an entry point's limits, a null pointer, a misaligned
+ * pointer or a workspace shorter than its *_workspace_bytes is WISE_E_INVALID with a wise_last_error text, and nothing is written.  No
+ * call allocates or reads back: all can be captured into a graph.  All deterministic.
+ * THE SCORE IS A CONTRACT: score(q, r) = q0[q] + s_0, ONE fp32 addition, with W, q0 the bits of wise_sq_query and s_0 of the
+ * wise_ivfsq_scan arithmetic above — one fmaf chain of 16 per chunk from +0, the tree of adds over steps 1, 2, 4, ....  Keys, ties, the
+ * range test and every returned value are on that final sum.  tests/sq8_flat_ref.py restates it; every entry point below returns exactly
+ * these bits.
+ *   wise_ipsq8_topk: the exact scan.  1 <= nq <= 1024, 1 <= k <= 2048; ids / id_base as wise_ip_topk_f32 (ids == NULL: id_base + row);
+ *     outD descending, ties: the lower position wins, (-3.4028235e38, -1) padding when N < k; N = 0 gives all padding.  The grid runs
+ *     over row ranges and a pass carries up to 4 queries; a pass reads N d bytes.  Workspace: wise_ipsq8_topk_workspace_bytes.
+ *   wise_ipsq8_topk_pos: the same scan over the rows codes[pos[i]], i < n_pos (pos ascending, entries in [0, N): what
+ *     wise_sel_positions writes) — the counterpart of wise_ipsq16_topk_pos.  Keys carry pos[i]; n_pos == 0 gives all padding.
+ *     Workspace: wise_ipsq8_topk_workspace_bytes(n_pos, d, nq, k).
+ *   wise_ipsq8_range_count / _fill: the count / fill pair of range_search above over the N rows (segments, keep, radius, counts, lims,
+ *     the fixed order, ids == NULL => id_base + position: as wise_ipsq16_range_*); a hit iff score > radius, strictly, and a hit's
+ *     score is the exact scan's, from the same device routine.  1 <= nq <= 65535.  The count pass leaves W and q0 in the workspace
+ *     for the fill pass: both take the same workspace and queries.  Workspace: wise_ipsq8_range_workspace_bytes.
+ *   wise_ipsq8_reconstruct: out[i, c] = vmin[c] + ((codes[p, c] + 0.5) / 255) * vdiff[c], each operation rounded to fp32 on its own
+ *     (faiss's Codec8bit: wise_sq_decode without a centroid), for the row p that carries the id query_ids[i] (ids == NULL: p = id -
+ *     id_base), a row of NaN where no row does.
+ *   wise_ipsq8_prepare: norms[0] (device float) = sqrtf((float)max_r sum_c codes[r, c]^2), the largest row norm of the codes taken as
+ *     the numbers 0 .. 255, 0 for N = 0.  The integer sum is exact (255^2 1024 < 2^32): the same rows give the same bits.
+ *   wise_ipsq8_topk_batched: 3 or more queries in passes of 128 (d <= 512) or 64 on the matrix cores, in the threshold form of
+ *     wise_ipsq16_topk_batched: sample, collect rounds, exact re-scoring, the gated exact scan behind a list that overflows.  The
+ *     collect pass streams the codes, 16 to a load, expands them EXACTLY in registers to binary16 operands (every integer 0 .. 255 is
+ *     a binary16 value: no row-side rounding) and issues v_mfma_f32_32x32x16_f16 against the binary16 image of 2^e W[q], e the power
+ *     of two that puts the query's largest weight into [2^14, 2^15) (exact).  In that scaled space eps = |2^e W - f16(2^e W)|_2
+ *     norms[0] (Cauchy-Schwarz on the image's rounding) + d 2^-22 |2^e W|_2 norms[0] (fp32 accumulation of both sums), and the threshold
+ *     of a k-th score t is 2^e ((t - q0) - 2^-21 (|t| + |q0|)) - eps: the keys order fl(q0 + s_0) while the pass sees s_0 alone, and
+ *     the slack pays for that addition's rounding.  A query whose weights, q0 or band are not finite, or whose
+ *     largest weight is below 2^-112, hands its pass to the exact scan.  The answer has the bits of wise_ipsq8_topk on any data.
+ *     norms: what wise_ipsq8_prepare wrote for these codes.  counters as wise_ipsq16_topk_batched.  Served: d % 128 == 0 in
+ *     [256, 1024], 3 <= nq <= 1024, k <= 128, 4096 <= N < 2^31.  Workspace: wise_ipsq8_topk_batched_workspace_bytes (0: not served). */
+size_t wise_ipsq8_topk_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_ipsq8_topk(const uint8_t* codes, const float* trained, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids,
+                    int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ipsq8_topk_pos(const uint8_t* codes, const float* trained, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q,
+                        int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t wise_ipsq8_range_workspace_bytes(int64_t N, int d, int nq);
+int wise_ipsq8_range_count(const uint8_t* codes, const float* trained, int64_t N, int d, const float* Q, int nq, float radius,
+                           const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_ipsq8_range_fill(const uint8_t* codes, const float* trained, int64_t N, int d, const float* Q, int nq, float radius,
+                          const int64_t* ids, int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int wise_ipsq8_reconstruct(const uint8_t* codes, const float* trained, int64_t N, int d, const int64_t* ids, int64_t id_base,
+                           const int64_t* query_ids, int n, float* out, void* stream);
+int wise_ipsq8_prepare(const uint8_t* codes, int64_t N, int d, float* norms /*[1]*/, void* stream);
+size_t wise_ipsq8_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_ipsq8_topk_batched(const uint8_t* codes, const float* trained, const float* norms /*[1]*/, int64_t N, int d, const float* Q,
+                            int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters,
+                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 5, additive) IndexFlatL2: exhaustive squared-L2 search over fp32 rows — faiss's IndexFlatL2(d) under an IndexIDMap.  The index
  * is X [N, d] fp32 row-major (4 d bytes a row, 16-byte aligned), the array IndexFlatIP keeps, plus the ids.  Returned distances are

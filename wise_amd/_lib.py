@@ -131,6 +131,7 @@ SIGNATURES = {
     "wise_opq_corr": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
     "wise_opq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "wise_sq_train": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_sq_minmax": (_i, [_vp, _i64, _i, _vp, _vp, _i, _vp]),
     "wise_sq_encode": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "wise_sq_query": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "wise_sq_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
@@ -165,6 +166,16 @@ SIGNATURES = {
     "wise_ipsq16_prepare": (_i, [_vp, _i64, _i, _vp, _vp]),
     "wise_ipsqfp16_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_ipsq16_topk_batched": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq8_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ipsq8_topk": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq8_topk_pos": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq8_range_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wise_ipsq8_range_count": (_i, [_vp, _vp, _i64, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq8_range_fill": (_i, [_vp, _vp, _i64, _i, _vp, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ipsq8_reconstruct": (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp, _i, _vp, _vp]),
+    "wise_ipsq8_prepare": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_ipsq8_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ipsq8_topk_batched": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_l2_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_l2_topk_f32": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "wise_l2_topk_pos_f32": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

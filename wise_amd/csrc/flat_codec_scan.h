@@ -1,7 +1,7 @@
-// The flat codec scans: everything IndexSQfp16 (ip_sq16.hip) and IndexFlatL2 (l2_topk.hip) share, written once and templated
-// on a METRIC POLICY M.  The two files keep their policy, the kernels that belong to one type alone (the stage kernels with their
-// error bands, reconstruct, the norm kernels, the flip) and their extern "C" entry points, which are thin calls into the drivers
-// below.  `static` on what is no template: two translation units include this header and each gets its own copy.
+// The flat codec scans: everything IndexSQfp16 (ip_sq16.hip), IndexFlatL2 (l2_topk.hip) and IndexSQ8bit (ip_sq8.hip) share, written
+// once and templated on a METRIC POLICY M.  The three files keep their policy, the kernels that belong to one type alone (the stage
+// kernels with their error bands, reconstruct, the norm kernels, the flip) and their extern "C" entry points, which are thin calls
+// into the drivers below.  `static` on what is no template: three translation units include this header and each gets its own copy.
 //
 // HOW A WAVE-LOAD IS LAID OUT.  A row is C = d / 16 chunks; lane (sub, c) of a wave-load holds chunk c of row sub, RPL = 64 / C
 // whole rows per load and SQ_T loads in flight.  Chunk c is the row's 16-byte pieces c, C + c, ... (Codec::PIECES of them: two
@@ -13,8 +13,12 @@
 // flat scan's: sortable (score, position) keys, per-wave threshold lists, merge_keys_kernel (ip_topk.hip).  No packed f32 math.
 //
 // THE POLICY: plain static members, no virtuals, nothing decided at run time.
-//   Codec                      Codec16 or CodecL2 (sq_codec.h): the loads, the weights and the chain of a row's score s
-//   key_score(s)               what the keys order, larger is better: s, or -s for a distance (negating an fp32 value is exact)
+//   Codec                      Codec16, CodecL2 or Codec8 (sq_codec.h): the loads, the weights and the chain of a row's sum s
+//   base(b, q), score(s, b)    the per-query base term (b: the array the entry point hands over, q: the query of the pass) and the
+//                              row's score as the caller sees it.  PlainPolicy: no base, score = s, nothing is loaded; IndexSQ8bit
+//                              (ip_sq8.hip): b[q] = q0 of wise_sq_query and score = q0 + s, ONE fp32 addition.  Keys, the range test
+//                              and every returned value are on score
+//   key_score(sc)              what the keys order, larger is better: sc, or -sc for a distance (negating an fp32 value is exact)
 //   out_score(ks)              a key's score as the caller sees it: the inverse of key_score
 //   PAD                        the output score of a slot that no row fills (-3.4028235e38, +3.4028235e38 for a distance)
 //   FLIP                       launch_merge_keys writes key scores: a pass of M::flip over its output follows
@@ -22,6 +26,9 @@
 //   thr_open(), thr_shut()     the collect thresholds that list every row (before the first sample) and no row (query slots past nq)
 //   tighten(thr, t, ws, q)     the threshold after a round whose k-th exact output score was t: never looser than thr
 //   Piece, mfma(a, b, acc)     the 8-element operand of the collect pass and its v_mfma_f32_32x32x16_* instruction
+//   LOAD_PIECES, operand(x, p) operands a 16-byte load of the collect pass holds: 1 (16-bit rows: the load IS the operand), or 2 (8-bit
+//                              codes: operand p = the load's codes 8 p .. 8 p + 7 expanded in registers)
+//   QUERY_EXP                  BatchSlots carries a per-query power of two (the stage kernel's scaling of the query image)
 //   HALF_NORMS                 the collect score is half[row] - acc, not acc: the half-norms are loaded, and BatchSlots carries |q|^2
 //   candidate(hv, acc, thr)    the collect test, written so that a NaN score is a candidate
 //   stage(...)                 launches the type's stage kernel (query images, eps, the opening thresholds); returns its name
@@ -36,6 +43,14 @@ using namespace ivf_sq;
 
 constexpr int MAX_D = 1024;
 constexpr int MAX_NQP = 4;                // queries a pass of the exact scan carries at most
+
+// what a policy over 16-bit collect rows whose score is the row's sum itself inherits
+struct PlainPolicy {
+    static constexpr int LOAD_PIECES = 1;
+    static constexpr bool QUERY_EXP = false;
+    static __device__ __forceinline__ float base(const float*, int) { return 0.f; }
+    static __device__ __forceinline__ float score(float s, float) { return s; }
+};
 
 static bool shape_ok(int d) { return d >= 16 && d <= MAX_D && d % 16 == 0; }
 
@@ -71,8 +86,8 @@ __device__ __forceinline__ long long row_of(const RowSource& src, long long i) {
 // score is sq_score_loads_nq's; a key carries the ROW, so ties go to the lower position whatever the order of the items.
 template <class M, int NQ, int MODE>
 __device__ __forceinline__ void scan_items(const unsigned char* __restrict__ rows, int d, long long n, long long g0, long long gstep,
-                                           const RowSource& src, const LanePlace& L, const float4 (&w)[NQ][4], WaveList (&wl)[NQ],
-                                           int lane) {
+                                           const RowSource& src, const LanePlace& L, const float4 (&w)[NQ][4], const float (&qb)[NQ],
+                                           WaveList (&wl)[NQ], int lane) {
     const long long ngroups = (n + L.RPL - 1) / L.RPL;
     for (long long g = g0; g < ngroups; g += gstep) {                               // wave-uniform
         long long r[SQ_T];
@@ -89,7 +104,7 @@ __device__ __forceinline__ void scan_items(const unsigned char* __restrict__ row
         for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t) {
-                const u64 key = make_key(M::key_score(s[q][t]), (unsigned)r[t]);
+                const u64 key = make_key(M::key_score(M::score(s[q][t], qb[q])), (unsigned)r[t]);
                 wl[q].offer(live[t] && L.c == 0 && key > wl[q].tau, key, lane);
             }
     }
@@ -120,8 +135,8 @@ __device__ __forceinline__ void fold_block_lists(WaveList (&wl)[NQ], const u64* 
 // unless *gate != 0 (the batched search's fallback)
 template <class M, int NQ, int MODE>
 __global__ __launch_bounds__(256) void flat_scan_kernel(const unsigned char* __restrict__ rows, long long n, int d,
-                                                        const float* __restrict__ Q, int k, int cap, u64* __restrict__ part,
-                                                        RowSource src, const int* __restrict__ gate) {
+                                                        const float* __restrict__ Q, const float* __restrict__ base, int k, int cap,
+                                                        u64* __restrict__ part, RowSource src, const int* __restrict__ gate) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (gate && *gate == 0) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -131,10 +146,13 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const unsigned char* __r
     float4 w[NQ][4];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) M::Codec::weights(Q + (size_t)q * d, d, L.c, w[q]);
+    float qb[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) qb[q] = M::base(base, q);
     WaveList wl[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) wl[q].init(lds + (size_t)(wave * NQ + q) * cap, cap, k, lane);
-    scan_items<M, NQ, MODE>(rows, d, n, ((long long)blockIdx.x * 4 + wave) * SQ_T, (long long)gridDim.x * 4 * SQ_T, src, L, w, wl, lane);
+    scan_items<M, NQ, MODE>(rows, d, n, ((long long)blockIdx.x * 4 + wave) * SQ_T, (long long)gridDim.x * 4 * SQ_T, src, L, w, qb, wl, lane);
     fold_block_lists<NQ>(wl, lds, cap, k, lane, wave);
     if (wave == 0) {
 #pragma unroll
@@ -150,8 +168,8 @@ __global__ __launch_bounds__(256) void flat_scan_kernel(const unsigned char* __r
 // count: block (x, y) owns segment x for the queries y NQ .. y NQ + NQ - 1 (a ragged tile repeats the last query, unwritten)
 template <class M, int NQ>
 __global__ __launch_bounds__(256) void flat_range_count_kernel(const unsigned char* __restrict__ rows, long long N, int d,
-                                                               const float* __restrict__ Q, int nq, float radius,
-                                                               const unsigned* __restrict__ keep, unsigned* __restrict__ hit,
+                                                               const float* __restrict__ Q, const float* __restrict__ base, int nq,
+                                                               float radius, const unsigned* __restrict__ keep, unsigned* __restrict__ hit,
                                                                long long wstride, long long* __restrict__ seg, long long ns) {
     __shared__ unsigned hb[NQ][RANGE_WORDS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -161,6 +179,9 @@ __global__ __launch_bounds__(256) void flat_range_count_kernel(const unsigned ch
     float4 w[NQ][4];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) M::Codec::weights(Q + (size_t)(q0 + q < nq ? q0 + q : nq - 1) * d, d, L.c, w[q]);
+    float qb[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) qb[q] = M::base(base, q0 + q < nq ? q0 + q : nq - 1);
     for (int i = threadIdx.x; i < NQ * RANGE_WORDS; i += 256) hb[i / RANGE_WORDS][i % RANGE_WORDS] = 0u;
     __syncthreads();
     const long long clo = (long long)blockIdx.x * RANGE_ROWS;
@@ -185,7 +206,7 @@ __global__ __launch_bounds__(256) void flat_range_count_kernel(const unsigned ch
         for (int q = 0; q < NQ; ++q)
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t)
-                if (live[t] && L.c == 0 && M::range_hit(s[q][t], radius)) range_mark(hb[q], (int)(r[t] - clo));
+                if (live[t] && L.c == 0 && M::range_hit(M::score(s[q][t], qb[q]), radius)) range_mark(hb[q], (int)(r[t] - clo));
     }
     __syncthreads();
     if (wave == 0) {
@@ -201,8 +222,9 @@ __global__ __launch_bounds__(256) void flat_range_count_kernel(const unsigned ch
 // fill: grid (ns, nq); the hits of one segment, in ascending position, behind lims[q] + the segment's offset
 template <class M>
 __global__ __launch_bounds__(256) void flat_range_fill_kernel(const unsigned char* __restrict__ rows, long long N, int d,
-                                                              const float* __restrict__ Q, const long long* __restrict__ ids,
-                                                              long long id_base, const unsigned* __restrict__ hit, long long wstride,
+                                                              const float* __restrict__ Q, const float* __restrict__ base,
+                                                              const long long* __restrict__ ids, long long id_base,
+                                                              const unsigned* __restrict__ hit, long long wstride,
                                                               const long long* __restrict__ seg, long long ns,
                                                               const long long* __restrict__ lims, float* __restrict__ outD,
                                                               long long* __restrict__ outI) {
@@ -221,6 +243,7 @@ __global__ __launch_bounds__(256) void flat_range_fill_kernel(const unsigned cha
     L.init(d, lane);
     float4 w[4];
     M::Codec::weights(Q + (size_t)qi * d, d, L.c, w);
+    const float qb = M::base(base, qi);
     if (wave == 0) {
         const int n = range_list(words, (int)((chi - clo + 31) >> 5), lst, lane);
         if (lane == 0) s_cnt = n;
@@ -243,7 +266,7 @@ __global__ __launch_bounds__(256) void flat_range_fill_kernel(const unsigned cha
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t)
             if (e[t] >= 0 && L.c == 0) {
-                outD[dest + e[t]] = s[t];
+                outD[dest + e[t]] = M::score(s[t], qb);
                 outI[dest + e[t]] = ids ? ids[r[t]] : id_base + r[t];
             }
     }
@@ -275,6 +298,8 @@ struct BatchSlots {                       // workspace of a pass
     float* eps;                           // [QB]
     float* q2;                            // [QB] |q|^2 (fp32); carved for M::HALF_NORMS only
     float* thr;                           // [QB]
+    int* qexp;                            // [QB] the power of two the stage kernel scaled the query image by; carved for M::QUERY_EXP only
+    const float* base;                    // [nq of the pass] the queries' base terms (M::base), the entry point's array; not carved
     int* ctl;                             // [QB] entries offered to a query's list
     int* flag;                            // [1] != 0: a list overflowed or a query has no usable image or band; the exact scan answers the pass
     unsigned* cand;                       // [QB][BATCH_CAP]
@@ -312,10 +337,11 @@ __global__ __launch_bounds__(256) void flat_query_block_kernel(const unsigned ch
     L.init(d, lane);
     float4 w[1][4];
     M::Codec::weights(Q + (size_t)q * d, d, L.c, w[0]);
+    const float qb[1] = {M::base(ws.base, q)};
     WaveList wl[1];
     wl[0].init(lds + (size_t)wave * cap, cap, k, lane);
     RowSource src{nullptr, ws.cand + (size_t)q * BATCH_CAP, gstride};
-    scan_items<M, 1, MODE>(rows, d, n, (long long)wave * SQ_T, 4 * SQ_T, src, L, w, wl, lane);
+    scan_items<M, 1, MODE>(rows, d, n, (long long)wave * SQ_T, 4 * SQ_T, src, L, w, qb, wl, lane);
     fold_block_lists<1>(wl, lds, cap, k, lane, wave);
     if (wave != 0) return;
     if (!final) {
@@ -350,16 +376,20 @@ __global__ __launch_bounds__(256) void flat_query_block_kernel(const unsigned ch
 // score.  QT = query tiles of 32 a pass carries.  group g stands for rows g * gstride * 32 ..: gstride > 1 is a sample round
 // (whole groups only), 1 the round over all rows.  A lane holds 16 rows of its group for 32 QT queries; under M::HALF_NORMS it
 // reads their half-norms (four runs of four consecutive floats).  Row r is listed for query q iff M::candidate.
+// 8-BIT CODES (M::LOAD_PIECES == 2: IndexSQ8bit).  A row is d bytes; the lane's half of it is d / 32 loads of 16 codes, and a load is
+// expanded in registers to the TWO operands of its codes 0 .. 7 and 8 .. 15 (M::operand), each against the matching piece of the
+// query image; the loads go out four at a time — the same eight MFMAs per query tile between two bursts of loads.
 template <class M, int QT>
-__global__ __launch_bounds__(BATCH_WAVES * 64) void flat_collect_kernel(const uint16_t* __restrict__ rows, const float* __restrict__ half,
+__global__ __launch_bounds__(BATCH_WAVES * 64) void flat_collect_kernel(const unsigned char* __restrict__ rows, const float* __restrict__ half,
                                                                         long long N, int d, int nq, long long ngroups,
                                                                         long long gstride, BatchSlots ws) {
     using Piece = typename M::Piece;
+    constexpr int LP = M::LOAD_PIECES, NL = 8 / LP;                                 // operands a load holds, loads of a burst
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (*ws.flag != 0) return;                                                      // before any barrier
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, h = lane >> 5;
-    const int ldb = 2 * d + 16, P = d >> 3, C = d >> 4;
+    const int ldb = 2 * d + 16, P = d >> 3, C = d / (16 * LP);                      // C: loads of a lane's half row
     for (int idx = threadIdx.x; idx < QT * 32 * P; idx += BATCH_WAVES * 64) {
         const int j = idx / P, p = idx - j * P;
         u32x4 v = {0u, 0u, 0u, 0u};
@@ -370,29 +400,35 @@ __global__ __launch_bounds__(BATCH_WAVES * 64) void flat_collect_kernel(const ui
     float thr[QT];
 #pragma unroll
     for (int t = 0; t < QT; ++t) thr[t] = t * 32 + i < nq ? ws.thr[t * 32 + i] : M::thr_shut();
-    const unsigned char* qbase = smem + (size_t)i * ldb + (size_t)h * C * 16;
+    const unsigned char* qbase = smem + (size_t)i * ldb + (size_t)h * d;           // the image of the lane's half row: d bytes in
     for (long long g = (long long)blockIdx.x * BATCH_WAVES + wave; g < ngroups; g += (long long)gridDim.x * BATCH_WAVES) {
         const long long row0 = g * gstride * 32;
         const long long mine = row0 + i < N ? row0 + i : N - 1;                     // stay in bounds; masked below
-        const Piece* src = reinterpret_cast<const Piece*>(rows + (size_t)mine * d) + (size_t)h * C;
+        const u32x4* src = reinterpret_cast<const u32x4*>(rows + (size_t)mine * (size_t)(2 * d / LP)) + (size_t)h * C;
         f32x16 acc[QT];
 #pragma unroll
         for (int t = 0; t < QT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        for (int j0 = 0; j0 < C; j0 += 8) {                                         // C % 8 == 0 (d % 128 == 0: host check)
-            Piece x[8];
+        for (int j0 = 0; j0 < C; j0 += NL) {                                        // C % NL == 0 (d % 128 == 0: host check)
+            u32x4 x[NL];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) x[j] = __builtin_nontemporal_load(src + j0 + j);
-            // the eight loads of a lane — one 128-byte line — go out back to back: spread between the MFMAs, as the scheduler
-            // would have them, a line is evicted from the vector cache between its pieces and fetched again for each
+            for (int j = 0; j < NL; ++j) x[j] = __builtin_nontemporal_load(src + j0 + j);
+            // the loads of a lane's burst — one 128-byte line of 16-bit rows — go out back to back: spread between the MFMAs, as
+            // the scheduler would have them, a line is evicted from the vector cache between its pieces and fetched again for each
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int j = 0; j < 8; ++j)
+            for (int j = 0; j < NL; ++j)
 #pragma unroll
-                for (int t = 0; t < QT; ++t) {
-                    const Piece b = *reinterpret_cast<const Piece*>(qbase + (size_t)t * 32 * ldb + (size_t)(j0 + j) * 16);
-                    acc[t] = M::mfma(x[j], b, acc[t]);
+                for (int p = 0; p < LP; ++p) {
+                    Piece a;
+                    if constexpr (LP == 1) a = __builtin_bit_cast(Piece, x[j]);
+                    else a = M::operand(x[j], p);
+#pragma unroll
+                    for (int t = 0; t < QT; ++t) {
+                        const Piece b = *reinterpret_cast<const Piece*>(qbase + (size_t)t * 32 * ldb + (size_t)((j0 + j) * LP + p) * 16);
+                        acc[t] = M::mfma(a, b, acc[t]);
+                    }
                 }
         }
         // acc[t][r]: row (r & 3) + 8 (r >> 2) + 4 h of the group, query 32 t + i
@@ -467,17 +503,18 @@ static size_t part_bytes(long long n, int d, int nq, int k) {
 }
 
 template <class M, int NQ, int MODE>
-static void launch_flat_scan(const FlatPlan& p, const unsigned char* rows, long long n, int d, const float* Q, int k, u64* part,
-                             const RowSource& src, const int* gate, hipStream_t st) {
+static void launch_flat_scan(const FlatPlan& p, const unsigned char* rows, long long n, int d, const float* Q, const float* base, int k,
+                             u64* part, const RowSource& src, const int* gate, hipStream_t st) {
     auto kern = flat_scan_kernel<M, NQ, MODE>;
     if (p.lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)p.lds);
-    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, rows, n, d, Q, k, p.cap, part, src, gate);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(256), p.lds, st, rows, n, d, Q, base, k, p.cap, part, src, gate);
 }
 
 // the exact scan, its merge (and the flip where M::FLIP) for nq queries over n items (pos == nullptr: the rows 0 .. n - 1), up to
-// MAX_NQP queries a pass: a pass carries the largest power of two of queries that is left.  workspace: part_bytes(n, d, nq, k)
+// MAX_NQP queries a pass: a pass carries the largest power of two of queries that is left.  base: the queries' base terms (M::base),
+// nullptr under a policy that has none.  workspace: part_bytes(n, d, nq, k)
 template <class M>
-static int flat_topk(const void* rows, long long n, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base,
+static int flat_topk(const void* rows, long long n, int d, const float* Q, const float* base, int nq, int k, const int64_t* ids, int64_t id_base,
                      float* outD, int64_t* outI, void* workspace, hipStream_t st, const long long* pos, const int* gate) {
     const unsigned char* rb = reinterpret_cast<const unsigned char*>(rows);
     u64* part = reinterpret_cast<u64*>(workspace);
@@ -488,16 +525,17 @@ static int flat_topk(const void* rows, long long n, int d, const float* Q, int n
         while (nqp > nq - q0) nqp >>= 1;
         const FlatPlan p = plan_flat(n, d, nqp, k);
         const float* qp = Q + (size_t)q0 * d;
+        const float* bp = base ? base + q0 : nullptr;
         if (n > 0) {
             ProfScope prof(PROF_SCAN, (double)n * (double)M::Codec::row_bytes(d), st);
             if (pos) {
-                if (nqp == 4) launch_flat_scan<M, 4, ROWS_POS>(p, rb, n, d, qp, k, part, src, gate, st);
-                else if (nqp == 2) launch_flat_scan<M, 2, ROWS_POS>(p, rb, n, d, qp, k, part, src, gate, st);
-                else launch_flat_scan<M, 1, ROWS_POS>(p, rb, n, d, qp, k, part, src, gate, st);
+                if (nqp == 4) launch_flat_scan<M, 4, ROWS_POS>(p, rb, n, d, qp, bp, k, part, src, gate, st);
+                else if (nqp == 2) launch_flat_scan<M, 2, ROWS_POS>(p, rb, n, d, qp, bp, k, part, src, gate, st);
+                else launch_flat_scan<M, 1, ROWS_POS>(p, rb, n, d, qp, bp, k, part, src, gate, st);
             } else {
-                if (nqp == 4) launch_flat_scan<M, 4, ROWS_ALL>(p, rb, n, d, qp, k, part, src, gate, st);
-                else if (nqp == 2) launch_flat_scan<M, 2, ROWS_ALL>(p, rb, n, d, qp, k, part, src, gate, st);
-                else launch_flat_scan<M, 1, ROWS_ALL>(p, rb, n, d, qp, k, part, src, gate, st);
+                if (nqp == 4) launch_flat_scan<M, 4, ROWS_ALL>(p, rb, n, d, qp, bp, k, part, src, gate, st);
+                else if (nqp == 2) launch_flat_scan<M, 2, ROWS_ALL>(p, rb, n, d, qp, bp, k, part, src, gate, st);
+                else launch_flat_scan<M, 1, ROWS_ALL>(p, rb, n, d, qp, bp, k, part, src, gate, st);
             }
             WISE_LAUNCH_CHECK("flat_scan_kernel");
         }
@@ -531,7 +569,7 @@ static size_t topk_workspace_bytes(int64_t N, int d, int nq, int k) {
 // the *_topk and *_topk_pos entry points: by_pos scans the n_pos rows pos[] of the N, else all N
 template <class M>
 static int topk_entry(const char* what, const void* rows, int64_t N, int d, bool by_pos, const int64_t* pos, int64_t n_pos, const float* Q,
-                      int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
+                      const float* base, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
                       size_t workspace_bytes, void* stream) {
     if (int rc = topk_args(what, rows, N, d, Q, nq, k, outD, outI)) return rc;
     if (by_pos)
@@ -540,7 +578,7 @@ static int topk_entry(const char* what, const void* rows, int64_t N, int d, bool
     const int64_t n = by_pos ? n_pos : N;
     const size_t need = topk_workspace_bytes(n, d, nq, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
-    return flat_topk<M>(rows, n, d, Q, nq, k, ids, id_base, outD, outI, workspace, (hipStream_t)stream,
+    return flat_topk<M>(rows, n, d, Q, base, nq, k, ids, id_base, outD, outI, workspace, (hipStream_t)stream,
                         by_pos && n_pos > 0 ? reinterpret_cast<const long long*>(pos) : nullptr, nullptr);
 }
 
@@ -565,7 +603,7 @@ static int range_args(const char* what, const void* rows, int64_t N, int d, cons
 }
 
 template <class M>
-static int range_count(const char* what, const void* rows, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
+static int range_count(const char* what, const void* rows, int64_t N, int d, const float* Q, const float* base, int nq, float radius, const uint32_t* keep,
                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = range_args(what, rows, N, d, Q, nq, radius, workspace, workspace_bytes)) return rc;
     WISE_CHECK_ARG(counts, "%s: null pointer", what);
@@ -579,11 +617,11 @@ static int range_count(const char* what, const void* rows, int64_t N, int d, con
         const dim3 grid((unsigned)ns, (unsigned)((nq + nqp - 1) / nqp));
         ProfScope prof(PROF_SCAN, (double)N * (double)M::Codec::row_bytes(d) * grid.y, st);
         if (nqp == 4)
-            hipLaunchKernelGGL((flat_range_count_kernel<M, 4>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, nq, radius, keep, hit, wstride, seg, ns);
+            hipLaunchKernelGGL((flat_range_count_kernel<M, 4>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, radius, keep, hit, wstride, seg, ns);
         else if (nqp == 2)
-            hipLaunchKernelGGL((flat_range_count_kernel<M, 2>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, nq, radius, keep, hit, wstride, seg, ns);
+            hipLaunchKernelGGL((flat_range_count_kernel<M, 2>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, radius, keep, hit, wstride, seg, ns);
         else
-            hipLaunchKernelGGL((flat_range_count_kernel<M, 1>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, nq, radius, keep, hit, wstride, seg, ns);
+            hipLaunchKernelGGL((flat_range_count_kernel<M, 1>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, radius, keep, hit, wstride, seg, ns);
         WISE_LAUNCH_CHECK("flat_range_count_kernel");
     }
     hipLaunchKernelGGL(range_scan_kernel, dim3(nq), dim3(1024), 0, st, seg, ns, reinterpret_cast<long long*>(counts));
@@ -592,7 +630,7 @@ static int range_count(const char* what, const void* rows, int64_t N, int d, con
 }
 
 template <class M>
-static int range_fill(const char* what, const void* rows, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
+static int range_fill(const char* what, const void* rows, int64_t N, int d, const float* Q, const float* base, int nq, float radius, const int64_t* ids,
                       int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
                       void* stream) {
     if (int rc = range_args(what, rows, N, d, Q, nq, radius, workspace, workspace_bytes)) return rc;
@@ -602,7 +640,7 @@ static int range_fill(const char* what, const void* rows, int64_t N, int d, cons
     const unsigned* hit = reinterpret_cast<const unsigned*>(workspace);
     const long long* seg = reinterpret_cast<const long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
     hipLaunchKernelGGL(flat_range_fill_kernel<M>, dim3((unsigned)ns, (unsigned)nq), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const unsigned char*>(rows), (long long)N, d, Q, reinterpret_cast<const long long*>(ids),
+                       reinterpret_cast<const unsigned char*>(rows), (long long)N, d, Q, base, reinterpret_cast<const long long*>(ids),
                        (long long)id_base, hit, wstride, seg, ns, reinterpret_cast<const long long*>(lims), outD,
                        reinterpret_cast<long long*>(outI));
     WISE_LAUNCH_CHECK("flat_range_fill_kernel");
@@ -628,6 +666,7 @@ static size_t batch_slot_bytes(int d, BatchSlots* ws, unsigned char* base) {
     unsigned char* eps = take((size_t)qb * 4);
     unsigned char* q2 = M::HALF_NORMS ? take((size_t)qb * 4) : nullptr;
     unsigned char* thr = take((size_t)qb * 4);
+    unsigned char* qexp = M::QUERY_EXP ? take((size_t)qb * 4) : nullptr;
     unsigned char* ctl = take((size_t)qb * 4);
     unsigned char* flag = take(4);
     unsigned char* cand = take((size_t)qb * BATCH_CAP * 4);
@@ -636,6 +675,8 @@ static size_t batch_slot_bytes(int d, BatchSlots* ws, unsigned char* base) {
         ws->eps = reinterpret_cast<float*>(eps);
         ws->q2 = reinterpret_cast<float*>(q2);
         ws->thr = reinterpret_cast<float*>(thr);
+        ws->qexp = reinterpret_cast<int*>(qexp);
+        ws->base = nullptr;
         ws->ctl = reinterpret_cast<int*>(ctl);
         ws->flag = reinterpret_cast<int*>(flag);
         ws->cand = reinterpret_cast<unsigned*>(cand);
@@ -650,7 +691,7 @@ static size_t batched_workspace_bytes(int64_t N, int d, int nq, int k) {
 }
 
 template <class M, int QT>
-static void launch_collect(const uint16_t* rows, const float* half, long long N, int d, int nq, long long ngroups, long long gstride,
+static void launch_collect(const unsigned char* rows, const float* half, long long N, int d, int nq, long long ngroups, long long gstride,
                            const BatchSlots& ws, hipStream_t st) {
     const size_t lds = (size_t)QT * 32 * (2 * d + 16);
     auto kern = flat_collect_kernel<M, QT>;
@@ -672,15 +713,17 @@ static void launch_query_blocks(const void* rows, int d, const float* Q, int nq,
 }
 
 // the *_topk_batched entry points behind their argument checks.  rows: what the exact routine scores; rows16 (and half, where
-// M::HALF_NORMS): what the collect pass streams.  workspace: batched_workspace_bytes<M>(N, d, nq, k)
+// M::HALF_NORMS): what the collect pass streams — 16-bit rows, or the 8-bit codes themselves (M::LOAD_PIECES == 2).  base: as
+// flat_topk.  workspace: batched_workspace_bytes<M>(N, d, nq, k)
 template <class M>
-static int topk_batched(const char* what, const void* rows, const uint16_t* rows16, const float* half, const float* norms, int64_t N, int d,
-                        const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
+static int topk_batched(const char* what, const void* rows, const void* rows16, const float* half, const float* norms, int64_t N, int d,
+                        const float* Q, const float* base, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
                         int32_t* counters, void* workspace, hipStream_t st) {
     BatchSlots ws;
     unsigned char* wsb = reinterpret_cast<unsigned char*>(workspace);
     void* scan_ws = wsb + batch_slot_bytes<M>(d, &ws, wsb);
     const int qb = batch_pass_queries(d);
+    const unsigned char* crows = reinterpret_cast<const unsigned char*>(rows16);
 
     // the rounds of a pass, from the shape alone: a first sample of S0 rows scored exactly, then collect rounds over shares of the
     // rows that grow by the same factor each, at most `ratio` — a round over S' rows under the threshold of a round over S rows
@@ -698,6 +741,8 @@ static int topk_batched(const char* what, const void* rows, const uint16_t* rows
     for (int q0 = 0; q0 < nq; q0 += qb) {
         const int nqa = nq - q0 < qb ? nq - q0 : qb;
         const float* Qp = Q + (size_t)q0 * d;
+        const float* bp = base ? base + q0 : nullptr;
+        ws.base = bp;
         float* oD = outD + (size_t)q0 * k;
         int64_t* oI = outI + (size_t)q0 * k;
         {
@@ -719,10 +764,10 @@ static int topk_batched(const char* what, const void* rows, const uint16_t* rows
                 gstride = full_groups / groups;
             }
             {
-                ProfScope prof(PROF_SCAN, (double)groups * 32 * d * 2.0, st);
-                if (qt == 4) launch_collect<M, 4>(rows16, half, N, d, nqa, groups, gstride, ws, st);
-                else if (qt == 2) launch_collect<M, 2>(rows16, half, N, d, nqa, groups, gstride, ws, st);
-                else launch_collect<M, 1>(rows16, half, N, d, nqa, groups, gstride, ws, st);
+                ProfScope prof(PROF_SCAN, (double)groups * 32 * d * 2.0 / M::LOAD_PIECES, st);
+                if (qt == 4) launch_collect<M, 4>(crows, half, N, d, nqa, groups, gstride, ws, st);
+                else if (qt == 2) launch_collect<M, 2>(crows, half, N, d, nqa, groups, gstride, ws, st);
+                else launch_collect<M, 1>(crows, half, N, d, nqa, groups, gstride, ws, st);
             }
             WISE_LAUNCH_CHECK("flat_collect_kernel");
             launch_query_blocks<M, ROWS_CAND>(rows, d, Qp, nqa, k, 0, 1, ws, last ? 1 : 0, ids, id_base, oD, oI, st);
@@ -733,7 +778,7 @@ static int topk_batched(const char* what, const void* rows, const uint16_t* rows
             WISE_LAUNCH_CHECK("flat_pass_counters_kernel");
         }
         // the exact scan, gated on the flag: returns at once unless a list overflowed
-        if (int rc = flat_topk<M>(rows, N, d, Qp, nqa, k, ids, id_base, oD, oI, scan_ws, st, nullptr, ws.flag)) return rc;
+        if (int rc = flat_topk<M>(rows, N, d, Qp, bp, nqa, k, ids, id_base, oD, oI, scan_ws, st, nullptr, ws.flag)) return rc;
     }
     return WISE_OK;
 }

@@ -122,7 +122,7 @@ __device__ __forceinline__ float threshold_below(float t, float eps) {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // THE POLICY (flat_codec_scan.h): the score is the inner product itself, larger is better
-struct MetricIP16 {
+struct MetricIP16 : PlainPolicy {
     using Codec = Codec16;
     static constexpr float PAD = -3.4028234663852886e38f;
     static constexpr bool FLIP = false;
@@ -157,14 +157,14 @@ extern "C" size_t wise_ipsqfp16_topk_workspace_bytes(int64_t N, int d, int nq, i
 
 extern "C" int wise_ipsq16_topk(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids,
                                 int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
-    return topk_entry<MetricIP16>("ipsq16_topk", rows, N, d, false, nullptr, 0, Q, nq, k, ids, id_base, outD, outI, workspace,
+    return topk_entry<MetricIP16>("ipsq16_topk", rows, N, d, false, nullptr, 0, Q, nullptr, nq, k, ids, id_base, outD, outI, workspace,
                                   workspace_bytes, stream);
 }
 
 extern "C" int wise_ipsq16_topk_pos(const uint16_t* rows, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq,
                                     int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    return topk_entry<MetricIP16>("ipsq16_topk_pos", rows, N, d, true, pos, n_pos, Q, nq, k, ids, id_base, outD, outI, workspace,
+    return topk_entry<MetricIP16>("ipsq16_topk_pos", rows, N, d, true, pos, n_pos, Q, nullptr, nq, k, ids, id_base, outD, outI, workspace,
                                   workspace_bytes, stream);
 }
 
@@ -172,13 +172,13 @@ extern "C" size_t wise_ipsqfp16_range_workspace_bytes(int64_t N, int d, int nq) 
 
 extern "C" int wise_ipsq16_range_count(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
                                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    return range_count<MetricIP16>("ipsq16_range_count", rows, N, d, Q, nq, radius, keep, counts, workspace, workspace_bytes, stream);
+    return range_count<MetricIP16>("ipsq16_range_count", rows, N, d, Q, nullptr, nq, radius, keep, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int wise_ipsq16_range_fill(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
                                       int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-    return range_fill<MetricIP16>("ipsq16_range_fill", rows, N, d, Q, nq, radius, ids, id_base, lims, outD, outI, workspace,
+    return range_fill<MetricIP16>("ipsq16_range_fill", rows, N, d, Q, nullptr, nq, radius, ids, id_base, lims, outD, outI, workspace,
                                   workspace_bytes, stream);
 }
 
@@ -224,6 +224,6 @@ extern "C" int wise_ipsq16_topk_batched(const uint16_t* rows, const float* norms
     WISE_CHECK_ARG(norms, "ipsq16_topk_batched: null pointer");
     const size_t need = wise_ipsqfp16_topk_batched_workspace_bytes(N, d, nq, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "ipsq16_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
-    return topk_batched<MetricIP16>("ipsq16_topk_batched", rows, rows, nullptr, norms, N, d, Q, nq, k, ids, id_base, outD, outI, counters,
+    return topk_batched<MetricIP16>("ipsq16_topk_batched", rows, rows, nullptr, norms, N, d, Q, nullptr, nq, k, ids, id_base, outD, outI, counters,
                                     workspace, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 // bins of the range [vmin[i], vmin[i] + vdiff[i]] the trainer saw.  One range per dimension, shared by all lists; no codebooks
 // and no per-query table.
 //   wise_sq_train    per-dimension min and range of the training residuals (exact: order does not matter)
+//   wise_sq_minmax   the same reduction as a running per-dimension minimum and maximum over chunks of rows (IndexSQ8bit)
 //   wise_sq_encode   code_i = clamp(floor((r_i - vmin[i]) * (255 / vdiff[i])), 0, 255), evaluated in double
 //   wise_sq_query    per query the weight row w[i] = q_i vdiff[i] / 255 and q0 = sum_i q_i (vmin[i] + vdiff[i] 0.5 / 255)
 //   wise_sq_decode   reconstruct_batch: c_l + vmin + vdiff (code + 0.5) / 255 (faiss Codec8bit)
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(256) void train_init_kernel(unsigned* __restrict__ 
 
 // block = (64 columns, a stride of rows); thread (column, row phase).  min / max are exact, so neither the order of the rows nor
 // that of the atomics changes a bit of the result.
-__global__ __launch_bounds__(256) void train_minmax_kernel(const float* __restrict__ r, long long n, int d, unsigned* __restrict__ cells) {
+__global__ __launch_bounds__(256) void train_minmax_kernel(const float* __restrict__ r, long long n, int d, unsigned* __restrict__ mincells,
+                                                           unsigned* __restrict__ maxcells) {
     __shared__ unsigned smin[4][64], smax[4][64];
     const int cx = threadIdx.x & 63, ry = threadIdx.x >> 6;
     const int col = blockIdx.x * 64 + cx;
@@ -73,8 +75,8 @@ __global__ __launch_bounds__(256) void train_minmax_kernel(const float* __restri
             mn = smin[y][cx] < mn ? smin[y][cx] : mn;
             mx = smax[y][cx] > mx ? smax[y][cx] : mx;
         }
-        atomicMin(&cells[col], mn);
-        atomicMax(&cells[d + col], mx);
+        atomicMin(&mincells[col], mn);
+        atomicMax(&maxcells[col], mx);
     }
 }
 
@@ -86,6 +88,22 @@ __global__ __launch_bounds__(256) void train_finish_kernel(float* __restrict__ t
     const float mn = f32_unorder(cells[i]), mx = f32_unorder(cells[d + i]);
     trained[i] = mn;
     trained[d + i] = mx - mn;
+}
+
+// wise_sq_minmax: lo / hi are used as ordered-unsigned cells while train_minmax_kernel runs.  open: the cells of what the arrays
+// hold (accumulate) or of +3.4028235e38 / -3.4028235e38, the minimum and maximum of no rows; close: back to floats
+__global__ __launch_bounds__(256) void minmax_open_kernel(float* __restrict__ lo, float* __restrict__ hi, int d, int accumulate) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d) return;
+    const float a = accumulate ? lo[i] : 3.4028234663852886e38f, b = accumulate ? hi[i] : -3.4028234663852886e38f;
+    reinterpret_cast<unsigned*>(lo)[i] = f32_order(a);
+    reinterpret_cast<unsigned*>(hi)[i] = f32_order(b);
+}
+__global__ __launch_bounds__(256) void minmax_close_kernel(float* __restrict__ lo, float* __restrict__ hi, int d) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= d) return;
+    lo[i] = f32_unorder(reinterpret_cast<const unsigned*>(lo)[i]);
+    hi[i] = f32_unorder(reinterpret_cast<const unsigned*>(hi)[i]);
 }
 
 // thread = one value
@@ -413,10 +431,28 @@ extern "C" int wise_sq_train(const float* resid, int64_t n, int d, float* traine
     WISE_LAUNCH_CHECK("sq train_init_kernel");
     long long slabs = (n + 3) / 4;
     if (slabs > 1024) slabs = 1024;
-    hipLaunchKernelGGL(train_minmax_kernel, dim3((d + 63) / 64, (unsigned)slabs), dim3(256), 0, st, resid, (long long)n, d, cells);
+    hipLaunchKernelGGL(train_minmax_kernel, dim3((d + 63) / 64, (unsigned)slabs), dim3(256), 0, st, resid, (long long)n, d, cells, cells + d);
     WISE_LAUNCH_CHECK("sq train_minmax_kernel");
     hipLaunchKernelGGL(train_finish_kernel, dim3((d + 255) / 256), dim3(256), 0, st, trained, d);
     WISE_LAUNCH_CHECK("sq train_finish_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_sq_minmax(const float* rows, int64_t n, int d, float* lo, float* hi, int accumulate, void* stream) {
+    SQ_CHECK_SHAPE("sq_minmax");
+    WISE_CHECK_ARG(n >= 0 && lo && hi && lo != hi && (rows || n == 0), "sq_minmax: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(minmax_open_kernel, dim3((d + 255) / 256), dim3(256), 0, st, lo, hi, d, accumulate);
+    WISE_LAUNCH_CHECK("sq minmax_open_kernel");
+    if (n > 0) {
+        long long slabs = (n + 3) / 4;
+        if (slabs > 1024) slabs = 1024;
+        hipLaunchKernelGGL(train_minmax_kernel, dim3((d + 63) / 64, (unsigned)slabs), dim3(256), 0, st, rows, (long long)n, d,
+                           reinterpret_cast<unsigned*>(lo), reinterpret_cast<unsigned*>(hi));
+        WISE_LAUNCH_CHECK("sq train_minmax_kernel");
+    }
+    hipLaunchKernelGGL(minmax_close_kernel, dim3((d + 255) / 256), dim3(256), 0, st, lo, hi, d);
+    WISE_LAUNCH_CHECK("sq minmax_close_kernel");
     return WISE_OK;
 }
 

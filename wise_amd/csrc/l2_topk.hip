@@ -120,7 +120,7 @@ __device__ __forceinline__ float threshold_above(float t, float q2, float eps) {
 }
 
 // THE POLICY (flat_codec_scan.h): the keys order the negated distance, smaller distances are better
-struct MetricL2 {
+struct MetricL2 : PlainPolicy {
     using Codec = CodecL2;
     static constexpr float PAD = 3.4028234663852886e38f;
     static constexpr bool FLIP = true;
@@ -160,14 +160,14 @@ extern "C" size_t wise_l2_topk_workspace_bytes(int64_t N, int d, int nq, int k) 
 
 extern "C" int wise_l2_topk_f32(const float* X, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base,
                                 float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
-    return topk_entry<MetricL2>("l2_topk_f32", X, N, d, false, nullptr, 0, Q, nq, k, ids, id_base, outD, outI, workspace, workspace_bytes,
+    return topk_entry<MetricL2>("l2_topk_f32", X, N, d, false, nullptr, 0, Q, nullptr, nq, k, ids, id_base, outD, outI, workspace, workspace_bytes,
                                 stream);
 }
 
 extern "C" int wise_l2_topk_pos_f32(const float* X, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq, int k,
                                     const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace,
                                     size_t workspace_bytes, void* stream) {
-    return topk_entry<MetricL2>("l2_topk_pos_f32", X, N, d, true, pos, n_pos, Q, nq, k, ids, id_base, outD, outI, workspace,
+    return topk_entry<MetricL2>("l2_topk_pos_f32", X, N, d, true, pos, n_pos, Q, nullptr, nq, k, ids, id_base, outD, outI, workspace,
                                 workspace_bytes, stream);
 }
 
@@ -175,13 +175,13 @@ extern "C" size_t wise_l2_range_workspace_bytes(int64_t N, int d, int nq) { retu
 
 extern "C" int wise_l2_range_count_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
                                        int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    return range_count<MetricL2>("l2_range_count_f32", X, N, d, Q, nq, radius, keep, counts, workspace, workspace_bytes, stream);
+    return range_count<MetricL2>("l2_range_count_f32", X, N, d, Q, nullptr, nq, radius, keep, counts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int wise_l2_range_fill_f32(const float* X, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
                                       int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace,
                                       size_t workspace_bytes, void* stream) {
-    return range_fill<MetricL2>("l2_range_fill_f32", X, N, d, Q, nq, radius, ids, id_base, lims, outD, outI, workspace, workspace_bytes,
+    return range_fill<MetricL2>("l2_range_fill_f32", X, N, d, Q, nullptr, nq, radius, ids, id_base, lims, outD, outI, workspace, workspace_bytes,
                                 stream);
 }
 
@@ -213,6 +213,6 @@ extern "C" int wise_l2_topk_batched(const float* X, const uint16_t* Xb, const fl
     WISE_CHECK_ARG(((uintptr_t)Xb & 15) == 0 && ((uintptr_t)half & 3) == 0, "l2_topk_batched: Xb must be 16-byte aligned");
     const size_t need = wise_l2_topk_batched_workspace_bytes(N, d, nq, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "l2_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
-    return topk_batched<MetricL2>("l2_topk_batched", X, Xb, half, norms, N, d, Q, nq, k, ids, id_base, outD, outI, counters, workspace,
+    return topk_batched<MetricL2>("l2_topk_batched", X, Xb, half, norms, N, d, Q, nullptr, nq, k, ids, id_base, outD, outI, counters, workspace,
                                   (hipStream_t)stream);
 }

@@ -34,7 +34,8 @@ __device__ __forceinline__ float chain_halves(float s, unsigned word, float wa, 
 // s_c.  Everything else — the lanes of a wave-load, the fold over the chunks, the list walk, the selection, the range passes — is
 // written once and takes the codec as a template parameter; it never branches on it.
 //   Codec8   IndexIVFSQ8: d bytes a row.  Chunk c is bytes 16 c .. 16 c + 15, ONE 16-byte load; the weights are W[q, 16 c ..] of
-//            wise_sq_query and the score's base is bias + q0.
+//            wise_sq_query and the score's base is bias + q0.  IndexSQ8bit (ip_sq8.hip) scans the same codes without lists: the
+//            same loads, weights and chain, and the base is q0 alone (its policy's score()).
 //   Codec16  IndexIVFSQfp16: d binary16 values a row, 2 d bytes = 2 C 16-byte pieces.  Chunk c is piece c and piece c + C, i.e.
 //            elements 8 c .. 8 c + 7 (i = 0 .. 7 of the chain) and d / 2 + 8 c .. d / 2 + 8 c + 7 (i = 8 .. 15): each of the TWO
 //            load instructions of a wave-load then reads, per row, C consecutive pieces — a contiguous run of d bytes — and whole

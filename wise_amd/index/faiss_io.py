@@ -82,6 +82,19 @@ A bare 'IxSQ' file (no id map) reads with ids equal to positions.  index_fourcc(
 wraps ('IxFI' or 'IxSQ'); read_index / read_index_range / index_ntotal serve this file too (dict(halves, ids)), and write_index
 writes it for a state of 'halves' and 'ids' alone.  A rank's part of a row-sharded index is a complete file of its rows.
 
+The file of index type 'IndexSQ8bit' (write_idmap_sq8_ip / read_idmap_sq8_ip, _range, idmap_sq8_ip_ntotal) is the same 'IxMp' around
+'IxSQ' with faiss's QT_8bit record, RS_minmax with argument 0:
+
+    u32  'IxMp' | header | u32 'IxSQ' | header    as above
+    i32  qtype (0 = QT_8bit) | i32 rangestat (0) | f32 rangestat_arg (0) | u64 d | u64 code_size (= d)
+    u64  2d | f32[2d]                             the trained vector: vmin [d], then vdiff [d]
+    u64  n_bytes (= ntotal*d) | u8[ntotal*d]      the codes vector: one byte per dimension
+    u64  ntotal | i64[ntotal]                     id_map
+
+The record's qtype tells the two 'IxSQ' files apart (flat_sq_qtype); every field is validated per qtype, so a record that says qtype 0
+with code_size 2d or without trained values is refused by file name, and neither reader takes the other's file.  read_index gives
+dict(trained, codes, ids), and write_index writes the file for a state of 'trained', 'codes' and 'ids' without 'centroids'.
+
 The file of index type 'IndexFlatL2' (write_idmap_flat_l2 / read_idmap_flat_l2, _range, idmap_flat_l2_ntotal) is the flat file at the
 top with faiss's IndexFlatL2 in the place of the IndexFlatIP: the inner fourcc is 'IxF2' and metric_type is 1 (METRIC_L2) in both
 headers; everything else is the 'IxFI' layout, a bare 'IxF2' file reads with ids equal to positions, and _flat_head refuses by name
@@ -159,6 +172,7 @@ class _FlatHead(NamedTuple):
     off: int             # byte offset of the payload
     dtype: object        # of a payload value
     idmap: bool          # an id map follows the payload (else ids are the positions)
+    trained: object = None   # [2d] float32 of an 'IxSQ' record of QT_8bit (vmin, then vdiff); None for every other flat file
 
 
 _FLAT_HEAD_BYTES = 4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8     # the most a flat head takes: both headers with a metric_arg
@@ -177,9 +191,9 @@ def _flat_outer(head: bytes):
     return cc, inner, off + 4, d0, n0
 
 
-def _flat_head(p, want: str) -> _FlatHead:
+def _flat_head(p, want: str, qtype_want: int = QT_FP16) -> _FlatHead:
     """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxF2' / 'IxSQ'), bare or inside 'IxMp'.  RuntimeError naming
-    the file for anything else, a metric_type that is not the fourcc's ('IxFI': 0, 'IxF2': 1, in either header), a ScalarQuantizer record other than QT_fp16 / code_size 2d, a payload length that is not n x d
+    the file for anything else, a metric_type that is not the fourcc's ('IxFI': 0, 'IxF2': 1, in either header), a ScalarQuantizer record other than the one asked for (qtype_want: QT_fp16 with code_size 2d and no trained value, or QT_8bit with code_size d and 2d trained values), a payload length that is not n x d
     values, or a file shorter than its header promises."""
     size = p.stat().st_size
     with open(p, "rb") as f:
@@ -201,14 +215,36 @@ def _flat_head(p, want: str) -> _FlatHead:
         if want == "IxSQ":
             qtype, rangestat, rangestat_arg, dsq, code_size, ntrained = struct.unpack_from("<iifQQQ", head, off)
             off += 36
+            if qtype_want == QT_8BIT and qtype == QT_8BIT and 0 < ntrained == 2 * d <= 2 * 65536:
+                # the trained values stand between the record and the payload's length: read on from the file
+                with open(p, "rb") as f:
+                    f.seek(off)
+                    trained = np.fromfile(f, dtype="<f4", count=int(ntrained))
+                    tail = f.read(8)
+                if trained.size != ntrained or len(tail) != 8:
+                    raise struct.error("the trained values end early")
+                off += 4 * int(ntrained)
+                head = head[:off].ljust(off, b"\0") + tail
         (count,) = struct.unpack_from("<Q", head, off)
         off += 8
     except struct.error as e:
-        raise RuntimeError(f"{p}: the head of an {_FLAT_NAMES[want]} file is cut short ({e})") from None
+        name = "IndexSQ8bit" if want == "IxSQ" and qtype_want == QT_8BIT else _FLAT_NAMES[want]
+        raise RuntimeError(f"{p}: the head of an {name} file is cut short ({e})") from None
     if want in _FLAT_METRIC and (metric != _FLAT_METRIC[want] or (idmap and metric0 != _FLAT_METRIC[want])):
         raise RuntimeError(f"{p}: an {_FLAT_NAMES[want]} file ('{want}') with metric_type {metric}"
                            + (f" under an IndexIDMap of metric_type {metric0}" if idmap else "")
                            + f": {_FLAT_NAMES[want]} is metric_type {_FLAT_METRIC[want]}")
+    if want == "IxSQ" and qtype_want == QT_8BIT:
+        if qtype != QT_8BIT or d < 1 or dsq != d or code_size != d or ntrained != 2 * d or (idmap and (d0 != d or n0 != n)):
+            raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, "
+                               f"code_size={code_size}, {ntrained} trained values): an IndexSQ8bit file is qtype 0 (QT_8bit) with "
+                               f"code_size d and 2 d trained values")
+        if n < 0 or count != n * d:
+            raise RuntimeError(f"{p}: {count} code bytes for {n} x {d} 8-bit codes")
+        need = off + n * d + ((8 + 8 * n) if idmap else 0)
+        if size < need:
+            raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {need} promised by its header)")
+        return _FlatHead(want, int(d), int(n), int(off), np.dtype(np.uint8), idmap, trained.astype(np.float32))
     if want == "IxSQ":
         if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
             raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, "
@@ -909,6 +945,80 @@ def _read_sq16_state_range(path, lo, hi):
     return {"halves": H, "ids": ids}
 
 
+# ---------------------------------------------------------------------------------------------- 'IxMp' around 'IxSQ': 8-bit codes
+def write_idmap_sq8_ip(path, trained: np.ndarray, codes: np.ndarray, ids: np.ndarray) -> None:
+    """trained [2d] float32 (vmin, then vdiff), codes [n,d] uint8, ids [n] int64: IndexIDMap around IndexScalarQuantizer(d, QT_8bit,
+    inner product) with RS_minmax, argument 0 — faiss's layout of index type 'IndexSQ8bit'."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    trained = np.ascontiguousarray(trained, dtype="<f4").reshape(-1)
+    n, d = codes.shape
+    assert ids.shape == (n,) and trained.shape == (2 * d,)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<I", _fourcc("IxMp")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<I", _fourcc("IxSQ")))
+        f.write(_header(d, n))
+        f.write(struct.pack("<iifQQ", QT_8BIT, 0, 0.0, d, d))          # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
+        f.write(struct.pack("<Q", 2 * d))
+        trained.tofile(f)
+        f.write(struct.pack("<Q", n * d))                        # codes
+        codes.tofile(f)
+        f.write(struct.pack("<Q", n))
+        ids.tofile(f)
+
+
+def read_idmap_sq8_ip(path, mmap: bool = True):
+    """-> (trained [2d] float32, codes [n,d] uint8 (a memmap view unless mmap is False), ids int64[n]) of an IndexSQ8bit file; a bare
+    'IxSQ' file (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated or foreign file — an
+    IndexSQfp16 file (qtype 4) among them."""
+    p = _existing(path)
+    head = _flat_head(p, "IxSQ", QT_8BIT)
+    return head.trained, _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
+
+
+def read_idmap_sq8_ip_range(path, lo: int, hi: int):
+    """(trained, codes, ids) with rows [lo, hi) of what read_idmap_sq8_ip returns, reading only those rows and ids (one rank's
+    shard_range of the file); the ranges are whole."""
+    p = _existing(path)
+    head = _flat_head(p, "IxSQ", QT_8BIT)
+    lo, hi = int(lo), int(hi)
+    if not (0 <= lo <= hi <= head.n):
+        raise ValueError(f"read_idmap_sq8_ip_range: [{lo}, {hi}) outside [0, {head.n}]")
+    C = np.fromfile(p, dtype=np.uint8, count=(hi - lo) * head.d, offset=head.off + lo * head.d).reshape(hi - lo, head.d)
+    return head.trained, C, _flat_ids(p, head, lo, hi)
+
+
+def idmap_sq8_ip_ntotal(path) -> int:
+    """Rows of an IndexSQ8bit file (its header)."""
+    return _flat_head(_existing(path), "IxSQ", QT_8BIT).n
+
+
+def flat_sq_qtype(path):
+    """qtype of the ScalarQuantizer record of an 'IxSQ' file, bare or inside 'IxMp' (0: IndexSQ8bit, 4: IndexSQfp16); None where the
+    file is no such file or ends before it."""
+    with open(path, "rb") as f:
+        head = f.read(_FLAT_HEAD_BYTES)
+    try:
+        _, inner, off, _, _ = _flat_outer(head)
+        if inner != _fourcc("IxSQ"):
+            return None
+        _, _, _, off = _read_header(head, off)
+        return struct.unpack_from("<i", head, off)[0]
+    except struct.error:
+        return None
+
+
+def _read_sq8_state(path):
+    trained, C, ids = read_idmap_sq8_ip(path, mmap=False)
+    return {"trained": trained, "codes": C, "ids": ids}
+
+
+def _read_sq8_state_range(path, lo, hi):
+    trained, C, ids = read_idmap_sq8_ip_range(path, lo, hi)
+    return {"trained": trained, "codes": C, "ids": ids}
+
+
 # ---------------------------------------------------------------------------------------------- any IVF file, by its fourcc
 _BY_FOURCC = {                                    # fourcc -> (reader, range reader, ntotal)
     "IwFl": (read_ivf_flat_ip, read_ivf_flat_ip_range, ivf_flat_ip_ntotal),
@@ -917,6 +1027,7 @@ _BY_FOURCC = {                                    # fourcc -> (reader, range rea
     "WiOP": (read_ivf_opq_ip, read_ivf_opq_ip_range, ivf_opq_ip_ntotal),
     "IwSq": (read_ivf_sq_ip, read_ivf_sq_ip_range, ivf_sq_ip_ntotal),
     "IxSQ": (_read_sq16_state, _read_sq16_state_range, idmap_sq16_ip_ntotal),      # IndexSQfp16: no lists, dict(halves, ids)
+    "IxSQ/8": (_read_sq8_state, _read_sq8_state_range, idmap_sq8_ip_ntotal),      # IndexSQ8bit: no lists, dict(trained, codes, ids)
 }
 
 
@@ -925,9 +1036,11 @@ def _by_fourcc(path, which: int):
     cc = index_fourcc(p)
     if cc == "IxMp" and index_fourcc(p, inner=True) == "IxSQ":
         cc = "IxSQ"
+    if cc == "IxSQ" and flat_sq_qtype(p) == QT_8BIT:         # the record's qtype tells the two 'IxSQ' files apart
+        cc = "IxSQ/8"
     if cc not in _BY_FOURCC:
-        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(k for k in _BY_FOURCC if k != 'IxSQ')}) "
-                           f"nor an IndexSQfp16 file ('IxSQ', bare or inside 'IxMp')")
+        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(k for k in _BY_FOURCC if not k.startswith('IxSQ'))}) "
+                           f"nor an IndexSQfp16 file ('IxSQ', bare or inside 'IxMp') nor an IndexSQ8bit file (the same with qtype 0)")
     return _BY_FOURCC[cc][which]
 
 
@@ -950,9 +1063,11 @@ def index_ntotal(path) -> int:
 def write_index(path, state, nprobe=None) -> None:
     """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
     'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl'; 'halves'
-    without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ').  nprobe: state's own unless given."""
+    without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ'), 'trained' without 'centroids' the IndexSQ8bit file.  nprobe: state's own unless given."""
     if "halves" in state and "centroids" not in state:       # IndexSQfp16: rows and ids, no lists
         return write_idmap_sq16_ip(path, state["halves"], state["ids"])
+    if "trained" in state and "centroids" not in state:      # IndexSQ8bit: ranges, codes and ids, no lists
+        return write_idmap_sq8_ip(path, state["trained"], state["codes"], state["ids"])
     nprobe = state.get("nprobe", 1) if nprobe is None else nprobe
     lists = (state["ids"], state["list_off"])
     store = {k: state[k] for k in ("kind", "k_factor", "rows", "scales") if k in state}

@@ -33,6 +33,14 @@ factory attribute, the shape check, the file's payload, its writer and reader, a
     IndexFlatIP                      FlatIPIndex                                 the fp32 row                                            'IxMp' around 'IxFI' (faiss)
     IndexSQfp16                      FlatSQfp16IPIndex                           d binary16 values, 2 d bytes, no fp32 rows              'IxMp' around 'IxSQ' (faiss), qtype 4
     IndexFlatL2 (flat_l2.py)         FlatL2Index                                 the fp32 row; squared-L2 distances, ascending           'IxMp' around 'IxF2' (faiss), metric_type 1
+    IndexSQ8bit                      FlatSQ8IPIndex                              d code bytes (QT_8bit) under ranges [2d]: vmin, vdiff   'IxMp' around 'IxSQ' (faiss), qtype 0
+
+IndexSQ8bit is the one exhaustive type that carries a trained vector: create_index trains its ranges over EVERY row of the store (a
+minimum and a maximum per dimension are exact and order-free, so nothing clamps at build), encodes the rows on the GPU and writes
+ranges, codes and ids; load_index hands the file's ranges to the index before its codes; update_index adds against the ranges as
+trained (values outside them clamp).  Under a process group the ranks all-reduce their minima and maxima (MIN / MAX) so that every
+part holds the one-process build's ranges — a rank whose store slice is empty contributes +max / -max and writes an empty part — and
+the skip-if-exists decision is collective for this type (an all-reduce of "my part exists", as for the sharded IVF build).
 
 The classes are one row store and one shared surface (flat_common.py) around their own payload and search.  Wherever IndexFlatIP
 is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
@@ -86,7 +94,7 @@ from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .flat_l2 import FlatL2Index, check_shape as check_flat_l2_shape
-from .flat_sq import FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape
+from .flat_sq import FlatSQ8IPIndex, FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape, check_sq8_shape
 from .ivf_flat import IVFFlatIPIndex, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
@@ -251,7 +259,7 @@ def _host_state(index, fam):
 def _unknown_index_type(index_type):
     return NotImplementedError(f'{index_type}: IndexFlatIP, IndexIVFFlat and IndexIVFPQ<m> (with its R8 / R16 and '
                                f'IndexIVFOPQ<m> forms) and IndexIVFSQ8 are the index types WISE builds, and IndexIVFSQfp16, '
-                               f'and IndexSQfp16, and IndexFlatL2')
+                               f'and IndexSQ8bit, and IndexSQfp16, and IndexFlatL2')
 
 
 def _to_halves(X):
@@ -268,19 +276,24 @@ class _FlatType:
     fourcc: str          # of the index inside the file's id map (faiss_io.index_fourcc(fn, inner=True))
     dtype: type          # of a value of the file's payload, which is the index's own rows_host()[0]
     encode: Callable     # store rows [n,d] float32 -> that payload, on the host
-    writer: Callable     # (path, payload, ids) -> the file
-    reader: Callable     # path -> (payload [N,d], memory-mapped; ids [N])
+    writer: Callable     # (path, payload, ids) -> the file; a trained type: (path, trained, payload, ids)
+    reader: Callable     # path -> (payload [N,d], memory-mapped; ids [N]); a trained type: (trained [2d], payload, ids)
     add: str             # the index method that takes rows of the file's payload and their ids
     metric: str = 'ip'   # the index object's `metric` (flat_common.py): tells the types apart that share a payload dtype
+    qtype: int = None    # of the file's ScalarQuantizer record, which tells the 'IxSQ' files apart (faiss_io.flat_sq_qtype)
+    trained: bool = False  # the type carries a trained vector [2d] (vmin, vdiff): the index has minmax / set_minmax / set_trained /
+    #                        trained_host, the build goes through the index object (encode is unused), and the file holds the vector
 
 
 FLAT_TYPES = {
     'IndexFlatIP': _FlatType('flat_index_factory', None, 'IxFI', np.float32, lambda X: X, faiss_io.write_idmap_flat_ip,
                              faiss_io.read_idmap_flat_ip, 'add_with_ids'),
     'IndexSQfp16': _FlatType('flat_sqfp16_index_factory', check_sqfp16_flat_shape, 'IxSQ', np.float16, _to_halves,
-                             faiss_io.write_idmap_sq16_ip, faiss_io.read_idmap_sq16_ip, 'add_halves_with_ids'),
+                             faiss_io.write_idmap_sq16_ip, faiss_io.read_idmap_sq16_ip, 'add_halves_with_ids', qtype=faiss_io.QT_FP16),
     'IndexFlatL2': _FlatType('flat_l2_index_factory', check_flat_l2_shape, 'IxF2', np.float32, lambda X: X, faiss_io.write_idmap_flat_l2,
                              faiss_io.read_idmap_flat_l2, 'add_with_ids', metric='l2'),
+    'IndexSQ8bit': _FlatType('flat_sq8_index_factory', check_sq8_shape, 'IxSQ', np.uint8, None, faiss_io.write_idmap_sq8_ip,
+                             faiss_io.read_idmap_sq8_ip, 'add_codes_with_ids', qtype=faiss_io.QT_8BIT, trained=True),
 }
 
 
@@ -325,6 +338,7 @@ class FeatureSearchIndex(SearchIndex):
     flat_index_factory = FlatIPIndex
     flat_sqfp16_index_factory = FlatSQfp16IPIndex
     flat_l2_index_factory = FlatL2Index
+    flat_sq8_index_factory = FlatSQ8IPIndex
     ivf_index_factory = IVFFlatIPIndex
     ivfpq_index_factory = IVFPQIPIndex
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
@@ -367,7 +381,7 @@ class FeatureSearchIndex(SearchIndex):
         if sharded and (index_type in FLAT_TYPES or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
         exists = index_fn.exists()
-        if sharded_ivf:                             # the build is collective: every rank takes the same decision
+        if sharded_ivf or (sharded and flat is not None and flat.trained):   # the build is collective: every rank takes the same decision
             import torch
             import torch.distributed as dist
             flag = torch.tensor([int(exists)], dtype=torch.int64, device=_coll_device())
@@ -408,9 +422,30 @@ class FeatureSearchIndex(SearchIndex):
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
             faiss_io.write_index(index_fn, _host_state(ivf, fam), nprobe=ivf.nprobe)
+        elif flat.trained:
+            self._create_trained_flat(flat, X, ids, index_fn, sharded)
         else:
             flat.writer(index_fn, flat.encode(X), ids)
         print(f'  saved index to {index_fn}')
+
+    def _create_trained_flat(self, flat, X, ids, index_fn, sharded):
+        """The build of an exhaustive type with a trained vector (IndexSQ8bit): the ranges over EVERY row — under a process group
+        over every rank's rows, one MIN and one MAX all-reduce of the ranks' own minima and maxima; a rank without rows contributes
+        +max / -max — then this rank's rows encoded by the index object, and its file.  Collective when sharded."""
+        index = getattr(self, flat.factory)(X.shape[1])
+        lohi = index.minmax(X)
+        if sharded:
+            import torch.distributed as dist
+            lohi = lohi.to(_coll_device())
+            lo, hi = lohi[0].contiguous(), lohi[1].contiguous()
+            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            lohi[0], lohi[1] = lo, hi
+        index.set_minmax(lohi)
+        index.reserve(X.shape[0])
+        for s0 in range(0, X.shape[0], 1 << 20):
+            index.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
+        self._write_index_file(index, index_fn)
 
     def _create_sharded_ivf(self, X, ids, part_fn, rank, world, index_type, fam, pq_m=None, kind=None):
         """The collective IVF build of create_index (module docstring): X / ids are this rank's store rows, fam the family of
@@ -565,17 +600,22 @@ class FeatureSearchIndex(SearchIndex):
 
     def _index_from_file(self, fn, shard=None):
         """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
-        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16, an
+        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16 or, where
+        its ScalarQuantizer record says qtype 0, an IndexSQ8bit, an
         'IxF2' file an IndexFlatL2;
         anything else that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
         shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
         if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
             return self._local_index(faiss_io.read_index(fn))[1]
         inner = faiss_io.index_fourcc(fn, inner=True) if fn.exists() else None
-        flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner), FLAT_TYPES['IndexFlatIP'])
-        rows, ids = flat.reader(fn)                  # rows memory-mapped: only [lo, hi) is ever touched
+        qtype = faiss_io.flat_sq_qtype(fn) if inner == 'IxSQ' else None       # the two 'IxSQ' files differ in their record's qtype
+        flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner and t.qtype == qtype),
+                    FLAT_TYPES['IndexSQfp16' if inner == 'IxSQ' else 'IndexFlatIP'])       # (whose reader refuses the file by name)
+        *trained, rows, ids = flat.reader(fn)        # rows memory-mapped: only [lo, hi) is ever touched
         lo, hi = shard_range(rows.shape[0], *shard) if shard is not None else (0, rows.shape[0])
         index = getattr(self, flat.factory)(rows.shape[1])
+        if flat.trained:                             # the ranges are whole on every rank
+            index.set_trained(trained[0][:rows.shape[1]], trained[0][rows.shape[1]:])
         index.reserve(hi - lo)                       # one [n,d] device tensor, filled slice by slice
         add = getattr(index, flat.add)               # binary16 rows go to HBM as they are: nothing is converted
         for s in range(lo, hi, 1 << 20):             # stream the memory-mapped rows into HBM
@@ -593,6 +633,8 @@ class FeatureSearchIndex(SearchIndex):
         flat = next((t for t in FLAT_TYPES.values() if t.dtype == payload.dtype and t.metric == metric), None)
         if flat is None:
             raise TypeError(f'{type(index).__name__}: no index file format')
+        if flat.trained:
+            return flat.writer(fn, np.concatenate(index.trained_host()), payload, ids)
         flat.writer(fn, payload, ids)
 
     def update_index(self, index_type):

@@ -119,6 +119,11 @@ class FlatIndexBase:
     _RANGE: Tuple[str, str, str]
     _RECONSTRUCT: str
 
+    def _payload_args(self) -> tuple:
+        """What the range and reconstruct entry points of the subclass take right behind the rows: nothing, or the device address
+        of what the payload was trained with (IndexSQ8bit's ranges)."""
+        return ()
+
     def __init__(self, d: int, device, dtype: torch.dtype, what: str):
         self.d = int(d)
         self.device = torch.device(device)
@@ -241,14 +246,15 @@ class FlatIndexBase:
         X, n, d, st = self._store.rows, self._store.n, self.d, _lib.stream_ptr()
         bytes_name, count_name, fill_name = self._RANGE
         bytes_fn, count_fn, fill_fn = getattr(lib, bytes_name), getattr(lib, count_name), getattr(lib, fill_name)
+        extra = self._payload_args()
 
         def stage(qs):
             def count(counts, ws):
-                _lib.check(count_fn(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, _lib.ptr(keep), counts.data_ptr(),
+                _lib.check(count_fn(X.data_ptr(), *extra, n, d, qs.data_ptr(), qs.shape[0], radius, _lib.ptr(keep), counts.data_ptr(),
                                     ws.data_ptr(), ws.numel(), st), count_name)
 
             def fill(lims, D, P, ws):
-                _lib.check(fill_fn(X.data_ptr(), n, d, qs.data_ptr(), qs.shape[0], radius, 0, 0, lims.data_ptr(), D.data_ptr(),
+                _lib.check(fill_fn(X.data_ptr(), *extra, n, d, qs.data_ptr(), qs.shape[0], radius, 0, 0, lims.data_ptr(), D.data_ptr(),
                                    P.data_ptr(), ws.data_ptr(), ws.numel(), st), fill_name)
             return count, fill
 
@@ -268,7 +274,7 @@ class FlatIndexBase:
         self._finalize()
         qi = torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64)).to(self.device)
         out = torch.empty(qi.numel(), self.d, dtype=torch.float32, device=self.device)
-        rc = getattr(lib, self._RECONSTRUCT)(self._store.rows.data_ptr(), self._store.n, self.d, _lib.ptr(self._store.ids),
+        rc = getattr(lib, self._RECONSTRUCT)(self._store.rows.data_ptr(), *self._payload_args(), self._store.n, self.d, _lib.ptr(self._store.ids),
                                              self._store.id_base, qi.data_ptr(), qi.numel(), out.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, self._RECONSTRUCT)
         return out.cpu().numpy()

@@ -1,4 +1,7 @@
-"""faiss-shaped exhaustive inner-product index whose rows live in HBM as IEEE binary16: IndexSQfp16.
+"""faiss-shaped exhaustive inner-product indexes over scalar-quantized rows: IndexSQfp16 (binary16 rows, below) and IndexSQ8bit
+(one byte per dimension under trained ranges: FlatSQ8IPIndex at the end of the file).
+
+IndexSQfp16.
 
 Stands where `faiss.IndexIDMap(faiss.IndexScalarQuantizer(d, QT_fp16, METRIC_INNER_PRODUCT))` would stand beside the reference's
 `IndexFlatIP` (src/index/feature_search_index.py:47-52): no training, no nprobe, every row scored — at 2 d bytes a row and nothing
@@ -159,3 +162,219 @@ class FlatSQfp16IPIndex(FlatIndexBase):
             return 0, 0
         c = self._counters.cpu()
         return int(c[0]), int(c[1])
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------
+# IndexSQ8bit
+def check_sq8_shape(d: int) -> None:
+    if d < 16 or d % 16 != 0 or d > 1024:
+        raise ValueError(f"IndexSQ8bit: d={d} must be a multiple of 16 in [16, 1024]")
+
+
+def _codes(t: torch.Tensor) -> torch.Tensor:
+    if t.dtype != torch.uint8:
+        raise ValueError(f"IndexSQ8bit: uint8 codes expected, got {t.dtype}")
+    return t
+
+
+class FlatSQ8IPIndex(FlatIndexBase):
+    """faiss-shaped exhaustive inner-product index whose rows live in HBM as ONE BYTE per dimension: IndexSQ8bit.
+
+    Stands where `faiss.IndexIDMap(faiss.IndexScalarQuantizer(d, QT_8bit, METRIC_INNER_PRODUCT))` (RS_minmax, argument 0) would
+    stand: codes [N, d] uint8, trained [2 d] fp32 (vmin, then vdiff) and the ids — N (d + 8) + 8 d bytes, no lists, no nprobe.  The
+    surface is FlatSQfp16IPIndex's plus the training: `train(x)` or `set_trained(vmin, vdiff)` must come before the first add.  A
+    score is q0 + s_0 of include/wise_hip.h (W, q0 of wise_sq_query, the wise_ivfsq_scan arithmetic) whichever path computes it:
+    search, search under a selector, range_search and the batched search return the same bits for the same row.
+    """
+    # PROVISIONAL: rows from which search_device hands a batch to wise_ipsq8_topk_batched.  IndexSQfp16's floor, not measured for this
+    # type: tools/sq8_bench.py measured ONE size (10M x 512)
+    BATCH_MIN_ROWS = 1 << 18
+    # queries from which a batch takes the batched search.  Measured at 10M x 512, k = 10 (profiles/sq8_bench.json): a batched pass
+    # takes 3.5 - 3.6 ms whatever it carries up to 32 queries, the exact scan 2.7 ms per pass of 4 - 2.66 ms at nq = 3, 2.69 at 4, 5.35
+    # at 8, 21.0 at 32: 8 is the smallest measured batch from which the batched search wins at every larger measured one (the rule
+    # IndexFlatL2 recorded).  One size, so PROVISIONAL like the row floor
+    BATCH_MIN_QUERIES = 8
+    ENCODE_BYTES = 64 << 20          # fp32 staging of train / add_with_ids: rows go through the GPU this many bytes at a time
+    _RANGE = ("wise_ipsq8_range_workspace_bytes", "wise_ipsq8_range_count", "wise_ipsq8_range_fill")
+    _RECONSTRUCT = "wise_ipsq8_reconstruct"          # faiss's Codec8bit decode: vmin + ((code + 0.5) / 255) vdiff
+
+    def __init__(self, d: int, device: str = "cuda"):
+        check_sq8_shape(d)
+        super().__init__(d, device, torch.uint8, f"codes must be contiguous uint8 [N,{int(d)}] on the index's device")
+        self.is_trained = False
+        self._trained: Optional[torch.Tensor] = None  # device [2 d] fp32: vmin, then vdiff
+        self._norms: Optional[torch.Tensor] = None    # device [1]: the largest code norm (wise_ipsq8_prepare), built on demand
+        self._counters: Optional[torch.Tensor] = None
+        self._bws: Optional[torch.Tensor] = None
+
+    # -- training -------------------------------------------------------------------------------
+    def _staged(self, x: torch.Tensor):
+        """x [n,d] float32 (host or device) as device chunks of at most ENCODE_BYTES: (start, chunk) pairs"""
+        rows = max(1, self.ENCODE_BYTES // (4 * self.d))
+        stage = None
+        for s in range(0, x.shape[0], rows):
+            part = x[s:s + rows]
+            if part.device.type != self.device.type or not part.is_contiguous() or part.dtype != torch.float32:
+                if stage is None:
+                    stage = torch.empty(min(rows, x.shape[0]), self.d, dtype=torch.float32, device=self.device)
+                stage[:part.shape[0]].copy_(part)
+                part = stage[:part.shape[0]]
+            yield s, part
+
+    def minmax(self, x, lohi: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The running per-dimension minimum and maximum of rows x [n,d] float32 (n may be 0) folded into lohi (device [2, d]: lo,
+        then hi; None: a fresh one holding +3.4028235e38 / -3.4028235e38) by wise_sq_minmax, chunk by chunk.  Exact and order-free:
+        the same rows in any chunks, or the MIN / MAX all-reduce of several ranks' results, give the same bits."""
+        lib = _lib.lib()
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError(f"minmax: expected [n,{self.d}], got {tuple(x.shape)}")
+        fresh = lohi is None
+        if fresh:
+            lohi = torch.empty(2, self.d, dtype=torch.float32, device=self.device)
+        st = _lib.stream_ptr()
+        if fresh or x.shape[0] == 0:
+            _lib.check(lib.wise_sq_minmax(0, 0, self.d, lohi[0].data_ptr(), lohi[1].data_ptr(), 0 if fresh else 1, st), "wise_sq_minmax")
+        for _, part in self._staged(x):
+            _lib.check(lib.wise_sq_minmax(part.data_ptr(), part.shape[0], self.d, lohi[0].data_ptr(), lohi[1].data_ptr(), 1, st),
+                       "wise_sq_minmax")
+        return lohi
+
+    def set_minmax(self, lohi: torch.Tensor) -> None:
+        """Train from a minimum and maximum: vmin = lo, vdiff = hi - lo, one fp32 subtraction (wise_sq_train's bits)."""
+        lohi = lohi.to(torch.float32)
+        if bool((lohi[0] > lohi[1]).any()):            # the minimum and maximum of no rows at all: ranges of zero width at zero
+            lohi = torch.zeros_like(lohi)
+        self.set_trained(lohi[0], lohi[1] - lohi[0])
+
+    def train(self, x) -> None:
+        """faiss's RS_minmax with argument 0 over the rows x [n >= 1, d]: one range per dimension."""
+        x = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if x.dim() != 2 or x.shape[1] != self.d or x.shape[0] < 1:
+            raise ValueError(f"train: expected [n >= 1,{self.d}], got {tuple(x.shape)}")
+        self.set_minmax(self.minmax(x))
+
+    def set_trained(self, vmin, vdiff) -> None:
+        """The ranges as they are (an index file's): vmin [d], vdiff [d] float32.  Only an empty index is trained."""
+        if self._n:
+            raise RuntimeError("IndexSQ8bit: the index holds rows encoded against its ranges; they cannot change")
+        as_t = lambda v: (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))).to(torch.float32).reshape(-1)
+        vmin, vdiff = as_t(vmin), as_t(vdiff)
+        if vmin.numel() != self.d or vdiff.numel() != self.d:
+            raise ValueError(f"set_trained: vmin and vdiff must hold {self.d} values each")
+        self._trained = torch.cat([vmin.to(self.device), vdiff.to(self.device)]).contiguous()
+        self.is_trained = True
+
+    def trained_host(self):
+        """(vmin [d], vdiff [d]) float32 on the host: what the index file holds."""
+        self._need_trained("trained_host")
+        t = self._trained.cpu().numpy()
+        return t[:self.d].copy(), t[self.d:].copy()
+
+    def _need_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise RuntimeError(f"IndexSQ8bit: {what} before train() or set_trained()")
+
+    def _payload_args(self) -> tuple:
+        return (self._trained.data_ptr(),)
+
+    # -- construction ---------------------------------------------------------------------------
+    @property
+    def _codes_t(self) -> Optional[torch.Tensor]:
+        """[N,d] uint8 on device: the whole payload"""
+        return self._store.rows
+
+    def hbm_bytes(self) -> int:
+        """Bytes of HBM the index itself holds: the codes, the ids and the ranges."""
+        return self._n * (self.d + (8 if self._store.has_ids else 0)) + 8 * self.d
+
+    def add_with_ids(self, x, ids) -> None:
+        self._need_trained("add_with_ids")
+        super().add_with_ids(x, ids)
+
+    def _fill(self, dst: torch.Tensor, x: torch.Tensor) -> None:
+        """add_with_ids: the rows are encoded on the GPU (wise_sq_encode; values outside the trained ranges clamp), chunk by chunk,
+        so that no fp32 form of the index exists in HBM"""
+        lib = _lib.lib()
+        for s, part in self._staged(x):
+            _lib.check(lib.wise_sq_encode(part.data_ptr(), self._trained.data_ptr(), part.shape[0], self.d,
+                                          dst[s:s + part.shape[0]].data_ptr(), _lib.stream_ptr()), "wise_sq_encode")
+
+    def add_codes_with_ids(self, codes, ids) -> None:
+        """codes [n,d] uint8 (numpy or tensor), ids [n] int64: rows that are already encoded — an index file's — go to HBM as they
+        are."""
+        self._need_trained("add_codes_with_ids")
+        c = _codes(codes if torch.is_tensor(codes) else torch.from_numpy(np.array(codes, dtype=np.uint8, order="C")))
+        if c.dim() != 2 or c.shape[1] != self.d:
+            raise ValueError(f"add_codes_with_ids: expected [n,{self.d}], got {tuple(c.shape)}")
+        self._slot(c.shape[0], ids, "add_codes_with_ids").copy_(c)
+
+    def adopt(self, codes: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: int = 0) -> "FlatSQ8IPIndex":
+        """Take ownership of codes already resident in HBM (no copy).  ids None => id = id_base + row."""
+        self._need_trained("adopt")
+        return super().adopt(_codes(codes), ids, id_base)
+
+    def _rows_changed(self) -> None:
+        self._norms = None
+
+    def range_search_device(self, q, thresh, sel=None, chunk=None):
+        self._need_trained("range_search")
+        return super().range_search_device(q, thresh, sel=sel, chunk=chunk)
+
+    def reconstruct_batch(self, ids) -> np.ndarray:
+        self._need_trained("reconstruct_batch")
+        return super().reconstruct_batch(ids)
+
+    # -- search ---------------------------------------------------------------------------------
+    def _ensure_norms(self, lib) -> torch.Tensor:
+        if self._norms is None:
+            self._norms = torch.zeros(1, dtype=torch.float32, device=self.device)
+            _lib.check(lib.wise_ipsq8_prepare(self._codes_t.data_ptr(), self._n, self.d, self._norms.data_ptr(), _lib.stream_ptr()),
+                       "wise_ipsq8_prepare")
+        return self._norms
+
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64) on device, no host sync.  The routing is FlatSQfp16IPIndex's:
+        BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the matrix-core passes where they serve the
+        shape (wise_ipsq8_topk_batched: the same bits), everything else through the exact scan; sel: the scan over its positions."""
+        lib = _lib.lib()
+        self._need_trained("search")
+        self._finalize()
+        q = self._queries(q, "search")
+        nq, k = q.shape[0], int(k)
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return D, I
+        st, C, T = _lib.stream_ptr(), self._codes_t, self._trained
+        if sel is not None:
+            pos = resolve_for(self, sel).positions()
+            need = lib.wise_ipsq8_topk_workspace_bytes(pos.numel(), self.d, nq, k)
+            if need == 0:
+                raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
+            ws = self._grown("_ws", need)
+            _lib.check(lib.wise_ipsq8_topk_pos(C.data_ptr(), T.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq,
+                                               k, _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
+                                               ws.numel(), st), "wise_ipsq8_topk_pos")
+            return D, I
+        batch = self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
+        need = lib.wise_ipsq8_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
+        if need:
+            self._grown("_bws", need)
+            if self._counters is None:
+                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+            norms = self._ensure_norms(lib)
+            _lib.check(lib.wise_ipsq8_topk_batched(C.data_ptr(), T.data_ptr(), norms.data_ptr(), self._n, self.d, q.data_ptr(), nq, k,
+                                                   _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(),
+                                                   self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
+                       "wise_ipsq8_topk_batched")
+            return D, I
+        need = lib.wise_ipsq8_topk_workspace_bytes(self._n, self.d, nq, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
+        ws = self._grown("_ws", need)
+        _lib.check(lib.wise_ipsq8_topk(C.data_ptr(), T.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids),
+                                       self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ipsq8_topk")
+        return D, I
+
+    batched_counts = FlatSQfp16IPIndex.batched_counts
