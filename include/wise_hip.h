@@ -47,7 +47,8 @@ const char* wise_last_error(void);
  * IndexSQfp16; and the wise_l2_* entry points (wise_l2_topk_f32, wise_l2_topk_pos_f32, wise_l2_range_count_f32 / _fill_f32,
  * wise_l2_prepare, wise_l2_topk_batched and their three workspace functions), IndexFlatL2; and wise_sq_minmax and the wise_ipsq8_*
  * entry points (wise_ipsq8_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and their three workspace
- * functions), IndexSQ8bit.  The version is 5. */
+ * functions), IndexSQ8bit; and the wise_ivfl2_* entry points (wise_ivfl2_scan, _scan_sel, _scan_local, _range_count / _fill and their
+ * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -678,6 +679,58 @@ size_t wise_l2_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
 int wise_l2_topk_batched(const float* X, const uint16_t* Xb, const float* half, const float* norms /*[2]*/, int64_t N, int d,
                          const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
                          int32_t* counters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexIVFFlatL2: inverted-file search under squared L2 — faiss's IndexIVFFlat(IndexFlatL2(d), d, nlist, METRIC_L2).
+ * The lists hold the raw fp32 rows X [N, d] grouped by list (no residual), 4 d bytes a row.  Limits are IndexFlatL2's: d % 16 == 0,
+ * 16 <= d <= 1024, X and Q 16-byte aligned, 0 <= N < 2^32 - 1; and k <= 2048, nprobe <= 2048, nq <= 65535.  Anything else, a null
+ * pointer or a short workspace is WISE_E_INVALID with a wise_last_error text, and nothing is written.  No call allocates or reads
+ * back: every call can be captured into a graph.  All deterministic.
+ * THE DISTANCE IS THE CONTRACT OF wise_l2_topk_f32 ABOVE: a row of a list scores, bit for bit, what IndexFlatL2 gives the same (query,
+ * row) — the same device routine.  Selection runs on -dist (exact), so keys, ties (the row that comes first in X wins), the merge of the
+ * probed lists and wise_topk_merge are the inner-product types'.  Outputs are squared distances, ascending, padded with
+ * (+3.4028235e38, -1).
+ *   wise_ivfl2_scan: arguments as wise_ivf_scan_f32.  Probes < 0 or >= nlist are skipped, and so are empty lists.  One block per
+ *     (query, probe), the list kernels of wise_ivfsq16_scan over fp32 rows.  Workspace: wise_ivfl2_scan_workspace_bytes(nq, nprobe, k).
+ *   wise_ivfl2_scan_sel: the same with keep, (N + 31) / 32 words as wise_sel_bitmap writes them: only the rows whose bit is set compete;
+ *     a selected row's distance is the unfiltered scan's, and with every bit set the output is the unfiltered scan's.
+ *   wise_ivfl2_scan_local: the rank-local form for a slice of the list-major array, as wise_ivfsq16_scan_local: list_off clipped to
+ *     the slice, pos_base >= 0 the position of the slice's first row, probes whose list is empty in the slice dropped first (in probe
+ *     order; probe_count [nq], optional, receives the number kept), group-major block order, and with ids == NULL outI = pos_base +
+ *     row.  wise_topk_merge of the ranks' NEGATED answers in rank order gives, negated back, the bits of wise_ivfl2_scan over the
+ *     whole array.  Workspace: wise_ivfl2_scan_local_workspace_bytes(nq, nprobe, k).
+ *   wise_ivfl2_range_count / _fill: the count / fill pair of range_search above over the probed lists; a hit iff dist < radius,
+ *     strictly; fixed order: probe order, then ascending position; keep optional; radius finite; a hit's distance is the scan's.
+ *     Workspace: wise_ivfl2_range_workspace_bytes(N, nlist, nq, nprobe).
+ * THE COARSE RULE IS A CONTRACT: g(x, c) = fl(s(x, c) - h_c), where s is wise_ip_scores_f32's index-ordered fmaf chain from +0 and
+ * h_c = 0.5f * |c|^2 is wise_l2_half_norms's value (|x - c|^2 = |x|^2 - 2 (x . c - |c|^2 / 2): the largest g is the nearest
+ * centroid).  A row goes to argmax_c g, ties to the lowest c (wise_ivf_argmax); a query probes the nprobe largest g
+ * (wise_select_topk_f32, -1 padding when nprobe > nlist).  Assignment and probing use the same arithmetic, so a stored row's own list
+ * is among its probes at any nprobe >= 1.
+ *   wise_l2_half_norms: half[r] = 0.5f * |x_r|^2, exactly wise_l2_prepare's (the same kernel); N = 0 writes nothing.
+ *   wise_ivf_l2_coarse: in place, scores[r, c] = scores[r, c] - half[c] for scores [rows, nlist]: one rounded fp32 subtraction.
+ *   wise_ivf_list_means: out[c, :] = sums[c, :] / (float)counts[c], one correctly rounded fp32 division per element (counts int64, as
+ *     wise_ivf_group writes them); rows with count 0 are left as they are; out may be sums.  The plain k-means update. */
+size_t wise_ivfl2_scan_workspace_bytes(int nq, int nprobe, int k);
+int wise_ivfl2_scan(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q, int nq,
+                    const int64_t* probes, int nprobe, int k, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int wise_ivfl2_scan_sel(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q, int nq,
+                        const int64_t* probes, int nprobe, int k, const uint32_t* keep, float* outD, int64_t* outI, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t wise_ivfl2_scan_local_workspace_bytes(int nq, int nprobe, int k);
+int wise_ivfl2_scan_local(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                          int nq, const int64_t* probes, int nprobe, int k, int64_t pos_base, float* outD, int64_t* outI,
+                          int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream);
+size_t wise_ivfl2_range_workspace_bytes(int64_t N, int nlist, int nq, int nprobe);
+int wise_ivfl2_range_count(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                           const int64_t* probes, int nprobe, float radius, const uint32_t* keep, int64_t* counts, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int wise_ivfl2_range_fill(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                          int nq, const int64_t* probes, int nprobe, float radius, const int64_t* lims, float* outD, int64_t* outI,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2_half_norms(const float* X, int64_t N, int d, float* half /*[N]*/, void* stream);
+int wise_ivf_l2_coarse(float* scores, const float* half, int rows, int nlist, void* stream);
+int wise_ivf_list_means(const float* sums, const int64_t* counts, int nlist, int d, float* out, void* stream);
 
 /* (ABI 5, additive) remove_ids — stable, in-place compaction of an index's per-row arrays under a bitmap over row positions.
  *   keep      (N + 31) / 32 words as wise_sel_bitmap writes them, bit p set = row p STAYS.  The bits past N are ignored, whatever

@@ -185,6 +185,17 @@ SIGNATURES = {
     "wise_l2_prepare": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "wise_l2_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_l2_topk_batched": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfl2_scan_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wise_ivfl2_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfl2_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfl2_scan_local_workspace_bytes": (_sz, [_i, _i, _i]),
+    "wise_ivfl2_scan_local": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfl2_range_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_ivfl2_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_ivfl2_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2_half_norms": (_i, [_vp, _i64, _i, _vp, _vp]),
+    "wise_ivf_l2_coarse": (_i, [_vp, _vp, _i, _i, _vp]),
+    "wise_ivf_list_means": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "wise_compact_plan_entries": (_i64, [_i64]),
     "wise_compact_plan": (_i, [_vp, _i64, _vp, _vp, _vp]),
     "wise_compact_rank": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _vp]),

@@ -9,6 +9,8 @@
 //   wise_ivf_list_sums       per list the sum of its rows IN THAT ORDER (one workgroup per list, fixed order of addition: the same
 //                            bits run after run, which a float atomicAdd scatter does not give), the spherical k-means update
 //   wise_ivf_normalize_rows  c / max(||c||, 1e-20); wise_ivf_reseed: an empty cell becomes a perturbed copy of a full one
+//   wise_ivf_l2_coarse       the L2 coarse rule's second half: scores - half-norms in place (IndexIVFFlatL2: argmax / select follow)
+//   wise_ivf_list_means      sums / counts, the plain (non-spherical) k-means update of IndexIVFFlatL2; empty cells left alone
 //   wise_ivf_gather_rows / _i64, wise_ivf_expand_lists   the copies of add() / finalize
 // All HBM-bound integer / copy work: n * d * 4 bytes per pass over the rows, n * 16 bytes per sort pass.
 #include "common.h"
@@ -182,6 +184,22 @@ __global__ __launch_bounds__(256) void reseed_kernel(float* __restrict__ sums, c
     }
 }
 
+// wise_ivf_l2_coarse: thread = one score; g = s - h_c, one rounded fp32 subtraction
+__global__ __launch_bounds__(256) void l2_coarse_kernel(float* __restrict__ scores, const float* __restrict__ half, long long total, int nlist) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e < total) scores[e] = scores[e] - half[e % nlist];
+}
+
+// wise_ivf_list_means: block = list, out[c][:] = sums[c][:] / (float)counts[c], one correctly rounded division per element; a list
+// without rows is left as it is (block-uniform)
+__global__ __launch_bounds__(256) void list_means_kernel(const float* __restrict__ sums, const long long* __restrict__ counts, int d,
+                                                         float* __restrict__ out) {
+    const long long n = counts[blockIdx.x];
+    if (n <= 0) return;
+    const float fn = (float)n;
+    for (int c = threadIdx.x; c < d; c += 256) out[(size_t)blockIdx.x * d + c] = sums[(size_t)blockIdx.x * d + c] / fn;
+}
+
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ x, const long long* __restrict__ idx, long long n, int d,
                                                           float* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -277,6 +295,21 @@ extern "C" int wise_ivf_reseed(float* sums, const int64_t* empty, const int64_t*
     if (n_empty == 0) return WISE_OK;
     hipLaunchKernelGGL(reseed_kernel, dim3(n_empty), dim3(256), 0, (hipStream_t)stream, sums, (const long long*)empty, (const long long*)donor, d);
     WISE_LAUNCH_CHECK("ivf reseed_kernel");
+    return WISE_OK;
+}
+extern "C" int wise_ivf_l2_coarse(float* scores, const float* half, int rows, int nlist, void* stream) {
+    WISE_CHECK_ARG(rows >= 0 && nlist > 0 && half && (scores || rows == 0), "ivf_l2_coarse: bad argument");
+    if (rows == 0) return WISE_OK;
+    const long long total = (long long)rows * nlist;
+    WISE_CHECK_ARG((total + 255) / 256 <= 0x7FFFFFFFll, "ivf_l2_coarse: rows=%d x nlist=%d too large", rows, nlist);
+    hipLaunchKernelGGL(l2_coarse_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, half, total, nlist);
+    WISE_LAUNCH_CHECK("ivf l2_coarse_kernel");
+    return WISE_OK;
+}
+extern "C" int wise_ivf_list_means(const float* sums, const int64_t* counts, int nlist, int d, float* out, void* stream) {
+    WISE_CHECK_ARG(sums && counts && out && nlist > 0 && d > 0, "ivf_list_means: bad argument");
+    hipLaunchKernelGGL(list_means_kernel, dim3(nlist), dim3(256), 0, (hipStream_t)stream, sums, (const long long*)counts, d, out);
+    WISE_LAUNCH_CHECK("ivf list_means_kernel");
     return WISE_OK;
 }
 extern "C" int wise_ivf_gather_rows(const float* x, const int64_t* idx, int64_t n, int d, float* out, void* stream) {

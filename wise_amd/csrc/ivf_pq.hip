@@ -473,7 +473,7 @@ extern "C" int wise_ivfpq_scan_local(const uint8_t* codes, int64_t N, int m, con
     hipStream_t st = (hipStream_t)stream;
     const LocalWorkspace lw = LocalWorkspace::carve(workspace, local_part_bytes(s, nq, k), nq, nprobe, probe_count);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
-    hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
+    hipLaunchKernelGGL(compact_probes_bias_kernel<true>, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
                        nlist, s.groups, LOCAL_MIN_SHARE, lw.live, lw.lbias, lw.count, lw.used);
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
     if (m % 16 == 0) launch_pq_scan<16, true>(s, nq, codes, lo, nlist, lut, lw.live, lw.lbias, nprobe, m, k, lw.part, st, lw.count, lw.used);

@@ -35,6 +35,10 @@
 // The SQ8 entry points instantiate the bodies with Codec8 and keep their arithmetic and their bits.
 // The two codecs and sq_score_loads — the sum of the contract — live in sq_codec.h: the flat scan over binary16 rows (ip_sq16.hip,
 // IndexSQfp16) scores with the same device code.
+// IndexIVFFlatL2 (faiss IndexIVFFlat over IndexFlatL2, METRIC_L2: raw fp32 rows in the lists, no residual) is the SAME kernels under
+// the flat L2 index's codec (CodecL2: the query is the weight row, s_0 is the squared distance) and the L2 sense of a score (SenseL2
+// below): no bias, keys order -dist, a range hit is dist < radius, the sign flips back behind the merge.
+//   wise_ivfl2_scan / _scan_sel / _scan_local / wise_ivfl2_range_*   a row's distance is wise_l2_topk_f32's, bit for bit
 #include "probe_compact.h"
 #include "range_common.h"
 #include "sq_codec.h"
@@ -45,6 +49,31 @@ namespace ivf_sq {
 constexpr int MAX_D = 1024;
 
 static bool sq_shape_ok(int d) { return d >= 16 && d <= MAX_D && d % 16 == 0; }
+
+// THE SENSE of a list kernel's score, a static policy beside the codec (what flat_codec_scan.h's policies are to the flat scan): the
+// row's value from its base and s_0, the score its key orders, and the range rule.  Nothing branches on it at run time.
+//   SenseIP  the inner-product types: value = base + s_0 with base = the codec's (bias, q0) term; larger is better; hit: value > radius
+//   SenseL2  IndexIVFFlatL2 over CodecL2: value = s_0, the squared distance itself (no bias is read: the pointer may be null); the
+//            key orders -value (exact), so keys, ties and merges are the other types'; hit: value < radius.  FLIP: the merge's
+//            output, scores and padding, is negated behind it (l2_flip_launch, l2_topk.hip)
+struct SenseIP {
+    static constexpr bool FLIP = false;
+    template <class Codec>
+    static __device__ __forceinline__ float base(const float* bias, size_t i, const float* q0, int qi) {
+        return Codec::base(bias[i], q0, qi);
+    }
+    static __device__ __forceinline__ float value(float base, float s) { return base + s; }
+    static __device__ __forceinline__ float key_score(float v) { return v; }
+    static __device__ __forceinline__ bool range_hit(float v, float radius) { return v > radius; }
+};
+struct SenseL2 {
+    static constexpr bool FLIP = true;
+    template <class Codec>
+    static __device__ __forceinline__ float base(const float*, size_t, const float*, int) { return 0.f; }
+    static __device__ __forceinline__ float value(float, float s) { return s; }
+    static __device__ __forceinline__ float key_score(float v) { return -v; }
+    static __device__ __forceinline__ bool range_hit(float v, float radius) { return v < radius; }
+};
 
 // trained is used as 2 d ordered-unsigned cells while the reduction runs: min cells start at the largest key, max cells at 0
 __global__ __launch_bounds__(256) void train_init_kernel(unsigned* __restrict__ cells, int d) {
@@ -198,9 +227,10 @@ __global__ __launch_bounds__(256) void decode16_kernel(const _Float16* __restric
     for (int c = threadIdx.x; c < d; c += blockDim.x) o[c] = cr[c] + (float)h[c];
 }
 
-// One block's scan of the rows [lo, hi) of codes under the weight row wrow [d]: score = base + s_0; the k best keys go to dst.
+// One block's scan of the rows [lo, hi) of codes under the weight row wrow [d]: score = base + s_0 (SenseL2: -s_0); the k best keys go
+// to dst.
 // SEL: only the rows whose bit of `keep` is set are offered; a wave whose SQ_T loads hold no such row skips them (wave-uniform)
-template <class Codec, bool SEL>
+template <class Codec, bool SEL, class Sense = SenseIP>
 __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ codes, long long lo, long long hi,
                                              const float* __restrict__ wrow, float base, int d, int k, int cap, u64* __restrict__ dst,
                                              const unsigned* __restrict__ keep) {
@@ -237,7 +267,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
         sq_score_loads<Codec>(codes, d, C, c, r, w, s);
 #pragma unroll
         for (int t = 0; t < SQ_T; ++t) {
-            const u64 key = make_key(base + s[t], (unsigned)row[t]);
+            const u64 key = make_key(Sense::key_score(Sense::value(base, s[t])), (unsigned)row[t]);
             wl.offer(live[t] && c == 0 && key > wl.tau, key, lane);
         }
     }
@@ -259,7 +289,7 @@ __device__ __forceinline__ void sq_scan_list(const unsigned char* __restrict__ c
 }
 
 // grid = nq * nprobe: block b scans the list probes[b] of query b / nprobe; its k keys go to part[(b % nprobe) * nq + b / nprobe]
-template <class Codec, bool SEL>
+template <class Codec, bool SEL, class Sense = SenseIP>
 __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                       int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                       const long long* __restrict__ probes, const float* __restrict__ bias, int nprobe,
@@ -269,8 +299,8 @@ __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __res
     const long long l = probes[(size_t)qi * nprobe + pi];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }          // block-uniform
-    sq_scan_list<Codec, SEL>(codes, lo, hi, W + (size_t)qi * d, Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi), d, k, cap,
-                             part + ((size_t)pi * nq + qi) * k, keep);
+    sq_scan_list<Codec, SEL, Sense>(codes, lo, hi, W + (size_t)qi * d, Sense::template base<Codec>(bias, (size_t)qi * nprobe + pi, q0, qi),
+                                    d, k, cap, part + ((size_t)pi * nq + qi) * k, keep);
 }
 
 // wise_ivfsq_scan_local.  grid = nq * nprobe: block b is probe group b / nq of query b % nq — group-major, so the blocks that
@@ -279,7 +309,7 @@ __global__ __launch_bounds__(256) void sq_scan_kernel(const unsigned char* __res
 // probes / bias are the compacted ones (compact_probes_bias_kernel with G = nprobe and a share of 1: used[q] = the probes kept =
 // the groups of query q, one kept probe each); a block past used[q] returns BEFORE it loads the query's weight row, and its slot
 // of part is never read: the merge folds used[q] lists.  list_off is clipped to the slice, rows are positions in the slice.
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 __global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                             int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                             const long long* __restrict__ probes, const float* __restrict__ bias,
@@ -290,11 +320,12 @@ __global__ __launch_bounds__(256) void sq_scan_local_kernel(const unsigned char*
     const long long l = probes[(size_t)qi * nprobe + g];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }
-    sq_scan_list<Codec, false>(codes, lo, hi, W + (size_t)qi * d, Codec::base(bias[(size_t)qi * nprobe + g], q0, qi), d, k, cap,
-                               part + ((size_t)g * nq + qi) * k, nullptr);
+    sq_scan_list<Codec, false, Sense>(codes, lo, hi, W + (size_t)qi * d, Sense::template base<Codec>(bias, (size_t)qi * nprobe + g, q0, qi),
+                                      d, k, cap, part + ((size_t)g * nq + qi) * k, nullptr);
 }
 
-// ---- range_search (wise_ivfsq_range_*): every row of the probed lists with (bias + q0) + s_0 > radius, s_0 from sq_score_loads.
+// ---- range_search (wise_ivfsq_range_*): every row of the probed lists with (bias + q0) + s_0 > radius, s_0 from sq_score_loads
+// (SenseL2, wise_ivfl2_range_*: s_0 < radius).
 // One block per (query, probe) as sq_scan_kernel; structure, workspace and the determinism argument: range_common.h
 template <class Codec>
 struct SqLane {
@@ -307,7 +338,7 @@ struct SqLane {
     }
 };
 
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                              int nlist, const float* __restrict__ W, const float* __restrict__ q0,
                                                              const long long* __restrict__ probes, const float* __restrict__ bias,
@@ -319,7 +350,7 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
     const long long l = probes[(size_t)qi * nprobe + pi];
     long long lo = 0, hi = 0;
     if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }            // block-uniform
-    const float base = Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi);
+    const float base = Sense::template base<Codec>(bias, (size_t)qi * nprobe + pi, q0, qi);
     SqLane<Codec> L;
     L.init(W + (size_t)qi * d, d, lane);
     unsigned* dst = hit + (size_t)qi * wstride + (lo >> 5) + (l > 0 ? l : 0);
@@ -346,7 +377,7 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
             sq_score_loads<Codec>(codes, d, L.C, L.c, r, L.w, s);
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t)
-                if (live[t] && L.c == 0 && base + s[t] > radius) range_mark(hb, (int)(r[t] - clo));
+                if (live[t] && L.c == 0 && Sense::range_hit(Sense::value(base, s[t]), radius)) range_mark(hb, (int)(r[t] - clo));
         }
         __syncthreads();
         if (wave == 0) total += range_publish(hb, dst, (int)((chi - clo + 31) >> 5), lane);
@@ -354,7 +385,7 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
     if (threadIdx.x == 0) seg[(size_t)qi * (nprobe + 1) + pi] = total;
 }
 
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                             int nlist, const long long* __restrict__ ids, const float* __restrict__ W,
                                                             const float* __restrict__ q0, const long long* __restrict__ probes,
@@ -374,7 +405,7 @@ __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char*
     if (l < 0 || l >= nlist) return;                                                // not the probes count saw: nothing to read
     const long long lo = list_off[l], hi = list_off[l + 1];
     const unsigned* words = hit + (size_t)qi * wstride + (lo >> 5) + l;
-    const float base = Codec::base(bias[(size_t)qi * nprobe + pi], q0, qi);
+    const float base = Sense::template base<Codec>(bias, (size_t)qi * nprobe + pi, q0, qi);
     SqLane<Codec> L;
     L.init(W + (size_t)qi * d, d, lane);
     for (long long clo = lo; clo < hi; clo += RANGE_ROWS, words += RANGE_WORDS) {
@@ -400,7 +431,7 @@ __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char*
 #pragma unroll
             for (int t = 0; t < SQ_T; ++t)
                 if (e[t] >= 0 && L.c == 0) {
-                    outD[dest + e[t]] = base + s[t];
+                    outD[dest + e[t]] = Sense::value(base, s[t]);
                     outI[dest + e[t]] = ids ? ids[r[t]] : r[t];
                 }
         }
@@ -501,29 +532,34 @@ extern "C" size_t wise_ivfsq_scan_local_workspace_bytes(int nq, int nprobe, int 
 }
 
 // wise_ivfsq_scan / wise_ivfsq16_scan and, with keep, their _sel forms.  Codec16 has no q0
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 static int sq_scan_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                         const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k, float* outD,
                         int64_t* outI, void* workspace, size_t workspace_bytes, void* stream, const uint32_t* keep) {
     constexpr bool HAS_Q0 = Codec::PIECES == 1;
+    constexpr const char* ALIGNED = Sense::FLIP ? "X and Q" : "codes and W";
     WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
     WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "%s: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)", what, nq,
                    nprobe, k);
     WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld nlist=%d out of range", what, (long long)N, nlist);
-    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
-    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
+    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && (bias || Sense::FLIP) && outD && outI && list_off && (codes || N == 0),
+                   "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: %s must be 16-byte aligned", what, ALIGNED);
     const size_t need = wise_ivfsq_scan_workspace_bytes(nq, nprobe, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     u64* part = reinterpret_cast<u64*>(workspace);
     const int cap = topk_list_cap(k);
     const size_t lds = (size_t)4 * cap * 8;
-    auto kern = keep ? sq_scan_kernel<Codec, true> : sq_scan_kernel<Codec, false>;
+    auto kern = keep ? sq_scan_kernel<Codec, true, Sense> : sq_scan_kernel<Codec, false, Sense>;
     if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(kern), (int)lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st, reinterpret_cast<const unsigned char*>(codes),
                        (const long long*)list_off, nlist, W, q0, (const long long*)probes, bias, nprobe, nq, d, k, cap, part, keep);
     WISE_LAUNCH_CHECK("sq_scan_kernel");
-    return merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st);
+    if (int rc = merge_lists_launch(part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st))
+        return rc;
+    if constexpr (Sense::FLIP) return l2_flip_launch(outD, nq * k, nullptr, st);     // scores and padding become distances again
+    return WISE_OK;
 }
 
 extern "C" int wise_ivfsq_scan(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
@@ -558,37 +594,42 @@ extern "C" int wise_ivfsq16_scan_sel(const uint16_t* halves, int64_t N, int d, c
                                  outI, workspace, workspace_bytes, stream, keep);
 }
 
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 static int sq_scan_local_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                               const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, int k,
                               int64_t pos_base, float* outD, int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes,
                               void* stream) {
     constexpr bool HAS_Q0 = Codec::PIECES == 1;
+    constexpr const char* ALIGNED = Sense::FLIP ? "X and Q" : "codes and W";
     WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
     WISE_CHECK_ARG(scan_shape_ok(nq, nprobe, k), "%s: nq=%d nprobe=%d k=%d unsupported (nq <= 65535, nprobe <= 2048, k <= 2048)", what, nq,
                    nprobe, k);
     WISE_CHECK_ARG(nlist >= 1 && N >= 0 && N < 0xFFFFFFFFll && pos_base >= 0, "%s: N=%lld nlist=%d pos_base=%lld out of range", what,
                    (long long)N, nlist, (long long)pos_base);
-    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && bias && outD && outI && list_off && (codes || N == 0), "%s: null pointer", what);
-    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
+    WISE_CHECK_ARG(W && (q0 || !HAS_Q0) && probes && (bias || Sense::FLIP) && outD && outI && list_off && (codes || N == 0),
+                   "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: %s must be 16-byte aligned", what, ALIGNED);
     const size_t need = wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     const LocalWorkspace lw = LocalWorkspace::carve(workspace, wise_ivfsq_scan_workspace_bytes(nq, nprobe, k), nq, nprobe, probe_count);
     const long long* lo = reinterpret_cast<const long long*>(list_off);
-    hipLaunchKernelGGL(compact_probes_bias_kernel, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias, nprobe, lo,
-                       nlist, nprobe, 1, lw.live, lw.lbias, lw.count, lw.used);
+    hipLaunchKernelGGL(compact_probes_bias_kernel<!Sense::FLIP>, dim3(nq), dim3(64), 0, st, reinterpret_cast<const long long*>(probes), bias,
+                       nprobe, lo, nlist, nprobe, 1, lw.live, lw.lbias, lw.count, lw.used);
     WISE_LAUNCH_CHECK("compact_probes_bias_kernel");
     const int cap = topk_list_cap(k);
     const size_t lds = (size_t)4 * cap * 8;
-    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel<Codec>), (int)lds);
-    hipLaunchKernelGGL(sq_scan_local_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st,
+    if (lds > 48 * 1024) raise_lds_limit(reinterpret_cast<const void*>(sq_scan_local_kernel<Codec, Sense>), (int)lds);
+    hipLaunchKernelGGL((sq_scan_local_kernel<Codec, Sense>), dim3((unsigned)((long long)nq * nprobe)), dim3(256), lds, st,
                        reinterpret_cast<const unsigned char*>(codes), lo, nlist, W, q0, lw.live, lw.lbias, nprobe, nq, d, k, cap, lw.part,
                        lw.used);
     WISE_LAUNCH_CHECK("sq_scan_local_kernel");
     // keys carry local rows; without ids the merge writes pos_base + row, the row's position in the whole array
-    return merge_lists_launch(lw.part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI), st,
-                              lw.used, (long long)pos_base);
+    if (int rc = merge_lists_launch(lw.part, nprobe, nq, k, reinterpret_cast<const long long*>(ids), outD, reinterpret_cast<long long*>(outI),
+                                    st, lw.used, (long long)pos_base))
+        return rc;
+    if constexpr (Sense::FLIP) return l2_flip_launch(outD, nq * k, nullptr, st);
+    return WISE_OK;
 }
 
 extern "C" int wise_ivfsq_scan_local(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
@@ -616,33 +657,34 @@ extern "C" size_t wise_ivfsq_range_workspace_bytes(int64_t N, int nlist, int nq,
     return range_workspace_bytes(nq, range_ivf_wstride(N, nlist), nprobe);
 }
 
-static int sq_range_args(const char* what, bool has_q0, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist,
+static int sq_range_args(const char* what, bool has_q0, bool l2, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist,
                          const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
                          void* workspace, size_t workspace_bytes) {
     WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
     WISE_CHECK_ARG(sq_range_shape_ok(N, nlist, nq, nprobe), "%s: N=%lld nlist=%d nq=%d nprobe=%d unsupported (nq <= 65535, nprobe <= 2048)",
                    what, (long long)N, nlist, nq, nprobe);
-    WISE_CHECK_ARG(W && (q0 || !has_q0) && probes && bias && list_off && (codes || N == 0), "%s: null pointer", what);
-    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: codes and W must be 16-byte aligned", what);
+    WISE_CHECK_ARG(W && (q0 || !has_q0) && probes && (bias || l2) && list_off && (codes || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: %s must be 16-byte aligned", what,
+                   l2 ? "X and Q" : "codes and W");
     WISE_CHECK_ARG(radius == radius && radius - radius == 0.f, "%s: radius must be finite", what);
     const size_t need = wise_ivfsq_range_workspace_bytes(N, nlist, nq, nprobe);
     WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
     return WISE_OK;
 }
 
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 static int sq_range_count_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
                                const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
                                const uint32_t* keep, int64_t* counts, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = sq_range_args(what, Codec::PIECES == 1, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
-                               workspace_bytes))
+    if (int rc = sq_range_args(what, Codec::PIECES == 1, Sense::FLIP, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius,
+                               workspace, workspace_bytes))
         return rc;
     WISE_CHECK_ARG(counts, "%s: null pointer", what);
     hipStream_t st = (hipStream_t)stream;
     const long long wstride = range_ivf_wstride(N, nlist);
     unsigned* hit = reinterpret_cast<unsigned*>(workspace);
     long long* seg = reinterpret_cast<long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
-    hipLaunchKernelGGL(sq_range_count_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st,
+    hipLaunchKernelGGL((sq_range_count_kernel<Codec, Sense>), dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st,
                        reinterpret_cast<const unsigned char*>(codes), (const long long*)list_off, nlist, W, q0, (const long long*)probes, bias,
                        nprobe, d, radius, keep, hit, wstride, seg);
     WISE_LAUNCH_CHECK("sq_range_count_kernel");
@@ -651,18 +693,18 @@ static int sq_range_count_impl(const char* what, const void* codes, int64_t N, i
     return WISE_OK;
 }
 
-template <class Codec>
+template <class Codec, class Sense = SenseIP>
 static int sq_range_fill_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
                               const float* W, const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, float radius,
                               const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = sq_range_args(what, Codec::PIECES == 1, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius, workspace,
-                               workspace_bytes))
+    if (int rc = sq_range_args(what, Codec::PIECES == 1, Sense::FLIP, codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, radius,
+                               workspace, workspace_bytes))
         return rc;
     WISE_CHECK_ARG(lims && outD && outI, "%s: null pointer", what);
     const long long wstride = range_ivf_wstride(N, nlist);
     const unsigned* hit = reinterpret_cast<const unsigned*>(workspace);
     const long long* seg = reinterpret_cast<const long long*>(reinterpret_cast<unsigned char*>(workspace) + range_hit_bytes(nq, wstride));
-    hipLaunchKernelGGL(sq_range_fill_kernel<Codec>, dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((sq_range_fill_kernel<Codec, Sense>), dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const unsigned char*>(codes), (const long long*)list_off, nlist, reinterpret_cast<const long long*>(ids),
                        W, q0, (const long long*)probes, bias, nprobe, d, hit, wstride, seg, reinterpret_cast<const long long*>(lims), outD,
                        reinterpret_cast<long long*>(outI));
@@ -721,4 +763,52 @@ extern "C" int wise_sq16_decode(const uint16_t* halves, int64_t N, const int64_t
                        (long long)N, (const long long*)pos, (const long long*)list_off, nlist, centroids, d, out);
     WISE_LAUNCH_CHECK("sq decode16_kernel");
     return WISE_OK;
+}
+
+// ---- IndexIVFFlatL2: the same bodies over CodecL2 (raw fp32 rows, the query itself as the weight row, no bias, no q0) under SenseL2.
+// A row's distance is wise_l2_topk_f32's, bit for bit: both are s_0 of sq_score_loads<CodecL2>.
+extern "C" size_t wise_ivfl2_scan_workspace_bytes(int nq, int nprobe, int k) { return wise_ivfsq_scan_workspace_bytes(nq, nprobe, k); }
+
+extern "C" size_t wise_ivfl2_scan_local_workspace_bytes(int nq, int nprobe, int k) {
+    return wise_ivfsq_scan_local_workspace_bytes(nq, nprobe, k);
+}
+
+extern "C" int wise_ivfl2_scan(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                               int nq, const int64_t* probes, int nprobe, int k, float* outD, int64_t* outI, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    return sq_scan_impl<CodecL2, SenseL2>("ivfl2_scan", X, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, nullptr, nprobe, k, outD, outI,
+                                          workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int wise_ivfl2_scan_sel(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids, const float* Q,
+                                   int nq, const int64_t* probes, int nprobe, int k, const uint32_t* keep, float* outD, int64_t* outI,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    WISE_CHECK_ARG(keep || N == 0, "ivfl2_scan_sel: null bitmap");
+    return sq_scan_impl<CodecL2, SenseL2>("ivfl2_scan_sel", X, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, nullptr, nprobe, k, outD,
+                                          outI, workspace, workspace_bytes, stream, keep);
+}
+
+extern "C" int wise_ivfl2_scan_local(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* Q, int nq, const int64_t* probes, int nprobe, int k, int64_t pos_base, float* outD,
+                                     int64_t* outI, int32_t* probe_count, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_scan_local_impl<CodecL2, SenseL2>("ivfl2_scan_local", X, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, nullptr, nprobe, k,
+                                                pos_base, outD, outI, probe_count, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t wise_ivfl2_range_workspace_bytes(int64_t N, int nlist, int nq, int nprobe) {
+    return wise_ivfsq_range_workspace_bytes(N, nlist, nq, nprobe);
+}
+
+extern "C" int wise_ivfl2_range_count(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                                      const int64_t* probes, int nprobe, float radius, const uint32_t* keep, int64_t* counts,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_range_count_impl<CodecL2, SenseL2>("ivfl2_range_count", X, N, d, list_off, nlist, Q, nullptr, nq, probes, nullptr, nprobe,
+                                                 radius, keep, counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivfl2_range_fill(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const int64_t* ids,
+                                     const float* Q, int nq, const int64_t* probes, int nprobe, float radius, const int64_t* lims,
+                                     float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
+    return sq_range_fill_impl<CodecL2, SenseL2>("ivfl2_range_fill", X, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, nullptr, nprobe,
+                                                radius, lims, outD, outI, workspace, workspace_bytes, stream);
 }

@@ -124,11 +124,7 @@ struct MetricL2 : PlainPolicy {
     using Codec = CodecL2;
     static constexpr float PAD = 3.4028234663852886e38f;
     static constexpr bool FLIP = true;
-    static int flip(float* D, int n, const int* gate, hipStream_t st) {
-        hipLaunchKernelGGL(l2_flip_kernel, dim3((n + 255) / 256), dim3(256), 0, st, D, n, gate);
-        WISE_LAUNCH_CHECK("l2_flip_kernel");
-        return WISE_OK;
-    }
+    static int flip(float* D, int n, const int* gate, hipStream_t st) { return l2_flip_launch(D, n, gate, st); }
     static __device__ __forceinline__ float key_score(float s) { return -s; }
     static __device__ __forceinline__ float out_score(float ks) { return -ks; }
     static __device__ __forceinline__ bool range_hit(float s, float radius) { return s < radius; }
@@ -151,6 +147,13 @@ struct MetricL2 : PlainPolicy {
 };
 
 }  // namespace l2
+
+int l2_flip_launch(float* D, int n, const int* gate, hipStream_t st) {
+    hipLaunchKernelGGL(l2::l2_flip_kernel, dim3((n + 255) / 256), dim3(256), 0, st, D, n, gate);
+    WISE_LAUNCH_CHECK("l2_flip_kernel");
+    return WISE_OK;
+}
+
 }  // namespace wise
 
 using namespace wise;
@@ -190,6 +193,14 @@ extern "C" int wise_l2_prepare(const float* X, int64_t N, int d, uint16_t* Xb, f
     WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && norms && ((X && Xb && half) || N == 0), "l2_prepare: bad argument");
     WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Xb & 15) == 0, "l2_prepare: X and Xb must be 16-byte aligned");
     if (int rc = wise_ip_shadow_bf16(X, N, d, Xb, norms, stream)) return rc;        // the copy and the two norms
+    return wise_l2_half_norms(X, N, d, half, stream);
+}
+
+// half[r] of wise_l2_prepare alone: the h_c of the L2 coarse rule (wise_ivf_l2_coarse) over a centroid table
+extern "C" int wise_l2_half_norms(const float* X, int64_t N, int d, float* half, void* stream) {
+    WISE_CHECK_ARG(shape_ok(d), "l2_half_norms: d=%d unsupported (d %% 16 == 0 in [16, 1024])", d);
+    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && ((X && half) || N == 0), "l2_half_norms: bad argument");
+    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0, "l2_half_norms: X must be 16-byte aligned");
     if (N == 0) return WISE_OK;
     long long grid = (N + 3) / 4;
     if (grid > 2048) grid = 2048;

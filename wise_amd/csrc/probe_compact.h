@@ -39,7 +39,9 @@ struct LocalWorkspace {
 };
 
 // one wave per query: keep, in probe order, the probes whose list holds rows in this slice together with their bias;
-// count[q] = the number kept, used[q] = min(G, ceil(count / min_share)) = the probe groups the query uses
+// count[q] = the number kept, used[q] = min(G, ceil(count / min_share)) = the probe groups the query uses.  BIAS = false: a scan
+// without a bias term (wise_ivfl2_scan_local): neither bias array is touched
+template <bool BIAS>
 static __global__ __launch_bounds__(64) void compact_probes_bias_kernel(const long long* __restrict__ probes, const float* __restrict__ bias,
                                                                         int nprobe, const long long* __restrict__ list_off, int nlist, int G,
                                                                         int min_share, long long* __restrict__ out,
@@ -56,7 +58,7 @@ static __global__ __launch_bounds__(64) void compact_probes_bias_kernel(const lo
         if (keep) {
             const int o = n + __popcll(mask & ((1ull << lane) - 1ull));
             out[base + o] = l;
-            out_bias[base + o] = bias[base + i];
+            if constexpr (BIAS) out_bias[base + o] = bias[base + i];
         }
         n += __popcll(mask);
     }

@@ -5,6 +5,11 @@
 #include "topk_common.h"
 
 namespace wise {
+
+// behind a merge of keys that order -dist (l2_topk.hip): the n outputs D become distances again, the padding +3.4028235e38.
+// gate: optional device flag, nothing is done while *gate == 0
+int l2_flip_launch(float* D, int n, const int* gate, hipStream_t st);
+
 namespace ivf_sq {
 
 constexpr int SQ_T = 4;                   // wave-loads in flight per wave of the scan
@@ -87,7 +92,8 @@ struct Codec16 {
     }
 };
 
-//   CodecL2  IndexFlatL2 (l2_topk.hip): d fp32 values a row, 4 d bytes = 4 C 16-byte pieces of four floats.  Chunk c is the pieces
+//   CodecL2  IndexFlatL2 (l2_topk.hip) and the lists of IndexIVFFlatL2 (ivf_sq.hip).
+//            d fp32 values a row, 4 d bytes = 4 C 16-byte pieces of four floats.  Chunk c is the pieces
 //            c, C + c, 2 C + c and 3 C + c, i.e. element i = 0 .. 15 of the chain is e = (i / 4) (d / 4) + 4 c + i % 4: Codec16's
 //            load shape with four pieces — each of the FOUR load instructions of a wave-load reads, per row, a contiguous run of
 //            d bytes.  The "weights" are the query's own values at those elements and the chain is the squared DISTANCE:

@@ -100,6 +100,12 @@ top with faiss's IndexFlatL2 in the place of the IndexFlatIP: the inner fourcc i
 headers; everything else is the 'IxFI' layout, a bare 'IxF2' file reads with ids equal to positions, and _flat_head refuses by name
 an 'IxFI' file whose metric_type is 1 and an 'IxF2' file whose metric_type is 0.
 
+The IndexIVFFlatL2 file (write_ivf_flat_l2 / read_ivf_flat_l2 / read_ivf_flat_l2_range / ivf_flat_l2_ntotal) is faiss's
+IndexIVFFlat(IndexFlatL2(d), d, nlist, METRIC_L2): the 'IwFl' record above with metric_type 1 in its header and an 'IxF2' quantizer
+whose header says metric_type 1 too; everything else is the inner-product layout.  The record's metric_type tells the two 'IwFl'
+files apart (read_index and its siblings dispatch on it), the L2 reader's dict carries metric='l2' (write_index picks the record by
+that key), read_ivf_flat_ip refuses an L2 file at its quantizer's fourcc and the L2 readers refuse a metric-0 file by name.
+
 Under a process group with WISE_SHARDED_IVF=1 a rank's part file (`...faiss.part-RRR-of-WWW`) is a complete 'IwFl' / 'IwPQ' / 'WiPR' / 'WiOP' / 'IwSq' file
 of the rank's rows with the list sizes clipped to them; the *_range readers cut the same slice out of a single file, opening only
 the lists that overlap it.
@@ -368,14 +374,15 @@ def _ivf_arrays(centroids, ids, list_off, n: int):
     return centroids, ids, list_off
 
 
-def _write_ivf_head(f, record: str, centroids, n: int, nprobe: int) -> None:
-    """What the 'IwFl', 'IwPQ' and 'IwSq' records open with: fourcc, header, nlist, nprobe, the 'IxFI' quantizer, an empty direct map."""
+def _write_ivf_head(f, record: str, centroids, n: int, nprobe: int, metric: int = 0) -> None:
+    """What the 'IwFl', 'IwPQ' and 'IwSq' records open with: fourcc, header, nlist, nprobe, the 'IxFI' quantizer, an empty direct map.
+    metric 1 (METRIC_L2, IndexIVFFlatL2): both headers say so and the quantizer is an 'IxF2' (IndexFlatL2)."""
     nlist, d = centroids.shape
     f.write(struct.pack("<I", _fourcc(record)))
-    f.write(_header(d, n))
+    f.write(_header(d, n, metric))
     f.write(struct.pack("<QQ", nlist, nprobe))
-    f.write(struct.pack("<I", _fourcc("IxFI")))
-    f.write(_header(d, nlist))
+    f.write(struct.pack("<I", _fourcc("IxF2" if metric == 1 else "IxFI")))
+    f.write(_header(d, nlist, metric))
     f.write(struct.pack("<Q", nlist * d))
     centroids.tofile(f)
     f.write(struct.pack("<BQ", 0, 0))
@@ -450,8 +457,9 @@ def write_ivf_flat_ip(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarra
         _write_lists(f, X, ids, list_off)
 
 
-def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
+def _read_ivf_head(f, p, pq: bool = False, sq: bool = False, l2: bool = False):
     """Everything of an 'IwFl' file up to the list payload: (centroids, list_off, nprobe, start of the payload).
+    l2: an 'IwFl' record of metric_type 1 over an 'IxF2' quantizer instead (IndexIVFFlatL2); a metric-0 file is refused by name.
     pq: an 'IwPQ' file instead; the ProductQuantizer record read on the way is appended as (m, codebooks).
     sq: an 'IwSq' file instead; the ScalarQuantizer record's trained values [2d] are appended (QT_8bit), None for QT_fp16."""
     base = f.tell()                                          # (an 'IwPQ' record may sit inside a 'WiPR' file)
@@ -461,11 +469,20 @@ def _read_ivf_head(f, p, pq: bool = False, sq: bool = False):
     f.seek(base + 4 + off)
     nlist, nprobe = struct.unpack("<QQ", f.read(16))
     (cq,) = struct.unpack("<I", f.read(4))
-    if cq != _fourcc("IxFI"):
+    if l2:
+        if metric == 0 and cq == _fourcc("IxFI"):
+            raise RuntimeError(f"{p}: an IndexIVFFlat file of metric_type 0 (inner product) is not an IndexIVFFlatL2 file; "
+                               f"read_ivf_flat_ip reads it")
+        if metric != 1 or cq != _fourcc("IxF2"):
+            raise RuntimeError(f"{p}: metric_type {metric} over a coarse quantizer of type 0x{cq:08x}: an IndexIVFFlatL2 file has "
+                               f"metric_type 1 (METRIC_L2) and an IndexFlatL2 quantizer")
+    elif cq != _fourcc("IxFI"):
         raise RuntimeError(f"{p}: coarse quantizer type 0x{cq:08x}, expected IndexFlatIP")
     pos = f.tell()
     hdr = f.read(_HDR_SIZE + 4)
-    dq, nq_, _, off = _read_header(hdr, 0)
+    dq, nq_, qmetric, off = _read_header(hdr, 0)
+    if l2 and qmetric != 1:
+        raise RuntimeError(f"{p}: the IndexFlatL2 quantizer of an IndexIVFFlatL2 file says metric_type {qmetric}, expected 1")
     f.seek(pos + off)
     (cnt,) = struct.unpack("<Q", f.read(8))
     if dq != d or nq_ != nlist or cnt != nlist * d:
@@ -548,6 +565,54 @@ def read_ivf_flat_ip_range(path, lo: int, hi: int):
         centroids, list_off, nprobe, data = _read_ivf_head(f, p)
         X, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1], np.float32, lo, hi, "read_ivf_flat_ip_range")
     return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe}
+
+
+# ---------------------------------------------------------------------------------------------- 'IwFl', metric_type 1: IndexIVFFlatL2
+def write_ivf_flat_l2(path, centroids: np.ndarray, X: np.ndarray, ids: np.ndarray, list_off: np.ndarray, nprobe: int = 1) -> None:
+    """faiss's IndexIVFFlat(IndexFlatL2(d), d, nlist, METRIC_L2): the 'IwFl' record of write_ivf_flat_ip with metric_type 1 in its
+    header and an 'IxF2' quantizer (metric_type 1) holding the centroids; the raw fp32 rows in the lists, the IP layout otherwise."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    centroids, ids, list_off = _ivf_arrays(centroids, ids, list_off, X.shape[0])
+    assert X.shape == (X.shape[0], centroids.shape[1])
+    with open(path, "wb") as f:
+        _write_ivf_head(f, "IwFl", centroids, X.shape[0], nprobe, metric=1)
+        _write_lists(f, X, ids, list_off)
+
+
+def ivf_flat_metric(path) -> int:
+    """metric_type of an 'IwFl' file's header (0: inner product, IndexIVFFlat; 1: L2, IndexIVFFlatL2)."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        _expect_record(f, p, "IwFl")
+        return int(_read_header(f.read(_HDR_SIZE + 4), 0)[2])
+
+
+def read_ivf_flat_l2(path):
+    """-> dict(centroids [nlist,d], X [n,d], ids [n], list_off [nlist+1], nprobe, metric='l2'): read_ivf_flat_ip's dict for an
+    IndexIVFFlatL2 file; `metric` is the family's mark.  A metric-0 ('IndexIVFFlat') file is refused by name."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        centroids, list_off, nprobe, data = _read_ivf_head(f, p, l2=True)
+        X, ids = _read_lists(f, p, list_off, data, centroids.shape[1], np.float32)
+    return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe, "metric": "l2"}
+
+
+def ivf_flat_l2_ntotal(path) -> int:
+    """Rows of an IndexIVFFlatL2 file (its header), without reading the lists; a metric-0 file is refused as by read_ivf_flat_l2."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        _, list_off, _, _ = _read_ivf_head(f, p, l2=True)
+    return int(list_off[-1])
+
+
+def read_ivf_flat_l2_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of the list-major array read_ivf_flat_l2 returns, reading only the lists that overlap the range: as
+    read_ivf_flat_ip_range, with metric='l2'."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        centroids, list_off, nprobe, data = _read_ivf_head(f, p, l2=True)
+        X, ids, list_off = _read_lists_range(f, p, list_off, data, centroids.shape[1], np.float32, lo, hi, "read_ivf_flat_l2_range")
+    return {"centroids": centroids, "X": X, "ids": ids, "list_off": list_off, "nprobe": nprobe, "metric": "l2"}
 
 
 # ---------------------------------------------------------------------------------------------- 'IwPQ': m code bytes a row
@@ -1022,6 +1087,7 @@ def _read_sq8_state_range(path, lo, hi):
 # ---------------------------------------------------------------------------------------------- any IVF file, by its fourcc
 _BY_FOURCC = {                                    # fourcc -> (reader, range reader, ntotal)
     "IwFl": (read_ivf_flat_ip, read_ivf_flat_ip_range, ivf_flat_ip_ntotal),
+    "IwFl/L2": (read_ivf_flat_l2, read_ivf_flat_l2_range, ivf_flat_l2_ntotal),   # the record's metric_type 1: IndexIVFFlatL2
     "IwPQ": (read_ivf_pq_ip, read_ivf_pq_ip_range, ivf_pq_ip_ntotal),
     "WiPR": (read_ivf_pq_refine_ip, read_ivf_pq_refine_ip_range, ivf_pq_refine_ip_ntotal),
     "WiOP": (read_ivf_opq_ip, read_ivf_opq_ip_range, ivf_opq_ip_ntotal),
@@ -1038,14 +1104,18 @@ def _by_fourcc(path, which: int):
         cc = "IxSQ"
     if cc == "IxSQ" and flat_sq_qtype(p) == QT_8BIT:         # the record's qtype tells the two 'IxSQ' files apart
         cc = "IxSQ/8"
+    if cc == "IwFl" and ivf_flat_metric(p) == 1:             # the record's metric_type tells the two 'IwFl' files apart
+        cc = "IwFl/L2"
     if cc not in _BY_FOURCC:
-        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({', '.join(k for k in _BY_FOURCC if not k.startswith('IxSQ'))}) "
+        names = ', '.join(k for k in _BY_FOURCC if not k.startswith('IxSQ') and '/' not in k)
+        raise RuntimeError(f"{p}: index type {cc!r} is not an inverted-file index ({names}) "
                            f"nor an IndexSQfp16 file ('IxSQ', bare or inside 'IxMp') nor an IndexSQ8bit file (the same with qtype 0)")
     return _BY_FOURCC[cc][which]
 
 
 def read_index(path):
-    """The dict of the named reader of the file's record: read_ivf_flat_ip ('IwFl'), read_ivf_pq_ip ('IwPQ'), read_ivf_pq_refine_ip
+    """The dict of the named reader of the file's record: read_ivf_flat_ip ('IwFl'; read_ivf_flat_l2 where the record's metric_type is
+    1), read_ivf_pq_ip ('IwPQ'), read_ivf_pq_refine_ip
     ('WiPR'), read_ivf_opq_ip ('WiOP') or read_ivf_sq_ip ('IwSq').  (The flat 'IxMp' file holds no lists: read_idmap_flat_ip.)"""
     return _by_fourcc(path, 0)(path)
 
@@ -1062,7 +1132,8 @@ def index_ntotal(path) -> int:
 
 def write_index(path, state, nprobe=None) -> None:
     """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
-    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl'; 'halves'
+    'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl' (with
+    metric == 'l2': its metric_type 1 form); 'halves'
     without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ'), 'trained' without 'centroids' the IndexSQ8bit file.  nprobe: state's own unless given."""
     if "halves" in state and "centroids" not in state:       # IndexSQfp16: rows and ids, no lists
         return write_idmap_sq16_ip(path, state["halves"], state["ids"])
@@ -1081,6 +1152,8 @@ def write_index(path, state, nprobe=None) -> None:
         write_ivf_sq_ip(path, state["centroids"], state["trained"], state["codes"], *lists, nprobe=nprobe)
     elif "halves" in state:
         write_ivf_sq16_ip(path, state["centroids"], state["halves"], *lists, nprobe=nprobe)
+    elif "X" in state and state.get("metric") == "l2":       # IndexIVFFlatL2: the 'IwFl' record with metric_type 1
+        write_ivf_flat_l2(path, state["centroids"], state["X"], *lists, nprobe=nprobe)
     elif "X" in state:
         write_ivf_flat_ip(path, state["centroids"], state["X"], *lists, nprobe=nprobe)
     else:

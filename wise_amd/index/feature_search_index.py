@@ -25,6 +25,8 @@ one entry of FAMILIES below: what it adds to IndexIVFFlat is its trained state, 
                                      IVFOPQRefineIPIndex     of the residuals (faiss's OPQ)                               / 'WiPR'
     IndexIVFSQ8                      IVFSQIPIndex            ranges [2d]: vmin, vdiff       d code bytes (QT_8bit)        'IwSq' (faiss)
     IndexIVFSQfp16                   IVFSQfp16IPIndex        -                              d binary16 values (QT_fp16)   'IwSq' (faiss), qtype 4
+    IndexIVFFlatL2                   IVFFlatL2Index          - (plain k-means centroids)    the fp32 row; squared-L2      'IwFl' (faiss), metric_type 1,
+                                                                                            distances, ascending          'IxF2' quantizer
 
 and the exhaustive types, which have no lists and no training and are the entries of a table of their own (FLAT_TYPES below: the
 factory attribute, the shape check, the file's payload, its writer and reader, and the method that takes a file's rows):
@@ -95,7 +97,7 @@ from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .flat_l2 import FlatL2Index, check_shape as check_flat_l2_shape
 from .flat_sq import FlatSQ8IPIndex, FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape, check_sq8_shape
-from .ivf_flat import IVFFlatIPIndex, reference_nlist
+from .ivf_flat import IVFFlatIPIndex, IVFFlatL2Index, check_l2_shape, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
 from .ivf_sq import IVFSQfp16IPIndex, IVFSQIPIndex, check_sq_shape
@@ -185,11 +187,14 @@ class _Family:
     payload: str         # state key of a row's list payload
     wrapper: type        # the Sharded* class around a rank's index
     refine: bool = False  # compact rows beside the codes: 'kind', 'k_factor', 'rows', 'scales' in the state
+    extra: tuple = ()    # further (key, value) pairs of the state that are neither trained nor per-row: ('metric', 'l2') tells
+    #                      IndexIVFFlatL2's state from IndexIVFFlat's, whose payload key 'X' it shares
 
     @property
     def marks(self):
         """the state keys that tell this family's reader dict from the others' (faiss_io.write_index picks the record by them)"""
-        return {k for k, _, _ in self.trained} | ({'kind'} if self.refine else set()) | ({self.payload} - {'codes'})
+        return ({k for k, _, _ in self.trained} | ({'kind'} if self.refine else set()) | ({self.payload} - {'codes'})
+                | {k for k, _ in self.extra})
 
 
 _CENTROIDS = ('centroids', lambda index, v: index.set_centroids(v), lambda d, nlist, m: (nlist, d))
@@ -232,6 +237,8 @@ FAMILIES = (
             (_RANGES,), 'codes', ShardedIVFSQIPIndex),
     _Family(_named('IndexIVFSQfp16', check_sq_shape), lambda: IVFSQfp16IPIndex, 'ivfsqfp16_index_factory',
             lambda d, nlist, m, kind: (d, nlist), (), 'halves', ShardedIVFSQfp16IPIndex),
+    _Family(_named('IndexIVFFlatL2', check_l2_shape), lambda: IVFFlatL2Index, 'ivf_l2_index_factory', lambda d, nlist, m, kind: (d, nlist),
+            (), 'X', ShardedIVFFlatIPIndex, extra=(('metric', 'l2'),)),
 )
 _MARKS = set().union(*(fam.marks for fam in FAMILIES))
 
@@ -253,7 +260,7 @@ def _host_state(index, fam):
     if hasattr(index, 'state_host'):
         return index.state_host()
     keys = ('centroids',) + tuple(k for k, _, _ in fam.trained if k != 'rotation') + (fam.payload, 'ids', 'list_off')
-    return dict(zip(keys, index.lists_host()))
+    return dict(zip(keys, index.lists_host()), **dict(fam.extra))
 
 
 def _unknown_index_type(index_type):
@@ -346,6 +353,7 @@ class FeatureSearchIndex(SearchIndex):
     ivfopq_refine_index_factory = IVFOPQRefineIPIndex
     ivfsq_index_factory = IVFSQIPIndex
     ivfsqfp16_index_factory = IVFSQfp16IPIndex
+    ivf_l2_index_factory = IVFFlatL2Index
 
     def __init__(self, media_type, asset_id, asset):
         self.media_type = media_type
@@ -491,7 +499,7 @@ class FeatureSearchIndex(SearchIndex):
             state[key] = t.cpu().numpy()
             setter(ivf, state[key])
         # each rank assigns (and encodes) its own rows; the per-rank list counts fix the global list-major order
-        if fam is IVF_FLAT:
+        if fam.payload == 'X':                      # the fp32 row is the payload (IndexIVFFlat, IndexIVFFlatL2)
             a = ivf.assign(X)
             fields = [X]
         else:
@@ -540,7 +548,7 @@ class FeatureSearchIndex(SearchIndex):
             arr[pos] = np.ascontiguousarray(gbytes[:, b0:b0 + w]).view(f.dtype).reshape((got.shape[0],) + f.shape[1:])
             loc.append(arr)
             b0 += w
-        state.update({fam.payload: loc[0], 'ids': ids_loc, 'list_off': np.clip(list_off - lo, 0, hi - lo)})
+        state.update({fam.payload: loc[0], 'ids': ids_loc, 'list_off': np.clip(list_off - lo, 0, hi - lo)}, **dict(fam.extra))
         if fam.refine:                              # bf16 rows travel as their bit patterns; the file holds them as uint16
             state.update(kind=kind, k_factor=ivf.k_factor, rows=loc[1] if kind == 8 else loc[1].view(np.uint16),
                          scales=loc[2] if kind == 8 else None)

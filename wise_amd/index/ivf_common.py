@@ -5,6 +5,8 @@ the faiss-shaped surface around the two.
                       by inner product — what faiss's Clustering does for an inner-product IVF), run on the GPU as dense
                       products; deterministic (seeded sample for the initial centroids, empty cells re-seeded from the
                       fullest cell); the assignment of rows to lists; the probes of a query
+  L2CoarseQuantizer   the same for the L2 metric (IndexIVFFlatL2): plain k-means and the coarse rule s(x, c) - |c|^2 / 2, one path
+                      for assignment and probes
   ListStore           the payload (fp32 rows or uint8 codes) and the ids grouped by list, with the chunks added since the
                       last merge; optionally further per-row arrays kept in the same order (the compact rows a re-ranking
                       index scores its candidates from, ivf_pq.py)
@@ -122,10 +124,8 @@ class CoarseQuantizer:
         n = x.shape[0]
         if n < self.nlist:
             raise ValueError(f"train: {n} training vectors for {self.nlist} cells")
-        g = torch.Generator(device="cpu").manual_seed(self.seed)
-        perm = torch.randperm(n, generator=g)[: self.nlist].to(self.device)
         st = _lib.stream_ptr()
-        c = self._gather_rows(x, perm)
+        c = self._seed_rows(x)
         _lib.check(lib.wise_ivf_normalize_rows(c.data_ptr(), self.nlist, self.d, c.data_ptr(), st), "wise_ivf_normalize_rows")
         sums = torch.empty(self.nlist, self.d, dtype=torch.float32, device=self.device)
         for _ in range(self.niter):
@@ -133,18 +133,28 @@ class CoarseQuantizer:
             order, list_off, counts = self._group(a)
             _lib.check(lib.wise_ivf_list_sums(x.data_ptr(), order.data_ptr(), list_off.data_ptr(), self.nlist, self.d,
                                               sums.data_ptr(), st), "wise_ivf_list_sums")
-            cnt = counts.cpu().numpy()                       # nlist numbers: which cells are empty is decided on the host
-            empty = np.flatnonzero(cnt == 0)
-            if empty.size:
-                # re-seed every empty cell with a slightly perturbed copy of the fullest cells' sums (ties: the lower cell first)
-                donors = np.argsort(-cnt, kind="stable")[: empty.size]
-                e_d = torch.from_numpy(empty.astype(np.int64)).to(self.device)
-                d_d = torch.from_numpy(donors.astype(np.int64)).to(self.device)
-                _lib.check(lib.wise_ivf_reseed(sums.data_ptr(), e_d.data_ptr(), d_d.data_ptr(), int(empty.size), self.d, st),
-                           "wise_ivf_reseed")
+            self._reseed_empty(sums, counts)
             _lib.check(lib.wise_ivf_normalize_rows(sums.data_ptr(), self.nlist, self.d, c.data_ptr(), st),
                        "wise_ivf_normalize_rows")    # spherical: unit centroids
         self._install(c)
+
+    def _seed_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """[nlist, d]: the rows of x at randperm(n, seed)[:nlist], the initial centroids of either k-means, as they are"""
+        g = torch.Generator(device="cpu").manual_seed(self.seed)
+        perm = torch.randperm(x.shape[0], generator=g)[: self.nlist].to(self.device)
+        return self._gather_rows(x, perm)
+
+    def _reseed_empty(self, cells: torch.Tensor, counts: torch.Tensor) -> None:
+        """The host decision on empty cells and wise_ivf_reseed: every row of `cells` [nlist, d] (the sums, or the means of the plain
+        k-means) whose cell is empty becomes a slightly perturbed copy of a fullest cell's row (ties: the lower cell first)."""
+        cnt = counts.cpu().numpy()                           # nlist numbers: which cells are empty is decided on the host
+        empty = np.flatnonzero(cnt == 0)
+        if empty.size:
+            donors = np.argsort(-cnt, kind="stable")[: empty.size]
+            e_d = torch.from_numpy(empty.astype(np.int64)).to(self.device)
+            d_d = torch.from_numpy(donors.astype(np.int64)).to(self.device)
+            _lib.check(_lib.lib().wise_ivf_reseed(cells.data_ptr(), e_d.data_ptr(), d_d.data_ptr(), int(empty.size), self.d,
+                                                  _lib.stream_ptr()), "wise_ivf_reseed")
 
     def set_centroids(self, centroids) -> None:
         """Install a trained quantizer (file load, tests)."""
@@ -176,6 +186,83 @@ class CoarseQuantizer:
         rc = lib.wise_select_topk_f32(scores.data_ptr(), q.shape[0], self.nlist, nprobe, out.data_ptr(),
                                       _lib.stream_ptr())
         _lib.check(rc, "wise_select_topk_f32")
+        return out
+
+
+class L2CoarseQuantizer(CoarseQuantizer):
+    """The coarse stage of IndexIVFFlatL2 (ivf_flat.py: IVFFlatL2Index): the nearest centroid under squared L2, and a plain
+    (non-spherical) k-means.  THE COARSE RULE (include/wise_hip.h): g(x, c) = fl(s(x, c) - h_c), s wise_ip_scores_f32's chain and
+    h_c = |c|^2 / 2 (wise_l2_half_norms); a row goes to argmax_c g (ties: the lowest c), a query probes the nprobe largest g —
+    ONE path for every nprobe, so assignment and probing share their arithmetic and a stored row's own list is among its probes
+    at any nprobe >= 1.  Grouping, gathering, seeding and the decision on empty cells are CoarseQuantizer's."""
+
+    def __init__(self, d: int, nlist: int, device: str = "cuda"):
+        super().__init__(d, nlist, device)
+        self.half: Optional[torch.Tensor] = None         # [nlist] fp32: h_c of the installed centroids
+
+    @staticmethod
+    def half_norms(c: torch.Tensor) -> torch.Tensor:
+        half = torch.empty(c.shape[0], dtype=torch.float32, device=c.device)
+        _lib.check(_lib.lib().wise_l2_half_norms(c.data_ptr(), c.shape[0], c.shape[1], half.data_ptr(), _lib.stream_ptr()),
+                   "wise_l2_half_norms")
+        return half
+
+    @staticmethod
+    def scores_device(q: torch.Tensor, c: torch.Tensor, half: torch.Tensor, scores: torch.Tensor) -> None:
+        """scores[:nq] = g(q, c) for every (row of q, centroid)"""
+        lib, st = _lib.lib(), _lib.stream_ptr()
+        _lib.check(lib.wise_ip_scores_f32(c.data_ptr(), c.shape[0], c.shape[1], q.data_ptr(), q.shape[0], scores.data_ptr(), st),
+                   "wise_ip_scores_f32")
+        _lib.check(lib.wise_ivf_l2_coarse(scores.data_ptr(), half.data_ptr(), q.shape[0], c.shape[0], st), "wise_ivf_l2_coarse")
+
+    def assign_device(self, x: torch.Tensor, centroids: torch.Tensor, chunk: int = 4096, half: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """nearest centroid of every row by the coarse rule; half: h_c of `centroids` when the caller has it (the installed ones':
+        looked up here)"""
+        lib = _lib.lib()
+        c = centroids.contiguous()
+        if half is None:
+            half = self.half if centroids is self.centroids else self.half_norms(c)
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+        scores = torch.empty(min(chunk, max(x.shape[0], 1)), c.shape[0], dtype=torch.float32, device=x.device)
+        for s in range(0, x.shape[0], chunk):
+            q = x[s:s + chunk]
+            self.scores_device(q, c, half, scores)
+            _lib.check(lib.wise_ivf_argmax(scores.data_ptr(), q.shape[0], c.shape[0], out[s:].data_ptr(), _lib.stream_ptr()),
+                       "wise_ivf_argmax")
+        return out
+
+    def train(self, x) -> None:
+        """Plain k-means, deterministic: the seeds are rows of x as they are; `niter` times the coarse rule, wise_ivf_group,
+        wise_ivf_list_sums, wise_ivf_list_means (an empty cell keeps its sum, zeros), then on the means the decision on empty cells
+        and wise_ivf_reseed."""
+        lib = _lib.lib()
+        x = _as_tensor(x, np.float32).to(self.device, torch.float32).contiguous()
+        _rows_f32(x, self.d, "train")
+        if x.shape[0] < self.nlist:
+            raise ValueError(f"train: {x.shape[0]} training vectors for {self.nlist} cells")
+        st = _lib.stream_ptr()
+        c = self._seed_rows(x)
+        for _ in range(self.niter):
+            a = self.assign_device(x, c, half=self.half_norms(c))
+            order, list_off, counts = self._group(a)
+            _lib.check(lib.wise_ivf_list_sums(x.data_ptr(), order.data_ptr(), list_off.data_ptr(), self.nlist, self.d, c.data_ptr(), st),
+                       "wise_ivf_list_sums")
+            _lib.check(lib.wise_ivf_list_means(c.data_ptr(), counts.data_ptr(), self.nlist, self.d, c.data_ptr(), st), "wise_ivf_list_means")
+            self._reseed_empty(c, counts)
+        self._install(c)
+
+    def _install(self, c: torch.Tensor) -> None:
+        self.centroids = c.contiguous()
+        self.half = self.half_norms(self.centroids)
+        self.is_trained = True
+
+    def probes_device(self, q: torch.Tensor, nprobe: int) -> torch.Tensor:
+        """[nq, nprobe] int64 list numbers in list order: the nprobe centroids of largest g (-1 padding when nprobe > nlist)"""
+        scores = torch.empty(q.shape[0], self.nlist, dtype=torch.float32, device=self.device)
+        self.scores_device(q, self.centroids, self.half, scores)
+        out = torch.empty(q.shape[0], nprobe, dtype=torch.int64, device=self.device)
+        _lib.check(_lib.lib().wise_select_topk_f32(scores.data_ptr(), q.shape[0], self.nlist, nprobe, out.data_ptr(), _lib.stream_ptr()),
+                   "wise_select_topk_f32")
         return out
 
 
@@ -261,9 +348,12 @@ class ListStore:
 class IVFIndexBase:
     """One CoarseQuantizer (`_coarse`), one ListStore (`_lists`), and the surface both indexes show around them."""
 
+    COARSE = CoarseQuantizer      # the class of `_coarse` (IVFFlatL2Index: L2CoarseQuantizer)
+    metric = "ip"                 # 'l2': distances, ascending (IVFFlatL2Index); the sharded wrappers and range_search read it
+
     def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable,
                  extra_gathers: Sequence[Callable] = ()):
-        self._coarse = CoarseQuantizer(d, nlist, device)
+        self._coarse = self.COARSE(d, nlist, device)
         self.d, self.nlist, self.device = self._coarse.d, self._coarse.nlist, self._coarse.device
         self._lists = ListStore(self.nlist, width, dtype, self.device, gather, extra_gathers)
         self.nprobe = 1           # faiss default; the REST layer sets it (routes.py:902)
@@ -360,7 +450,8 @@ class IVFIndexBase:
         def stage(qs):
             return self._range_stage(qs, self._coarse.probes_device(qs, nprobe).contiguous(), nprobe, radius, keep)
 
-        return _range.run(q, lambda m: self._range_workspace_bytes(m, nprobe), stage, self._workspace, self._lists.ids, 0, chunk)
+        return _range.run(q, lambda m: self._range_workspace_bytes(m, nprobe), stage, self._workspace, self._lists.ids, 0, chunk,
+                          ascending=self.metric == "l2")
 
     def range_search(self, x, thresh: float, params=None):
         """faiss signature: x np.ndarray [nq,d] float32 -> (lims, D, I) numpy.  params: SearchParametersIVF(sel=..., nprobe=...);
