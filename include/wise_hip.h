@@ -48,7 +48,8 @@ const char* wise_last_error(void);
  * wise_l2_prepare, wise_l2_topk_batched and their three workspace functions), IndexFlatL2; and wise_sq_minmax and the wise_ipsq8_*
  * entry points (wise_ipsq8_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and their three workspace
  * functions), IndexSQ8bit; and the wise_ivfl2_* entry points (wise_ivfl2_scan, _scan_sel, _scan_local, _range_count / _fill and their
- * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2.  The version is 5. */
+ * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2; and wise_pqflat_topk, wise_pqflat_topk_pos (with
+ * wise_pqflat_topk_workspace_bytes) and wise_pqflat_decode, IndexPQ<m>.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -620,6 +621,35 @@ size_t wise_ipsq8_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
 int wise_ipsq8_topk_batched(const uint8_t* codes, const float* trained, const float* norms /*[1]*/, int64_t N, int d, const float* Q,
                             int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters,
                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexPQ<m>: exhaustive inner-product search over 8-bit product-quantizer codes kept in ROW order — faiss's
+ * IndexPQ(d, m, 8, METRIC_INNER_PRODUCT) under an IndexIDMap: no lists, no centroids, no residuals.  The index is codes [N, m] uint8
+ * row-major, 16-byte aligned, and the codebooks [m, 256, d / m] fp32 of the wise_pq_* entry points above, which train them, encode the
+ * rows (wise_pq_encode on the rows themselves) and build the per-query tables (wise_pq_lut).
+ *   lut      [nq, m, 256] fp32 exactly as wise_pq_lut writes it, 16-byte aligned: the entry points take the tables, not the queries
+ *            (wise_ivfpq_scan's convention; a rotation in front would change the tables only).
+ * THE SCORE IS A CONTRACT: acc = +0.0f, then acc = acc + lut[q, j, codes[r, j]] for j = 0 .. m - 1, in fp32, in that order — the bits
+ * wise_ivfpq_scan gives a row of a list whose bias is +0, and the bits of tests/ivfpq_ref.scan over one list (tests/pq_flat_ref.py).
+ *   wise_pqflat_topk: outD / outI [nq, k], descending scores, ties: the lower position wins, (-3.4028235e38, -1) padding when fewer
+ *     than k rows compete; N = 0 gives padding only.  ids == NULL writes id_base + position (id_base = 0: the positions
+ *     wise_ivf_refine takes).  nq >= 0 of any size: the call makes its own passes of 4, 2 or 1 queries, whose tables share the LDS
+ *     of a workgroup; a pass reads the N m code bytes once.  Workspace: wise_pqflat_topk_workspace_bytes(N, m, nq, k).
+ *   wise_pqflat_topk_pos: the same scan over the rows codes[pos[i]], i < n_pos <= N (pos ascending, entries in [0, N): what
+ *     wise_sel_positions writes; an entry outside [0, N) is no row).  Keys carry pos[i], so ties go to the lower position;
+ *     n_pos == 0 gives all padding.  Workspace: wise_pqflat_topk_workspace_bytes(n_pos, m, nq, k).
+ *   wise_pqflat_decode: out[i, :] = concat_j codebooks[j, codes[pos[i], j], :], exact copies (wise_pq_decode without a centroid);
+ *     a position outside [0, N) gives a row of NaN.  d, m as wise_pq_encode.
+ * Limits: 1 <= m <= 128, 1 <= k <= 2048, 0 <= N < 2^32 - 1 (keys carry a 32-bit row): WISE_E_UNSUPPORTED / a workspace of 0 bytes
+ * otherwise; a null or misaligned pointer is WISE_E_INVALID, a short workspace WISE_E_WORKSPACE, each with a wise_last_error text and
+ * nothing written.  No call allocates or reads back: all can be captured into a graph.  Deterministic, no atomics on global memory. */
+size_t wise_pqflat_topk_workspace_bytes(int64_t N, int m, int nq, int k);
+int wise_pqflat_topk(const uint8_t* codes, int64_t N, int m, const float* lut, int nq, int k, const int64_t* ids, int64_t id_base,
+                     float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_pqflat_topk_pos(const uint8_t* codes, int64_t N, int m, const int64_t* pos, int64_t n_pos, const float* lut, int nq, int k,
+                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                         void* stream);
+int wise_pqflat_decode(const uint8_t* codes, int64_t N, const int64_t* pos, int rows, const float* codebooks, int d, int m, float* out,
+                       void* stream);
 
 /* (ABI 5, additive) IndexFlatL2: exhaustive squared-L2 search over fp32 rows — faiss's IndexFlatL2(d) under an IndexIDMap.  The index
  * is X [N, d] fp32 row-major (4 d bytes a row, 16-byte aligned), the array IndexFlatIP keeps, plus the ids.  Returned distances are

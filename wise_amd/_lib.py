@@ -176,6 +176,10 @@ SIGNATURES = {
     "wise_ipsq8_prepare": (_i, [_vp, _i64, _i, _vp, _vp]),
     "wise_ipsq8_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_ipsq8_topk_batched": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_pqflat_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_pqflat_topk": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_pqflat_topk_pos": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_pqflat_decode": (_i, [_vp, _i64, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "wise_l2_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_l2_topk_f32": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
     "wise_l2_topk_pos_f32": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),

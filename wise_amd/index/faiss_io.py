@@ -95,6 +95,29 @@ The record's qtype tells the two 'IxSQ' files apart (flat_sq_qtype); every field
 with code_size 2d or without trained values is refused by file name, and neither reader takes the other's file.  read_index gives
 dict(trained, codes, ids), and write_index writes the file for a state of 'trained', 'codes' and 'ids' without 'centroids'.
 
+The file of index types 'IndexPQ<m>' (write_idmap_pq_ip / read_idmap_pq_ip, _range, idmap_pq_ip_ntotal) restates faiss's
+IndexIDMap(IndexPQ(d, m, 8, METRIC_INNER_PRODUCT)) record — product-quantizer codes in row order, no lists:
+
+    u32  'IxMp' | header | u32 'IxPq' | header(d, ntotal, ..., metric_type 0)
+    u64  d | u64 M | u64 nbits (8) | u64 n_floats (= 256 d) | f32[M*256*dsub]     the ProductQuantizer record of 'IwPQ'
+    u64  n_bytes (= ntotal*m) | u8[ntotal*m]                                     codes
+    i32  search_type (0 = ST_PQ) | u8 encode_signs (0) | i32 polysemous_ht (8 m + 1, faiss's constructor default)
+    u64  ntotal | i64[ntotal]                                                    id_map
+
+The codes are memory-mapped on read; a bare 'IxPq' file (no id map) reads with ids equal to positions.  read_index gives
+dict(codebooks, codes, ids), and write_index writes the file for a state of 'codebooks', 'codes' and 'ids' without 'centroids'.
+
+The file of index types 'IndexPQ<m>R8' / 'IndexPQ<m>R16' (write_pq_refine_ip / read_pq_refine_ip, _range, pq_refine_ip_ntotal) is THIS
+REPOSITORY'S OWN FORMAT, modelled on 'WiPR':
+
+    u32  'WiFR' | u32 version (1) | u32 kind (8 or 16) | u32 k_factor
+    the complete 'IxMp' record above
+    u64  n_bytes | the compact rows in row order: i8[N*d] (kind 8) or bf16[N*d] (kind 16)
+    u64  N | f32[N]                                                               the row scales (kind 8 only)
+
+Every reader of either refuses a foreign, truncated or mismatched file by file name (n_bytes != ntotal*m, n_floats != 256 d,
+nbits != 8, an id map of another length, ...).
+
 The file of index type 'IndexFlatL2' (write_idmap_flat_l2 / read_idmap_flat_l2, _range, idmap_flat_l2_ntotal) is the flat file at the
 top with faiss's IndexFlatL2 in the place of the IndexFlatIP: the inner fourcc is 'IxF2' and metric_type is 1 (METRIC_L2) in both
 headers; everything else is the 'IxFI' layout, a bare 'IxF2' file reads with ids equal to positions, and _flat_head refuses by name
@@ -945,7 +968,8 @@ def read_ivf_sq_ip_range(path, lo: int, hi: int):
 
 def index_fourcc(path, inner: bool = False) -> str:
     """The fourcc the file opens with; inner: for an 'IxMp' (IndexIDMap) file the fourcc of the index it wraps — 'IxFI' for
-    IndexFlatIP, 'IxF2' for IndexFlatL2, 'IxSQ' for IndexSQfp16 — ('' where the file ends before it), for any other file its own."""
+    IndexFlatIP, 'IxF2' for IndexFlatL2, 'IxSQ' for IndexSQfp16, 'IxPq' for IndexPQ<m> — ('' where the file ends before it), for any
+    other file its own ('WiFR' for IndexPQ<m>R8 / R16)."""
     with open(path, "rb") as f:
         head = f.read(_FLAT_HEAD_BYTES if inner else 4)
     if not inner or head[:4] != b"IxMp":
@@ -1084,6 +1108,212 @@ def _read_sq8_state_range(path, lo, hi):
     return {"trained": trained, "codes": C, "ids": ids}
 
 
+# ---------------------------------------------------------------------------------------------- 'IxMp' around 'IxPq': m code bytes a row, no lists
+def _pq_flat_arrays(codebooks, codes, ids):
+    codebooks = np.ascontiguousarray(codebooks, dtype="<f4")
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    assert codes.ndim == 2 and codebooks.ndim == 3
+    n, m = codes.shape
+    assert ids.shape == (n,) and codebooks.shape[:2] == (m, 256) and codebooks.shape[2] >= 1
+    return codebooks, codes, ids
+
+
+def _write_idmap_pq_record(f, codebooks, codes, ids) -> None:
+    (n, m), d = codes.shape, codebooks.shape[0] * codebooks.shape[2]
+    f.write(struct.pack("<I", _fourcc("IxMp")))
+    f.write(_header(d, n))
+    f.write(struct.pack("<I", _fourcc("IxPq")))
+    f.write(_header(d, n))
+    f.write(struct.pack("<QQQQ", d, m, 8, 256 * d))          # ProductQuantizer: d, M, nbits, centroids
+    codebooks.tofile(f)
+    f.write(struct.pack("<Q", n * m))                        # codes
+    codes.tofile(f)
+    f.write(struct.pack("<iBi", 0, 0, 8 * m + 1))            # search_type ST_PQ, encode_signs, polysemous_ht
+    f.write(struct.pack("<Q", n))
+    ids.tofile(f)
+
+
+def write_idmap_pq_ip(path, codebooks: np.ndarray, codes: np.ndarray, ids: np.ndarray) -> None:
+    """codebooks [m,256,d/m] float32, codes [n,m] uint8, ids [n] int64: IndexIDMap around IndexPQ(d, m, 8, inner product) — faiss's
+    layout of index types 'IndexPQ<m>'."""
+    with open(path, "wb") as f:
+        _write_idmap_pq_record(f, *_pq_flat_arrays(codebooks, codes, ids))
+
+
+class _PQFlatHead(NamedTuple):
+    """The head of an 'IxPq' record, bare or inside 'IxMp' (_pq_flat_head); offsets are absolute."""
+    d: int
+    m: int
+    n: int
+    codebooks: np.ndarray
+    off: int             # of the codes
+    idmap: bool
+    end: int             # of the record
+
+
+_PQ_TAIL = struct.calcsize("<iBi")
+
+
+def _pq_flat_head(f, p, size: int) -> _PQFlatHead:
+    """Parse the 'IxPq' record the open file stands at, up to its codes; RuntimeError naming the file for anything else or a record
+    that contradicts itself or ends early."""
+    base = f.tell()
+    try:
+        head = f.read(4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4))
+        cc, inner, off, d0, n0 = _flat_outer(head)
+        idmap = cc == _fourcc("IxMp")
+        if inner != _fourcc("IxPq"):
+            raise RuntimeError(f"{p}: index type 0x{inner:08x} is not IndexPQ ('IxPq', bare or inside 'IxMp')")
+        d, n, metric, off = _read_header(head, off)
+        f.seek(base + off)
+        dp, m, nbits, cnt = struct.unpack("<QQQQ", f.read(32))
+    except struct.error as e:
+        raise RuntimeError(f"{p}: the head of an IndexPQ file is cut short ({e})") from None
+    if metric != 0 or (idmap and struct.unpack_from("<i", head, 4 + _HDR_SIZE - 4)[0] != 0):
+        raise RuntimeError(f"{p}: an IndexPQ file with metric_type {metric}: inner product (metric_type 0) is what is read")
+    if nbits != 8 or d < 1 or dp != d or m < 1 or m > d or d % m or cnt != 256 * d or n < 0 or (idmap and (d0 != d or n0 != n)):
+        raise RuntimeError(f"{p}: unsupported IndexPQ (d={dp} under a header of d={d}, M={m}, nbits={nbits}, {cnt} codebook values, "
+                           f"{n} rows): 8-bit codes with 256 d codebook values are what is read")
+    codebooks = np.fromfile(f, dtype="<f4", count=int(cnt))
+    tail = f.read(8)
+    if codebooks.size != cnt or len(tail) != 8:
+        raise RuntimeError(f"{p}: the codebooks of an IndexPQ file are cut short")
+    (nbytes,) = struct.unpack("<Q", tail)
+    if nbytes != n * m:
+        raise RuntimeError(f"{p}: {nbytes} code bytes for {n} x {m} 8-bit codes")
+    off = f.tell()
+    end = off + n * m + _PQ_TAIL + ((8 + 8 * n) if idmap else 0)
+    if size < end:
+        raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {end} promised by its header)")
+    return _PQFlatHead(int(d), int(m), int(n), codebooks.astype(np.float32).reshape(m, 256, d // m), int(off), idmap, int(end))
+
+
+def _pq_flat_ids(f, p, head: _PQFlatHead, lo: int, hi: int):
+    if not head.idmap:
+        return np.arange(lo, hi, dtype=np.int64)
+    f.seek(head.off + head.n * head.m + _PQ_TAIL)
+    (nid,) = struct.unpack("<Q", f.read(8))
+    if nid != head.n:
+        raise RuntimeError(f"{p}: id_map has {nid} entries for {head.n} rows")
+    f.seek(8 * lo, 1)
+    ids = np.fromfile(f, dtype=np.int64, count=hi - lo)
+    if ids.size != hi - lo:
+        raise RuntimeError(f"{p}: the id_map is cut short ({ids.size} of {hi - lo} ids)")
+    return ids
+
+
+def _read_idmap_pq_record(f, p, lo=None, hi=None, mmap: bool = True, who: str = "read_idmap_pq_ip_range"):
+    """(dict(codebooks, codes, ids) of rows [lo, hi) — default all, the codes then a memmap view unless mmap is False —, the head)
+    of the 'IxPq' record the open file stands at."""
+    head = _pq_flat_head(f, p, p.stat().st_size)
+    whole = lo is None
+    lo, hi = (0, head.n) if whole else (int(lo), int(hi))
+    if not (0 <= lo <= hi <= head.n):
+        raise ValueError(f"{who}: [{lo}, {hi}) outside [0, {head.n}]")
+    if whole and mmap and head.n:
+        codes = np.memmap(p, dtype=np.uint8, mode="r", offset=head.off, shape=(head.n, head.m))
+    else:
+        codes = np.fromfile(p, dtype=np.uint8, count=(hi - lo) * head.m, offset=head.off + lo * head.m).reshape(hi - lo, head.m)
+    return {"codebooks": head.codebooks, "codes": codes, "ids": _pq_flat_ids(f, p, head, lo, hi)}, head
+
+
+def read_idmap_pq_ip(path, mmap: bool = True):
+    """-> dict(codebooks [m,256,d/m] float32, codes [n,m] uint8 (a memmap view unless mmap is False), ids int64[n]) of an IndexPQ<m>
+    file; a bare 'IxPq' file (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated, foreign or
+    self-contradicting file."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        return _read_idmap_pq_record(f, p, mmap=mmap)[0]
+
+
+def read_idmap_pq_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of what read_idmap_pq_ip returns, reading only those codes and ids; the codebooks are whole."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        return _read_idmap_pq_record(f, p, lo, hi)[0]
+
+
+def idmap_pq_ip_ntotal(path) -> int:
+    """Rows of an IndexPQ<m> file (its header)."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        return _pq_flat_head(f, p, p.stat().st_size).n
+
+
+# ---------------------------------------------------------------------------------------------- 'WiFR': an 'IxPq' record + compact rows
+def write_pq_refine_ip(path, codebooks, codes, ids, kind: int, k_factor: int, rows: np.ndarray, scales=None) -> None:
+    """The 'IxMp' / 'IxPq' record plus the compact rows of a re-ranking index in the same row order: rows [n,d] int8 with scales [n]
+    fp32 (kind 8) or rows [n,d] uint16 bf16 bit patterns (kind 16).  This repository's own format (module docstring)."""
+    codebooks, codes, ids = _pq_flat_arrays(codebooks, codes, ids)
+    rows, scales = _refine_arrays(codes.shape[0], codebooks.shape[0] * codebooks.shape[2], kind, k_factor, rows, scales)
+    with open(path, "wb") as f:
+        f.write(struct.pack("<IIII", _fourcc("WiFR"), 1, kind, k_factor))
+        _write_idmap_pq_record(f, codebooks, codes, ids)
+        f.write(struct.pack("<Q", rows.nbytes))
+        rows.tofile(f)
+        if kind == 8:
+            f.write(struct.pack("<Q", rows.shape[0]))
+            scales.tofile(f)
+
+
+def _read_pq_refine_head(f, p):
+    head = f.read(16)
+    if len(head) != 16:
+        raise RuntimeError(f"{p}: the head of a re-ranking IndexPQ file is cut short")
+    cc, version, kind, k_factor = struct.unpack("<IIII", head)
+    if cc != _fourcc("WiFR") or version != 1 or kind not in (8, 16) or k_factor < 1:
+        raise RuntimeError(f"{p}: not a re-ranking IndexPQ file (type 0x{cc:08x}, version {version}, kind {kind}, k_factor {k_factor})")
+    return int(kind), int(k_factor)
+
+
+def _read_pq_refine(path, lo=None, hi=None, mmap: bool = True):
+    p = _existing(path)
+    size = p.stat().st_size
+    with open(p, "rb") as f:
+        kind, k_factor = _read_pq_refine_head(f, p)
+        out, head = _read_idmap_pq_record(f, p, lo, hi, mmap, "read_pq_refine_ip_range")
+        lo, hi = (0, head.n) if lo is None else (int(lo), int(hi))
+        n, d = head.n, head.d
+        width = d * (1 if kind == 8 else 2)
+        if size < head.end + 8 + n * width + ((8 + 4 * n) if kind == 8 else 0):
+            raise RuntimeError(f"{p}: the file is cut short ({size} bytes: the compact rows of {n} x {d} of kind {kind} do not fit)")
+        f.seek(head.end)
+        (nbytes,) = struct.unpack("<Q", f.read(8))
+        if nbytes != n * width:
+            raise RuntimeError(f"{p}: {nbytes} bytes of compact rows for {n} x {d} of kind {kind}")
+        f.seek(head.end + 8 + lo * width)
+        rows = np.fromfile(f, dtype=np.int8 if kind == 8 else np.uint16, count=(hi - lo) * d).reshape(hi - lo, d)
+        scales = None
+        if kind == 8:
+            f.seek(head.end + 8 + n * width)
+            (ns,) = struct.unpack("<Q", f.read(8))
+            if ns != n:
+                raise RuntimeError(f"{p}: {ns} scales for {n} rows")
+            f.seek(4 * lo, 1)
+            scales = np.fromfile(f, dtype=np.float32, count=hi - lo)
+    out.update(kind=kind, k_factor=k_factor, rows=rows, scales=scales)
+    return out
+
+
+def read_pq_refine_ip(path, mmap: bool = True):
+    """-> the dict of read_idmap_pq_ip plus kind, k_factor, rows [n,d] (int8 / uint16 bf16 bits) and scales [n] (None for kind 16)."""
+    return _read_pq_refine(path, mmap=mmap)
+
+
+def read_pq_refine_ip_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of what read_pq_refine_ip returns, read by position; the codebooks are whole."""
+    return _read_pq_refine(path, lo, hi)
+
+
+def pq_refine_ip_ntotal(path) -> int:
+    """Rows of a 'WiFR' file (the header of its 'IxPq' record)."""
+    p = _existing(path)
+    with open(p, "rb") as f:
+        _read_pq_refine_head(f, p)
+        return _pq_flat_head(f, p, p.stat().st_size).n
+
+
 # ---------------------------------------------------------------------------------------------- any IVF file, by its fourcc
 _BY_FOURCC = {                                    # fourcc -> (reader, range reader, ntotal)
     "IwFl": (read_ivf_flat_ip, read_ivf_flat_ip_range, ivf_flat_ip_ntotal),
@@ -1095,6 +1325,10 @@ _BY_FOURCC = {                                    # fourcc -> (reader, range rea
     "IxSQ": (_read_sq16_state, _read_sq16_state_range, idmap_sq16_ip_ntotal),      # IndexSQfp16: no lists, dict(halves, ids)
     "IxSQ/8": (_read_sq8_state, _read_sq8_state_range, idmap_sq8_ip_ntotal),      # IndexSQ8bit: no lists, dict(trained, codes, ids)
 }
+_BY_FOURCC_PQ_FLAT = {                            # the list-less product-quantizer files: dict(codebooks, codes, ids[, kind, ...])
+    "IxPq": (read_idmap_pq_ip, read_idmap_pq_ip_range, idmap_pq_ip_ntotal),
+    "WiFR": (read_pq_refine_ip, read_pq_refine_ip_range, pq_refine_ip_ntotal),
+}
 
 
 def _by_fourcc(path, which: int):
@@ -1102,6 +1336,10 @@ def _by_fourcc(path, which: int):
     cc = index_fourcc(p)
     if cc == "IxMp" and index_fourcc(p, inner=True) == "IxSQ":
         cc = "IxSQ"
+    if cc == "IxMp" and index_fourcc(p, inner=True) == "IxPq":
+        cc = "IxPq"
+    if cc in _BY_FOURCC_PQ_FLAT:
+        return _BY_FOURCC_PQ_FLAT[cc][which]
     if cc == "IxSQ" and flat_sq_qtype(p) == QT_8BIT:         # the record's qtype tells the two 'IxSQ' files apart
         cc = "IxSQ/8"
     if cc == "IwFl" and ivf_flat_metric(p) == 1:             # the record's metric_type tells the two 'IwFl' files apart
@@ -1134,11 +1372,17 @@ def write_index(path, state, nprobe=None) -> None:
     """The inverse of read_index: `state` is a dict with a reader's keys, and the keys pick the record — 'rotation': 'WiOP'; else
     'kind': 'WiPR'; else 'codebooks': 'IwPQ'; else 'trained': 'IwSq'; else 'halves': 'IwSq' with QT_fp16; else 'X': 'IwFl' (with
     metric == 'l2': its metric_type 1 form); 'halves'
-    without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ'), 'trained' without 'centroids' the IndexSQ8bit file.  nprobe: state's own unless given."""
+    without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ'), 'trained' without 'centroids' the IndexSQ8bit file,
+    'codebooks' without 'centroids' the IndexPQ<m> file ('IxMp' around 'IxPq'; with 'kind' its 'WiFR' form).  nprobe: state's own unless given."""
     if "halves" in state and "centroids" not in state:       # IndexSQfp16: rows and ids, no lists
         return write_idmap_sq16_ip(path, state["halves"], state["ids"])
     if "trained" in state and "centroids" not in state:      # IndexSQ8bit: ranges, codes and ids, no lists
         return write_idmap_sq8_ip(path, state["trained"], state["codes"], state["ids"])
+    if "codebooks" in state and "centroids" not in state:    # IndexPQ<m> (with 'kind': its R8 / R16 form): codebooks, codes and ids, no lists
+        if "kind" in state:
+            return write_pq_refine_ip(path, state["codebooks"], state["codes"], state["ids"], state["kind"], state["k_factor"],
+                                      state["rows"], state.get("scales"))
+        return write_idmap_pq_ip(path, state["codebooks"], state["codes"], state["ids"])
     nprobe = state.get("nprobe", 1) if nprobe is None else nprobe
     lists = (state["ids"], state["list_off"])
     store = {k: state[k] for k in ("kind", "k_factor", "rows", "scales") if k in state}

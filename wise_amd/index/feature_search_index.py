@@ -37,6 +37,20 @@ factory attribute, the shape check, the file's payload, its writer and reader, a
     IndexFlatL2 (flat_l2.py)         FlatL2Index                                 the fp32 row; squared-L2 distances, ascending           'IxMp' around 'IxF2' (faiss), metric_type 1
     IndexSQ8bit                      FlatSQ8IPIndex                              d code bytes (QT_8bit) under ranges [2d]: vmin, vdiff   'IxMp' around 'IxSQ' (faiss), qtype 0
 
+and the exhaustive product-quantizer types (flat_pq.py), which have no lists but are trained, and so are neither a FAMILIES entry nor a
+FLAT_TYPES entry: parse_pq_flat_type reads their names, `^IndexPQ([1-9][0-9]*)(R8|R16)?$` (the code size is always named):
+
+    index type (example)             class (flat_pq.py)                          a row in HBM and in the file                            file record (faiss_io.py)
+    IndexPQ<m> (IndexPQ64)           FlatPQIPIndex                               m code bytes under codebooks [m,256,d/m]                'IxMp' around 'IxPq' (faiss)
+    IndexPQ<m>R8                     FlatPQRefineIPIndex                         codes + an int8 row and a scale to re-rank from         'WiFR' (own) around 'IxMp' / 'IxPq'
+    IndexPQ<m>R16                    FlatPQRefineIPIndex                         codes + a bf16 row to re-rank from                      'WiFR' (own) around 'IxMp' / 'IxPq'
+
+create_index trains their codebooks on the seeded sample of the store an inverted-file build draws (_training_plan: min(N, 100 nlist)
+rows), encodes every row on the GPU in chunks of 2^20 and writes codebooks, codes (and compact rows) and ids; load_index hands the
+file's codebooks to the index before its codes; update_index adds against the codebooks as trained, and k_factor stays.  Under a process
+group they behave as the inverted-file families do WITHOUT WISE_SHARDED_IVF: rank 0 builds the one file and every rank loads the
+whole file (row-sharding them is not built).
+
 IndexSQ8bit is the one exhaustive type that carries a trained vector: create_index trains its ranges over EVERY row of the store (a
 minimum and a maximum per dimension are exact and order-free, so nothing clamps at build), encodes the rows on the GPU and writes
 ranges, codes and ids; load_index hands the file's ranges to the index before its codes; update_index adds against the ranges as
@@ -85,6 +99,7 @@ then list 1's, ...):
     ranges are replicated, so every rank rotates and encodes its own rows and queries.
 """
 import os
+import re
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Callable
@@ -96,6 +111,7 @@ from ..feature.store.feature_store_factory import FeatureStoreFactory
 from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .flat_l2 import FlatL2Index, check_shape as check_flat_l2_shape
+from .flat_pq import FlatPQIPIndex, FlatPQRefineIPIndex
 from .flat_sq import FlatSQ8IPIndex, FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape, check_sq8_shape
 from .ivf_flat import IVFFlatIPIndex, IVFFlatL2Index, check_l2_shape, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
@@ -172,6 +188,24 @@ def parse_ivfopq_type(index_type, feature_dim=None):
 def parse_ivfopq_refine_type(index_type, feature_dim=None):
     """(m, kind) of 'IndexIVFOPQ<m>R<kind>', as parse_ivfpq_refine_type; None for any other index type."""
     return parse_ivfpq_refine_type(index_type, feature_dim, 'IndexIVFOPQ')
+
+
+_PQ_FLAT_NAME = re.compile(r'^IndexPQ([1-9][0-9]*)(R8|R16)?$')
+
+
+def parse_pq_flat_type(index_type, feature_dim=None):
+    """(m, kind) of 'IndexPQ<m>' / 'IndexPQ<m>R8' / 'IndexPQ<m>R16' ('IndexPQ64' -> (64, None), 'IndexPQ64R8' -> (64, 8)), the
+    exhaustive product-quantizer types; None for any other index type — the bare 'IndexPQ', a leading zero and any other suffix among
+    them.  With feature_dim the shapes of the codes and of the store are checked (ValueError)."""
+    hit = _PQ_FLAT_NAME.fullmatch(index_type)            # (match() would let a trailing newline through at '$')
+    if hit is None:
+        return None
+    m, kind = int(hit.group(1)), (int(hit.group(2)[1:]) if hit.group(2) else None)
+    if feature_dim is not None:
+        check_pq_shape(feature_dim, m)
+        if kind is not None:
+            check_refine_shape(feature_dim, kind)
+    return m, kind
 
 
 @dataclass(frozen=True)
@@ -346,6 +380,8 @@ class FeatureSearchIndex(SearchIndex):
     flat_sqfp16_index_factory = FlatSQfp16IPIndex
     flat_l2_index_factory = FlatL2Index
     flat_sq8_index_factory = FlatSQ8IPIndex
+    flat_pq_index_factory = FlatPQIPIndex
+    flat_pq_refine_index_factory = FlatPQRefineIPIndex
     ivf_index_factory = IVFFlatIPIndex
     ivfpq_index_factory = IVFPQIPIndex
     ivfpq_refine_index_factory = IVFPQRefineIPIndex
@@ -385,6 +421,7 @@ class FeatureSearchIndex(SearchIndex):
         rank, world, sharded = _dist_rank_world()
         fam = _family(index_type)                   # None: an exhaustive type (or a name refused below)
         flat = FLAT_TYPES.get(index_type)
+        pq_flat = parse_pq_flat_type(index_type)    # (m, kind) of an exhaustive product-quantizer type
         sharded_ivf = sharded and fam is not None and _sharded_ivf_on()
         if sharded and (index_type in FLAT_TYPES or sharded_ivf):
             index_fn = self.get_index_part_filename(index_type, rank, world)
@@ -398,10 +435,10 @@ class FeatureSearchIndex(SearchIndex):
         if exists and overwrite is False:
             print(f'{index_type} for {self.media_type} already exists')
             return
-        if index_type not in FLAT_TYPES and fam is None:
+        if index_type not in FLAT_TYPES and fam is None and pq_flat is None:
             raise _unknown_index_type(index_type)
         self.index_type = index_type
-        if sharded and fam is not None and not sharded_ivf and rank != 0:
+        if sharded and ((fam is not None and not sharded_ivf) or pq_flat is not None) and rank != 0:
             return                                  # k-means needs every row: one rank builds the one file
 
         feature_store = FeatureStoreFactory.load_store(self.media_type, self.features_dir)
@@ -412,6 +449,8 @@ class FeatureSearchIndex(SearchIndex):
         feature_dim = feature_store.feature_dim
         if fam is not None:                         # a bad shape is refused before any row is read
             pq_m, kind = fam.parse(index_type, feature_dim)
+        elif pq_flat is not None:
+            parse_pq_flat_type(index_type, feature_dim)
         elif flat.check is not None:
             flat.check(feature_dim)
 
@@ -430,6 +469,8 @@ class FeatureSearchIndex(SearchIndex):
             for s0 in range(0, n, 1 << 20):
                 ivf.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
             faiss_io.write_index(index_fn, _host_state(ivf, fam), nprobe=ivf.nprobe)
+        elif pq_flat is not None:
+            self._create_pq_flat(X, ids, index_fn, index_type, *pq_flat)
         elif flat.trained:
             self._create_trained_flat(flat, X, ids, index_fn, sharded)
         else:
@@ -452,6 +493,25 @@ class FeatureSearchIndex(SearchIndex):
         index.set_minmax(lohi)
         index.reserve(X.shape[0])
         for s0 in range(0, X.shape[0], 1 << 20):
+            index.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
+        self._write_index_file(index, index_fn)
+
+    def _new_pq_flat(self, d, m, kind, k_factor=None):
+        """The index object of an exhaustive product-quantizer type, from its factory attribute."""
+        if kind is None:
+            return self.flat_pq_index_factory(d, m)
+        return self.flat_pq_refine_index_factory(d, m, kind, **({} if k_factor is None else {'k_factor': k_factor}))
+
+    def _create_pq_flat(self, X, ids, index_fn, index_type, m, kind):
+        """The build of IndexPQ<m> and its R8 / R16 forms: the codebooks from the seeded sample an inverted-file build trains on, then
+        every row encoded by the index object in chunks of 2^20, and its file."""
+        n = X.shape[0]
+        _, train_count, sample = _training_plan(n)
+        print(f'  training {index_type} index with {train_count} features ...')
+        index = self._new_pq_flat(X.shape[1], m, kind)
+        index.train(X[sample])
+        index.reserve(n)
+        for s0 in range(0, n, 1 << 20):
             index.add_with_ids(X[s0:s0 + (1 << 20)], ids[s0:s0 + (1 << 20)])
         self._write_index_file(index, index_fn)
 
@@ -615,6 +675,8 @@ class FeatureSearchIndex(SearchIndex):
         shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
         if fn.exists() and faiss_io.index_fourcc(fn) in self.IVF_FOURCCS:
             return self._local_index(faiss_io.read_index(fn))[1]
+        if self._is_pq_flat_file(fn):
+            return self._pq_flat_from_file(fn)
         inner = faiss_io.index_fourcc(fn, inner=True) if fn.exists() else None
         qtype = faiss_io.flat_sq_qtype(fn) if inner == 'IxSQ' else None       # the two 'IxSQ' files differ in their record's qtype
         flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner and t.qtype == qtype),
@@ -632,10 +694,30 @@ class FeatureSearchIndex(SearchIndex):
         return index
 
     @staticmethod
+    def _is_pq_flat_file(fn):
+        """an IndexPQ<m> file ('IxMp' around 'IxPq', or the bare record) or the 'WiFR' file of its R8 / R16 forms"""
+        return fn.exists() and (faiss_io.index_fourcc(fn) == 'WiFR' or faiss_io.index_fourcc(fn, inner=True) == 'IxPq')
+
+    def _pq_flat_from_file(self, fn):
+        """An IndexPQ<m> / IndexPQ<m>R8 / R16 file -> its index object: the codebooks first, then the memory-mapped codes (and the
+        compact rows) streamed into HBM as they are, 2^20 rows at a time."""
+        f = faiss_io.read_index(fn)
+        m, _, dsub = f['codebooks'].shape
+        index = self._new_pq_flat(m * dsub, m, f.get('kind'), f.get('k_factor'))
+        index.set_codebooks(f['codebooks'])
+        n = f['codes'].shape[0]
+        index.reserve(n)
+        for s in range(0, n, 1 << 20):
+            e = min(s + (1 << 20), n)
+            extra = {} if 'kind' not in f else {'rows': f['rows'][s:e], 'scales': None if f['scales'] is None else f['scales'][s:e]}
+            index.add_codes_with_ids(np.ascontiguousarray(f['codes'][s:e]), f['ids'][s:e], **extra)
+        return index
+
+    @staticmethod
     def _write_index_file(index, fn):
         """index object -> file (the inverse of _index_from_file)."""
-        if hasattr(index, 'state_host'):                 # an inverted-file index
-            return faiss_io.write_index(fn, index.state_host(), nprobe=index.nprobe)
+        if hasattr(index, 'state_host'):                 # an inverted-file index, or an exhaustive product-quantizer one (no nprobe)
+            return faiss_io.write_index(fn, index.state_host(), nprobe=getattr(index, 'nprobe', None))
         payload, ids = index.rows_host()                 # an exhaustive one: its payload's dtype and its metric name the type
         metric = getattr(index, 'metric', 'ip')
         flat = next((t for t in FLAT_TYPES.values() if t.dtype == payload.dtype and t.metric == metric), None)
@@ -653,7 +735,7 @@ class FeatureSearchIndex(SearchIndex):
         temporary name beside it and renamed over it.  Returns (n_added, n_removed); with nothing to do the file is left
         alone.  The feature extractor is not built.  A `self.index` loaded from that file before the call is stale
         afterwards: call load_index again.  Lists are not rebalanced and nothing is retrained, however many updates pile up."""
-        if index_type not in FLAT_TYPES and _family(index_type) is None:
+        if index_type not in FLAT_TYPES and _family(index_type) is None and parse_pq_flat_type(index_type) is None:
             raise _unknown_index_type(index_type)
         if _dist_rank_world()[2]:
             raise NotImplementedError('update_index under a sharded process group is not built (a collective removal is not): '
@@ -707,7 +789,7 @@ class FeatureSearchIndex(SearchIndex):
         elif sharded and _sharded_ivf_on() and index_fn.exists() and faiss_io.index_fourcc(index_fn) == 'IwFl':
             lo, hi = shard_range(faiss_io.index_ntotal(index_fn), rank, world)
             index = self._sharded_ivf_index(faiss_io.read_index_range(index_fn, lo, hi))
-        elif index_fn.exists() and faiss_io.index_fourcc(index_fn) in self.IVF_FOURCCS:
+        elif index_fn.exists() and (faiss_io.index_fourcc(index_fn) in self.IVF_FOURCCS or self._is_pq_flat_file(index_fn)):
             index = self._index_from_file(index_fn)   # unsharded: every rank of a process group loads the whole file
         else:
             if sharded and part_fn.exists():         # built by this many ranks: a rank's part is its shard

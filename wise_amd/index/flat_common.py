@@ -1,4 +1,4 @@
-"""What the exhaustive indexes (flat_ip.py, flat_sq.py, flat_l2.py) are made of: one row store and the faiss-shaped surface around it.
+"""What the exhaustive indexes (flat_ip.py, flat_sq.py, flat_l2.py, flat_pq.py) are made of: one row store and the faiss-shaped surface around it.
 
   RowStore        ONE [N, d] payload tensor of one dtype (fp32 rows, binary16 rows) and its ids: the tensors reserved up front and
                   their fill mark, the chunks added since the last merge, rows adopted as they are, the implicit ids
@@ -190,9 +190,13 @@ class FlatIndexBase:
         if c is None:
             return 0
         self._store.compact(c)
+        self._compact_extra(c)
         self._rows_changed()
         self._mutations = getattr(self, "_mutations", 0) + 1
         return c.n - c.kept
+
+    def _compact_extra(self, c: "_mutate.RowCompaction") -> None:
+        """remove_ids: further per-row arrays of the subclass go through the same plan (flat_pq.py: the compact rows and scales)"""
 
     def rows_host(self):
         """(payload [N,d], ids [N] int64) on the host: what the index file holds."""

@@ -90,7 +90,46 @@ def _gather_scales(scales: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
-class IVFPQIPIndex(CodedIVFIndexBase):
+class PQCodebooks:
+    """The codebook trainer the product-quantizer indexes share (IVFPQIPIndex trains on residuals, flat_pq.py's FlatPQIPIndex on
+    the rows themselves): what it is given are `resid` [n, d] fp32 rows on the device, in training order.  The index supplies d, m,
+    dsub, device, niter and the attribute `codebooks`."""
+
+    def _encode(self, resid: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+        codes = torch.empty(resid.shape[0], self.m, dtype=torch.uint8, device=self.device)
+        _lib.check(_lib.lib().wise_pq_encode(resid.data_ptr(), codebooks.data_ptr(), resid.shape[0], self.d, self.m, codes.data_ptr(),
+                                             _lib.stream_ptr()), "wise_pq_encode")
+        return codes
+
+    def _update(self, resid: torch.Tensor, codes: torch.Tensor, cb_in: torch.Tensor) -> torch.Tensor:
+        cb_out = torch.empty_like(cb_in)
+        _lib.check(_lib.lib().wise_pq_update(resid.data_ptr(), codes.data_ptr(), resid.shape[0], self.d, self.m, cb_in.data_ptr(),
+                                             cb_out.data_ptr(), _lib.stream_ptr()), "wise_pq_update")
+        return cb_out
+
+    def initial_codebooks(self, resid: torch.Tensor) -> torch.Tensor:
+        """[m, 256, dsub]: codeword c of every sub-space = the sub-vector of residual row c (one Lloyd update in which row c
+        alone is assigned to codeword c: the slicing is the library's, not a torch permute)."""
+        first = resid[:KSUB].contiguous()
+        codes = torch.arange(KSUB, dtype=torch.uint8, device=self.device).unsqueeze(1).expand(KSUB, self.m).contiguous()
+        return self._update(first, codes, torch.zeros(self.m, KSUB, self.dsub, dtype=torch.float32, device=self.device))
+
+    def train_codebooks(self, resid: torch.Tensor, codebooks: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """niter Lloyd iterations from `codebooks` (default: initial_codebooks(resid))."""
+        cb = self.initial_codebooks(resid) if codebooks is None else codebooks
+        for _ in range(self.niter):
+            cb = self._update(resid, self._encode(resid, cb), cb)
+        return cb
+
+    def set_codebooks(self, codebooks) -> None:
+        """Install trained codebooks [m, 256, dsub] (file load, tests)."""
+        cb = _as_tensor(codebooks, np.float32)
+        if tuple(cb.shape) != (self.m, KSUB, self.dsub):
+            raise ValueError(f"set_codebooks: expected [{self.m},{KSUB},{self.dsub}]")
+        self.codebooks = cb.to(self.device, torch.float32).contiguous()
+
+
+class IVFPQIPIndex(PQCodebooks, CodedIVFIndexBase):
     SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfpq_scan", "wise_ivfpq_scan_sel", "wise_ivfpq_scan_local"
     WORKSPACE, WORKSPACE_LOCAL = "wise_ivfpq_scan_workspace_bytes", "wise_ivfpq_scan_local_workspace_bytes"
     WHO = "IVFPQIPIndex"                                 # the subclasses' "train() before ..." texts carry this name too
@@ -114,39 +153,13 @@ class IVFPQIPIndex(CodedIVFIndexBase):
         self._finalize()
         return self._lists.nbytes() + sum(t.numel() * t.element_size() for t in (self.centroids, self.codebooks))
 
-    # -- training -------------------------------------------------------------------------------
-    def _encode(self, resid: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
-        codes = torch.empty(resid.shape[0], self.m, dtype=torch.uint8, device=self.device)
-        _lib.check(_lib.lib().wise_pq_encode(resid.data_ptr(), codebooks.data_ptr(), resid.shape[0], self.d, self.m, codes.data_ptr(),
-                                             _lib.stream_ptr()), "wise_pq_encode")
-        return codes
-
-    def _update(self, resid: torch.Tensor, codes: torch.Tensor, cb_in: torch.Tensor) -> torch.Tensor:
-        cb_out = torch.empty_like(cb_in)
-        _lib.check(_lib.lib().wise_pq_update(resid.data_ptr(), codes.data_ptr(), resid.shape[0], self.d, self.m, cb_in.data_ptr(),
-                                             cb_out.data_ptr(), _lib.stream_ptr()), "wise_pq_update")
-        return cb_out
-
-    def initial_codebooks(self, resid: torch.Tensor) -> torch.Tensor:
-        """[m, 256, dsub]: codeword c of every sub-space = the sub-vector of residual row c (one Lloyd update in which row c
-        alone is assigned to codeword c: the slicing is the library's, not a torch permute)."""
-        first = resid[:KSUB].contiguous()
-        codes = torch.arange(KSUB, dtype=torch.uint8, device=self.device).unsqueeze(1).expand(KSUB, self.m).contiguous()
-        return self._update(first, codes, torch.zeros(self.m, KSUB, self.dsub, dtype=torch.float32, device=self.device))
-
+    # -- training (the codebook trainer: PQCodebooks) -----------------------------------------------
     def training_residuals(self, x: torch.Tensor) -> torch.Tensor:
         """The residuals the codebooks are trained on: rows perm[:65536] of x (seeded host permutation), in that order."""
         n = x.shape[0]
         perm = np.random.default_rng(self.seed).permutation(n)[:MAX_TRAIN_ROWS].astype(np.int64)
         xs = self._coarse._gather_rows(x, torch.from_numpy(perm).to(self.device))
         return self._residuals(xs, self._coarse.assign_device(xs, self.centroids))
-
-    def train_codebooks(self, resid: torch.Tensor, codebooks: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """niter Lloyd iterations from `codebooks` (default: initial_codebooks(resid))."""
-        cb = self.initial_codebooks(resid) if codebooks is None else codebooks
-        for _ in range(self.niter):
-            cb = self._update(resid, self._encode(resid, cb), cb)
-        return cb
 
     def train(self, x) -> None:
         x = _rows_f32(x, self.d, "train")
@@ -155,13 +168,6 @@ class IVFPQIPIndex(CodedIVFIndexBase):
         self._coarse.train(x)
         x = x.to(self.device, torch.float32).contiguous()
         self.codebooks = self.train_codebooks(self.training_residuals(x))
-
-    def set_codebooks(self, codebooks) -> None:
-        """Install trained codebooks [m, 256, dsub] (file load, tests)."""
-        cb = _as_tensor(codebooks, np.float32)
-        if tuple(cb.shape) != (self.m, KSUB, self.dsub):
-            raise ValueError(f"set_codebooks: expected [{self.m},{KSUB},{self.dsub}]")
-        self.codebooks = cb.to(self.device, torch.float32).contiguous()
 
     # -- construction (add_with_ids, encode_rows, adopt_lists: CodedIVFIndexBase) ------------------
     def _payload(self, xs: torch.Tensor, assign: torch.Tensor) -> torch.Tensor:
