@@ -339,6 +339,43 @@ __global__ __launch_bounds__(256) void head_pool_kernel(const bf16_t* __restrict
     *reinterpret_cast<uint4*>(lat + (size_t)b * C + g * 8) = pk;
 }
 
+// launches of the two kernels above: one host function each, called by forward() and by the wise_debug_* twins at the end of
+// this file (tests/test_gpu_audio_kernels.py), so a test launches what the tower launches.
+// block 1: both convolutions and the pooling in one kernel (the tensor between them never leaves the CU); chunk 0 = the
+// tower's rule, else that many pooled rows per workgroup
+static int launch_block1(const float* mel, const float* w0, const float* s0, const bf16_t* Wt, const float* bias2, int B, int T,
+                         int chunk, bf16_t* out, hipStream_t st) {
+    const int rows2 = B * (T / 2);
+    const size_t lds = B1_MEL + 8192;        // six image rows + conv 1's four weight fragments + the log-mel rows in flight
+    static PerDeviceOnce attr_b1;
+    attr_b1([&] {
+        raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<0>), (int)lds);
+#ifdef WISE_DEBUG_KNOBS
+        raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<1>), (int)lds);
+        raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<2>), (int)lds);
+#endif
+    });
+    auto kern = conv_block1_kernel<0>;
+#ifdef WISE_DEBUG_KNOBS
+    if (g_b1_ablate == 1) kern = conv_block1_kernel<1>;
+    if (g_b1_ablate == 2) kern = conv_block1_kernel<2>;
+#endif
+    if (chunk == 0) {
+        // two persistent workgroups per CU, each a contiguous run of pooled rows (consecutive rows of a clip share image rows)
+        const int nblk = rows2 < 512 ? rows2 : 512;
+        chunk = (rows2 + nblk - 1) / nblk;
+    }
+    hipLaunchKernelGGL(kern, dim3((rows2 + chunk - 1) / chunk), dim3(256), lds, st, mel, w0, s0, Wt, bias2, T, rows2, chunk, out);
+    WISE_LAUNCH_CHECK("cnn14 conv_block1_kernel");
+    return WISE_OK;
+}
+
+static int launch_head_pool(const bf16_t* x, int B, int T, int F, int C, bf16_t* lat, hipStream_t st) {
+    hipLaunchKernelGGL(head_pool_kernel, dim3((B * (C / 8) + 255) / 256), dim3(256), 0, st, x, B, T, F, C, lat);
+    WISE_LAUNCH_CHECK("cnn14 head_pool_kernel");
+    return WISE_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // blob layout + workspace
 // ------------------------------------------------------------------------------------------------
@@ -420,29 +457,8 @@ static int forward(const bf16_t* wb, const float* pf, const float* wave, int B, 
     if ((rc = htsat::frontend(wave, B, samples, T, pf + o.hann, pf + o.mel_start, pf + o.mel_len, pf + o.mel_wt,
                               pf + o.bn_scale, pf + o.bn_shift, mel, st)))
         return rc;
-    {   // block 1: both convolutions and the pooling in one kernel (the tensor between them never leaves the CU)
-        const int rows2 = B * (T / 2);
-        const size_t lds = B1_MEL + 8192;        // six image rows + conv 1's four weight fragments + the log-mel rows in flight
-        static PerDeviceOnce attr_b1;
-        attr_b1([&] {
-            raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<0>), (int)lds);
-#ifdef WISE_DEBUG_KNOBS
-            raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<1>), (int)lds);
-            raise_lds_limit(reinterpret_cast<const void*>(conv_block1_kernel<2>), (int)lds);
-#endif
-        });
-        auto kern = conv_block1_kernel<0>;
-#ifdef WISE_DEBUG_KNOBS
-        if (g_b1_ablate == 1) kern = conv_block1_kernel<1>;
-        if (g_b1_ablate == 2) kern = conv_block1_kernel<2>;
-#endif
-        // two persistent workgroups per CU, each a contiguous run of pooled rows (consecutive rows of a clip share image rows)
-        const int nblk = rows2 < 512 ? rows2 : 512, chunk = (rows2 + nblk - 1) / nblk;
-        hipLaunchKernelGGL(kern, dim3((rows2 + chunk - 1) / chunk), dim3(256), lds, st, mel, pf + o.c0_w, pf + o.c0_b,
-                           wb + o.cw[0][1], pf + o.cb[0][1], T, rows2, chunk, cur);
-        WISE_LAUNCH_CHECK("cnn14 conv_block1_kernel");
-        T /= 2; F /= 2;
-    }
+    if ((rc = launch_block1(mel, pf + o.c0_w, pf + o.c0_b, wb + o.cw[0][1], pf + o.cb[0][1], B, T, 0, cur, st))) return rc;
+    T /= 2; F /= 2;
     for (int i = 1; i < NBLK; ++i) {
         const int cin = CH[i - 1], cout = CH[i];
         for (int j = 0; j < 2; ++j) {
@@ -454,8 +470,7 @@ static int forward(const bf16_t* wb, const float* pf, const float* wave, int B, 
         }
         if (i < NBLK - 1) { T /= 2; F /= 2; }
     }
-    hipLaunchKernelGGL(head_pool_kernel, dim3((B * (EMB / 8) + 255) / 256), dim3(256), 0, st, cur, B, T, F, EMB, lat);
-    WISE_LAUNCH_CHECK("cnn14 head_pool_kernel");
+    if ((rc = launch_head_pool(cur, B, T, F, EMB, lat, st))) return rc;
     if ((rc = gemm_bf16(lat, wb + o.fc1_w, pf + o.fc1_b, Bp, EMB, EMB, 6 /*ReLU*/, h, st))) return rc;
     return clap_projection(h, wb + o.pj_w1, wb + o.pj_w2, pf + o.pj_lw, pf + o.pj_lb, B, EMB,
                            reinterpret_cast<float*>(wsb + ws.e), reinterpret_cast<bf16_t*>(wsb + ws.g), out, st);
@@ -494,6 +509,28 @@ extern "C" int wise_cnn14_forward(const uint16_t* wb, const float* pf, const flo
 extern "C" int wise_debug_set_cnn14(int block1_ablate) {
     wise::cnn14::g_b1_ablate = block1_ablate;
     return 0;
+}
+// The tower's own kernels one by one, through the launch functions forward() calls (tests/test_gpu_audio_kernels.py).
+// block 1: mel [B, T, 64] fp32 -> out [B*(T/2)*32, 64] bf16 (pooled, NHWC); chunk 0 = the tower's rule, else that many pooled
+// rows per workgroup (the benchmark's 128 clips x 10 s run at chunk 188; no small shape reaches a run longer than 3 by the rule)
+extern "C" int wise_debug_cnn14_block1(const float* mel, const float* w0, const float* s0, const uint16_t* Wt, const float* bias2,
+                                       int B, int T, int chunk, uint16_t* out, void* stream) {
+    WISE_CHECK_ARG(mel && w0 && s0 && Wt && bias2 && out, "debug_cnn14_block1: null pointer");
+    WISE_CHECK_ARG(B >= 1 && T >= cnn14::MIN_FRAMES && (long long)B * T * 64 < (1ll << 31) - 256 && chunk >= 0,
+                   "debug_cnn14_block1: B=%d T=%d (at least %d frames) chunk=%d (0, or pooled rows per workgroup)", B, T,
+                   cnn14::MIN_FRAMES, chunk);
+    WISE_CHECK_ARG(((uintptr_t)mel & 15) == 0 && ((uintptr_t)Wt & 15) == 0 && ((uintptr_t)s0 & 15) == 0 &&
+                       ((uintptr_t)bias2 & 15) == 0 && ((uintptr_t)out & 15) == 0,
+                   "debug_cnn14_block1: mel, Wt, s0, bias2 and out must be 16-byte aligned");
+    return cnn14::launch_block1(mel, w0, s0, Wt, bias2, B, T, chunk, out, (hipStream_t)stream);
+}
+// x [B, T, F, C] bf16 -> mean over F, then max over T + mean over T -> lat [B, C] bf16
+extern "C" int wise_debug_cnn14_head_pool(const uint16_t* x, int B, int T, int F, int C, uint16_t* lat, void* stream) {
+    WISE_CHECK_ARG(x && lat, "debug_cnn14_head_pool: null pointer");
+    WISE_CHECK_ARG(B >= 1 && T >= 1 && F >= 1 && C >= 8 && C % 8 == 0 && (long long)B * T * F * C < (1ll << 31),
+                   "debug_cnn14_head_pool: B=%d T=%d F=%d C=%d (a multiple of 8)", B, T, F, C);
+    WISE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)lat & 15) == 0, "debug_cnn14_head_pool: x and lat must be 16-byte aligned");
+    return cnn14::launch_head_pool(x, B, T, F, C, lat, (hipStream_t)stream);
 }
 #endif
 

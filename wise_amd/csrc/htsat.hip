@@ -50,8 +50,27 @@ constexpr int HEADS[4] = {4, 8, 16, 32};
 // embed: wave per token (b, i, j) of the 64x64 grid
 // image[R][c] with R = r*64 + f, c = t' holds mel[t = r*256 + t'][f] resampled to 1024 frames
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float cubic1(float v) { const float A = -0.75f; return ((A + 2.f) * v - (A + 3.f)) * v * v + 1.f; }
-__device__ __forceinline__ float cubic2(float v) { const float A = -0.75f; return ((A * v - 5.f * A) * v + 8.f * A) * v - 4.f * A; }
+// Keys' cubic (A = -0.75) at fraction t: the weights of taps i0 - 1 .. i0 + 2, in factored form —
+//   c2(1 + t) = A t (1 - t)^2,   c1(t) = (1 - t) (1 + t - (A + 2) t^2),   and the same in 1 - t for the other two.
+// The Horner forms ((A v - 5A) v + 8A) v - 4A and ((A + 2) v - (A + 3)) v^2 + 1 cancel from terms of 3 down to weights of
+// 0.05: 4.5e-7 of absolute error in fp32, which a LayerNorm row of small variance turned into 22 fp32 steps of its output
+// (tests/test_gpu_audio_kernels.py, Fc = 5).  Factored, nothing cancels (1e-7).
+__device__ __forceinline__ void cubic_weights(float t, float& w0, float& w1, float& w2, float& w3) {
+    const float A = -0.75f, u = 1.f - t;
+    w0 = A * t * (u * u);
+    w1 = u * (1.f + t - (A + 2.f) * (t * t));
+    w2 = t * (1.f + u - (A + 2.f) * (u * u));
+    w3 = A * u * (t * t);
+}
+// Sampling position of output frame t: the ROUNDED fp32 product, as torch's upsample_bicubic2d and the oracle take it — its
+// floor AND its fraction.  Opaque to the compiler: left visible, `src - floorf(src)` is contracted into fma(t, scale, -floor),
+// the fraction of the unrounded product, which is off by up to half an fp32 step of src (6e-5 at frame 1000) and moved the
+// embedding by up to 3e-4 (tests/test_gpu_audio_kernels.py, Fc = 601 and 1023).
+__device__ __forceinline__ float bicubic_src(int t, float scale) {
+    float src = (float)t * scale;
+    asm volatile("" : "+v"(src));
+    return src;
+}
 
 __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ melbn, int B, int Fc,
                                                     const float* __restrict__ pw /*[96][16]*/,
@@ -72,11 +91,12 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ me
             v = *reinterpret_cast<const float4*>(m + (size_t)t * 64);
         } else {
             const float scale = (float)(Fc - 1) / (float)(MAXF - 1);
-            const float src = (float)t * scale;
+            const float src = bicubic_src(t, scale);
             const float fl = floorf(src);
             const int i0 = (int)fl;
             const float tt = src - fl;
-            const float w0 = cubic2(tt + 1.f), w1 = cubic1(tt), w2 = cubic1(1.f - tt), w3 = cubic2(2.f - tt);
+            float w0, w1, w2, w3;
+            cubic_weights(tt, w0, w1, w2, w3);
             const int a0 = min(max(i0 - 1, 0), Fc - 1), a1 = min(max(i0, 0), Fc - 1), a2 = min(max(i0 + 1, 0), Fc - 1),
                       a3 = min(max(i0 + 2, 0), Fc - 1);
             const float4 q0 = *reinterpret_cast<const float4*>(m + (size_t)a0 * 64);
@@ -146,11 +166,12 @@ __global__ __launch_bounds__(256) void embed_tok_kernel(const float* __restrict_
             for (int q = 0; q < 4; ++q) v[q] = *reinterpret_cast<const float4*>(m + (size_t)t * 64 + 4 * q);
         } else {
             const float scale = (float)(Fc - 1) / (float)(MAXF - 1);
-            const float src = (float)t * scale;
+            const float src = bicubic_src(t, scale);
             const float fl = floorf(src);
             const int j0 = (int)fl;
             const float tt = src - fl;
-            const float w0 = cubic2(tt + 1.f), w1 = cubic1(tt), w2 = cubic1(1.f - tt), w3 = cubic2(2.f - tt);
+            float w0, w1, w2, w3;
+            cubic_weights(tt, w0, w1, w2, w3);
             const int a0 = min(max(j0 - 1, 0), Fc - 1), a1 = min(max(j0, 0), Fc - 1), a2 = min(max(j0 + 1, 0), Fc - 1),
                       a3 = min(max(j0 + 2, 0), Fc - 1);
 #pragma unroll
@@ -822,6 +843,62 @@ __global__ __launch_bounds__(256) void proj_ln_norm_kernel(const float* __restri
     for (int u = 0; u < 16; ++u) out[(size_t)b * OUT + u * 64 + lane] = v[u] / nrm;
 }
 
+// ------------------------------------------------------------------------------------------------
+// launches of the tower's own kernels: one host function each, called by htsat_forward_impl / clap_projection and by the
+// wise_debug_* twins at the end of this file (tests/test_gpu_audio_kernels.py), so a test launches what the tower launches
+// ------------------------------------------------------------------------------------------------
+static int launch_embed(const float* mel, int B, int Fc, const float* pw, const float* pb, const float* lnw, const float* lnb,
+                        float* x, bool lane_is_token, hipStream_t st) {
+    if (lane_is_token)
+        hipLaunchKernelGGL(embed_tok_kernel, dim3((unsigned)(B * 16)), dim3(256), 0, st, mel, B, Fc, pw, pb, lnw, lnb, x);
+    else
+        hipLaunchKernelGGL(embed_kernel, dim3((unsigned)(B * 64)), dim3(256), 0, st, mel, B, Fc, pw, pb, lnw, lnb, x);
+    WISE_LAUNCH_CHECK("htsat embed_kernel");
+    return WISE_OK;
+}
+
+// stage 1: LayerNorm, QKV, window attention, projection and residual add in one kernel (2 workgroups per CU);
+// grid 0 = the tower's rule, one workgroup per window up to 512
+static int launch_swin96_block_attn(float* x, int B, const float* n1w, const float* n1b, const bf16_t* wq, const float* qb,
+                                    const float* rb, const bf16_t* wproj, const float* pb, int shift, int grid, hipStream_t st) {
+    const int nwin = B * 64;
+    if (grid == 0) grid = nwin < 512 ? nwin : 512;
+    // counted with the GEMM family: the QKV and projection products (the 64 x 64 attention products are not)
+    ProfScope prof(PROF_GEMM, 2.0 * (double)B * 4096.0 * 96.0 * (288.0 + 96.0), st);
+    if (shift)
+        hipLaunchKernelGGL(swin96_block_attn_kernel<4>, dim3(grid), dim3(256), 0, st, x, B, n1w, n1b, wq, qb, rb, wproj, pb);
+    else
+        hipLaunchKernelGGL(swin96_block_attn_kernel<0>, dim3(grid), dim3(256), 0, st, x, B, n1w, n1b, wq, qb, rb, wproj, pb);
+    WISE_LAUNCH_CHECK("htsat swin96_block_attn_kernel");
+    return WISE_OK;
+}
+
+static int launch_merge_ln(const float* x, int B, int H, int C, const float* w, const float* b, bf16_t* y, long long lo_off,
+                           hipStream_t st) {
+    const long long toks = (long long)B * (H / 2) * (H / 2);
+    const dim3 grid((unsigned)((toks + 3) / 4)), block(256);
+    switch ((C + 63) / 64) {
+        case 2: hipLaunchKernelGGL(merge_ln_kernel<2>, grid, block, 0, st, x, B, H, H, C, w, b, y, lo_off); break;
+        case 3: hipLaunchKernelGGL(merge_ln_kernel<3>, grid, block, 0, st, x, B, H, H, C, w, b, y, lo_off); break;
+        case 6: hipLaunchKernelGGL(merge_ln_kernel<6>, grid, block, 0, st, x, B, H, H, C, w, b, y, lo_off); break;
+        default: set_error("htsat: unexpected C=%d", C); return WISE_E_UNSUPPORTED;
+    }
+    WISE_LAUNCH_CHECK("htsat merge_ln_kernel");
+    return WISE_OK;
+}
+
+static int launch_latent(const float* x, int B, const float* nw, const float* nb, bf16_t* lat, long long lo_off, hipStream_t st) {
+    hipLaunchKernelGGL(latent_kernel, dim3(B), dim3(256), 0, st, x, nw, nb, lat, lo_off);
+    WISE_LAUNCH_CHECK("htsat latent_kernel");
+    return WISE_OK;
+}
+
+static int launch_proj_ln_norm(const float* e, int B, const float* lw, const float* lb, float* out, hipStream_t st) {
+    hipLaunchKernelGGL(proj_ln_norm_kernel, dim3((B + 3) / 4), dim3(256), 0, st, e, B, lw, lb, out);
+    WISE_LAUNCH_CHECK("proj_ln_norm_kernel");
+    return WISE_OK;
+}
+
 }  // namespace htsat
 
 // msclap `Projection` (shared by the audio head and the caption encoder): e1 = lat @ W1^T, e2 = gelu(e1) @ W2^T,
@@ -834,9 +911,7 @@ int clap_projection(const bf16_t* lat, const bf16_t* W1, const bf16_t* W2, const
     if ((rc = gemm_bf16(lat, W1, nullptr, Bp, htsat::OUT, d_in, 4, e, st))) return rc;
     if ((rc = gemm_bf16(lat, W1, nullptr, Bp, htsat::OUT, d_in, 2, g, st))) return rc;
     if ((rc = gemm_bf16(g, W2, nullptr, Bp, htsat::OUT, htsat::OUT, 3, e, st))) return rc;
-    hipLaunchKernelGGL(htsat::proj_ln_norm_kernel, dim3((B + 3) / 4), dim3(256), 0, st, e, B, lw, lb, out);
-    WISE_LAUNCH_CHECK("proj_ln_norm_kernel");
-    return WISE_OK;
+    return htsat::launch_proj_ln_norm(e, B, lw, lb, out, st);
 }
 
 namespace htsat {
@@ -945,13 +1020,8 @@ static int htsat_forward_impl(const uint16_t* wb, const float* pf, const float* 
                        pf + o.bn_shift, mel, st, 16 /* widest band of the 50..8000 Hz filterbank (pack_htsat_weights asserts it) */)))
         return rc;
     if (g_frontend_only) return WISE_OK;
-    if (g_fuse_ln & 8)
-        hipLaunchKernelGGL(embed_tok_kernel, dim3((unsigned)(B * 16)), dim3(256), 0, st, mel, B, Fc,
-                           pf + o.pe_w, pf + o.pe_b, pf + o.pe_nw, pf + o.pe_nb, x);
-    else
-        hipLaunchKernelGGL(embed_kernel, dim3((unsigned)(B * 64)), dim3(256), 0, st, mel, B, Fc,
-                           pf + o.pe_w, pf + o.pe_b, pf + o.pe_nw, pf + o.pe_nb, x);
-    WISE_LAUNCH_CHECK("htsat embed_kernel");
+    if ((rc = launch_embed(mel, B, Fc, pf + o.pe_w, pf + o.pe_b, pf + o.pe_nw, pf + o.pe_nb, x, (g_fuse_ln & 8) != 0, st)))
+        return rc;
 
     // flags bit 0: stages 2 - 4 with their LayerNorms folded into the GEMMs (gemm_w4.h FoldArgs; the packer stored the folded
     // qkv / fc1 weights and biases): the residual stream of those stages is bf16 hi + lo where the fp32 rows would be, started
@@ -992,18 +1062,7 @@ static int htsat_forward_impl(const uint16_t* wb, const float* pf, const float* 
             // 173 vs 140 us), so stage 2 keeps the two-kernel form.
             const bool fuse_ln = (g_fuse_ln & 1) && C == 96 && gemm_ln_supported(3 * C, C, 0);
             if (C == 96 && H == 64 && (g_fuse_ln & 4)) {
-                // stage 1: LayerNorm, QKV, window attention, projection and residual add in one kernel (2 workgroups per CU)
-                const int nwin = B * 64;
-                const int grid = nwin < 512 ? nwin : 512;
-                // counted with the GEMM family: the QKV and projection products (the 64 x 64 attention products are not)
-                ProfScope prof(PROF_GEMM, 2.0 * (double)M * 96.0 * (288.0 + 96.0), st);
-                if (shift)
-                    hipLaunchKernelGGL(swin96_block_attn_kernel<4>, dim3(grid), dim3(256), 0, st, x, B, n1w, n1b, wq, qb, rb,
-                                       wproj, pb);
-                else
-                    hipLaunchKernelGGL(swin96_block_attn_kernel<0>, dim3(grid), dim3(256), 0, st, x, B, n1w, n1b, wq, qb, rb,
-                                       wproj, pb);
-                WISE_LAUNCH_CHECK("htsat swin96_block_attn_kernel");
+                if ((rc = launch_swin96_block_attn(x, B, n1w, n1b, wq, qb, rb, wproj, pb, shift, 0, st))) return rc;
             } else if ((flags & 4) && swin_qkv_attn_ok(C, H)) {
                 // flags bit 2: norm1, the QKV projection and the window attention in one kernel (swin_stream.hip: the normalised rows
                 // and the qkv rows never written); the packer stored W_qkv and its bias as that kernel's stream
@@ -1047,14 +1106,7 @@ static int htsat_forward_impl(const uint16_t* wb, const float* pf, const float* 
         if (i < 3) {
             const float* mp = pf + o.merge_f[i];
             const long long toks = (long long)B * (H / 2) * (H / 2);
-            const dim3 grid((unsigned)((toks + 3) / 4)), block(256);
-            switch ((C + 63) / 64) {
-                case 2: hipLaunchKernelGGL(merge_ln_kernel<2>, grid, block, 0, st, x, B, H, H, C, mp, mp + 4 * C, h, x_lo_off); break;
-                case 3: hipLaunchKernelGGL(merge_ln_kernel<3>, grid, block, 0, st, x, B, H, H, C, mp, mp + 4 * C, h, x_lo_off); break;
-                case 6: hipLaunchKernelGGL(merge_ln_kernel<6>, grid, block, 0, st, x, B, H, H, C, mp, mp + 4 * C, h, x_lo_off); break;
-                default: set_error("htsat: unexpected C=%d", C); return WISE_E_UNSUPPORTED;
-            }
-            WISE_LAUNCH_CHECK("htsat merge_ln_kernel");
+            if ((rc = launch_merge_ln(x, B, H, C, mp, mp + 4 * C, h, x_lo_off, st))) return rc;
             const int M2 = (int)toks, M2p = (M2 + 127) / 128 * 128;
             if (fold_on) {   // the projection STARTS the next stage's hi + lo stream and its first statistics
                 if (hipMemsetAsync(stats + M2p, 0, gemm_fold_counters_bytes(M2p), st) != hipSuccess) {
@@ -1071,8 +1123,7 @@ static int htsat_forward_impl(const uint16_t* wb, const float* pf, const float* 
     }
     // head: final LN + token mean -> latent bf16 [Bp,768] (aliases h); then the msclap Projection
     {
-        hipLaunchKernelGGL(latent_kernel, dim3(B), dim3(256), 0, st, x, pf + o.fin_nw, pf + o.fin_nb, h, x_lo_off);
-        WISE_LAUNCH_CHECK("htsat latent_kernel");
+        if ((rc = launch_latent(x, B, pf + o.fin_nw, pf + o.fin_nb, h, x_lo_off, st))) return rc;
         if ((rc = clap_projection(h, wb + o.pj_w1, wb + o.pj_w2, pf + o.pj_lw, pf + o.pj_lb, B, LATENT,
                                   reinterpret_cast<float*>(qkv), a, out, st)))
             return rc;
@@ -1109,6 +1160,59 @@ extern "C" int wise_debug_swin_attention(const uint16_t* qkv, int B, int H, int 
     hipLaunchKernelGGL(swin_attention_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, qkv, B, H, H, C, heads, shift, relb, o);
     WISE_LAUNCH_CHECK("htsat swin_attention_kernel");
     return WISE_OK;
+}
+
+// The tower's own kernels one by one, through the launch functions htsat_forward_impl calls (tests/test_gpu_audio_kernels.py).
+// embed: melbn [B, Fc, 64] fp32 -> x [B*4096, 96] fp32; form 0 = embed_tok_kernel (the one that runs), 1 = embed_kernel
+extern "C" int wise_debug_htsat_embed(const float* melbn, int B, int Fc, const float* pw, const float* pb, const float* lnw,
+                                      const float* lnb, float* x, int form, void* stream) {
+    WISE_CHECK_ARG(melbn && pw && pb && lnw && lnb && x, "debug_htsat_embed: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= 4096 && Fc >= 2 && Fc <= MAXF && (form == 0 || form == 1),
+                   "debug_htsat_embed: B=%d Fc=%d (2 .. %d) form=%d (0 | 1)", B, Fc, MAXF, form);
+    WISE_CHECK_ARG(((uintptr_t)melbn & 15) == 0 && ((uintptr_t)x & 15) == 0, "debug_htsat_embed: melbn and x must be 16-byte aligned");
+    return launch_embed(melbn, B, Fc, pw, pb, lnw, lnb, x, form == 0, (hipStream_t)stream);
+}
+// x [B*4096, 96] fp32 in place: x += proj(window_attention(LN1(x) Wqkv^T + b)) + b_proj; relb [4][64][64] must be Toeplitz in
+// (dy, dx) (the kernel keeps its 15 x 15 distinct values); grid 0 = the tower's rule min(64 B, 512), else that many workgroups
+extern "C" int wise_debug_swin96_block_attn(float* x, int B, const float* n1w, const float* n1b, const uint16_t* wqkv,
+                                            const float* qkvb, const float* relb, const uint16_t* wproj, const float* pb,
+                                            int shift, int grid, void* stream) {
+    WISE_CHECK_ARG(x && n1w && n1b && wqkv && qkvb && relb && wproj && pb, "debug_swin96_block_attn: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= 4096 && (shift == 0 || shift == 4) && grid >= 0 && grid <= 512,
+                   "debug_swin96_block_attn: B=%d shift=%d (0 | 4) grid=%d (0 .. 512)", B, shift, grid);
+    WISE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)wqkv & 15) == 0 && ((uintptr_t)wproj & 15) == 0 &&
+                       ((uintptr_t)pb & 15) == 0,
+                   "debug_swin96_block_attn: x, wqkv, wproj and pb must be 16-byte aligned");
+    return launch_swin96_block_attn(x, B, n1w, n1b, wqkv, qkvb, relb, wproj, pb, shift, grid, (hipStream_t)stream);
+}
+// x [B, H, H, C] (fp32 rows, or lo_off != 0: a bf16 hi stream with lo that many elements behind it) -> y [B*(H/2)^2, 4C] bf16
+extern "C" int wise_debug_htsat_merge_ln(const void* x, int B, int H, int C, const float* w, const float* b, uint16_t* y,
+                                         long long lo_off, void* stream) {
+    WISE_CHECK_ARG(x && w && b && y, "debug_htsat_merge_ln: null pointer");
+    WISE_CHECK_ARG(B >= 1 && H >= 2 && H % 2 == 0 && H <= 4096 && (long long)B * H * H <= (1ll << 28) &&
+                       (C == 96 || C == 192 || C == 384) && lo_off >= 0,
+                   "debug_htsat_merge_ln: B=%d H=%d (even, at least 2) C=%d (96 | 192 | 384) lo_off=%lld", B, H, C, lo_off);
+    WISE_CHECK_ARG(lo_off == 0 || (lo_off >= (long long)B * H * H * C && lo_off % 4 == 0),
+                   "debug_htsat_merge_ln: lo_off=%lld lies inside the hi stream of %lld elements, or is no multiple of 4", lo_off,
+                   (long long)B * H * H * C);
+    WISE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)w & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)y & 7) == 0,
+                   "debug_htsat_merge_ln: x, w, b must be 16-byte and y 8-byte aligned");
+    return launch_merge_ln(reinterpret_cast<const float*>(x), B, H, C, w, b, y, lo_off, (hipStream_t)stream);
+}
+// x [B*64, 768] (fp32, or hi + lo as above) -> final LayerNorm -> token mean -> lat [B, 768] bf16
+extern "C" int wise_debug_htsat_latent(const void* x, int B, const float* nw, const float* nb, uint16_t* lat, long long lo_off,
+                                       void* stream) {
+    WISE_CHECK_ARG(x && nw && nb && lat, "debug_htsat_latent: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= 65536 && (lo_off == 0 || lo_off >= (long long)B * 64 * LATENT),
+                   "debug_htsat_latent: B=%d lo_off=%lld (0, or at least the %lld elements of the hi stream)", B, lo_off,
+                   (long long)B * 64 * LATENT);
+    return launch_latent(reinterpret_cast<const float*>(x), B, nw, nb, lat, lo_off, (hipStream_t)stream);
+}
+// e [B, 1024] fp32 -> normalize(LayerNorm(e)) [B, 1024] fp32, the last kernel of clap_projection
+extern "C" int wise_debug_proj_ln_norm(const float* e, int B, const float* lw, const float* lb, float* out, void* stream) {
+    WISE_CHECK_ARG(e && lw && lb && out, "debug_proj_ln_norm: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= (1 << 20), "debug_proj_ln_norm: B=%d", B);
+    return launch_proj_ln_norm(e, B, lw, lb, out, (hipStream_t)stream);
 }
 #endif
 
