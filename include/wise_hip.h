@@ -49,7 +49,8 @@ const char* wise_last_error(void);
  * entry points (wise_ipsq8_topk, _topk_pos, _range_count / _fill, _reconstruct, _prepare, _topk_batched and their three workspace
  * functions), IndexSQ8bit; and the wise_ivfl2_* entry points (wise_ivfl2_scan, _scan_sel, _scan_local, _range_count / _fill and their
  * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2; and wise_pqflat_topk, wise_pqflat_topk_pos (with
- * wise_pqflat_topk_workspace_bytes) and wise_pqflat_decode, IndexPQ<m>.  The version is 5. */
+ * wise_pqflat_topk_workspace_bytes) and wise_pqflat_decode, IndexPQ<m>; and the wise_l2sq16_* entry points (wise_l2sq16_topk, _topk_pos,
+ * _range_count / _fill, _prepare, _topk_batched and their three workspace functions), IndexSQfp16L2.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -709,6 +710,66 @@ size_t wise_l2_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
 int wise_l2_topk_batched(const float* X, const uint16_t* Xb, const float* half, const float* norms /*[2]*/, int64_t N, int d,
                          const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
                          int32_t* counters, void* workspace, size_t workspace_bytes, void* stream);
+
+/* (ABI 5, additive) IndexSQfp16L2: exhaustive squared-L2 search over rows stored as IEEE binary16 — faiss's IndexScalarQuantizer(d,
+ * QT_fp16, METRIC_L2) under an IndexIDMap, the L2 twin of IndexSQfp16.  The index is rows [N, d] binary16 row-major (2 d bytes a row,
+ * 16-byte aligned; the bits wise_sq16_encode writes, as IndexSQfp16 stores them) plus the ids: N (2 d + 8) bytes, no fp32 rows and no
+ * second copy of the rows.  Returned distances are SQUARED L2, ascending; ties: the lower position wins; the padding when fewer than
+ * k rows compete is (+3.4028235e38, -1).  Limits of every entry point are IndexSQfp16's: d % 16 == 0, 16 <= d <= 1024,
+ * 0 <= N < 2^32 - 1, rows and Q 16-byte aligned.  Anything outside an entry point's limits, a null pointer, a misaligned pointer or a
+ * workspace shorter than its *_workspace_bytes is WISE_E_INVALID with a wise_last_error text, and nothing is written.  No call
+ * allocates or reads back: all can be captured into a graph.  All deterministic; no packed-f32 math.
+ * THE DISTANCE IS A CONTRACT.  With C = d / 16, chunk c = 0 .. C - 1 of a row is the chunk of the wise_ivfsq16_scan arithmetic: the
+ * elements 8 c .. 8 c + 7 (i = 0 .. 7) and d / 2 + 8 c .. d / 2 + 8 c + 7 (i = 8 .. 15).  Start with s_c = +0; for i = 0 .. 15 in
+ * order: t = q[e] - (float)h[e], ONE rounded fp32 subtraction (the widening is exact, subnormals are kept), then s_c = fmaf(t, t, s_c).
+ * Then for step = 1, 2, 4, ... < C, at once for every c with c + step < C: s_c = s_c + s_{c + step}.  dist(q, h) = s_0.
+ * tests/sqfp16_l2_ref.py restates it; every entry point below returns exactly these bits.  Non-finite inputs are outside the
+ * contract.  On the device the selection runs on the score -dist, as for IndexFlatL2; the sign flips back on output.
+ *   wise_l2sq16_topk: the exact scan.  1 <= nq <= 1024, 1 <= k <= 2048; ids / id_base as wise_ip_topk_f32 (ids == NULL: id_base + row);
+ *     N = 0 gives all padding.  The grid runs over row ranges and a pass carries up to 4 queries; a pass reads N d 2 bytes.
+ *     Workspace: wise_l2sqfp16_topk_workspace_bytes (0: shape not served; answers without a device).
+ *   wise_l2sq16_topk_pos: the same scan over the rows rows[pos[i]], i < n_pos (pos ascending, entries in [0, N): what
+ *     wise_sel_positions writes).  Keys carry pos[i]; n_pos == 0 gives all padding.
+ *     Workspace: wise_l2sqfp16_topk_workspace_bytes(n_pos, d, nq, k).
+ *   wise_l2sq16_range_count / _fill: the count / fill pair of range_search above over the N rows (segments, keep, counts, lims, the
+ *     fixed order — ascending position —, ids == NULL => id_base + position: as wise_ipsq16_range_*; no atomic touches global
+ *     memory); a hit iff dist < radius, strictly, and a hit's distance is the exact scan's, from the same device routine.
+ *     1 <= nq <= 65535, radius finite.  Workspace: wise_l2sqfp16_range_workspace_bytes.
+ *   wise_l2sq16_prepare: ALL the batched search keeps beside the rows, N 4 bytes.  half[r] (N device floats) = 0.5f * sum (float)h^2
+ *     as a fixed-order fp32 sum, wise_l2_prepare's order over pieces of 8 halves: lane l of 64 runs s = fmaf(x, x, s) from +0 over the
+ *     widened elements of the row's 16-byte pieces l, l + 64 in ascending order, then s = s + s[lane ^ o] for o = 32, 16, 8, 4, 2, 1,
+ *     then the exact halving.  norms[0] (one device float) = sqrtf(2 max_r half[r]): the largest row norm max_r |h_r|, 0 for N = 0
+ *     (one block folds the half-norms: a maximum is exact in any order, no atomic).
+ *   wise_l2sq16_topk_batched: 3 or more queries in passes of 128 (d <= 512) or 64 on the matrix cores: wise_l2_topk_batched in its
+ *     threshold form — sample, collect rounds, exact re-scoring, the gated exact scan behind a list (4096 rows) that overflows (a
+ *     list is appended to through its counter, in any order: the re-scoring keys carry the row) — where the collect operand is the
+ *     stored binary16 row AS LOADED on v_mfma_f32_32x32x16_f16 against q16 = f16(q): there is no bf16 copy.  a(r) = half[r] - q16 . h_r
+ *     approximates (dist - |q|^2) / 2, and eps is wise_l2_topk_batched's term by term with the rows' rounding term gone (the rows are
+ *     exact operands): |q - q16| norms[0] (the query's rounding) + d 2^-22 |q| norms[0] (fp32 accumulation) + d 2^-24 norms[0]^2 / 2
+ *     (the rounding of half[r]) + (d + 2) 2^-24 (|q| + norms[0])^2 (the contract distance against the real one, and the threshold's
+ *     own arithmetic) + a term for values below the normal range.  A query whose binary16 image (a component
+ *     beyond 65504) or eps is not finite hands its pass to the exact scan.  The answer has the bits of wise_l2sq16_topk on any finite
+ *     data.  half, norms: what wise_l2sq16_prepare wrote for these rows.  counters as wise_l2_topk_batched.  Served:
+ *     d % 128 == 0 in [256, 1024], 3 <= nq <= 1024, k <= 128, 4096 <= N < 2^31.
+ *     Workspace: wise_l2sqfp16_topk_batched_workspace_bytes (0: shape not served).
+ * reconstruct_batch over these rows is wise_ipsq16_reconstruct. */
+size_t wise_l2sqfp16_topk_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_l2sq16_topk(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, int k, const int64_t* ids, int64_t id_base,
+                     float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2sq16_topk_pos(const uint16_t* rows, int64_t N, int d, const int64_t* pos, int64_t n_pos, const float* Q, int nq, int k,
+                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                         void* stream);
+size_t wise_l2sqfp16_range_workspace_bytes(int64_t N, int d, int nq);
+int wise_l2sq16_range_count(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const uint32_t* keep,
+                            int64_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int wise_l2sq16_range_fill(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, float radius, const int64_t* ids,
+                           int64_t id_base, const int64_t* lims, float* outD, int64_t* outI, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int wise_l2sq16_prepare(const uint16_t* rows, int64_t N, int d, float* half /*[N]*/, float* norms /*[1]*/, void* stream);
+size_t wise_l2sqfp16_topk_batched_workspace_bytes(int64_t N, int d, int nq, int k);
+int wise_l2sq16_topk_batched(const uint16_t* rows, const float* half, const float* norms /*[1]*/, int64_t N, int d, const float* Q,
+                             int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* (ABI 5, additive) IndexIVFFlatL2: inverted-file search under squared L2 — faiss's IndexIVFFlat(IndexFlatL2(d), d, nlist, METRIC_L2).
  * The lists hold the raw fp32 rows X [N, d] grouped by list (no residual), 4 d bytes a row.  Limits are IndexFlatL2's: d % 16 == 0,

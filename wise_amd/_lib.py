@@ -189,6 +189,15 @@ SIGNATURES = {
     "wise_l2_prepare": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "wise_l2_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_l2_topk_batched": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2sqfp16_topk_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_l2sq16_topk": (_i, [_vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2sq16_topk_pos": (_i, [_vp, _i64, _i, _vp, _i64, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2sqfp16_range_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "wise_l2sq16_range_count": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2sq16_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _f, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_l2sq16_prepare": (_i, [_vp, _i64, _i, _vp, _vp, _vp]),
+    "wise_l2sqfp16_topk_batched_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "wise_l2sq16_topk_batched": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _i, _i, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfl2_scan_workspace_bytes": (_sz, [_i, _i, _i]),
     "wise_ivfl2_scan": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfl2_scan_sel": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -1,7 +1,7 @@
-// The flat codec scans: everything IndexSQfp16 (ip_sq16.hip), IndexFlatL2 (l2_topk.hip) and IndexSQ8bit (ip_sq8.hip) share, written
-// once and templated on a METRIC POLICY M.  The three files keep their policy, the kernels that belong to one type alone (the stage
-// kernels with their error bands, reconstruct, the norm kernels, the flip) and their extern "C" entry points, which are thin calls
-// into the drivers below.  `static` on what is no template: three translation units include this header and each gets its own copy.
+// The flat codec scans: everything IndexSQfp16 (ip_sq16.hip), IndexFlatL2 (l2_topk.hip), IndexSQ8bit (ip_sq8.hip) and IndexSQfp16L2
+// (l2_sq16.hip) share, written once and templated on a METRIC POLICY M.  The four files keep their policy, the kernels that belong
+// to one type alone (the stage kernels with their error bands, reconstruct, the norm kernels, the flip) and their extern "C" entry
+// points, which are thin calls into the drivers below.  `static` on what is no template: four translation units include this header and each gets its own copy.
 //
 // HOW A WAVE-LOAD IS LAID OUT.  A row is C = d / 16 chunks; lane (sub, c) of a wave-load holds chunk c of row sub, RPL = 64 / C
 // whole rows per load and SQ_T loads in flight.  Chunk c is the row's 16-byte pieces c, C + c, ... (Codec::PIECES of them: two
@@ -13,7 +13,7 @@
 // flat scan's: sortable (score, position) keys, per-wave threshold lists, merge_keys_kernel (ip_topk.hip).  No packed f32 math.
 //
 // THE POLICY: plain static members, no virtuals, nothing decided at run time.
-//   Codec                      Codec16, CodecL2 or Codec8 (sq_codec.h): the loads, the weights and the chain of a row's sum s
+//   Codec                      Codec16, CodecL2, Codec8 or Codec16L2 (sq_codec.h): the loads, the weights and the chain of a row's sum s
 //   base(b, q), score(s, b)    the per-query base term (b: the array the entry point hands over, q: the query of the pass) and the
 //                              row's score as the caller sees it.  PlainPolicy: no base, score = s, nothing is loaded; IndexSQ8bit
 //                              (ip_sq8.hip): b[q] = q0 of wise_sq_query and score = q0 + s, ONE fp32 addition.  Keys, the range test

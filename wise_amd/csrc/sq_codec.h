@@ -1,5 +1,5 @@
 // The row codecs and THE SUM OF THE CONTRACT of their scans: what the inverted-list kernels (ivf_sq.hip: IndexIVFSQ8,
-// IndexIVFSQfp16) and the flat codec scans (flat_codec_scan.h: IndexSQfp16 over binary16 rows, IndexFlatL2 over fp32 rows) share,
+// IndexIVFSQfp16) and the flat codec scans (flat_codec_scan.h: IndexSQfp16 and IndexSQfp16L2 over binary16 rows, IndexFlatL2 over fp32 rows) share,
 // so that a row's score is the same bits whichever index holds it.
 #pragma once
 #include "topk_common.h"
@@ -122,6 +122,31 @@ struct CodecL2 {
             a = sq_step(a, w[p].y, x[p][1]);
             a = sq_step(a, w[p].z, x[p][2]);
             a = sq_step(a, w[p].w, x[p][3]);
+        }
+        return a;
+    }
+};
+
+//   Codec16L2  IndexSQfp16L2 (l2_sq16.hip): Codec16's rows, load shape and weights — chunk c is piece c and piece c + C, elements
+//            8 c .. 8 c + 7 (i = 0 .. 7) and d / 2 + 8 c .. d / 2 + 8 c + 7 (i = 8 .. 15) — under CodecL2's step:
+//            t = q[e] - (float)h[e] (the widening is exact, subnormals kept; ONE rounded fp32 subtraction), s = fmaf(t, t, s).
+//            No bias; s_0 after the fold is the squared distance.
+struct Codec16L2 : Codec16 {
+    static __device__ __forceinline__ float sq_halves(float s, unsigned word, float qa, float qb) {
+        const f16x2 h = __builtin_bit_cast(f16x2, word);
+        const float ta = qa - (float)h.x;
+        s = fmaf(ta, ta, s);
+        const float tb = qb - (float)h.y;
+        return fmaf(tb, tb, s);
+    }
+    static __device__ __forceinline__ float chain(const u32x4 (&x)[PIECES], const float4 (&w)[4]) {
+        float a = 0.f;
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            a = sq_halves(a, x[p][0], w[2 * p].x, w[2 * p].y);
+            a = sq_halves(a, x[p][1], w[2 * p].z, w[2 * p].w);
+            a = sq_halves(a, x[p][2], w[2 * p + 1].x, w[2 * p + 1].y);
+            a = sq_halves(a, x[p][3], w[2 * p + 1].z, w[2 * p + 1].w);
         }
         return a;
     }

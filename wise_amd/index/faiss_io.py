@@ -206,6 +206,7 @@ class _FlatHead(NamedTuple):
 
 _FLAT_HEAD_BYTES = 4 + (_HDR_SIZE + 4) + 4 + (_HDR_SIZE + 4) + 36 + 8     # the most a flat head takes: both headers with a metric_arg
 _FLAT_NAMES = {"IxFI": "IndexFlatIP", "IxSQ": "IndexSQfp16", "IxF2": "IndexFlatL2"}
+_SQ16_NAMES = {0: "IndexSQfp16", 1: "IndexSQfp16L2"}     # the two QT_fp16 'IxSQ' files, by the metric_type of their headers
 _FLAT_METRIC = {"IxFI": 0, "IxF2": 1}     # faiss METRIC_INNER_PRODUCT / METRIC_L2: what the headers of an fp32 flat file must say
 
 
@@ -220,8 +221,9 @@ def _flat_outer(head: bytes):
     return cc, inner, off + 4, d0, n0
 
 
-def _flat_head(p, want: str, qtype_want: int = QT_FP16) -> _FlatHead:
-    """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxF2' / 'IxSQ'), bare or inside 'IxMp'.  RuntimeError naming
+def _flat_head(p, want: str, qtype_want: int = QT_FP16, sq_metric=None) -> _FlatHead:
+    """The head of the flat file `p`, which has to hold the index `want` ('IxFI' / 'IxF2' / 'IxSQ'), bare or inside 'IxMp'.  sq_metric: the
+    metric_type both headers of a QT_fp16 'IxSQ' file must carry (0: IndexSQfp16, 1: IndexSQfp16L2; None: not looked at).  RuntimeError naming
     the file for anything else, a metric_type that is not the fourcc's ('IxFI': 0, 'IxF2': 1, in either header), a ScalarQuantizer record other than the one asked for (qtype_want: QT_fp16 with code_size 2d and no trained value, or QT_8bit with code_size d and 2d trained values), a payload length that is not n x d
     values, or a file shorter than its header promises."""
     size = p.stat().st_size
@@ -274,6 +276,11 @@ def _flat_head(p, want: str, qtype_want: int = QT_FP16) -> _FlatHead:
         if size < need:
             raise RuntimeError(f"{p}: the file is cut short ({size} bytes, {need} promised by its header)")
         return _FlatHead(want, int(d), int(n), int(off), np.dtype(np.uint8), idmap, trained.astype(np.float32))
+    if want == "IxSQ" and sq_metric is not None and qtype == QT_FP16 and (metric != sq_metric or (idmap and metric0 != sq_metric)):
+        name = _SQ16_NAMES[sq_metric]
+        raise RuntimeError(f"{p}: an {name} file ('IxSQ', qtype 4) with metric_type {metric}"
+                           + (f" under an IndexIDMap of metric_type {metric0}" if idmap else "")
+                           + f": {name} is metric_type {sq_metric} ({_SQ16_NAMES[1 - sq_metric]} is metric_type {1 - sq_metric})")
     if want == "IxSQ":
         if qtype != QT_FP16 or d < 1 or dsq != d or code_size != 2 * d or ntrained != 0 or (idmap and (d0 != d or n0 != n)):
             raise RuntimeError(f"{p}: unsupported IndexScalarQuantizer (qtype={qtype}, d={dsq} under a header of d={d}, "
@@ -983,15 +990,20 @@ def index_fourcc(path, inner: bool = False) -> str:
 # ---------------------------------------------------------------------------------------------- 'IxMp' around 'IxSQ': binary16 rows
 def write_idmap_sq16_ip(path, halves: np.ndarray, ids: np.ndarray) -> None:
     """halves [n,d] float16 (IEEE binary16), ids [n] int64: IndexIDMap around IndexScalarQuantizer(d, QT_fp16, inner product)."""
+    _write_idmap_sq16(path, halves, ids, 0)
+
+
+def _write_idmap_sq16(path, halves, ids, metric: int) -> None:
+    """the QT_fp16 'IxSQ' file under either metric_type (0: IndexSQfp16, 1: IndexSQfp16L2), written into both headers"""
     halves = np.ascontiguousarray(halves, dtype="<f2")
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     n, d = halves.shape
     assert ids.shape == (n,)
     with open(path, "wb") as f:
         f.write(struct.pack("<I", _fourcc("IxMp")))
-        f.write(_header(d, n))
+        f.write(_header(d, n, metric))
         f.write(struct.pack("<I", _fourcc("IxSQ")))
-        f.write(_header(d, n))
+        f.write(_header(d, n, metric))
         f.write(struct.pack("<iifQQ", QT_FP16, 0, 0.0, d, 2 * d))      # ScalarQuantizer: qtype, rangestat, rangestat_arg, d, code_size
         f.write(struct.pack("<Q", 0))                            # trained: empty
         f.write(struct.pack("<Q", n * 2 * d))                    # codes
@@ -1004,14 +1016,14 @@ def read_idmap_sq16_ip(path, mmap: bool = True):
     """-> (halves [n,d] float16 (a memmap view unless mmap is False), ids int64[n]) of an IndexSQfp16 file; a bare 'IxSQ' file
     (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated or foreign file."""
     p = _existing(path)
-    head = _flat_head(p, "IxSQ")
+    head = _flat_head(p, "IxSQ", sq_metric=0)
     return _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
 
 
 def read_idmap_sq16_ip_range(path, lo: int, hi: int):
     """Rows [lo, hi) of what read_idmap_sq16_ip returns, reading only those rows and ids (one rank's shard_range of the file)."""
     p = _existing(path)
-    head = _flat_head(p, "IxSQ")
+    head = _flat_head(p, "IxSQ", sq_metric=0)
     lo, hi = int(lo), int(hi)
     if not (0 <= lo <= hi <= head.n):
         raise ValueError(f"read_idmap_sq16_ip_range: [{lo}, {hi}) outside [0, {head.n}]")
@@ -1021,7 +1033,53 @@ def read_idmap_sq16_ip_range(path, lo: int, hi: int):
 
 def idmap_sq16_ip_ntotal(path) -> int:
     """Rows of an IndexSQfp16 file (its header)."""
-    return _flat_head(_existing(path), "IxSQ").n
+    return _flat_head(_existing(path), "IxSQ", sq_metric=0).n
+
+
+def write_idmap_sq16_l2(path, halves: np.ndarray, ids: np.ndarray) -> None:
+    """halves [n,d] float16 (IEEE binary16), ids [n] int64: IndexIDMap around IndexScalarQuantizer(d, QT_fp16, METRIC_L2) — the
+    IndexSQfp16 layout with metric_type 1 in both headers."""
+    _write_idmap_sq16(path, halves, ids, 1)
+
+
+def read_idmap_sq16_l2(path, mmap: bool = True):
+    """-> (halves [n,d] float16 (a memmap view unless mmap is False), ids int64[n]) of an IndexSQfp16L2 file; a bare 'IxSQ' file
+    (no id map) gives ids = positions.  RuntimeError naming the file for a missing, truncated or foreign file — an IndexSQfp16 file
+    (metric_type 0) among them, by name."""
+    p = _existing(path)
+    head = _flat_head(p, "IxSQ", sq_metric=1)
+    return _flat_rows(p, head, mmap), _flat_ids(p, head, 0, head.n)
+
+
+def read_idmap_sq16_l2_range(path, lo: int, hi: int):
+    """Rows [lo, hi) of what read_idmap_sq16_l2 returns, reading only those rows and ids (one rank's shard_range of the file)."""
+    p = _existing(path)
+    head = _flat_head(p, "IxSQ", sq_metric=1)
+    lo, hi = int(lo), int(hi)
+    if not (0 <= lo <= hi <= head.n):
+        raise ValueError(f"read_idmap_sq16_l2_range: [{lo}, {hi}) outside [0, {head.n}]")
+    H = np.fromfile(p, dtype=head.dtype, count=(hi - lo) * head.d, offset=head.off + lo * 2 * head.d).reshape(hi - lo, head.d)
+    return H, _flat_ids(p, head, lo, hi)
+
+
+def idmap_sq16_l2_ntotal(path) -> int:
+    """Rows of an IndexSQfp16L2 file (its header)."""
+    return _flat_head(_existing(path), "IxSQ", sq_metric=1).n
+
+
+def flat_sq_metric(path):
+    """metric_type of the 'IxSQ' record of a file, bare or inside 'IxMp' (0: inner product, 1: L2 — what tells an IndexSQfp16L2 file
+    from an IndexSQfp16 one, as ivf_flat_metric tells the two 'IwFl' files apart); None where the file is no such file or ends before
+    it."""
+    with open(path, "rb") as f:
+        head = f.read(_FLAT_HEAD_BYTES)
+    try:
+        _, inner, off, _, _ = _flat_outer(head)
+        if inner != _fourcc("IxSQ"):
+            return None
+        return _read_header(head, off)[2]
+    except struct.error:
+        return None
 
 
 def _read_sq16_state(path):
@@ -1323,6 +1381,9 @@ _BY_FOURCC = {                                    # fourcc -> (reader, range rea
     "WiOP": (read_ivf_opq_ip, read_ivf_opq_ip_range, ivf_opq_ip_ntotal),
     "IwSq": (read_ivf_sq_ip, read_ivf_sq_ip_range, ivf_sq_ip_ntotal),
     "IxSQ": (_read_sq16_state, _read_sq16_state_range, idmap_sq16_ip_ntotal),      # IndexSQfp16: no lists, dict(halves, ids)
+    "IxSQ/L2": (lambda path: dict(zip(("halves", "ids"), read_idmap_sq16_l2(path, mmap=False)), metric="l2"),
+                lambda path, lo, hi: dict(zip(("halves", "ids"), read_idmap_sq16_l2_range(path, lo, hi)), metric="l2"),
+                idmap_sq16_l2_ntotal),                                             # IndexSQfp16L2: the same with metric_type 1
     "IxSQ/8": (_read_sq8_state, _read_sq8_state_range, idmap_sq8_ip_ntotal),      # IndexSQ8bit: no lists, dict(trained, codes, ids)
 }
 _BY_FOURCC_PQ_FLAT = {                            # the list-less product-quantizer files: dict(codebooks, codes, ids[, kind, ...])
@@ -1342,6 +1403,8 @@ def _by_fourcc(path, which: int):
         return _BY_FOURCC_PQ_FLAT[cc][which]
     if cc == "IxSQ" and flat_sq_qtype(p) == QT_8BIT:         # the record's qtype tells the two 'IxSQ' files apart
         cc = "IxSQ/8"
+    if cc == "IxSQ" and flat_sq_metric(p) == 1:              # the record's metric_type tells the two QT_fp16 'IxSQ' files apart
+        cc = "IxSQ/L2"
     if cc == "IwFl" and ivf_flat_metric(p) == 1:             # the record's metric_type tells the two 'IwFl' files apart
         cc = "IwFl/L2"
     if cc not in _BY_FOURCC:
@@ -1374,8 +1437,8 @@ def write_index(path, state, nprobe=None) -> None:
     metric == 'l2': its metric_type 1 form); 'halves'
     without 'centroids' is the list-less IndexSQfp16 file ('IxMp' around 'IxSQ'), 'trained' without 'centroids' the IndexSQ8bit file,
     'codebooks' without 'centroids' the IndexPQ<m> file ('IxMp' around 'IxPq'; with 'kind' its 'WiFR' form).  nprobe: state's own unless given."""
-    if "halves" in state and "centroids" not in state:       # IndexSQfp16: rows and ids, no lists
-        return write_idmap_sq16_ip(path, state["halves"], state["ids"])
+    if "halves" in state and "centroids" not in state:       # IndexSQfp16 (with metric == 'l2': IndexSQfp16L2): rows and ids, no lists
+        return (write_idmap_sq16_l2 if state.get("metric") == "l2" else write_idmap_sq16_ip)(path, state["halves"], state["ids"])
     if "trained" in state and "centroids" not in state:      # IndexSQ8bit: ranges, codes and ids, no lists
         return write_idmap_sq8_ip(path, state["trained"], state["codes"], state["ids"])
     if "codebooks" in state and "centroids" not in state:    # IndexPQ<m> (with 'kind': its R8 / R16 form): codebooks, codes and ids, no lists

@@ -36,6 +36,7 @@ factory attribute, the shape check, the file's payload, its writer and reader, a
     IndexSQfp16                      FlatSQfp16IPIndex                           d binary16 values, 2 d bytes, no fp32 rows              'IxMp' around 'IxSQ' (faiss), qtype 4
     IndexFlatL2 (flat_l2.py)         FlatL2Index                                 the fp32 row; squared-L2 distances, ascending           'IxMp' around 'IxF2' (faiss), metric_type 1
     IndexSQ8bit                      FlatSQ8IPIndex                              d code bytes (QT_8bit) under ranges [2d]: vmin, vdiff   'IxMp' around 'IxSQ' (faiss), qtype 0
+    IndexSQfp16L2                    FlatSQfp16L2Index                           d binary16 values; squared-L2 distances, ascending      'IxMp' around 'IxSQ' (faiss), qtype 4, metric_type 1
 
 and the exhaustive product-quantizer types (flat_pq.py), which have no lists but are trained, and so are neither a FAMILIES entry nor a
 FLAT_TYPES entry: parse_pq_flat_type reads their names, `^IndexPQ([1-9][0-9]*)(R8|R16)?$` (the code size is always named):
@@ -60,8 +61,8 @@ the skip-if-exists decision is collective for this type (an all-reduce of "my pa
 
 The classes are one row store and one shared surface (flat_common.py) around their own payload and search.  Wherever IndexFlatIP
 is named below — the skip-if-exists build straight from the store, the row-sharded part files, the
-ShardedFlatIPIndex wrapper — IndexSQfp16 and IndexFlatL2 go the same way (the wrapper exchanges and merges an L2 index's negated
-distances).  IndexFlatIP and IndexFlatL2 hold the same fp32 payload: the fourcc inside the file's id map tells their files apart,
+ShardedFlatIPIndex wrapper — IndexSQfp16, IndexFlatL2 and IndexSQfp16L2 go the same way (the wrapper exchanges and merges an L2
+index's negated distances).  The IndexSQfp16 and IndexSQfp16L2 files differ in the metric_type of their two headers only.  IndexFlatIP and IndexFlatL2 hold the same fp32 payload: the fourcc inside the file's id map tells their files apart,
 and an index object's `metric` its type.  The IndexSQfp16 file holds the rows rounded to binary16 (numpy's float32 ->
 float16 cast, which is what the GPU encoder of add_with_ids computes bit for bit).
 
@@ -112,7 +113,8 @@ from . import faiss_io
 from .flat_ip import FlatIPIndex
 from .flat_l2 import FlatL2Index, check_shape as check_flat_l2_shape
 from .flat_pq import FlatPQIPIndex, FlatPQRefineIPIndex
-from .flat_sq import FlatSQ8IPIndex, FlatSQfp16IPIndex, check_shape as check_sqfp16_flat_shape, check_sq8_shape
+from .flat_sq import (FlatSQ8IPIndex, FlatSQfp16IPIndex, FlatSQfp16L2Index, check_shape as check_sqfp16_flat_shape, check_sq8_shape,
+                      check_sqfp16_l2_shape)
 from .ivf_flat import IVFFlatIPIndex, IVFFlatL2Index, check_l2_shape, reference_nlist
 from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefineIPIndex, check_opq_shape, check_pq_shape,
                      check_refine_shape)
@@ -335,6 +337,9 @@ FLAT_TYPES = {
                              faiss_io.read_idmap_flat_l2, 'add_with_ids', metric='l2'),
     'IndexSQ8bit': _FlatType('flat_sq8_index_factory', check_sq8_shape, 'IxSQ', np.uint8, None, faiss_io.write_idmap_sq8_ip,
                              faiss_io.read_idmap_sq8_ip, 'add_codes_with_ids', qtype=faiss_io.QT_8BIT, trained=True),
+    'IndexSQfp16L2': _FlatType('flat_sqfp16_l2_index_factory', check_sqfp16_l2_shape, 'IxSQ', np.float16, _to_halves,
+                               faiss_io.write_idmap_sq16_l2, faiss_io.read_idmap_sq16_l2, 'add_halves_with_ids', metric='l2',
+                               qtype=faiss_io.QT_FP16),
 }
 
 
@@ -378,6 +383,7 @@ class FeatureSearchIndex(SearchIndex):
     # the classes that hold a rank's rows in HBM; CPU tests of the multi-rank wiring put stand-ins here
     flat_index_factory = FlatIPIndex
     flat_sqfp16_index_factory = FlatSQfp16IPIndex
+    flat_sqfp16_l2_index_factory = FlatSQfp16L2Index
     flat_l2_index_factory = FlatL2Index
     flat_sq8_index_factory = FlatSQ8IPIndex
     flat_pq_index_factory = FlatPQIPIndex
@@ -668,8 +674,8 @@ class FeatureSearchIndex(SearchIndex):
 
     def _index_from_file(self, fn, shard=None):
         """file -> index object holding the file's rows in HBM, by the file's fourcc; load_index and update_index share it.
-        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16 or, where
-        its ScalarQuantizer record says qtype 0, an IndexSQ8bit, an
+        An 'IxSQ' file, bare or inside 'IxMp' (the fourcc INSIDE the id map decides, fp32 is not assumed), is an IndexSQfp16 — where its
+        record's metric_type is 1, an IndexSQfp16L2 — or, where its ScalarQuantizer record says qtype 0, an IndexSQ8bit, an
         'IxF2' file an IndexFlatL2;
         anything else that is not one of IVF_FOURCCS is read as the flat IndexIDMap file (a missing file raises from that reader);
         shard = (rank, world): only rows shard_range(N, rank, world) of either flat file."""
@@ -678,8 +684,10 @@ class FeatureSearchIndex(SearchIndex):
         if self._is_pq_flat_file(fn):
             return self._pq_flat_from_file(fn)
         inner = faiss_io.index_fourcc(fn, inner=True) if fn.exists() else None
-        qtype = faiss_io.flat_sq_qtype(fn) if inner == 'IxSQ' else None       # the two 'IxSQ' files differ in their record's qtype
-        flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner and t.qtype == qtype),
+        qtype = faiss_io.flat_sq_qtype(fn) if inner == 'IxSQ' else None       # the 'IxSQ' files differ in their record's qtype
+        # and the two of qtype 4 in its metric_type (an fp32 file's fourcc names its metric)
+        metric = 'l2' if inner == 'IxF2' or (qtype == faiss_io.QT_FP16 and faiss_io.flat_sq_metric(fn) == 1) else 'ip'
+        flat = next((t for t in FLAT_TYPES.values() if t.fourcc == inner and t.qtype == qtype and t.metric == metric),
                     FLAT_TYPES['IndexSQfp16' if inner == 'IxSQ' else 'IndexFlatIP'])       # (whose reader refuses the file by name)
         *trained, rows, ids = flat.reader(fn)        # rows memory-mapped: only [lo, hi) is ever touched
         lo, hi = shard_range(rows.shape[0], *shard) if shard is not None else (0, rows.shape[0])

@@ -1,5 +1,6 @@
-"""faiss-shaped exhaustive inner-product indexes over scalar-quantized rows: IndexSQfp16 (binary16 rows, below) and IndexSQ8bit
-(one byte per dimension under trained ranges: FlatSQ8IPIndex at the end of the file).
+"""faiss-shaped exhaustive indexes over scalar-quantized rows: IndexSQfp16 (binary16 rows, inner product, below), IndexSQfp16L2 (the
+same rows under squared L2: FlatSQfp16L2Index behind it) and IndexSQ8bit (one byte per dimension under trained ranges, inner product:
+FlatSQ8IPIndex at the end of the file).
 
 IndexSQfp16.
 
@@ -162,6 +163,95 @@ class FlatSQfp16IPIndex(FlatIndexBase):
             return 0, 0
         c = self._counters.cpu()
         return int(c[0]), int(c[1])
+
+
+# -------------------------------------------------------------------------------------------------------------------------------------
+# IndexSQfp16L2
+def check_sqfp16_l2_shape(d: int) -> None:
+    if d < 16 or d % 16 != 0 or d > 1024:
+        raise ValueError(f"IndexSQfp16L2: d={d} must be a multiple of 16 in [16, 1024]")
+
+
+class FlatSQfp16L2Index(FlatSQfp16IPIndex):
+    """faiss-shaped exhaustive squared-L2 index over binary16 rows: IndexSQfp16L2, the L2 twin of IndexSQfp16.
+
+    Stands where `faiss.IndexIDMap(faiss.IndexScalarQuantizer(d, QT_fp16, METRIC_L2))` would stand.  The payload and everything that
+    builds it are FlatSQfp16IPIndex's — ONE [N, d] array of halves, encoded on the GPU chunk by chunk, N (2 d + 8) bytes with the
+    ids; what differs is the metric: returned distances are SQUARED L2, ascending, padded with (+3.4028235e38, -1), and a range hit
+    is dist < thresh, strictly (FlatL2Index's surface).  A distance is the fixed-order fp32 sum of include/wise_hip.h (THE DISTANCE
+    IS A CONTRACT; tests/sqfp16_l2_ref.py restates it) whichever path computes it.  The stored rows serve the exact scan
+    (wise_l2sq16_topk) and, as matrix-core operands as loaded, the batched passes (wise_l2sq16_topk_batched): beside the rows
+    the batched search keeps one fp32 half-norm per row and the largest row norm (wise_l2sq16_prepare, N 4 bytes), built lazily and
+    dropped whenever the rows change.  There is no bf16 copy.
+    """
+    metric = "l2"
+    # PROVISIONAL: the row floor of the siblings, not measured for this type: tools/sqfp16_l2_bench.py measured ONE size (10M x 512)
+    BATCH_MIN_ROWS = 1 << 18
+    # queries from which a batch takes the batched search.  Measured at 10M x 512, k = 10 (profiles/sqfp16_l2_bench.json): a batched
+    # pass takes 4.9 - 5.0 ms whatever it carries up to 32 queries, the exact scan 3.3 ms per pass of 4 - 3.69 ms at nq = 3 (two
+    # passes), 3.31 at 4, 6.30 at 8, 24.2 at 32: 8 is the smallest measured batch from which the batched search wins at every larger
+    # measured one (5 to 7 were not measured).  The siblings' value, confirmed at that one size
+    BATCH_MIN_QUERIES = 8
+    _RANGE = ("wise_l2sqfp16_range_workspace_bytes", "wise_l2sq16_range_count", "wise_l2sq16_range_fill")
+
+    def __init__(self, d: int, device: str = "cuda"):
+        check_sqfp16_l2_shape(d)
+        super().__init__(d, device)
+        self._half: Optional[torch.Tensor] = None    # device [N] fp32: |h|^2 / 2 (wise_l2sq16_prepare), built on demand
+
+    def _rows_changed(self) -> None:
+        """The half-norms and the largest norm go with the rows they derive from; the next batched search builds them as a fresh
+        index over the rows would."""
+        self._half = self._norms = None
+
+    def _ensure_norms(self, lib) -> torch.Tensor:
+        if self._norms is None:
+            half = torch.empty(self._n, dtype=torch.float32, device=self.device)
+            norms = torch.zeros(1, dtype=torch.float32, device=self.device)
+            _lib.check(lib.wise_l2sq16_prepare(self._H.data_ptr(), self._n, self.d, half.data_ptr(), norms.data_ptr(),
+                                               _lib.stream_ptr()), "wise_l2sq16_prepare")
+            self._half, self._norms = half, norms
+        return self._norms
+
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32 squared distances, ascending; I [nq,k] int64) on device, no host sync.  The
+        routing is FlatSQfp16IPIndex's: BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the
+        matrix-core passes where they serve the shape (wise_l2sq16_topk_batched: the same bits), everything else through the exact
+        scan, up to 4 queries a pass; sel: the scan over the selected rows' positions."""
+        lib = _lib.lib()
+        self._finalize()
+        q = self._queries(q, "search")
+        nq, k = q.shape[0], int(k)
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return D, I
+        st = _lib.stream_ptr()
+        pos = None if sel is None else resolve_for(self, sel).positions()
+        batch = pos is None and self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
+        bneed = lib.wise_l2sqfp16_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
+        if bneed:
+            self._grown("_bws", bneed)
+            if self._counters is None:
+                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+            norms = self._ensure_norms(lib)
+            _lib.check(lib.wise_l2sq16_topk_batched(self._H.data_ptr(), self._half.data_ptr(), norms.data_ptr(), self._n, self.d,
+                                                    q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(),
+                                                    self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
+                       "wise_l2sq16_topk_batched")
+            return D, I
+        need = lib.wise_l2sqfp16_topk_workspace_bytes(self._n if pos is None else pos.numel(), self.d, nq, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
+        ws = self._grown("_ws", need)
+        if pos is not None:
+            _lib.check(lib.wise_l2sq16_topk_pos(self._H.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
+                                                _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
+                                                ws.numel(), st), "wise_l2sq16_topk_pos")
+            return D, I
+        _lib.check(lib.wise_l2sq16_topk(self._H.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base,
+                                        D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_l2sq16_topk")
+        return D, I
 
 
 # -------------------------------------------------------------------------------------------------------------------------------------
