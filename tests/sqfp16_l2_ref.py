@@ -10,7 +10,7 @@ c with c + step < C: s_c = s_c + s_{c + step}.  dist = s_0.  Selection: the smal
 (+3.4028235e38, -1).  A range hit is dist < radius, strictly; a query's hits come by ascending distance, ties by ascending position.
 
   half_norms, max_norm   what wise_l2sq16_prepare writes: half[r] in its fixed order, norms[0] = sqrt32(2 max half)
-  band_terms             the terms of the batched search's eps
+  band_terms             the terms of the batched search's eps (DESIGN.md section 4, l2_stage_kernel<_Float16, false>)
   quality_study          tests/golden/sqfp16_l2_quality.json: what the rows' rounding to binary16 costs
   band_study             tests/golden/sqfp16_l2_band.json: the collect error against eps, and the longest candidate list
 """
@@ -168,7 +168,7 @@ STUDY = dict(rows=40000, centres=64, noise=0.35, spread=4.0, queries=64, query_n
 
 
 def band_terms(d, Q, M):
-    """The terms of eps in float64, per query: dict of [nq] arrays.  M: the largest norm
+    """The terms of eps (DESIGN.md section 4, l2_stage_kernel<_Float16, false>) in float64, per query: dict of [nq] arrays.  M: the largest norm
     of a stored row.  There is no row-rounding term: the stored rows are the matrix-core operands."""
     Q = np.asarray(Q, dtype=np.float32)
     with np.errstate(over="ignore"):

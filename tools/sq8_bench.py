@@ -141,7 +141,7 @@ def main():
 
     # the crossover: the batched search beside the exact scan's 4-query passes
     C, T = sq8._codes_t, sq8._trained
-    norms = sq8._ensure_norms(lib)
+    (norms,) = sq8._batch_operands()
     counters = torch.zeros(2, dtype=torch.int32, device="cuda")
     wins = {}
     for nq in NQS[1:]:

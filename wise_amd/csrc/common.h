@@ -88,6 +88,7 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 
 using short8 = __attribute__((ext_vector_type(8))) short;
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 

@@ -1,7 +1,14 @@
 // The flat codec scans: everything IndexSQfp16 (ip_sq16.hip), IndexFlatL2 (l2_topk.hip), IndexSQ8bit (ip_sq8.hip) and IndexSQfp16L2
 // (l2_sq16.hip) share, written once and templated on a METRIC POLICY M.  The four files keep their policy, the kernels that belong
-// to one type alone (the stage kernels with their error bands, reconstruct, the norm kernels, the flip) and their extern "C" entry
-// points, which are thin calls into the drivers below.  `static` on what is no template: four translation units include this header and each gets its own copy.
+// to one type alone (the inner-product stage kernels with their error bands, reconstruct, the norm kernels, the flip) and their
+// extern "C" entry points, which are thin calls into the drivers below.  `static` on what is no template: four translation units
+// include this header and each gets its own copy.
+// WHAT LIVES HERE: the exact scan (flat_scan_kernel, flat_topk, topk_entry), the range pair (flat_range_*_kernel, range_count,
+// range_fill), the batched search (flat_query_block_kernel, flat_collect_kernel, topk_batched), their workspace planners and
+// argument checks (topk_args, range_args, batched_args), and the pieces two types share: the sum of squares of a binary16 row
+// (square_halves, half_row_square_sum), the grid of the wave-per-row kernels (wave_row_grid), and the stage kernel and threshold of
+// the two squared-L2 types (l2_stage_kernel<Image, ROW_TERM>, threshold_above).  The id lookup of the reconstruct kernels is
+// row_of_id (topk_common.h); f16x8 stands beside bf16x8 (common.h).
 //
 // HOW A WAVE-LOAD IS LAID OUT.  A row is C = d / 16 chunks; lane (sub, c) of a wave-load holds chunk c of row sub, RPL = 64 / C
 // whole rows per load and SQ_T loads in flight.  Chunk c is the row's 16-byte pieces c, C + c, ... (Codec::PIECES of them: two
@@ -53,6 +60,31 @@ struct PlainPolicy {
 };
 
 static bool shape_ok(int d) { return d >= 16 && d <= MAX_D && d % 16 == 0; }
+
+// blocks of a kernel whose waves take one row at a time, four waves a block (the norm and half-norm kernels of the prepare entry points)
+static unsigned wave_row_grid(int64_t N) { return (unsigned)((N + 3) / 4 < 2048 ? (N + 3) / 4 : 2048); }
+
+// THE SUM OF SQUARES OF A BINARY16 ROW (wise_ipsq16_prepare, wise_l2sq16_prepare), one wave per row: lane l runs s = fmaf(x, x, s)
+// over the widened elements of the row's 16-byte pieces (8 halves each) l, l + 64 in ascending order from +0, and the lanes are
+// folded by wave_sum's butterfly (lane masks 32, 16, 8, 4, 2, 1): a row's sum depends on the row alone.
+__device__ __forceinline__ float square_halves(float s, unsigned word) {
+    const f16x2 h = __builtin_bit_cast(f16x2, word);
+    const float a = (float)h.x, b = (float)h.y;
+    s = fmaf(a, a, s);
+    return fmaf(b, b, s);
+}
+__device__ __forceinline__ float half_row_square_sum(const unsigned char* __restrict__ rows, long long r, int d, int lane) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(rows + (size_t)r * 2 * d);
+    float s = 0.f;
+    for (int p = lane; p < (d >> 3); p += 64) {
+        const u32x4 x = src[p];
+        s = square_halves(s, x[0]);
+        s = square_halves(s, x[1]);
+        s = square_halves(s, x[2]);
+        s = square_halves(s, x[3]);
+    }
+    return wave_sum(s);
+}
 
 // the place of a lane in a wave-load (sq_scan_list's): chunk c of row `sub` of the load; lanes past RPL * C idle
 struct LanePlace {
@@ -306,6 +338,94 @@ struct BatchSlots {                       // workspace of a pass
 };
 
 __device__ __forceinline__ bool is_finite_f32(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
+// ---- the stage kernel and the threshold of the two squared-L2 types (IndexFlatL2: bf16 image, rows with a rounding term;
+// IndexSQfp16L2: binary16 image, rows used as stored).  With q16 the query's 16-bit image and x16 the 16-bit rows,
+// |q - x|^2 / 2 = |q|^2 / 2 + |x|^2 / 2 - q . x, and a(r) = half[r] - (q16 . x16_r on the matrix cores) approximates
+// (dist(q, r) - |q|^2) / 2 within eps:
+//   stage    the queries rounded to the image (ONE piece), |q|^2 and eps per query; a query whose image or whose eps is not finite
+//            hands the pass to the exact scan at once
+//   sample   t = the k-th smallest distance over the sample is an upper bound of the index's exact k-th, so every row of the exact
+//            top-k has a(r) <= thr = (t - |q|^2) / 2 + eps
+//   collect  every (query, row) with a(r) <= thr[query] is listed
+// a query element rounded into the image; returns the image's value
+__device__ __forceinline__ float round_image(bf16_t* dst, float v) {
+    const bf16_t h = f32_to_bf16(v);
+    *dst = h;
+    return bf16_to_f32(h);
+}
+__device__ __forceinline__ float round_image(_Float16* dst, float v) {
+    const _Float16 h = (_Float16)v;
+    *dst = h;
+    return (float)h;
+}
+
+// block = one wave = one query.  eps bounds |a(r) - (dist(q, r) - |q|^2) / 2| plus what the threshold's own arithmetic loses, for
+// EVERY row, from norms[0] = M = max |x| and, under ROW_TERM, norms[1] = Rx = max |x - x16| alone (u = 2^-24):
+//   |q - q16| M                     the query's rounding (Cauchy-Schwarz)
+//   |q16| Rx                        the rows' rounding                                    (ROW_TERM only: binary16 rows drop it)
+//   d 2^-22 |q| (M + Rx)            fp32 accumulation of the matrix-core sum (as IndexSQfp16 bounds it; binary16 rows: Rx = 0)
+//   d u M^2 / 2                     the rounding of half[r]: at most 16 fmaf and 6 adds of non-negative terms, halved exactly
+//   (d + 2) u (|q| + M)^2           the contract distance against the real one; the band needs half of it, the other half pays for
+//                                   the rounding of |q|^2 (a sum like half[r]'s), of half[r] - acc and of the threshold's three
+//                                   operations, each a few u of at most (|q| + M)^2
+//   sqrt(d) (|q| + M) 2^-125 + 1e-33  operands or partial results below the normal range, flushed or not
+// every factor is an fp32 result itself and is rounded up by 1.001.
+template <class Image, bool ROW_TERM>
+__global__ __launch_bounds__(64) void l2_stage_kernel(const float* __restrict__ Q, int d, const float* __restrict__ norms, BatchSlots ws) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x, q = blockIdx.x;
+    Image* image = reinterpret_cast<Image*>(ws.qb);
+    float e2 = 0.f, q2 = 0.f, b2 = 0.f;
+    bool bad = false;
+    for (int i = lane; i < d; i += 64) {
+        const float v = Q[(size_t)q * d + i];
+        const float back = round_image(image + (size_t)q * d + i, v), r = v - back;
+        bad = bad || !is_finite_f32(back);                        // the image is infinite or NaN
+        e2 = fmaf(r, r, e2);
+        q2 = fmaf(v, v, q2);
+        if constexpr (ROW_TERM) b2 = fmaf(back, back, b2);
+    }
+    e2 = wave_sum(e2);
+    q2 = wave_sum(q2);
+    if constexpr (ROW_TERM) b2 = wave_sum(b2);
+    const bool any_bad = __ballot(bad) != 0;
+    if (lane == 0) {
+        const float u = 5.9604644775390625e-08f, fd = (float)d;
+        const float M = norms[0] * 1.001f;
+        const float nq = sqrtf(q2) * 1.001f, ne = sqrtf(e2) * 1.001f;
+        const float reach = nq + M;
+        float eps = ne * M;
+        if constexpr (ROW_TERM) {
+            const float Rx = norms[1] * 1.001f, nb = sqrtf(b2) * 1.001f;
+            eps = eps + nb * Rx;
+            eps = eps + fd * 4.f * u * nq * (M + Rx);
+        } else {
+            eps = eps + fd * 4.f * u * nq * M;
+        }
+        eps = eps + fd * u * 0.5f * M * M;
+        eps = eps + (fd + 2.f) * u * reach * reach;
+        eps = eps + sqrtf(fd) * reach * 2.35098870164457501594e-38f + 1e-33f;
+        eps = eps * 1.001f;
+        // A query whose image is not finite (a binary16 component beyond 65504), or whose band is not (|q| or M beyond ~1e19), has
+        // no usable matrix-core score: it raises the pass's flag here — the host cleared it before this launch — and the exact scan
+        // answers the pass.  Every block that raises it stores the same value.
+        if (any_bad || !is_finite_f32(eps) || !is_finite_f32(q2)) {
+            eps = __builtin_inff();
+            *ws.flag = 1;
+        }
+        ws.eps[q] = eps;
+        ws.q2[q] = q2;
+        ws.thr[q] = __builtin_inff();
+        ws.ctl[q] = 0;
+    }
+}
+
+// thr of a query whose k-th smallest exact distance over some of the rows is t: (t - |q|^2) / 2 + eps, rounded up
+__device__ __forceinline__ float threshold_above(float t, float q2, float eps) {
+#pragma clang fp contract(off)
+    return ((0.5f * t - 0.5f * q2) + eps) + (t + q2) * 2.384185791015625e-07f + 1e-37f;
+}
 
 // block = one query.  ROWS_SAMPLE: the exact top-k over n_sample evenly spaced rows sets thr.  ROWS_CAND: the exact top-k over the
 // query's list; final == 0 tightens thr and empties the list, final != 0 writes the answer
@@ -688,6 +808,18 @@ static size_t batched_workspace_bytes(int64_t N, int d, int nq, int k) {
     if (!batch_shape_ok(N, d, nq, k)) return 0;
     const int qb = batch_pass_queries(d);
     return batch_slot_bytes<M>(d, nullptr, nullptr) + part_bytes(N, d, nq < qb ? nq : qb, k) + 256;
+}
+
+// what every *_topk_batched entry point checks before anything of its own; need: its *_topk_batched_workspace_bytes
+static int batched_args(const char* what, const void* rows, int64_t N, int d, const float* Q, int nq, int k, const float* outD,
+                        const int64_t* outI, const float* norms, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (int rc = topk_args(what, rows, N, d, Q, nq, k, outD, outI)) return rc;
+    WISE_CHECK_ARG(batch_shape_ok(N, d, nq, k),
+                   "%s: N=%lld d=%d nq=%d k=%d not served (d %% 128 == 0 in [256, 1024], nq >= 3, k <= 128, N >= 4096)", what,
+                   (long long)N, d, nq, k);
+    WISE_CHECK_ARG(norms, "%s: null pointer", what);
+    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    return WISE_OK;
 }
 
 template <class M, int QT>

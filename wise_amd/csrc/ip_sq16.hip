@@ -17,52 +17,25 @@ namespace ipsq16 {
 
 using namespace flat_codec;
 
-// wise_ipsq16_reconstruct: reconstruct_kernel (ip_topk.hip) for this payload; the highest position wins where an id repeats
+// wise_ipsq16_reconstruct: reconstruct_kernel (ip_topk.hip) for this payload
 __global__ __launch_bounds__(256) void sq16_reconstruct_kernel(const _Float16* __restrict__ rows, long long N, int d,
                                                                const long long* __restrict__ ids, long long id_base,
                                                                const long long* __restrict__ qids, float* __restrict__ out) {
-    __shared__ unsigned long long s_row1;  // row + 1, 0 = not found
     const int i = blockIdx.x;
-    const long long want = qids[i];
-    if (threadIdx.x == 0)
-        s_row1 = ids ? 0ull : ((want >= id_base && want - id_base < N) ? (unsigned long long)(want - id_base + 1) : 0ull);
-    __syncthreads();
-    if (ids) {
-        for (long long r = threadIdx.x; r < N; r += blockDim.x)
-            if (ids[r] == want) atomicMax(&s_row1, (unsigned long long)(r + 1));
-        __syncthreads();
-    }
-    const long long row = (long long)s_row1 - 1;
+    const long long row = row_of_id(ids, id_base, N, qids[i]);
     for (int c = threadIdx.x; c < d; c += blockDim.x)
         out[(size_t)i * d + c] = row >= 0 ? (float)rows[(size_t)row * d + c] : __builtin_nanf("");
 }
 
-// wise_ipsq16_prepare: one wave per row at a time; lane l runs s = fmaf(x, x, s) over the elements of the row's 16-byte pieces
-// l, l + 64 in ascending order from +0, the lanes are folded by wave_sum's butterfly and the norm is sqrtf of that: a row's norm
-// depends on the row alone.  The maximum is exact, and non-negative floats order as their bit patterns: atomicMax on the bits
-// gives the same value in any order.
-__device__ __forceinline__ float square_halves(float s, unsigned word) {
-    const f16x2 h = __builtin_bit_cast(f16x2, word);
-    const float a = (float)h.x, b = (float)h.y;
-    s = fmaf(a, a, s);
-    return fmaf(b, b, s);
-}
+// wise_ipsq16_prepare: one wave per row at a time; the norm is sqrtf of half_row_square_sum (flat_codec_scan.h): a row's norm depends
+// on the row alone.  The maximum is exact, and non-negative floats order as their bit patterns: atomicMax on the bits gives the same
+// value in any order.
 __global__ __launch_bounds__(256) void sq16_norm_kernel(const unsigned char* __restrict__ rows, long long N, int d,
                                                         unsigned* __restrict__ norm_bits) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pieces = d >> 3;
     float best = 0.f;
     for (long long r = (long long)blockIdx.x * 4 + wave; r < N; r += (long long)gridDim.x * 4) {
-        const u32x4* src = reinterpret_cast<const u32x4*>(rows + (size_t)r * 2 * d);
-        float s = 0.f;
-        for (int p = lane; p < pieces; p += 64) {
-            const u32x4 x = src[p];
-            s = square_halves(s, x[0]);
-            s = square_halves(s, x[1]);
-            s = square_halves(s, x[2]);
-            s = square_halves(s, x[3]);
-        }
-        s = sqrtf(wave_sum(s));
+        const float s = sqrtf(half_row_square_sum(rows, r, d, lane));
         best = s > best ? s : best;                              // (a NaN norm is never kept: non-finite rows are outside the contract)
     }
     if (lane == 0) atomicMax(norm_bits, __float_as_uint(best));
@@ -118,8 +91,6 @@ __device__ __forceinline__ float threshold_below(float t, float eps) {
 #pragma clang fp contract(off)
     return (t - eps * 1.0001f) - fabsf(t) * 4.76837158203125e-07f - 1e-37f;
 }
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // THE POLICY (flat_codec_scan.h): the score is the inner product itself, larger is better
 struct MetricIP16 : PlainPolicy {
@@ -202,9 +173,7 @@ extern "C" int wise_ipsq16_prepare(const uint16_t* rows, int64_t N, int d, float
     const hipError_t e = hipMemsetAsync(norms, 0, sizeof(float), st);
     if (e != hipSuccess) { set_error("ipsq16_prepare: memset: %s", hipGetErrorString(e)); return (int)e; }
     if (N == 0) return WISE_OK;
-    long long grid = (N + 3) / 4;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(sq16_norm_kernel, dim3((unsigned)grid), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(rows), (long long)N,
+    hipLaunchKernelGGL(sq16_norm_kernel, dim3(wave_row_grid(N)), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(rows), (long long)N,
                        d, reinterpret_cast<unsigned*>(norms));
     WISE_LAUNCH_CHECK("sq16_norm_kernel");
     return WISE_OK;
@@ -217,13 +186,9 @@ extern "C" size_t wise_ipsqfp16_topk_batched_workspace_bytes(int64_t N, int d, i
 extern "C" int wise_ipsq16_topk_batched(const uint16_t* rows, const float* norms, int64_t N, int d, const float* Q, int nq, int k,
                                         const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters,
                                         void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = topk_args("ipsq16_topk_batched", rows, N, d, Q, nq, k, outD, outI)) return rc;
-    WISE_CHECK_ARG(batch_shape_ok(N, d, nq, k),
-                   "ipsq16_topk_batched: N=%lld d=%d nq=%d k=%d not served (d %% 128 == 0 in [256, 1024], nq >= 3, k <= 128, N >= 4096)",
-                   (long long)N, d, nq, k);
-    WISE_CHECK_ARG(norms, "ipsq16_topk_batched: null pointer");
-    const size_t need = wise_ipsqfp16_topk_batched_workspace_bytes(N, d, nq, k);
-    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "ipsq16_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (int rc = batched_args("ipsq16_topk_batched", rows, N, d, Q, nq, k, outD, outI, norms, workspace, workspace_bytes,
+                              wise_ipsqfp16_topk_batched_workspace_bytes(N, d, nq, k)))
+        return rc;
     return topk_batched<MetricIP16>("ipsq16_topk_batched", rows, rows, nullptr, norms, N, d, Q, nullptr, nq, k, ids, id_base, outD, outI, counters,
                                     workspace, (hipStream_t)stream);
 }

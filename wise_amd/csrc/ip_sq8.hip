@@ -38,18 +38,8 @@ __global__ __launch_bounds__(256) void sq8_reconstruct_kernel(const unsigned cha
                                                               long long N, int d, const long long* __restrict__ ids, long long id_base,
                                                               const long long* __restrict__ qids, float* __restrict__ out) {
 #pragma clang fp contract(off)
-    __shared__ unsigned long long s_row1;  // row + 1, 0 = not found
     const int i = blockIdx.x;
-    const long long want = qids[i];
-    if (threadIdx.x == 0)
-        s_row1 = ids ? 0ull : ((want >= id_base && want - id_base < N) ? (unsigned long long)(want - id_base + 1) : 0ull);
-    __syncthreads();
-    if (ids) {
-        for (long long r = threadIdx.x; r < N; r += blockDim.x)
-            if (ids[r] == want) atomicMax(&s_row1, (unsigned long long)(r + 1));
-        __syncthreads();
-    }
-    const long long row = (long long)s_row1 - 1;
+    const long long row = row_of_id(ids, id_base, N, qids[i]);
     for (int c = threadIdx.x; c < d; c += blockDim.x) {
         float y = __builtin_nanf("");
         if (row >= 0) {
@@ -163,8 +153,6 @@ __device__ __forceinline__ float threshold_below_scaled(float t, float q0, int e
     const float v = ldexpf(s, e);
     return (v - eps * 1.0001f) - fabsf(v) * 4.76837158203125e-07f - 1e-37f;
 }
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // codes b0 .. b3 of a word -> the binary16 pairs (b0, b1) and (b2, b3): v_perm_b32 puts each code under the exponent byte 0x64 —
 // 0x6400 | b is 1024 + b exactly, the ulp of binary16 in [1024, 2048) being 1 — and the operand is that minus 1024 (packed binary16
@@ -318,9 +306,7 @@ extern "C" int wise_ipsq8_prepare(const uint8_t* codes, int64_t N, int d, float*
     const hipError_t e = hipMemsetAsync(norms, 0, sizeof(float), st);
     if (e != hipSuccess) { set_error("ipsq8_prepare: memset: %s", hipGetErrorString(e)); return (int)e; }
     if (N == 0) return WISE_OK;
-    long long grid = (N + 3) / 4;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(sq8_norm_kernel, dim3((unsigned)grid), dim3(256), 0, st, codes, (long long)N, d, reinterpret_cast<unsigned*>(norms));
+    hipLaunchKernelGGL(sq8_norm_kernel, dim3(wave_row_grid(N)), dim3(256), 0, st, codes, (long long)N, d, reinterpret_cast<unsigned*>(norms));
     WISE_LAUNCH_CHECK("sq8_norm_kernel");
     hipLaunchKernelGGL(sq8_norm_finish_kernel, dim3(1), dim3(64), 0, st, norms);
     WISE_LAUNCH_CHECK("sq8_norm_finish_kernel");
@@ -335,13 +321,9 @@ extern "C" size_t wise_ipsq8_topk_batched_workspace_bytes(int64_t N, int d, int 
 extern "C" int wise_ipsq8_topk_batched(const uint8_t* codes, const float* trained, const float* norms, int64_t N, int d, const float* Q,
                                        int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI, int32_t* counters,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = topk_args("ipsq8_topk_batched", codes, N, d, Q, nq, k, outD, outI)) return rc;
-    WISE_CHECK_ARG(batch_shape_ok(N, d, nq, k),
-                   "ipsq8_topk_batched: N=%lld d=%d nq=%d k=%d not served (d %% 128 == 0 in [256, 1024], nq >= 3, k <= 128, N >= 4096)",
-                   (long long)N, d, nq, k);
-    WISE_CHECK_ARG(norms, "ipsq8_topk_batched: null pointer");
-    const size_t need = wise_ipsq8_topk_batched_workspace_bytes(N, d, nq, k);
-    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "ipsq8_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (int rc = batched_args("ipsq8_topk_batched", codes, N, d, Q, nq, k, outD, outI, norms, workspace, workspace_bytes,
+                              wise_ipsq8_topk_batched_workspace_bytes(N, d, nq, k)))
+        return rc;
     if (int rc = sq8_args("ipsq8_topk_batched", trained, workspace)) return rc;
     const QuerySlots qs(workspace, nq, d);
     if (int rc = wise_sq_query(Q, trained, nq, d, qs.W, qs.q0, stream)) return rc;

@@ -285,18 +285,8 @@ __global__ __launch_bounds__(64) void merge_pairs_kernel(const float* __restrict
 __global__ void reconstruct_kernel(const float* __restrict__ X, long long N, int d,
                                    const long long* __restrict__ ids, long long id_base,
                                    const long long* __restrict__ qids, int n, float* __restrict__ out) {
-    __shared__ unsigned long long s_row1;  // row + 1, 0 = not found
     const int i = blockIdx.x;
-    const long long want = qids[i];
-    if (threadIdx.x == 0)
-        s_row1 = ids ? 0ull : ((want >= id_base && want - id_base < N) ? (unsigned long long)(want - id_base + 1) : 0ull);
-    __syncthreads();
-    if (ids) {
-        for (long long r = threadIdx.x; r < N; r += blockDim.x)
-            if (ids[r] == want) atomicMax(&s_row1, (unsigned long long)(r + 1));
-        __syncthreads();
-    }
-    const long long row = (long long)s_row1 - 1;
+    const long long row = row_of_id(ids, id_base, N, qids[i]);
     for (int c = threadIdx.x; c < d; c += blockDim.x)
         out[(size_t)i * d + c] = (row >= 0) ? X[row * d + c] : __builtin_nanf("");
 }

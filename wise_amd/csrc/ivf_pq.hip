@@ -250,14 +250,8 @@ __global__ __launch_bounds__(256) void gather_codes_kernel(const unsigned char* 
 // pos[i] = position of query_ids[i] in ids (the highest, if it occurs more than once), -1 when absent
 __global__ __launch_bounds__(256) void find_kernel(const long long* __restrict__ ids, long long N, const long long* __restrict__ qids,
                                                    long long* __restrict__ pos) {
-    __shared__ unsigned long long s_row1;
-    const long long want = qids[blockIdx.x];
-    if (threadIdx.x == 0) s_row1 = 0ull;
-    __syncthreads();
-    for (long long r = threadIdx.x; r < N; r += blockDim.x)
-        if (ids[r] == want) atomicMax(&s_row1, (unsigned long long)(r + 1));
-    __syncthreads();
-    if (threadIdx.x == 0) pos[blockIdx.x] = (long long)s_row1 - 1;
+    const long long row = row_of_id(ids, 0, N, qids[blockIdx.x]);
+    if (threadIdx.x == 0) pos[blockIdx.x] = row;
 }
 
 // out[i][:] = c_l + concat_j cb[j][codes[pos[i]][j]], l = the list that holds position pos[i]; NaN when pos[i] is out of range

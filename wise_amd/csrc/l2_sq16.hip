@@ -17,30 +17,13 @@ namespace l2sq16 {
 
 using namespace flat_codec;
 
-// wise_l2sq16_prepare, first launch: half[r] = 0.5f * |h_r|^2.  One wave per row at a time; lane l runs s = fmaf(x, x, s) over the
-// widened elements of the row's 16-byte pieces (8 halves each) l, l + 64 in ascending order from +0, the lanes are folded by
-// wave_sum's butterfly (lane masks 32, 16, 8, 4, 2, 1) and the sum is halved (exact): a row's half-norm depends on the row alone.
-__device__ __forceinline__ float square_halves(float s, unsigned word) {
-    const f16x2 h = __builtin_bit_cast(f16x2, word);
-    const float a = (float)h.x, b = (float)h.y;
-    s = fmaf(a, a, s);
-    return fmaf(b, b, s);
-}
+// wise_l2sq16_prepare, first launch: half[r] = 0.5f * |h_r|^2.  One wave per row at a time; the sum is half_row_square_sum's
+// (flat_codec_scan.h), halved (exact): a row's half-norm depends on the row alone.
 __global__ __launch_bounds__(256) void l2sq16_half_norm_kernel(const unsigned char* __restrict__ rows, long long N, int d,
                                                                float* __restrict__ half) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pieces = d >> 3;
     for (long long r = (long long)blockIdx.x * 4 + wave; r < N; r += (long long)gridDim.x * 4) {
-        const u32x4* src = reinterpret_cast<const u32x4*>(rows + (size_t)r * 2 * d);
-        float s = 0.f;
-        for (int p = lane; p < pieces; p += 64) {
-            const u32x4 x = src[p];
-            s = square_halves(s, x[0]);
-            s = square_halves(s, x[1]);
-            s = square_halves(s, x[2]);
-            s = square_halves(s, x[3]);
-        }
-        s = wave_sum(s);
+        const float s = half_row_square_sum(rows, r, d, lane);
         if (lane == 0) half[r] = 0.5f * s;
     }
 }
@@ -74,67 +57,9 @@ __global__ __launch_bounds__(1024) void l2sq16_max_norm_kernel(const float* __re
     }
 }
 
-// ---- the batched search (wise_l2sq16_topk_batched): wise_l2_topk_batched's pass over rows that ARE their own matrix-core
-// operands.  With q16 = f16(q), |q - h|^2 / 2 = |q|^2 / 2 + |h|^2 / 2 - q . h, and a(r) = half[r] - (q16 . h_r on the matrix cores)
-// approximates (dist(q, r) - |q|^2) / 2 within eps.  block = one wave = one query.  eps is l2_stage_kernel's
-// term by term with the rows' rounding term gone (u = 2^-24, M = norms[0] = max |h|):
-//   |q - q16| M                     the query's rounding (Cauchy-Schwarz)
-//   d 2^-22 |q| M                   fp32 accumulation of the matrix-core sum
-//   d u M^2 / 2                     the rounding of half[r]: at most 16 fmaf and 6 adds of non-negative terms, halved exactly
-//   (d + 2) u (|q| + M)^2           the contract distance against the real one; the band needs half of it, the other half pays for
-//                                   the rounding of |q|^2, of half[r] - acc and of the threshold's three operations
-//   sqrt(d) (|q| + M) 2^-125 + 1e-33  operands or partial results below the normal range, flushed or not
-// every factor is an fp32 result itself and is rounded up by 1.001.
-__global__ __launch_bounds__(64) void l2sq16_stage_kernel(const float* __restrict__ Q, int d, const float* __restrict__ norms,
-                                                          BatchSlots ws) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x, q = blockIdx.x;
-    float e2 = 0.f, q2 = 0.f;
-    bool bad = false;
-    for (int i = lane; i < d; i += 64) {
-        const float v = Q[(size_t)q * d + i];
-        const _Float16 h = (_Float16)v;
-        ws.q16[(size_t)q * d + i] = h;
-        const float back = (float)h, r = v - back;
-        bad = bad || !is_finite_f32(back);                        // the half is infinite or NaN (a component beyond 65504)
-        e2 = fmaf(r, r, e2);
-        q2 = fmaf(v, v, q2);
-    }
-    e2 = wave_sum(e2);
-    q2 = wave_sum(q2);
-    const bool any_bad = __ballot(bad) != 0;
-    if (lane == 0) {
-        const float u = 5.9604644775390625e-08f, fd = (float)d;
-        const float M = norms[0] * 1.001f;
-        const float nq = sqrtf(q2) * 1.001f, ne = sqrtf(e2) * 1.001f;
-        const float reach = nq + M;
-        float eps = ne * M;
-        eps = eps + fd * 4.f * u * nq * M;
-        eps = eps + fd * u * 0.5f * M * M;
-        eps = eps + (fd + 2.f) * u * reach * reach;
-        eps = eps + sqrtf(fd) * reach * 2.35098870164457501594e-38f + 1e-33f;
-        eps = eps * 1.001f;
-        // A query whose binary16 image is not finite, or whose band is not, has no usable matrix-core score: it raises the pass's
-        // flag here — the host cleared it before this launch — and the exact scan answers the pass.  Every block that raises it
-        // stores the same value.
-        if (any_bad || !is_finite_f32(eps) || !is_finite_f32(q2)) {
-            eps = __builtin_inff();
-            *ws.flag = 1;
-        }
-        ws.eps[q] = eps;
-        ws.q2[q] = q2;
-        ws.thr[q] = __builtin_inff();
-        ws.ctl[q] = 0;
-    }
-}
-
-// thr of a query whose k-th smallest exact distance over some of the rows is t: (t - |q|^2) / 2 + eps, rounded up
-__device__ __forceinline__ float threshold_above(float t, float q2, float eps) {
-#pragma clang fp contract(off)
-    return ((0.5f * t - 0.5f * q2) + eps) + (t + q2) * 2.384185791015625e-07f + 1e-37f;
-}
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// ---- the batched search (wise_l2sq16_topk_batched): wise_l2_topk_batched's pass over rows that ARE their own matrix-core operands:
+// l2_stage_kernel<_Float16, false> and threshold_above of flat_codec_scan.h — the binary16 image of the queries, and eps without the
+// rows' rounding term (M = norms[0] = max |h|).
 
 // THE POLICY (flat_codec_scan.h): the keys order the negated distance; the collect operand is the stored row
 struct MetricL2SQ16 : PlainPolicy {
@@ -158,8 +83,8 @@ struct MetricL2SQ16 : PlainPolicy {
     static constexpr bool HALF_NORMS = true;
     static __device__ __forceinline__ bool candidate(float hv, float acc, float thr) { return !(hv - acc > thr); }
     static const char* stage(const float* Q, int d, const float* norms, const BatchSlots& ws, int nq, hipStream_t st) {
-        hipLaunchKernelGGL(l2sq16_stage_kernel, dim3(nq), dim3(64), 0, st, Q, d, norms, ws);
-        return "l2sq16_stage_kernel";
+        hipLaunchKernelGGL((l2_stage_kernel<_Float16, false>), dim3(nq), dim3(64), 0, st, Q, d, norms, ws);
+        return "l2_stage_kernel<binary16>";
     }
 };
 
@@ -205,9 +130,7 @@ extern "C" int wise_l2sq16_prepare(const uint16_t* rows, int64_t N, int d, float
     WISE_CHECK_ARG(((uintptr_t)rows & 15) == 0 && ((uintptr_t)half & 3) == 0, "l2sq16_prepare: rows must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (N > 0) {
-        long long grid = (N + 3) / 4;
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(l2sq16_half_norm_kernel, dim3((unsigned)grid), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(rows),
+        hipLaunchKernelGGL(l2sq16_half_norm_kernel, dim3(wave_row_grid(N)), dim3(256), 0, st, reinterpret_cast<const unsigned char*>(rows),
                            (long long)N, d, half);
         WISE_LAUNCH_CHECK("l2sq16_half_norm_kernel");
     }
@@ -223,14 +146,11 @@ extern "C" size_t wise_l2sqfp16_topk_batched_workspace_bytes(int64_t N, int d, i
 extern "C" int wise_l2sq16_topk_batched(const uint16_t* rows, const float* half, const float* norms, int64_t N, int d, const float* Q,
                                         int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
                                         int32_t* counters, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = topk_args("l2sq16_topk_batched", rows, N, d, Q, nq, k, outD, outI)) return rc;
-    WISE_CHECK_ARG(batch_shape_ok(N, d, nq, k),
-                   "l2sq16_topk_batched: N=%lld d=%d nq=%d k=%d not served (d %% 128 == 0 in [256, 1024], nq >= 3, k <= 128, N >= 4096)",
-                   (long long)N, d, nq, k);
-    WISE_CHECK_ARG(half && norms, "l2sq16_topk_batched: null pointer");
+    if (int rc = batched_args("l2sq16_topk_batched", rows, N, d, Q, nq, k, outD, outI, norms, workspace, workspace_bytes,
+                              wise_l2sqfp16_topk_batched_workspace_bytes(N, d, nq, k)))
+        return rc;
+    WISE_CHECK_ARG(half, "l2sq16_topk_batched: null pointer");
     WISE_CHECK_ARG(((uintptr_t)half & 3) == 0, "l2sq16_topk_batched: half must be 4-byte aligned");
-    const size_t need = wise_l2sqfp16_topk_batched_workspace_bytes(N, d, nq, k);
-    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "l2sq16_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
     return topk_batched<MetricL2SQ16>("l2sq16_topk_batched", rows, rows, half, norms, N, d, Q, nullptr, nq, k, ids, id_base, outD, outI, counters,
                                       workspace, (hipStream_t)stream);
 }

@@ -48,76 +48,9 @@ __global__ __launch_bounds__(256) void l2_half_norm_kernel(const float* __restri
     }
 }
 
-// ---- the batched search (wise_l2_topk_batched): the pass of flat_codec_scan.h in its threshold form for distances.  With
-// qb = bf16(q) and xb the bf16 rows, |q - x|^2 / 2 = |q|^2 / 2 + |x|^2 / 2 - q . x, and a(r) = half[r] - (qb . xb_r on the matrix
-// cores) approximates (dist(q, r) - |q|^2) / 2 within eps (restated at l2_stage_kernel).  This type's own:
-//   stage    the queries rounded to bf16 (ONE piece), |q|^2 and eps per query; a query whose bf16 image or whose eps is not finite
-//            hands the pass to the exact scan at once
-//   sample   t = the k-th smallest distance over the sample is an upper bound of the index's exact k-th, so every row of the exact
-//            top-k has a(r) <= thr = (t - |q|^2) / 2 + eps
-//   collect  every (query, row) with a(r) <= thr[query] is listed
-
-// block = one wave = one query.  eps bounds |a(r) - (dist(q, r) - |q|^2) / 2| plus what the threshold's own arithmetic loses, for
-// EVERY row, from norms[0] = M = max |x| and norms[1] = Rx = max |x - xb| alone (u = 2^-24):
-//   |q - qb| M                      the query's rounding (Cauchy-Schwarz)
-//   |qb| Rx                         the rows' rounding
-//   d 2^-22 |q| (M + Rx)            fp32 accumulation of the matrix-core sum (as IndexSQfp16 bounds it)
-//   d u M^2 / 2                     the rounding of half[r]: 4 d / 256 <= 16 fmaf and 6 adds of non-negative terms, halved exactly
-//   (d + 2) u (|q| + M)^2           the contract distance against the real one; the band needs half of it, the other half pays for
-//                                   the rounding of |q|^2 (a sum like half[r]'s), of half[r] - acc and of the threshold's three
-//                                   operations, each a few u of at most (|q| + M)^2
-//   sqrt(d) (|q| + M) 2^-125 + 1e-33  operands or partial results below the normal range, flushed or not
-// every factor is an fp32 result itself and is rounded up by 1.001.
-__global__ __launch_bounds__(64) void l2_stage_kernel(const float* __restrict__ Q, int d, const float* __restrict__ norms, BatchSlots ws) {
-#pragma clang fp contract(off)
-    const int lane = threadIdx.x, q = blockIdx.x;
-    float e2 = 0.f, q2 = 0.f, b2 = 0.f;
-    bool bad = false;
-    for (int i = lane; i < d; i += 64) {
-        const float v = Q[(size_t)q * d + i];
-        const bf16_t h = f32_to_bf16(v);
-        ws.qb[(size_t)q * d + i] = h;
-        const float back = bf16_to_f32(h), r = v - back;
-        bad = bad || !is_finite_f32(back);                        // the bf16 image is infinite or NaN
-        e2 = fmaf(r, r, e2);
-        q2 = fmaf(v, v, q2);
-        b2 = fmaf(back, back, b2);
-    }
-    e2 = wave_sum(e2);
-    q2 = wave_sum(q2);
-    b2 = wave_sum(b2);
-    const bool any_bad = __ballot(bad) != 0;
-    if (lane == 0) {
-        const float u = 5.9604644775390625e-08f, fd = (float)d;
-        const float M = norms[0] * 1.001f, Rx = norms[1] * 1.001f;
-        const float nq = sqrtf(q2) * 1.001f, ne = sqrtf(e2) * 1.001f, nb = sqrtf(b2) * 1.001f;
-        const float reach = nq + M;
-        float eps = ne * M;
-        eps = eps + nb * Rx;
-        eps = eps + fd * 4.f * u * nq * (M + Rx);
-        eps = eps + fd * u * 0.5f * M * M;
-        eps = eps + (fd + 2.f) * u * reach * reach;
-        eps = eps + sqrtf(fd) * reach * 2.35098870164457501594e-38f + 1e-33f;
-        eps = eps * 1.001f;
-        // A query whose bf16 image is not finite, or whose band is not (|q| or M beyond ~1e19), has no usable matrix-core score:
-        // it raises the pass's flag here — the host cleared it before this launch — and the exact scan answers the pass.  Every
-        // block that raises it stores the same value.
-        if (any_bad || !is_finite_f32(eps) || !is_finite_f32(q2)) {
-            eps = __builtin_inff();
-            *ws.flag = 1;
-        }
-        ws.eps[q] = eps;
-        ws.q2[q] = q2;
-        ws.thr[q] = __builtin_inff();
-        ws.ctl[q] = 0;
-    }
-}
-
-// thr of a query whose k-th smallest exact distance over some of the rows is t: (t - |q|^2) / 2 + eps, rounded up
-__device__ __forceinline__ float threshold_above(float t, float q2, float eps) {
-#pragma clang fp contract(off)
-    return ((0.5f * t - 0.5f * q2) + eps) + (t + q2) * 2.384185791015625e-07f + 1e-37f;
-}
+// ---- the batched search (wise_l2_topk_batched): the pass of flat_codec_scan.h in its threshold form for distances —
+// l2_stage_kernel<bf16_t, true> and threshold_above there: the bf16 image of the queries against the bf16 copy of the rows, whose
+// rounding (norms[1]) is part of eps.
 
 // THE POLICY (flat_codec_scan.h): the keys order the negated distance, smaller distances are better
 struct MetricL2 : PlainPolicy {
@@ -141,8 +74,8 @@ struct MetricL2 : PlainPolicy {
     static constexpr bool HALF_NORMS = true;
     static __device__ __forceinline__ bool candidate(float hv, float acc, float thr) { return !(hv - acc > thr); }
     static const char* stage(const float* Q, int d, const float* norms, const BatchSlots& ws, int nq, hipStream_t st) {
-        hipLaunchKernelGGL(l2_stage_kernel, dim3(nq), dim3(64), 0, st, Q, d, norms, ws);
-        return "l2_stage_kernel";
+        hipLaunchKernelGGL((l2_stage_kernel<bf16_t, true>), dim3(nq), dim3(64), 0, st, Q, d, norms, ws);
+        return "l2_stage_kernel<bf16>";
     }
 };
 
@@ -202,9 +135,7 @@ extern "C" int wise_l2_half_norms(const float* X, int64_t N, int d, float* half,
     WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && ((X && half) || N == 0), "l2_half_norms: bad argument");
     WISE_CHECK_ARG(((uintptr_t)X & 15) == 0, "l2_half_norms: X must be 16-byte aligned");
     if (N == 0) return WISE_OK;
-    long long grid = (N + 3) / 4;
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(l2_half_norm_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, X, (long long)N, d, half);
+    hipLaunchKernelGGL(l2_half_norm_kernel, dim3(wave_row_grid(N)), dim3(256), 0, (hipStream_t)stream, X, (long long)N, d, half);
     WISE_LAUNCH_CHECK("l2_half_norm_kernel");
     return WISE_OK;
 }
@@ -216,14 +147,11 @@ extern "C" size_t wise_l2_topk_batched_workspace_bytes(int64_t N, int d, int nq,
 extern "C" int wise_l2_topk_batched(const float* X, const uint16_t* Xb, const float* half, const float* norms, int64_t N, int d,
                                     const float* Q, int nq, int k, const int64_t* ids, int64_t id_base, float* outD, int64_t* outI,
                                     int32_t* counters, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = topk_args("l2_topk_batched", X, N, d, Q, nq, k, outD, outI)) return rc;
-    WISE_CHECK_ARG(batch_shape_ok(N, d, nq, k),
-                   "l2_topk_batched: N=%lld d=%d nq=%d k=%d not served (d %% 128 == 0 in [256, 1024], nq >= 3, k <= 128, N >= 4096)",
-                   (long long)N, d, nq, k);
-    WISE_CHECK_ARG(Xb && half && norms, "l2_topk_batched: null pointer");
+    if (int rc = batched_args("l2_topk_batched", X, N, d, Q, nq, k, outD, outI, norms, workspace, workspace_bytes,
+                              wise_l2_topk_batched_workspace_bytes(N, d, nq, k)))
+        return rc;
+    WISE_CHECK_ARG(Xb && half, "l2_topk_batched: null pointer");
     WISE_CHECK_ARG(((uintptr_t)Xb & 15) == 0 && ((uintptr_t)half & 3) == 0, "l2_topk_batched: Xb must be 16-byte aligned");
-    const size_t need = wise_l2_topk_batched_workspace_bytes(N, d, nq, k);
-    WISE_CHECK_ARG(workspace && workspace_bytes >= need, "l2_topk_batched: workspace %zu < %zu bytes", workspace_bytes, need);
     return topk_batched<MetricL2>("l2_topk_batched", X, Xb, half, norms, N, d, Q, nullptr, nq, k, ids, id_base, outD, outI, counters, workspace,
                                   (hipStream_t)stream);
 }

@@ -1,5 +1,5 @@
-// Sortable 64-bit (score,row) keys shared by the scan kernels and the merge kernels, and what the flat-search files
-// (ip_topk.hip, ip_range.hip, ip_shadow.hip, ip_topk_mfma.hip) share.
+// Sortable 64-bit (score,row) keys shared by the scan kernels and the merge kernels, the id lookup of the reconstruct kernels
+// (row_of_id), and what the flat-search files (ip_topk.hip, ip_range.hip, ip_shadow.hip, ip_topk_mfma.hip) share.
 #pragma once
 #include "common.h"
 
@@ -18,6 +18,22 @@ __device__ __forceinline__ float f32_unorder(unsigned o) {
 // larger key = better: higher score first, then lower row
 __device__ __forceinline__ u64 make_key(float score, unsigned row) {
     return ((u64)f32_order(score) << 32) | (u64)(0xFFFFFFFFu - row);
+}
+
+// THE ROW OF AN ID (the reconstruct kernels, find_kernel of ivf_pq.hip).  Block-wide: every thread of the block calls it with the
+// same arguments and gets the row that carries the id `want`, or -1.  ids == nullptr: the ids are id_base + row.  The highest
+// position wins where an id repeats.
+__device__ __forceinline__ long long row_of_id(const long long* __restrict__ ids, long long id_base, long long N, long long want) {
+    __shared__ unsigned long long s_row1;  // row + 1, 0 = not found
+    if (threadIdx.x == 0)
+        s_row1 = ids ? 0ull : ((want >= id_base && want - id_base < N) ? (unsigned long long)(want - id_base + 1) : 0ull);
+    __syncthreads();
+    if (ids) {
+        for (long long r = threadIdx.x; r < N; r += blockDim.x)
+            if (ids[r] == want) atomicMax(&s_row1, (unsigned long long)(r + 1));
+        __syncthreads();
+    }
+    return (long long)s_row1 - 1;
 }
 
 __device__ __forceinline__ void wave_lds_fence() {

@@ -4,11 +4,23 @@
                   their fill mark, the chunks added since the last merge, rows adopted as they are, the implicit ids
                   (id_base + row) of adopted rows, and the compaction of a removal.  Pure torch: it works on the host too.
   FlatIndexBase   everything that does not depend on the payload: ntotal, reserve, adopt, remove_ids, the argument handling of
-                  add_with_ids, the numpy search / range_search, range_search_device and reconstruct_batch over the entry points
-                  a subclass names, rows_host, and the grow-only workspaces.
+                  add_with_ids, the numpy search / range_search, range_search_device, reconstruct_batch and the exact scan
+                  (`_exact_scan`: all rows, or the rows pos[]) over the entry points a subclass names, rows_host, the grow-only
+                  workspaces, and the fp32 staging of rows on their way to an encoder (`_staged`).
+  FlatCodecIndex  the search of the types of csrc/flat_codec_scan.h (IndexFlatL2, IndexSQfp16, IndexSQfp16L2, IndexSQ8bit), ONE
+                  ROUTE: `_finalize`, the queries, then
+                    a selector                    -> the exact scan over its positions (`_TOPK[2]`)
+                    BATCH_MIN_ROWS rows and BATCH_MIN_QUERIES queries or more, a shape the batched search serves
+                    (`_BATCHED[0]` != 0) and `_batch_operands()` not None
+                                                  -> the batched search (`_BATCHED[1]`), counted in `_counters`
+                    everything else               -> the exact scan over all rows (`_TOPK[1]`), up to 4 queries a pass
+                  Every call is rows, `_payload_args()`, [the operands,] N, d, ... in the order of include/wise_hip.h.
+                  THE HOOK `_batch_operands()` returns the device tensors the batched entry point takes between the payload and
+                  N — built on first use, dropped by the class's `_rows_changed` — or None where they cannot be built.
 
-A subclass keeps the constructor's shape check, how rows enter their slot (`_fill`: a copy, or the binary16 encoder),
-`search_device` with its dispatch rules, and whatever it derives from the rows — which it drops in `_rows_changed`.
+A subclass keeps the constructor's shape check (`check_codec_shape` under its own name), how rows enter their slot (`_fill`: a
+copy, or an encoder over `_staged`), its entry-point names and BATCH_MIN_* values, and whatever it derives from the rows — which
+it drops in `_rows_changed`.  FlatIPIndex (shadow routing) and FlatPQIPIndex (tables, query chunks) keep a search_device of their own.
 """
 from __future__ import annotations
 
@@ -21,6 +33,12 @@ from .. import _lib
 from . import mutate as _mutate
 from . import range_search as _range
 from .selector import resolve_for, unpack_params
+
+
+def check_codec_shape(name: str, d: int) -> None:
+    """The row widths csrc/flat_codec_scan.h serves; name: the faiss name the message opens with"""
+    if d < 16 or d % 16 != 0 or d > 1024:
+        raise ValueError(f"{name}: d={d} must be a multiple of 16 in [16, 1024]")
 
 
 class RowStore:
@@ -115,9 +133,11 @@ class RowStore:
 class FlatIndexBase:
     REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
     metric = "ip"        # "l2" (flat_l2.py): D holds squared distances, ascending; a range hit is dist < thresh
-    # entry points of the subclass's payload: (workspace bytes, count pass, fill pass) of range_search, and reconstruct_batch's
+    # entry points of the subclass's payload: (workspace bytes, count pass, fill pass) of range_search, reconstruct_batch's, and
+    # (workspace bytes, all rows, the rows pos[]) of the exact scan
     _RANGE: Tuple[str, str, str]
     _RECONSTRUCT: str
+    _TOPK: Tuple[str, str, str]
 
     def _payload_args(self) -> tuple:
         """What the range and reconstruct entry points of the subclass take right behind the rows: nothing, or the device address
@@ -167,6 +187,21 @@ class FlatIndexBase:
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError(f"add_with_ids: expected [n,{self.d}], got {tuple(x.shape)}")
         self._fill(self._slot(x.shape[0], ids, "add_with_ids"), x)
+
+    def _staged(self, x: torch.Tensor):
+        """x [n,d] (host or device) as float32 device chunks of at most ENCODE_BYTES (the subclass's): (start, chunk) pairs.  A
+        chunk that is on the device, contiguous and float32 already is a view of x; any other is copied — and converted — through
+        ONE staging buffer, so that no fp32 form of the whole input exists in HBM."""
+        rows = max(1, self.ENCODE_BYTES // (4 * self.d))
+        stage = None
+        for s in range(0, x.shape[0], rows):
+            part = x[s:s + rows]
+            if part.device.type != self.device.type or not part.is_contiguous() or part.dtype != torch.float32:
+                if stage is None:
+                    stage = torch.empty(min(rows, x.shape[0]), self.d, dtype=torch.float32, device=self.device)
+                stage[:part.shape[0]].copy_(part)
+                part = stage[:part.shape[0]]
+            yield s, part
 
     def adopt(self, rows: torch.Tensor, ids: Optional[torch.Tensor] = None, id_base: int = 0):
         """Take ownership of rows already resident in HBM (no copy, no conversion). ids None => id = id_base + row."""
@@ -223,6 +258,20 @@ class FlatIndexBase:
             ws = torch.empty(need, dtype=torch.uint8, device=self.device)
             setattr(self, name, ws)
         return ws
+
+    def _exact_scan(self, lib, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor, pos: Optional[torch.Tensor] = None) -> None:
+        """The exact scan of the queries q [nq >= 1, d] into D / I [nq,k]: over every row (`_TOPK[1]`), or over the rows at the
+        ascending positions pos (`_TOPK[2]`: a resolved selector)."""
+        bytes_name, all_name, pos_name = self._TOPK
+        X, n, nq = self._store.rows, self._store.n, q.shape[0]
+        need = getattr(lib, bytes_name)(n if pos is None else pos.numel(), self.d, nq, k)
+        if need == 0:
+            raise ValueError(f"search: unsupported shape N={n} d={self.d} nq={nq} k={k}")
+        ws = self._grown("_ws", need)
+        name = all_name if pos is None else pos_name
+        over = () if pos is None else (pos.data_ptr(), pos.numel())
+        _lib.check(getattr(lib, name)(X.data_ptr(), *self._payload_args(), n, self.d, *over, q.data_ptr(), nq, k, _lib.ptr(self._store.ids),
+                                      self._store.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()), name)
 
     def search(self, x, k: int, params=None):
         """faiss signature: x np.ndarray [nq,d] float32 -> (D, I) numpy (feature_search_index.py:113).
@@ -282,3 +331,63 @@ class FlatIndexBase:
                                              self._store.id_base, qi.data_ptr(), qi.numel(), out.data_ptr(), _lib.stream_ptr())
         _lib.check(rc, self._RECONSTRUCT)
         return out.cpu().numpy()
+
+
+class FlatCodecIndex(FlatIndexBase):
+    """The search route of the types of csrc/flat_codec_scan.h (module docstring).  A subclass sets BATCH_MIN_ROWS and
+    BATCH_MIN_QUERIES where it records their measurement."""
+    BATCH_MIN_ROWS: int
+    BATCH_MIN_QUERIES: int
+    _BATCHED: Tuple[str, str]        # entry points of the batched search: (workspace bytes, the search)
+
+    def __init__(self, d: int, device, dtype: torch.dtype, what: str):
+        super().__init__(d, device, dtype, what)
+        self._counters: Optional[torch.Tensor] = None  # device [2] int32: queries answered from the lists / by the exact scan
+        self._bws: Optional[torch.Tensor] = None
+
+    def _batch_operands(self) -> Optional[tuple]:
+        """THE HOOK (module docstring): the tensors of the batched call between the payload and N, or None."""
+        raise NotImplementedError
+
+    def search_device(self, q: torch.Tensor, k: int, sel=None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32 — squared distances, ascending, under metric "l2" —, I [nq,k] int64) on device,
+        no host sync.  BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the matrix-core passes where
+        they serve the shape (the same bits); everything else through the exact scan, up to 4 queries a pass.
+        sel: an IDSelector (selector.py) — only the rows it selects compete, by the scan over their positions."""
+        lib = _lib.lib()
+        self._finalize()
+        q = self._queries(q, "search")
+        nq, k = q.shape[0], int(k)
+        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
+        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return D, I
+        pos = None if sel is None else resolve_for(self, sel).positions()
+        batch = pos is None and self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
+        if not (batch and self._batched_scan(lib, q, k, D, I)):
+            self._exact_scan(lib, q, k, D, I, pos)
+        return D, I
+
+    def _batched_scan(self, lib, q: torch.Tensor, k: int, D: torch.Tensor, I: torch.Tensor) -> bool:
+        """The batched search of the queries q into D / I; False where it does not serve the shape or its operands cannot be built."""
+        bytes_name, name = self._BATCHED
+        n, nq = self._store.n, q.shape[0]
+        need = getattr(lib, bytes_name)(n, self.d, nq, k)
+        operands = self._batch_operands() if need else None
+        if operands is None:
+            return False
+        bws = self._grown("_bws", need)
+        if self._counters is None:
+            self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
+        _lib.check(getattr(lib, name)(self._store.rows.data_ptr(), *self._payload_args(), *(t.data_ptr() for t in operands), n, self.d,
+                                      q.data_ptr(), nq, k, _lib.ptr(self._store.ids), self._store.id_base, D.data_ptr(), I.data_ptr(),
+                                      self._counters.data_ptr(), bws.data_ptr(), bws.numel(), _lib.stream_ptr()), name)
+        return True
+
+    def batched_counts(self):
+        """(queries answered from the candidate lists, queries handed to the exact scan) over the batched searches of THIS index so
+        far.  Synchronises (a diagnostic, not part of the search path)."""
+        if self._counters is None:
+            return 0, 0
+        c = self._counters.cpu()
+        return int(c[0]), int(c[1])

@@ -48,6 +48,7 @@ class FlatIPIndex(FlatIndexBase):
 
     _RANGE = ("wise_ip_range_workspace_bytes", "wise_ip_range_count_f32", "wise_ip_range_fill_f32")
     _RECONSTRUCT = "wise_reconstruct_batch"
+    _TOPK = ("wise_ip_topk_workspace_bytes", "wise_ip_topk_f32", "wise_ip_topk_pos_f32")
 
     @property
     def _X(self) -> Optional[torch.Tensor]:
@@ -69,13 +70,15 @@ class FlatIPIndex(FlatIndexBase):
         list of selected positions (wise_ip_topk_pos_f32); the shadow copies and their counters are not touched."""
         lib = _lib.lib()
         self._finalize()
-        if sel is not None:
-            return self._search_selected(lib, q, k, resolve_for(self, sel))
+        res = None if sel is None else resolve_for(self, sel)
         q = self._queries(q, "search")
         nq = q.shape[0]
         D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
         I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
         if nq == 0:
+            return D, I
+        if res is not None:
+            self._exact_scan(lib, q, k, D, I, res.positions())
             return D, I
         # one query (the reference's shape) at any k <= 1024 — REST `end` = 20, evaluation k = 100 / 1000 —, or two and
         # more where the matrix-core passes apply (d = 256 / 512 / 768 / 1024: k <= 12 from two queries on, k <= 128 —
@@ -125,32 +128,7 @@ class FlatIPIndex(FlatIndexBase):
             self._shadow_calls += 1
             self._review_shadow()
             return D, I
-        need = lib.wise_ip_topk_workspace_bytes(self._n, self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        self._grown("_ws", need)
-        rc = lib.wise_ip_topk_f32(self._X.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids),
-                                  self.id_base, D.data_ptr(), I.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                  _lib.stream_ptr())
-        _lib.check(rc, "wise_ip_topk_f32")
-        return D, I
-
-    def _search_selected(self, lib, q: torch.Tensor, k: int, res):
-        q = self._queries(q, "search")
-        nq = q.shape[0]
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        if nq == 0:
-            return D, I
-        pos = res.positions()
-        need = lib.wise_ip_topk_workspace_bytes(pos.numel(), self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        self._grown("_ws", need)
-        rc = lib.wise_ip_topk_pos_f32(self._X.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
-                                      _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), self._ws.data_ptr(),
-                                      self._ws.numel(), _lib.stream_ptr())
-        _lib.check(rc, "wise_ip_topk_pos_f32")
+        self._exact_scan(lib, q, k, D, I)
         return D, I
 
     def _ensure_shadow(self, lib) -> bool:

@@ -23,16 +23,14 @@ from typing import Optional
 import torch
 
 from .. import _lib
-from .flat_common import FlatIndexBase
-from .selector import resolve_for
+from .flat_common import FlatCodecIndex, check_codec_shape
 
 
 def check_shape(d: int) -> None:
-    if d < 16 or d % 16 != 0 or d > 1024:
-        raise ValueError(f"IndexFlatL2: d={d} must be a multiple of 16 in [16, 1024]")
+    check_codec_shape("IndexFlatL2", d)
 
 
-class FlatL2Index(FlatIndexBase):
+class FlatL2Index(FlatCodecIndex):
     metric = "l2"
     # PROVISIONAL: rows from which search_device hands a batch to wise_l2_topk_batched (below it the bf16 copy is never built).
     # FlatSQfp16IPIndex's floor; tools/flatl2_bench.py measured ONE size (10M x 512), so the row count at which the batched search
@@ -45,6 +43,8 @@ class FlatL2Index(FlatIndexBase):
     BATCH_MIN_QUERIES = 8
     _RANGE = ("wise_l2_range_workspace_bytes", "wise_l2_range_count_f32", "wise_l2_range_fill_f32")
     _RECONSTRUCT = "wise_reconstruct_batch"          # the fp32 rows as they were added
+    _TOPK = ("wise_l2_topk_workspace_bytes", "wise_l2_topk_f32", "wise_l2_topk_pos_f32")
+    _BATCHED = ("wise_l2_topk_batched_workspace_bytes", "wise_l2_topk_batched")
 
     def __init__(self, d: int, device: str = "cuda"):
         check_shape(d)
@@ -52,8 +52,6 @@ class FlatL2Index(FlatIndexBase):
         self._Xb: Optional[torch.Tensor] = None      # [N,d] bf16 bits (int16) on device
         self._half: Optional[torch.Tensor] = None    # [N] fp32: |x|^2 / 2
         self._norms: Optional[torch.Tensor] = None   # device [2]: largest row norm, largest bf16 rounding-residual norm
-        self._counters: Optional[torch.Tensor] = None  # device [2] int32: queries answered from the lists / by the exact scan
-        self._bws: Optional[torch.Tensor] = None
 
     @property
     def _X(self):
@@ -72,67 +70,18 @@ class FlatL2Index(FlatIndexBase):
         a fresh index over the rows would."""
         self._Xb = self._half = self._norms = None
 
-    def _ensure_prepared(self, lib) -> bool:
-        """Build the bf16 copy, the half-norms and the norms if they are not there; False (and the batched route switched off for
+    def _batch_operands(self):
+        """(Xb, half, norms) of wise_l2_topk_batched, built if they are not there; None (and the batched route switched off for
         this index) when HBM has no room for them."""
-        if self._Xb is not None:
-            return True
-        free, _ = torch.cuda.mem_get_info(self.device)
-        if free < self._n * (2 * self.d + 4) + (2 << 30):       # keep 2 GiB for workspaces and the caller
-            self.BATCH_MIN_ROWS = 1 << 62
-            return False
-        Xb = torch.empty(self._n, self.d, dtype=torch.int16, device=self.device)
-        half = torch.empty(self._n, dtype=torch.float32, device=self.device)
-        norms = torch.zeros(2, dtype=torch.float32, device=self.device)
-        _lib.check(lib.wise_l2_prepare(self._X.data_ptr(), self._n, self.d, Xb.data_ptr(), half.data_ptr(), norms.data_ptr(),
-                                       _lib.stream_ptr()), "wise_l2_prepare")
-        self._Xb, self._half, self._norms = Xb, half, norms
-        return True
-
-    # -- search ---------------------------------------------------------------------------------
-    def search_device(self, q: torch.Tensor, k: int, sel=None):
-        """q [nq,d] fp32 on device -> (D [nq,k] fp32 squared distances, ascending; I [nq,k] int64) on device, no host sync.
-        BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the matrix-core passes where they serve the
-        shape (wise_l2_topk_batched: the same bits); everything else through the exact scan, up to 4 queries a pass.
-        sel: an IDSelector (selector.py) — only the rows it selects compete, by the scan over their positions."""
-        lib = _lib.lib()
-        self._finalize()
-        q = self._queries(q, "search")
-        nq, k = q.shape[0], int(k)
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        if nq == 0:
-            return D, I
-        st = _lib.stream_ptr()
-        pos = None if sel is None else resolve_for(self, sel).positions()
-        need = lib.wise_l2_topk_workspace_bytes(self._n if pos is None else pos.numel(), self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        ws = self._grown("_ws", need)
-        if pos is not None:
-            _lib.check(lib.wise_l2_topk_pos_f32(self._X.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
-                                                _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), st), "wise_l2_topk_pos_f32")
-            return D, I
-        batch = self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
-        bneed = lib.wise_l2_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
-        if bneed and self._ensure_prepared(lib):
-            self._grown("_bws", bneed)
-            if self._counters is None:
-                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
-            _lib.check(lib.wise_l2_topk_batched(self._X.data_ptr(), self._Xb.data_ptr(), self._half.data_ptr(), self._norms.data_ptr(),
-                                                self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base, D.data_ptr(),
-                                                I.data_ptr(), self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
-                       "wise_l2_topk_batched")
-            return D, I
-        _lib.check(lib.wise_l2_topk_f32(self._X.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base,
-                                        D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_l2_topk_f32")
-        return D, I
-
-    def batched_counts(self):
-        """(queries answered from the candidate lists, queries handed to the exact scan) over the batched searches of THIS index so
-        far.  Synchronises (a diagnostic, not part of the search path)."""
-        if self._counters is None:
-            return 0, 0
-        c = self._counters.cpu()
-        return int(c[0]), int(c[1])
+        if self._Xb is None:
+            free, _ = torch.cuda.mem_get_info(self.device)
+            if free < self._n * (2 * self.d + 4) + (2 << 30):       # keep 2 GiB for workspaces and the caller
+                self.BATCH_MIN_ROWS = 1 << 62
+                return None
+            Xb = torch.empty(self._n, self.d, dtype=torch.int16, device=self.device)
+            half = torch.empty(self._n, dtype=torch.float32, device=self.device)
+            norms = torch.zeros(2, dtype=torch.float32, device=self.device)
+            _lib.check(_lib.lib().wise_l2_prepare(self._X.data_ptr(), self._n, self.d, Xb.data_ptr(), half.data_ptr(), norms.data_ptr(),
+                                                  _lib.stream_ptr()), "wise_l2_prepare")
+            self._Xb, self._half, self._norms = Xb, half, norms
+        return self._Xb, self._half, self._norms

@@ -56,19 +56,6 @@ class FlatPQIPIndex(PQCodebooks, FlatIndexBase):
         self.is_trained = False
 
     # -- training -------------------------------------------------------------------------------
-    def _staged(self, x: torch.Tensor):
-        """x [n,d] float32 (host or device) as device chunks of at most ENCODE_BYTES: (start, chunk) pairs"""
-        rows = max(1, self.ENCODE_BYTES // (4 * self.d))
-        stage = None
-        for s in range(0, x.shape[0], rows):
-            part = x[s:s + rows]
-            if part.device.type != self.device.type or not part.is_contiguous() or part.dtype != torch.float32:
-                if stage is None:
-                    stage = torch.empty(min(rows, x.shape[0]), self.d, dtype=torch.float32, device=self.device)
-                stage[:part.shape[0]].copy_(part)
-                part = stage[:part.shape[0]]
-            yield s, part
-
     def training_rows(self, x: torch.Tensor) -> torch.Tensor:
         """The rows the codebooks are trained on: rows perm[:65536] of x (seeded host permutation), in that order, on the device."""
         perm = np.random.default_rng(self.seed).permutation(x.shape[0])[:MAX_TRAIN_ROWS].astype(np.int64)

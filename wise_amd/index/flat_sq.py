@@ -21,13 +21,11 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .flat_common import FlatIndexBase
-from .selector import resolve_for
+from .flat_common import FlatCodecIndex, check_codec_shape
 
 
 def check_shape(d: int) -> None:
-    if d < 16 or d % 16 != 0 or d > 1024:
-        raise ValueError(f"IndexSQfp16: d={d} must be a multiple of 16 in [16, 1024]")
+    check_codec_shape("IndexSQfp16", d)
 
 
 def _halves(t: torch.Tensor) -> torch.Tensor:
@@ -39,7 +37,7 @@ def _halves(t: torch.Tensor) -> torch.Tensor:
     raise ValueError(f"IndexSQfp16: binary16 rows expected (float16, or int16 bit patterns), got {t.dtype}")
 
 
-class FlatSQfp16IPIndex(FlatIndexBase):
+class FlatSQfp16IPIndex(FlatCodecIndex):
     # PROVISIONAL: rows from which search_device hands a batch of 3 or more queries to wise_ipsq16_topk_batched.  FlatIPIndex's floor
     # for its shadow passes; provisional because tools/sqfp16_bench.py measured ONE size (10M x 512) and two batch sizes (1 and 256):
     # neither the row count nor the batch size at which the batched search overtakes the exact scan's 4-query passes is measured
@@ -51,13 +49,13 @@ class FlatSQfp16IPIndex(FlatIndexBase):
     ENCODE_BYTES = 64 << 20          # fp32 staging of add_with_ids: rows are encoded on the GPU this many bytes at a time
     _RANGE = ("wise_ipsqfp16_range_workspace_bytes", "wise_ipsq16_range_count", "wise_ipsq16_range_fill")
     _RECONSTRUCT = "wise_ipsq16_reconstruct"         # the halves widened to float32: float32(float16(x)) of what was added
+    _TOPK = ("wise_ipsqfp16_topk_workspace_bytes", "wise_ipsq16_topk", "wise_ipsq16_topk_pos")
+    _BATCHED = ("wise_ipsqfp16_topk_batched_workspace_bytes", "wise_ipsq16_topk_batched")
 
     def __init__(self, d: int, device: str = "cuda"):
         check_shape(d)
         super().__init__(d, device, torch.float16, f"H must be contiguous binary16 [N,{int(d)}] on the index's device")
         self._norms: Optional[torch.Tensor] = None   # device [1]: the largest row norm (wise_ipsq16_prepare), built on demand
-        self._counters: Optional[torch.Tensor] = None  # device [2] int32: queries answered from the lists / by the exact scan
-        self._bws: Optional[torch.Tensor] = None
 
     # -- construction ---------------------------------------------------------------------------
     @property
@@ -69,25 +67,13 @@ class FlatSQfp16IPIndex(FlatIndexBase):
         """Bytes of HBM the index itself holds: the halves and the ids (workspaces and the encoder's staging are not part of it)."""
         return self._n * (2 * self.d + (8 if self._store.has_ids else 0))
 
-    def _encode_into(self, x: torch.Tensor, dst: torch.Tensor) -> None:
-        """dst [n,d] float16 (device) = binary16(x [n,d] float32, host or device): wise_sq16_encode over chunks staged in HBM, so
-        that the fp32 form of the index never exists there."""
-        lib = _lib.lib()
-        rows = max(1, self.ENCODE_BYTES // (4 * self.d))
-        stage = None
-        for s in range(0, x.shape[0], rows):
-            part = x[s:s + rows]
-            if part.device.type != self.device.type or not part.is_contiguous():
-                if stage is None:
-                    stage = torch.empty(min(rows, x.shape[0]), self.d, dtype=torch.float32, device=self.device)
-                stage[:part.shape[0]].copy_(part)
-                part = stage[:part.shape[0]]
-            _lib.check(lib.wise_sq16_encode(part.data_ptr(), part.shape[0], self.d, dst[s:s + rows].data_ptr(), _lib.stream_ptr()),
-                       "wise_sq16_encode")
-
     def _fill(self, dst: torch.Tensor, x: torch.Tensor) -> None:
-        """add_with_ids: the rows are rounded to binary16 on the GPU (numpy's float32 -> float16 cast)"""
-        self._encode_into(x.to(torch.float32), dst)
+        """add_with_ids: the rows are rounded to binary16 on the GPU (wise_sq16_encode: numpy's float32 -> float16 cast), chunk by
+        chunk, so that the fp32 form of the index never exists in HBM"""
+        lib = _lib.lib()
+        for s, part in self._staged(x):
+            _lib.check(lib.wise_sq16_encode(part.data_ptr(), part.shape[0], self.d, dst[s:s + part.shape[0]].data_ptr(),
+                                            _lib.stream_ptr()), "wise_sq16_encode")
 
     def add_halves_with_ids(self, h, ids) -> None:
         """h [n,d] binary16 (numpy float16, or a float16 / int16 tensor), ids [n] int64: rows that are already encoded — an index
@@ -105,71 +91,18 @@ class FlatSQfp16IPIndex(FlatIndexBase):
         self._norms = None
 
     # -- search ---------------------------------------------------------------------------------
-    def _ensure_norms(self, lib) -> torch.Tensor:
+    def _batch_operands(self):
         if self._norms is None:
             self._norms = torch.zeros(1, dtype=torch.float32, device=self.device)
-            _lib.check(lib.wise_ipsq16_prepare(self._H.data_ptr(), self._n, self.d, self._norms.data_ptr(), _lib.stream_ptr()),
+            _lib.check(_lib.lib().wise_ipsq16_prepare(self._H.data_ptr(), self._n, self.d, self._norms.data_ptr(), _lib.stream_ptr()),
                        "wise_ipsq16_prepare")
-        return self._norms
-
-    def search_device(self, q: torch.Tensor, k: int, sel=None):
-        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64) on device, no host sync.
-        BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the matrix-core passes where they serve the shape
-        (wise_ipsq16_topk_batched: the same bits); everything else through the exact scan, up to 4 queries a pass.
-        sel: an IDSelector (selector.py) — only the rows it selects compete, by the scan over their positions."""
-        lib = _lib.lib()
-        self._finalize()
-        q = self._queries(q, "search")
-        nq, k = q.shape[0], int(k)
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        if nq == 0:
-            return D, I
-        st = _lib.stream_ptr()
-        if sel is not None:
-            pos = resolve_for(self, sel).positions()
-            need = lib.wise_ipsqfp16_topk_workspace_bytes(pos.numel(), self.d, nq, k)
-            if need == 0:
-                raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-            ws = self._grown("_ws", need)
-            _lib.check(lib.wise_ipsq16_topk_pos(self._H.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
-                                                _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), st), "wise_ipsq16_topk_pos")
-            return D, I
-        batch = self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
-        need = lib.wise_ipsqfp16_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
-        if need:
-            self._grown("_bws", need)
-            if self._counters is None:
-                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
-            norms = self._ensure_norms(lib)
-            _lib.check(lib.wise_ipsq16_topk_batched(self._H.data_ptr(), norms.data_ptr(), self._n, self.d, q.data_ptr(), nq, k,
-                                                    _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(),
-                                                    self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
-                       "wise_ipsq16_topk_batched")
-            return D, I
-        need = lib.wise_ipsqfp16_topk_workspace_bytes(self._n, self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        ws = self._grown("_ws", need)
-        _lib.check(lib.wise_ipsq16_topk(self._H.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base,
-                                        D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ipsq16_topk")
-        return D, I
-
-    def batched_counts(self):
-        """(queries answered from the candidate lists, queries handed to the exact scan) over the batched searches of THIS index so
-        far.  Synchronises (a diagnostic, not part of the search path)."""
-        if self._counters is None:
-            return 0, 0
-        c = self._counters.cpu()
-        return int(c[0]), int(c[1])
+        return (self._norms,)
 
 
 # -------------------------------------------------------------------------------------------------------------------------------------
 # IndexSQfp16L2
 def check_sqfp16_l2_shape(d: int) -> None:
-    if d < 16 or d % 16 != 0 or d > 1024:
-        raise ValueError(f"IndexSQfp16L2: d={d} must be a multiple of 16 in [16, 1024]")
+    check_codec_shape("IndexSQfp16L2", d)
 
 
 class FlatSQfp16L2Index(FlatSQfp16IPIndex):
@@ -193,6 +126,8 @@ class FlatSQfp16L2Index(FlatSQfp16IPIndex):
     # measured one (5 to 7 were not measured).  The siblings' value, confirmed at that one size
     BATCH_MIN_QUERIES = 8
     _RANGE = ("wise_l2sqfp16_range_workspace_bytes", "wise_l2sq16_range_count", "wise_l2sq16_range_fill")
+    _TOPK = ("wise_l2sqfp16_topk_workspace_bytes", "wise_l2sq16_topk", "wise_l2sq16_topk_pos")
+    _BATCHED = ("wise_l2sqfp16_topk_batched_workspace_bytes", "wise_l2sq16_topk_batched")
 
     def __init__(self, d: int, device: str = "cuda"):
         check_sqfp16_l2_shape(d)
@@ -204,61 +139,20 @@ class FlatSQfp16L2Index(FlatSQfp16IPIndex):
         index over the rows would."""
         self._half = self._norms = None
 
-    def _ensure_norms(self, lib) -> torch.Tensor:
+    def _batch_operands(self):
         if self._norms is None:
             half = torch.empty(self._n, dtype=torch.float32, device=self.device)
             norms = torch.zeros(1, dtype=torch.float32, device=self.device)
-            _lib.check(lib.wise_l2sq16_prepare(self._H.data_ptr(), self._n, self.d, half.data_ptr(), norms.data_ptr(),
-                                               _lib.stream_ptr()), "wise_l2sq16_prepare")
+            _lib.check(_lib.lib().wise_l2sq16_prepare(self._H.data_ptr(), self._n, self.d, half.data_ptr(), norms.data_ptr(),
+                                                      _lib.stream_ptr()), "wise_l2sq16_prepare")
             self._half, self._norms = half, norms
-        return self._norms
-
-    def search_device(self, q: torch.Tensor, k: int, sel=None):
-        """q [nq,d] fp32 on device -> (D [nq,k] fp32 squared distances, ascending; I [nq,k] int64) on device, no host sync.  The
-        routing is FlatSQfp16IPIndex's: BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the
-        matrix-core passes where they serve the shape (wise_l2sq16_topk_batched: the same bits), everything else through the exact
-        scan, up to 4 queries a pass; sel: the scan over the selected rows' positions."""
-        lib = _lib.lib()
-        self._finalize()
-        q = self._queries(q, "search")
-        nq, k = q.shape[0], int(k)
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        if nq == 0:
-            return D, I
-        st = _lib.stream_ptr()
-        pos = None if sel is None else resolve_for(self, sel).positions()
-        batch = pos is None and self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
-        bneed = lib.wise_l2sqfp16_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
-        if bneed:
-            self._grown("_bws", bneed)
-            if self._counters is None:
-                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
-            norms = self._ensure_norms(lib)
-            _lib.check(lib.wise_l2sq16_topk_batched(self._H.data_ptr(), self._half.data_ptr(), norms.data_ptr(), self._n, self.d,
-                                                    q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(),
-                                                    self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
-                       "wise_l2sq16_topk_batched")
-            return D, I
-        need = lib.wise_l2sqfp16_topk_workspace_bytes(self._n if pos is None else pos.numel(), self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        ws = self._grown("_ws", need)
-        if pos is not None:
-            _lib.check(lib.wise_l2sq16_topk_pos(self._H.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq, k,
-                                                _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
-                                                ws.numel(), st), "wise_l2sq16_topk_pos")
-            return D, I
-        _lib.check(lib.wise_l2sq16_topk(self._H.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids), self.id_base,
-                                        D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_l2sq16_topk")
-        return D, I
+        return self._half, self._norms
 
 
 # -------------------------------------------------------------------------------------------------------------------------------------
 # IndexSQ8bit
 def check_sq8_shape(d: int) -> None:
-    if d < 16 or d % 16 != 0 or d > 1024:
-        raise ValueError(f"IndexSQ8bit: d={d} must be a multiple of 16 in [16, 1024]")
+    check_codec_shape("IndexSQ8bit", d)
 
 
 def _codes(t: torch.Tensor) -> torch.Tensor:
@@ -267,7 +161,7 @@ def _codes(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-class FlatSQ8IPIndex(FlatIndexBase):
+class FlatSQ8IPIndex(FlatCodecIndex):
     """faiss-shaped exhaustive inner-product index whose rows live in HBM as ONE BYTE per dimension: IndexSQ8bit.
 
     Stands where `faiss.IndexIDMap(faiss.IndexScalarQuantizer(d, QT_8bit, METRIC_INNER_PRODUCT))` (RS_minmax, argument 0) would
@@ -287,6 +181,8 @@ class FlatSQ8IPIndex(FlatIndexBase):
     ENCODE_BYTES = 64 << 20          # fp32 staging of train / add_with_ids: rows go through the GPU this many bytes at a time
     _RANGE = ("wise_ipsq8_range_workspace_bytes", "wise_ipsq8_range_count", "wise_ipsq8_range_fill")
     _RECONSTRUCT = "wise_ipsq8_reconstruct"          # faiss's Codec8bit decode: vmin + ((code + 0.5) / 255) vdiff
+    _TOPK = ("wise_ipsq8_topk_workspace_bytes", "wise_ipsq8_topk", "wise_ipsq8_topk_pos")
+    _BATCHED = ("wise_ipsq8_topk_batched_workspace_bytes", "wise_ipsq8_topk_batched")
 
     def __init__(self, d: int, device: str = "cuda"):
         check_sq8_shape(d)
@@ -294,23 +190,8 @@ class FlatSQ8IPIndex(FlatIndexBase):
         self.is_trained = False
         self._trained: Optional[torch.Tensor] = None  # device [2 d] fp32: vmin, then vdiff
         self._norms: Optional[torch.Tensor] = None    # device [1]: the largest code norm (wise_ipsq8_prepare), built on demand
-        self._counters: Optional[torch.Tensor] = None
-        self._bws: Optional[torch.Tensor] = None
 
     # -- training -------------------------------------------------------------------------------
-    def _staged(self, x: torch.Tensor):
-        """x [n,d] float32 (host or device) as device chunks of at most ENCODE_BYTES: (start, chunk) pairs"""
-        rows = max(1, self.ENCODE_BYTES // (4 * self.d))
-        stage = None
-        for s in range(0, x.shape[0], rows):
-            part = x[s:s + rows]
-            if part.device.type != self.device.type or not part.is_contiguous() or part.dtype != torch.float32:
-                if stage is None:
-                    stage = torch.empty(min(rows, x.shape[0]), self.d, dtype=torch.float32, device=self.device)
-                stage[:part.shape[0]].copy_(part)
-                part = stage[:part.shape[0]]
-            yield s, part
-
     def minmax(self, x, lohi: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The running per-dimension minimum and maximum of rows x [n,d] float32 (n may be 0) folded into lohi (device [2, d]: lo,
         then hi; None: a fresh one holding +3.4028235e38 / -3.4028235e38) by wise_sq_minmax, chunk by chunk.  Exact and order-free:
@@ -416,55 +297,13 @@ class FlatSQ8IPIndex(FlatIndexBase):
         return super().reconstruct_batch(ids)
 
     # -- search ---------------------------------------------------------------------------------
-    def _ensure_norms(self, lib) -> torch.Tensor:
+    def _batch_operands(self):
         if self._norms is None:
             self._norms = torch.zeros(1, dtype=torch.float32, device=self.device)
-            _lib.check(lib.wise_ipsq8_prepare(self._codes_t.data_ptr(), self._n, self.d, self._norms.data_ptr(), _lib.stream_ptr()),
+            _lib.check(_lib.lib().wise_ipsq8_prepare(self._codes_t.data_ptr(), self._n, self.d, self._norms.data_ptr(), _lib.stream_ptr()),
                        "wise_ipsq8_prepare")
-        return self._norms
+        return (self._norms,)
 
     def search_device(self, q: torch.Tensor, k: int, sel=None):
-        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64) on device, no host sync.  The routing is FlatSQfp16IPIndex's:
-        BATCH_MIN_QUERIES or more queries over BATCH_MIN_ROWS rows or more go through the matrix-core passes where they serve the
-        shape (wise_ipsq8_topk_batched: the same bits), everything else through the exact scan; sel: the scan over its positions."""
-        lib = _lib.lib()
         self._need_trained("search")
-        self._finalize()
-        q = self._queries(q, "search")
-        nq, k = q.shape[0], int(k)
-        D = torch.empty(nq, k, dtype=torch.float32, device=self.device)
-        I = torch.empty(nq, k, dtype=torch.int64, device=self.device)
-        if nq == 0:
-            return D, I
-        st, C, T = _lib.stream_ptr(), self._codes_t, self._trained
-        if sel is not None:
-            pos = resolve_for(self, sel).positions()
-            need = lib.wise_ipsq8_topk_workspace_bytes(pos.numel(), self.d, nq, k)
-            if need == 0:
-                raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-            ws = self._grown("_ws", need)
-            _lib.check(lib.wise_ipsq8_topk_pos(C.data_ptr(), T.data_ptr(), self._n, self.d, pos.data_ptr(), pos.numel(), q.data_ptr(), nq,
-                                               k, _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(),
-                                               ws.numel(), st), "wise_ipsq8_topk_pos")
-            return D, I
-        batch = self._n >= self.BATCH_MIN_ROWS and nq >= self.BATCH_MIN_QUERIES
-        need = lib.wise_ipsq8_topk_batched_workspace_bytes(self._n, self.d, nq, k) if batch else 0
-        if need:
-            self._grown("_bws", need)
-            if self._counters is None:
-                self._counters = torch.zeros(2, dtype=torch.int32, device=self.device)
-            norms = self._ensure_norms(lib)
-            _lib.check(lib.wise_ipsq8_topk_batched(C.data_ptr(), T.data_ptr(), norms.data_ptr(), self._n, self.d, q.data_ptr(), nq, k,
-                                                   _lib.ptr(self._ids), self.id_base, D.data_ptr(), I.data_ptr(),
-                                                   self._counters.data_ptr(), self._bws.data_ptr(), self._bws.numel(), st),
-                       "wise_ipsq8_topk_batched")
-            return D, I
-        need = lib.wise_ipsq8_topk_workspace_bytes(self._n, self.d, nq, k)
-        if need == 0:
-            raise ValueError(f"search: unsupported shape N={self._n} d={self.d} nq={nq} k={k}")
-        ws = self._grown("_ws", need)
-        _lib.check(lib.wise_ipsq8_topk(C.data_ptr(), T.data_ptr(), self._n, self.d, q.data_ptr(), nq, k, _lib.ptr(self._ids),
-                                       self.id_base, D.data_ptr(), I.data_ptr(), ws.data_ptr(), ws.numel(), st), "wise_ipsq8_topk")
-        return D, I
-
-    batched_counts = FlatSQfp16IPIndex.batched_counts
+        return super().search_device(q, k, sel=sel)
