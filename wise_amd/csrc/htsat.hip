@@ -1162,6 +1162,25 @@ extern "C" int wise_debug_swin_attention(const uint16_t* qkv, int B, int H, int 
     return WISE_OK;
 }
 
+// The STFT / log-mel front end alone, through frontend() as both audio towers call it (tests/test_gpu_frontend.py): wave [B, N]
+// fp32 (4-byte aligned is enough: the kernel picks its load path by address), mel_wt [36][64] -> melbn [B, Fc, 64];
+// form 0 = the half-length transform (the one that runs), 1 = the full-length one
+extern "C" int wise_debug_frontend(const float* wave, int B, int N, int Fc, const float* hann, const float* mel_start,
+                                   const float* mel_len, const float* mel_wt, const float* bn_scale, const float* bn_shift,
+                                   float* melbn, int max_band, int form, void* stream) {
+    WISE_CHECK_ARG(wave && hann && mel_start && mel_len && mel_wt && bn_scale && bn_shift && melbn, "debug_frontend: null pointer");
+    WISE_CHECK_ARG(B >= 1 && N >= 513 && Fc >= 1 && Fc <= N / 320 + 1 && (long long)B * Fc * 64 < (1ll << 31) &&
+                       max_band >= 1 && max_band <= FRONT_MELW && (form == 0 || form == 1),
+                   "debug_frontend: B=%d N=%d (at least 513) Fc=%d (1 .. N / 320 + 1) max_band=%d (1 .. %d) form=%d (0 | 1)", B, N,
+                   Fc, max_band, FRONT_MELW, form);
+    WISE_CHECK_ARG(((uintptr_t)wave & 3) == 0 && ((uintptr_t)melbn & 3) == 0, "debug_frontend: wave and melbn must be 4-byte aligned");
+    const int prev = wise::htsat::frontend_set_variant(form);
+    const int rc = wise::htsat::frontend(wave, B, N, Fc, hann, mel_start, mel_len, mel_wt, bn_scale, bn_shift, melbn,
+                                         (hipStream_t)stream, max_band);
+    wise::htsat::frontend_set_variant(prev);
+    return rc;
+}
+
 // The tower's own kernels one by one, through the launch functions htsat_forward_impl calls (tests/test_gpu_audio_kernels.py).
 // embed: melbn [B, Fc, 64] fp32 -> x [B*4096, 96] fp32; form 0 = embed_tok_kernel (the one that runs), 1 = embed_kernel
 extern "C" int wise_debug_htsat_embed(const float* melbn, int B, int Fc, const float* pw, const float* pb, const float* lnw,

@@ -55,6 +55,10 @@ __device__ __forceinline__ void bfly(float2& a, float2& q, const float2 t) {
     q = make_float2(a0.x - tr, a0.y - ti);
 }
 
+// 10 log10(max(p, 1e-10)).  The floor is -100 dB by definition: log10f(1e-10f) comes out one step below -10, which put every band
+// of a silent frame at -100.00001 (tests/test_gpu_frontend.py).
+__device__ __forceinline__ float power_db(float p) { return p > 1e-10f ? 10.f * log10f(p) : -100.f; }
+
 constexpr int FFT_LDS = 1088;  // float2 per wave: max(64 * 17, 1024 + 3 * 16)
 
 // MW = mel weights a lane keeps and applies per frame: the widest band of the filterbank in use (16 FFT bins for the 2023
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(256, 2) void frontend_kernel(const float* __restric
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < MW; ++j) acc = fmaf(mw[j], pw[min(mst + j, 512)], acc);
-        const float db = 10.f * log10f(fmaxf(acc, 1e-10f));
+        const float db = power_db(acc);
         melbn[((size_t)b * Fc + f) * 64 + lane] = db * bsc + bsh;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -349,14 +353,18 @@ __global__ __launch_bounds__(256, 2) void frontend_rfft_kernel(const float* __re
         float acc = 0.f;
 #pragma unroll
         for (int j = 0; j < MW; ++j) acc = fmaf(mw[j], pw[min(mst + j, 512)], acc);
-        const float db = 10.f * log10f(fmaxf(acc, 1e-10f));
+        const float db = power_db(acc);
         melbn[((size_t)b * Fc + f) * 64 + lane] = db * bsc + bsh;
         wave_sync();
     }
 }
 
 static int g_frontend_full_fft = 0;      // (debug) 1: the full-length transform of rounds 1-2
-void frontend_set_variant(int full_fft) { g_frontend_full_fft = full_fft; }
+int frontend_set_variant(int full_fft) {   // returns the previous value
+    const int prev = g_frontend_full_fft;
+    g_frontend_full_fft = full_fft;
+    return prev;
+}
 
 // mel+bn0 of the first Fc frames of every clip: melbn [B, Fc, 64]; params are the packed fp32 front-end tables
 int frontend(const float* wave, int B, int samples, int Fc, const float* hann, const float* mel_start,
