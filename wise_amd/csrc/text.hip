@@ -62,6 +62,13 @@ __global__ __launch_bounds__(256) void text_embed_kernel(const int* __restrict__
     }
 }
 
+static int launch_text_embed(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int T, int W, int vocab,
+                             int pool, float* x, int* eot, hipStream_t st) {
+    hipLaunchKernelGGL(text_embed_kernel, dim3((B * T + 3) / 4), dim3(256), 0, st, tokens, tok_emb, pos_emb, B, T, W, vocab, pool, x, eot);
+    WISE_LAUNCH_CHECK("text_embed_kernel");
+    return WISE_OK;
+}
+
 struct TextDims {
     int T, V, W, L, H, F, D, act, pool, head, no_causal;
     float eps;
@@ -72,8 +79,9 @@ static int text_dims(const wise_text_config* c, TextDims* d) {
     d->D = c->embed_dim;
     WISE_CHECK_ARG(d->T >= 1 && d->T <= 128, "text: context %d must be in [1,128]", d->T);
     WISE_CHECK_ARG(d->V >= 2, "text: vocab %d", d->V);
-    WISE_CHECK_ARG(d->W > 0 && d->W % 128 == 0 && d->H * 64 == d->W && d->W <= 4096,
-                   "text: width %d must be heads*64 and a multiple of 128", d->W);
+    WISE_CHECK_ARG(d->W > 0 && d->W % 128 == 0 && d->H * 64 == d->W, "text: width %d must be heads*64 and a multiple of 128", d->W);
+    // (the head's LayerNorm of the pooled row, pooled_ln, holds a row of up to 2048 floats in a wave's registers)
+    WISE_CHECK_ARG(d->W <= 2048, "text: width %d is beyond 2048, the widest row the pooled LayerNorm of the head serves", d->W);
     WISE_CHECK_ARG(d->F > 0 && d->F % 128 == 0, "text: mlp %d must be a multiple of 128", d->F);
     WISE_CHECK_ARG(d->D > 0 && d->D % 4 == 0 && d->L >= 0, "text: bad dims");
     WISE_CHECK_ARG(c->act >= 0 && c->act <= 2, "text: act must be 0 (quick_gelu), 1 (gelu) or 2 (gelu_new)");
@@ -173,9 +181,7 @@ extern "C" int wise_text_forward(const wise_text_config* cfg, const uint16_t* wb
     bf16_t* a = reinterpret_cast<bf16_t*>(wsb + ws.a);
     int* eot = reinterpret_cast<int*>(wsb + ws.eot);
 
-    hipLaunchKernelGGL(text_embed_kernel, dim3((ws.M + 3) / 4), dim3(256), 0, st, tokens, pf + o.tok, pf + o.pos, batch,
-                       d.T, d.W, d.V, d.pool, x, eot);
-    WISE_LAUNCH_CHECK("text_embed_kernel");
+    if ((rc = launch_text_embed(tokens, pf + o.tok, pf + o.pos, batch, d.T, d.W, d.V, d.pool, x, eot, st))) return rc;
     const BlockWeights bw = {wb + o.layer0_b, o.per_layer_b, o.in_proj, o.out_proj, o.c_fc, o.c_proj,
                              pf + o.layer0_f, o.per_layer_f, o.ln1_w, o.ln1_b, o.in_b, o.out_b, o.ln2_w, o.ln2_b,
                              o.fc_b, o.proj_b};
@@ -185,10 +191,23 @@ extern "C" int wise_text_forward(const wise_text_config* cfg, const uint16_t* wb
         return pooled_head(x, pf + o.lnf_w, pf + o.lnf_b, wb + o.projT, batch, d.T, d.W, d.D, eot, h,
                            reinterpret_cast<float*>(qkv), out, st, d.eps, d.head == 2 ? pf + o.pj_lw : nullptr);
     // msclap: ln_f on the pooled row -> Projection(W1, GELU, W2, LayerNorm(e1 + e2)) -> L2 normalise
-    if ((rc = pooled_ln(x, pf + o.lnf_w, pf + o.lnf_b, batch, d.T, d.W, eot, h, st))) return rc;
+    if ((rc = pooled_ln(x, pf + o.lnf_w, pf + o.lnf_b, batch, d.T, d.W, eot, h, st, d.eps))) return rc;
     return clap_projection(h, wb + o.projT, wb + o.proj2, pf + o.pj_lw, pf + o.pj_lb, batch, d.W,
                            reinterpret_cast<float*>(qkv), a, out, st);
 }
+
+#ifdef WISE_DEBUG_KNOBS
+// text_embed_kernel alone, through the launch function wise_text_forward calls (tests/test_gpu_tower_kernels.py):
+// x fp32 [B*T, W] = tok_emb[tokens] + pos_emb[t]; eot int32 [B] = the pooled position (pool 0 first argmax, 1 count of ids != 0 less one, 2 T - 1)
+extern "C" int wise_debug_text_embed(const int32_t* tokens, const float* tok_emb, const float* pos_emb, int B, int T, int W,
+                                     int vocab, int pool, float* x, int32_t* eot, void* stream) {
+    WISE_CHECK_ARG(tokens && tok_emb && pos_emb && x && eot, "debug_text_embed: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= (1 << 20) && T >= 1 && T <= 128 && W >= 4 && W % 4 == 0 && W <= 4096 && vocab >= 2 && pool >= 0 && pool <= 2,
+                   "debug_text_embed: B=%d T=%d (1 .. 128) W=%d (a multiple of 4, <= 4096) vocab=%d pool=%d (0 .. 2)", B, T, W, vocab, pool);
+    WISE_CHECK_ARG((((uintptr_t)tok_emb | (uintptr_t)pos_emb | (uintptr_t)x) & 15) == 0, "debug_text_embed: tok_emb, pos_emb, x must be 16-byte aligned");
+    return launch_text_embed(tokens, tok_emb, pos_emb, B, T, W, vocab, pool, x, eot, (hipStream_t)stream);
+}
+#endif
 
 // parity tap: the residual stream x [batch*context, W] after a forward with the same batch
 extern "C" int wise_text_tap_residual(const wise_text_config* cfg, int batch, const void* workspace, float* dst,

@@ -941,6 +941,31 @@ __global__ __launch_bounds__(256) void patchify8_kernel(const TIN* __restrict__ 
     *reinterpret_cast<uint4*>(patches + (size_t)prow * (3 * P * P) + k) = o;
 }
 
+// images [B,3,S,S] (u8 or fp32) -> patches bf16 [B*g*g, Kp]: the 8-pixel form where the shape and the address allow it
+static int launch_patchify(const void* images, int in_kind, int B, int S, int P, int g, int Kp, int arch, bf16_t* patches,
+                           hipStream_t st) {
+    const NormConst nc = norm_const(arch);
+    const int Mpatch = B * g * g;
+    const bool fast_gather = P % 8 == 0 && S % 8 == 0 && Kp == 3 * P * P && ((uintptr_t)images & 15) == 0;
+    if (fast_gather) {
+        const long long total8 = (long long)Mpatch * (Kp / 8);
+        const unsigned blocks = (unsigned)((total8 + 255) / 256);
+        if (in_kind == WISE_VIT_IN_U8)
+            hipLaunchKernelGGL(patchify8_kernel<unsigned char>, dim3(blocks), dim3(256), 0, st,
+                               reinterpret_cast<const unsigned char*>(images), total8, S, P, g, patches, nc);
+        else
+            hipLaunchKernelGGL(patchify8_kernel<float>, dim3(blocks), dim3(256), 0, st,
+                               reinterpret_cast<const float*>(images), total8, S, P, g, patches, nc);
+    } else if (in_kind == WISE_VIT_IN_U8)
+        hipLaunchKernelGGL(patchify_kernel<unsigned char>, dim3(Mpatch), dim3(256), 0, st,
+                           reinterpret_cast<const unsigned char*>(images), B, S, P, g, Kp, patches, nc);
+    else
+        hipLaunchKernelGGL(patchify_kernel<float>, dim3(Mpatch), dim3(256), 0, st,
+                           reinterpret_cast<const float*>(images), B, S, P, g, Kp, patches, nc);
+    WISE_LAUNCH_CHECK("patchify_kernel");
+    return WISE_OK;
+}
+
 // timm towers without a class token and without ln_pre (SigLIP): x[row, :] = patch_out[row, :] + pos[row % T, :]
 // (the patch embedding's bias is folded into pos by the packer).  float4 per thread.
 __global__ __launch_bounds__(256) void embed_pos_kernel(const float* __restrict__ patch_out, const float* __restrict__ pos,
@@ -953,6 +978,13 @@ __global__ __launch_bounds__(256) void embed_pos_kernel(const float* __restrict_
     const float4 a = reinterpret_cast<const float4*>(patch_out)[idx];
     const float4 p = reinterpret_cast<const float4*>(pos)[(size_t)(row % T) * w4 + c];
     reinterpret_cast<float4*>(x)[idx] = make_float4(a.x + p.x, a.y + p.y, a.z + p.z, a.w + p.w);
+}
+
+static int launch_embed_pos(const float* patch_out, const float* pos, int rows, int T, int W, float* x, hipStream_t st) {
+    const long long total4 = (long long)rows * (W >> 2);
+    hipLaunchKernelGGL(embed_pos_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, patch_out, pos, total4, T, W, x);
+    WISE_LAUNCH_CHECK("embed_pos_kernel");
+    return WISE_OK;
 }
 
 // Attention pooling with one latent query (timm AttentionPoolLatent, the 'map' head of the SigLIP towers): per (image,
@@ -1028,6 +1060,13 @@ __global__ __launch_bounds__(64) void map_pool_kernel(const bf16_t* __restrict__
     o[(size_t)b * W + h * 64 + lane] = f32_to_bf16(mine);
 }
 
+// kv bf16 [B*T, 2W], qv fp32 [W] -> o bf16 [B, W]; W / 64 heads, T <= 1024 (vit_dims holds the towers to that)
+static int launch_map_pool(const bf16_t* kv, const float* qv, int B, int T, int W, bf16_t* o, hipStream_t st) {
+    hipLaunchKernelGGL(map_pool_kernel, dim3(B, W / 64), dim3(64), 0, st, kv, qv, T, W, o);
+    WISE_LAUNCH_CHECK("map_pool_kernel");
+    return WISE_OK;
+}
+
 // x[b*T + t, :] = ln_pre( (t == 0 ? cls : patch_out[b*g*g + t-1, :]) + pos[t, :] ), one wave per row
 template <int NV>
 __global__ __launch_bounds__(256) void embed_lnpre_kernel(const float* __restrict__ patch_out,
@@ -1066,6 +1105,21 @@ __global__ __launch_bounds__(256) void embed_lnpre_kernel(const float* __restric
         r.restat(lane, w4, W, eps);
         if (lane == 0) rstd_out[row] = r.rstd;
     }
+}
+
+// rows = B*T rows of width W <= 2048 -> x fp32 [rows, W], or (hcopy) hi at hcopy, lo at hcopy + lo_off and rstd_out [rows]
+static int launch_embed_lnpre(const float* patch_out, const float* cls, const float* pos, const float* w, const float* bb,
+                              int rows, int T, int W, float eps, float* x, bf16_t* hcopy, float* rstd_out, long long lo_off,
+                              hipStream_t st) {
+    if (!with_nv<8>((W / 4 + 63) / 64, [&](auto n) {
+            hipLaunchKernelGGL(embed_lnpre_kernel<decltype(n)::value>, dim3((rows + 3) / 4), dim3(256), 0, st, patch_out, cls, pos,
+                               w, bb, rows, T, W, eps, x, hcopy, rstd_out, lo_off);
+        })) {
+        set_error("vit_forward: width %d too large", W);
+        return WISE_E_UNSUPPORTED;
+    }
+    WISE_LAUNCH_CHECK("embed_lnpre_kernel");
+    return WISE_OK;
 }
 
 // LayerNorm of ONE row per sequence: x[b*T + pos[b], :] -> y[b, :] bf16 (pos == nullptr: row 0, the class
@@ -1370,6 +1424,13 @@ __global__ __launch_bounds__(256) void hilo_rows_kernel(const bf16_t* __restrict
     out[(size_t)r * ostride * W + c] = bf16_to_f32(hi[src]) + bf16_to_f32(hi[src + lo_off]);
 }
 
+static int launch_hilo_rows(const bf16_t* hi, long long lo_off, int n, int stride, int W, float* out, int ostride, hipStream_t st) {
+    const long long total = (long long)n * W;
+    hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, hi, lo_off, n, stride, W, out, ostride);
+    WISE_LAUNCH_CHECK("hilo_rows_kernel");
+    return WISE_OK;
+}
+
 // one contiguous part of the batch on one stream; `wsb` is that part's own workspace region
 static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const VitOffsets& o, const bf16_t* wb,
                             const float* pf, const void* images, int in_kind, int batch, float* out,
@@ -1385,45 +1446,20 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
     int rc;
 
     // 1. patch gather + conv1-as-GEMM (no bias)
-    const NormConst nc = norm_const(d.arch);
-    const bool fast_gather = d.P % 8 == 0 && d.S % 8 == 0 && d.Kp == 3 * d.P * d.P && ((uintptr_t)images & 15) == 0;
-    if (fast_gather) {
-        const long long total8 = (long long)ws.Mpatch * (d.Kp / 8);
-        const unsigned blocks = (unsigned)((total8 + 255) / 256);
-        if (in_kind == WISE_VIT_IN_U8)
-            hipLaunchKernelGGL(patchify8_kernel<unsigned char>, dim3(blocks), dim3(256), 0, st,
-                               reinterpret_cast<const unsigned char*>(images), total8, d.S, d.P, d.g, patches, nc);
-        else
-            hipLaunchKernelGGL(patchify8_kernel<float>, dim3(blocks), dim3(256), 0, st,
-                               reinterpret_cast<const float*>(images), total8, d.S, d.P, d.g, patches, nc);
-    } else if (in_kind == WISE_VIT_IN_U8)
-        hipLaunchKernelGGL(patchify_kernel<unsigned char>, dim3(ws.Mpatch), dim3(256), 0, st,
-                           reinterpret_cast<const unsigned char*>(images), batch, d.S, d.P, d.g, d.Kp, patches, nc);
-    else
-        hipLaunchKernelGGL(patchify_kernel<float>, dim3(ws.Mpatch), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(images), batch, d.S, d.P, d.g, d.Kp, patches, nc);
-    WISE_LAUNCH_CHECK("patchify_kernel");
+    if ((rc = launch_patchify(images, in_kind, batch, d.S, d.P, d.g, d.Kp, d.arch, patches, st))) return rc;
     rc = gemm_bf16(patches, wb + o.conv1, nullptr, ws.Mpp, W, d.Kp, 4, patch_out, st);
     if (rc) return rc;
     // 2. cls + pos + ln_pre -> x   (arch 1: patch rows + pos, nothing else)
     if (d.arch == 1) {
-        const long long total4 = (long long)ws.M * (W >> 2);
-        hipLaunchKernelGGL(embed_pos_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, patch_out, pf + o.pos,
-                           total4, d.T, W, x);
-        WISE_LAUNCH_CHECK("embed_pos_kernel");
+        if ((rc = launch_embed_pos(patch_out, pf + o.pos, ws.M, d.T, W, x, st))) return rc;
     } else {
         // fold mode: the fp32 rows' region holds the residual stream as hi [Mp, W] bf16, then lo [Mp, W] bf16
         bf16_t* fh = d.fold ? reinterpret_cast<bf16_t*>(x) : nullptr;
         float* frs = d.fold ? reinterpret_cast<float*>(wsb + ws.rstd) : nullptr;
         const long long flo = (long long)ws.Mp * W;
-        if (!with_nv<8>((W / 4 + 63) / 64, [&](auto n) {
-                hipLaunchKernelGGL(embed_lnpre_kernel<decltype(n)::value>, dim3((ws.M + 3) / 4), dim3(256), 0, st, patch_out,
-                                   pf + o.cls, pf + o.pos, pf + o.ln_pre_w, pf + o.ln_pre_b, ws.M, d.T, W, 1e-5f, x, fh, frs, flo);
-            })) {
-            set_error("vit_forward: width %d too large", W);
-            return WISE_E_UNSUPPORTED;
-        }
-        WISE_LAUNCH_CHECK("embed_lnpre_kernel");
+        if ((rc = launch_embed_lnpre(patch_out, pf + o.cls, pf + o.pos, pf + o.ln_pre_w, pf + o.ln_pre_b, ws.M, d.T, W, 1e-5f, x,
+                                     fh, frs, flo, st)))
+            return rc;
     }
     // 3. transformer blocks
     const BlockWeights bw = {wb + o.layer0_b, o.per_layer_b, o.in_proj, o.out_proj, o.c_fc, o.c_proj,
@@ -1445,8 +1481,7 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
         if ((rc = layernorm_f32_bf16(x, pf + o.ln_post_w, pf + o.ln_post_b, ws.M, W, 1e-6f, h, st))) return rc;
         if ((rc = gemm_bf16(h, wb + o.h_kv, pf + o.h_kvb, ws.Mp, 2 * W, W, 0, qkv, st))) return rc;
         bf16_t* pooled = h;                                    // [Bp, W] bf16 (h is free once the kv GEMM has read it)
-        hipLaunchKernelGGL(map_pool_kernel, dim3(batch, d.H), dim3(64), 0, st, qkv, pf + o.hq, d.T, W, pooled);
-        WISE_LAUNCH_CHECK("map_pool_kernel");
+        if ((rc = launch_map_pool(qkv, pf + o.hq, batch, d.T, W, pooled, st))) return rc;
         float* y = reinterpret_cast<float*>(qkv);              // [Bp, W] fp32 (keys | values are consumed; x stays for the parity tap)
         bf16_t* yn = a;                                        // [Bp, W] bf16, then the hidden rows [Bp, F] behind it
         bf16_t* hid = a + (size_t)Bp * W;
@@ -1459,14 +1494,11 @@ static int vit_forward_part(const wise_vit_config* cfg, const VitDims& d, const 
     // 4. ln_post(cls) -> bf16 [Bp,W] (aliases h) ; @ proj -> fp32 [Bp,D] (aliases qkv) ; L2 normalise rows
     if (d.fold) {   // the class rows of the hi + lo stream as fp32 [batch, W] (in `a`, free now), then the same head with T = 1
         float* xc = reinterpret_cast<float*>(a);
-        const long long n = (long long)batch * W;
         if (cls_tail)   // the compact rows the last block left
-            hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, tail.hc, (long long)tail.Bp * W,
-                               batch, 1, W, xc, 1);
+            rc = launch_hilo_rows(tail.hc, (long long)tail.Bp * W, batch, 1, W, xc, 1, st);
         else
-            hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const bf16_t*>(x),
-                               (long long)ws.Mp * W, batch, d.T, W, xc, 1);
-        WISE_LAUNCH_CHECK("hilo_rows_kernel");
+            rc = launch_hilo_rows(reinterpret_cast<const bf16_t*>(x), (long long)ws.Mp * W, batch, d.T, W, xc, 1, st);
+        if (rc) return rc;
         return pooled_head(xc, pf + o.ln_post_w, pf + o.ln_post_b, wb + o.projT, batch, 1, W, d.D, nullptr, cls_tail ? tail.hb : h,
                            reinterpret_cast<float*>(qkv), out, st);
     }
@@ -1651,19 +1683,15 @@ extern "C" int wise_vit_tap_residual(const wise_vit_config* cfg, int batch, cons
         part_range(batch, parts, i, &lo, &hi);
         const VitWs ws = vit_ws(d, hi - lo);
         if (d.fold) {
-            const long long n = (long long)ws.M * d.W;
-            hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                               reinterpret_cast<const bf16_t*>(wsb + base + ws.x), (long long)ws.Mp * d.W, ws.M, 1, d.W, dp, 1);
-            WISE_LAUNCH_CHECK("hilo_rows_kernel");
+            if ((rc = launch_hilo_rows(reinterpret_cast<const bf16_t*>(wsb + base + ws.x), (long long)ws.Mp * d.W, ws.M, 1, d.W, dp, 1,
+                                       (hipStream_t)stream)))
+                return rc;
             ClsTail t;
             if (cls_tail_layout(d, ws, hi - lo, const_cast<unsigned char*>(wsb + base), &t)) {
                 // the last block ran for the class rows only: theirs come from the compact stream; every other row holds what
                 // block L-2 left (ln_fold = 1), or that plus the last block's attention half (ln_fold = 2: its attention and
                 // out-projection kernel still runs on every row)
-                const long long nc = (long long)(hi - lo) * d.W;
-                hipLaunchKernelGGL(hilo_rows_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, (hipStream_t)stream, t.hc,
-                                   (long long)t.Bp * d.W, hi - lo, 1, d.W, dp, d.T);
-                WISE_LAUNCH_CHECK("hilo_rows_kernel");
+                if ((rc = launch_hilo_rows(t.hc, (long long)t.Bp * d.W, hi - lo, 1, d.W, dp, d.T, (hipStream_t)stream))) return rc;
             }
         } else {
             hipError_t e = hipMemcpyAsync(dp, wsb + base + ws.x, (size_t)ws.M * d.W * 4, hipMemcpyDeviceToDevice,
@@ -1696,6 +1724,86 @@ extern "C" int wise_debug_attention_cls_bf16(const uint16_t* qkv, int B, int T, 
 extern "C" int wise_debug_ao_set(int flags) { wise::g_ao_dbg = flags & 15; return 0; }
 extern "C" int wise_debug_ao_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(wise::g_ao_stamps), sizeof(unsigned long long) * 96) == hipSuccess ? 0 : -1;
+}
+
+// The image tower's own kernels one by one, through the launch functions vit_forward_part calls (tests/test_gpu_tower_kernels.py).
+// images [B,3,S,S] u8 or fp32 (in_kind as wise_vit_forward takes it) -> patches bf16 [B*g*g, Kp], Kp = 3 P P rounded up to 64 as
+// vit_dims has it; the 8-pixel form runs where vit_forward_part would run it (the rule lives in launch_patchify)
+extern "C" int wise_debug_vit_patchify(const void* images, int in_kind, int B, int S, int P, int Kp, int arch, uint16_t* patches,
+                                       void* stream) {
+    WISE_CHECK_ARG(images && patches, "debug_vit_patchify: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= 4096 && P >= 1 && P <= 64 && S >= P && S <= 1024 && S % P == 0 && (arch == 0 || arch == 1) &&
+                       (in_kind == WISE_VIT_IN_U8 || in_kind == WISE_VIT_IN_F32),
+                   "debug_vit_patchify: B=%d S=%d P=%d (S a multiple of P, P <= 64, S <= 1024) arch=%d in_kind=%d", B, S, P, arch, in_kind);
+    WISE_CHECK_ARG(Kp == (3 * P * P + 63) / 64 * 64, "debug_vit_patchify: Kp=%d is not 3 P P = %d rounded up to 64", Kp, 3 * P * P);
+    WISE_CHECK_ARG((in_kind == WISE_VIT_IN_U8 || ((uintptr_t)images & 3) == 0) && ((uintptr_t)patches & 15) == 0,
+                   "debug_vit_patchify: fp32 images must be 4-byte and patches 16-byte aligned");
+    return wise::launch_patchify(images, in_kind, B, S, P, S / P, Kp, arch, patches, (hipStream_t)stream);
+}
+// x[row, :] = patch_out[row, :] + pos[row % T, :], rows x W fp32
+extern "C" int wise_debug_vit_embed_pos(const float* patch_out, const float* pos, int rows, int T, int W, float* x, void* stream) {
+    WISE_CHECK_ARG(patch_out && pos && x, "debug_vit_embed_pos: null pointer");
+    WISE_CHECK_ARG(rows >= 1 && rows <= (1 << 24) && T >= 1 && W >= 4 && W % 4 == 0 && W <= 4096,
+                   "debug_vit_embed_pos: rows=%d T=%d W=%d (a multiple of 4, <= 4096)", rows, T, W);
+    WISE_CHECK_ARG((((uintptr_t)patch_out | (uintptr_t)pos | (uintptr_t)x) & 15) == 0, "debug_vit_embed_pos: pointers must be 16-byte aligned");
+    return wise::launch_embed_pos(patch_out, pos, rows, T, W, x, (hipStream_t)stream);
+}
+// class row / patch rows + pos -> ln_pre -> x fp32 [rows, W]; or (hcopy != null: the fold form) hi bf16 at hcopy, lo at
+// hcopy + lo_off and the normalised rows' own rstd in rstd_out [rows].  rows = B*T; patch_out has B*(T-1) rows
+extern "C" int wise_debug_vit_embed_lnpre(const float* patch_out, const float* cls, const float* pos, const float* w, const float* b,
+                                          int rows, int T, int W, float eps, float* x, uint16_t* hcopy, float* rstd_out,
+                                          long long lo_off, void* stream) {
+    WISE_CHECK_ARG(patch_out && cls && pos && w && b && (hcopy ? rstd_out != nullptr : x != nullptr), "debug_vit_embed_lnpre: null pointer");
+    WISE_CHECK_ARG(rows >= 1 && rows <= (1 << 24) && T >= 1 && rows % T == 0 && W >= 4 && W % 4 == 0 && W <= 2048 && eps > 0.f,
+                   "debug_vit_embed_lnpre: rows=%d T=%d (rows a multiple of T) W=%d (a multiple of 4, <= 2048) eps=%g", rows, T, W, (double)eps);
+    WISE_CHECK_ARG(!hcopy || (lo_off >= (long long)rows * W && lo_off % 4 == 0),
+                   "debug_vit_embed_lnpre: lo_off=%lld lies inside the hi rows (%lld elements) or is no multiple of 4", lo_off, (long long)rows * W);
+    WISE_CHECK_ARG((((uintptr_t)patch_out | (uintptr_t)cls | (uintptr_t)pos | (uintptr_t)w | (uintptr_t)b | (uintptr_t)x) & 15) == 0 &&
+                       ((uintptr_t)hcopy & 7) == 0, "debug_vit_embed_lnpre: fp32 pointers must be 16-byte, hcopy 8-byte aligned");
+    return wise::launch_embed_lnpre(patch_out, cls, pos, w, b, rows, T, W, eps, x, hcopy, rstd_out, lo_off, (hipStream_t)stream);
+}
+// y[b, :] = LayerNorm(x[b*T + pos[b], :]) bf16 (pos null: row 0) — pooled_ln as every head calls it; pos[b] must lie in [0, T)
+extern "C" int wise_debug_pooled_ln(const float* x, const float* w, const float* b, int B, int T, int W, float eps, const int* pos,
+                                    uint16_t* y, void* stream) {
+    WISE_CHECK_ARG(x && w && b && y, "debug_pooled_ln: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= (1 << 20) && T >= 1 && T <= 4096 && W >= 4 && W % 4 == 0 && W <= 2048 && eps > 0.f,
+                   "debug_pooled_ln: B=%d T=%d W=%d (a multiple of 4, <= 2048) eps=%g", B, T, W, (double)eps);
+    WISE_CHECK_ARG((((uintptr_t)x | (uintptr_t)w | (uintptr_t)b) & 15) == 0 && ((uintptr_t)y & 7) == 0,
+                   "debug_pooled_ln: x, w, b must be 16-byte and y 8-byte aligned");
+    return wise::pooled_ln(x, w, b, B, T, W, pos, y, (hipStream_t)stream, eps);
+}
+// out[r, :] = e[r, :] / ||e[r, :]||
+extern "C" int wise_debug_l2norm_rows(const float* e, int rows, int D, float* out, void* stream) {
+    WISE_CHECK_ARG(e && out, "debug_l2norm_rows: null pointer");
+    WISE_CHECK_ARG(rows >= 1 && rows <= (1 << 24) && D >= 1 && D <= 65536, "debug_l2norm_rows: rows=%d D=%d (1 .. 65536)", rows, D);
+    return wise::l2norm_rows(e, rows, D, out, (hipStream_t)stream);
+}
+// kv bf16 [B*T, 2W] (keys | values), qv fp32 [W] -> o bf16 [B, W]: one latent query per head of 64
+extern "C" int wise_debug_vit_map_pool(const uint16_t* kv, const float* qv, int B, int T, int W, uint16_t* o, void* stream) {
+    WISE_CHECK_ARG(kv && qv && o, "debug_vit_map_pool: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= 65535 && T >= 1 && T <= 1024 && W >= 64 && W % 64 == 0 && W <= 4096,
+                   "debug_vit_map_pool: B=%d T=%d (1 .. 1024) W=%d (heads of 64, <= 4096)", B, T, W);
+    WISE_CHECK_ARG(((uintptr_t)kv & 15) == 0, "debug_vit_map_pool: kv must be 16-byte aligned");
+    return wise::launch_map_pool(kv, qv, B, T, W, o, (hipStream_t)stream);
+}
+// out[r * ostride, :] = hi[r * stride, :] + lo[r * stride, :] (lo = hi + lo_off), n rows of width W
+extern "C" int wise_debug_vit_hilo_rows(const uint16_t* hi, long long lo_off, int n, int stride, int W, float* out, int ostride,
+                                        void* stream) {
+    WISE_CHECK_ARG(hi && out, "debug_vit_hilo_rows: null pointer");
+    WISE_CHECK_ARG(n >= 1 && n <= (1 << 24) && stride >= 1 && ostride >= 1 && W >= 1 && W <= 4096 &&
+                       lo_off >= ((long long)(n - 1) * stride + 1) * W,
+                   "debug_vit_hilo_rows: n=%d stride=%d ostride=%d W=%d (1 .. 4096) lo_off=%lld (behind the hi rows)", n, stride, ostride, W, lo_off);
+    return wise::launch_hilo_rows(hi, lo_off, n, stride, W, out, ostride, (hipStream_t)stream);
+}
+// LayerNorm with the fp32 copy: xo fp32 [rows, W] (may be x) and y bf16 [rows, W] — layernorm_f32_dual of the post-LN towers
+extern "C" int wise_debug_layernorm_dual(const float* x, const float* w, const float* b, int rows, int W, float eps, float* xo,
+                                         uint16_t* y, void* stream) {
+    WISE_CHECK_ARG(x && w && b && xo && y, "debug_layernorm_dual: null pointer");
+    WISE_CHECK_ARG(rows >= 1 && rows <= (1 << 24) && W > 128 && W % 4 == 0 && W <= 4096 && eps > 0.f,
+                   "debug_layernorm_dual: rows=%d W=%d (a multiple of 4 in (128, 4096]) eps=%g", rows, W, (double)eps);
+    WISE_CHECK_ARG((((uintptr_t)x | (uintptr_t)w | (uintptr_t)b | (uintptr_t)xo) & 15) == 0 && ((uintptr_t)y & 7) == 0,
+                   "debug_layernorm_dual: x, w, b, xo must be 16-byte and y 8-byte aligned");
+    return wise::layernorm_f32_dual(x, w, b, rows, W, eps, xo, y, (hipStream_t)stream);
 }
 #endif
 extern "C" int wise_attention_oproj_fold(const uint16_t* qkv, int B, int T, int H, const uint16_t* Wt, const float* bias,

@@ -75,6 +75,20 @@ __global__ __launch_bounds__(256) void xlmr_meanpool_kernel(const float* __restr
     }
 }
 
+static int launch_xlmr_embed(const int* tokens, const float* word, const float* pos, const float* type0, int B, int T, int W,
+                             int vocab, int max_pos, int pad, int pos_abs, float* x, int* lens, hipStream_t st) {
+    hipLaunchKernelGGL(xlmr_embed_kernel, dim3((B * T + 3) / 4), dim3(256), 0, st, tokens, word, pos, type0, B, T, W, vocab, max_pos,
+                       pad, pos_abs, x, lens);
+    WISE_LAUNCH_CHECK("xlmr_embed_kernel");
+    return WISE_OK;
+}
+
+static int launch_xlmr_meanpool(const float* x, const int* lens, int B, int T, int W, int first_only, bf16_t* pooled, hipStream_t st) {
+    hipLaunchKernelGGL(xlmr_meanpool_kernel, dim3(B), dim3(256), 0, st, x, lens, T, W, first_only, pooled);
+    WISE_LAUNCH_CHECK("xlmr_meanpool_kernel");
+    return WISE_OK;
+}
+
 struct XlmrDims {
     int T, V, P, W, L, H, F, Hd, D, pad, pos_abs, pool, head;
     float eps;
@@ -192,9 +206,8 @@ extern "C" int wise_xlmr_forward(const wise_xlmr_config* cfg, const uint16_t* wb
     const int M = ws.M, Mp = ws.Mp, W = d.W;
     const float eps = d.eps;                                  // layer_norm_eps: 1e-5 XLM-RoBERTa, 1e-12 BERT
 
-    hipLaunchKernelGGL(xlmr_embed_kernel, dim3((M + 3) / 4), dim3(256), 0, st, tokens, pf + o.word, pf + o.pos, pf + o.type0,
-                       batch, d.T, W, d.V, d.P, d.pad, d.pos_abs, x, lens);
-    WISE_LAUNCH_CHECK("xlmr_embed_kernel");
+    if ((rc = launch_xlmr_embed(tokens, pf + o.word, pf + o.pos, pf + o.type0, batch, d.T, W, d.V, d.P, d.pad, d.pos_abs, x, lens, st)))
+        return rc;
     if ((rc = layernorm_f32_dual(x, pf + o.eln_w, pf + o.eln_b, M, W, eps, x, h, st))) return rc;
     for (int l = 0; l < d.L; ++l) {
         const bf16_t* lw = wb + o.per_layer_b * l;
@@ -213,8 +226,7 @@ extern "C" int wise_xlmr_forward(const wise_xlmr_config* cfg, const uint16_t* wb
         hipError_t me = hipMemsetAsync(h, 0, (size_t)Bp * W * 2, st);
         if (me != hipSuccess) { set_error("xlmr_forward: hipMemsetAsync: %s", hipGetErrorString(me)); return (int)me; }
     }
-    hipLaunchKernelGGL(xlmr_meanpool_kernel, dim3(batch), dim3(256), 0, st, x, lens, d.T, W, d.pool, h);
-    WISE_LAUNCH_CHECK("xlmr_meanpool_kernel");
+    if ((rc = launch_xlmr_meanpool(x, lens, batch, d.T, W, d.pool, h, st))) return rc;
     float* e = reinterpret_cast<float*>(qkv);
     if (d.head == 1)
         return clap_projection(h, wb + o.proj1, wb + o.proj2, pf + o.head_ln, pf + o.head_ln + d.D, batch, W, e, a, out, st);
@@ -222,6 +234,32 @@ extern "C" int wise_xlmr_forward(const wise_xlmr_config* cfg, const uint16_t* wb
     if ((rc = gemm_bf16_rows(a, wb + o.proj2, nullptr, Bp, batch, d.D, d.Hd, 4, e, st, sk, skb))) return rc;
     return l2norm_rows(e, batch, d.D, out, st);
 }
+
+#ifdef WISE_DEBUG_KNOBS
+// The tower's own two kernels, through the launch functions wise_xlmr_forward calls (tests/test_gpu_tower_kernels.py).
+// x fp32 [B*T, W] = word[tokens] + pos[position] + type0 (position: pos_abs 0 cumsum(mask) * mask + pad, 1 arange(T));
+// lens int32 [B] = the tokens that are not `pad`
+extern "C" int wise_debug_xlmr_embed(const int32_t* tokens, const float* word, const float* pos, const float* type0, int B, int T,
+                                     int W, int vocab, int max_pos, int pad, int pos_abs, float* x, int32_t* lens, void* stream) {
+    WISE_CHECK_ARG(tokens && word && pos && type0 && x && lens, "debug_xlmr_embed: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= (1 << 20) && T >= 1 && T <= 128 && W >= 4 && W % 4 == 0 && W <= 4096 && vocab >= 2 && pad >= 0 &&
+                       pad < vocab && (pos_abs == 0 || pos_abs == 1) && max_pos >= (pos_abs ? T : T + pad + 1),
+                   "debug_xlmr_embed: B=%d T=%d (1 .. 128) W=%d (a multiple of 4, <= 4096) vocab=%d pad=%d pos_abs=%d max_pos=%d", B, T, W,
+                   vocab, pad, pos_abs, max_pos);
+    WISE_CHECK_ARG((((uintptr_t)word | (uintptr_t)pos | (uintptr_t)type0 | (uintptr_t)x) & 15) == 0,
+                   "debug_xlmr_embed: word, pos, type0, x must be 16-byte aligned");
+    return launch_xlmr_embed(tokens, word, pos, type0, B, T, W, vocab, max_pos, pad, pos_abs, x, lens, (hipStream_t)stream);
+}
+// pooled bf16 [B, W] = the mean of the first lens[b] rows of x [B, T, W] (first_only: row 0)
+extern "C" int wise_debug_xlmr_meanpool(const float* x, const int32_t* lens, int B, int T, int W, int first_only, uint16_t* pooled,
+                                        void* stream) {
+    WISE_CHECK_ARG(x && lens && pooled, "debug_xlmr_meanpool: null pointer");
+    WISE_CHECK_ARG(B >= 1 && B <= (1 << 20) && T >= 1 && T <= 128 && W >= 4 && W % 4 == 0 && W <= 4096 && (first_only == 0 || first_only == 1),
+                   "debug_xlmr_meanpool: B=%d T=%d (1 .. 128) W=%d (a multiple of 4, <= 4096) first_only=%d", B, T, W, first_only);
+    WISE_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)pooled & 7) == 0, "debug_xlmr_meanpool: x must be 16-byte, pooled 8-byte aligned");
+    return launch_xlmr_meanpool(x, lens, B, T, W, first_only, pooled, (hipStream_t)stream);
+}
+#endif
 
 // parity tap: the residual stream x [batch*context, W] after a forward with the same batch
 extern "C" int wise_xlmr_tap_residual(const wise_xlmr_config* cfg, int batch, const void* workspace, float* dst, void* stream) {
