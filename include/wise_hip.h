@@ -50,7 +50,8 @@ const char* wise_last_error(void);
  * functions), IndexSQ8bit; and the wise_ivfl2_* entry points (wise_ivfl2_scan, _scan_sel, _scan_local, _range_count / _fill and their
  * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2; and wise_pqflat_topk, wise_pqflat_topk_pos (with
  * wise_pqflat_topk_workspace_bytes) and wise_pqflat_decode, IndexPQ<m>; and the wise_l2sq16_* entry points (wise_l2sq16_topk, _topk_pos,
- * _range_count / _fill, _prepare, _topk_batched and their three workspace functions), IndexSQfp16L2.  The version is 5. */
+ * _range_count / _fill, _prepare, _topk_batched and their three workspace functions), IndexSQfp16L2; and the nine *_group_scores
+ * entry points with wise_group_best, wise_group_topk and wise_group_workspace_bytes, search_grouped.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -1182,6 +1183,55 @@ int wise_attention_dh_bf16(const uint16_t* qkv, int B, int T, int H, int dh, uin
 int wise_attention_lens_bf16(const uint16_t* qkv, int B, int T, int H, const int32_t* lens, uint16_t* o, void* stream);
 /* head dim 64 with the causal mask of the text tower: query t attends keys <= t */
 int wise_attention_causal_bf16(const uint16_t* qkv, int B, int T, int H, uint16_t* o, void* stream);
+
+/* (ABI 5) search_grouped: the k best GROUPS of rows (videos, shots, files), one hit per group.  Not in the reference, which groups
+ * the top `end` <= 1000 rows by media_id AFTER the search (api/routes.py:582-596) and so shows a dozen results when a thousand best
+ * frames come from a dozen files.  Every stored row belongs to one group; over a query's CANDIDATE rows — every row of an exhaustive
+ * index, the rows of the probed lists of an inverted-file index, under a selector only the selected ones — a group's representative
+ * is its candidate row with the best score, ties to the lower row position (the row of the payload; the position in list order),
+ * and the answer is the k groups whose representatives are best, in the order of the representatives' (score, position) keys: the
+ * tie rule of the scans.  Three stages, all on the device, no global atomics, the same bytes on every run:
+ *   1  a *_group_scores call writes, per (query, candidate row), ord[q][row] = the 32-bit ordered image of the key score (the
+ *      score; the negated squared distance for the L2 types): u = the float's bits, u ^ 0x80000000 where u >= 0, ~u where u < 0 — the
+ *      upper half of the scans' 64-bit keys.  The score is, bit for bit, what the type's exact top-k scan gives that (query, row).
+ *      0 = no candidate.  ord [nq][N] uint32.  keep: a selector's bitmap over the positions (wise_sel_bitmap), or null.  The
+ *      arguments before `keep` are those of the type's range count entry point without radius, counts and workspace; the calls
+ *      over inverted lists clear ord first (the rows of the lists a query does not probe read 0), the exhaustive ones write every
+ *      row.  wise_ipsq8_group_scores takes W and q0 of wise_sq_query, as the wise_ivfsq_* entry points do.
+ *   2  wise_group_best: best[q][g] = the maximum over the rows r of group g of (ord[q][r] << 32) | (0xFFFFFFFF - r), 0 for a
+ *      group without a candidate.  group_rows [N] uint32: the row positions sorted by (group, position); group_off [G + 1]: group g
+ *      owns group_rows[group_off[g] .. group_off[g + 1]), group_off[0] = 0, group_off[G] = N, ascending.  best [nq][G] uint64.
+ *   3  wise_group_topk: the k largest keys of each query -> outD / outI / outG [nq][k]: the representative's score (flip != 0: the
+ *      key score negated back into a distance), its external id (ids[row], or id_base + row where ids is null) and its group's
+ *      key group_keys[gid[row]] (gid [N] int32: the group of every row, group_keys [G] int64).  Slots no group fills hold
+ *      (-3.4028235e38, -1, -1); flip != 0: (+3.4028235e38, -1, -1).  workspace: the merge parts.
+ * Limits: N < 2^32 - 1, 0 <= G <= min(N, 2^31 - 1) (gid is int32), 1 <= nq <= 65535, 1 <= k <= 2048, d as each type's scan takes it; anything else returns
+ * WISE_E_INVALID and leaves the outputs untouched.  wise_group_workspace_bytes: ord, best and the merge parts of nq queries in
+ * one allocation, each region aligned to 256 bytes, in this order — 4 N + 8 G bytes a query plus the parts —; 0 for an
+ * unsupported shape.  wise_group_topk itself needs only the last region. */
+size_t wise_group_workspace_bytes(int64_t N, int64_t G, int nq, int k);
+int wise_ip_group_scores_f32(const float* X, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord, void* stream);
+int wise_ipsq16_group_scores(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                             void* stream);
+int wise_ipsq8_group_scores(const uint8_t* codes, int64_t N, int d, const float* W, const float* q0, int nq, const uint32_t* keep,
+                            uint32_t* ord, void* stream);
+int wise_l2_group_scores_f32(const float* X, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord, void* stream);
+int wise_l2sq16_group_scores(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                             void* stream);
+int wise_ivf_group_scores_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                              const int64_t* probes, int nprobe, const uint32_t* keep, uint32_t* ord, void* stream);
+int wise_ivfsq_group_scores(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W, const float* q0,
+                            int nq, const int64_t* probes, const float* bias, int nprobe, const uint32_t* keep, uint32_t* ord,
+                            void* stream);
+int wise_ivfsq16_group_scores(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                              const int64_t* probes, const float* bias, int nprobe, const uint32_t* keep, uint32_t* ord, void* stream);
+int wise_ivfl2_group_scores(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                            const int64_t* probes, int nprobe, const uint32_t* keep, uint32_t* ord, void* stream);
+int wise_group_best(const uint32_t* ord, int64_t N, int nq, const int64_t* group_off, const uint32_t* group_rows, int64_t G,
+                    uint64_t* best, void* stream);
+int wise_group_topk(const uint64_t* best, int64_t G, int nq, int k, const int32_t* gid, int64_t N, const int64_t* group_keys,
+                    const int64_t* ids, int64_t id_base, int flip, float* outD, int64_t* outI, int64_t* outG, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

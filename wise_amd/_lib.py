@@ -206,6 +206,18 @@ SIGNATURES = {
     "wise_ivfl2_range_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "wise_ivfl2_range_count": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "wise_ivfl2_range_fill": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_group_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
+    "wise_ip_group_scores_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_ipsq16_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_ipsq8_group_scores": (_i, [_vp, _i64, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "wise_l2_group_scores_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_l2sq16_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_ivf_group_scores_f32": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_ivfsq_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "wise_ivfsq16_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "wise_ivfl2_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "wise_group_best": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
+    "wise_group_topk": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "wise_l2_half_norms": (_i, [_vp, _i64, _i, _vp, _vp]),
     "wise_ivf_l2_coarse": (_i, [_vp, _vp, _i, _i, _vp]),
     "wise_ivf_list_means": (_i, [_vp, _vp, _i, _i, _vp, _vp]),

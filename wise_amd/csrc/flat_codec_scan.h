@@ -251,6 +251,61 @@ __global__ __launch_bounds__(256) void flat_range_count_kernel(const unsigned ch
     }
 }
 
+// ---- search_grouped, stage 1 (group_topk.hip holds stages 2 and 3): flat_range_count_kernel with the hit mark replaced by one store.
+// Block (x, y) owns segment x for the queries y NQ .. y NQ + NQ - 1 and leaves, per query, ord[q][r] = f32_order(key score of row r)
+// — the upper half of the key the exact scan makes of that (query, row) — for every row r of the segment; a row cleared in keep
+// reads 0, the keys' empty value.  The images are gathered in LDS and leave as whole runs of 4-byte words: every row of the
+// segment is written, selected or not, so nothing has to be cleared first.
+template <class M, int NQ>
+__global__ __launch_bounds__(256) void flat_group_scores_kernel(const unsigned char* __restrict__ rows, long long N, int d,
+                                                                const float* __restrict__ Q, const float* __restrict__ base, int nq,
+                                                                const unsigned* __restrict__ keep, unsigned* __restrict__ ord) {
+    __shared__ unsigned sc[NQ][RANGE_ROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q0 = blockIdx.y * NQ;
+    LanePlace L;
+    L.init(d, lane);
+    float4 w[NQ][4];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) M::Codec::weights(Q + (size_t)(q0 + q < nq ? q0 + q : nq - 1) * d, d, L.c, w[q]);
+    float qb[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) qb[q] = M::base(base, q0 + q < nq ? q0 + q : nq - 1);
+    for (int i = threadIdx.x; i < NQ * RANGE_ROWS; i += 256) sc[i / RANGE_ROWS][i % RANGE_ROWS] = 0u;
+    __syncthreads();
+    const long long clo = (long long)blockIdx.x * RANGE_ROWS;
+    const long long chi = clo + RANGE_ROWS < N ? clo + RANGE_ROWS : N;
+    const int ngroups = (int)((chi - clo + L.RPL - 1) / L.RPL);
+    for (int g = wave * SQ_T; g < ngroups; g += 4 * SQ_T) {                         // wave-uniform
+        long long r[SQ_T];
+        bool live[SQ_T];
+        bool any = false;
+#pragma unroll
+        for (int t = 0; t < SQ_T; ++t) {
+            r[t] = clo + (long long)(g + t) * L.RPL + L.sub;
+            live[t] = L.active && r[t] < chi;
+            if (r[t] >= chi) r[t] = chi - 1;                                        // stay inside the segment; masked by live
+            if (keep) live[t] = live[t] && ((keep[r[t] >> 5] >> (r[t] & 31)) & 1u) != 0;
+            any = any || live[t];
+        }
+        if (keep && __ballot(any) == 0) continue;
+        float s[NQ][SQ_T];
+        sq_score_loads_nq<typename M::Codec, NQ>(rows, d, L.C, L.c, r, w, s);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q)
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t)
+                if (live[t] && L.c == 0) sc[q][(int)(r[t] - clo)] = f32_order(M::key_score(M::score(s[q][t], qb[q])));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (q0 + q >= nq) break;
+        unsigned* dst = ord + (size_t)(q0 + q) * (size_t)N + (size_t)clo;
+        for (int i = threadIdx.x; i < (int)(chi - clo); i += 256) dst[i] = sc[q][i];
+    }
+}
+
 // fill: grid (ns, nq); the hits of one segment, in ascending position, behind lims[q] + the segment's offset
 template <class M>
 __global__ __launch_bounds__(256) void flat_range_fill_kernel(const unsigned char* __restrict__ rows, long long N, int d,
@@ -764,6 +819,31 @@ static int range_fill(const char* what, const void* rows, int64_t N, int d, cons
                        (long long)id_base, hit, wstride, seg, ns, reinterpret_cast<const long long*>(lims), outD,
                        reinterpret_cast<long long*>(outI));
     WISE_LAUNCH_CHECK("flat_range_fill_kernel");
+    return WISE_OK;
+}
+
+// the *_group_scores entry points: ord [nq][N] receives every row's ordered key score, 0 for the rows keep clears
+template <class M>
+static int group_scores(const char* what, const void* rows, int64_t N, int d, const float* Q, const float* base, int nq, const uint32_t* keep,
+                        uint32_t* ord, void* stream) {
+    WISE_CHECK_ARG(shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
+    WISE_CHECK_ARG(range_shape_ok(N, d, nq), "%s: N=%lld nq=%d out of range (nq <= 65535)", what, (long long)N, nq);
+    WISE_CHECK_ARG(Q && (rows || N == 0) && (ord || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)rows & 15) == 0 && ((uintptr_t)Q & 15) == 0, "%s: rows and Q must be 16-byte aligned", what);
+    const long long ns = range_flat_segments(N);
+    if (ns == 0) return WISE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* rb = reinterpret_cast<const unsigned char*>(rows);
+    const int nqp = nq >= 4 ? 4 : nq >= 2 ? 2 : 1;
+    const dim3 grid((unsigned)ns, (unsigned)((nq + nqp - 1) / nqp));
+    ProfScope prof(PROF_SCAN, (double)N * (double)M::Codec::row_bytes(d) * grid.y, st);
+    if (nqp == 4)
+        hipLaunchKernelGGL((flat_group_scores_kernel<M, 4>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, keep, ord);
+    else if (nqp == 2)
+        hipLaunchKernelGGL((flat_group_scores_kernel<M, 2>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, keep, ord);
+    else
+        hipLaunchKernelGGL((flat_group_scores_kernel<M, 1>), grid, dim3(256), 0, st, rb, (long long)N, d, Q, base, nq, keep, ord);
+    WISE_LAUNCH_CHECK("flat_group_scores_kernel");
     return WISE_OK;
 }
 

@@ -97,6 +97,69 @@ __global__ __launch_bounds__(256) void ip_range_count_kernel(const f32x4* __rest
     }
 }
 
+// ---- search_grouped, stage 1 (group_topk.hip holds stages 2 and 3): the count kernels with the hit mark replaced by one store.
+// range_mark_chunk with sc[q][row - clo] = f32_order(score) in place of the mark — the upper half of the key ip_scan_kernel makes
+// of that (query, row).  sc is cleared by the caller: a row cleared in keep reads 0, the keys' empty value.
+template <int NV, int NQ>
+__device__ __forceinline__ void group_score_chunk(const f32x4* __restrict__ X, int d4, const float4 (&qv)[NQ][NV], long long clo,
+                                                  long long chi, const unsigned* __restrict__ keep, unsigned (*sc)[RANGE_ROWS]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int myr = reduced_row<RANGE_R>(lane);
+    const bool owner = (lane & 15) == 0;
+    const int ngroups = (int)((chi - clo + RANGE_R - 1) / RANGE_R);
+    for (int g = wave; g < ngroups; g += 4) {
+        const long long row0 = clo + (long long)g * RANGE_R;
+        const long long mine = row0 + myr;
+        bool chosen = mine < chi;
+        if (keep) {
+            chosen = chosen && ((keep[mine >> 5] >> (mine & 31)) & 1u) != 0;
+            if (__ballot(chosen) == 0) continue;
+        }
+        long long row[RANGE_R];
+#pragma unroll
+        for (int r = 0; r < RANGE_R; ++r) row[r] = row0 + r < chi ? row0 + r : chi - 1;   // stay in bounds; masked by chosen
+        f32x4 x[RANGE_R][NV];
+        range_load_rows<NV>(X, d4, row, lane, x);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            float a[RANGE_R];
+            row_partials<NV, RANGE_R>(x, qv[q], a);
+            const float s = rows_reduce<RANGE_R>(a, lane);
+            if (owner && chosen) sc[q][(int)(mine - clo)] = f32_order(s);
+        }
+    }
+}
+
+// the images of the rows [clo, chi) leave LDS as one run of 4-byte words per query: every row of the chunk is written
+template <int NQ>
+__device__ __forceinline__ void group_publish(const unsigned (*sc)[RANGE_ROWS], unsigned* __restrict__ ord, long long N, int q0, int nq,
+                                              long long clo, long long chi) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (q0 + q >= nq) break;
+        unsigned* dst = ord + (size_t)(q0 + q) * (size_t)N + (size_t)clo;
+        for (int i = threadIdx.x; i < (int)(chi - clo); i += 256) dst[i] = sc[q][i];
+    }
+}
+
+// flat: block (x, y) owns segment x = rows [x RANGE_ROWS, ...) for the queries y NQ .. y NQ + NQ - 1, as ip_range_count_kernel
+template <int NV, int NQ>
+__global__ __launch_bounds__(256) void ip_group_scores_kernel(const f32x4* __restrict__ X, long long N, int d4, const float* __restrict__ Q,
+                                                              int nq, const unsigned* __restrict__ keep, unsigned* __restrict__ ord) {
+    __shared__ unsigned sc[NQ][RANGE_ROWS];
+    const int lane = threadIdx.x & 63;
+    const int q0 = blockIdx.y * NQ;
+    float4 qv[NQ][NV];
+    range_load_queries<NV, NQ>(Q, d4, q0, nq, lane, qv);
+    for (int i = threadIdx.x; i < NQ * RANGE_ROWS; i += 256) sc[i / RANGE_ROWS][i % RANGE_ROWS] = 0u;
+    __syncthreads();
+    const long long clo = (long long)blockIdx.x * RANGE_ROWS;
+    const long long chi = clo + RANGE_ROWS < N ? clo + RANGE_ROWS : N;
+    group_score_chunk<NV, NQ>(X, d4, qv, clo, chi, keep, sc);
+    __syncthreads();
+    group_publish<NQ>(sc, ord, N, q0, nq, clo, chi);
+}
+
 struct RangeLists {
     const long long* probes;    // [nq][nprobe], < 0 or >= nlist: nothing to scan
     const long long* list_off;  // [nlist + 1]
@@ -128,6 +191,33 @@ __global__ __launch_bounds__(256) void ivf_range_count_kernel(const f32x4* __res
         if (wave == 0) total += range_publish(hb[0], dst, (int)((chi - clo + 31) >> 5), lane);
     }
     if (threadIdx.x == 0) seg[(size_t)qi * (ls.nprobe + 1) + pi] = total;
+}
+
+// inverted lists: block b owns probe b % nprobe of query b / nprobe, as ivf_range_count_kernel.  Probed lists are distinct, so
+// every (query, row) is stored at most once; the rows of the lists a query does not probe are not written (the entry point
+// clears ord first)
+template <int NV>
+__global__ __launch_bounds__(256) void ivf_group_scores_kernel(const f32x4* __restrict__ X, long long N, int d4, const float* __restrict__ Q,
+                                                               const unsigned* __restrict__ keep, RangeLists ls, unsigned* __restrict__ ord) {
+    __shared__ unsigned sc[1][RANGE_ROWS];
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x / ls.nprobe, pi = blockIdx.x - qi * ls.nprobe;
+    const long long l = ls.probes[(size_t)qi * ls.nprobe + pi];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < ls.nlist) { lo = ls.list_off[l]; hi = ls.list_off[l + 1]; }   // block-uniform
+    if (lo < 0) lo = 0;
+    if (hi > N) hi = N;                                                             // never past ord's row, whatever list_off holds
+    float4 qv[1][NV];
+    range_load_queries<NV, 1>(Q, d4, qi, qi + 1, lane, qv);
+    for (long long clo = lo; clo < hi; clo += RANGE_ROWS) {
+        const long long chi = clo + RANGE_ROWS < hi ? clo + RANGE_ROWS : hi;
+        for (int i = threadIdx.x; i < RANGE_ROWS; i += 256) sc[0][i] = 0u;
+        __syncthreads();
+        group_score_chunk<NV, 1>(X, d4, qv, clo, chi, keep, sc);
+        __syncthreads();
+        group_publish<1>(sc, ord, N, qi, qi + 1, clo, chi);
+        __syncthreads();
+    }
 }
 
 // fill, both forms: the hits of one segment, in ascending position, behind lims[q] + the segment's offset.
@@ -354,5 +444,66 @@ extern "C" int wise_ivf_range_fill_f32(const float* X, int64_t N, int d, const i
     RANGE_NV_SWITCH(d, CALL)
 #undef CALL
     WISE_LAUNCH_CHECK("range_fill_kernel");
+    return WISE_OK;
+}
+
+// ---- search_grouped, stage 1 over the fp32 rows: ord [nq][N] receives f32_order(score) of every candidate (query, row)
+template <int NV>
+static void launch_ip_group_scores(int nqp, const float* X, long long N, int d, const float* Q, int nq, const unsigned* keep, unsigned* ord,
+                                   long long ns, hipStream_t st) {
+    const f32x4* X4 = reinterpret_cast<const f32x4*>(X);
+    const dim3 grid((unsigned)ns, (unsigned)((nq + nqp - 1) / nqp));
+    if constexpr (NV * 4 <= 8) {
+        if (nqp == 4) { hipLaunchKernelGGL((ip_group_scores_kernel<NV, 4>), grid, dim3(256), 0, st, X4, N, d / 4, Q, nq, keep, ord); return; }
+    }
+    if constexpr (NV * 2 <= 8) {
+        if (nqp == 2) { hipLaunchKernelGGL((ip_group_scores_kernel<NV, 2>), grid, dim3(256), 0, st, X4, N, d / 4, Q, nq, keep, ord); return; }
+    }
+    hipLaunchKernelGGL((ip_group_scores_kernel<NV, 1>), grid, dim3(256), 0, st, X4, N, d / 4, Q, nq, keep, ord);
+}
+
+static int group_common_args(const char* what, int64_t N, int d, int nq, const void* X, const void* Q, const void* ord) {
+    WISE_CHECK_ARG(d >= 4 && d <= 2048 && d % 4 == 0, "%s: d=%d must be a multiple of 4 in [4,2048]", what, d);
+    WISE_CHECK_ARG(nq >= 1 && nq <= 65535, "%s: nq=%d out of [1,65535]", what, nq);
+    WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll, "%s: N=%lld out of range", what, (long long)N);
+    WISE_CHECK_ARG(Q && (X || N == 0) && (ord || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)X & 15) == 0 && ((uintptr_t)Q & 15) == 0, "%s: X and Q must be 16-byte aligned", what);
+    return WISE_OK;
+}
+
+// the exact fp32 routine of wise_ip_topk_f32 over every row; a row cleared in keep reads 0.  Every row is written: nothing is cleared
+extern "C" int wise_ip_group_scores_f32(const float* X, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                                        void* stream) {
+    if (int rc = group_common_args("ip_group_scores", N, d, nq, X, Q, ord)) return rc;
+    const long long ns = range_flat_segments(N);
+    if (ns == 0) return WISE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int nqp = range_queries_per_pass(d, nq);
+    ProfScope prof(PROF_SCAN, (double)N * d * 4.0 * ((nq + nqp - 1) / nqp), st);
+#define CALL(NV) launch_ip_group_scores<NV>(nqp, X, N, d, Q, nq, keep, ord, ns, st)
+    RANGE_NV_SWITCH(d, CALL)
+#undef CALL
+    WISE_LAUNCH_CHECK("ip_group_scores_kernel");
+    return WISE_OK;
+}
+
+// the rows of the probed lists (wise_ivf_scan_f32's candidates and scores); every other row of ord reads 0: ord is cleared first
+extern "C" int wise_ivf_group_scores_f32(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                                         const int64_t* probes, int nprobe, const uint32_t* keep, uint32_t* ord, void* stream) {
+    if (int rc = group_common_args("ivf_group_scores", N, d, nq, X, Q, ord)) return rc;
+    WISE_CHECK_ARG(ivf_range_shape_ok(N, nlist, nq, nprobe), "ivf_group_scores: nq=%d nprobe=%d nlist=%d out of range (nq <= 65535, nprobe <= 2048)",
+                   nq, nprobe, nlist);
+    WISE_CHECK_ARG(list_off && probes, "ivf_group_scores: null pointer");
+    if (N == 0) return WISE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(ord, 0, (size_t)nq * (size_t)N * sizeof(uint32_t), st);
+    if (e != hipSuccess) { set_error("ivf_group_scores: memset: %s", hipGetErrorString(e)); return (int)e; }
+    const RangeLists ls{reinterpret_cast<const long long*>(probes), reinterpret_cast<const long long*>(list_off), nprobe, nlist};
+#define CALL(NV)                                                                                                                   \
+    hipLaunchKernelGGL((ivf_group_scores_kernel<NV>), dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st,                  \
+                       reinterpret_cast<const f32x4*>(X), (long long)N, d / 4, Q, keep, ls, ord)
+    RANGE_NV_SWITCH(d, CALL)
+#undef CALL
+    WISE_LAUNCH_CHECK("ivf_group_scores_kernel");
     return WISE_OK;
 }

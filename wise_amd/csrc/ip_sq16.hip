@@ -153,6 +153,12 @@ extern "C" int wise_ipsq16_range_fill(const uint16_t* rows, int64_t N, int d, co
                                   workspace_bytes, stream);
 }
 
+// search_grouped, stage 1: ord [nq][N] = the ordered key score of every (query, row), 0 for the rows keep clears
+extern "C" int wise_ipsq16_group_scores(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                                        void* stream) {
+    return group_scores<MetricIP16>("ipsq16_group_scores", rows, N, d, Q, nullptr, nq, keep, ord, stream);
+}
+
 extern "C" int wise_ipsq16_reconstruct(const uint16_t* rows, int64_t N, int d, const int64_t* ids, int64_t id_base, const int64_t* query_ids,
                                        int n, float* out, void* stream) {
     WISE_CHECK_ARG(shape_ok(d), "ipsq16_reconstruct: d=%d unsupported (d %% 16 == 0 in [16, 1024])", d);

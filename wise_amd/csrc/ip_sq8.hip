@@ -287,6 +287,14 @@ extern "C" int wise_ipsq8_range_fill(const uint8_t* codes, const float* trained,
                                  workspace_bytes - head, stream);
 }
 
+// search_grouped, stage 1: ord [nq][N] = the ordered image of q0 + s_0 of every (query, row), 0 for the rows keep clears.  W and q0
+// are wise_sq_query's for the queries, as the wise_ivfsq_* entry points take them: no workspace
+extern "C" int wise_ipsq8_group_scores(const uint8_t* codes, int64_t N, int d, const float* W, const float* q0, int nq, const uint32_t* keep,
+                                       uint32_t* ord, void* stream) {
+    WISE_CHECK_ARG(q0, "ipsq8_group_scores: null pointer (q0)");
+    return group_scores<MetricIP8>("ipsq8_group_scores", codes, N, d, W, q0, nq, keep, ord, stream);
+}
+
 extern "C" int wise_ipsq8_reconstruct(const uint8_t* codes, const float* trained, int64_t N, int d, const int64_t* ids, int64_t id_base,
                                       const int64_t* query_ids, int n, float* out, void* stream) {
     WISE_CHECK_ARG(shape_ok(d), "ipsq8_reconstruct: d=%d unsupported (d %% 16 == 0 in [16, 1024])", d);

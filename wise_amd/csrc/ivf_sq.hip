@@ -385,6 +385,59 @@ __global__ __launch_bounds__(256) void sq_range_count_kernel(const unsigned char
     if (threadIdx.x == 0) seg[(size_t)qi * (nprobe + 1) + pi] = total;
 }
 
+// ---- search_grouped, stage 1 (group_topk.hip holds stages 2 and 3): sq_range_count_kernel with the hit mark replaced by one store.
+// ord[q][r] = f32_order(Sense::key_score(value)) — the upper half of the key sq_scan_list makes of that (query, row) — for every row
+// r of the probed lists; a row cleared in keep reads 0, the keys' empty value.  A chunk's images are gathered in LDS and leave as
+// one run of 4-byte words.  Probed lists are distinct, so every (query, row) is stored at most once; the rows of the lists a query
+// does not probe are not written (the entry point clears ord first).
+template <class Codec, class Sense = SenseIP>
+__global__ __launch_bounds__(256) void sq_group_scores_kernel(const unsigned char* __restrict__ codes, long long N,
+                                                              const long long* __restrict__ list_off, int nlist, const float* __restrict__ W,
+                                                              const float* __restrict__ q0, const long long* __restrict__ probes,
+                                                              const float* __restrict__ bias, int nprobe, int d,
+                                                              const unsigned* __restrict__ keep, unsigned* __restrict__ ord) {
+    __shared__ unsigned sc[RANGE_ROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int qi = blockIdx.x / nprobe, pi = blockIdx.x - qi * nprobe;
+    const long long l = probes[(size_t)qi * nprobe + pi];
+    long long lo = 0, hi = 0;
+    if (l >= 0 && l < nlist) { lo = list_off[l]; hi = list_off[l + 1]; }            // block-uniform
+    if (lo < 0) lo = 0;
+    if (hi > N) hi = N;                                                             // never past ord's row, whatever list_off holds
+    const float base = Sense::template base<Codec>(bias, (size_t)qi * nprobe + pi, q0, qi);
+    SqLane<Codec> L;
+    L.init(W + (size_t)qi * d, d, lane);
+    unsigned* dst = ord + (size_t)qi * (size_t)N;
+    for (long long clo = lo; clo < hi; clo += RANGE_ROWS) {
+        const long long chi = clo + RANGE_ROWS < hi ? clo + RANGE_ROWS : hi;
+        for (int i = threadIdx.x; i < RANGE_ROWS; i += 256) sc[i] = 0u;
+        __syncthreads();
+        const int ngroups = (int)((chi - clo + L.RPL - 1) / L.RPL);
+        for (int g = wave * SQ_T; g < ngroups; g += 4 * SQ_T) {                     // wave-uniform
+            long long r[SQ_T];
+            bool live[SQ_T];
+            bool any = false;
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t) {
+                r[t] = clo + (long long)(g + t) * L.RPL + L.sub;
+                live[t] = L.active && r[t] < chi;
+                if (r[t] >= chi) r[t] = chi - 1;                                    // stay inside the list; masked by live
+                if (keep) live[t] = live[t] && ((keep[r[t] >> 5] >> (r[t] & 31)) & 1u) != 0;
+                any = any || live[t];
+            }
+            if (keep && __ballot(any) == 0) continue;
+            float s[SQ_T];
+            sq_score_loads<Codec>(codes, d, L.C, L.c, r, L.w, s);
+#pragma unroll
+            for (int t = 0; t < SQ_T; ++t)
+                if (live[t] && L.c == 0) sc[(int)(r[t] - clo)] = f32_order(Sense::key_score(Sense::value(base, s[t])));
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < (int)(chi - clo); i += 256) dst[clo + i] = sc[i];
+        __syncthreads();
+    }
+}
+
 template <class Codec, class Sense = SenseIP>
 __global__ __launch_bounds__(256) void sq_range_fill_kernel(const unsigned char* __restrict__ codes, const long long* __restrict__ list_off,
                                                             int nlist, const long long* __restrict__ ids, const float* __restrict__ W,
@@ -742,6 +795,42 @@ extern "C" int wise_ivfsq16_range_fill(const uint16_t* halves, int64_t N, int d,
                                        radius, lims, outD, outI, workspace, workspace_bytes, stream);
 }
 
+// search_grouped, stage 1 over the probed lists: ord [nq][N] is cleared, then every candidate (query, row) receives its ordered key score
+template <class Codec, class Sense = SenseIP>
+static int sq_group_scores_impl(const char* what, const void* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                                const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, const uint32_t* keep,
+                                uint32_t* ord, void* stream) {
+    constexpr bool has_q0 = Codec::PIECES == 1, l2 = Sense::FLIP;
+    WISE_CHECK_ARG(sq_shape_ok(d), "%s: d=%d unsupported (d %% 16 == 0 in [16, 1024])", what, d);
+    WISE_CHECK_ARG(sq_range_shape_ok(N, nlist, nq, nprobe), "%s: N=%lld nlist=%d nq=%d nprobe=%d unsupported (nq <= 65535, nprobe <= 2048)",
+                   what, (long long)N, nlist, nq, nprobe);
+    WISE_CHECK_ARG(W && (q0 || !has_q0) && probes && (bias || l2) && list_off && (codes || N == 0) && (ord || N == 0), "%s: null pointer", what);
+    WISE_CHECK_ARG(((uintptr_t)codes & 15) == 0 && ((uintptr_t)W & 15) == 0, "%s: %s must be 16-byte aligned", what,
+                   l2 ? "X and Q" : "codes and W");
+    if (N == 0) return WISE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(ord, 0, (size_t)nq * (size_t)N * sizeof(uint32_t), st);
+    if (e != hipSuccess) { set_error("%s: memset: %s", what, hipGetErrorString(e)); return (int)e; }
+    hipLaunchKernelGGL((sq_group_scores_kernel<Codec, Sense>), dim3((unsigned)((long long)nq * nprobe)), dim3(256), 0, st,
+                       reinterpret_cast<const unsigned char*>(codes), (long long)N, (const long long*)list_off, nlist, W, q0,
+                       (const long long*)probes, bias, nprobe, d, keep, ord);
+    WISE_LAUNCH_CHECK("sq_group_scores_kernel");
+    return WISE_OK;
+}
+
+extern "C" int wise_ivfsq_group_scores(const uint8_t* codes, int64_t N, int d, const int64_t* list_off, int nlist, const float* W,
+                                       const float* q0, int nq, const int64_t* probes, const float* bias, int nprobe, const uint32_t* keep,
+                                       uint32_t* ord, void* stream) {
+    return sq_group_scores_impl<Codec8>("ivfsq_group_scores", codes, N, d, list_off, nlist, W, q0, nq, probes, bias, nprobe, keep, ord, stream);
+}
+
+extern "C" int wise_ivfsq16_group_scores(const uint16_t* halves, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                                         const int64_t* probes, const float* bias, int nprobe, const uint32_t* keep, uint32_t* ord,
+                                         void* stream) {
+    return sq_group_scores_impl<Codec16>("ivfsq16_group_scores", halves, N, d, list_off, nlist, Q, nullptr, nq, probes, bias, nprobe, keep, ord,
+                                         stream);
+}
+
 extern "C" int wise_sq16_encode(const float* resid, int64_t n, int d, uint16_t* halves, void* stream) {
     SQ_CHECK_SHAPE("sq16_encode");
     WISE_CHECK_ARG(n >= 0 && n < (1ll << 31) && (n == 0 || (resid && halves)), "sq16_encode: bad argument");
@@ -811,4 +900,10 @@ extern "C" int wise_ivfl2_range_fill(const float* X, int64_t N, int d, const int
                                      float* outD, int64_t* outI, void* workspace, size_t workspace_bytes, void* stream) {
     return sq_range_fill_impl<CodecL2, SenseL2>("ivfl2_range_fill", X, N, d, list_off, nlist, ids, Q, nullptr, nq, probes, nullptr, nprobe,
                                                 radius, lims, outD, outI, workspace, workspace_bytes, stream);
+}
+
+extern "C" int wise_ivfl2_group_scores(const float* X, int64_t N, int d, const int64_t* list_off, int nlist, const float* Q, int nq,
+                                       const int64_t* probes, int nprobe, const uint32_t* keep, uint32_t* ord, void* stream) {
+    return sq_group_scores_impl<CodecL2, SenseL2>("ivfl2_group_scores", X, N, d, list_off, nlist, Q, nullptr, nq, probes, nullptr, nprobe, keep,
+                                                  ord, stream);
 }

@@ -124,6 +124,12 @@ extern "C" int wise_l2sq16_range_fill(const uint16_t* rows, int64_t N, int d, co
                                     workspace_bytes, stream);
 }
 
+// search_grouped, stage 1: ord [nq][N] = the ordered image of -dist of every (query, row), 0 for the rows keep clears
+extern "C" int wise_l2sq16_group_scores(const uint16_t* rows, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                                        void* stream) {
+    return group_scores<MetricL2SQ16>("l2sq16_group_scores", rows, N, d, Q, nullptr, nq, keep, ord, stream);
+}
+
 extern "C" int wise_l2sq16_prepare(const uint16_t* rows, int64_t N, int d, float* half, float* norms, void* stream) {
     WISE_CHECK_ARG(shape_ok(d), "l2sq16_prepare: d=%d unsupported (d %% 16 == 0 in [16, 1024])", d);
     WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && norms && ((rows && half) || N == 0), "l2sq16_prepare: bad argument");

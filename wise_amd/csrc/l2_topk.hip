@@ -121,6 +121,12 @@ extern "C" int wise_l2_range_fill_f32(const float* X, int64_t N, int d, const fl
                                 stream);
 }
 
+// search_grouped, stage 1: ord [nq][N] = the ordered image of -dist of every (query, row), 0 for the rows keep clears
+extern "C" int wise_l2_group_scores_f32(const float* X, int64_t N, int d, const float* Q, int nq, const uint32_t* keep, uint32_t* ord,
+                                        void* stream) {
+    return group_scores<MetricL2>("l2_group_scores_f32", X, N, d, Q, nullptr, nq, keep, ord, stream);
+}
+
 extern "C" int wise_l2_prepare(const float* X, int64_t N, int d, uint16_t* Xb, float* half, float* norms, void* stream) {
     WISE_CHECK_ARG(shape_ok(d), "l2_prepare: d=%d unsupported (d %% 16 == 0 in [16, 1024])", d);
     WISE_CHECK_ARG(N >= 0 && N < 0xFFFFFFFFll && norms && ((X && Xb && half) || N == 0), "l2_prepare: bad argument");

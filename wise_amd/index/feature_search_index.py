@@ -853,6 +853,35 @@ class FeatureSearchIndex(SearchIndex):
         lims, dist, ids = self.index.range_search(query_features, threshold, params=params)
         return dist[lims[0]:lims[1]], ids[lims[0]:lims[1]]
 
+    def set_groups(self, ids, keys):
+        """Not in the reference: keys[i] >= 0 is the group — the media id of a video, a shot, a file — of the vector id ids[i]
+        (wise_amd/index/group_search.py).  Every vector of the loaded index needs one; groups are not part of an index file, so
+        this follows load_index, and again whatever changes the index's rows."""
+        self.index.set_groups(ids, keys)
+
+    def search_grouped(self, media_type, query, topk=5, query_type='text', *, within=None):
+        """Not in the reference, which groups the top `end` rows by media_id after the search (api/routes.py:582-596) and so shows a
+        dozen results when the best thousand frames come from a dozen files: the topk best GROUPS, each with its best vector,
+        found inside the index scan.  Same prompt rules as `search`; returns (dist, ids, groups) of the first query — the score
+        and vector id of each group's best vector and the group's key, best group first.  On an inverted-file index the
+        candidates are the vectors of the probed lists.  `within`: as on `search`; a group none of whose vectors is selected
+        does not appear."""
+        if query_type != 'text':
+            raise ValueError('query_type={query_type} not implemented')
+
+        if media_type == 'audio':
+            if isinstance(query, str):
+                media_query_text = [query]
+            else:
+                media_query_text = [(self.prompt[media_type] + x) for x in query]
+        else:
+            media_query_text = [(self.prompt[media_type] + query)]
+
+        query_features = self.feature_extractor.extract_text_features(media_query_text)
+        params = None if within is None else SearchParameters(sel=as_selector(within))
+        dist, ids, groups = self.index.search_grouped(query_features, topk, params=params)
+        return dist[0], ids[0], groups[0]
+
     def search_batch(self, media_type, queries, topk=5, query_type='text', *, within=None):
         """Not in the reference: what `search` returns for every string of `queries`, from ONE text-tower batch and ONE
         batched index search per 256 of them (wise_amd/search/batch_queries.py; the --queries-from loop of search.py:894-950

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import group_search as _group
 from . import mutate as _mutate
 from . import range_search as _range
 from .selector import resolve_for, unpack_params
@@ -55,6 +56,7 @@ class RowStore:
         self.reserved: Optional[torch.Tensor] = None      # reserve(): the tensors slot() hands out slice by slice
         self.reserved_ids: Optional[torch.Tensor] = None
         self.fill = 0
+        self.version = 0                             # counts what changed the rows (slot, adopt, compact): group tables belong to one value
 
     @property
     def has_ids(self) -> bool:
@@ -77,6 +79,7 @@ class RowStore:
         ids = ids if torch.is_tensor(ids) else torch.as_tensor(np.ascontiguousarray(ids, dtype=np.int64))
         if ids.shape != (n,):
             raise ValueError(f"{what}: ids must have one entry per row")
+        self.version += 1
         if self.reserved is not None and self.fill + n <= self.reserved.shape[0]:
             a, b = self.fill, self.fill + n
             self.reserved_ids[a:b].copy_(ids)
@@ -101,6 +104,7 @@ class RowStore:
         self.chunks, self.id_chunks = [], []
         self.reserved = self.reserved_ids = None
         self.rows, self.ids, self.id_base, self.n = rows, ids, int(id_base), rows.shape[0]
+        self.version += 1
 
     def finalize(self) -> None:
         """Merge the chunks behind the rows held so far (implicit ids become explicit once rows with ids follow them); an empty
@@ -126,11 +130,12 @@ class RowStore:
         from the new end."""
         self.rows, self.ids = c.rows(self.rows), c.rows(self.ids)
         self.n = c.kept
+        self.version += 1
         if self.reserved is not None:
             self.fill = c.kept
 
 
-class FlatIndexBase:
+class FlatIndexBase(_group.GroupTables):
     REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
     metric = "ip"        # "l2" (flat_l2.py): D holds squared distances, ascending; a range hit is dist < thresh
     # entry points of the subclass's payload: (workspace bytes, count pass, fill pass) of range_search, reconstruct_batch's, and
@@ -138,6 +143,7 @@ class FlatIndexBase:
     _RANGE: Tuple[str, str, str]
     _RECONSTRUCT: str
     _TOPK: Tuple[str, str, str]
+    _GROUP_SCORES: str   # stage 1 of search_grouped (group_search.py)
 
     def _payload_args(self) -> tuple:
         """What the range and reconstruct entry points of the subclass take right behind the rows: nothing, or the device address
@@ -319,6 +325,36 @@ class FlatIndexBase:
         sel, _ = unpack_params(params, ivf=False)
         lims, D, I = self.range_search_device(_range.to_numpy(x).to(self.device), thresh, sel=sel)
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    # -- grouped search (set_groups, clear_groups, ngroups, the numpy search_grouped: group_search.GroupTables) ----------------
+    def _rows_version(self) -> int:
+        return self._store.version
+
+    def _group_operands(self, lib, qs: torch.Tensor) -> tuple:
+        """What the subclass's *_group_scores entry point takes between d and nq for the queries qs: the queries themselves, or
+        what the payload makes of them (IndexSQ8bit: W and q0)."""
+        return (qs,)
+
+    def search_grouped_device(self, q: torch.Tensor, k: int, sel=None, chunk: Optional[int] = None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64, G [nq,k] int64) on the device, no host sync: the k best
+        groups of rows, each with its best row (group_search.py).  The score is the exact scan's over the payload, never a shadow
+        copy's.  sel: only the selected rows are candidates (their bitmap is tested in the score pass).  chunk: queries per
+        workspace chunk (default: what range_search.WORKSPACE_BYTES allows).  RuntimeError before set_groups."""
+        tables = self._need_groups()
+        lib = _lib.lib()
+        self._finalize()
+        res = resolve_for(self, sel)
+        keep = None if res is None else res.bitmap
+        q = self._queries(q, "search_grouped")
+        X, n, d, st, name = self._store.rows, self._store.n, self.d, _lib.stream_ptr(), self._GROUP_SCORES
+        fn = getattr(lib, name)
+
+        def scores(qs, ord_ptr):
+            operands = self._group_operands(lib, qs)
+            _lib.check(fn(_lib.ptr(X), n, d, *(t.data_ptr() for t in operands), qs.shape[0], _lib.ptr(keep), ord_ptr, st), name)
+
+        return _group.run(q, k, tables, scores, lambda need: self._grown("_ws", need), self._store.ids, self._store.id_base,
+                          self.metric, chunk)
 
     def reconstruct_batch(self, ids) -> np.ndarray:
         """the stored rows under the given external ids as float32 (api/routes.py:1078); NaN rows for ids the index does not

@@ -49,6 +49,7 @@ class FlatIPIndex(FlatIndexBase):
     _RANGE = ("wise_ip_range_workspace_bytes", "wise_ip_range_count_f32", "wise_ip_range_fill_f32")
     _RECONSTRUCT = "wise_reconstruct_batch"
     _TOPK = ("wise_ip_topk_workspace_bytes", "wise_ip_topk_f32", "wise_ip_topk_pos_f32")
+    _GROUP_SCORES = "wise_ip_group_scores_f32"       # the exact fp32 routine: a grouped search never reads a shadow
 
     @property
     def _X(self) -> Optional[torch.Tensor]:

@@ -45,6 +45,7 @@ class FlatL2Index(FlatCodecIndex):
     _RECONSTRUCT = "wise_reconstruct_batch"          # the fp32 rows as they were added
     _TOPK = ("wise_l2_topk_workspace_bytes", "wise_l2_topk_f32", "wise_l2_topk_pos_f32")
     _BATCHED = ("wise_l2_topk_batched_workspace_bytes", "wise_l2_topk_batched")
+    _GROUP_SCORES = "wise_l2_group_scores_f32"
 
     def __init__(self, d: int, device: str = "cuda"):
         check_shape(d)

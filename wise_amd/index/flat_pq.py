@@ -180,6 +180,13 @@ class FlatPQIPIndex(PQCodebooks, FlatIndexBase):
     def range_search(self, x, thresh, params=None):
         raise NotImplementedError("IndexPQ: range_search is not built on the product-quantizer types")
 
+    def _group_refusal(self) -> None:
+        from .group_search import UNSUPPORTED
+        raise NotImplementedError(UNSUPPORTED.format("IndexPQ"))
+
+    def search_grouped_device(self, q, k, sel=None, chunk=None):
+        self._group_refusal()
+
     # -- the rest of the surface ------------------------------------------------------------------
     def _positions(self, ids) -> torch.Tensor:
         """[n] int64 on the device: the position of each external id (-1: not held)"""

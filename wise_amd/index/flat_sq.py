@@ -51,6 +51,7 @@ class FlatSQfp16IPIndex(FlatCodecIndex):
     _RECONSTRUCT = "wise_ipsq16_reconstruct"         # the halves widened to float32: float32(float16(x)) of what was added
     _TOPK = ("wise_ipsqfp16_topk_workspace_bytes", "wise_ipsq16_topk", "wise_ipsq16_topk_pos")
     _BATCHED = ("wise_ipsqfp16_topk_batched_workspace_bytes", "wise_ipsq16_topk_batched")
+    _GROUP_SCORES = "wise_ipsq16_group_scores"
 
     def __init__(self, d: int, device: str = "cuda"):
         check_shape(d)
@@ -128,6 +129,7 @@ class FlatSQfp16L2Index(FlatSQfp16IPIndex):
     _RANGE = ("wise_l2sqfp16_range_workspace_bytes", "wise_l2sq16_range_count", "wise_l2sq16_range_fill")
     _TOPK = ("wise_l2sqfp16_topk_workspace_bytes", "wise_l2sq16_topk", "wise_l2sq16_topk_pos")
     _BATCHED = ("wise_l2sqfp16_topk_batched_workspace_bytes", "wise_l2sq16_topk_batched")
+    _GROUP_SCORES = "wise_l2sq16_group_scores"
 
     def __init__(self, d: int, device: str = "cuda"):
         check_sqfp16_l2_shape(d)
@@ -183,6 +185,7 @@ class FlatSQ8IPIndex(FlatCodecIndex):
     _RECONSTRUCT = "wise_ipsq8_reconstruct"          # faiss's Codec8bit decode: vmin + ((code + 0.5) / 255) vdiff
     _TOPK = ("wise_ipsq8_topk_workspace_bytes", "wise_ipsq8_topk", "wise_ipsq8_topk_pos")
     _BATCHED = ("wise_ipsq8_topk_batched_workspace_bytes", "wise_ipsq8_topk_batched")
+    _GROUP_SCORES = "wise_ipsq8_group_scores"
 
     def __init__(self, d: int, device: str = "cuda"):
         check_sq8_shape(d)
@@ -295,6 +298,15 @@ class FlatSQ8IPIndex(FlatCodecIndex):
     def reconstruct_batch(self, ids) -> np.ndarray:
         self._need_trained("reconstruct_batch")
         return super().reconstruct_batch(ids)
+
+    def _group_operands(self, lib, qs: torch.Tensor) -> tuple:
+        """(W, q0) of wise_sq_query for the queries: what wise_ipsq8_topk makes of them in its workspace"""
+        self._need_trained("search_grouped")
+        W = torch.empty(qs.shape[0], self.d, dtype=torch.float32, device=self.device)
+        q0 = torch.empty(qs.shape[0], dtype=torch.float32, device=self.device)
+        _lib.check(lib.wise_sq_query(qs.data_ptr(), self._trained.data_ptr(), qs.shape[0], self.d, W.data_ptr(), q0.data_ptr(),
+                                     _lib.stream_ptr()), "wise_sq_query")
+        return W, q0
 
     # -- search ---------------------------------------------------------------------------------
     def _batch_operands(self):

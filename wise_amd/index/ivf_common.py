@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import group_search as _group
 from . import mutate as _mutate
 from . import range_search as _range
 from .flat_ip import FlatIPIndex
@@ -284,6 +285,7 @@ class ListStore:
         self.ids: Optional[torch.Tensor] = None
         self.list_off: Optional[torch.Tensor] = None
         self.n = 0
+        self.version = 0                                 # counts what changed the rows (append, adopt, compact): group tables belong to one value
 
     def _check_extra(self, extra: Sequence[torch.Tensor], n: int) -> tuple:
         if len(extra) != len(self._extra_gathers) or any(t.shape[0] != n for t in extra):
@@ -293,6 +295,7 @@ class ListStore:
     def append(self, payload: torch.Tensor, ids: torch.Tensor, assign: torch.Tensor, extra: Sequence[torch.Tensor] = ()) -> None:
         self._pending.append((payload, ids, assign, self._check_extra(extra, payload.shape[0])))
         self.n += payload.shape[0]
+        self.version += 1
 
     def adopt(self, data: torch.Tensor, ids: torch.Tensor, list_off: torch.Tensor, extra: Sequence[torch.Tensor] = ()) -> None:
         """Take a payload that is already grouped by list (file load); chunks not yet merged are dropped."""
@@ -302,6 +305,7 @@ class ListStore:
         self.ids = ids.to(self.device, torch.int64).contiguous()
         self.list_off = list_off.to(self.device, torch.int64).contiguous()
         self.n = self.data.shape[0]
+        self.version += 1
 
     def finalize(self, group: Callable) -> None:
         """Merge the pending chunks into the lists; `group` is the quantizer's stable grouping (CoarseQuantizer._group)."""
@@ -339,17 +343,19 @@ class ListStore:
         self.data, self.ids = c.rows(self.data), c.rows(self.ids)
         self.extra = [c.rows(t) for t in self.extra]
         self.n = c.kept
+        self.version += 1
 
     def nbytes(self) -> int:
         """Bytes of HBM the merged lists hold: payload, ids, offsets, extra arrays."""
         return sum(t.numel() * t.element_size() for t in (self.data, self.ids, self.list_off, *self.extra))
 
 
-class IVFIndexBase:
+class IVFIndexBase(_group.GroupTables):
     """One CoarseQuantizer (`_coarse`), one ListStore (`_lists`), and the surface both indexes show around them."""
 
     COARSE = CoarseQuantizer      # the class of `_coarse` (IVFFlatL2Index: L2CoarseQuantizer)
     metric = "ip"                 # 'l2': distances, ascending (IVFFlatL2Index); the sharded wrappers and range_search read it
+    GROUP_SCORES: Optional[str] = None   # stage 1 of search_grouped in the C ABI; None: the type has none (product-quantized)
 
     def __init__(self, d: int, nlist: int, device: str, width: int, dtype: torch.dtype, gather: Callable,
                  extra_gathers: Sequence[Callable] = ()):
@@ -467,6 +473,37 @@ class IVFIndexBase:
         finally:
             self.nprobe = kept
         return lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+
+    # -- grouped search: the part every inverted-file type shares (group_search.py: set_groups, clear_groups, ngroups, search_grouped)
+    def _rows_version(self) -> int:
+        return self._lists.version
+
+    def _group_refusal(self) -> None:
+        if self.GROUP_SCORES is None:
+            raise NotImplementedError(_group.UNSUPPORTED.format(type(self).__name__))
+        if getattr(self, "pos_base", 0) != 0:
+            raise NotImplementedError(_group.NO_SLICE.format(type(self).__name__, self.pos_base))
+
+    def _group_scores(self, lib, st: int, qs: torch.Tensor, probes: torch.Tensor, nprobe: int, keep: Optional[torch.Tensor], ord_ptr: int) -> None:
+        """The type's GROUP_SCORES call for the queries qs and their probes: the lists' fp32 rows take the queries as they are"""
+        ls = self._lists
+        _lib.check(getattr(lib, self.GROUP_SCORES)(ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist, qs.data_ptr(),
+                                                   qs.shape[0], probes.data_ptr(), nprobe, _lib.ptr(keep), ord_ptr, st), self.GROUP_SCORES)
+
+    def search_grouped_device(self, q: torch.Tensor, k: int, sel=None, chunk: Optional[int] = None):
+        """q [nq,d] fp32 on device -> (D [nq,k] fp32, I [nq,k] int64, G [nq,k] int64) on the device, no host sync: the k best
+        groups among the rows OF THE PROBED LISTS, each with its best row (group_search.py); nprobe and the coarse rule are
+        search's.  sel: only the selected rows are candidates.  chunk: queries per workspace chunk.  RuntimeError before set_groups."""
+        tables = self._need_groups()
+        lib = _lib.lib()
+        q = self._queries(q)
+        keep = self._keep(sel)
+        nprobe, st = self._clamped_nprobe(), _lib.stream_ptr()
+
+        def scores(qs, ord_ptr):
+            self._group_scores(lib, st, qs, self._coarse.probes_device(qs, nprobe).contiguous(), nprobe, keep, ord_ptr)
+
+        return _group.run(q, k, tables, scores, self._workspace, self._lists.ids, 0, self.metric, chunk)
 
     REMOVE_SCRATCH_BYTES = _mutate.SCRATCH_BYTES
 

@@ -45,6 +45,8 @@ def reference_nlist(feature_count: int) -> int:
 
 
 class IVFFlatIPIndex(IVFIndexBase):
+    GROUP_SCORES = "wise_ivf_group_scores_f32"
+
     def __init__(self, d: int, nlist: int, device: str = "cuda"):
         super().__init__(d, nlist, device, width=int(d), dtype=torch.float32, gather=CoarseQuantizer._gather_rows)
 
@@ -168,6 +170,7 @@ class IVFFlatL2Index(IVFFlatIPIndex):
     rank's slice of the list-major rows: list_off clipped to the slice and `pos_base`, the position of its first row."""
     COARSE = L2CoarseQuantizer
     metric = "l2"
+    GROUP_SCORES = "wise_ivfl2_group_scores"
 
     def __init__(self, d: int, nlist: int, device: str = "cuda"):
         check_l2_shape(int(d))

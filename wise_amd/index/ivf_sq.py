@@ -67,6 +67,7 @@ class IVFSQIPIndex(CodedIVFIndexBase):
     SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq_scan", "wise_ivfsq_scan_sel", "wise_ivfsq_scan_local"
     WORKSPACE, WORKSPACE_LOCAL = "wise_ivfsq_scan_workspace_bytes", "wise_ivfsq_scan_local_workspace_bytes"
     RANGE_COUNT, RANGE_FILL = "wise_ivfsq_range_count", "wise_ivfsq_range_fill"
+    GROUP_SCORES = "wise_ivfsq_group_scores"
 
     def __init__(self, d: int, nlist: int, device: str = "cuda"):
         check_sq_shape(int(d))
@@ -141,6 +142,15 @@ class IVFSQIPIndex(CodedIVFIndexBase):
                                                      ws.numel(), st), self.RANGE_FILL)
         return count, fill
 
+    def _group_scores(self, lib, st, qs, probes, nprobe, keep, ord_ptr) -> None:
+        """bias and operands as _scan computes them, then the GROUP_SCORES call over the same probes"""
+        ls = self._lists
+        bias = self._bias(lib, st, qs, probes, nprobe)
+        weights = self._operands(lib, st, qs)
+        _lib.check(getattr(lib, self.GROUP_SCORES)(ls.data.data_ptr(), ls.n, self.d, ls.list_off.data_ptr(), self.nlist,
+                                                   *(t.data_ptr() for t in weights), qs.shape[0], probes.data_ptr(), bias.data_ptr(), nprobe,
+                                                   _lib.ptr(keep), ord_ptr, st), self.GROUP_SCORES)
+
     # -- the rest of the surface the REST layer touches -------------------------------------------
     def reconstruct_batch(self, ids) -> np.ndarray:
         """Decoded rows (approximate, as faiss's): centroid of the row's list + the bin centres; NaN for an unknown id."""
@@ -173,6 +183,7 @@ class IVFSQfp16IPIndex(IVFSQIPIndex):
     PAYLOAD_DTYPE = torch.float16
     SCAN, SCAN_SEL, SCAN_LOCAL = "wise_ivfsq16_scan", "wise_ivfsq16_scan_sel", "wise_ivfsq16_scan_local"
     RANGE_COUNT, RANGE_FILL = "wise_ivfsq16_range_count", "wise_ivfsq16_range_fill"
+    GROUP_SCORES = "wise_ivfsq16_group_scores"
 
     @property
     def is_trained(self) -> bool:

@@ -162,6 +162,13 @@ class ShardedFlatIPIndex:
 
     range_search_device = range_search
 
+    def search_grouped(self, *args, **kwargs):
+        """Not built: a group's rows may lie on several ranks and nothing exchanges per-group representatives."""
+        from .group_search import NO_SHARDED as NO_SHARDED_GROUPS
+        raise NotImplementedError(NO_SHARDED_GROUPS)
+
+    search_grouped_device = set_groups = search_grouped
+
     def remove_ids(self, sel, scratch_bytes=None) -> int:
         """Not built: every rank would have to compact its slice and the ranks agree on the new row ranges."""
         raise NotImplementedError(NO_COLLECTIVE_REMOVAL)
