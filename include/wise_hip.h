@@ -51,7 +51,9 @@ const char* wise_last_error(void);
  * three workspace functions) with wise_l2_half_norms, wise_ivf_l2_coarse and wise_ivf_list_means, IndexIVFFlatL2; and wise_pqflat_topk, wise_pqflat_topk_pos (with
  * wise_pqflat_topk_workspace_bytes) and wise_pqflat_decode, IndexPQ<m>; and the wise_l2sq16_* entry points (wise_l2sq16_topk, _topk_pos,
  * _range_count / _fill, _prepare, _topk_batched and their three workspace functions), IndexSQfp16L2; and the nine *_group_scores
- * entry points with wise_group_best, wise_group_topk and wise_group_workspace_bytes, search_grouped.  The version is 5. */
+ * entry points with wise_group_best, wise_group_topk and wise_group_workspace_bytes, search_grouped; and wise_sel_bitmap_groups
+ * (with wise_sel_groups_workspace_bytes), wise_sel_bitmap_idbits and wise_sel_combine, the group selector, faiss's IDSelectorBitmap
+ * and the And / Or / XOr / Not trees of selectors.  The version is 5. */
 int wise_abi_version(void);
 /* Host-side hint for the GEMM tile heuristic (no device work), local to the CALLING THREAD: on != 0 while this thread
  * enqueues batches that will run beside another stream's (two batches in flight); tilings that measured slower there
@@ -1232,6 +1234,36 @@ int wise_group_best(const uint32_t* ord, int64_t N, int nq, const int64_t* group
 int wise_group_topk(const uint64_t* best, int64_t G, int nq, int k, const int32_t* gid, int64_t N, const int64_t* group_keys,
                     const int64_t* ids, int64_t id_base, int flip, float* outD, int64_t* outI, int64_t* outG, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* (ABI 5) Selectors over GROUPS and trees of selectors (csrc/sel_tree.hip; wise_amd/index/selector.py: IDSelectorGroups,
+ * IDSelectorBitmap, IDSelectorAnd / Or / XOr, IDSelectorNot over anything).  Every entry writes or combines bitmaps of the layout and
+ * with the guarantees of wise_sel_bitmap: (N + 31) / 32 uint32 words, ALL written, bit (p & 31) of word p >> 5, and the bits past N
+ * are zero, also when inverted — what the *_scan_sel, *_topk_pos (through wise_sel_positions), *_range_count, *_group_scores and
+ * wise_compact_* entry points take.  One lane per row, a wave's 64 answers are one ballot written by one lane as two words; no
+ * atomics, the same bits on every run; nothing allocates or reads back, so every call can be captured into a graph.
+ * Limits: 0 <= N < 2^32 - 1 (N = 0: nothing is launched and no pointer is looked at), 0 <= G <= 2^31 - 1 (gid is int32), n_sel >= 0,
+ * n_bytes >= 0, op in 0 .. 4.  Anything else — also a null pointer where rows exist (gid, bitmap, a, out; group_keys where G > 0;
+ * sel_keys where n_sel > 0; bits where n_bytes > 0; b where op != 4), or, where N > 0, a workspace that is null or shorter than
+ * wise_sel_groups_workspace_bytes(G) — is WISE_E_INVALID with a wise_last_error text, and nothing is written.  The checks need no
+ * device.
+ *   wise_sel_bitmap_groups: bit p = 1 iff 0 <= gid[p] < G and group_keys[gid[p]] occurs in sel_keys.  gid [N] int32 and group_keys
+ *     [G] int64 ascending are the group tables of set_groups (wise_group_topk reads the same two); sel_keys [n_sel] int64 sorted
+ *     ascending without duplicates.  n_sel = 0 selects nothing, and so does a key no group carries; invert != 0 complements the
+ *     answer within the index; G = 0 is legal (no row has a group: all zero, or all N bits set when inverted).  Two launches: a
+ *     MARK pass, one lane per group, a binary search of its key in sel_keys, G bits into the workspace; a ROW pass, one lane per
+ *     row, which reads gid[p] and tests that group's mark bit.  The device reads 4 N bytes and writes N / 8.
+ *     wise_sel_groups_workspace_bytes(G): the mark bits, a multiple of 256 bytes and never 0 for a legal G; 0 for G out of range.
+ *   wise_sel_bitmap_idbits: faiss's IDSelectorBitmap.  The external id i of row p is ids[p], or id_base + p with ids == NULL; i is
+ *     selected iff i >= 0, (i >> 3) < n_bytes and (bits[i >> 3] >> (i & 7)) & 1.  n_bytes = 0 selects nothing; invert as above.
+ *   wise_sel_combine: word by word over two bitmaps of N positions, op 0: a AND b, 1: a OR b, 2: a XOR b, 3: a AND NOT b, 4: NOT a
+ *     (b is ignored and may be NULL).  out may be a or b (any other overlap is undefined).  The tail bits of out are zero for
+ *     every op, whatever the tails of a and b hold.  Words go four at a time where a, b and out are 16-byte aligned. */
+size_t wise_sel_groups_workspace_bytes(int64_t G);
+int wise_sel_bitmap_groups(const int32_t* gid, int64_t N, const int64_t* group_keys, int64_t G, const int64_t* sel_keys, int64_t n_sel,
+                           int invert, uint32_t* bitmap, void* workspace, size_t workspace_bytes, void* stream);
+int wise_sel_bitmap_idbits(const int64_t* ids, int64_t id_base, int64_t N, const uint8_t* bits, int64_t n_bytes, int invert,
+                           uint32_t* bitmap, void* stream);
+int wise_sel_combine(const uint32_t* a, const uint32_t* b, int64_t N, int op, uint32_t* out, void* stream);
 
 #ifdef __cplusplus
 }

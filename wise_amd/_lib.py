@@ -218,6 +218,10 @@ SIGNATURES = {
     "wise_ivfl2_group_scores": (_i, [_vp, _i64, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "wise_group_best": (_i, [_vp, _i64, _i, _vp, _vp, _i64, _vp, _vp]),
     "wise_group_topk": (_i, [_vp, _i64, _i, _i, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "wise_sel_groups_workspace_bytes": (_sz, [_i64]),
+    "wise_sel_bitmap_groups": (_i, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _vp, _vp, _sz, _vp]),
+    "wise_sel_bitmap_idbits": (_i, [_vp, _i64, _i64, _vp, _i64, _i, _vp, _vp]),
+    "wise_sel_combine": (_i, [_vp, _vp, _i64, _i, _vp, _vp]),
     "wise_l2_half_norms": (_i, [_vp, _i64, _i, _vp, _vp]),
     "wise_ivf_l2_coarse": (_i, [_vp, _vp, _i, _i, _vp]),
     "wise_ivf_list_means": (_i, [_vp, _vp, _i, _i, _vp, _vp]),

@@ -121,7 +121,7 @@ from .ivf_pq import (IVFOPQIPIndex, IVFOPQRefineIPIndex, IVFPQIPIndex, IVFPQRefi
 from .ivf_sq import IVFSQfp16IPIndex, IVFSQIPIndex, check_sq_shape
 from .mutate import plan_update
 from .search_index import SearchIndex
-from .selector import SearchParameters, as_selector
+from .selector import IDSelectorGroups, SearchParameters, within_selector
 from .sharded import (ShardedFlatIPIndex, ShardedIVFFlatIPIndex, ShardedIVFPQIPIndex, ShardedIVFPQRefineIPIndex,
                       ShardedIVFSQfp16IPIndex, ShardedIVFSQIPIndex, shard_range)
 
@@ -776,6 +776,48 @@ class FeatureSearchIndex(SearchIndex):
         print(f'{index_type} for {self.media_type}: added {n_added}, removed {n_removed} vectors')
         return n_added, n_removed
 
+    def remove_groups(self, index_type, keys):
+        """Not in the reference: "delete these videos" — remove from the EXISTING index file of `index_type` every vector whose
+        group key (set_groups: the media id) is in `keys`; the caller passes keys, not vector ids.  Groups are not
+        part of an index file, so this NEEDS THE GROUPS SET ON THE LOADED INDEX: load_index(index_type) and set_groups(ids, keys)
+        come first (RuntimeError otherwise), and the loaded index must hold the file's vectors (ValueError from set_groups where
+        the file holds an id the loaded index has no group for).  Like update_index it works on its own copy of the file — the
+        file is loaded, the copy is given the loaded index's groups, its rows go by remove_ids(IDSelectorGroups(keys)), an in-place
+        compaction on the GPU, and the file is written to a temporary name beside it and renamed over it — so a `self.index` is
+        stale afterwards: call load_index and set_groups again.  COST: because the file holds no groups, every call copies the loaded
+        index's ids and per-row keys to the host and builds the copy's group tables there (set_groups: a sort over all N rows) before
+        the device-side selector runs — O(N) host work a call, beside reading and writing the file; only the selection of the rows
+        is on the device.  Returns the number of vectors removed; with none the file is left
+        alone.  The types that take no groups (product-quantized) raise NotImplementedError, as does a sharded process group."""
+        if index_type not in FLAT_TYPES and _family(index_type) is None and parse_pq_flat_type(index_type) is None:
+            raise _unknown_index_type(index_type)
+        if _dist_rank_world()[2]:
+            raise NotImplementedError('remove_groups under a sharded process group is not built (a collective removal is not): '
+                                      'update the single file in one process and shard it again')
+        if not self.is_index_loaded():
+            raise RuntimeError('remove_groups: load_index and set_groups first (groups are not part of an index file)')
+        index_fn = self.get_index_filename(index_type)
+        if not index_fn.exists():
+            raise FileNotFoundError(f'index {index_fn} does not exist; use create_index (the create-index.py script) first')
+        tables = self.index._need_groups()               # the type's refusal; RuntimeError without groups for the present rows
+        row_ids, id_base, n = self.index._selector_rows()
+        ids = np.arange(n, dtype=np.int64) + int(id_base) if row_ids is None else row_ids.cpu().numpy()
+        keys_of_rows = tables['keys'][tables['gid'].long()].cpu().numpy()
+        sel = IDSelectorGroups(keys)                     # non-integer keys are refused before the file is read
+        index = self._index_from_file(index_fn)
+        index.set_groups(ids, keys_of_rows)
+        n_removed = index.remove_ids(sel)
+        if n_removed:
+            tmp_fn = index_fn.with_name(index_fn.name + '.tmp-%d' % os.getpid())
+            try:
+                self._write_index_file(index, tmp_fn)
+                os.replace(tmp_fn, index_fn)
+            finally:
+                if tmp_fn.exists():
+                    tmp_fn.unlink()
+        print(f'{index_type} for {self.media_type}: removed {n_removed} vectors of {np.unique(sel.keys).size} groups')
+        return n_removed
+
     def is_index_loaded(self):
         return hasattr(self, 'index')
 
@@ -810,10 +852,13 @@ class FeatureSearchIndex(SearchIndex):
         self.feature_extractor = FeatureExtractorFactory(self.feature_extractor_id)
         return True
 
-    def search(self, media_type, query, topk=5, query_type='text', *, within=None):
+    def search(self, media_type, query, topk=5, query_type='text', *, within=None, within_groups=None):
         """`within` (not in the reference): an IDSelector (wise_amd/index/selector.py) or an array-like of vector ids — the
         topk best among THOSE vectors, filtered inside the index scan (the reference intersects after the top-k, search.py's
-        `in` / `not_in` merges, and so returns fewer than topk).  None: the reference's call, unchanged."""
+        `in` / `not_in` merges, and so returns fewer than topk).  `within_groups` (not in the reference): an array-like of group
+        keys (set_groups: media ids) — the topk best among the vectors of THOSE groups, an IDSelectorGroups resolved on the device
+        from the keys alone; with `within` as well, the vectors both select (IDSelectorAnd).  Neither: the reference's call,
+        unchanged."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
 
@@ -826,17 +871,18 @@ class FeatureSearchIndex(SearchIndex):
             media_query_text = [(self.prompt[media_type] + query)]
 
         query_features = self.feature_extractor.extract_text_features(media_query_text)
-        if within is None:
+        sel = within_selector(within, within_groups)
+        if sel is None:
             dist, ids = self.index.search(query_features, topk)
         else:
-            dist, ids = self.index.search(query_features, topk, params=SearchParameters(sel=as_selector(within)))
+            dist, ids = self.index.search(query_features, topk, params=SearchParameters(sel=sel))
         return dist[0], ids[0]
 
-    def search_range(self, media_type, query, threshold, query_type='text', *, within=None):
+    def search_range(self, media_type, query, threshold, query_type='text', *, within=None, within_groups=None):
         """Not in the reference: EVERY vector that scores above `threshold` for the query (faiss's range_search: score > threshold,
         strictly) instead of the topk best — exhaustive retrieval, near-duplicate sweeps, full positive sets.  Same prompt rules
         as `search`; returns (dist, ids) of the first query, by descending score.  On an inverted-file index the hits come from
-        the probed lists.  `within`: as on `search`."""
+        the probed lists.  `within`, `within_groups`: as on `search`."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
 
@@ -849,7 +895,8 @@ class FeatureSearchIndex(SearchIndex):
             media_query_text = [(self.prompt[media_type] + query)]
 
         query_features = self.feature_extractor.extract_text_features(media_query_text)
-        params = None if within is None else SearchParameters(sel=as_selector(within))
+        sel = within_selector(within, within_groups)
+        params = None if sel is None else SearchParameters(sel=sel)
         lims, dist, ids = self.index.range_search(query_features, threshold, params=params)
         return dist[lims[0]:lims[1]], ids[lims[0]:lims[1]]
 
@@ -859,13 +906,13 @@ class FeatureSearchIndex(SearchIndex):
         this follows load_index, and again whatever changes the index's rows."""
         self.index.set_groups(ids, keys)
 
-    def search_grouped(self, media_type, query, topk=5, query_type='text', *, within=None):
+    def search_grouped(self, media_type, query, topk=5, query_type='text', *, within=None, within_groups=None):
         """Not in the reference, which groups the top `end` rows by media_id after the search (api/routes.py:582-596) and so shows a
         dozen results when the best thousand frames come from a dozen files: the topk best GROUPS, each with its best vector,
         found inside the index scan.  Same prompt rules as `search`; returns (dist, ids, groups) of the first query — the score
         and vector id of each group's best vector and the group's key, best group first.  On an inverted-file index the
-        candidates are the vectors of the probed lists.  `within`: as on `search`; a group none of whose vectors is selected
-        does not appear."""
+        candidates are the vectors of the probed lists.  `within`, `within_groups`: as on `search`; a group none of whose vectors
+        is selected does not appear."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
 
@@ -878,15 +925,16 @@ class FeatureSearchIndex(SearchIndex):
             media_query_text = [(self.prompt[media_type] + query)]
 
         query_features = self.feature_extractor.extract_text_features(media_query_text)
-        params = None if within is None else SearchParameters(sel=as_selector(within))
+        sel = within_selector(within, within_groups)
+        params = None if sel is None else SearchParameters(sel=sel)
         dist, ids, groups = self.index.search_grouped(query_features, topk, params=params)
         return dist[0], ids[0], groups[0]
 
-    def search_batch(self, media_type, queries, topk=5, query_type='text', *, within=None):
+    def search_batch(self, media_type, queries, topk=5, query_type='text', *, within=None, within_groups=None):
         """Not in the reference: what `search` returns for every string of `queries`, from ONE text-tower batch and ONE
         batched index search per 256 of them (wise_amd/search/batch_queries.py; the --queries-from loop of search.py:894-950
-        calls `search` row by row).  `within`: as on `search`, one selector for all queries."""
+        calls `search` row by row).  `within`, `within_groups`: as on `search`, one selector for all queries."""
         if query_type != 'text':
             raise ValueError('query_type={query_type} not implemented')
         from ..search.batch_queries import batched_text_search
-        return batched_text_search(self, media_type, queries, topk, within=within)
+        return batched_text_search(self, media_type, queries, topk, within=within_selector(within, within_groups))

@@ -5,7 +5,21 @@
 
   IDSelectorBatch(ids)         the rows whose external id occurs in `ids` (duplicates allowed; ids no row carries select nothing)
   IDSelectorRange(imin, imax)  the rows with imin <= id < imax
-  IDSelectorNot(sel)           the complement within the index
+  IDSelectorNot(sel)           the complement within the index, of any selector
+  IDSelectorAll()              every row
+  IDSelectorArray(ids)         IDSelectorBatch under faiss's other name
+  IDSelectorBitmap(bits)       the ids whose bit is set in a uint8 array: bit (i & 7) of bits[i >> 3]
+  IDSelectorGroups(keys)       the rows whose GROUP key (set_groups: a video's media id) occurs in `keys`; not in faiss
+  IDSelectorAnd(lhs, rhs), IDSelectorOr, IDSelectorXOr      trees of the above
+
+    index.search(q, k, params=SearchParameters(sel=IDSelectorAnd(IDSelectorGroups(media_ids), IDSelectorNot(IDSelectorBatch(seen)))))
+    index.remove_ids(IDSelectorGroups([media_id]))            # "delete a video"
+
+Resolution is a recursion over the tree (csrc/sel_tree.hip).  A leaf is one launch — two for a group selector, whose keys are first
+marked group by group and then looked up row by row through the group tables, so that "inside these 5,000 videos" ships 5,000 keys
+and not the millions of vector ids they stand for —, a Not over a leaf folds into the leaf's `invert`, and a node of two children
+is one word-by-word pass over their bitmaps.  Every node keeps its own result per index, so a subtree shared by two filters is
+resolved once.  Nothing on the way uses an atomic: a tree resolves to the same bits on every run.
 
 A selector says which EXTERNAL ids may be returned; an index turns it into a bitmap over its own row POSITIONS (rows of
 FlatIPIndex._X, rows in list order of a ListStore) — uint32[ceil(N / 32)] on the device, bit (p & 31) of word p >> 5 — that its
@@ -49,8 +63,50 @@ class ResolvedSelector:
         return self._positions
 
 
+def _leaf_bitmap(ids, id_base: int, n: int, spec, device) -> torch.Tensor:
+    """One wise_sel_bitmap launch: the bitmap of a `_spec` over the rows (ids, id_base, n)."""
+    mode, sorted_ids, imin, imax, invert = spec
+    bitmap = torch.empty((n + 31) // 32, dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().wise_sel_bitmap(_lib.ptr(ids), int(id_base), n, mode, _lib.ptr(sorted_ids),
+                                          0 if sorted_ids is None else sorted_ids.numel(), imin, imax, int(invert), bitmap.data_ptr(),
+                                          _lib.stream_ptr()), "wise_sel_bitmap")
+    return bitmap
+
+
+def _groups_bitmap(tables: dict, n: int, sel_keys: torch.Tensor, invert: bool, device) -> torch.Tensor:
+    """wise_sel_bitmap_groups: the rows whose group key occurs in sel_keys (sorted, unique, on the device), from an index's group
+    tables (group_search.GroupTables); two launches, the mark bits of the groups in a workspace of G / 8 bytes."""
+    lib = _lib.lib()
+    G = int(tables["keys"].numel())
+    bitmap = torch.empty((n + 31) // 32, dtype=torch.int32, device=device)
+    ws = torch.empty(max(int(lib.wise_sel_groups_workspace_bytes(G)), 1), dtype=torch.uint8, device=device)
+    _lib.check(lib.wise_sel_bitmap_groups(tables["gid"].data_ptr(), n, tables["keys"].data_ptr(), G, sel_keys.data_ptr(), sel_keys.numel(),
+                                          int(invert), bitmap.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr()),
+               "wise_sel_bitmap_groups")
+    return bitmap
+
+
+def _idbits_bitmap(ids, id_base: int, n: int, bits: torch.Tensor, invert: bool, device) -> torch.Tensor:
+    """wise_sel_bitmap_idbits: the rows whose external id has its bit set in `bits` (uint8 on the device, faiss's bit order)."""
+    bitmap = torch.empty((n + 31) // 32, dtype=torch.int32, device=device)
+    _lib.check(_lib.lib().wise_sel_bitmap_idbits(_lib.ptr(ids), int(id_base), n, bits.data_ptr(), bits.numel(), int(invert),
+                                                 bitmap.data_ptr(), _lib.stream_ptr()), "wise_sel_bitmap_idbits")
+    return bitmap
+
+
+OP_AND, OP_OR, OP_XOR, OP_ANDNOT, OP_NOT = range(5)   # wise_sel_combine's `op`
+
+
+def _combine(a: torch.Tensor, b: Optional[torch.Tensor], n: int, op: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """wise_sel_combine over two bitmaps of n positions into `out` (a new one by default; a or b may be given): one launch."""
+    if out is None:
+        out = torch.empty_like(a)
+    _lib.check(_lib.lib().wise_sel_combine(a.data_ptr(), _lib.ptr(b), n, op, out.data_ptr(), _lib.stream_ptr()), "wise_sel_combine")
+    return out
+
+
 class IDSelector:
-    """Base of the three selectors.  `resolve(index)` is what the index classes call."""
+    """Base of the selectors.  `resolve(index)` is what the index classes call; a class says how its bitmap is made in `_bitmap`."""
 
     def __init__(self):
         self._resolved = weakref.WeakKeyDictionary()      # index -> ResolvedSelector
@@ -59,34 +115,49 @@ class IDSelector:
         """(mode, sorted unique ids on `device` or None, imin, imax, invert) — wise_sel_bitmap's arguments"""
         raise NotImplementedError
 
+    def _uses_groups(self) -> bool:
+        """does the tree under this selector hold an IDSelectorGroups (its bitmap then belongs to one state of the group tables)"""
+        return False
+
+    def _bitmap(self, index, rows, invert: bool) -> torch.Tensor:
+        """A NEW bitmap (int32 words on the device) of this selector, complemented within the index where `invert`, over
+        rows = index._selector_rows().  Here: the single wise_sel_bitmap launch of a selector that has a `_spec`."""
+        ids, id_base, n = rows
+        mode, sorted_ids, imin, imax, inv = self._spec(index.device)
+        return _leaf_bitmap(ids, id_base, n, (mode, sorted_ids, imin, imax, bool(inv) != bool(invert)), index.device)
+
     def resolve(self, index) -> ResolvedSelector:
         """The bitmap of this selector over the rows of `index` (anything with `_selector_rows()`: the merged external ids on the
-        device or None, id_base, row count), cached until the index's row count changes or rows are removed."""
-        ids, id_base, n = index._selector_rows()
+        device or None, id_base, row count), cached until the index's row count changes or rows are removed — and, for a tree with
+        a group selector in it, until the index's `_rows_version()` moves: group tables of another state are never used."""
+        uses_groups = self._uses_groups()
+        if uses_groups:                                    # refused before anything else is asked of the index or launched
+            IDSelectorGroups._tables(index)
+        rows = index._selector_rows()
+        ids, id_base, n = rows
         hit = self._resolved.get(index)
         gen = getattr(index, "_mutations", 0)              # remove_ids moves rows under an unchanged array: resolve again
-        if hit is not None and hit.n == n and hit.ids_ptr == _lib.ptr(ids) and hit.gen == gen:
+        version = index._rows_version() if uses_groups else None
+        if hit is not None and hit.n == n and hit.ids_ptr == _lib.ptr(ids) and hit.gen == gen and hit.version == version:
             return hit
-        lib = _lib.lib()
-        device = index.device
-        mode, sorted_ids, imin, imax, invert = self._spec(device)
-        bitmap = torch.empty((n + 31) // 32, dtype=torch.int32, device=device)
-        _lib.check(lib.wise_sel_bitmap(_lib.ptr(ids), int(id_base), n, mode, _lib.ptr(sorted_ids),
-                                       0 if sorted_ids is None else sorted_ids.numel(), imin, imax, int(invert), bitmap.data_ptr(),
-                                       _lib.stream_ptr()), "wise_sel_bitmap")
-        res = ResolvedSelector(bitmap, n)
-        res.ids_ptr, res.gen = _lib.ptr(ids), gen
+        res = ResolvedSelector(self._bitmap(index, rows, False), n)
+        res.ids_ptr, res.gen, res.version = _lib.ptr(ids), gen, version
         self._resolved[index] = res
         return res
+
+
+def _integers(name: str, values) -> np.ndarray:
+    """[n] int64 of an array-like (or tensor) of integers; ValueError for any other dtype"""
+    a = np.asarray(values.cpu() if torch.is_tensor(values) else values)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must be integers, got {a.dtype}")
+    return np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
 
 
 class IDSelectorBatch(IDSelector):
     def __init__(self, ids):
         super().__init__()
-        a = np.asarray(ids.cpu() if torch.is_tensor(ids) else ids)
-        if a.size and not np.issubdtype(a.dtype, np.integer):
-            raise ValueError(f"IDSelectorBatch: ids must be integers, got {a.dtype}")
-        self.ids = np.ascontiguousarray(a, dtype=np.int64).reshape(-1)
+        self.ids = _integers(f"{type(self).__name__}: ids", ids)
         self._sorted = {}                                  # device -> sorted, de-duplicated ids
 
     def _spec(self, device):
@@ -95,6 +166,10 @@ class IDSelectorBatch(IDSelector):
             t = torch.from_numpy(self.ids).to(device)
             self._sorted[key] = torch.unique_consecutive(torch.sort(t).values).contiguous()
         return MODE_BATCH, self._sorted[key], 0, 0, False
+
+
+class IDSelectorArray(IDSelectorBatch):
+    """faiss's IDSelectorArray: the same rows as IDSelectorBatch(ids)"""
 
 
 class IDSelectorRange(IDSelector):
@@ -109,16 +184,127 @@ class IDSelectorRange(IDSelector):
         return MODE_RANGE, None, self.imin, self.imax, False
 
 
+class IDSelectorAll(IDSelector):
+    """faiss's IDSelectorAll: every row (the complement of an empty id list: one wise_sel_bitmap launch, whatever the ids)"""
+
+    def _spec(self, device):
+        return MODE_BATCH, None, 0, 0, True
+
+
 class IDSelectorNot(IDSelector):
+    """The complement within the index of any selector.  Over a leaf it folds into that leaf's `invert` (no launch of its own);
+    over a compound selector it is one wise_sel_combine pass."""
+
     def __init__(self, sel: IDSelector):
         super().__init__()
         if not isinstance(sel, IDSelector):
             raise ValueError(f"IDSelectorNot: expected an IDSelector, got {type(sel).__name__}")
         self.sel = sel
+        self._groups_below = sel._uses_groups()           # once: a selector's children do not change
 
     def _spec(self, device):
         mode, sorted_ids, imin, imax, invert = self.sel._spec(device)
         return mode, sorted_ids, imin, imax, not invert
+
+    def _uses_groups(self) -> bool:
+        return self._groups_below
+
+    def _bitmap(self, index, rows, invert: bool) -> torch.Tensor:
+        return self.sel._bitmap(index, rows, not invert)
+
+
+class IDSelectorBitmap(IDSelector):
+    """faiss's IDSelectorBitmap: id i is selected iff i >= 0, i >> 3 < len(bits) and bit (i & 7) of bits[i >> 3] is set."""
+
+    def __init__(self, bits):
+        super().__init__()
+        a = np.asarray(bits.cpu() if torch.is_tensor(bits) else bits)
+        if a.dtype != np.uint8:
+            raise ValueError(f"IDSelectorBitmap: bits must be a uint8 array, got {a.dtype}")
+        self.bits = np.ascontiguousarray(a).reshape(-1)
+        self._on = {}                                      # device -> the bits there
+
+    def _bitmap(self, index, rows, invert: bool) -> torch.Tensor:
+        ids, id_base, n = rows
+        key = str(index.device)
+        if key not in self._on:
+            self._on[key] = torch.from_numpy(self.bits).to(index.device)
+        return _idbits_bitmap(ids, id_base, n, self._on[key], invert, index.device)
+
+
+class IDSelectorGroups(IDSelector):
+    """The rows whose GROUP key (set_groups: the media id of a video, a shot, a file) occurs in `keys` — duplicates allowed, keys
+    no group carries select nothing.  Resolved on the device against the index's group tables (csrc/sel_tree.hip): the keys travel,
+    not the rows' ids.  RuntimeError on an index without tables for its present rows (as search_grouped), NotImplementedError on the
+    types that take no groups (the product-quantized types, the Sharded* wrappers, a slice of a sharded index)."""
+
+    def __init__(self, keys):
+        super().__init__()
+        self.keys = _integers("IDSelectorGroups: keys", keys)
+        self._sorted = {}                                  # device -> sorted, de-duplicated keys
+
+    def _uses_groups(self) -> bool:
+        return True
+
+    @staticmethod
+    def _tables(index) -> dict:
+        """the group tables of the index's present rows: the type's refusal of set_groups, or RuntimeError where it holds none"""
+        need = getattr(index, "_need_groups", None)
+        if need is None:                                   # a Sharded* wrapper
+            from .group_search import NO_SHARDED
+            raise NotImplementedError(NO_SHARDED)
+        return need()
+
+    def _bitmap(self, index, rows, invert: bool) -> torch.Tensor:
+        tables = self._tables(index)
+        n = rows[2]
+        if int(tables["n"]) != n:
+            raise RuntimeError(f"IDSelectorGroups: the group tables cover {int(tables['n'])} rows, the index holds {n}")
+        key = str(index.device)
+        if key not in self._sorted:                        # sorted on the host: what travels is every key once
+            self._sorted[key] = torch.from_numpy(np.unique(self.keys)).to(index.device)
+        return _groups_bitmap(tables, n, self._sorted[key], invert, index.device)
+
+
+class _IDSelectorPair(IDSelector):
+    """A node of two selectors: each child is resolved (and cached) on its own, then one wise_sel_combine pass joins the two
+    bitmaps into a new one; a complement asked of the node is one more pass over that."""
+    OP = None
+
+    def __init__(self, lhs: IDSelector, rhs: IDSelector):
+        super().__init__()
+        for s in (lhs, rhs):
+            if not isinstance(s, IDSelector):
+                raise ValueError(f"{type(self).__name__}: expected two IDSelectors, got {type(s).__name__}")
+        self.lhs, self.rhs = lhs, rhs
+        self._groups_below = lhs._uses_groups() or rhs._uses_groups()          # once: a selector's children do not change
+
+    def _uses_groups(self) -> bool:
+        return self._groups_below
+
+    def _bitmap(self, index, rows, invert: bool) -> torch.Tensor:
+        n = rows[2]
+        a = self.lhs.resolve(index).bitmap
+        if self.OP == OP_AND and isinstance(self.rhs, IDSelectorNot):          # a AND NOT b: b as it is, the complement in the pass
+            out = _combine(a, self.rhs.sel.resolve(index).bitmap, n, OP_ANDNOT)
+        else:
+            out = _combine(a, self.rhs.resolve(index).bitmap, n, self.OP)
+        return _combine(out, None, n, OP_NOT, out=out) if invert else out
+
+
+class IDSelectorAnd(_IDSelectorPair):
+    """faiss's IDSelectorAnd: the rows both selectors select"""
+    OP = OP_AND
+
+
+class IDSelectorOr(_IDSelectorPair):
+    """faiss's IDSelectorOr: the rows either selector selects"""
+    OP = OP_OR
+
+
+class IDSelectorXOr(_IDSelectorPair):
+    """faiss's IDSelectorXOr: the rows exactly one of the two selects"""
+    OP = OP_XOR
 
 
 class SearchParameters:
@@ -170,3 +356,13 @@ def resolve_for(index, sel) -> Optional[ResolvedSelector]:
 def as_selector(within):
     """FeatureSearchIndex's `within`: a selector as it is, an array-like of vector ids as an IDSelectorBatch."""
     return within if isinstance(within, (IDSelector, ResolvedSelector)) else IDSelectorBatch(within)
+
+
+def within_selector(within=None, within_groups=None):
+    """FeatureSearchIndex's `within` and `within_groups` as one selector: None for neither, `as_selector(within)`,
+    IDSelectorGroups(within_groups) — an array-like of group keys —, or the IDSelectorAnd of the two (a `within` already resolved
+    against an index cannot be joined: ValueError)."""
+    if within_groups is None:
+        return None if within is None else as_selector(within)
+    groups = IDSelectorGroups(within_groups)
+    return groups if within is None else IDSelectorAnd(as_selector(within), groups)
